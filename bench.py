@@ -9,9 +9,12 @@ run through the mxfusion_amd API (Model / SVGPRegression / GradBasedInference) -
 At --gpus N>1 (one process per GPU, torch.distributed 'nccl' == RCCL) the S samples are sharded S/N per rank and
 the flat gradient is summed with ONE all-reduce per step (strong scaling: the total work is fixed).
 
-Prints ONE JSON line (rank 0).  `roofline` is the RBF Gram build at N=65536, Q=8 (HBM-write bound, the kernel
-BASELINE.json's target names); `roofline_mfma` is the dominant MFMA kernel of the step; `cpu_baseline` is the oracle
-(CPU restatement of the reference's op sequence, fwd+bwd+Adam) timed on this box's host cores on a bounded sample.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and reports them (`value`, `ms_per_step`);
+--dump-outputs DIR also writes the last timed step's outputs.  Everything else is measured with --full only: `roofline` is the
+RBF Gram build at N=65536, Q=8 (HBM-write bound, the kernel BASELINE.json's target names); `roofline_mfma` is the dominant MFMA
+kernel of the step; `cpu_baseline` is the oracle (CPU restatement of the reference's op sequence, fwd+bwd+Adam) timed on this
+box's host cores on a bounded sample; further the in-step kernel breakdown, the trained-like and whitened steps, one rank's share
+of an 8-GPU run, the other precision and the f32-vs-f64 ELBO agreement.
 """
 import argparse
 import json
@@ -195,6 +198,25 @@ def _finish_timing(t0, distributed):
     return (dt,)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, **arrays):
+    """--dump-outputs: what a caller of the timed step holds after the last timed step -- its loss, the flat gradient the reverse mode handed
+    to the optimiser and the flat parameters the optimiser updated -- as DIR/<name>.npy in the dtype computed (float32 / float64).  Above
+    DUMP_LIMIT_BYTES in all, every array but a single value keeps a share of its elements at indices drawn from a fixed seed, the same on
+    every run with the same arguments, so that two builds can be compared element for element."""
+    host = {k: np.atleast_1d(v.detach().cpu().numpy()) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    single = sum(a.nbytes for a in host.values() if a.size == 1)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        if total > DUMP_LIMIT_BYTES and a.size > 1:
+            keep = a.size * (DUMP_LIMIT_BYTES - single) // (total - single)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(dirname, name + '.npy'), a)
+
+
 def dist_report(world, steps, grad_elems, dtype):
     """What a reader needs to check an N-GPU line without the builder in the loop: the rank count the communicator itself reports, every
     rank's own ms per step, and the cost of the step's one collective (all-reduce of a flat gradient of this model's size) measured on its
@@ -225,9 +247,9 @@ def dist_report(world, steps, grad_elems, dtype):
     return rep
 
 
-def time_minibatch_steps(infr, loop, Xd, Yd, B, steps, warmup, lr, distributed):
+def time_minibatch_steps(infr, loop, Xd, Yd, B, steps, warmup, lr, distributed, dump=None):
     """One step = one minibatch: slice B rows of a fixed shuffle (the same on every rank), forward + reverse mode on this rank's MC samples,
-    gradient all-reduce, Trainer.step(batch_size=B)."""
+    gradient all-reduce, Trainer.step(batch_size=B).  dump: directory for the last timed step's outputs (dump_outputs)."""
     import torch.distributed as dist
     executor = infr.create_executor()
     trainer = loop._make_trainer(infr.params, lr, 'adam')
@@ -235,9 +257,11 @@ def time_minibatch_steps(infr, loop, Xd, Yd, B, steps, warmup, lr, distributed):
     perm = torch.randperm(N, device=Xd.device, generator=torch.Generator(device=Xd.device).manual_seed(99))
     nb = N // B
 
-    def one(i):
+    def one(i, keep=None):
         sel = perm[(i % nb) * B:(i % nb + 1) * B]
         loss = loop.step(executor, [Xd[sel], Yd[sel]], infr.params)
+        if keep is not None:
+            keep['grad'] = infr.params.flat.grad.detach().clone()
         trainer.step(batch_size=B)
         return loss
     loss = None
@@ -247,10 +271,14 @@ def time_minibatch_steps(infr, loop, Xd, Yd, B, steps, warmup, lr, distributed):
         dist.barrier()
     torch.cuda.synchronize()
     _mark_loop(loop, steps)
+    keep = {}
     t0 = time.perf_counter()
     for i in range(steps):
-        loss = one(warmup + i)
-    return _finish_timing(t0, distributed) + (float(loss.detach()),)
+        loss = one(warmup + i, keep if dump and i == steps - 1 else None)
+    res = _finish_timing(t0, distributed) + (float(loss.detach()),)
+    if dump:
+        dump_outputs(dump, loss=loss, grad=keep['grad'], params=infr.params.flat)
+    return res
 
 
 def time_minibatch_run(infr, data_kw, epochs, lr, distributed):
@@ -351,7 +379,7 @@ def _pendulum_cost(state, action):
     return (2. * (state[:, :, 0:1] - 1) ** 2).sum(-1) + (.001 * action ** 2).sum(-1) + (.1 * state[:, :, 2:3] ** 2).sum(-1)
 
 
-def bench_pilco(N, S, T, dtype, steps, warmup, use_graph, cpu_baseline=True):
+def bench_pilco(N, S, T, dtype, steps, warmup, use_graph, cpu_baseline=True, dump=None):
     """the PILCO rollout (pilco_alg.py:72-90) as a GP-predict-in-a-loop latency benchmark.  A GPRegression dynamics
     model on N conditioning points (3 state + 1 action inputs, 3 outputs; the pendulum shapes of testing/inference/pilco_test.py), S
     trajectories rolled T time steps under a Dense(100)-Dense(1) policy; one step = rollout + reverse pass + Adam on the policy."""
@@ -396,11 +424,15 @@ def bench_pilco(N, S, T, dtype, steps, warmup, use_graph, cpu_baseline=True):
         opt.step()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for i in range(steps):
         loss = loop.step(ex, [Xd, Yd], ip.params)
+        if dump and i == steps - 1:
+            grad = ip.params.flat.grad.detach().clone()         # the optimiser zeroes it in place
         opt.step()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
+    if dump:
+        dump_outputs(dump, loss=loss, grad=grad, params=ip.params.flat)
     out = {"metric": "policy-gradient steps/sec, PILCO rollout over a GPRegression dynamics model (SURVEY 8(f) rank 4)", "value": 1.0 / dt,
            "unit": "policy-gradient steps/sec", "n_gpus": 1, "steps": steps, "warmup": warmup, "ms_per_step": dt * 1e3,
            "us_per_rollout_time_step": dt / T * 1e6, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -454,7 +486,7 @@ def cpu_baseline_gp(N, Q, X, Y, reps=2):
             "sample": "oracle MAP step of the exact GP at the full N=%d (fwd + autograd bwd + Adam, float64, torch-CPU, %d threads): %.2f s" % (N, th, t)}
 
 
-def time_steps_multi(infr, loop, data, steps, warmup, lr, distributed):
+def time_steps_multi(infr, loop, data, steps, warmup, lr, distributed, dump=None):
     from mxfusion_amd.inference.batch_loop import _Adam
     import torch.distributed as dist
     executor = infr.create_executor()
@@ -468,10 +500,15 @@ def time_steps_multi(infr, loop, data, steps, warmup, lr, distributed):
     torch.cuda.synchronize()
     _mark_loop(loop, steps)
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for i in range(steps):
         loss = loop.step(executor, data, infr.params)
+        if dump and i == steps - 1:
+            grad = infr.params.flat.grad.detach().clone()       # the optimiser's zero_grad drops it
         trainer.step(batch_size=1)
-    return _finish_timing(t0, distributed) + (float(loss.detach()),)
+    res = _finish_timing(t0, distributed) + (float(loss.detach()),)
+    if dump:
+        dump_outputs(dump, loss=loss, grad=grad, params=infr.params.flat)
+    return res
 
 
 def set_trained_like(m, infr, Q, M, td):
@@ -530,7 +567,7 @@ def step_breakdown(infr, loop, Yd, lr, M, SB):
     return out
 
 
-def time_steps(infr, loop, Yd, steps, warmup, lr, distributed):
+def time_steps(infr, loop, Yd, steps, warmup, lr, distributed, dump=None):
     from mxfusion_amd.inference.batch_loop import _Adam
     import torch.distributed as dist
     executor = infr.create_executor()
@@ -544,10 +581,15 @@ def time_steps(infr, loop, Yd, steps, warmup, lr, distributed):
     torch.cuda.synchronize()
     _mark_loop(loop, steps)
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for i in range(steps):
         loss = loop.step(executor, [Yd], infr.params)
+        if dump and i == steps - 1:
+            grad = infr.params.flat.grad.detach().clone()       # the optimiser's zero_grad drops it
         trainer.step(batch_size=1)
-    return _finish_timing(t0, distributed) + (float(loss.detach()),)
+    res = _finish_timing(t0, distributed) + (float(loss.detach()),)
+    if dump:
+        dump_outputs(dump, loss=loss, grad=grad, params=infr.params.flat)
+    return res
 
 
 def _pmc_traffic(stem):
@@ -760,8 +802,13 @@ def main():
                          "'gloo' on device tensors (the same product loops and HIP kernels, collectives staged through the host)")
     ap.add_argument('--same-device', action='store_true',
                     help='with --backend gloo: every rank runs on cuda:0 -- a software check of the multi-process path on a one-GPU box, not a measurement')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the roofline micro-measurements and the f64 cross-check')
+    ap.add_argument('--full', action='store_true', help='besides the timed steps: the CPU baseline, the roofline micro-measurements, the in-step '
+                    'kernel breakdown, the trained-like / whitened steps, the per-rank proxy, the other precision and the f32-vs-f64 cross-check '
+                    '(svgp), the steps through GradBasedInference.run (--minibatch)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the roofline micro-measurements and the f64 cross-check')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help="write the last timed step's loss, flat gradient and updated flat "
+                    "parameters as DIR/<name>.npy (rank 0)")
     ap.add_argument('--f32-form', default='auto', choices=['auto', 'explicit', 'whitened', 'float64'],
                     help="float32 SVGP calls: 'auto' = the per-module guard picks (explicit-inverse up to cond 1e3, whitened up to 1e6, float64 above); "
                          "the others force one form for a measurement")
@@ -770,6 +817,8 @@ def main():
     ap.add_argument('--no-f32-guard', action='store_true', help='disable the automatic float64 fallback of the float32 SVGP step above cond_1(Kuu) 3e3 '
                                                                     '(DESIGN.md section 5): raw float32 timing of an ill-conditioned model')
     args = ap.parse_args()
+    # a plain run times the steps and nothing else: everything further is --full
+    extras, cpu_base = args.full and not args.no_extras, args.full and not args.no_cpu_baseline
 
     # stdout carries exactly ONE line, the JSON: RCCL prints a version banner to the C stdout at start-up (seen after the JSON when stdout
     # is a pipe), so file descriptor 1 is pointed at stderr for the rest of the run and the JSON goes to the saved descriptor
@@ -836,10 +885,12 @@ def main():
         raise SystemExit('--samples must be divisible by the number of GPUs')
     S_local = args.samples // world
     torch.manual_seed(1234 + rank)
+    np.random.seed(1234 + rank)            # (initial values of parameters the models leave unset: identical inputs from run to run)
+    dump = args.dump_outputs if rank == 0 else None
 
     if args.workload == 'pilco':       # GP-predict-in-a-loop latency (single GPU; the rollout is a serial chain)
         out = bench_pilco(1000 if args.N == 65536 else args.N, 64 if args.samples == 32 else args.samples, args.horizon,
-                          'float64' if args.dtype == 'float64' else 'float32', args.steps, args.warmup, args.graph, not args.no_cpu_baseline)
+                          'float64' if args.dtype == 'float64' else 'float32', args.steps, args.warmup, args.graph, cpu_base, dump)
         if rank == 0:
             emit(out)
         return
@@ -849,7 +900,7 @@ def main():
         m, infr, loop = build_gp(N, Q, args.dtype, X, Y)
         td = torch.float32 if args.dtype == 'float32' else torch.float64
         data = [torch.as_tensor(X, dtype=td).cuda(), torch.as_tensor(Y, dtype=td).cuda()]
-        dt, last_loss = time_steps_multi(infr, loop, data, args.steps, args.warmup, args.lr, False)
+        dt, last_loss = time_steps_multi(infr, loop, data, args.steps, args.warmup, args.lr, False, dump)
         out = {"metric": "MAP-steps/sec, exact GPRegression (BASELINE.json configs[1])", "value": world * args.steps / dt, "unit": "MAP-steps/sec",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
                "scaling": "weak", "vs_baseline": None, "dtype": "f32" if args.dtype == 'float32' else "f64", "data": "synthetic",
@@ -866,7 +917,7 @@ def main():
             out["roofline_f64_mfma"] = {"bound": "mfma", "kernel": "potrf + trtri + lower L^-T L^-1 (float64 v_mfma_f64_16x16x4_f64)", "achieved": ach,
                                         "peak": 78.6, "unit": "TFLOP/s", "frac": ach / 78.6,
                                         "note": "whole step (incl. Gram, reverse pass, Adam) in the denominator"}
-        if rank == 0 and not args.no_cpu_baseline:
+        if rank == 0 and cpu_base:
             out["cpu_baseline"] = cpu_baseline_gp(N, Q, X, Y)
         if rank == 0:
             emit(out)
@@ -880,7 +931,7 @@ def main():
         infr, loop = build_deepgp(N, Q, M, Dh, S_local, args.dtype, X, Y, distributed)
         td = torch.float32 if args.dtype == 'float32' else torch.float64
         data = [torch.as_tensor(X, dtype=td).cuda(), torch.as_tensor(Y, dtype=td).cuda()]
-        dt, last_loss = time_steps_multi(infr, loop, data, args.steps, args.warmup, args.lr, distributed)
+        dt, last_loss = time_steps_multi(infr, loop, data, args.steps, args.warmup, args.lr, distributed, dump)
         rep = dist_report(world, args.steps, infr.params.flat.numel(), td)          # collective: every rank
         if rank == 0:
             emit(dict({
@@ -901,14 +952,15 @@ def main():
         td = torch.float32 if args.dtype == 'float32' else torch.float64
         m, infr, loop = build_minibatch_rows(N, Q, M, B, args.dtype, Z, proxy_world=args.proxy_world)
         Xd, Yd = torch.as_tensor(X, dtype=td).cuda(), torch.as_tensor(Y, dtype=td).cuda()
-        dt, last_loss = time_minibatch_steps(infr, loop, Xd, Yd, B, args.steps, args.warmup, args.lr, distributed)
-        run_s = time_minibatch_run(infr, {'X': Xd, 'Y': Yd}, max(2, args.steps // (N // B)), args.lr, distributed)
+        dt, last_loss = time_minibatch_steps(infr, loop, Xd, Yd, B, args.steps, args.warmup, args.lr, distributed, dump)
         rep = dist_report(world, args.steps, infr.params.flat.numel(), td)
+        if args.full:
+            rep["ms_per_step_through_run"] = time_minibatch_run(infr, {'X': Xd, 'Y': Yd}, max(2, args.steps // (N // B)), args.lr, distributed) * 1e3
         w = args.proxy_world if args.proxy_world > 1 else world
         if rank == 0:
             emit(dict({"metric": "ELBO-steps/sec (minibatch steps), SVGP MAP on observed inputs N=65k D=8 M=1024 minibatch=%d, rows sharded" % B,
                   "value": args.steps / dt, "unit": "ELBO-steps/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                  "ms_per_step": dt / args.steps * 1e3, "ms_per_step_through_run": run_s * 1e3, "higher_is_better": True, "scaling": "strong",
+                  "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong",
                   "vs_baseline": None, "dtype": "f32" if args.dtype == 'float32' else "f64", "data": "synthetic",
                   "config": {"workload": "SVGPRegression RBF-ARD N=%d Q=%d M=%d, MAP on observed inputs (no sample axis: the reference's svgp_regression "
                                          "notebook), minibatch %d (rv_scaling %g), step = minibatch ELBO + reverse mode + grad all-reduce + Adam"
@@ -926,12 +978,12 @@ def main():
         td = torch.float32 if args.dtype == 'float32' else torch.float64
         m, infr, loop = build_minibatch(N, Q, M, B, S_local, args.dtype, Z)
         Xd_, Yd_ = torch.as_tensor(X, dtype=td).cuda(), torch.as_tensor(Y, dtype=td).cuda()
-        dt, last_loss = time_minibatch_steps(infr, loop, Xd_, Yd_, B, args.steps, args.warmup, args.lr, distributed)
-        # the same steps through GradBasedInference.run (what a user calls): r04's loop synchronised the device on every minibatch
-        run_s = time_minibatch_run(infr, {'Xobs': Xd_, 'Y': Yd_}, max(2, args.steps // (N // B)), args.lr, distributed)
+        dt, last_loss = time_minibatch_steps(infr, loop, Xd_, Yd_, B, args.steps, args.warmup, args.lr, distributed, dump)
         rep = dist_report(world, args.steps, infr.params.flat.numel(), td)          # collective: every rank
-        rep["ms_per_step_through_run"] = run_s * 1e3
-        if world == 1 and not args.no_extras and args.samples % 8 == 0 and args.samples >= 8:
+        if args.full:
+            # the same steps through GradBasedInference.run (what a user calls): r04's loop synchronised the device on every minibatch
+            rep["ms_per_step_through_run"] = time_minibatch_run(infr, {'Xobs': Xd_, 'Y': Yd_}, max(2, args.steps // (N // B)), args.lr, distributed) * 1e3
+        if world == 1 and extras and args.samples % 8 == 0 and args.samples >= 8:
             # one rank's share of an 8-GPU run of this config on THIS GPU (samples / 8, no collective): the projection the scaling curve will be
             # read against -- the sample-independent M x M chain is the floor of a rank's step
             del infr, m, loop
@@ -960,7 +1012,7 @@ def main():
     if args.trained_like:
         set_trained_like(m, infr, Q, M, td)
     Yd = torch.as_tensor(Y, dtype=td).cuda()
-    dt, last_loss = time_steps(infr, loop, Yd, args.steps, args.warmup, args.lr, distributed)
+    dt, last_loss = time_steps(infr, loop, Yd, args.steps, args.warmup, args.lr, distributed, dump)
     rep = dist_report(world, args.steps, infr.params.flat.numel(), td)              # collective: every rank
 
     out = {
@@ -980,9 +1032,9 @@ def main():
     out.update(guard_report())
     out["parameters"] = "trained-like (length-scale 2.2, noise 0.02, non-trivial q(u))" if args.trained_like else "initial point (length-scale 1, q(u) = N(0, I))"
     out["f32_form"] = args.f32_form
-    if rank == 0 and world == 1 and not args.no_extras and args.dtype == 'float32':
+    if rank == 0 and world == 1 and extras and args.dtype == 'float32':
         out.update(step_breakdown(infr, loop, Yd, args.lr, M, N * S_local))
-    if rank == 0 and world == 1 and not args.no_extras and args.dtype == 'float32' and not args.trained_like and args.f32_form == 'auto':
+    if rank == 0 and world == 1 and extras and args.dtype == 'float32' and not args.trained_like and args.f32_form == 'auto':
         # the regime the step is used in: the same step at trained-like parameters (explicit form: cond ~ 1.4e3 < 3e3), and in the
         # whitened float32 form the guard selects above cond 1e3
         from mxfusion_amd.modules.gp_modules._fused import Float32Guard
@@ -999,7 +1051,7 @@ def main():
             out["whitened"] = step_breakdown(infr, loop, Yd, args.lr, M, N * S_local)
         finally:
             Float32Guard.force = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and extras:
         del infr, m, q
         torch.cuda.empty_cache()
         if args.samples % 8 == 0 and args.samples >= 8 and not args.trained_like:
@@ -1046,7 +1098,7 @@ def main():
                 del mm, qq, ii, ex
                 torch.cuda.empty_cache()
             out[key] = abs(vals['float32'] - vals['float64']) / abs(vals['float64'])
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and cpu_base:
         out["cpu_baseline"] = cpu_baseline(N, Q, M, args.samples, X, Y, Z)
     if rank == 0:
         emit(out)

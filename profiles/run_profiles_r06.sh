@@ -6,7 +6,7 @@ O=$R/gpurun_out/prof_r06
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 # 1. rocprofv3 kernel stats of the default bench command (the roofline kernels' per-launch averages) and of the bare step; one step as a timeline
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_full -o bench -- python $R/bench.py --steps 3 --warmup 2 --no-cpu-baseline > $O/bench_trace_full.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_full -o bench -- python $R/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline > $O/bench_trace_full.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_step -o bench -- python $R/bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-extras > $O/bench_trace_step.log 2>&1
 python $R/profiles/timeline.py $(find $O/trace_step -name "*kernel_trace.csv") 0.15 > $O/r06_step_timeline.txt 2>&1
 # 2. the whitened float32 form at trained-like parameters
@@ -36,21 +36,21 @@ done
 rm -rf $O/trace_* $O/pmc_*_fetch $O/pmc_*_write $O/pmc_*_sq $O/pmc_*_lds $O/pmc_gram_write $O/pmc_gram_fetch 2>/dev/null
 # 6. bench lines
 cd $R
-python bench.py > $O/r06_bench_full.json 2> $O/full.log
+python bench.py --full > $O/r06_bench_full.json 2> $O/full.log
 python bench.py --samples 4 --steps 30 --warmup 5 --no-cpu-baseline --no-extras > $O/r06_bench_4samples_per_gpu.json 2>/dev/null
 python bench.py --samples 4 --trained-like --steps 30 --warmup 5 --no-cpu-baseline --no-extras > $O/r06_bench_4samples_per_gpu_trained_like.json 2>/dev/null
 python bench.py --samples 4 --steps 30 --warmup 5 --no-cpu-baseline --no-extras --force-dist > $O/r06_bench_4samples_per_gpu_rccl_path.json 2>/dev/null
-python bench.py --minibatch 8192 --steps 40 --warmup 5 --no-cpu-baseline > $O/r06_bench_minibatch8192.json 2>/dev/null
-python bench.py --minibatch 8192 --samples 4 --steps 40 --warmup 5 --no-cpu-baseline > $O/r06_bench_minibatch8192_4samples.json 2>/dev/null
-python bench.py --minibatch 8192 --shard rows --samples 1 --steps 40 --warmup 5 --no-cpu-baseline > $O/r06_bench_rows_minibatch8192_1gpu.json 2>/dev/null
-python bench.py --minibatch 8192 --shard rows --samples 1 --proxy-world 8 --steps 40 --warmup 5 --no-cpu-baseline > $O/r06_bench_rows_minibatch8192_rank_of_8.json 2>/dev/null
+python bench.py --full --minibatch 8192 --steps 40 --warmup 5 --no-cpu-baseline > $O/r06_bench_minibatch8192.json 2>/dev/null
+python bench.py --full --minibatch 8192 --samples 4 --steps 40 --warmup 5 --no-cpu-baseline > $O/r06_bench_minibatch8192_4samples.json 2>/dev/null
+python bench.py --full --minibatch 8192 --shard rows --samples 1 --steps 40 --warmup 5 --no-cpu-baseline > $O/r06_bench_rows_minibatch8192_1gpu.json 2>/dev/null
+python bench.py --full --minibatch 8192 --shard rows --samples 1 --proxy-world 8 --steps 40 --warmup 5 --no-cpu-baseline > $O/r06_bench_rows_minibatch8192_rank_of_8.json 2>/dev/null
 python bench.py --workload gp --dtype float64 --steps 5 --warmup 2 --no-cpu-baseline > $O/r06_bench_exact_gp_f64.json 2>/dev/null
 python bench.py --workload deepgp --samples 4 --steps 10 --warmup 3 --no-cpu-baseline > $O/r06_bench_deepgp_4samples.json 2>/dev/null
 python bench.py --workload deepgp --samples 32 --steps 5 --warmup 2 --no-cpu-baseline > $O/r06_bench_deepgp_32samples.json 2>/dev/null
 # the distributed product with REAL kernels in 2 / 4 processes on this one GPU (gloo on device tensors): a software check, not a measurement
 python bench.py --gpus 2 --backend gloo --same-device --steps 5 --warmup 2 --no-cpu-baseline --no-extras > $O/r06_bench_2ranks_one_gpu_gloo.json 2>/dev/null
 python bench.py --gpus 4 --backend gloo --same-device --steps 5 --warmup 2 --no-cpu-baseline --no-extras > $O/r06_bench_4ranks_one_gpu_gloo.json 2>/dev/null
-python bench.py --gpus 2 --backend gloo --same-device --minibatch 8192 --steps 10 --warmup 2 --no-cpu-baseline > $O/r06_bench_2ranks_one_gpu_gloo_minibatch8192.json 2>/dev/null
+python bench.py --full --gpus 2 --backend gloo --same-device --minibatch 8192 --steps 10 --warmup 2 --no-cpu-baseline > $O/r06_bench_2ranks_one_gpu_gloo_minibatch8192.json 2>/dev/null
 for f in $O/*.json; do python - $f <<'PY'
 import json,sys
 try:

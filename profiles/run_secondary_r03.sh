@@ -1,9 +1,9 @@
 cd $GRAFT_REPO_ROOT; O=gpurun_out/sec_r03; mkdir -p $O
-python bench.py > $O/r03_bench_full.json 2> $O/full.log
+python bench.py --full > $O/r03_bench_full.json 2> $O/full.log
 python bench.py --samples 4 --steps 30 --warmup 5 --no-cpu-baseline --no-extras > $O/r03_bench_4samples_per_gpu.json 2>/dev/null
 python bench.py --samples 4 --steps 30 --warmup 5 --no-cpu-baseline --no-extras --force-dist > $O/r03_bench_4samples_per_gpu_rccl_path.json 2>/dev/null
-python bench.py --minibatch 8192 --steps 30 --warmup 5 --no-cpu-baseline > $O/r03_bench_minibatch8192.json 2>/dev/null
-python bench.py --minibatch 8192 --samples 4 --steps 30 --warmup 5 --no-cpu-baseline > $O/r03_bench_minibatch8192_4samples.json 2>/dev/null
+python bench.py --full --minibatch 8192 --steps 30 --warmup 5 --no-cpu-baseline > $O/r03_bench_minibatch8192.json 2>/dev/null
+python bench.py --full --minibatch 8192 --samples 4 --steps 30 --warmup 5 --no-cpu-baseline > $O/r03_bench_minibatch8192_4samples.json 2>/dev/null
 python bench.py --workload gp --dtype float64 --steps 5 --warmup 2 --no-cpu-baseline > $O/r03_bench_exact_gp_f64.json 2>/dev/null
 python bench.py --workload deepgp --samples 4 --steps 10 --warmup 3 --no-cpu-baseline > $O/r03_bench_deepgp_4samples.json 2>/dev/null
 python bench.py --workload deepgp --samples 32 --steps 5 --warmup 2 --no-cpu-baseline > $O/r03_bench_deepgp_32samples.json 2>/dev/null
