@@ -777,13 +777,13 @@ __global__ __launch_bounds__(256) void sumlogdiag_kernel(const T* __restrict__ L
 //  and tile reads share its L2) and 120 mostly waiting workgroups hold CUs the look-ahead GEMM wants: potrf(8192) 7.18 vs 6.72 ms.)
 // MFMA conventions as potrf_tiles_kernel: A operand lane (li, lq) = P[m = li][k = lq], B operand = Q[n = li][k = lq], accumulator register r of
 // lane (li, lq) = element (row lq + 4 r, column li).
-// RH (r06): rows per workgroup.  A block row's critical chain is npt x (solve + ONE wave's tile update): at RH = 64 that update is 256 float64
-// MFMAs of 64 cycles each, 7.8 us, i.e. >= 62 us per outer panel on <= 120 of the 256 CUs.  RH = 32 / 16 halve / quarter the chain and
-// double / quadruple the workgroup count (each re-reads the L2-resident diagonal block L11: 1.2 MB per workgroup).
+// RH (r06): rows per workgroup.  A block row's critical chain is npt x (solve + ONE wave's tile update): at 64 rows that update is 256 float64
+// MFMAs of 64 cycles each, 7.8 us, i.e. >= 62 us per outer panel on <= 120 of the 256 CUs.  32 rows halve the chain and double the workgroup
+// count (each re-reads the L2-resident diagonal block L11: 1.2 MB per workgroup).
 static_assert(NBO / NB <= 8, "potrf_rows_kernel: one wave per tile of the panel, eight waves");
-template <int RH>
 __global__ __launch_bounds__(512) void potrf_rows_kernel(double* __restrict__ A, int64_t lda, int64_t sA, int64_t c0, int npt, int row0,
                                                          const double* __restrict__ inv_all) {
+    constexpr int RH = 32;
     constexpr int XR = RH / 16;
     __shared__ double Tb[2][RH][NB + 1];
     __shared__ double a[NB][NB + 1];          // L[k][k]
@@ -892,23 +892,8 @@ int trtri_typed(mxf_ctx* h, int dtype, int S, int64_t n, const T* L, int64_t ldl
 template <typename T>
 __global__ void zero_block_kernel(T* __restrict__ P, int64_t rows, int64_t cols, int64_t ld, int64_t stride);
 
-// Row block i (rows [c0, pe)) of L^-1 from the finished leading part of the factor (r05; the merge step of trtri_typed with a first block of c0 rows
-// and a second of pe - c0):  I_ii = inv(L_ii),  X = -I_ii (L[i, :c0] I[:c0, :c0]),  the temporary (L[i, :c0] I[:c0, :c0])^T in the upper mirror block.
-// Needs L[:pe, :pe] only, i.e. it can run as soon as the outer panel ending at pe has been factored -- next to the rest of the factorisation.
-template <typename T>
-int trtri_row_block(mxf_ctx* h, int dtype, int64_t c0, int64_t pe, const T* L, int64_t ldl, T* Li, int64_t ldi, hipStream_t st) {
-    const int64_t b2 = pe - c0;
-    int rc = trtri_typed<T>(h, dtype, 1, b2, L + c0 * (ldl + 1), ldl, 0, Li + c0 * (ldi + 1), ldi, 0, st);
-    if (rc || c0 == 0) return rc;
-    static const int res = (int)MXF_KNOB("MXF_POTRF_EAGER_RES", 0);      // CUs these products leave to the factorisation's chain (probe knob)
-    rc = mxf_gemm_internal(h, dtype, 1, 1, c0, b2, c0, 1.0, Li, ldi, 0, L + c0 * ldl, ldl, 0, 0.0, Li + c0, ldi, 0, 1, 0, st, res, 1);
-    if (rc) return rc;
-    rc = mxf_gemm_internal(h, dtype, 0, 1, b2, c0, b2, -1.0, Li + c0 * (ldi + 1), ldi, 0, Li + c0, ldi, 0, 0.0, Li + c0 * ldi, ldi, 0, 1, 0, st, res, 2);
-    if (rc) return rc;
-    hipLaunchKernelGGL((zero_block_kernel<T>), dim3((unsigned)((c0 * b2 + 255) / 256 > 1024 ? 1024 : (c0 * b2 + 255) / 256), 1), dim3(256), 0, st, Li + c0, c0, b2, ldi, (int64_t)0);
-    return 0;
-}
-// The same row block in its three dependent pieces (r06), so that each starts as soon as ITS inputs exist:
+// Row block i (rows [c0, pe)) of L^-1 from the finished leading part of the factor (the merge step of trtri_typed with a first block of c0 rows
+// and a second of pe - c0), in three dependent pieces, so that each starts as soon as ITS inputs exist:
 //   p1: (L[i, :c0] I[:c0, :c0])^T into the upper mirror block -- needs the rows below the panel ending at c0 and the finished leading inverse,
 //       NOT the block's own panels (the bulk of the row block's work: 2 b2 c0^2 / 2 flops);
 //   the inverse of the diagonal block L[i, i] -- needs the block's own panels only (latency-bound small launches: a stream of its own);
@@ -931,21 +916,18 @@ int trtri_row_block_p2(mxf_ctx* h, int dtype, int64_t c0, int64_t pe, T* Li, int
 // trtri(8192) afterwards took 3.9 ms of a 15 ms MAP step.  *eager_done tells the caller whether Ie was filled (else: call trtri afterwards).
 template <typename T>
 int potrf_typed(mxf_ctx* h, int dtype, int S, int64_t n, T* A, int64_t lda, int64_t sA, int* info, hipStream_t st, bool zero_upper, bool zero_info,
-                T* Ie = nullptr, int64_t ldie = 0, bool* eager_done = nullptr, T* Kacc = nullptr, int64_t ldk = 0, double kcoef = 0.0,
-                bool* kacc_done = nullptr) {
+                T* Ie = nullptr, int64_t ldie = 0, bool* eager_done = nullptr) {
     if (eager_done) *eager_done = false;
-    if (kacc_done) *kacc_done = false;
     if (info && zero_info) MXF_HIP(h, hipMemsetAsync(info, 0, sizeof(int) * S, st));
     // Look-ahead (n >= 2048): the trailing update after an outer panel is split into the part that touches the NEXT outer panel's columns
     // (on the caller's stream, so that panel's latency-bound factorisation starts right away) and the rest (on an auxiliary stream, next to
     // that factorisation).  At n = 8192 the 128 panel steps (85 us each) otherwise serialise with 3.7 ms of trailing GEMMs.
-    static const int tiles_env = MXF_KNOB("MXF_POTRF_TILES", 1);
-    // tiles_env: 0 = launch-per-panel form everywhere, 1 = the tile kernel (one launch up to MXF_POTRF_ONE_MAX = 512, per outer panel beyond), 2 = only its one-launch form
+    // float64: the tile kernel, one launch up to MXF_POTRF_ONE_MAX = 512, one per outer panel beyond; float32: the launch-per-panel form
     // The tile kernel's workgroups hand tiles to each other through progress counters: every workgroup of a launch must be RESIDENT at once
     // (one per CU: 256 threads at one wave per SIMD, ~76 KB of LDS), or a waiting workgroup could hold the CU its producer needs.  The grid
     // (block rows x batch) is therefore bounded by the CU count of the device; larger problems take the launch-per-panel form below.
     static const int ncu = [] { int dev = 0, v = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 64; return v; }();
-    const bool tiles_ok = sizeof(T) == 8 && tiles_env && n % NB == 0 && n >= 2 * NB && S <= 64;
+    const bool tiles_ok = sizeof(T) == 8 && n % NB == 0 && n >= 2 * NB && S <= 64;
     if constexpr (sizeof(T) == 8) {
         static const int one_max = MXF_KNOB("MXF_POTRF_ONE_MAX", 512);
         if (tiles_ok && n <= one_max && (int64_t)(n / NB) * S <= ncu) {    // (n = 2048 as ONE left-looking launch: 2.6 ms vs 1.9 -- the last block rows carry 32 i^2 columns of products each)
@@ -960,57 +942,22 @@ int potrf_typed(mxf_ctx* h, int dtype, int S, int64_t n, T* A, int64_t lda, int6
             return 0;
         }
     }
-    const bool panel_tiles = tiles_ok && tiles_env == 1 && (int64_t)(n / NB) * S <= ncu;      // every block row's workgroup must be resident at once
+    const bool panel_tiles = tiles_ok && (int64_t)(n / NB) * S <= ncu;      // every block row's workgroup must be resident at once
     static const int look_env = MXF_KNOB("MXF_POTRF_LOOKAHEAD", 2);
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(st, &cap);
     const bool look = look_env && n >= 2048 && cap == hipStreamCaptureStatusNone && mxf_potrf_aux_init(h);
-    // MXF_POTRF_CUMASK (common.h): CU-masked bulk streams are blocking streams -- the chain moves to a non-blocking stream of its own
-    hipStream_t st_user = st;
-    const bool own_chain = look && (h->potrf_masked || h->potrf_chain_always) && h->potrf_chain;
-    if (own_chain) {
-        MXF_HIP(h, hipEventRecord(h->ev_pk, st_user));
-        MXF_HIP(h, hipStreamWaitEvent(h->potrf_chain, h->ev_pk, 0));
-        st = h->potrf_chain;
-    }
     hipStream_t ax = look ? h->potrf_aux : st;
-    bool pending_b = false, pending_h = false, pending_r = false;
-    // r06, measured and NOT kept -- probe knob MXF_POTRF_ROWS2=1: only the NEXT panel's eight block rows of the rows below
-    // an outer panel are on the serial path (its diagonal block's head update reads them), so the rows further down are solved on a stream
-    // of their own next to that head update and the next chain, and the auxiliary stream's products -- the only readers of those rows --
-    // wait for them.  Correct (tests/test_gpu_linalg.py passes either way), but same box, alternating: potrf(8192) 6.65 / 6.67 ms with it,
-    // 6.57 / 6.60 without; exact-GP MAP step 14.64-14.67 against 14.52-14.53 ms -- the hundred far-row workgroups now run NEXT TO the next
-    // panel's latency-bound chain and head update instead of before them, and the chain pays more than the shorter path saves (the same
-    // outcome as r03's rows kernel following the chain's progress counters and r05's per-panel eager inverse).
-    static const int rows2_env = MXF_KNOB("MXF_POTRF_ROWS2", 0);
+    bool pending_b = false, pending_h = false;
     // row blocks of FOUR outer panels (2048 rows), from four row blocks on.  Measured at n = 8192 (MAP step of the exact GP, two alternating rounds,
     // profiles/r05_potrf_eager_inverse_ab.txt): off 15.0 ms; every panel 18.1 (208 more launches, and products of a few tiles each that hold CUs the
     // chain's tile workgroups are waiting for); every second 14.6-14.7; every fourth 14.5; two halves 15.0; leaving the products 64 / 128 CUs less changes nothing
-    // r06: with the row blocks in split pieces (MXF_POTRF_EAGER_SPLIT below) blocks of TWO panels are best: 14.10-14.15 ms against 14.42-14.44
+    // r06: with the row blocks in split pieces (below) blocks of TWO panels are best: 14.10-14.15 ms against 14.42-14.44
     // (four), 15.0 (three: ragged last block), 14.72 for the r05 form
     static const int eager_env = MXF_KNOB("MXF_POTRF_EAGER_INV", 2);
-    // r06 (session 4), measured and NOT kept -- probe knob MXF_POTRF_KACC=1: kcoef L^-T L^-1 = sum over row blocks b of Linv[b, :]^T Linv[b, :],
-    // each share accumulated into the caller's zeroed buffer (lower triangle) on a stream of its own as soon as row block b of the eager inverse
-    // is final -- 2.6 ms of products moved under the factorisation, leaving 1.2 ms (the last block's share) instead of the 2.9 ms product behind it.
-    // Correct (the exact-GP tests pass with it), but the MAP step at n = 8192 goes 13.82-13.87 -> 15.73-15.84 ms (same box, alternating,
-    // tests/probes/r06_kacc_ab*.sh): the chain pays ~4 ms for the 1.7 ms the tail saves.  What the chain suffers from is not a lack of free
-    // CUs: with the bulk streams CU-masked so that 2 / 4 / 8 CUs of every XCD stay free for it (MXF_POTRF_CUMASK, common.h; the masked streams
-    // are blocking streams, so the chain then runs on a non-blocking stream of its own) the step takes 18.5-18.7 ms (22.3-24.0 with the
-    // accumulation), and the chain alone on a most-urgent stream (MXF_POTRF_CHAIN_PRIO=1) 16.8 ms; GPU_MAX_HW_QUEUES 4 / 8 changes nothing.
-    // Its tile hand-offs go through L2 / the fabric, and that is what the products next to it load.
-    static const int kacc_env = MXF_KNOB("MXF_POTRF_KACC", 0);
     const bool eager = Ie != nullptr && eager_env && sizeof(T) == 8 && S == 1 && panel_tiles && look && n % NBO == 0 && n >= 16 * NBO &&
                        n >= 4 * (eager_env >= 100 ? n / 8 : (int64_t)eager_env * NBO);
-    static const int esplit_env0 = MXF_KNOB("MXF_POTRF_EAGER_SPLIT", 1);
-    const bool kacc = eager && Kacc != nullptr && kacc_env && esplit_env0 && !rows2_env && h->potrf_acc;
-    if (kacc) {     // (the buffer is zeroed on the accumulation stream, behind whatever the caller's stream did with it before)
-        MXF_HIP(h, hipEventRecord(h->ev_pq, st));
-        MXF_HIP(h, hipStreamWaitEvent(h->potrf_acc, h->ev_pq, 0));
-        MXF_HIP(h, hipMemsetAsync(Kacc, 0, sizeof(T) * (size_t)n * (size_t)ldk, h->potrf_acc));
-    }
     static const int split_rows_g = MXF_KNOB("MXF_POTRF_SPLIT_ROWS", 64);
-    static const int rows_env_g = MXF_KNOB("MXF_POTRF_ROWS_KERNEL", 1);     // 0: the rows below through potrf_tiles_kernel (r02)
-    static const int head_split_env = MXF_KNOB("MXF_POTRF_HEAD_SPLIT", 1);  // 1: the next panel's rows-below head update on the auxiliary stream
     // does the outer panel at c0 take the split form (chain launch + rows-below launch)?
     auto is_split = [&](int64_t c0_) {
         const int64_t pe_ = (c0_ + NBO < n) ? c0_ + NBO : n;
@@ -1038,85 +985,37 @@ int potrf_typed(mxf_ctx* h, int dtype, int S, int64_t n, T* A, int64_t lda, int6
                 double* pinv = mxf_potrf_inv(h, (size_t)npt * S * 1024);
                 if (!pinv) MXF_FAIL(h, -4, "mxf_potrf: cannot allocate the inverse-block scratch");
                 hipLaunchKernelGGL(potrf_tiles_kernel, dim3(na, (unsigned)S), dim3(256), 0, st, A, lda, sA, c0, (int)npt, info, progress, pinv, 0, 0);
-                const int rows_env = rows_env_g;
                 // (the rows below this panel's diagonal block were updated on the auxiliary stream, next to the chain above)
-                const bool had_h = pending_h;
                 if (pending_h) { MXF_HIP(h, hipStreamWaitEvent(st, h->ev_ph, 0)); pending_h = false; }
-                // nblk block rows of NB rows from block row row0 of the panel on: workgroups of RH rows each (MXF_POTRF_ROWS_RH, see the kernel)
-                auto launch_rows = [&](unsigned nblk, unsigned row0, hipStream_t s_) {
-                    static const int rh_env = MXF_KNOB("MXF_POTRF_ROWS_RH", 32);
-                    if (rh_env == 16) hipLaunchKernelGGL(potrf_rows_kernel<16>, dim3(nblk * 4, (unsigned)S), dim3(512), 0, s_, A, lda, sA, c0, (int)npt, (int)row0, (const double*)pinv);
-                    else if (rh_env == 32) hipLaunchKernelGGL(potrf_rows_kernel<32>, dim3(nblk * 2, (unsigned)S), dim3(512), 0, s_, A, lda, sA, c0, (int)npt, (int)row0, (const double*)pinv);
-                    else hipLaunchKernelGGL(potrf_rows_kernel<64>, dim3(nblk, (unsigned)S), dim3(512), 0, s_, A, lda, sA, c0, (int)npt, (int)row0, (const double*)pinv);
-                };
-                if (split && rows_env) {       // r03: the rows below right-looking from registers (potrf_rows_kernel)
-                    const unsigned nbel = nbr - npt, nfirst = (unsigned)(NBO / NB) < nbel ? (unsigned)(NBO / NB) : nbel;
-                    if (rows2_env && look && head_split_env && nbel >= nfirst + 16 && pe + NBO < n) {
-                        if (had_h) MXF_HIP(h, hipStreamWaitEvent(h->potrf_rows, h->ev_ph, 0));      // (their columns' head update, auxiliary stream)
-                        MXF_HIP(h, hipEventRecord(h->ev_pc, st));                                   // the chain of this panel (and all before it)
-                        MXF_HIP(h, hipStreamWaitEvent(h->potrf_rows, h->ev_pc, 0));
-                        launch_rows(nfirst, npt, st);
-                        launch_rows(nbel - nfirst, npt + nfirst, h->potrf_rows);
-                        MXF_HIP(h, hipEventRecord(h->ev_rb, h->potrf_rows));
-                        pending_r = true;
-                    } else
-                    launch_rows(nbr - npt, npt, st);
-                } else if (split)
-                    hipLaunchKernelGGL(potrf_tiles_kernel, dim3(nbr - npt, (unsigned)S), dim3(256), 0, st, A, lda, sA, c0, (int)npt, info, progress, pinv, (int)npt, 1);
+                // r03: the rows below right-looking from registers, workgroups of 32 rows (see potrf_rows_kernel)
+                if (split) hipLaunchKernelGGL(potrf_rows_kernel, dim3((nbr - npt) * 2, (unsigned)S), dim3(512), 0, st, A, lda, sA, c0, (int)npt, (int)npt, (const double*)pinv);
             }
         }
         // row block [rb0, pe) of L is final once the panel ending at pe has been factored (the rows above it in these columns are zero).  Row blocks
-        // of eager_rb outer panels (probe knob MXF_POTRF_EAGER_INV: 1 = every panel, 2 = every second, ..., 100 = two halves)
+        // of eager_rb outer panels (MXF_POTRF_EAGER_INV: 1 = every panel, 2 = every second, ..., 100 = two halves)
         const int64_t rbw = eager_env >= 100 ? n / 2 : (int64_t)eager_env * NBO;
-        // r06 probe knob MXF_POTRF_EAGER_TAIL = t > 0: behind the first 3/4 of the rows the row blocks shrink to t outer panels -- the last
-        // block is what stays exposed behind the factorisation (2.5 ms of the 14.6 ms MAP step at n = 8192 with blocks of four panels), and
-        // the late panels are chain-bound, i.e. the chip is mostly idle next to them
-        static const int tail_env = MXF_KNOB("MXF_POTRF_EAGER_TAIL", 0);
-        const int64_t tail0 = (n * 3 / 4) / rbw * rbw, tbw = (int64_t)(tail_env > 0 ? tail_env : 1) * NBO;
-        const bool in_tail = tail_env > 0 && eager_env < 100 && tbw < rbw && pe > tail0;
-        const bool fire = in_tail ? ((pe - tail0) % tbw == 0 || pe == n) : (pe % rbw == 0 || pe == n);
-        // r06, MXF_POTRF_EAGER_SPLIT (default 1): the row block's pieces separately (trtri_row_block_p1 / _p2).  When block b's panels end, its
-        // diagonal inverse goes to the third auxiliary stream, its p2 follows on the inverse stream, and p1 of block b + 1 -- whose inputs are
-        // complete at this point, four panels before that block is factored -- is queued right behind.  What is left behind the factorisation
-        // is the last block's diagonal inverse and p2 instead of its whole row block.
-        static const int esplit_env = MXF_KNOB("MXF_POTRF_EAGER_SPLIT", 1);
-        const bool esplit = esplit_env && !rows2_env;
-        auto fires_at = [&](int64_t pe_) {
-            const bool it_ = tail_env > 0 && eager_env < 100 && tbw < rbw && pe_ > tail0;
-            return it_ ? ((pe_ - tail0) % tbw == 0 || pe_ == n) : (pe_ % rbw == 0 || pe_ == n);
-        };
-        if (eager && fire) {
-            const int64_t rb0 = in_tail ? tail0 + (pe - tail0 - 1) / tbw * tbw : (pe - 1) / rbw * rbw;
+        auto fires_at = [&](int64_t pe_) { return pe_ % rbw == 0 || pe_ == n; };
+        // r06: the row block's pieces separately (trtri_row_block_p1 / _p2).  When block b's panels end, its diagonal inverse goes to the third
+        // auxiliary stream, its p2 follows on the inverse stream, and p1 of block b + 1 -- whose inputs are complete at this point, four panels
+        // before that block is factored -- is queued right behind.  What is left behind the factorisation is the last block's diagonal inverse
+        // and p2 instead of its whole row block.
+        if (eager && fires_at(pe)) {
+            const int64_t rb0 = (pe - 1) / rbw * rbw;
             MXF_HIP(h, hipEventRecord(h->ev_pi, st));
             if constexpr (sizeof(T) == 8) {
-                if (esplit) {
-                    hipStream_t qd = h->potrf_rows, qp = h->potrf_inv;
-                    MXF_HIP(h, hipStreamWaitEvent(qd, h->ev_pi, 0));
-                    int rc = trtri_typed<T>(h, dtype, 1, pe - rb0, A + rb0 * (lda + 1), lda, 0, Ie + rb0 * (ldie + 1), ldie, 0, qd);
-                    if (rc) return rc;
-                    MXF_HIP(h, hipEventRecord(h->ev_pc, qd));
-                    MXF_HIP(h, hipStreamWaitEvent(qp, h->ev_pc, 0));       // (block 0: p1 of block 1 reads this inverse)
-                    if (rb0 > 0) { rc = trtri_row_block_p2<T>(h, dtype, rb0, pe, Ie, ldie, qp); if (rc) return rc; }
-                    if (kacc) {
-                        // rows [rb0, pe) of L^-1 are final (columns < pe; zero beyond): their share of kcoef L^-T L^-1, on a stream of its own so
-                        // that the next block's p1 is not held up behind it (the shares update the same tiles: one stream keeps them in order)
-                        MXF_HIP(h, hipEventRecord(h->ev_pq, qp));
-                        MXF_HIP(h, hipStreamWaitEvent(h->potrf_acc, h->ev_pq, 0));
-                        rc = mxf_gemm_internal(h, dtype, 1, 0, pe, pe, pe - rb0, kcoef, Ie + rb0 * ldie, ldie, 0, Ie + rb0 * ldie, ldie, 0, 1.0, Kacc, ldk, 0,
-                                               1, 1, h->potrf_acc, 0, 0);
-                        if (rc) return rc;
-                    }
-                    if (pe < n) {
-                        MXF_HIP(h, hipStreamWaitEvent(qp, h->ev_pi, 0));   // the rows below the panel that just ended
-                        int64_t ne = pe + NBO;                           // the end of the next row block = the next firing point
-                        while (ne < n && !fires_at(ne)) ne += NBO;
-                        if (ne > n) ne = n;
-                        rc = trtri_row_block_p1<T>(h, dtype, pe, ne, A, lda, Ie, ldie, qp);
-                        if (rc) return rc;
-                    }
-                } else {
-                    MXF_HIP(h, hipStreamWaitEvent(h->potrf_inv, h->ev_pi, 0));
-                    int rc = trtri_row_block<T>(h, dtype, rb0, pe, A, lda, Ie, ldie, h->potrf_inv);
+                hipStream_t qd = h->potrf_rows, qp = h->potrf_inv;
+                MXF_HIP(h, hipStreamWaitEvent(qd, h->ev_pi, 0));
+                int rc = trtri_typed<T>(h, dtype, 1, pe - rb0, A + rb0 * (lda + 1), lda, 0, Ie + rb0 * (ldie + 1), ldie, 0, qd);
+                if (rc) return rc;
+                MXF_HIP(h, hipEventRecord(h->ev_pc, qd));
+                MXF_HIP(h, hipStreamWaitEvent(qp, h->ev_pc, 0));       // (block 0: p1 of block 1 reads this inverse)
+                if (rb0 > 0) { rc = trtri_row_block_p2<T>(h, dtype, rb0, pe, Ie, ldie, qp); if (rc) return rc; }
+                if (pe < n) {
+                    MXF_HIP(h, hipStreamWaitEvent(qp, h->ev_pi, 0));   // the rows below the panel that just ended
+                    int64_t ne = pe + NBO;                           // the end of the next row block = the next firing point
+                    while (ne < n && !fires_at(ne)) ne += NBO;
+                    if (ne > n) ne = n;
+                    rc = trtri_row_block_p1<T>(h, dtype, pe, ne, A, lda, Ie, ldie, qp);
                     if (rc) return rc;
                 }
             }
@@ -1137,12 +1036,7 @@ int potrf_typed(mxf_ctx* h, int dtype, int S, int64_t n, T* A, int64_t lda, int6
         if (pe < n) {   // trailing update, lower blocks only: A22 -= L21 L21^T with K = panel width
             const int64_t pe2 = (pe + NBO < n) ? pe + NBO : n, K = pe - c0;
             if (pending_b) { MXF_HIP(h, hipStreamWaitEvent(st, h->ev_pb, 0)); pending_b = false; }   // the previous rest-update touched these columns
-            // the far rows of this panel (potrf_rows stream): every product below except the next diagonal block's head update reads them
-            const bool far_rows = pending_r;
-            if (far_rows) MXF_HIP(h, hipStreamWaitEvent(ax, h->ev_rb, 0));
-            pending_r = false;
             if (!look || pe2 >= n) {
-                if (far_rows) MXF_HIP(h, hipStreamWaitEvent(st, h->ev_rb, 0));
                 int rc = mxf_gemm_internal(h, dtype, 0, 1, n - pe, n - pe, K, -1.0, A + pe * lda + c0, lda, sA,
                                            A + pe * lda + c0, lda, sA, 1.0, A + pe * lda + pe, lda, sA, S, 1, st);
                 if (rc) return rc;
@@ -1150,7 +1044,7 @@ int potrf_typed(mxf_ctx* h, int dtype, int S, int64_t n, T* A, int64_t lda, int6
                 // r03: when the NEXT panel takes the split form, only its diagonal block (what its chain launch reads) is updated on the caller's
                 // stream; the rows below it -- read by potrf_rows_kernel only, 0.2 ms later -- are updated on the auxiliary stream next to that
                 // chain (0.09 ms per panel off the serial path at n = 8192)
-                const bool head_aux = head_split_env && sizeof(T) == 8 && rows_env_g && is_split(pe);
+                const bool head_aux = sizeof(T) == 8 && is_split(pe);
                 if (look_env != 2 || head_aux) MXF_HIP(h, hipEventRecord(h->ev_pa, st));  // the panel's columns (L21) are final
                 // next outer panel's columns: its diagonal block (lower) and the rows below it
                 int rc = mxf_gemm_internal(h, dtype, 0, 1, pe2 - pe, pe2 - pe, K, -1.0, A + pe * lda + c0, lda, sA,
@@ -1164,7 +1058,6 @@ int potrf_typed(mxf_ctx* h, int dtype, int S, int64_t n, T* A, int64_t lda, int6
                     MXF_HIP(h, hipEventRecord(h->ev_ph, ax));
                     pending_h = true;
                 } else {
-                    if (far_rows) MXF_HIP(h, hipStreamWaitEvent(st, h->ev_rb, 0));
                     rc = mxf_gemm_internal(h, dtype, 0, 1, n - pe2, pe2 - pe, K, -1.0, A + pe2 * lda + c0, lda, sA,
                                            A + pe * lda + c0, lda, sA, 1.0, A + pe2 * lda + pe, lda, sA, S, 0, st);
                     if (rc) return rc;
@@ -1185,21 +1078,11 @@ int potrf_typed(mxf_ctx* h, int dtype, int S, int64_t n, T* A, int64_t lda, int6
         MXF_HIP(h, hipStreamWaitEvent(st, h->ev_pj, 0));
         if (eager_done) *eager_done = true;
     }
-    if (kacc) {
-        MXF_HIP(h, hipEventRecord(h->ev_pz, h->potrf_acc));
-        MXF_HIP(h, hipStreamWaitEvent(st, h->ev_pz, 0));
-        if (kacc_done) *kacc_done = true;
-    }
-    if (pending_r) MXF_HIP(h, hipStreamWaitEvent(st, h->ev_rb, 0));
     if (pending_b) MXF_HIP(h, hipStreamWaitEvent(st, h->ev_pb, 0));
     if (pending_h) MXF_HIP(h, hipStreamWaitEvent(st, h->ev_ph, 0));      // (never pending here today: the last panel has no successor; kept so that the caller's stream always joins the auxiliary one)
     if (n > 1 && zero_upper) {      // (internal callers that only ever read the lower triangle skip this pass)
         if (n > 65535) MXF_FAIL(h, -3, "mxf_potrf: n too large");
         hipLaunchKernelGGL((zero_upper_kernel<T>), dim3((unsigned)((n + 255) / 256), (unsigned)n, S), dim3(256), 0, st, A, n, lda, sA);
-    }
-    if (own_chain) {
-        MXF_HIP(h, hipEventRecord(h->ev_pk, st));
-        MXF_HIP(h, hipStreamWaitEvent(st_user, h->ev_pk, 0));
     }
     MXF_LAUNCH_CHECK(h);
     return 0;
@@ -1244,13 +1127,11 @@ int trsm_typed(mxf_ctx* h, int dtype, int transpose, int S, int64_t n, int64_t n
 }  // namespace
 
 int mxf_potrf_internal(mxf_ctx* h, int dtype, int S, int64_t n, void* A, int64_t lda, int64_t sA, int* info, hipStream_t st, bool zero_upper, bool zero_info,
-                       void* Linv_eager, int64_t ldie, bool* eager_done, void* Kacc, int64_t ldk, double kcoef, bool* kacc_done) {
+                       void* Linv_eager, int64_t ldie, bool* eager_done) {
     if (eager_done) *eager_done = false;
-    if (kacc_done) *kacc_done = false;
     if (n <= 0 || S <= 0) return 0;
     if (dtype == MXF_F32) return potrf_typed<float>(h, dtype, S, n, (float*)A, lda, sA, info, st, zero_upper, zero_info);
-    if (dtype == MXF_F64) return potrf_typed<double>(h, dtype, S, n, (double*)A, lda, sA, info, st, zero_upper, zero_info, (double*)Linv_eager, ldie, eager_done,
-                                                     (double*)Kacc, ldk, kcoef, kacc_done);
+    if (dtype == MXF_F64) return potrf_typed<double>(h, dtype, S, n, (double*)A, lda, sA, info, st, zero_upper, zero_info, (double*)Linv_eager, ldie, eager_done);
     MXF_FAIL(h, -2, "mxf_potrf: bad dtype %d", dtype);
 }
 

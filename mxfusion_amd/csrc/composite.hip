@@ -312,16 +312,12 @@ int gp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t N, int Q, in
     const bool via_inverse = want_grad && N >= 2048;
     if (via_inverse) Linv = cv.take<T>((size_t)S * NN);
     // (r06) one matrix, few right-hand sides: the two skinny products with L^-1 as triangular streaming reads, 1/2 alpha alpha^T folded into
-    // the symmetrisation of dK (MXF_GP_TRI_SKINNY, probe builds)
-    static const int tri_skinny_env = (int)MXF_KNOB("MXF_GP_TRI_SKINNY", 1);
-    const bool tri_skinny = via_inverse && S == 1 && P <= 8 && tri_skinny_env != 0;
+    // the symmetrisation of dK
+    const bool tri_skinny = via_inverse && S == 1 && P <= 8;
     // (r05) float64, one matrix: the factorisation forms L^-1 itself, row block by row block on a third stream next to its serial chain
-    // (r06) ... and -P/2 L^-T L^-1, the bulk of dlogL/dK, is accumulated row block by row block of that inverse as well (the chip is half idle
-    // under the factorisation's serial chain; behind it only the last row block's share is left)
-    bool inv_done = false, kacc_done = false;
-    T* dK_early = (tri_skinny && sizeof(T) == 8) ? cv.take<T>((size_t)S * NN) : nullptr;
-    rc = mxf_potrf_internal(h, dtype, S, N, L, N, NN, info, st, true, true, (via_inverse && S == 1 && sizeof(T) == 8) ? (void*)Linv : nullptr, N, &inv_done,
-                            dK_early, N, -0.5 * P, &kacc_done);   // :61
+    bool inv_done = false;
+    rc = mxf_potrf_internal(h, dtype, S, N, L, N, NN, info, st, true, true, (via_inverse && S == 1 && sizeof(T) == 8) ? (void*)Linv : nullptr, N,
+                            &inv_done);   // :61
     if (rc) return rc;
     if (via_inverse) {
         if (!inv_done) rc = mxf_trtri_internal(h, dtype, S, N, L, N, NN, Linv, N, NN, st);
@@ -349,23 +345,15 @@ int gp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t N, int Q, in
         rc = mxf_trtri_internal(h, dtype, S, N, L, N, NN, Linv, N, NN, st);
         if (rc) return rc;
     }
-    T* dK = dK_early ? dK_early : cv.take<T>((size_t)S * NN);
-    // (r06, probe knob, off) one matrix, Q <= 16: dK stays a LOWER triangle (no mirror pass) and the Gram's reverse pass walks the lower pairs only, twice
-    // each, with both sides.  Correct (exact-GP tests pass with it), not faster: MAP step 13.71-13.75 ms without, 13.74-13.77 with -- half the pairs, but the
-    // row side is back and the early row bands' blocks leave the chip half empty.
-    static const int lower_bwd_env = (int)MXF_KNOB("MXF_GP_LOWER_BWD", 0);
-    const bool lower_bwd = lower_bwd_env && tri_skinny && Q <= 16;
+    T* dK = cv.take<T>((size_t)S * NN);
     T* alpha = cv.take<T>((size_t)S * NP);
     if (tri_skinny) {
         MXF_HIP(h, hipMemsetAsync(alpha, 0, sizeof(T) * NP, st));
         hipLaunchKernelGGL((trmv_lower_t_kernel<T>), dim3((unsigned)((N + 255) / 256), (unsigned)((N + 127) / 128)), dim3(256), 0, st, N, P, (const T*)Linv, N,
                            (const T*)LinvY, alpha);                                                                 // alpha = Linv^T LinvY
-        if (!kacc_done) {
         rc = mxf_gemm_internal(h, dtype, 1, 0, N, N, N, -0.5 * P, Linv, N, NN, Linv, N, NN, 0.0, dK, N, NN, S, 1, st, 0, 1);
         if (rc) return rc;
-        }
-        hipLaunchKernelGGL((symmetrize_rankp_kernel<T>), dim3((unsigned)((N + 31) / 32), (unsigned)((N + 31) / 32)), dim3(256), 0, st, dK, N, N, (const T*)alpha, P, (T)0.5,
-                           lower_bwd ? 0 : 1);
+        hipLaunchKernelGGL((symmetrize_rankp_kernel<T>), dim3((unsigned)((N + 31) / 32), (unsigned)((N + 31) / 32)), dim3(256), 0, st, dK, N, N, (const T*)alpha, P, (T)0.5);
     } else {
     rc = mxf_gemm_internal(h, dtype, 1, 0, N, P, N, 1.0, Linv, N, NN, LinvY, P, NP, 0.0, alpha, P, NP, S, 0, st);   // alpha = Linv^T LinvY
     if (rc) return rc;
@@ -387,7 +375,7 @@ int gp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t N, int Q, in
         rc = mxf_gram_bwd_internal(h, kind, dtype, 1, N, N, Q, X + (int64_t)s * sX, 0, nullptr, 0, ls + (int64_t)s * sls, ard, 0,
                                    var + (int64_t)s * svar, 0, dK + (int64_t)s * NN, N, NN,
                                    dX ? dX + (int64_t)s * N * Q : nullptr, nullptr, dls ? dls + (int64_t)s * lsn : nullptr,
-                                   dvar ? dvar + s : nullptr, st, lower_bwd ? 2 : 1 /* dK was symmetrised above, or only its lower triangle is read */);
+                                   dvar ? dvar + s : nullptr, st, 1 /* dK was symmetrised above */);
         if (rc) return rc;
     }
     MXF_LAUNCH_CHECK(h);
@@ -948,11 +936,8 @@ int svgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t B, int64_t
     // register-tiled fused reverse pass does not cover (gram_bwd.hip: generic kernel)
     // r04: per-row noise (B, 1) with one output column on the float32 split path runs the STREAMING form (het_* kernels above); every other
     // heteroscedastic shape keeps the generic (materialised dKuf) path
-    static const int het_stream_env = MXF_KNOB("MXF_SVGP_HET_STREAM", 1);
-    // float32 streaming: the two big GEMMs run on the 16-bit matrix pipe from split planes of their operands (gemm_split.hip)
-    static const int split_env = MXF_KNOB("MXF_SVGP_SPLIT", 1);
     const int64_t SBh = ((sX == 0) ? (int64_t)1 : (int64_t)S) * B;
-    const bool het_stream = (het_stream_env != 0) && (split_env != 0) && sizeof(T) == 4 && want_grad && nrows == B && nrows > 1 && ncols == 1 && P == 1 && !use_mat && !ysamp && Q <= 8 &&
+    const bool het_stream = sizeof(T) == 4 && want_grad && nrows == B && nrows > 1 && ncols == 1 && P == 1 && !use_mat && !ysamp && Q <= 8 &&
                             (B % 16 == 0) && (M % 16 == 0) && M >= 128 && h->svgp_form == MXF_SVGP_EXPLICIT && mxf_svgp_bwd_is_mfma(kind, dtype, SBh, B, Q, P, X);
     const bool het = (nrows > 1 || ncols > 1 || use_mat || ysamp || Q > 16) && !het_stream;
     if (sX != 0 && sX != B * Q) MXF_FAIL(h, -2, "mxf_svgp_logpdf: X samples must be contiguous");
@@ -971,16 +956,17 @@ int svgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t B, int64_t
     acc(MP, 8); acc(16, 8); acc(2 * (size_t)S, 8); acc(8, sizeof(int));
     acc((size_t)(M + P) * M, sizeof(T)); acc(MP, sizeof(T));
     acc((size_t)(M + P) * SB, sizeof(T)); acc((size_t)SB, sizeof(T));
-    const bool use_split = split_env && want_grad && sizeof(T) == 4 && !het && (SB % 16 == 0) && (M % 16 == 0) && M >= 128 && Q <= 16;
-    // operand format of the split GEMMs: two scaled f16 terms / three products (default) or three bf16 terms / six products
-    static const int split_mode = MXF_KNOB("MXF_SPLIT_BF16X3", 0) ? MXF_SPLIT_BF16X3 : MXF_SPLIT_F16X2;
-    const float split_ga = split_mode == MXF_SPLIT_F16X2 ? (1.f / 16384.f) : 1.f;     // Gram planes hold k / variance * 2^14 in the f16x2 format
-    const float* split_var = split_mode == MXF_SPLIT_F16X2 ? (const float*)var : nullptr;
+    // float32 streaming: the two big GEMMs run on the 16-bit matrix pipe from split planes of their operands (gemm_split.hip), in the format
+    // of two scaled f16 terms (three products)
+    const bool use_split = want_grad && sizeof(T) == 4 && !het && (SB % 16 == 0) && (M % 16 == 0) && M >= 128 && Q <= 16;
+    constexpr int split_mode = MXF_SPLIT_F16X2;
+    const float split_ga = 1.f / 16384.f;     // Gram planes hold k / variance * 2^14 in the f16x2 format
+    const float* split_var = (const float*)var;
     const size_t pl_big = mxf_split_plane_elems(M, SB), pl_h0 = mxf_split_plane_elems(M, M);     // == mxf_split_plane_elems(SB, M)
     const size_t gp_scr = use_split ? mxf_gram_planes_scratch_bytes(SB, SB, Q) : 0;      // upper bound for either orientation
     // float32 streaming form (mxf_svgp_configure): the whitened tier runs on the f16x2 split kernels' wide forms only
     const bool whiten = sizeof(T) == 4 && want_grad && h->svgp_form == MXF_SVGP_WHITENED;
-    if (whiten && !(use_split && split_mode == MXF_SPLIT_F16X2 && (M % 128) == 0 && (SB % 256) == 0))
+    if (whiten && !(use_split && (M % 128) == 0 && (SB % 256) == 0))
         MXF_FAIL(h, -3, "mxf_svgp_logpdf: the whitened float32 form needs M %% 128 == 0, S B %% 256 == 0, Q <= 16, homoscedastic noise (see mxf_svgp_whitened_ok)");
     // (each branch mirrors one carve below, in the same order)
     if (use_split) { acc(3 * pl_big, 2); acc(3 * pl_h0, 2); acc(3 * pl_big, 2); acc(gp_scr, 1); acc(gp_scr, 1); }
@@ -989,19 +975,17 @@ int svgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t B, int64_t
     // r06: ONE set of Kuf planes.  T = H0 Kuf reads the planes Psi2 reads (operand (m, k = n)) through gemm_bt.hip's transposing LDS read, and
     // forms the row U = w^T Kuf on the way: the second planes pass (8.6 GB written between the two products, 1.8 ms of the 24 ms step with the
     // matrix pipe idle) and its 8.6 GB buffer are gone.  Needs the explicit float32 form, one output column, whole 256 x 256 tiles.
-    static const int bt_env = (int)MXF_KNOB("MXF_SVGP_BT", 1);
-    const bool bt_path = bt_env && use_split && !whiten && !het_stream && P == 1 && split_mode == MXF_SPLIT_F16X2 && M <= 2048 && mxf_gemm_bt_ok(M, SB, M);
+    const bool bt_path = use_split && !whiten && !het_stream && P == 1 && M <= 2048 && mxf_gemm_bt_ok(M, SB, M);
     // the whitened tier likewise: T = Hh V reads the planes of V that Phi = V V^T reads (the V product's planes output IS the K-major layout),
     // and forms U = a^T V on the way -- the V product no longer writes the planes of V^T (8.6 GB, its "second output") nor the partial sums of U
-    const bool bt_wh = bt_env && whiten && P == 1 && M <= 2048 && mxf_gemm_bt_ok(M, SB, M);
+    const bool bt_wh = whiten && P == 1 && M <= 2048 && mxf_gemm_bt_ok(M, SB, M);
     if (bt_path || bt_wh) acc(2 * (size_t)M + 8, 2);
     if (het_stream) { acc(B, 4); acc(B, 4); acc((size_t)(sY == 0 ? B : SB), 4); acc(4, 8); acc(S, 8); acc(4, 4); }
     // r06: the generic (materialised-Gram / heteroscedastic) float32 path's two big products on the f16 matrix pipe as well: T = H0 Kuf through the
     // K-major product from the planes of Kuf (split from the float32 Gram: one maxabs + one split pass, 0.17 ms at 512 x 131 072), and
     // G' = Ksc Kuf^T from the planes of Ksc and the same Kuf planes -- f32-equivalent like the streaming path's products (three f16 products, f32
     // accumulation) where the generic kernel ran true-f32 MFMAs at 100 TF: the deep GP's first layer 0.68 + 0.66 ms -> planes 0.35 + products 0.3.
-    static const int het_split_env = (int)MXF_KNOB("MXF_SVGP_HET_SPLIT", 1);
-    const bool het_split = het_split_env && het && sizeof(T) == 4 && want_grad && split_env && split_mode == MXF_SPLIT_F16X2 && mxf_gemm_bt_ok(M, SB, M) &&
+    const bool het_split = het && sizeof(T) == 4 && want_grad && mxf_gemm_bt_ok(M, SB, M) &&
                            (int64_t)M * SB >= (int64_t)1 << 24;
     if (het_split) { acc(2 * pl_h0, 2); acc(2 * pl_big, 2); acc(2 * pl_big, 2); acc(4, sizeof(unsigned)); }
     if (want_grad) { acc(MM, sizeof(T)); acc(MP, sizeof(T)); acc((size_t)SB * P, sizeof(T)); for (int i = 0; i < 6; ++i) acc(MM, 8); acc(MP, 8); acc(MP, 8); acc(M * Q, 8); acc(lsn, 8); acc(4, 8); }
@@ -1135,17 +1119,12 @@ int svgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t B, int64_t
         // whitened tier: only the Kfu planes (operand (n, k = m) of V = L^-1 Kuf); they need nothing from the core, so they are written
         // first; V, its transposition (+ U = a^T V) and Phi = V V^T follow on this stream once L^-1 exists (below, after the Kuu chain
         // has been queued)
-        // (r05 probe knob MXF_SVGP_WH_DEFER = 1 / 2: the pass held back until potrf(Kuu) / trtri(Kuu) has finished -- in this form the Kuu chain is a
-        //  serial prefix of everything, and next to the planes pass its float64 workgroups wait for CUs: a 60 us GEMM inside potrf took 1.26 ms)
-        static const int wh_defer = (int)MXF_KNOB("MXF_SVGP_WH_DEFER", 0);
-        if (!wh_defer) {
         MXF_T0(h, MXF_T_PLANES_A, sd_);
         rc = mxf_gram_planes_internal(h, kind, SB, M, Q, (const float*)X, (const float*)Z, (const float*)ls, ard, (const float*)var, plKfu,
                                       (int64_t)pl_big, gscr1, sd_, split_mode);
         if (rc) return rc;
         MXF_T1(h, MXF_T_PLANES_A, sd_);
         MXF_STAGE(h, "Kfu planes (sd)", sd_);
-        }
     } else if (use_split) {
         // float32 training step: the Grams are written directly as split planes (two scaled f16 terms = 4 bytes per element, never as f32):
         // Kuf planes (operand (m, k = n)) feed Psi2 and come first so that Psi2 (MFMA bound) starts early; the Kfu planes (operand
@@ -1183,12 +1162,11 @@ int svgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t B, int64_t
         MXF_T0(h, MXF_T_PSI2, sd_);
         if (use_split) {
             if (KA > 0) {
-                // 3 workgroups of the three-term kernel fit a CU: (256 - 184) * 3 = 216 workgroups = one per CU on 216 CUs; the two-term
-                // kernel fits 4: (256 - 202) * 4 = 216.  r06, one-planes path: (256 - 214) * 4 = 168 workgroups -- with the second planes pass
+                // 4 workgroups of the two-term kernel fit a CU: (256 - 202) * 4 = 216 workgroups = one per CU on 216 CUs.  r06, one-planes path: (256 - 214) * 4 = 168 workgroups -- with the second planes pass
                 // gone the chains are alone on what Psi2 leaves, and 88 CUs serve the few-sample step better than 40 (same box, 4 samples:
                 // 4.30 -> 4.21 ms; 210: 4.25-4.32, 218: 4.22-4.26, 224: 4.27; configs[3] at 4 samples 2.41 -> 2.37)
                 rc = mxf_gemm_split_internal(h, M, M, KA, (double)split_ga * split_ga, plKuf, (int64_t)pl_big, plKuf, (int64_t)pl_big, 0.0, (float*)Psi2, M, 1, sd_,
-                                             psi2_ra_env ? psi2_ra : (split_mode == MXF_SPLIT_F16X2 ? (bt_path ? 214 : 202) : 184), split_mode, split_var, 2, nullptr);
+                                             psi2_ra_env ? psi2_ra : (bt_path ? 214 : 202), split_mode, split_var, 2, nullptr);
                 if (rc) return rc;
             }
             if (KA < SB) {
@@ -1217,54 +1195,19 @@ int svgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t B, int64_t
     }
     // ---- main stream: Kuu -> L -> L^-1 -> Ki, w (the critical path up to the T GEMM) --------------------------------------------
     // condition number of Kuu + jitter I (1-norm), for the float32 validity check of mxf_svgp_last_cond: |Kuu|_1 here, |Ki|_1 below
-    // r06 probe knob MXF_SVGP_CHAIN_LATE (one-planes path, many samples): the Kuu chain (2: the Su chain too) starts only when the planes pass is
-    // done.  A profiler timeline shows the planes pass at 2.17 instead of 1.7 ms next to the chains -- without the profiler it takes 1.79 ms
-    // either way and the step does not move (same box: 22.60-22.69 / 22.66-22.77 / 22.60-22.70 ms for 0 / 1 / 2).  Off.
-    static const int chain_late = (int)MXF_KNOB("MXF_SVGP_CHAIN_LATE", 0);
-    const bool late = chain_late && bt_path && want_grad && SB > 2 * 192 * M;
-    if (late) MXF_HIP(h, hipStreamWaitEvent(st, h->ev_aux, 0));
-    // r06 (MXF_SVGP_OFFPATH, default on): what the T product does not need leaves the caller's stream -- the two condition norms (64 workgroups walking
-    // 16 rows each: 0.05 ms alone, 0.22 ms in front of the factorisation while the planes pass holds every CU), mu.w, tr(Ki Su), log|Kuu| go to
-    // the second side stream; w = Ki mu is a one-wave-per-row kernel.  Kuu is copied for its norm (the factorisation works in place).
-    static const int offpath_env = (int)MXF_KNOB("MXF_SVGP_OFFPATH", 1);
-    const bool offpath = offpath_env != 0;
-    if (offpath) {
-        hipLaunchKernelGGL((convert_kernel<D, D>), dim3(gridn(MM)), dim3(256), 0, st, (int64_t)1, MM, (const D*)Lm, MM, Sui, MM);     // (Su^-1's buffer: written at the end of the Su chain, on the same stream as the norm)
-        MXF_HIP(h, hipEventRecord(h->ev_k1, st));
-        MXF_HIP(h, hipStreamWaitEvent(s2_, h->ev_k1, 0));
-        hipLaunchKernelGGL(norm1_sym16_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, s2_, M, (const double*)Sui, M, h->cond_dev);
-    } else
-    hipLaunchKernelGGL(norm1_sym16_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, st, M, (const double*)Lm, M, h->cond_dev);
+    // r06: what the T product does not need leaves the caller's stream -- the two condition norms (64 workgroups walking 16 rows each: 0.05 ms
+    // alone, 0.22 ms in front of the factorisation while the planes pass holds every CU), mu.w, tr(Ki Su), log|Kuu| go to the second side
+    // stream; w = Ki mu is a one-wave-per-row kernel.  Kuu is copied for its norm (the factorisation works in place).
+    hipLaunchKernelGGL((convert_kernel<D, D>), dim3(gridn(MM)), dim3(256), 0, st, (int64_t)1, MM, (const D*)Lm, MM, Sui, MM);     // (Su^-1's buffer: written at the end of the Su chain, on the same stream as the norm)
+    MXF_HIP(h, hipEventRecord(h->ev_k1, st));
+    MXF_HIP(h, hipStreamWaitEvent(s2_, h->ev_k1, 0));
+    hipLaunchKernelGGL(norm1_sym16_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, s2_, M, (const double*)Sui, M, h->cond_dev);
     rc = mxf_potrf_internal(h, MXF_F64, 1, M, Lm, M, MM, info, st, false, false);                     // L :83 (trtri / sumlogdiag read the lower triangle only)
     if (rc) return rc;
     MXF_STAGE(h, "potrf Kuu", st);
-    static const int wh_defer2 = (int)MXF_KNOB("MXF_SVGP_WH_DEFER", 0);
-    auto deferred_planes = [&]() -> int {        // (probe knob, see above)
-        MXF_HIP(h, hipEventRecord(h->ev_join2, st));
-        MXF_HIP(h, hipStreamWaitEvent(sd_, h->ev_join2, 0));
-        MXF_T0(h, MXF_T_PLANES_A, sd_);
-        int r_ = mxf_gram_planes_internal(h, kind, SB, M, Q, (const float*)X, (const float*)Z, (const float*)ls, ard, (const float*)var, plKfu,
-                                          (int64_t)pl_big, gscr1, sd_, split_mode);
-        MXF_T1(h, MXF_T_PLANES_A, sd_);
-        return r_;
-    };
-    if (whiten && wh_defer2 == 1) { rc = deferred_planes(); if (rc) return rc; }
     rc = mxf_trtri_internal(h, MXF_F64, 1, M, Lm, M, MM, Linv, M, MM, st);
     if (rc) return rc;
     MXF_STAGE(h, "trtri Kuu", st);
-    if (whiten && wh_defer2 == 2) { rc = deferred_planes(); if (rc) return rc; }
-    static const int phi_late_env = (int)MXF_KNOB("MXF_SVGP_WH_PHI_LATE", 0);
-    const bool phi_late = phi_late_env && whiten && bt_wh && want_grad && !het && SB <= 2 * 192 * M;
-    auto launch_phi = [&](bool few_) -> int {
-        MXF_T0(h, MXF_T_PSI2, sd_);
-        int r_ = mxf_gemm_split_internal(h, M, M, SB, (double)split_ga * split_ga, plKuf, (int64_t)pl_big, plKuf, (int64_t)pl_big, 0.0, (float*)Psi2, M, 1, sd_,
-                                         few_ ? 202 : psi2_rb, split_mode, split_var, 1, nullptr);
-        if (r_) return r_;
-        hipLaunchKernelGGL((symmetrize_kernel<T>), dim3((unsigned)((M + 31) / 32), (unsigned)((M + 31) / 32), 1), dim3(256), 0, sd_, Psi2, M, M, MM);
-        MXF_T1(h, MXF_T_PSI2, sd_);
-        MXF_STAGE(h, "Phi (sd)", sd_);
-        return 0;
-    };
     unsigned* limax = (unsigned*)(info2 + 4);           // bit pattern of max |L^-1| (whitened tier; word cleared by svgp_init_kernel)
     if (whiten) {
         // L^-1 as f16x2 planes (the A operand of V = L^-1 Kuf); Aext is free until Hh is formed
@@ -1275,11 +1218,7 @@ int svgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t B, int64_t
         if (rc) return rc;
         // a = L^-1 mu (float64, then the streaming dtype): the V product's epilogue forms U = a^T V from it
         MXF_HIP(h, hipStreamWaitEvent(st, h->ev_su, 0));                                              // mu (second side stream)
-        if (offpath) hipLaunchKernelGGL((trmv_lower_kernel<D>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, M, P, (const D*)Linv, M, (const D*)mud, (int64_t)P, ad);
-        else {
-        rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, P, M, 1.0, Linv, M, 0, mud, P, 0, 0.0, ad, P, 0, 1, 0, st);
-        if (rc) return rc;
-        }
+        hipLaunchKernelGGL((trmv_lower_kernel<D>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, M, P, (const D*)Linv, M, (const D*)mud, (int64_t)P, ad);
         hipLaunchKernelGGL((convert_kernel<D, T>), dim3(gridn(MP)), dim3(256), 0, st, (int64_t)1, MP, (const D*)ad, MP, aT, MP);
         MXF_HIP(h, hipEventRecord(h->ev_aux2, st));                                                   // L^-1 planes and a ready
         // side stream: V = L^-1 Kuf, written as the planes of the (m, k = n) operand holding V / sigma * 2^14 (|v_n|^2 <= k_nn = sigma^2):
@@ -1309,37 +1248,32 @@ int svgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t B, int64_t
         MXF_T1(h, MXF_T_PLANES_B, sd_);
         MXF_HIP(h, hipEventRecord(h->ev_aux, sd_));      // V^T planes and U ready: the T GEMM / the reverse pass wait for it
         // Phi = V V^T (lower tiles, split-K) = sigma^2 2^-28 (planes)(planes)^T
-        // r06 probe knob MXF_SVGP_WH_PHI_LATE, few samples per GPU: Phi is enqueued BEHIND the T product (launch_phi above) -- T is on the
-        // critical path (the reverse pass needs it), Phi only feeds the core's reverse mode in the tail.  Measured, same box, 4 samples at
-        // trained-like parameters: 6.14-6.17 ms with it against 6.04 -- Phi then runs next to the latency-bound reverse pass and the tail waits
-        // for it; whitened parity tests pass either way.  Off.
-        if (!phi_late) { rc = launch_phi(few); if (rc) return rc; }
+        MXF_T0(h, MXF_T_PSI2, sd_);
+        rc = mxf_gemm_split_internal(h, M, M, SB, (double)split_ga * split_ga, plKuf, (int64_t)pl_big, plKuf, (int64_t)pl_big, 0.0, (float*)Psi2, M, 1, sd_,
+                                     few ? 202 : psi2_rb, split_mode, split_var, 1, nullptr);
+        if (rc) return rc;
+        hipLaunchKernelGGL((symmetrize_kernel<T>), dim3((unsigned)((M + 31) / 32), (unsigned)((M + 31) / 32), 1), dim3(256), 0, sd_, Psi2, M, M, MM);
+        MXF_T1(h, MXF_T_PSI2, sd_);
+        MXF_STAGE(h, "Phi (sd)", sd_);
     }
-    // r06 (MXF_SVGP_SYM_LOWER): the symmetric products of the chain -- Ki here, H0 below -- as lower tiles + mirror (half the work of a product that
-    // runs on the 88 CUs Psi2 leaves in the few-sample regime; the results become exactly symmetric)
-    static const int symlow_env = (int)MXF_KNOB("MXF_SVGP_SYM_LOWER", 1);
-    // (float32 mode only: the float64 path is the parity path and stays operation for operation what the trajectory tests were recorded with --
-    //  tests/test_svgp_notebook.py's 100-epoch float64 run moved its learned noise by 12 % with exactly symmetric Ki / H0, past its 10 % band)
-    const int symlow = (symlow_env && sizeof(T) == 4) ? 1 : 0;
+    // r06, float32 mode: the symmetric products of the core -- Ki here, H0 and X = Ki G Ki below -- as lower tiles + mirror (half the work of a
+    // product that runs on the 88 CUs Psi2 leaves in the few-sample regime; the results become exactly symmetric), and the core's reverse mode in
+    // the X form.  dKuu then comes out exactly symmetric, and its Gram reverse pass skips the row side (dk_symmetric): one condition for both.
+    // (The float64 path is the parity path and stays operation for operation what the trajectory tests were recorded with --
+    //  tests/test_svgp_notebook.py's 100-epoch float64 run moved its learned noise by 12 % with exactly symmetric Ki / H0, past its 10 % band.)
+    constexpr bool sym_core = sizeof(T) == 4;
+    const int symlow = sym_core ? 1 : 0;
     rc = mxf_gemm_internal(h, MXF_F64, 1, 0, M, M, M, 1.0, Linv, M, 0, Linv, M, 0, 0.0, Ki, M, 0, 1, symlow, st);   // Ki = Linv^T Linv
     if (rc) return rc;
     if (symlow) hipLaunchKernelGGL((symmetrize_kernel<D>), dim3((unsigned)((M + 31) / 32), (unsigned)((M + 31) / 32), 1), dim3(256), 0, st, Ki, M, M, MM);
-    if (!offpath) hipLaunchKernelGGL(norm1_sym16_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, st, M, (const double*)Ki, M, h->cond_dev + 1);
     MXF_HIP(h, hipStreamWaitEvent(st, h->ev_su, 0));                                                  // Su, mu, noise, accumulators (second side stream)
-    if (offpath) hipLaunchKernelGGL((gemv_rows_kernel<D>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, M, P, (const D*)Ki, M, (const D*)mud, (int64_t)P, wd);   // w = Ki mu
-    else {
-    rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, P, M, 1.0, Ki, M, 0, mud, P, 0, 0.0, wd, P, 0, 1, 0, st);       // w = Ki mu
-    if (rc) return rc;
-    }
-    if (!offpath) hipLaunchKernelGGL((dot_kernel<D>), dim3(dotgrid(MP)), dim3(256), 0, st, MP, (const D*)mud, (const D*)wd, 1.0, sc + 3);
+    hipLaunchKernelGGL((gemv_rows_kernel<D>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, M, P, (const D*)Ki, M, (const D*)mud, (int64_t)P, wd);   // w = Ki mu
     hipLaunchKernelGGL((convert_kernel<D, T>), dim3(gridn(MP)), dim3(256), 0, st, (int64_t)1, MP, (const D*)wd, MP, wT, MP);      // w in the streaming dtype
     MXF_STAGE(h, "Ki, w", st);
     if (use_split && !whiten) MXF_HIP(h, hipEventRecord(h->ev_aux2, st));                             // w ready: the Kfu planes + U pass may start
-    if (!offpath) { rc = mxf_sumlogdiag_internal(h, MXF_F64, 1, M, Lm, M, MM, sc + 0, st); if (rc) return rc; }
     // ---- second side stream: Su -> Ls -> Su^-1 ----------------------------------------------------------------------------------
     // (a plain kernel, not hipMemcpyAsync: the runtime's copy path sat idle for ~1 ms before it started next to busy queues -- r02 timeline:
     //  the Su chain did not begin until 1.66 ms although nothing in the Kuu chain feeds it)
-    if (late && chain_late >= 2) MXF_HIP(h, hipStreamWaitEvent(s2_, h->ev_aux, 0));
     hipLaunchKernelGGL((convert_kernel<D, D>), dim3(gridn(MM)), dim3(256), 0, s2_, (int64_t)1, MM, (const D*)Su, MM, tmp, MM);
     rc = mxf_potrf_internal(h, MXF_F64, 1, M, tmp, M, MM, info2, s2_, false, false);                  // Ls = chol(Su) :84
     if (rc) return rc;
@@ -1383,10 +1317,9 @@ int svgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t B, int64_t
     if (rc) return rc;
     if (symlow) hipLaunchKernelGGL((symmetrize_kernel<D>), dim3((unsigned)((M + 31) / 32), (unsigned)((M + 31) / 32), 1), dim3(256), 0, st, H0, M, M, MM);
     }
-    if (!offpath) hipLaunchKernelGGL((dot_kernel<D>), dim3(dotgrid(MM)), dim3(256), 0, st, MM, (const D*)Ki, (const D*)Su, 1.0, sc + 2);
     // A_ext = [H0 ; w^T] in the streaming dtype
     // (the w^T row that used to follow H0 in A_ext was read by nothing since U = w^T Kuf left the product: its launch is gone)
-    const bool fused_h0max = use_split && split_mode == MXF_SPLIT_F16X2 && sizeof(T) == 4;
+    const bool fused_h0max = use_split && sizeof(T) == 4;
     if (fused_h0max) hipLaunchKernelGGL(convert_max_kernel, dim3((unsigned)(gridn(MM) > 256 ? 256 : gridn(MM))), dim3(256), 0, st, MM, (const D*)H0, (float*)Aext, (unsigned*)(info2 + 2));
     else
     hipLaunchKernelGGL((convert_kernel<D, T>), dim3(gridn(MM)), dim3(256), 0, st, M, M, (const D*)H0, M, Aext, M);
@@ -1398,44 +1331,27 @@ int svgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t B, int64_t
     const int t_blocked = (use_split && want_grad && !het && SB % 16 == 0 && mxf_svgp_bwd_reads_blocked(kind, dtype, SB, B, Q, P, Text)) ? 1 : 0;
     if (use_split) {
         unsigned* h0max = (unsigned*)(info2 + 2);       // bit pattern of max |H0|: the power-of-two scale of its f16x2 planes
-        if (split_mode == MXF_SPLIT_F16X2 && !fused_h0max) { rc = mxf_maxabs_internal(h, M, M, (const float*)Aext, M, h0max, st, false); if (rc) return rc; }      // (word cleared by svgp_init_kernel)
-        rc = mxf_split_planes_internal(h, M, M, (const float*)Aext, M, plH0, st, split_mode, split_mode == MXF_SPLIT_F16X2 ? h0max : nullptr);
+        if (!fused_h0max) { rc = mxf_maxabs_internal(h, M, M, (const float*)Aext, M, h0max, st, false); if (rc) return rc; }      // (word cleared by svgp_init_kernel)
+        rc = mxf_split_planes_internal(h, M, M, (const float*)Aext, M, plH0, st, split_mode, h0max);
         if (rc) return rc;
     }
     MXF_T1(h, MXF_T_CHAIN, st);
     MXF_STAGE(h, "H0 planes", st);
     MXF_HIP(h, hipEventRecord(h->ev_fork, st));                                                       // core (Ki, KiSu, H0, w) ready
-    if (offpath) {      // |Ki|_1, mu.w, tr(Ki Su), log|Kuu| behind the Su chain on the second side stream; the caller's stream picks them up behind the T product
-        MXF_HIP(h, hipStreamWaitEvent(s2_, h->ev_fork, 0));
-        hipLaunchKernelGGL(norm1_sym16_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, s2_, M, (const double*)Ki, M, h->cond_dev + 1);
-        hipLaunchKernelGGL((dot_kernel<D>), dim3(dotgrid(MP)), dim3(256), 0, s2_, MP, (const D*)mud, (const D*)wd, 1.0, sc + 3);
-        hipLaunchKernelGGL((dot_kernel<D>), dim3(dotgrid(MM)), dim3(256), 0, s2_, MM, (const D*)Ki, (const D*)Su, 1.0, sc + 2);
-        rc = mxf_sumlogdiag_internal(h, MXF_F64, 1, M, Lm, M, MM, sc + 0, s2_);
-        if (rc) return rc;
-        MXF_HIP(h, hipEventRecord(h->ev_k3, s2_));
-    }
+    // |Ki|_1, mu.w, tr(Ki Su), log|Kuu| behind the Su chain on the second side stream; the caller's stream picks them up behind the T product
+    MXF_HIP(h, hipStreamWaitEvent(s2_, h->ev_fork, 0));
+    hipLaunchKernelGGL(norm1_sym16_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, s2_, M, (const double*)Ki, M, h->cond_dev + 1);
+    hipLaunchKernelGGL((dot_kernel<D>), dim3(dotgrid(MP)), dim3(256), 0, s2_, MP, (const D*)mud, (const D*)wd, 1.0, sc + 3);
+    hipLaunchKernelGGL((dot_kernel<D>), dim3(dotgrid(MM)), dim3(256), 0, s2_, MM, (const D*)Ki, (const D*)Su, 1.0, sc + 2);
+    rc = mxf_sumlogdiag_internal(h, MXF_F64, 1, M, Lm, M, MM, sc + 0, s2_);
+    if (rc) return rc;
+    MXF_HIP(h, hipEventRecord(h->ev_k3, s2_));
     MXF_HIP(h, hipStreamWaitEvent(st, h->ev_aux, 0));                                                 // Kuf_all from the side stream
     // (in-step timing only: the T product is held until Psi2 has finished, so that `t_gemm` is the product's own duration -- untimed, its
     //  first workgroups take the CUs Psi2's last work items free, and the event pair would count that queueing)
     if (h->tm.on && bt_path && want_grad && !het) MXF_HIP(h, hipStreamWaitEvent(st, h->ev_join2, 0));
     MXF_T0(h, MXF_T_TGEMM, st);
-    // r05: the reverse pass as the EPILOGUE of the T product (gemm_split.hip wide_body<..., FUSE>): T is never written
-    const bool fuse_bwd = use_split && want_grad && !het && !het_stream && split_mode == MXF_SPLIT_F16X2 && !bt_path && !bt_wh &&
-                          mxf_svgp_bwd_fuse_ok(kind, dtype, M, SB, B, Q, P) != 0;
-    mxf_fuse_args fza;
-    if (fuse_bwd) {
-        rc = mxf_svgp_bwd_fuse_prepare(h, M, SB, B, Q, (const float*)Z, (const float*)X, (const float*)ls, ard, (const float*)var,
-                                       (const float*)(Text + M * SB), (const float*)Y, sY, (const float*)wT, (const float*)noise, a1, (float*)dX, (float*)dY,
-                                       (sY == 0 && SS > 1) ? 1 : 0, scal, (const unsigned*)(info2 + 2), &fza, st);
-        if (rc) return rc;
-    }
-    if (fuse_bwd && whiten)
-        rc = mxf_gemm_split_internal(h, M, SB, M, (double)split_ga, plH0, (int64_t)pl_h0, plVt, pVt, 0.0, (float*)Text, SB, 0, st, 0, split_mode,
-                                     sigf, 1, (const unsigned*)(info2 + 2), nullptr, 0, nullptr, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, &fza);
-    else if (fuse_bwd)
-        rc = mxf_gemm_split_internal(h, M, SB, M, (double)split_ga, plH0, (int64_t)pl_h0, plKfu, (int64_t)pl_big, 0.0, (float*)Text, SB, 0, st, 0, split_mode,
-                                     split_var, 1, (const unsigned*)(info2 + 2), nullptr, 0, nullptr, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, &fza);
-    else if (bt_wh)       // T = Hh V from the planes of V (scaled from max |Hh|; V / sigma 2^14), U = a^T V from the same fragments
+    if (bt_wh)       // T = Hh V from the planes of V (scaled from max |Hh|; V / sigma 2^14), U = a^T V from the same fragments
         rc = mxf_gemm_bt_internal(h, M, SB, M, (double)split_ga, plH0, (int64_t)pl_h0, plKuf, (int64_t)pl_big, M, (float*)Text, SB, t_blocked, st, 0,
                                   sigf, (const unsigned*)(info2 + 2), (unsigned*)(info2 + 3), (const float*)aT, (float*)(Text + M * SB),
                                   1.0 / 16384.0, wpl);
@@ -1448,7 +1364,7 @@ int svgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t B, int64_t
                                   1.0 / 16384.0, wpl);
     else if (use_split)   // T = H0 Kuf = H0 Kfu^T on the 16-bit matrix pipe (f32-equivalent splitting, gemm_split.hip)
         rc = mxf_gemm_split_internal(h, M, SB, M, (double)split_ga, plH0, (int64_t)pl_h0, plKfu, (int64_t)pl_big, 0.0, (float*)Text, SB, 0, st, 0, split_mode,
-                                     split_var, 1, split_mode == MXF_SPLIT_F16X2 ? (const unsigned*)(info2 + 2) : nullptr, nullptr, t_blocked,
+                                     split_var, 1, (const unsigned*)(info2 + 2), nullptr, t_blocked,
                                      (unsigned*)(info2 + 3));       // max |T| for the reverse pass (word cleared by svgp_init_kernel)
     else if (het_split) {
         rc = mxf_maxabs_internal(h, M, M, (const float*)Aext, M, hsw + 0, st);
@@ -1462,12 +1378,6 @@ int svgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t B, int64_t
     if (rc) return rc;
     MXF_T1(h, MXF_T_TGEMM, st);
     MXF_STAGE(h, "T", st);
-    if (phi_late) {      // Phi behind T: next to the reverse pass instead of next to T
-        MXF_HIP(h, hipEventRecord(h->ev_tg, st));
-        MXF_HIP(h, hipStreamWaitEvent(sd_, h->ev_tg, 0));
-        rc = launch_phi(true);
-        if (rc) return rc;
-    }
     if (use_split) {
         // (U = w^T Kuf was written by the Kfu planes pass)
     } else {
@@ -1489,10 +1399,7 @@ int svgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t B, int64_t
     // (r06) float32 mode: the whole R-independent part of the core's reverse mode -- dKuu0 included -- on the side stream, from X = Ki G Ki (below).
     // float64 mode keeps the r05 flow: forming A_Ki = G - G Ki Su - ... FIRST and multiplying by Ki afterwards cancels before it amplifies; the X form
     // multiplies first and loses ~2 digits on ill-conditioned Kuu (uncertain-input toy of tests/test_gpu_config4.py, cond ~ 1e6: float64 lengthscale
-    // gradient 8.6e-10 -> 5.8e-8 against the oracle, tests/probes/r06_early_kuu_accuracy.py) -- nothing next to float32 streaming (1e-5), but the
-    // float64 path is the parity path.  Probe knob MXF_SVGP_EARLY_KUU: 0 = r05 flow everywhere, 2 = X form in float64 too.
-    static const int early_kuu_env = (int)MXF_KNOB("MXF_SVGP_EARLY_KUU", 1);
-    const bool early_kuu = early_kuu_env == 2 || (early_kuu_env != 0 && sizeof(T) == 4);
+    // gradient 8.6e-10 -> 5.8e-8 against the oracle) -- nothing next to float32 streaming (1e-5), but the float64 path is the parity path.
     auto su_reverse = [&](hipStream_t s_, bool with_t1) -> int {
         int r_ = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 1.0, Ki, M, 0, G, M, 0, 0.0, tmp, M, 0, 1, 0, s_);            // T3 = Ki G
         if (r_) return r_;
@@ -1508,8 +1415,7 @@ int svgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t B, int64_t
         if (with_t1) r_ = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 1.0, G, M, 0, KiSu, M, 0, 0.0, T1, M, 0, 1, 0, s_);           // T1 = G Ki Su
         return r_;
     };
-    bool side_split = false;
-    if (want_grad && !het && early_kuu) {
+    if (want_grad && !het && sym_core) {
         // r06: the whole R-independent part of the core's reverse mode from X = Ki G Ki (G = c Psi2, c = P a1 beta / 2):
         //   dSu   = -X + bP/2 (Su^-1 - Ki)                                  (as before)
         //   dKuu0 = -Ki A0 Ki - bP/2 Ki,  A0 = G - T1 - T1^T - b (P/2 Su + 1/2 mu mu^T),  T1 = G Ki Su
@@ -1521,30 +1427,23 @@ int svgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t B, int64_t
         MXF_HIP(h, hipStreamWaitEvent(sd_, h->ev_fork, 0));      // Ki, KiSu, H0 (main)
         MXF_HIP(h, hipStreamWaitEvent(sd_, h->ev_join, 0));      // Su^-1; `tmp` (chol(Su)) is free from here on
         D* Xb = whiten ? G : T2;
-        static const int xlow_env = (int)MXF_KNOB("MXF_SVGP_X_LOWER", 1);
-        const int xlow = xlow_env ? 1 : 0;
         if (whiten) {
             hipLaunchKernelGGL((scale_beta_kernel<T>), dim3(gridn(MM)), dim3(256), 0, sd_, MM, (const T*)Psi2, (const D*)noised, 0.5 * P * a1, T2);   // c Phi
             hipLaunchKernelGGL((trace_kernel<D>), dim3(1), dim3(256), 0, sd_, M, (const D*)T2, M, (int64_t)0, sc + 6);                                 // c tr(Phi)
             rc = mxf_gemm_internal(h, MXF_F64, 1, 0, M, M, M, 1.0, Linv, M, 0, T2, M, 0, 0.0, tmp, M, 0, 1, 0, sd_);       // L^-T (c Phi)
             if (rc) return rc;
-            rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 1.0, tmp, M, 0, Linv, M, 0, 0.0, Xb, M, 0, 1, xlow, sd_);    // X = c L^-T Phi L^-1 (symmetric: lower tiles, mirrored)
+            rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 1.0, tmp, M, 0, Linv, M, 0, 0.0, Xb, M, 0, 1, symlow, sd_);    // X = c L^-T Phi L^-1 (symmetric: lower tiles, mirrored)
             if (rc) return rc;
-            if (xlow) hipLaunchKernelGGL((symmetrize_kernel<D>), dim3((unsigned)((M + 31) / 32), (unsigned)((M + 31) / 32), 1), dim3(256), 0, sd_, Xb, M, M, MM);
+            hipLaunchKernelGGL((symmetrize_kernel<D>), dim3((unsigned)((M + 31) / 32), (unsigned)((M + 31) / 32), 1), dim3(256), 0, sd_, Xb, M, M, MM);
             hipLaunchKernelGGL(dot_t_kernel, dim3(dotgrid(MM)), dim3(256), 0, sd_, M, (const D*)Su, (const D*)Xb, sc + 7);   // tr(Su X): the accurate total of the q_n
         } else {
             hipLaunchKernelGGL((scale_beta_kernel<T>), dim3(gridn(MM)), dim3(256), 0, sd_, MM, (const T*)Psi2, (const D*)noised, 0.5 * P * a1, G);
             rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 1.0, Ki, M, 0, G, M, 0, 0.0, tmp, M, 0, 1, 0, sd_);           // Ki G
             if (rc) return rc;
-            rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 1.0, tmp, M, 0, Ki, M, 0, 0.0, Xb, M, 0, 1, xlow, sd_);       // X = Ki G Ki (symmetric: lower tiles, mirrored)
+            rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 1.0, tmp, M, 0, Ki, M, 0, 0.0, Xb, M, 0, 1, symlow, sd_);       // X = Ki G Ki (symmetric: lower tiles, mirrored)
             if (rc) return rc;
-            if (xlow) hipLaunchKernelGGL((symmetrize_kernel<D>), dim3((unsigned)((M + 31) / 32), (unsigned)((M + 31) / 32), 1), dim3(256), 0, sd_, Xb, M, M, MM);
+            hipLaunchKernelGGL((symmetrize_kernel<D>), dim3((unsigned)((M + 31) / 32), (unsigned)((M + 31) / 32), 1), dim3(256), 0, sd_, Xb, M, M, MM);
         }
-        // (probe knob, off: measured neutral to slower -- per-rank step 3.79-3.84 ms without, 3.85-3.90 with it, tests/probes/r06_side_split.sh: the two
-        //  branches then share the CUs the reverse pass leaves, and the tail still waits for the later of them)
-        static const int side_split_env = (int)MXF_KNOB("MXF_SVGP_SIDE_SPLIT", 0);
-        side_split = side_split_env != 0;
-        if (side_split) { MXF_HIP(h, hipEventRecord(h->ev_k1, sd_)); MXF_HIP(h, hipStreamWaitEvent(s2_, h->ev_k1, 0)); }      // X ready
         hipLaunchKernelGGL(dsu_kernel, dim3(gridn(MM)), dim3(256), 0, sd_, MM, (const D*)Xb, (const D*)Sui, (const D*)Ki, 0.5 * bw * P, dSu);
         if (dW) {
             rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 2.0, dSu, M, 0, Wd, M, 0, 0.0, Lsinv, M, 0, 1, 0, sd_);     // dW = 2 dSu W (Lsinv buffer is free)
@@ -1552,18 +1451,14 @@ int svgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t B, int64_t
             hipLaunchKernelGGL((add_convert_kernel<D, T>), dim3(gridn(MM)), dim3(256), 0, sd_, MM, (T)1, (const D*)Lsinv, dW, 0);
         }
         if (dSdiag) hipLaunchKernelGGL((diag_extract_kernel<D, T>), dim3(gridn(M)), dim3(256), 0, sd_, M, (const D*)dSu, M, dSdiag);
-        // the dKuu0 branch (Y, Ki Su Ki, dKuu0) needs X only: it runs on the second side stream next to the dSu / dW branch (MXF_SVGP_SIDE_SPLIT) --
-        // in the few-sample regime this stream ends after the reverse pass, and the step's tail waits for it
-        hipStream_t sk_ = side_split ? s2_ : sd_;
-        rc = mxf_gemm_internal(h, MXF_F64, 0, 1, M, M, M, 1.0, Xb, M, 0, KiSu, M, 0, 0.0, T1, M, 0, 1, 0, sk_);             // Y = X (Ki Su)^T
+        rc = mxf_gemm_internal(h, MXF_F64, 0, 1, M, M, M, 1.0, Xb, M, 0, KiSu, M, 0, 0.0, T1, M, 0, 1, 0, sd_);             // Y = X (Ki Su)^T
         if (rc) return rc;
         if (whiten) {
-            rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 1.0, KiSu, M, 0, Ki, M, 0, 0.0, AKi, M, 0, 1, 0, sk_);        // Ki Su Ki (H0 holds Hh in this form)
+            rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 1.0, KiSu, M, 0, Ki, M, 0, 0.0, AKi, M, 0, 1, 0, sd_);        // Ki Su Ki (H0 holds Hh in this form)
             if (rc) return rc;
         }
-        hipLaunchKernelGGL(dkuu0_kernel, dim3(gridn(MM)), dim3(256), 0, sk_, M, P, (const D*)Xb, (const D*)T1, (const D*)Ki, whiten ? (const D*)AKi : (const D*)nullptr,
+        hipLaunchKernelGGL(dkuu0_kernel, dim3(gridn(MM)), dim3(256), 0, sd_, M, P, (const D*)Xb, (const D*)T1, (const D*)Ki, whiten ? (const D*)AKi : (const D*)nullptr,
                            (const D*)H0, (const D*)wd, bw, dKuu);
-        if (side_split) MXF_HIP(h, hipEventRecord(h->ev_k2, s2_));
     } else if (want_grad && !het) {
         MXF_HIP(h, hipStreamWaitEvent(sd_, h->ev_fork, 0));      // Ki, KiSu (main)
         MXF_HIP(h, hipStreamWaitEvent(sd_, h->ev_join, 0));      // Su^-1; `tmp` (chol(Su)) is free from here on
@@ -1588,10 +1483,10 @@ int svgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t B, int64_t
     }
     if (want_grad && !het) {
         MXF_STAGE(h, "Su reverse (sd)", sd_);
-        MXF_HIP(h, hipEventRecord(h->ev_join2, sd_));            // Psi2, G, T1, dSu outputs (early_kuu: dKuu0 as well)
+        MXF_HIP(h, hipEventRecord(h->ev_join2, sd_));            // Psi2, G, T1, dSu outputs (float32 mode: dKuu0 as well)
     }
     MXF_HIP(h, hipStreamWaitEvent(st, h->ev_join, 0));      // Su chain complete (log-det for the value, Su^-1 for the reverse mode); hidden under the T GEMM
-    if (offpath) MXF_HIP(h, hipStreamWaitEvent(st, h->ev_k3, 0));      // ... and the condition norms and value scalars behind it
+    MXF_HIP(h, hipStreamWaitEvent(st, h->ev_k3, 0));      // ... and the condition norms and value scalars behind it
     const int dY_shared = (sY == 0 && SS > 1) ? 1 : 0;
     D* dnz = nullptr; D* dvdir = nullptr;
     if (het) {
@@ -1641,12 +1536,10 @@ int svgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t B, int64_t
         // (dY, dZ, dls, dvar, dX, R were cleared on the second side stream at the start of the call: early_clear)
         // one pass over T: q_n, |e_n|^2, dY, R = Kuf E, and the Kuf-side reverse mode (dX, dZ, dls, dvar) without materialising dKuf
         MXF_T0(h, MXF_T_BWD, st);
-        if (fuse_bwd) rc = mxf_svgp_bwd_fuse_finish(h, M, Q, ard, (const float*)ls, (const float*)var, &fza, (float*)dZ, (float*)dls, (float*)dvar, (float*)R, st);
-        else
         rc = mxf_svgp_bwd_fused_internal(h, kind, dtype, M, SB, B, Q, P, Z, X, ls, ard, var, Text, het_stream ? (const T*)hys : Y, sY, wT,
                                          het_stream ? (const T*)hnz : noise, a1, dZ, dX, dls, dvar,
                                          dY, dY_shared, R, scal, st, t_blocked,
-                                         (use_split && split_mode == MXF_SPLIT_F16X2) ? (const unsigned*)(info2 + 2) : nullptr,
+                                         use_split ? (const unsigned*)(info2 + 2) : nullptr,
                                          (const unsigned*)(info2 + 3));
         if (rc) return rc;
     }
@@ -1683,11 +1576,10 @@ int svgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t B, int64_t
         if (rc) return rc;
     } else {
         MXF_HIP(h, hipStreamWaitEvent(st, h->ev_join2, 0));      // side stream: Psi2 -> G, T1, dSu / dW / dSdiag (already done)
-        if (side_split) MXF_HIP(h, hipStreamWaitEvent(st, h->ev_k2, 0));      // ... and dKuu0 from the second side stream
         hipLaunchKernelGGL((scale_beta_kernel<T>), dim3(gridn(MP)), dim3(256), 0, st, MP, (const T*)R, (const D*)noised, a1, Gw);
     }
     // main: dKuu = -Ki A_Ki Ki - bP/2 Ki; dmu = Ki Gw - b w
-    if (!(early_kuu && !het)) {
+    if (!(sym_core && !het)) {
     hipLaunchKernelGGL(aki_kernel, dim3(gridn(MM)), dim3(256), 0, st, M, P, (const D*)G, (const D*)T1, (const D*)Gw, (const D*)mud, (const D*)Su, bw, AKi);
     rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 1.0, Ki, M, 0, AKi, M, 0, 0.0, T2, M, 0, 1, 0, st);           // T2 = Ki A_Ki
     if (rc) return rc;
@@ -1695,13 +1587,8 @@ int svgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t B, int64_t
     rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, -1.0, T2, M, 0, Ki, M, 0, -0.5 * bw * P, dKuu, M, 0, 1, 0, st);
     if (rc) return rc;
     }
-    if (offpath) hipLaunchKernelGGL((gemv_rows_kernel<D>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, M, P, (const D*)Ki, M, (const D*)Gw, (int64_t)P, dmud, -bw, (const D*)wd);
-    else {
-    hipLaunchKernelGGL((axpby_kernel<D>), dim3(gridn(MP)), dim3(256), 0, st, MP, -bw, (const D*)wd, 0.0, (const D*)nullptr, dmud);
-    rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, P, M, 1.0, Ki, M, 0, Gw, P, 0, 1.0, dmud, P, 0, 1, 0, st);
-    if (rc) return rc;
-    }
-    if (early_kuu && !het) hipLaunchKernelGGL(dkuu_rank_kernel, dim3(gridn(MM)), dim3(256), 0, st, M, P, (const D*)dmud, (const D*)wd, bw, dKuu);
+    hipLaunchKernelGGL((gemv_rows_kernel<D>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, M, P, (const D*)Ki, M, (const D*)Gw, (int64_t)P, dmud, -bw, (const D*)wd);
+    if (sym_core && !het) hipLaunchKernelGGL(dkuu_rank_kernel, dim3(gridn(MM)), dim3(256), 0, st, M, P, (const D*)dmud, (const D*)wd, bw, dKuu);
     // Kuu-side reverse mode in float64, then added to the streaming-side gradients
     FinishArgs fa;
     fa.cnt = 0;
@@ -1717,9 +1604,10 @@ int svgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t B, int64_t
             MXF_HIP(h, hipMemsetAsync(dlsc, 0, sizeof(D) * lsn, st));
             MXF_HIP(h, hipMemsetAsync(dvc, 0, sizeof(D) * 4, st));
         }
-        // (float32 mode: dKuu is symmetric up to the rounding of its float64 products -- the row side of its reverse pass is skipped; float64 keeps both sides)
+        // (float32 mode: dKuu is formed from the mirrored X, Ki and H0, i.e. symmetric -- the row side of its reverse pass is skipped (sym_core);
+        //  float64 keeps both sides)
         rc = mxf_gram_bwd_internal(h, kind, MXF_F64, 1, M, M, Q, Zd, 0, nullptr, 0, lsd, ard, 0, vard, 0, dKuu, M, 0, dZc, nullptr, dlsc, dvc, st,
-                                   (early_kuu && !het) ? 1 : 0);
+                                   (sym_core && !het) ? 1 : 0);
         if (rc) return rc;
         if (dZ) fin(dZc, nullptr, dZ, M * Q, 1);
         if (dls) fin(dlsc, nullptr, dls, lsn, 1);

@@ -33,10 +33,8 @@ extern "C" int mxf_destroy(mxf_handle h) {
     if (h->ev_join2) (void)hipEventDestroy(h->ev_join2);
     if (h->ev_aux) (void)hipEventDestroy(h->ev_aux);
     if (h->ev_aux2) (void)hipEventDestroy(h->ev_aux2);
-    if (h->ev_tg) (void)hipEventDestroy(h->ev_tg);
     if (h->ev_su) (void)hipEventDestroy(h->ev_su);
     if (h->ev_k1) (void)hipEventDestroy(h->ev_k1);
-    if (h->ev_k2) (void)hipEventDestroy(h->ev_k2);
     if (h->ev_k3) (void)hipEventDestroy(h->ev_k3);
     if (h->side) (void)hipStreamDestroy(h->side);
     if (h->side2) (void)hipStreamDestroy(h->side2);
@@ -50,11 +48,6 @@ extern "C" int mxf_destroy(mxf_handle h) {
     if (h->potrf_rows) (void)hipStreamDestroy(h->potrf_rows);
     if (h->ev_pc) (void)hipEventDestroy(h->ev_pc);
     if (h->ev_rb) (void)hipEventDestroy(h->ev_rb);
-    if (h->potrf_acc) (void)hipStreamDestroy(h->potrf_acc);
-    if (h->ev_pq) (void)hipEventDestroy(h->ev_pq);
-    if (h->ev_pz) (void)hipEventDestroy(h->ev_pz);
-    if (h->potrf_chain) (void)hipStreamDestroy(h->potrf_chain);
-    if (h->ev_pk) (void)hipEventDestroy(h->ev_pk);
     delete h;
     return 0;
 }

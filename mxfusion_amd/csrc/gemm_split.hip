@@ -176,8 +176,7 @@ struct SplitArgs {
     // Upart[(m / 128) * N + n] = sum over the 128-row band of avec[m] * (hi + lo)(m, n)  (the whitened SVGP tier's V^T and a^T V)
     unsigned short* Ct; int64_t pCt;
     const float* avec; float* Upart;
-    int cp_nt;                           // bit 0: the planes, bit 1: the transposed planes are stored non-temporally
-    mxf_fuse_args fz;                    // FUSE instantiation: the SVGP reverse pass in the epilogue (internal.h)
+    int cp_nt;                           // bit 0: the planes, bit 1: the transposed planes are stored non-temporally (0 in every launch)
 };
 
 __device__ __forceinline__ int lds_unit(int row, int kh) { return row * 2 + (kh ^ ((row >> 3) & 1)); }
@@ -307,7 +306,7 @@ __global__ __launch_bounds__(SNT, (NP == 2 && !DMA) ? 4 : 3) void gemm_split_ker
 #undef BF
                 } else {
 #define HF(v) __builtin_bit_cast(f16x8, v)
-                    if (g.nprod >= 3) {      // (MXF_SPLIT_NPROD=1: diagnostic only -- the kernel's time without the cross products)
+                    if (g.nprod >= 3) {
                         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(HF(a[x][0]), HF(b[y][1]), acc, 0, 0, 0);    // hi lo'
                         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(HF(a[x][1]), HF(b[y][0]), acc, 0, 0, 0);    // lo hi'
                     }
@@ -357,14 +356,12 @@ __global__ __launch_bounds__(SNT, (NP == 2 && !DMA) ? 4 : 3) void gemm_split_ker
             }
 }
 
-// ------------------------------------------------------------------------------------------------ the (32 XT) x 256 kernels (f16x2 operands)
+// ------------------------------------------------------------------------------------------------ the (128 NH) x 256 kernels (f16x2 operands)
 // The 128 x 128 kernel above moves every operand through LDS: per 16-wide k block and workgroup 16 KB of LDS-DMA writes and 32 KB of
 // fragment reads for 48 MFMAs, and the LDS (not the matrix pipe: 58 % busy) is what it runs out of.  This kernel cuts the LDS traffic per
 // MFMA to a quarter:
-//   * block tile (32 XT) (A rows) x 256 (B rows), four waves side by side along B: wave w owns ALL A rows x columns [64 w, 64 w + 64)
-//     = XT x 2 MFMA tiles, 6 XT v_mfma_f32_32x32x16_f16 per k block.  XT = 4: 128 rows, 128 accumulator registers, two workgroups per CU;
-//     XT = 8: 256 rows, 256 accumulators (the whole AGPR half of the register file), one workgroup per CU -- per MFMA it moves 2/3 of
-//     the bytes the 128-row tile moves from L2 (A 16 KB + B 16 KB per 192 MFMAs instead of 8 + 16 per 96);
+//   * block tile 128 (A rows) x 256 (B rows), four waves side by side along B: wave w owns ALL A rows x columns [64 w, 64 w + 64)
+//     = XT x 2 MFMA tiles (XT = 4), 6 XT v_mfma_f32_32x32x16_f16 per k block, 128 accumulator registers, two workgroups per CU;
 //   * A (shared by the four waves) goes through LDS: LDS-DMA, a three-slot ring, 2 XT ds_read_b128 per wave and k block;
 //   * B is private to a wave, so it never touches LDS: each lane fetches its 16-byte fragment units straight from global memory
 //     (the plane layout makes a wave's 32 rows x 16 k one contiguous 1 KB run) two k blocks ahead into a three-deep register ring.
@@ -414,38 +411,18 @@ __device__ __forceinline__ u32x4 gload16_o1024(unsigned voff, const void* sbase)
 
 // NH = 2: 512-thread workgroups, two row halves of four waves each (wave = 4 h + w owns rows [32 XT h, +32 XT) x columns [64 w, +64)):
 // the 256-row tile with TWO waves per SIMD -- a wave's loads, LDS reads and waits run under its partner's MFMAs, which a single
-// 512-register wave per SIMD cannot do (r03: the XT = 8, NH = 1 form halves the fabric fetch and clocks 1.83 instead of 1.56 GHz, but its
-// matrix pipe idles through every ds_read / VMEM issue: same wall time).  The two halves share the A slab in LDS; both fetch the B
+// 512-register wave per SIMD cannot do (r03: that form -- 256 rows by four waves -- halves the fabric fetch and clocks 1.83 instead of
+// 1.56 GHz, but its matrix pipe idles through every ds_read / VMEM issue: same wall time).  The two halves share the A slab in LDS; both fetch the B
 // fragments of their column quarter (identical addresses, a few hundred cycles apart: the second is an L1 / L2 hit, no fabric traffic).
 //
-// PP ("ping-pong", NH = 2 only): the two row halves run half a k step apart.  A k step is split into a LOAD phase (request block k + 2,
-// read the A fragments of block k from LDS, wait for block k + 1) and a COMPUTE phase (24 MFMAs), with a workgroup barrier after each; the
-// second half starts one phase late, so on every SIMD one wave computes while its partner loads.  Without it both waves of a SIMD reach the
-// shared barrier together, want the matrix pipe together and then wait for LDS / memory together.
-// BLO = false: the B operand enters through its HIGH plane only (B rounded to f16, A still exact: two products instead of three, half the B
-// fetch) -- for products that feed GRADIENTS only (the T of the SVGP step; DESIGN.md section 4 states the error this leaves in them).
 // LSKIP (lower-only products): a wave whose 128 x 64 block lies strictly ABOVE the diagonal (the upper right quarter of a diagonal 256 x 256
 // tile: 2 of its 8 waves) runs a k loop WITHOUT its B loads and MFMAs -- it still fetches its share of the A slab and keeps every barrier.
 // (A branch around the MFMAs inside the one loop cost the kernel its schedule, see below; here the loop exists twice and the idle form is a
 //  separate instantiation, so the T product's kernel is untouched.)  The busiest SIMDs still carry two working waves: the gain is power.
-// BFI (probe builds only, MXF_SPLIT_BF16MFMA=1): the SAME kernel with v_mfma_f32_32x32x16_bf16 on the same bits -- the numbers mean nothing,
-// the time does: it separates the operand FORMAT (11-bit f16 mantissas vs 8-bit bf16 ones toggling the multiplier array; the guide's MFMA
-// microbenchmark gives 2178 vs 2382 TF) from the schedule when this kernel is compared with the guide's bf16 GEMM template.
-// FUSE (r05): the product is the T = H0 Kuf (or Hh V) of the SVGP training call and its epilogue IS the reverse pass of that call (see
-// mxf_fuse_args, internal.h): nothing of C is written.  Per 32 x 32 accumulator fragment (rows m on lanes, 16 columns n per lane):
-//   dots   x_n . z_m in the SAME accumulator layout, four v_mfma_f32_32x32x2_f32 (true float32: they feed r2 of near pairs);
-//   k = 2^(esc - r2), u = T + w_m e_n, W = u k  (the RBF weight up to -(c1 variance) 2^-esc, applied when the sums are flushed);
-//   row side  [B | S]_m += W [X | 1]: W's accumulator quads, converted to f16 hi + lo and paired by v_permlane32_swap, ARE the A operand
-//             (k = n) of v_mfma_f32_32x32x16_f16; the B operand [x_n | 1] (hi / lo) comes from an LDS table built per item;
-//   col side  [D | C]_n += W^T [Z | 1]: the same f16 pairs go through a wave-private LDS tile [m][n] and come back TRANSPOSED through
-//             ds_read_b64_tr_b16 (lane n, 8 consecutive m) as the A operand (k = m); B = [z_m | 1] from an LDS table built per row tile.
-// Row sums accumulate in LDS across all items of the workgroup (a persistent workgroup keeps its row tile) and leave as float64 atomics at
-// the end; column sums leave per item as float32 atomics into dX (two row halves x M / 256 row tiles per element).
-template <int XT, int NH, bool PP, bool BLO = true, bool LSKIP = false, bool CPL = false, bool BFI = false, bool FUSE = false>
+// CPL: the planes output (c_blk == 2), see the epilogue.
+template <int NH, bool LSKIP = false, bool CPL = false>
 __device__ __forceinline__ void wide_body(const SplitArgs& g) {
-    static_assert(!FUSE || (XT == 4 && NH == 2 && !PP && BLO && !LSKIP && !CPL && !BFI), "the fused reverse pass lives in the eight-wave 256 x 256 product");
-    static_assert(!PP || NH == 2, "ping-pong needs the two row halves");
-    static_assert(!LSKIP || (!PP && BLO), "the idle-wave loop mirrors the plain pipelined loop");
+    constexpr int XT = 4;                          // 32-row MFMA tiles per row half
     constexpr int WBMt = 32 * XT * NH;             // A rows per tile
     constexpr int NU = 64 * XT * NH;               // 16-byte units of one plane's (WBMt x 16) slab
     constexpr int ND = XT / 4;                     // LDS-DMA requests per thread, plane and k block
@@ -454,58 +431,6 @@ __device__ __forceinline__ void wide_body(const SplitArgs& g) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wq = wave & 3, wh = wave >> 2;
     int patience = 2;
     float cmax = 0.f;                              // max |C| over this thread's outputs (g.maxout)
-    // ---- FUSE: tables and constants of the fused reverse pass -------------------------------------------------------------------------
-    // fz_xb / fz_zb [plane][block of 16 k][j = 16 output columns][16 k] halves: B operands of the two accumulating products ([x | 1] of the
-    // item's 256 columns, [z | 1] of the row tile's 256 rows; j = 8 is the ones column, j > 8 zero); fz_col [|x_n|^2 - esc | e_n]; fz_row
-    // [256 rows][12]: 0..7 B_mq, 8 S_m, 9 R_m in the pass's units
-    constexpr int FZN = FUSE ? 2 * 16 * 16 * 16 : 8;
-    __shared__ __attribute__((aligned(16))) unsigned short fz_xb[FZN], fz_zb[FZN];
-    __shared__ __attribute__((aligned(16))) float fz_col[FUSE ? 2 * 256 : 4];
-    // float32 copies for the dot products and the flushes (LDS latency instead of a global round trip per fragment: the first form of this
-    // epilogue fetched them from global memory fragment by fragment and spent 97 us per item, mostly waiting): [z (8) | |z|^2 | w | - | -] per row
-    // of the row tile, [x (8)] per column of the item
-    __shared__ __attribute__((aligned(16))) float fz_zf[FUSE ? 256 * 12 : 4], fz_xf[FUSE ? 256 * 8 : 4];
-    __shared__ __attribute__((aligned(16))) float fz_row[FUSE ? 256 * 12 : 4];
-    float fz_escf = 0.f, fz_unsc = 1.f, fz_fl = 1.f, fz_var = 1.f, fz_ilj = 0.f, fz_dl3 = 0.f;
-    int64_t fz_m0 = -1;
-    constexpr float FZ_CS = 0.84932180028801904272f;       // the coordinates carry sqrt(log2(e) / 2): k = 2^-r2 (bwd_prescale_kernel)
-    if constexpr (FUSE) {
-        const mxf_fuse_args& z = g.fz;
-        fz_var = z.var[0];
-        const float c1 = (float)z.a1 / z.noise[0];
-        // |u k| <= bound: |T| <= max(variance, sqrt(variance)) M max |A operand| (explicit form: Gram planes hold k / variance, alpha carries
-        // the variance; whitened: V / sigma), |w e| <= max |w| max |e|.  (The separate pass took max |T| itself from the product: ~2^13 tighter;
-        // a loose bound costs absolute precision of the f16 pairs only -- dX 1.6e-6 -> 5e-6 when this bound was first tried, r03.)
-        const float vb = fmaxf(fz_var, sqrtf(fz_var));
-        const float bnd = vb * (float)g.M * __builtin_bit_cast(float, z.h0max[0]) + __builtin_bit_cast(float, z.mx[0]) * __builtin_bit_cast(float, z.mx[1]);
-        const int ex = (int)((__builtin_bit_cast(unsigned, bnd) >> 23) & 0xff);
-        int esc = (ex == 0 || ex == 0xff) ? 0 : 13 - (ex - 127);
-        esc = esc > 60 ? 60 : (esc < -60 ? -60 : esc);
-        fz_escf = (float)esc;
-        fz_unsc = __builtin_bit_cast(float, (unsigned)(127 - esc) << 23);
-        fz_fl = -c1 * fz_var * fz_unsc;
-        const int lj = lane & 31;
-        fz_ilj = (lj < z.Q) ? 1.f / z.ls[z.ard ? lj : 0] : 0.f;
-        for (int i = tid; i < FZN; i += NTH) {           // zero, and 1.0 in the hi plane's ones column
-            const unsigned short one = ((i >> 4) & 15) == 8 && i < FZN / 2 ? (unsigned short)0x3C00 : (unsigned short)0;
-            fz_xb[i] = one; fz_zb[i] = one;
-        }
-        for (int i = tid; i < 256 * 12; i += NTH) fz_row[i] = 0.f;
-        __syncthreads();
-    }
-    // rows of fz_row -> the float64 accumulators (when the workgroup's row tile changes, and at the end)
-    auto fz_flush_rows = [&](int64_t m0_) {
-        if constexpr (FUSE) {
-            __syncthreads();
-            for (int i = tid; i < 256 * 10; i += NTH) {
-                const int r = i / 10, cc = i % 10;
-                const float v = fz_row[r * 12 + cc];
-                if (v != 0.f) atomic_add(g.fz.zacc + (m0_ + r) * 16 + cc, (double)v * (double)(cc == 9 ? fz_var * fz_unsc : fz_fl));
-                fz_row[r * 12 + cc] = 0.f;
-            }
-            __syncthreads();
-        }
-    };
     // Persistent over the (tile, k split) work items: workgroup b takes items b, b + gridDim.x, ... (gridDim.x a multiple of 8, so its items
     // stay on its XCD's run of tiles).  The epilogue's stores of one item drain while the next item's first loads are in flight; with one
     // item per workgroup every tile paid a dispatch + an un-overlapped pipeline fill + a store burst (~30 % of a K = 1024 tile).
@@ -577,10 +502,8 @@ __device__ __forceinline__ void wide_body(const SplitArgs& g) {
         const unsigned short* bk_ = bbase + (kb) * g.N * 16;                                                                        \
         BR[0][0] = gload16(bvoff, bk_);                                                                                             \
         BR[1][0] = gload16_o1024(bvoff, bk_);                                                                                       \
-        if constexpr (BLO) {                                                                                                        \
-            BR[0][1] = gload16(bvoff, bk_ + g.pB);                                                                                  \
-            BR[1][1] = gload16_o1024(bvoff, bk_ + g.pB);                                                                            \
-        }                                                                                                                           \
+        BR[0][1] = gload16(bvoff, bk_ + g.pB);                                                                                      \
+        BR[1][1] = gload16_o1024(bvoff, bk_ + g.pB);                                                                                \
         _Pragma("unroll") for (int u_ = 0; u_ < ND; ++u_) {                                                                         \
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(da + u_ * (NTH / 2) * 16 + (kb) * g.M * 16), \
                                              (__attribute__((address_space(3))) void*)(&smem[SLOT][0][wave * 64 + NTH * u_]), 16, 0, 0); \
@@ -594,14 +517,12 @@ __device__ __forceinline__ void wide_body(const SplitArgs& g) {
     // registers whose loads are still in flight (seen in an earlier form of this kernel; csrc/check_wide_isa.py guards against it).
 #define W_WAIT_ASM(NSTR, BR)                                                                                                        \
     do {                                                                                                                            \
-        if constexpr (BLO) asm volatile("s_waitcnt vmcnt(" NSTR ")" : "+v"(BR[0][0]), "+v"(BR[0][1]), "+v"(BR[1][0]), "+v"(BR[1][1])::"memory"); \
-        else asm volatile("s_waitcnt vmcnt(" NSTR ")" : "+v"(BR[0][0]), "+v"(BR[1][0])::"memory");                                  \
+        asm volatile("s_waitcnt vmcnt(" NSTR ")" : "+v"(BR[0][0]), "+v"(BR[0][1]), "+v"(BR[1][0]), "+v"(BR[1][1])::"memory");      \
     } while (0)
-    // requests per k block: the B fragment loads (4, or 2 without the low plane) + 2 ND LDS-DMA requests
+    // requests per k block: the four B fragment loads + 2 ND LDS-DMA requests
 #define W_WAIT1(BR)                                                                                                                 \
     do {                                                                                                                            \
-        if constexpr (XT == 4 && BLO) W_WAIT_ASM("6", BR); else if constexpr (XT == 4) W_WAIT_ASM("4", BR);                         \
-        else if constexpr (BLO) W_WAIT_ASM("8", BR); else W_WAIT_ASM("6", BR);                                                      \
+        W_WAIT_ASM("6", BR);                                                                                                        \
         __builtin_amdgcn_s_barrier();                                                                                               \
         asm volatile("" ::: "memory");                                                                                              \
     } while (0)
@@ -612,8 +533,7 @@ __device__ __forceinline__ void wide_body(const SplitArgs& g) {
         asm volatile("" ::: "memory");                                                                                              \
     } while (0)
 #define HF(v) __builtin_bit_cast(f16x8, v)
-#define WMMA(a, b, c) (BFI ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0) \
-                           : __builtin_amdgcn_mfma_f32_32x32x16_f16(HF(a), HF(b), c, 0, 0, 0))
+#define WMMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(HF(a), HF(b), c, 0, 0, 0)
 #define W_COMPUTE(SLOT, BR)                                                                                                         \
     do {                                                                                                                            \
         u32x4 a_[XT][2];                                                                                                            \
@@ -625,11 +545,9 @@ __device__ __forceinline__ void wide_body(const SplitArgs& g) {
         _Pragma("unroll") for (int x = 0; x < XT; ++x)                                                                              \
             _Pragma("unroll") for (int y = 0; y < 2; ++y)                                                                           \
                 c[x][y] = WMMA(BR[y][0], a_[x][1], c[x][y]);                                                         /* hi' lo */   \
-        if constexpr (BLO) {                                                                                                        \
         _Pragma("unroll") for (int x = 0; x < XT; ++x)                                                                              \
             _Pragma("unroll") for (int y = 0; y < 2; ++y)                                                                           \
                 c[x][y] = WMMA(BR[y][1], a_[x][0], c[x][y]);                                                         /* lo' hi */   \
-        }                                                                                                                           \
         _Pragma("unroll") for (int x = 0; x < XT; ++x)                                                                              \
             _Pragma("unroll") for (int y = 0; y < 2; ++y)                                                                           \
                 c[x][y] = WMMA(BR[y][0], a_[x][0], c[x][y]);                                                         /* hi' hi */   \
@@ -644,30 +562,6 @@ __device__ __forceinline__ void wide_body(const SplitArgs& g) {
         W_ISSUE(k2_, SLOT2, BR2);                                                                                                   \
         W_COMPUTE(SLOT, BR);                                                                                                        \
         W_WAIT1(BRN);                                                                                                               \
-    } while (0)
-    // ping-pong form of a step: LOAD phase | barrier | COMPUTE phase | barrier.  Nothing may be scheduled across the barriers (the MFMAs
-    // are not memory operations: only sched_barrier keeps them on their side).  The fragment reads are complete (lgkmcnt(0)) before the
-    // barrier that ends the load phase: the slot they read is rewritten by a partner's request two barriers later.
-#define W_PHASE_END()                                                                                                               \
-    do {                                                                                                                            \
-        __builtin_amdgcn_sched_barrier(0);                                                                                          \
-        __builtin_amdgcn_s_barrier();                                                                                               \
-        __builtin_amdgcn_sched_barrier(0);                                                                                          \
-    } while (0)
-#define W_STEP_PP(kk, SLOT, BR, SLOT2, BR2, BRN)                                                                                    \
-    do {                                                                                                                            \
-        const int64_t i2_ = (kk) + 2 < nk ? (kk) + 2 : nk - 1;                                                                      \
-        const int64_t k2_ = KMAP(i2_);                                                                                              \
-        W_ISSUE(k2_, SLOT2, BR2);                                                                                                   \
-        u32x4 a_[XT][2];                                                                                                            \
-        _Pragma("unroll") for (int x = 0; x < XT; ++x) { a_[x][0] = smem[SLOT][0][ua[x]]; a_[x][1] = smem[SLOT][1][ua[x]]; }         \
-        if constexpr (BLO) W_WAIT_ASM("6", BRN); else W_WAIT_ASM("4", BRN);                                                         \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                          \
-        W_PHASE_END();                                                                                                              \
-        __builtin_amdgcn_s_setprio(1);                                                                                              \
-        W_MFMAS(a_, BR);                                                                                                            \
-        __builtin_amdgcn_s_setprio(0);                                                                                              \
-        W_PHASE_END();                                                                                                              \
     } while (0)
     bool idle = false;
     if constexpr (LSKIP) idle = g.lower_only && (m0 + 32 * XT * wh + 32 * XT - 1) < (n0 + 64 * wq);      // wave-uniform
@@ -694,14 +588,14 @@ __device__ __forceinline__ void wide_body(const SplitArgs& g) {
             if (kb < kend) {
                 W_ISSUE_A(kb, 0);
                 W_ISSUE_A(kb + 1, 1);
-                if constexpr (XT == 4) W_WAITL("2"); else W_WAITL("4");
+                W_WAITL("2");
                 int trip = 0, sync_ix = 0;
                 for (; kb < kend; kb += 3) {
 #pragma unroll
                     for (int s3 = 0; s3 < 3; ++s3) {
                         const int64_t k2_ = kb + s3 + 2 < kend ? kb + s3 + 2 : klast;
                         if (s3 == 0) W_ISSUE_A(k2_, 2); else if (s3 == 1) W_ISSUE_A(k2_, 0); else W_ISSUE_A(k2_, 1);
-                        if constexpr (XT == 4) W_WAITL("2"); else W_WAITL("4");
+                        W_WAITL("2");
                     }
                     if (g.sync_period > 0 && ++trip == g.sync_period) {
                         trip = 0;
@@ -728,18 +622,11 @@ __device__ __forceinline__ void wide_body(const SplitArgs& g) {
             W_ISSUE(KMAP(kb), 0, b0);
             W_ISSUE(KMAP(kb + 1), 1, b1);
             W_WAIT1(b0);
-            if constexpr (PP) { if (wh == 1) W_PHASE_END(); }         // the second half runs one phase behind from here on ...
             int trip = 0, sync_ix = 0;
             for (; kb < nk; kb += 3) {             // three k blocks per trip: ring indices are compile-time constants, one loop exit
-                if constexpr (PP) {
-                    W_STEP_PP(kb, 0, b0, 2, b2, b1);
-                    W_STEP_PP(kb + 1, 1, b1, 0, b0, b2);
-                    W_STEP_PP(kb + 2, 2, b2, 1, b1, b0);
-                } else {
                 W_STEP(kb, 0, b0, 2, b2, b1);
                 W_STEP(kb + 1, 1, b1, 0, b0, b2);
                 W_STEP(kb + 2, 2, b2, 1, b1, b0);
-                }
                 // long-K products: every sync_period trips the tiles of this k split wait for each other (bounded), so that the operand
                 // rows they share are fetched into the XCD's L2 once.  (The branch defines none of the ring registers: no merge copies.)
                 if (g.sync_period > 0 && ++trip == g.sync_period) {
@@ -748,20 +635,14 @@ __device__ __forceinline__ void wide_body(const SplitArgs& g) {
                     ++sync_ix;
                 }
             }
-            if constexpr (PP) { if (wh == 0) W_PHASE_END(); }         // ... to here: every wave has passed the same number of barriers
             // the surplus requests of the last two steps target registers / LDS the epilogue does not read, but they must have landed
             // before the registers are reused
-            if constexpr (BLO)
-                asm volatile("s_waitcnt vmcnt(0)" : "+v"(b0[0][0]), "+v"(b0[0][1]), "+v"(b0[1][0]), "+v"(b0[1][1]), "+v"(b1[0][0]), "+v"(b1[0][1]),
-                             "+v"(b1[1][0]), "+v"(b1[1][1])::"memory");
-            else
-                asm volatile("s_waitcnt vmcnt(0)" : "+v"(b0[0][0]), "+v"(b0[1][0]), "+v"(b1[0][0]), "+v"(b1[1][0])::"memory");
+            asm volatile("s_waitcnt vmcnt(0)" : "+v"(b0[0][0]), "+v"(b0[0][1]), "+v"(b0[1][0]), "+v"(b0[1][1]), "+v"(b1[0][0]), "+v"(b1[0][1]),
+                         "+v"(b1[1][0]), "+v"(b1[1][1])::"memory");
         }
     }
 #undef KMAP
 #undef W_STEP
-#undef W_STEP_PP
-#undef W_PHASE_END
 #undef W_MFMAS
 #undef WMMA
 #undef HF
@@ -777,178 +658,7 @@ __device__ __forceinline__ void wide_body(const SplitArgs& g) {
     const bool atomic = g.atomic != 0;
     // D = B A^T: accumulator register r of tile (x, y) is C[m0 + 32 XT wh + 32 x + (lane & 31)][n0 + 64 wq + 32 y + 8 (r >> 2) + 4 (lane >> 5) + (r & 3)]
     typedef float f32x4 __attribute__((ext_vector_type(4)));
-    if constexpr (FUSE) {
-        const mxf_fuse_args& z = g.fz;
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
-        typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-        typedef short s16x4 __attribute__((ext_vector_type(4)));
-        constexpr int RS = 40;                                   // row stride (halves) of the wave-private transposition tile [32 m][32 n]
-        // every wave has left the k loop: the A ring is dead until the next item's first request
-        asm volatile("; mxf_fz_epilogue_begin" ::: "memory"); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory");
-        if (m0 != fz_m0) {                                       // (a persistent workgroup keeps its row tile: once per launch)
-            if (fz_m0 >= 0) fz_flush_rows(fz_m0);
-            fz_m0 = m0;
-            const int mm = tid >> 1, hq = tid & 1;               // row mm of the tile, coordinates 4 hq .. + 3
-            const f32x4 zv = *reinterpret_cast<const f32x4*>(z.Zs + (m0 + mm) * 8 + 4 * hq);
-            *reinterpret_cast<f32x4*>(&fz_zf[mm * 12 + 4 * hq]) = zv;
-            if (hq == 0) { fz_zf[mm * 12 + 8] = z.Zn[m0 + mm]; fz_zf[mm * 12 + 9] = z.w[m0 + mm]; }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const _Float16 fh = (_Float16)zv[e];
-                const _Float16 fo = (_Float16)(zv[e] - (float)fh);
-                const int ix = (((mm >> 4) * 16) + 4 * hq + e) * 16 + (mm & 15);
-                fz_zb[ix] = __builtin_bit_cast(unsigned short, fh);
-                fz_zb[FZN / 2 + ix] = __builtin_bit_cast(unsigned short, fo);
-            }
-        }
-        const int64_t smp = n0 / z.B;                            // B % 256 == 0: the item's columns lie in one sample
-        {   // the item's column tables
-            const int nn = tid >> 1, hq = tid & 1;
-            const f32x4 xv = *reinterpret_cast<const f32x4*>(z.Xs + (n0 + nn) * 8 + 4 * hq);
-            *reinterpret_cast<f32x4*>(&fz_xf[nn * 8 + 4 * hq]) = xv;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const _Float16 fh = (_Float16)xv[e];
-                const _Float16 fo = (_Float16)(xv[e] - (float)fh);
-                const int ix = (((nn >> 4) * 16) + 4 * hq + e) * 16 + (nn & 15);
-                fz_xb[ix] = __builtin_bit_cast(unsigned short, fh);
-                fz_xb[FZN / 2 + ix] = __builtin_bit_cast(unsigned short, fo);
-            }
-            if (hq == 0) {
-                fz_col[nn] = z.Xn[n0 + nn] - fz_escf;
-                fz_col[256 + nn] = z.Y[smp * z.sY + (n0 + nn - smp * z.B)] - z.U[n0 + nn];
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory");
-        unsigned short* const wt = reinterpret_cast<unsigned short*>(&smem[0][0][0]) + wave * (2 * 32 * RS);      // [plane][32 m][RS]
-        const int g16 = lane >> 4, p16 = lane & 15;              // transposing read: 16-lane group (n block of 16 = g16 & 1, k half = g16 >> 1)
-        float qn = 0.f;
-        // (column fragments outside, row fragments inside: ONE column-side accumulator is live across the four row fragments, the row-side
-        //  sums of a fragment leave for LDS at once -- the 128 accumulators of T leave little room: the other order spilled 209 registers)
-#pragma unroll
-        for (int y = 0; y < 2; ++y) {
-            const int nf = 64 * wq + 32 * y;                     // first column of this fragment column inside the tile
-            const f32x4 xf = *reinterpret_cast<const f32x4*>(&fz_xf[(nf + li) * 8 + 4 * lk]);
-            f32x16 colacc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) colacc[r] = 0.f;
-#pragma unroll
-            for (int x = 0; x < XT; ++x) {
-                const int ml = 32 * XT * wh + 32 * x;            // first row of this fragment inside the tile
-                const f32x4 zf = *reinterpret_cast<const f32x4*>(&fz_zf[(ml + li) * 12 + 4 * lk]);
-                const f32x2 zw2 = *reinterpret_cast<const f32x2*>(&fz_zf[(ml + li) * 12 + 8]);
-                const float zzm = zw2[0], wmm = zw2[1];
-                f32x16 dots;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) dots[r] = 0.f;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) dots = __builtin_amdgcn_mfma_f32_32x32x2f32(xf[e], zf[e], dots, 0, 0, 0);      // [i = n][j = m], q = 4 lk + e
-                unsigned hi[8], lo[8];
-                float racc = 0.f;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const f32x4 xn4 = *reinterpret_cast<const f32x4*>(&fz_col[nf + 8 * q + 4 * lk]);
-                    const f32x4 e4 = *reinterpret_cast<const f32x4*>(&fz_col[256 + nf + 8 * q + 4 * lk]);
-                    float wv[4];
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        const float r2 = fmaf(-2.f, dots[4 * q + t], zzm + xn4[t]);
-                        const float k = __builtin_amdgcn_exp2f(-r2);                     // k 2^esc
-                        const float tv = alpha * c[x][y][4 * q + t];
-                        const float u = fmaf(wmm, e4[t], tv);
-                        wv[t] = u * k;
-                        qn = fmaf(k, tv, qn);
-                        racc = fmaf(k, e4[t], racc);
-                    }
-#pragma unroll
-                    for (int d = 0; d < 2; ++d) {
-                        const f32x2 v = {wv[2 * d], wv[2 * d + 1]};
-                        const f16x2 fh = __builtin_convertvector(v, f16x2);
-                        const f16x2 fo = __builtin_convertvector(v - __builtin_convertvector(fh, f32x2), f16x2);
-                        hi[2 * q + d] = __builtin_bit_cast(unsigned, fh); lo[2 * q + d] = __builtin_bit_cast(unsigned, fo);
-                    }
-                }
-                // quads (0, 1) and (2, 3): afterwards lane lk owns the EIGHT consecutive columns 16 c + 8 lk .. + 7 of k block c in
-                // {hi[4 c], .., hi[4 c + 3]} -- the A operand (k = n) of the row-side product
-#pragma unroll
-                for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-                    for (int d = 0; d < 2; ++d) {
-                        asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(hi[4 * cb + d]), "+v"(hi[4 * cb + 2 + d]));
-                        asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(lo[4 * cb + d]), "+v"(lo[4 * cb + 2 + d]));
-                    }
-                f32x16 rowf;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) rowf[r] = 0.f;
-#pragma unroll
-                for (int cb = 0; cb < 2; ++cb) {
-                    const u32x4 ah = {hi[4 * cb], hi[4 * cb + 1], hi[4 * cb + 2], hi[4 * cb + 3]}, al = {lo[4 * cb], lo[4 * cb + 1], lo[4 * cb + 2], lo[4 * cb + 3]};
-                    const int bix = ((((nf >> 4) + cb) * 16) + (li & 15)) * 16 + 8 * lk;
-                    const u32x4 bh = *reinterpret_cast<const u32x4*>(&fz_xb[bix]), bl = *reinterpret_cast<const u32x4*>(&fz_xb[FZN / 2 + bix]);
-                    rowf = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, al), __builtin_bit_cast(f16x8, bh), rowf, 0, 0, 0);
-                    rowf = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ah), __builtin_bit_cast(f16x8, bl), rowf, 0, 0, 0);
-                    rowf = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ah), __builtin_bit_cast(f16x8, bh), rowf, 0, 0, 0);
-                    // the same eight columns of row li into the transposition tile [m = li][n = 16 cb + 8 lk ..]
-                    *reinterpret_cast<u32x4*>(wt + li * RS + 16 * cb + 8 * lk) = ah;
-                    *reinterpret_cast<u32x4*>(wt + 32 * RS + li * RS + 16 * cb + 8 * lk) = al;
-                }
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                // column side: k = m.  16-lane group g16 = (n block of 16, k half): lane p16 fetches the 4 halves tile[m = 8 kh + 4 rr + p16 / 4]
-                // [n = 16 nb + 4 (p16 % 4) ..] and receives tile[m = 8 kh + 4 rr + 0 .. 3][n = 16 nb + p16] (ds_read_b64_tr_b16)
-#pragma unroll
-                for (int cc = 0; cc < 2; ++cc) {                 // k blocks of 16 rows m
-                    u32x4 th, tl;
-                    {
-                        const unsigned short* ph = wt + (16 * cc + 8 * (g16 >> 1) + (p16 >> 2)) * RS + 16 * (g16 & 1) + 4 * (p16 & 3);
-                        const s16x4 h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(ph));
-                        const s16x4 h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(ph + 4 * RS));
-                        const s16x4 l0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(ph + 32 * RS));
-                        const s16x4 l1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(ph + 32 * RS + 4 * RS));
-                        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-                        const u32x2 a0 = __builtin_bit_cast(u32x2, h0), a1 = __builtin_bit_cast(u32x2, h1), b0_ = __builtin_bit_cast(u32x2, l0), b1_ = __builtin_bit_cast(u32x2, l1);
-                        th = u32x4{a0[0], a0[1], a1[0], a1[1]}; tl = u32x4{b0_[0], b0_[1], b1_[0], b1_[1]};
-                    }
-                    const int zix = ((((ml >> 4) + cc) * 16) + (li & 15)) * 16 + 8 * lk;
-                    const u32x4 zh = *reinterpret_cast<const u32x4*>(&fz_zb[zix]), zl = *reinterpret_cast<const u32x4*>(&fz_zb[FZN / 2 + zix]);
-                    colacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, tl), __builtin_bit_cast(f16x8, zh), colacc, 0, 0, 0);
-                    colacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, th), __builtin_bit_cast(f16x8, zl), colacc, 0, 0, 0);
-                    colacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, th), __builtin_bit_cast(f16x8, zh), colacc, 0, 0, 0);
-                }
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                // row side of this fragment: rowf[r] = [B | S] of row ml + 8 (r >> 2) + 4 lk + (r & 3), entry j = li
-                if (li < 9) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) __hip_atomic_fetch_add(&fz_row[(ml + 8 * (r >> 2) + 4 * lk + (r & 3)) * 12 + li], rowf[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-                racc += __shfl_xor(racc, 32, 64);
-                if (lk == 0) __hip_atomic_fetch_add(&fz_row[(ml + li) * 12 + 9], racc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                __builtin_amdgcn_sched_barrier(0);       // keep the unrolled fragments apart: hoisting the next fragment's reads costs registers that are not there
-            }
-            // column side: colacc[r] = [D | C] of column nf + 8 (r >> 2) + 4 lk + (r & 3), entry j = li (this wave's 128 rows)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float Cn = __shfl(colacc[r], (lane & 32) | 8, 64);
-                const int nl = nf + 8 * (r >> 2) + 4 * lk + (r & 3);
-                if (li < z.Q) {
-                    const float xq = fz_xf[nl * 8 + li];
-                    const float pr = xq * Cn;
-                    fz_dl3 = fmaf(xq, pr, fz_dl3);
-                    if (z.dX) atomic_add(z.dX + (n0 + nl) * z.Q + li, (pr - colacc[r]) * (fz_ilj * (1.f / FZ_CS) * fz_fl));
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        {
-            double qs = (double)(qn * (fz_var * fz_unsc));
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) qs += __shfl_xor(qs, o, 64);
-            if (lane == 0) atomic_add(z.scal + 2 * smp, qs);
-        }
-        // the tables and the transposition tiles are rewritten by the next item (its first A request lands in the ring)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); asm volatile("; mxf_fz_epilogue_end" ::: "memory");
-    } else if constexpr (CPL) {
+    if constexpr (CPL) {
         // planes output: lane (li, lk) holds columns 8 q + 4 lk .. + 3 of quad q.  v_permlane32_swap trades quad q + 1 of the lanes lk = 0 for
         // quad q of the lanes lk = 1: afterwards lane lk owns EIGHT consecutive columns 8 (q + lk) .. + 7 (q even) = one 16-byte unit per
         // plane, and a store instruction covers 32 rows x 32 bytes = 1 KB contiguous of the 16-column block.
@@ -1088,12 +798,6 @@ __device__ __forceinline__ void wide_body(const SplitArgs& g) {
             }
     }
     }   // work items
-    if constexpr (FUSE) {
-        if (fz_m0 >= 0) fz_flush_rows(fz_m0);
-        float v = ((lane & 31) < g.fz.Q) ? fz_dl3 * fz_fl : 0.f;         // sum_n x_nq^2 C_n: lane (q = li) holds its share
-        v += __shfl_xor(v, 32, 64);
-        if (lane < 32 && lane < g.fz.Q) atomic_add(g.fz.dls3 + lane, (double)v);
-    }
     if (g.maxout) {                                // one atomic per wave, and only if it can raise the word (non-negative floats order as their bits)
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) cmax = fmaxf(cmax, __shfl_xor(cmax, o, 64));
@@ -1102,23 +806,13 @@ __device__ __forceinline__ void wide_body(const SplitArgs& g) {
 }
 
 // The kernels:  _128: 128 x 256 tiles, two workgroups per CU;  _256 (the default for 256-aligned shapes): 256 x 256, eight waves in two row
-// halves;  _256w4: 256 x 256 by four 512-register waves;  _256pp: eight waves, ping-pong phases.  (The last two are measured alternatives
-// kept for the probe build)
-__global__ __launch_bounds__(256, 2) void gemm_f16x2_wide_kernel_128(SplitArgs g) { wide_body<4, 1, false>(g); }
-__global__ __launch_bounds__(512, 2) void gemm_f16x2_wide_kernel_256(SplitArgs g) { wide_body<4, 2, false>(g); }
-__global__ __launch_bounds__(512, 2) void gemm_f16x2_wide_kernel_256lo(SplitArgs g) { wide_body<4, 2, false, true, true>(g); }
-#ifdef MXF_PROBES
-// measured alternatives and killed experiments: in the PROBE library only (r06; until r05 they were compiled into the shipped one)
-__global__ __launch_bounds__(256, 1) void gemm_f16x2_wide_kernel_256w4(SplitArgs g) { wide_body<8, 1, false>(g); }
-__global__ __launch_bounds__(512, 2) void gemm_f16x2_wide_kernel_256pp(SplitArgs g) { wide_body<4, 2, true>(g); }
-__global__ __launch_bounds__(512, 2) void gemm_f16x2_wide_kernel_256b1(SplitArgs g) { wide_body<4, 2, false, false>(g); }
-__global__ __launch_bounds__(512, 2) void gemm_f16x2_wide_kernel_256bf(SplitArgs g) { wide_body<4, 2, false, true, false, false, true>(g); }
-// the T product of the SVGP training call with the reverse pass as its epilogue (r05: correct, twice as slow -- 309 spilled registers)
-__global__ __launch_bounds__(512, 2) void gemm_f16x2_wide_kernel_256fz(SplitArgs g) { wide_body<4, 2, false, true, false, false, false, true>(g); }
-#endif
+// halves;  _256lo: the same for lower-only products, the waves above the diagonal idle.
+__global__ __launch_bounds__(256, 2) void gemm_f16x2_wide_kernel_128(SplitArgs g) { wide_body<1>(g); }
+__global__ __launch_bounds__(512, 2) void gemm_f16x2_wide_kernel_256(SplitArgs g) { wide_body<2>(g); }
+__global__ __launch_bounds__(512, 2) void gemm_f16x2_wide_kernel_256lo(SplitArgs g) { wide_body<2, true>(g); }
 // planes-output forms (c_blk == 2; the whitened SVGP tier's V = L^-1 Kuf)
-__global__ __launch_bounds__(512, 2) void gemm_f16x2_wide_kernel_256pl(SplitArgs g) { wide_body<4, 2, false, true, false, true>(g); }
-__global__ __launch_bounds__(256, 2) void gemm_f16x2_wide_kernel_128pl(SplitArgs g) { wide_body<4, 1, false, true, false, true>(g); }
+__global__ __launch_bounds__(512, 2) void gemm_f16x2_wide_kernel_256pl(SplitArgs g) { wide_body<2, false, true>(g); }
+__global__ __launch_bounds__(256, 2) void gemm_f16x2_wide_kernel_128pl(SplitArgs g) { wide_body<1, false, true>(g); }
 
 __global__ void split_scale_kernel(float* C, int64_t M, int64_t N, int64_t ldc, float beta, int lower_only) {
     const int64_t col = (int64_t)blockIdx.x * 256 + threadIdx.x, row = blockIdx.y;
@@ -1167,20 +861,13 @@ int mxf_gemm_split_internal(mxf_ctx* h, int64_t M, int64_t N, int64_t K, double 
                             const unsigned short* B, int64_t pB, double beta, float* C, int64_t ldc, int lower_only, hipStream_t st,
                             int reserve_cus, int mode, const float* ad0, int pow0, const unsigned* maxbits, const unsigned* maxbits2, int c_blocked,
                             unsigned* maxout, unsigned short* Cplanes, int64_t pC, int a_lower, unsigned short* Ct, int64_t pCt,
-                            const float* avec, float* Upart, const mxf_fuse_args* fuse) {
+                            const float* avec, float* Upart) {
     if (M <= 0 || N <= 0) return 0;
     SplitArgs g;
-    memset(&g.fz, 0, sizeof(g.fz));
-    if (fuse) {
-        if (mode != MXF_SPLIT_F16X2 || (M % 256) != 0 || (N % WBN) != 0 || (fuse->B % 256) != 0 || Cplanes || lower_only || beta != 0.0 || K < 128)
-            MXF_FAIL(h, -2, "mxf_gemm_split: the fused reverse pass needs the f16x2 format, M %% 256 == 0, whole 256-column tiles per sample and a plain product");
-        g.fz = *fuse;
-    }
     g.c_blk = c_blocked; g.maxout = nullptr;
     g.Cp = Cplanes; g.pC = pC; g.a_lower = a_lower; g.rot_div = 0;
     g.Ct = Ct; g.pCt = pCt; g.avec = avec; g.Upart = Upart;
-    static const int cp_nt = (int)MXF_KNOB("MXF_SPLIT_CPNT", 0);
-    g.cp_nt = cp_nt;
+    g.cp_nt = 0;
     if ((Ct && !Cplanes) || (avec && (!Ct || !Upart))) MXF_FAIL(h, -2, "mxf_gemm_split: the transposed planes come with the planes output, the partial sums with both");
     if (Cplanes) {
         if (mode != MXF_SPLIT_F16X2 || (M % 128) != 0 || (N % WBN) != 0 || beta != 0.0 || lower_only || c_blocked)
@@ -1192,29 +879,19 @@ int mxf_gemm_split_internal(mxf_ctx* h, int64_t M, int64_t N, int64_t K, double 
     g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K16 = (K + 15) / 16;
     g.pA = pA; g.pB = pB; g.ldc = ldc;
     g.alpha = (float)alpha; g.beta = (float)beta; g.lower_only = lower_only;
-    static const int nprod = (int)MXF_KNOB("MXF_SPLIT_NPROD", 6);      // diagnostic: fewer products
-    g.nprod = nprod;
-    static const int use_dma = (int)MXF_KNOB("MXF_SPLIT_DMA", 1);      // 0: staged loads instead of LDS-DMA (128 x 128 kernel)
-    g.use_dma = use_dma;
-    static const int wide_env = (int)MXF_KNOB("MXF_SPLIT_WIDE", 3);
-    // MXF_SPLIT_WIDE: 0 = never, 1 = whenever the shape allows, 2 = only the long-K lower-triangle products (Psi2), 3 (default) = those and
-    // products written in 16-column blocks (T of the training step).  The kernel's epilogue puts ROWS on lanes: fine for a blocked C
-    // (rows are 64 bytes apart) and for the small square Psi2, 16-byte pieces 4 N bytes apart for a wide row-major C -- the T shape then
-    // takes 16.7 ms instead of 13.4 on the 128 x 128 kernel, blocked it takes 12.3.  (Before the kernel walked its work items persistently
-    // the blocked T lost 1.9 ms on it as well.)
-    const bool wide = Cplanes != nullptr || fuse != nullptr ||
-                      (wide_env && (wide_env == 1 || lower_only || (wide_env == 3 && c_blocked)) && mode == MXF_SPLIT_F16X2 && g.use_dma && (M % 128) == 0 && (N % WBN) == 0 && (ldc % 4) == 0 &&
-                       (((uintptr_t)C) % 16) == 0 && g.nprod >= 3 && (!lower_only || M == N));
-    // rows per tile of the wide kernel: 256 when the shape allows, else 128 (four waves, two workgroups per CU).  MXF_SPLIT_XT: 4 = always
-    // 128; 8 = 256 rows by four 512-register waves (one per SIMD); 16 (default) = 256 rows by eight waves, two row halves (two per SIMD)
-    static const int xt_env = (int)MXF_KNOB("MXF_SPLIT_XT", 16);
-#ifdef MXF_PROBES
-    const int XT = (wide && !Cplanes && !fuse && xt_env == 8 && (M % 256) == 0) ? 8 : 4;
-#else
-    const int XT = 4;
-#endif
-    const int NH = (wide && (xt_env == 16 || Cplanes || fuse) && (M % 256) == 0) ? 2 : 1;
-    const int64_t WBMh = 32 * XT * NH;
+    g.nprod = 6;            // all six products of the three-plane format (the two-plane format's three are a subset)
+    g.use_dma = 1;
+    // the wide kernels take the planes-output products, the long-K lower-triangle products (Psi2) and the products written in 16-column
+    // blocks (T of the training step).  Their epilogue puts ROWS on lanes: fine for a blocked C (rows are 64 bytes apart) and for the small
+    // square Psi2, 16-byte pieces 4 N bytes apart for a wide row-major C -- the T shape then takes 16.7 ms instead of 13.4 on the 128 x 128
+    // kernel, blocked it takes 12.3.
+    const bool wide = Cplanes != nullptr ||
+                      ((lower_only || c_blocked) && mode == MXF_SPLIT_F16X2 && (M % 128) == 0 && (N % WBN) == 0 && (ldc % 4) == 0 &&
+                       (((uintptr_t)C) % 16) == 0 && (!lower_only || M == N));
+    // rows per tile of the wide kernel: 256 (eight waves, two row halves: two per SIMD) when the shape allows, else 128 (four waves, two
+    // workgroups per CU)
+    const int NH = (wide && (M % 256) == 0) ? 2 : 1;
+    const int64_t WBMh = 128 * NH;
     int64_t tm = (M + SBM - 1) / SBM, tn = (N + SBN - 1) / SBN;
     if (lower_only && tm != tn) MXF_FAIL(h, -2, "mxf_gemm_split: lower_only needs a square output");
     int64_t tiles = lower_only ? tm * (tm + 1) / 2 : tm * tn;
@@ -1230,7 +907,7 @@ int mxf_gemm_split_internal(mxf_ctx* h, int64_t M, int64_t N, int64_t K, double 
     // sized for the four-per-CU kernel: ~216 workgroups, one per CU on 216 CUs, whichever kernel runs.
     const int64_t slots = wide ? (reserve_cus >= 128 ? (int64_t)(256 - reserve_cus) * 4 : (int64_t)(256 - reserve_cus) * (WBMh == 256 ? 1 : 2))
                                : (int64_t)(256 - reserve_cus) * (mode == MXF_SPLIT_F16X2 ? 4 : 3);
-    if (tiles < slots && g.K16 >= 16 && !Cplanes && !fuse) {
+    if (tiles < slots && g.K16 >= 16 && !Cplanes) {
         int64_t sk = slots / tiles;
         if (sk * tiles < (slots * 3) / 4) sk = (2 * slots) / tiles;
         const int64_t maxsplit = g.K16 / 8 > 0 ? g.K16 / 8 : 1;
@@ -1244,9 +921,8 @@ int mxf_gemm_split_internal(mxf_ctx* h, int64_t M, int64_t N, int64_t K, double 
     if (splitk < 1) splitk = 1;
     g.splitk = splitk; g.kchunk = kchunk; g.atomic = splitk > 1;
     g.tm = tm; g.tn = tn; g.ntiles = tiles; g.nwg = tiles * splitk;
-    // triangular planes-output products walk PAIRS of column strips (SplitArgs::pair); MXF_SPLIT_PAIR=0 (probe builds): the r04 rotation
-    static const int pair_env = (int)MXF_KNOB("MXF_SPLIT_PAIR", 1);
-    g.pair = (wide && Cplanes && a_lower && pair_env && tm >= 2 && tn >= 2) ? 1 : 0;
+    // triangular planes-output products walk PAIRS of column strips (SplitArgs::pair)
+    g.pair = (wide && Cplanes && a_lower && tm >= 2 && tn >= 2) ? 1 : 0;
     if (g.pair) { g.ntiles = tm * ((tn + 1) / 2); g.nwg = g.ntiles; }
     g.sync = nullptr; g.sync_n = 1; g.sync_period = 0; g.sync_slots = 0;
     if (g.nwg > 2147483647LL) MXF_FAIL(h, -3, "mxf_gemm_split: grid too large");
@@ -1255,7 +931,7 @@ int mxf_gemm_split_internal(mxf_ctx* h, int64_t M, int64_t N, int64_t K, double 
         dim3 gs((unsigned)((N + 255) / 256), (unsigned)M);
         hipLaunchKernelGGL(split_scale_kernel, gs, dim3(256), 0, st, C, M, N, ldc, (float)beta, lower_only);
     }
-    const bool dma = g.use_dma && (M % SBM) == 0 && (N % SBN) == 0;
+    const bool dma = (M % SBM) == 0 && (N % SBN) == 0;
     if (wide) {
         g.maxout = (splitk == 1 && beta == 0.0 && !lower_only) ? maxout : nullptr;       // (other paths leave the word as it is: the caller sees 0)
         // persistent: as many workgroups as fit the chip (the kernel's occupancy) walk the work items; fewer items than that: one each
@@ -1265,33 +941,22 @@ int mxf_gemm_split_internal(mxf_ctx* h, int64_t M, int64_t N, int64_t K, double 
         // paired items: the tm roles of a pair must be resident in the same persistent round -- workgroups per XCD a multiple of tm
         if (g.pair && wide_grid / 8 >= tm) wide_grid = (wide_grid / 8) / tm * tm * 8;
         const int64_t grid = (wide_grid >= 8 && g.nwg > wide_grid) ? wide_grid / 8 * 8 : g.nwg;
-        // rendezvous groups (wg_rendezvous): MXF_SPLIT_SYNC 0 = none; 1 = the row tiles of one column strip (full products) / the tiles of
-        // one k split (split-K products); 2 = full products: all workgroups of an XCD, once per work item
-        static const int sync_env = (int)MXF_KNOB("MXF_SPLIT_SYNC", 1);
+        // rendezvous groups (wg_rendezvous): the row tiles of one column strip (full products) / the tiles of one k split (split-K products).
+        // Strip pairs (g.pair) go without: they stay in step by construction -- every role does tm + 1 units (r05: the pairing alone takes the
+        // fabric fetch from 21.5 to 13.5 GB, with or without a rendezvous, and the product is 0.1 ms faster without one).
         static const int sync_period_env = (int)MXF_KNOB("MXF_SPLIT_SYNC_PERIOD", 16);
-        if (g.pair) {
-            // the tm roles of a strip pair = tm consecutive items of one XCD's run, taken in the same round by tm different workgroups: they
-            // start together (bounded rendezvous, a pacing hint) and then stay in step by construction -- every role does tm + 1 units
-            // (r05 measurement: the pairing alone takes the fabric fetch from 21.5 to 13.5 GB -- with or without the rendezvous -- and the
-            //  product is 0.1 ms faster without it: 8.40 vs 8.50 ms.  Off by default; MXF_SPLIT_PAIR_SYNC=1 in probe builds.)
-            static const int pair_sync_env = (int)MXF_KNOB("MXF_SPLIT_PAIR_SYNC", 0);
-            const int64_t q = g.nwg / 8, per_xcd = grid / 8;
-            if (sync_env && pair_sync_env && g.nwg % 8 == 0 && q % tm == 0 && per_xcd >= tm && per_xcd % tm == 0) {
-                g.sync = mxf_gsync(h, (unsigned)(g.nwg / tm));
-                if (g.sync) { g.sync_n = (int)tm; g.sync_period = 0; g.sync_slots = 0; }
-            }
-        } else if (Cplanes && a_lower) {
-            g.rot_div = (grid / 8) / tm > 0 ? (grid / 8) / tm : 1;       // (no rendezvous: the row tiles of a strip carry unequal work)
-        } else if (sync_env && !lower_only && splitk == 1 && g.nwg % 8 == 0 && g.nwg >= 16) {
+        if (Cplanes && a_lower) {
+            if (!g.pair) g.rot_div = (grid / 8) / tm > 0 ? (grid / 8) / tm : 1;       // (no rendezvous: the row tiles of a strip carry unequal work)
+        } else if (!lower_only && splitk == 1 && g.nwg % 8 == 0 && g.nwg >= 16) {
             const int64_t q = g.nwg / 8, per_xcd = grid / 8;        // work items / resident workgroups per XCD
-            int64_t n = sync_env == 2 ? per_xcd : tm;
+            const int64_t n = tm;
             // a group = n consecutive work items of one XCD's run, taken in the same persistent round by n different workgroups
             const bool ok = n >= 2 && q % n == 0 && per_xcd % n == 0 && (g.nwg <= grid || g.nwg % grid == 0);
             if (ok) {
                 g.sync = mxf_gsync(h, (unsigned)(g.nwg / n));
                 g.sync_n = (int)n; g.sync_period = 0; g.sync_slots = 0;
             }
-        } else if (sync_env && splitk > 1 && g.nwg <= grid && tiles >= 2 && sync_period_env > 0) {
+        } else if (splitk > 1 && g.nwg <= grid && tiles >= 2 && sync_period_env > 0) {
             // every tile of a k split is resident at once: they meet every `period` trips of three k blocks
             const int64_t trips = kchunk / 3;
             int64_t period = sync_period_env;
@@ -1302,25 +967,9 @@ int mxf_gemm_split_internal(mxf_ctx* h, int64_t M, int64_t N, int64_t K, double 
                 g.sync_n = (int)tiles; g.sync_period = (int)period; g.sync_slots = (int)slots_per;
             }
         }
-        static const int pp_env = (int)MXF_KNOB("MXF_SPLIT_PP", 0);        // ping-pong phases of the two row halves (NH = 2)
-        static const int lskip_env = (int)MXF_KNOB("MXF_SPLIT_LSKIP", 1);  // lower-only products: the waves above the diagonal idle (see wide_body)
-        static const int bhi_env = (int)MXF_KNOB("MXF_SPLIT_BHI", 0);      // experiment: B through its high plane only, blocked-output products
-#ifdef MXF_PROBES
-        static const int bfi_env = (int)MXF_KNOB("MXF_SPLIT_BF16MFMA", 0);
-        if (bfi_env && NH == 2 && !Cplanes && !lower_only) { hipLaunchKernelGGL(gemm_f16x2_wide_kernel_256bf, dim3((unsigned)grid), dim3(512), 0, st, g); MXF_LAUNCH_CHECK(h); return 0; }
-#endif
-#ifdef MXF_PROBES
-        if (fuse) { hipLaunchKernelGGL(gemm_f16x2_wide_kernel_256fz, dim3((unsigned)grid), dim3(512), 0, st, g); MXF_LAUNCH_CHECK(h); return 0; }
-        if (!Cplanes && NH == 2 && bhi_env && c_blocked) { hipLaunchKernelGGL(gemm_f16x2_wide_kernel_256b1, dim3((unsigned)grid), dim3(512), 0, st, g); MXF_LAUNCH_CHECK(h); return 0; }
-        if (!Cplanes && NH == 2 && pp_env) { hipLaunchKernelGGL(gemm_f16x2_wide_kernel_256pp, dim3((unsigned)grid), dim3(512), 0, st, g); MXF_LAUNCH_CHECK(h); return 0; }
-        if (!Cplanes && NH != 2 && XT == 8) { hipLaunchKernelGGL(gemm_f16x2_wide_kernel_256w4, dim3((unsigned)grid), dim3(256), 0, st, g); MXF_LAUNCH_CHECK(h); return 0; }
-#else
-        if (fuse) MXF_FAIL(h, -3, "mxf_gemm_split: the fused reverse pass exists in the probe build only");
-        (void)bhi_env; (void)pp_env;
-#endif
         if (Cplanes && NH == 2) hipLaunchKernelGGL(gemm_f16x2_wide_kernel_256pl, dim3((unsigned)grid), dim3(512), 0, st, g);
         else if (Cplanes) hipLaunchKernelGGL(gemm_f16x2_wide_kernel_128pl, dim3((unsigned)grid), dim3(256), 0, st, g);
-        else if (NH == 2 && lower_only && lskip_env) hipLaunchKernelGGL(gemm_f16x2_wide_kernel_256lo, dim3((unsigned)grid), dim3(512), 0, st, g);
+        else if (NH == 2 && lower_only) hipLaunchKernelGGL(gemm_f16x2_wide_kernel_256lo, dim3((unsigned)grid), dim3(512), 0, st, g);
         else if (NH == 2) hipLaunchKernelGGL(gemm_f16x2_wide_kernel_256, dim3((unsigned)grid), dim3(512), 0, st, g);
         else hipLaunchKernelGGL(gemm_f16x2_wide_kernel_128, dim3((unsigned)grid), dim3(256), 0, st, g);
         MXF_LAUNCH_CHECK(h);

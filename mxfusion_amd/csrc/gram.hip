@@ -412,19 +412,12 @@ int launch_kind(mxf_ctx* h, GramArgs<T> a, int S, int mode, hipStream_t st) {
         return 0;
     }
     a.vecst = (a.ldk % VEC == 0) && (a.sK % VEC == 0) && (((uintptr_t)a.K) % 16 == 0);
-    // tuning knobs (A/B probes): rows per block, waves per block, store flavour.  Defaults measured on MI355X at N=65536, Q=8
-    // (tests/probes/gram_variants.hip, tests/probes/gram_time.py): single-wave workgroups of 16 rows.
-    static const int tr_env = MXF_KNOB("MXF_GRAM_TR", 0);
-    static const int nw_env = MXF_KNOB("MXF_GRAM_NW", 0);
-    static const int nt_env = MXF_KNOB("MXF_GRAM_NT", -1);
-    // f32 RBF: 16 rows (6.05 TB/s; 32: 5.75, 64: 5.29, 8: 5.27); the VALU-heavier epilogues (Matern, all float64) prefer 64 (f64 RBF 5.25 vs 5.13)
-    // (float64 RBF in the expansion form, gram_lean_kernel XF: 16 rows 5.71 ms = 6.02 TB/s, 32: 5.95, 64: 6.36 ms)
-    static const int xf_tr = MXF_KNOB("MXF_GRAM_F64_EXPAND", 1);
-    // (r03: float32 RBF 12 rows as a compile-time constant with the diagonal term hoisted, gram_lean_kernel TRC: between equal and +4 % against 16)
-    a.tr = (tr_env == 8 || tr_env == 12 || tr_env == 16 || tr_env == 32 || tr_env == 64) ? tr_env : ((KIND == MXF_K_RBF && sizeof(T) == 4) ? 12 : (KIND == MXF_K_RBF && xf_tr) ? 16 : 64);
-    a.nt = (nt_env >= 0) ? nt_env : 1;
-    const int NW = (nw_env == 1 || nw_env == 4) ? nw_env : 1;
-    const int64_t cw = (int64_t)NW * 64 * VEC;          // columns per workgroup
+    // rows per block, measured on MI355X at N=65536, Q=8 (tests/probes/gram_variants.hip, tests/probes/gram_time.py): single-wave workgroups;
+    // float32 RBF 12 rows as a compile-time constant with the diagonal term hoisted (gram_lean_kernel TRC); float64 RBF in the expansion form
+    // (gram_lean_kernel XF) 16 rows (5.71 ms = 6.02 TB/s, 32: 5.95, 64: 6.36 ms); the VALU-heavier epilogues (Matern, ...) 64
+    a.tr = (KIND == MXF_K_RBF && sizeof(T) == 4) ? 12 : (KIND == MXF_K_RBF ? 16 : 64);
+    a.nt = 1;
+    const int64_t cw = 64 * VEC;                        // columns per workgroup
     a.ncb = (unsigned)((a.N2 + cw - 1) / cw);
     const int64_t nblk = (int64_t)a.ncb * ((a.N + a.tr - 1) / a.tr);
     if (nblk > 2147483647LL) MXF_FAIL(h, -3, "mxf_gram: problem too large for one launch");
@@ -432,10 +425,8 @@ int launch_kind(mxf_ctx* h, GramArgs<T> a, int S, int mode, hipStream_t st) {
 #define GO(QT)                                                                                                        \
     do {                                                                                                              \
         const bool fast = a.vecst && mode == MXF_WRITE && a.nt && (a.N2 % VEC == 0);                                  \
-        static const int lean_env = MXF_KNOB("MXF_GRAM_LEAN", 1);                     \
-        static const int xf_env = MXF_KNOB("MXF_GRAM_F64_EXPAND", 1);           \
-        const bool lean_ok = NW == 1 && fast && lean_env && KIND != MXF_K_BIAS && KIND != MXF_K_WHITE && (a.N + a.tr - 1) / a.tr <= 65535; \
-        const bool xf = lean_ok && sizeof(T) == 8 && KIND == MXF_K_RBF && xf_env;                                     \
+        const bool lean_ok = fast && KIND != MXF_K_BIAS && KIND != MXF_K_WHITE && (a.N + a.tr - 1) / a.tr <= 65535; \
+        const bool xf = lean_ok && sizeof(T) == 8 && KIND == MXF_K_RBF;                                               \
         T* xnorm = nullptr; T* znorm = nullptr; int64_t sxn = 0, szn = 0;                                             \
         if (KIND != MXF_K_BIAS && KIND != MXF_K_WHITE) {                                                              \
             const int64_t padr = (a.N + TR - 1) / TR * TR, padc = (a.N2 + 4 * 64 * VEC - 1) / (4 * 64 * VEC) * (4 * 64 * VEC); \
@@ -471,19 +462,13 @@ int launch_kind(mxf_ctx* h, GramArgs<T> a, int S, int mode, hipStream_t st) {
             l.has_diag = ((hd || l.jitter != (T)0) ? 1 : 0) | ((xf && a.square) ? 2 : 0); l.sXn = sxn; l.sZn = szn;   \
             const T* dptr = hd ? a.dadd : (a.var ? a.var : a.Xs);          /* any readable word when there is no diagonal term */ \
             dim3 gl(a.ncb, (unsigned)((a.N + a.tr - 1) / a.tr), (unsigned)S);                                         \
-            if constexpr (sizeof(T) == 8 && KIND == MXF_K_RBF) {                                                      \
-                if (xf && a.tr == 16) hipLaunchKernelGGL((gram_lean_kernel<T, QT, KIND, 1, 16>), gl, dim3(64), 0, st, a.Xs, a.Zs, a.K, a.var, dptr, (const T*)xnorm, (const T*)znorm, l); \
-                else if (xf) hipLaunchKernelGGL((gram_lean_kernel<T, QT, KIND, 1, 0>), gl, dim3(64), 0, st, a.Xs, a.Zs, a.K, a.var, dptr, (const T*)xnorm, (const T*)znorm, l); \
-                else hipLaunchKernelGGL((gram_lean_kernel<T, QT, KIND, 0, 0>), gl, dim3(64), 0, st, a.Xs, a.Zs, a.K, a.var, dptr, (const T*)nullptr, (const T*)nullptr, l); \
-            } else if constexpr (sizeof(T) == 4 && KIND == MXF_K_RBF) {                                               \
-                if (a.tr == 12) hipLaunchKernelGGL((gram_lean_kernel<T, QT, KIND, 0, 12>), gl, dim3(64), 0, st, a.Xs, a.Zs, a.K, a.var, dptr, (const T*)nullptr, (const T*)nullptr, l); \
-                else if (a.tr == 16) hipLaunchKernelGGL((gram_lean_kernel<T, QT, KIND, 0, 16>), gl, dim3(64), 0, st, a.Xs, a.Zs, a.K, a.var, dptr, (const T*)nullptr, (const T*)nullptr, l); \
-                else hipLaunchKernelGGL((gram_lean_kernel<T, QT, KIND, 0, 0>), gl, dim3(64), 0, st, a.Xs, a.Zs, a.K, a.var, dptr, (const T*)nullptr, (const T*)nullptr, l); \
-            } else hipLaunchKernelGGL((gram_lean_kernel<T, QT, KIND, 0, 0>), gl, dim3(64), 0, st, a.Xs, a.Zs, a.K, a.var, dptr, (const T*)nullptr, (const T*)nullptr, l); \
-        } else if (NW == 1 && fast) hipLaunchKernelGGL((gram_kernel<T, QT, KIND, 1, true>), g, dim3(64), 0, st, a, a.Xs, a.Zs, a.K); \
-        else if (NW == 1) hipLaunchKernelGGL((gram_kernel<T, QT, KIND, 1, false>), g, dim3(64), 0, st, a, a.Xs, a.Zs, a.K);            \
-        else if (fast) hipLaunchKernelGGL((gram_kernel<T, QT, KIND, 4, true>), g, dim3(256), 0, st, a, a.Xs, a.Zs, a.K);               \
-        else hipLaunchKernelGGL((gram_kernel<T, QT, KIND, 4, false>), g, dim3(256), 0, st, a, a.Xs, a.Zs, a.K);                        \
+            if constexpr (sizeof(T) == 8 && KIND == MXF_K_RBF)                                                        \
+                hipLaunchKernelGGL((gram_lean_kernel<T, QT, KIND, 1, 16>), gl, dim3(64), 0, st, a.Xs, a.Zs, a.K, a.var, dptr, (const T*)xnorm, (const T*)znorm, l); \
+            else if constexpr (sizeof(T) == 4 && KIND == MXF_K_RBF)                                                   \
+                hipLaunchKernelGGL((gram_lean_kernel<T, QT, KIND, 0, 12>), gl, dim3(64), 0, st, a.Xs, a.Zs, a.K, a.var, dptr, (const T*)nullptr, (const T*)nullptr, l); \
+            else hipLaunchKernelGGL((gram_lean_kernel<T, QT, KIND, 0, 0>), gl, dim3(64), 0, st, a.Xs, a.Zs, a.K, a.var, dptr, (const T*)nullptr, (const T*)nullptr, l); \
+        } else if (fast) hipLaunchKernelGGL((gram_kernel<T, QT, KIND, 1, true>), g, dim3(64), 0, st, a, a.Xs, a.Zs, a.K); \
+        else hipLaunchKernelGGL((gram_kernel<T, QT, KIND, 1, false>), g, dim3(64), 0, st, a, a.Xs, a.Zs, a.K);                         \
     } while (0)
     if (KIND == MXF_K_BIAS || KIND == MXF_K_WHITE) GO(2);
     else if (a.Q <= 2) GO(2);
@@ -495,128 +480,23 @@ int launch_kind(mxf_ctx* h, GramArgs<T> a, int S, int mode, hipStream_t st) {
     return 0;
 }
 
-// ---- Gram matrix written as split planes (the operand formats of gemm_split.hip: NP = 3 bf16 terms, NP = 2 scaled f16 terms) ----------
+// ---- Gram matrix written as split planes (the f16x2 operand format of gemm_split.hip: two scaled f16 terms) ---------------------------
 // operand element (r, k) = cov(xmin[r], xmaj[k]); plane p element (r, k) at ((k / 16) * R + r) * 16 + k % 16.
-// Thread <-> (minor index r, k half): per 16-wide k block a thread evaluates 8 covariances, splits each f32 value exactly into
-// h + m + l (bf16 each) and writes ONE 16-byte unit per plane; a wave writes 1 KB contiguous per plane per k block.
-// HBM-write bound: 2 NP bytes per element (8.6 GB at M = 1024 x 2.1 M columns for NP = 2).
+// HBM-write bound: 4 bytes per element (8.6 GB at M = 1024 x 2.1 M columns).
 typedef unsigned int gp_u32x4 __attribute__((ext_vector_type(4)));
-// NP = 2 (f16x2 format of gemm_split.hip): the planes hold cov / variance * 2^14 as hi + lo (f16 each); the consumer multiplies by
-// variance * 2^-14 (unit-variance covariances are <= 1, so the format's power-of-two scale is known without a reduction).
+// The planes hold cov / variance * 2^14 as hi + lo (f16 each); the consumer multiplies by variance * 2^-14 (unit-variance covariances
+// are <= 1, so the format's power-of-two scale is known without a reduction).
 // PT > 0: the same pass also forms  U[p][r] = sum_k w[k][p] cov(xmin[r], xmaj[k])  (the row w^T Kuf of the SVGP step, svgp_regression.py:98:
 // Kuf^T Kuu^-1 mu) from the f32 covariances it has in registers -- the separate 8.6 GB read of the planes that product used to cost
 // (1.45 ms at the bench size) is gone.  Needs grid.y == 1 (every block walks all k blocks of its rows).
-template <int QT, int KIND, int NP, int PT>
-__global__ __launch_bounds__(256) void gram_planes_kernel(int64_t R, int64_t Kn, const float* __restrict__ Xmin_s, const float* __restrict__ Xmaj_s,
-                                                          const float* __restrict__ var, unsigned short* __restrict__ P, int64_t pstride,
-                                                          int chunks_per_block, const float* __restrict__ wk, int Pw, float* __restrict__ U,
-                                                          int64_t ldU) {
-    constexpr int CH = 16;                                   // k blocks per staged chunk (256 major points)
-    __shared__ __attribute__((aligned(16))) float xs[CH * 16 * QT];
-    __shared__ float ws[PT > 0 ? CH * 16 * PT : 1];          // w of the staged chunk, [k][p]
-    float uacc[PT > 0 ? PT : 1];
-#pragma unroll
-    for (int p = 0; p < (PT > 0 ? PT : 1); ++p) uacc[p] = 0.f;
-    const int tid = threadIdx.x, rl = tid >> 1, half = tid & 1;
-    const int64_t r = (int64_t)blockIdx.x * 128 + rl;
-    const bool rvalid = r < R;
-    const float variance = NP == 2 ? 16384.f : var[0];
-    float z[QT];
-#pragma unroll
-    for (int q = 0; q < QT; q += 4) *reinterpret_cast<f32x4_t*>(&z[q]) = *reinterpret_cast<const f32x4_t*>(Xmin_s + r * QT + q);   // padded
-    const int64_t K16 = (Kn + 15) / 16;
-    for (int c = 0; c < chunks_per_block; ++c) {
-        const int64_t kb0 = ((int64_t)blockIdx.y * chunks_per_block + c) * CH;
-        if (kb0 >= K16) break;
-        __syncthreads();
-        for (int i = tid * 4; i < CH * 16 * QT; i += 256 * 4)
-            *reinterpret_cast<f32x4_t*>(&xs[i]) = *reinterpret_cast<const f32x4_t*>(Xmaj_s + kb0 * 16 * QT + i);                   // padded
-        if (PT > 0) {
-            for (int i = tid; i < CH * 16 * PT; i += 256) {
-                const int64_t k = kb0 * 16 + i / PT;
-                const int p = i % PT;
-                ws[i] = (k < Kn && p < Pw) ? wk[k * Pw + p] : 0.f;
-            }
-        }
-        __syncthreads();
-        const int nkb = (int)((K16 - kb0) < CH ? (K16 - kb0) : CH);
-        // (FULL: every major point of the chunk exists -- always, when Kn is a multiple of 16 -- so the per-element range test, a 64-bit
-        //  compare + select per covariance, 8 % of the kernel's instructions, is compiled out)
-        auto chunk_body = [&](auto full_c) {
-        constexpr bool FULL = decltype(full_c)::value;
-        for (int kbl = 0; kbl < nkb; ++kbl) {
-            gp_u32x4 uh, um, ul;
-#pragma unroll
-            for (int j = 0; j < 8; j += 2) {
-                float kv[2];
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const int nl = kbl * 16 + half * 8 + j + e;
-                    typedef float f32x2 __attribute__((ext_vector_type(2)));
-                    f32x2 acc2 = {0.f, 0.f};
-#pragma unroll
-                    for (int q = 0; q < QT; q += 2) {
-                        const f32x2 xx = {xs[nl * QT + q], xs[nl * QT + q + 1]};
-                        const f32x2 zz = {z[q], z[q + 1]};
-                        const f32x2 d = xx - zz;
-                        acc2 = __builtin_elementwise_fma(d, d, acc2);
-                    }
-                    const float red = acc2.x + acc2.y;
-                    kv[e] = (FULL || kb0 * 16 + nl < Kn) ? cov_from<float, KIND>(red, variance) : 0.f;
-                    if (PT > 0) {
-#pragma unroll
-                        for (int p = 0; p < PT; ++p) uacc[p] = fmaf(ws[nl * PT + p], kv[e], uacc[p]);
-                    }
-                }
-                unsigned hh = 0, mm = 0, ll = 0;
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    if (NP == 2) {
-                        const _Float16 fh = (_Float16)kv[e];
-                        const _Float16 fl = (_Float16)(kv[e] - (float)fh);
-                        hh |= (unsigned)__builtin_bit_cast(unsigned short, fh) << (16 * e);
-                        mm |= (unsigned)__builtin_bit_cast(unsigned short, fl) << (16 * e);
-                        continue;
-                    }
-                    const __bf16 bh = (__bf16)kv[e];
-                    const float r1 = kv[e] - (float)bh;
-                    const __bf16 bm = (__bf16)r1;
-                    const float r2 = r1 - (float)bm;
-                    const __bf16 bl = (__bf16)r2;
-                    hh |= (unsigned)__builtin_bit_cast(unsigned short, bh) << (16 * e);
-                    mm |= (unsigned)__builtin_bit_cast(unsigned short, bm) << (16 * e);
-                    ll |= (unsigned)__builtin_bit_cast(unsigned short, bl) << (16 * e);
-                }
-                uh[j / 2] = hh; um[j / 2] = mm; ul[j / 2] = ll;
-            }
-            if (rvalid) {
-                unsigned short* dst = P + ((kb0 + kbl) * R + r) * 16 + half * 8;
-                __builtin_nontemporal_store(uh, reinterpret_cast<gp_u32x4*>(dst));
-                __builtin_nontemporal_store(um, reinterpret_cast<gp_u32x4*>(dst + pstride));
-                if (NP == 3) __builtin_nontemporal_store(ul, reinterpret_cast<gp_u32x4*>(dst + 2 * pstride));
-            }
-        }
-        };
-        if ((kb0 + nkb) * 16 <= Kn) chunk_body(std::true_type{}); else chunk_body(std::false_type{});
-    }
-    if (PT > 0) {      // the two threads of a row hold the two k halves: fold them, undo the plane scaling, one store per (row, p)
-        const float sc = NP == 2 ? var[0] * (1.f / 16384.f) : 1.f;
-#pragma unroll
-        for (int p = 0; p < PT; ++p) {
-            const float v = uacc[p] + __shfl_xor(uacc[p], 1, 64);
-            if (half == 0 && rvalid && p < Pw) U[(int64_t)p * ldU + r] = v * sc;
-        }
-    }
-}
-
-// (r03) NP = 2 as ONE-WAVE workgroups, lane <-> minor index r (64 rows per wave), the sixteen major points of a k block wave-uniform
+// (r03) ONE-WAVE workgroups, lane <-> minor index r (64 rows per wave), the sixteen major points of a k block wave-uniform
 // (scalar loads, no LDS staging, no barrier -- the layout of gram_lean_kernel).  A lane evaluates the 16 covariances of its row, i.e. BOTH
 // 16-byte halves of its 32-byte piece; v_permlane32_swap then trades half 1 of the rows of lanes 0..31 for half 0 of the rows of lanes
 // 32..63, so each of the two store instructions per plane covers 1 KB CONTIGUOUS (32 rows x 32 bytes).  (Without the swap each store
 // covers 16-byte pieces at a 32-byte stride: measured r02, 30 -> 40 ms per step.)  hi + lo come from the packed conversions
 // (v_cvt_pk_f16_f32: a plane's dword directly); the fused row U sums its sixteen terms per k block in index order.
-// Measured (tests/probes/planes_lean.sh, planes_store.hip): 1.82 / 1.69 ms for the two 8.6 GB passes of the bench step, the same as the staged
-// kernel -- neither the LDS staging nor the VALU count (16 -> 14 instructions per covariance here) is what bounds them; the store-only twin
+// Measured (planes_store.hip): 1.82 / 1.69 ms for the two 8.6 GB passes of the bench step, the same as the r02 staged kernel (LDS, 256
+// threads, a thread <-> (row, k half)) -- neither the LDS staging nor the VALU count (16 -> 14 instructions per covariance here) is what bounds them; the store-only twin
 // of the same pattern takes 1.45 - 1.65 ms alone, memset 1.36 ms; PLAIN instead of non-temporal stores: 2.1 - 2.4 ms inside the step.
 // ACC (r04): the squared distance as sum_q ((x_q - z_q)^2) (c / l_q)^2 from the RAW coordinates -- difference first, scale after -- instead of
 // the difference of pre-scaled coordinates: the rounding of x / l (2^-24 |x / l|) no longer enters r^2 of NEAR pairs, the ones that carry the
@@ -635,16 +515,13 @@ __global__ __launch_bounds__(256) void gram_planes_kernel(int64_t R, int64_t Kn,
 #else
 #define MXF_PLANES_OCC
 #endif
-template <int QT, int KIND, int PT, bool ACC = false, bool PERS = false>
+template <int QT, int KIND, int PT, bool ACC = false>
 __global__ __launch_bounds__(64) MXF_PLANES_OCC void gram_planes_lean_kernel(int64_t R, int64_t Kn, const float* __restrict__ Xmin_s, const float* __restrict__ Xmaj_s,
                                                               const float* __restrict__ var, unsigned short* __restrict__ P, int64_t pstride,
                                                               int kb_per_block, const float* __restrict__ wk, int Pw, float* __restrict__ U,
                                                               int64_t ldU, const float* __restrict__ ls = nullptr, int ard = 0, int Q = 0,
                                                               const float* __restrict__ majs = nullptr, const float* __restrict__ mins = nullptr,
-                                                              int64_t period = 1, int64_t pnbx = 0, int pnby = 0) {
-    // pnbx > 0 (r06, PT == 0 only): PERSISTENT form -- gridDim.x waves walk the pnbx x pnby (row block, k chunk) items, row block fastest.  The
-    // launcher sizes the grid to fewer waves than the chip holds, so that the float64 workgroups of the Kuu chain that runs next to this pass
-    // (four waves + LDS each) find room on every CU instead of waiting for four wave slots of one CU to drain at the same moment.
+                                                              int64_t period = 1) {
     // majs / mins (ACC form only; the streaming heteroscedastic SVGP bound, svgp_regression.py:61-67): every covariance is multiplied by
     // majs[major index % period] (wave-uniform) and / or mins[minor index % period] (per lane) before it is split into planes -- and before
     // it enters the fused row U -- i.e. the planes hold K diag(s) resp. diag(s) K for per-row weights s <= 1
@@ -657,11 +534,8 @@ __global__ __launch_bounds__(64) MXF_PLANES_OCC void gram_planes_lean_kernel(int
             s2[q] = m * m;
         }
     }
-    constexpr bool pers = PERS && PT == 0;      // (a compile-time form: the loop around the body cost the plain instance 7 % -- 1.72 -> 1.85 ms in the step)
-    int64_t item = blockIdx.x;
-    do {
-    const int64_t bxi = pers ? item % pnbx : (int64_t)blockIdx.x;
-    const int byi = pers ? (int)(item / pnbx) : (int)blockIdx.y;
+    const int64_t bxi = blockIdx.x;
+    const int byi = blockIdx.y;
     const int64_t r0 = bxi * 64, r = r0 + lane;
     float z[QT];
 #pragma unroll
@@ -748,8 +622,6 @@ __global__ __launch_bounds__(64) MXF_PLANES_OCC void gram_planes_lean_kernel(int
             for (int p = 0; p < PT; ++p) if (p < Pw) U[(int64_t)p * ldU + r] = uacc[p] * sc;
         }
     }
-    item += gridDim.x;
-    } while (pers && item < pnbx * (int64_t)pnby);
 }
 
 template <int KIND>
@@ -760,65 +632,26 @@ int gram_planes_kind(mxf_ctx* h, int64_t R, int64_t Kn, int Q, const float* Xmin
     const int64_t padr = (R + 127) / 128 * 128, padk = ((Kn + 15) / 16 + 15) / 16 * 256;
     float* buf = scratch;     // (padr + padk) * QT floats, caller-owned: two of these run concurrently on different streams
     float* bmaj = buf + (size_t)padr * QT;
-    const int64_t K16 = (Kn + 15) / 16, chunks = (K16 + 15) / 16, rblocks = padr / 128;
-    int cpb = 1;
-    while (rblocks * ((chunks + cpb - 1) / cpb) > 16384 && cpb < chunks) cpb *= 2;      // fewer, longer blocks once the chip is full
+    const int64_t K16 = (Kn + 15) / 16;
     const bool fuse_u = U != nullptr;
-    if (fuse_u) {
-        if (Pw > 8 || !wk) MXF_FAIL(h, -3, "gram planes: fused w^T K needs w and P <= 8");
-        cpb = (int)chunks;                                                              // every block walks all k blocks of its rows
-    }
-    dim3 grid((unsigned)rblocks, (unsigned)((chunks + cpb - 1) / cpb));
-    if (grid.y > 65535u) MXF_FAIL(h, -3, "gram planes: grid too large");
-    // (measured and dropped: one-wave workgroups with lane <-> row and the k-side points through scalar loads, as in the Gram kernel -- each
-    //  store instruction then covers 16-byte pieces at a 32-byte stride and the step went from 30.1 to 40.0 ms; the (row, k half) <-> thread
-    //  mapping below writes whole lines per instruction)
-    // r03: the one-wave form for the f16x2 planes (probe builds: MXF_PLANES_LEAN=0 selects the staged kernel)
-    const bool lean = mode == MXF_SPLIT_F16X2 && MXF_KNOB("MXF_PLANES_LEAN", 1) != 0;
-    const int raw = (lean && MXF_KNOB("MXF_PLANES_ACC", 1) != 0) ? 1 : 0;       // difference-then-scale distances (gram_planes_lean_kernel ACC)
-    if ((majs || mins) && !raw) MXF_FAIL(h, -3, "gram planes: per-row weights need the f16x2 lean kernel");
+    if (fuse_u && (Pw > 8 || !wk)) MXF_FAIL(h, -3, "gram planes: fused w^T K needs w and P <= 8");
+    if (mode != MXF_SPLIT_F16X2) MXF_FAIL(h, -3, "gram planes: the f16x2 format only");
+    const int raw = 1;                // difference-then-scale distances (gram_planes_lean_kernel ACC)
     int kbpb = fuse_u ? (int)K16 : (int)MXF_KNOB("MXF_PLANES_KB", 8);
     while (!fuse_u && (K16 + kbpb - 1) / kbpb > 65535) kbpb *= 2;
     dim3 lgrid((unsigned)((R + 63) / 64), (unsigned)((K16 + kbpb - 1) / kbpb));
-    // MXF_PLANES_PERSIST = w > 0 (r06, probe builds): the pass as w persistent waves per CU (gram_planes_lean_kernel pnbx) once it has more items than
-    // that.  Measured and NOT kept (same box, alternating, tests/probes/r06_planes_persist.sh; parity tests pass with it): whitened 32-sample step
-    // 31.4-31.6 ms without, 31.3-31.7 with 28 waves per CU, 31.9 with 16, 34 with 24; the explicit 32-sample step 22.5-22.9 -> 24.5-24.8 (28) --
-    // the chain next to the pass does not get faster and the pass itself loses its dispatch-order store pattern.
-    static const int pers_env = (int)MXF_KNOB("MXF_PLANES_PERSIST", 0);
-    int64_t pers_grid = 0;
-    if (pers_env > 0 && !fuse_u && (int64_t)lgrid.x * lgrid.y > (int64_t)256 * pers_env * 2) pers_grid = (int64_t)256 * pers_env;
 #define GO(QTV)                                                                                                                       \
     do {                                                                                                                              \
         hipLaunchKernelGGL((prescale_kernel<float, QTV, KIND>), dim3((unsigned)((padr * QTV + 255) / 256), 1), dim3(256), 0, st, Xmin, (int64_t)0, ls, \
                            (int64_t)0, ard, R, Q, padr, buf, (float*)nullptr, raw);                                                   \
         hipLaunchKernelGGL((prescale_kernel<float, QTV, KIND>), dim3((unsigned)((padk * QTV + 255) / 256), 1), dim3(256), 0, st, Xmaj, (int64_t)0, ls, \
                            (int64_t)0, ard, Kn, Q, padk, bmaj, (float*)nullptr, raw);                                                 \
-        if (lean && raw && fuse_u && Pw == 1)                                                                                         \
+        if (fuse_u && Pw == 1)                                                                                                        \
             hipLaunchKernelGGL((gram_planes_lean_kernel<QTV, KIND, 1, true>), lgrid, dim3(64), 0, st, R, Kn, (const float*)buf, (const float*)bmaj, var, planes, pstride, kbpb, wk, Pw, U, ldU, ls, ard, Q, majs, mins, period); \
-        else if (lean && raw && fuse_u)                                                                                               \
-            hipLaunchKernelGGL((gram_planes_lean_kernel<QTV, KIND, 8, true>), lgrid, dim3(64), 0, st, R, Kn, (const float*)buf, (const float*)bmaj, var, planes, pstride, kbpb, wk, Pw, U, ldU, ls, ard, Q, majs, mins, period); \
-        else if (lean && raw && pers_grid > 0)                                                                                        \
-            hipLaunchKernelGGL((gram_planes_lean_kernel<QTV, KIND, 0, true, true>), dim3((unsigned)pers_grid), dim3(64), 0, st, R, Kn, (const float*)buf, (const float*)bmaj, var, planes, pstride, kbpb, wk, Pw, U, ldU, ls, ard, Q, majs, mins, period, (int64_t)lgrid.x, (int)lgrid.y); \
-        else if (lean && raw)                                                                                                         \
-            hipLaunchKernelGGL((gram_planes_lean_kernel<QTV, KIND, 0, true>), lgrid, dim3(64), 0, st, R, Kn, (const float*)buf, (const float*)bmaj, var, planes, pstride, kbpb, wk, Pw, U, ldU, ls, ard, Q, majs, mins, period); \
-        else if (lean && fuse_u && Pw == 1)                                                                                           \
-            hipLaunchKernelGGL((gram_planes_lean_kernel<QTV, KIND, 1>), lgrid, dim3(64), 0, st, R, Kn, (const float*)buf, (const float*)bmaj, var, planes, pstride, kbpb, wk, Pw, U, ldU); \
-        else if (lean && fuse_u)                                                                                                      \
-            hipLaunchKernelGGL((gram_planes_lean_kernel<QTV, KIND, 8>), lgrid, dim3(64), 0, st, R, Kn, (const float*)buf, (const float*)bmaj, var, planes, pstride, kbpb, wk, Pw, U, ldU); \
-        else if (lean)                                                                                                                \
-            hipLaunchKernelGGL((gram_planes_lean_kernel<QTV, KIND, 0>), lgrid, dim3(64), 0, st, R, Kn, (const float*)buf, (const float*)bmaj, var, planes, pstride, kbpb, wk, Pw, U, ldU); \
-        else if (mode == MXF_SPLIT_F16X2 && fuse_u && Pw == 1)                                                                             \
-            hipLaunchKernelGGL((gram_planes_kernel<QTV, KIND, 2, 1>), grid, dim3(256), 0, st, R, Kn, (const float*)buf, (const float*)bmaj, var, planes, pstride, cpb, wk, Pw, U, ldU); \
-        else if (mode == MXF_SPLIT_F16X2 && fuse_u)                                                                                   \
-            hipLaunchKernelGGL((gram_planes_kernel<QTV, KIND, 2, 8>), grid, dim3(256), 0, st, R, Kn, (const float*)buf, (const float*)bmaj, var, planes, pstride, cpb, wk, Pw, U, ldU); \
-        else if (mode == MXF_SPLIT_F16X2)                                                                                             \
-            hipLaunchKernelGGL((gram_planes_kernel<QTV, KIND, 2, 0>), grid, dim3(256), 0, st, R, Kn, (const float*)buf, (const float*)bmaj, var, planes, pstride, cpb, wk, Pw, U, ldU); \
-        else if (fuse_u && Pw == 1)                                                                                                   \
-            hipLaunchKernelGGL((gram_planes_kernel<QTV, KIND, 3, 1>), grid, dim3(256), 0, st, R, Kn, (const float*)buf, (const float*)bmaj, var, planes, pstride, cpb, wk, Pw, U, ldU); \
         else if (fuse_u)                                                                                                              \
-            hipLaunchKernelGGL((gram_planes_kernel<QTV, KIND, 3, 8>), grid, dim3(256), 0, st, R, Kn, (const float*)buf, (const float*)bmaj, var, planes, pstride, cpb, wk, Pw, U, ldU); \
+            hipLaunchKernelGGL((gram_planes_lean_kernel<QTV, KIND, 8, true>), lgrid, dim3(64), 0, st, R, Kn, (const float*)buf, (const float*)bmaj, var, planes, pstride, kbpb, wk, Pw, U, ldU, ls, ard, Q, majs, mins, period); \
         else                                                                                                                          \
-            hipLaunchKernelGGL((gram_planes_kernel<QTV, KIND, 3, 0>), grid, dim3(256), 0, st, R, Kn, (const float*)buf, (const float*)bmaj, var, planes, pstride, cpb, wk, Pw, U, ldU); \
+            hipLaunchKernelGGL((gram_planes_lean_kernel<QTV, KIND, 0, true>), lgrid, dim3(64), 0, st, R, Kn, (const float*)buf, (const float*)bmaj, var, planes, pstride, kbpb, wk, Pw, U, ldU, ls, ard, Q, majs, mins, period); \
     } while (0)
     if (QT == 8) GO(8); else GO(16);
 #undef GO
@@ -877,8 +710,8 @@ extern "C" int mxf_gram(mxf_handle h, int kind, int dtype, int S, int64_t N, int
     MXF_FAIL(h, -2, "mxf_gram: bad dtype %d", dtype);
 }
 
-// Gram matrix cov(xmin[r], xmaj[k]) (r < R, k < Kn) as split planes in either format (float32 inputs, stationary kernels); see
-// gram_planes_kernel.  planes: 3 * pstride elements, pstride = mxf_split_plane_elems(R, Kn).
+// Gram matrix cov(xmin[r], xmaj[k]) (r < R, k < Kn) as split planes in the f16x2 format (float32 inputs, stationary kernels); see
+// gram_planes_lean_kernel.  planes: 2 * pstride elements, pstride = mxf_split_plane_elems(R, Kn).
 size_t mxf_gram_planes_scratch_bytes(int64_t R, int64_t Kn, int Q) {
     const int QT = Q <= 8 ? 8 : 16;
     const int64_t padr = (R + 127) / 128 * 128, padk = ((Kn + 15) / 16 + 15) / 16 * 256;

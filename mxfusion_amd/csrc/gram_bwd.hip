@@ -471,35 +471,9 @@ __device__ __forceinline__ void split4(const float (&x)[4], bw_f16x4& hi, bw_f16
     lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x4), bw_f16x4);
 }
 
-// LDS-DMA requests of the DMAT form below (inline asm: the compiler neither tracks nor waits for them -- the waits are counted by hand)
-//   bw_dma16: 64 lanes x 16 bytes from sbase + voff (wave-uniform base in SGPRs, per-lane byte offset) to the KB at LDS byte address lds
-//   bw_dma4 / bw_dma4v: 64 lanes x 4 bytes to the 256 bytes at lds; the v form takes a full per-lane address
-__device__ __forceinline__ void bw_dma16(const void* sbase, unsigned voff, unsigned lds) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds) : "memory", "m0");
-}
-__device__ __forceinline__ void bw_dma4(const void* sbase, unsigned voff, unsigned lds) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(voff), "s"(sbase), "s"(lds) : "memory", "m0");
-}
-__device__ __forceinline__ void bw_dma4v(const float* p, unsigned lds) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off" ::"v"(p), "s"(lds) : "memory", "m0");
-}
-
-// DMAT (r06; RBF, FULL, F16, T in 16-column blocks): the T tiles and the column-side values reach the wave through LDS-DMA instead of
-// registers.  The register form keeps PD = 4 tiles (64 bytes) per lane in flight -- at two waves per SIMD 32 KB per CU, about half of what
-// 8 TB/s x the loaded memory latency asks for -- and has no registers for more (256 VGPRs).  Here every wave owns a ring of eight 1 KB
-// slots, slot = row tile: at row tile mt the request of the tile that will next use the slot just consumed is issued (tile 7 of this
-// column tile at mt = 0, tile mt - 1 of the NEXT column tile otherwise), i.e. seven tiles = 7 KB per wave are in flight, 56 KB per CU.
-// A tile is one contiguous KB of the blocked T, so its LDS image is the memory image and lane (li, lq) reads its four values at
-// 64 li + 16 lq.  The sixteen columns' x, |x|^2, U and y of the next column tile come the same way (three requests, double-buffered).
-// Waits are counted: requests retire in order, so "all but the youngest N" is exact -- N = the requests issued behind the one needed
-// (the compiler's own memory operations -- the dX atomics of the previous column tile -- are counted when they are known to be there,
-// anything uncounted only makes a wait stricter).
-template <int KIND, bool FULL, bool F16, bool DMAT = false>       // FULL: M % MF_RB == 0 and SB % 64 == 0 (no ragged tiles: no masks); F16: RBF only
+template <int KIND, bool FULL, bool F16>       // FULL: M % MF_RB == 0 and SB % 64 == 0 (no ragged tiles: no masks); F16: RBF only
 __global__ __launch_bounds__(256, MXF_MF_MT <= 4 ? 3 : 2) void svgp_bwd_mfma_kernel(BwdMfmaArgs a) {
     static_assert(!F16 || KIND == MXF_K_RBF, "the f16 accumulation is scaled for the RBF weights");
-    static_assert(!DMAT || (FULL && F16 && MF_MT == 8), "the LDS-DMA form: full tiles, f16 accumulation, eight row tiles (slot = row tile)");
-    __shared__ __attribute__((aligned(16))) float tring[DMAT ? 4 : 1][DMAT ? 8 * 256 : 4];       // per wave: eight T tiles
-    __shared__ __attribute__((aligned(16))) float cbuf[DMAT ? 4 : 1][2][DMAT ? 192 : 4];        // per wave, two buffers: [x 16 x 8 | |x|^2 16 | U 16 | y 16 | -]
     constexpr int QT = 8;
     typedef float f32x4 __attribute__((ext_vector_type(4)));
     typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -511,7 +485,7 @@ __global__ __launch_bounds__(256, MXF_MF_MT <= 4 ? 3 : 2) void svgp_bwd_mfma_ker
     __shared__ float rowacc[MF_RB][10];
     __shared__ __attribute__((aligned(16))) float wt[4][2][16][20];  // per wave, double-buffered: the W tile, transposed on the way through (20-word rows)
     __shared__ float red[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = DMAT ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6, li = lane & 15, lq = lane >> 4;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lq = lane >> 4;
     const int64_t band0 = (int64_t)blockIdx.y * MF_RB;
     const int Q = a.Q;
     const float* __restrict__ Xs = a.Xs;
@@ -638,46 +612,7 @@ __global__ __launch_bounds__(256, MXF_MF_MT <= 4 ? 3 : 2) void svgp_bwd_mfma_ker
     f32x4 tq[PD];
     int smp_w = nt0 / bsz, smp_end = (smp_w + 1) * bsz;       // sample of the tile at nt0 and the first column behind it (< 2^31 + B: unsigned compare)
     auto advance_smp = [&](int nt0_) { while ((unsigned)nt0_ >= (unsigned)smp_end) { ++smp_w; smp_end += bsz; } return smp_w; };
-    // DMAT: request side
-    typedef __attribute__((address_space(3))) void* lds_ptr_t;
-    const unsigned lds_t = DMAT ? __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_ptr_t)&tring[DMAT ? wave : 0][0]) : 0u;
-    const unsigned lds_c = DMAT ? __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_ptr_t)&cbuf[DMAT ? wave : 0][0][0]) : 0u;
-    const unsigned voff16 = (unsigned)lane * 16u, voff4 = (unsigned)lane * 4u;
-    const bool hasdx = a.dX != nullptr;
-    auto tile_base = [&](int nt0_) -> const float* {              // the wave's column block of T at the band's first row (wave-uniform: SGPRs)
-        const int64_t off = ((int64_t)(nt0_ >> 4) * a.M + band0) * 16;
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(uint64_t)off), hi = __builtin_amdgcn_readfirstlane((unsigned)((uint64_t)off >> 32));
-        return Tm + (int64_t)(((uint64_t)hi << 32) | lo);
-    };
-    auto issue_cols = [&](int nt0_, int smp_, int buf) {
-        const unsigned nts = __builtin_amdgcn_readfirstlane((unsigned)nt0_);
-        const float* xb = Xs + (int64_t)nts * QT;
-        bw_dma4(xb, voff4, lds_c + buf * 768);
-        bw_dma4(xb, voff4 + 256u, lds_c + buf * 768 + 256);
-        // lanes 0..15 |x|^2, 16..31 U, 32..47 y, 48..63 |x|^2 again (padding)
-        const float* p = (lq == 1 ? a.U + nt0_ : lq == 2 ? a.Y + (int64_t)smp_ * a.sY + (nt0_ - (int64_t)smp_ * a.B) : a.Xn + nt0_) + li;
-        bw_dma4v(p, lds_c + buf * 768 + 512);
-    };
-    auto read_cols = [&](int buf, int smp_) -> Cols {
-        Cols c;
-        const float* cb = &cbuf[DMAT ? wave : 0][DMAT ? buf : 0][0];
-        c.smp = smp_;
-        c.xa0 = cb[li * 8 + lq]; c.xa1 = cb[li * 8 + 4 + lq];
-        c.xx = *reinterpret_cast<const f32x4*>(cb + 128 + 4 * lq);
-        c.uu = *reinterpret_cast<const f32x4*>(cb + 144 + 4 * lq);
-        c.yy = *reinterpret_cast<const f32x4*>(cb + 160 + 4 * lq);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) c.xv[t] = cb[(4 * lq + t) * 8 + (li & 7)];
-        return c;
-    };
-    if constexpr (DMAT) {
-        issue_cols(nt0, smp_w, 0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        cur = read_cols(0, smp_w);
-        tb_c = tile_base(nt0);
-#pragma unroll
-        for (int j = 0; j < 7; ++j) bw_dma16(tb_c + j * 256, voff16, lds_t + j * 1024);
-    } else if constexpr (AHEAD) {
+    if constexpr (AHEAD) {
         cur = load_cols(nt0, smp_w);
         tb_c = tbase(nt0, tl_c);
 #pragma unroll
@@ -689,15 +624,7 @@ __global__ __launch_bounds__(256, MXF_MF_MT <= 4 ? 3 : 2) void svgp_bwd_mfma_ker
         Cols nxt;
         const float* tl_n = tl_c;
         const float* tb_n = tb_c;
-        int smp_n = cur.smp;
-        if constexpr (DMAT) {
-            nt0n = col_nt0(it + 1);
-            has_next = it + 1 < a.CT && nt0n < sb;
-            if (!has_next) nt0n = nt0;                        // (no next tile: harmless requests of this one again -- the counts stay the same)
-            smp_n = has_next ? advance_smp(nt0n) : cur.smp;
-            issue_cols(nt0n, smp_n, (it + 1) & 1);
-            tb_n = tile_base(nt0n);
-        } else if constexpr (!AHEAD) {         // everything this column tile needs is requested here, at its top
+        if constexpr (!AHEAD) {         // everything this column tile needs is requested here, at its top
             cur = load_cols(nt0, advance_smp(nt0));
             tb_c = tbase(nt0, tl_c);
 #pragma unroll
@@ -754,22 +681,10 @@ __global__ __launch_bounds__(256, MXF_MF_MT <= 4 ? 3 : 2) void svgp_bwd_mfma_ker
             asm volatile("" ::: "memory");
             BT_STAMP(0, rl);
             f32x4 tv;
-            if constexpr (DMAT) {
-                // request into the slot consumed one row tile ago, then wait for this row tile's slot: requests behind it = the six others
-                // of the ring + this one + the three column requests issued at the top (mt < 7; at mt = 7 the slot was requested at mt = 0,
-                // seven tile requests ago) + the four dX atomics of the previous column tile when the caller wants dX
-                if (mt == 0) bw_dma16(tb_c + 7 * 256, voff16, lds_t + 7 * 1024);
-                else bw_dma16(tb_n + (mt - 1) * 256, voff16, lds_t + (mt - 1) * 1024);
-                if (mt == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-                else if (hasdx && it > 0) asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-                tv = *reinterpret_cast<const f32x4*>(&tring[DMAT ? wave : 0][DMAT ? mt * 256 + li * 16 + 4 * lq : 0]);
-            } else {
             tv = tq[mt % PD];
             BT_STAMP(1, tv[0]);
             if (mt + PD < MF_MT) tq[mt % PD] = tget(tb_c, tl_c, mt + PD);                               // PD row tiles ahead
             else if constexpr (AHEAD) tq[mt % PD] = tget(tb_n, tl_n, mt + PD - MF_MT);                  // ... into the next column tile
-            }
             if (!FULL) { const bool ok = cval && rowl + 16 * mt < a.M; tv = ok ? tv : f32x4{0.f, 0.f, 0.f, 0.f}; }
             f32x4 dotn = dotc;
             const f32x2 zwv = zwc;
@@ -898,11 +813,7 @@ __global__ __launch_bounds__(256, MXF_MF_MT <= 4 ? 3 : 2) void svgp_bwd_mfma_ker
             }
         }
         BT_STAMP2(7, 7, dl3);
-        if constexpr (DMAT) {
-            if (!has_next) break;
-            cur = read_cols((it + 1) & 1, smp_n);     // (landed: the wait of row tile 7 covers everything but the seven youngest requests)
-            nt0 = nt0n; tb_c = tb_n;
-        } else if constexpr (AHEAD) {
+        if constexpr (AHEAD) {
             if (!has_next) break;
             cur = nxt; nt0 = nt0n; tb_c = tb_n; tl_c = tl_n;
         } else {
@@ -910,7 +821,6 @@ __global__ __launch_bounds__(256, MXF_MF_MT <= 4 ? 3 : 2) void svgp_bwd_mfma_ker
             if (it + 1 >= a.CT || nt0 >= sb) break;
         }
     }
-    if constexpr (DMAT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // no request may land in LDS after the workgroup has gone
     }
     flush_scal();
     asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
@@ -1132,8 +1042,7 @@ int launch_mfma(mxf_ctx* h, int kind, int64_t M, int64_t SB, int64_t B, int Q, c
     float* Xn = Xs + (size_t)SB * 8;
     const float cs = kind == MXF_K_RBF ? 0.84932180028801904272f : 1.f;      // RBF: exp(-r2 / 2) = 2^-(cs^2 r2), the bare v_exp_f32 in the pass
     // f16 accumulation (RBF; the T product's operand bound must be known: the split GEMM's max |H0| word)
-    static const int f16_env = (int)MXF_KNOB("MXF_BWD_F16", 1);
-    const bool f16 = f16_env && kind == MXF_K_RBF && h0max != nullptr;
+    const bool f16 = kind == MXF_K_RBF && h0max != nullptr;
     unsigned* mx = reinterpret_cast<unsigned*>(zacc + (size_t)M * 16 + 8);          // two words behind dls3[8], zeroed with the accumulators
     const float* Urow = Text + M * SB;
     if (SB > 2147483647LL - 4096) MXF_FAIL(h, -3, "svgp reverse pass: more than 2^31 columns (%lld)", (long long)SB);       // (32-bit column indices in the pass)
@@ -1162,36 +1071,11 @@ int launch_mfma(mxf_ctx* h, int kind, int64_t M, int64_t SB, int64_t B, int Q, c
     dim3 g((unsigned)((quads + ct - 1) / ct), (unsigned)bands, 1);
     if (g.y > 65535u) MXF_FAIL(h, -3, "svgp reverse pass: too many row bands");
     const bool full = (M % MF_RB == 0) && (SB % 64 == 0);
-    // MXF_BWD_DMAT=1 (probe builds only): T tiles and column values through LDS-DMA (svgp_bwd_mfma_kernel DMAT) -- VERDICT r05 item 7's experiment.
-    // Correct (tests/test_gpu_fullsize_oracle.py, test_gpu_sweep.py pass with it) and NOT faster: the pass alone 2.99-3.06 against 2.63-2.74 ms,
-    // the step 22.1-22.5 either way (tests/probes/r06_bwd_dmat.sh).  With 56 instead of 32 KB per CU in flight nothing moves, i.e. the pass
-    // does not wait for memory: at 2 waves per SIMD a row tile costs a SIMD ~630 cycles, about the sum of its ~340 VALU cycles (exp2, the
-    // weights, two f16 splits) and its 8 MFMAs of 32 cycles -- the two do not overlap inside a wave's dependent chain, and the LDS read of
-    // the tile is one more exposed latency per step.  What would help is fewer instructions per element (a 16 x 32 tile on
-    // v_mfma_f32_16x16x32_f16), not deeper queues.
-    static const int dmat_env = (int)MXF_KNOB("MXF_BWD_DMAT", 0);
-    (void)dmat_env;
-#define MF_GO(KIND)                                                                                             \
-    do {                                                                                                        \
-        if (full) hipLaunchKernelGGL((svgp_bwd_mfma_kernel<KIND, true, false>), g, dim3(256), 0, st, a);       \
-        else hipLaunchKernelGGL((svgp_bwd_mfma_kernel<KIND, false, false>), g, dim3(256), 0, st, a);           \
-    } while (0)
-    switch (kind) {
-        case MXF_K_RBF:
-#ifdef MXF_PROBES
-            if (f16 && full && dmat_env && t_blocked && MF_MT == 8) hipLaunchKernelGGL((svgp_bwd_mfma_kernel<MXF_K_RBF, true, true, true>), g, dim3(256), 0, st, a);
-            else
-#endif
-            if (f16 && full) hipLaunchKernelGGL((svgp_bwd_mfma_kernel<MXF_K_RBF, true, true>), g, dim3(256), 0, st, a);
-            else if (f16) hipLaunchKernelGGL((svgp_bwd_mfma_kernel<MXF_K_RBF, false, true>), g, dim3(256), 0, st, a);
-            else MF_GO(MXF_K_RBF);
-            break;
-        case MXF_K_MATERN12: MF_GO(MXF_K_MATERN12); break;
-        case MXF_K_MATERN32: MF_GO(MXF_K_MATERN32); break;
-        case MXF_K_MATERN52: MF_GO(MXF_K_MATERN52); break;
-        default: MXF_FAIL(h, -2, "svgp reverse pass: kind %d has no stationary reverse mode", kind);
-    }
-#undef MF_GO
+    if (kind != MXF_K_RBF) MXF_FAIL(h, -2, "svgp reverse pass: the matrix-pipe form is RBF only (kind %d)", kind);
+    if (f16 && full) hipLaunchKernelGGL((svgp_bwd_mfma_kernel<MXF_K_RBF, true, true>), g, dim3(256), 0, st, a);
+    else if (f16) hipLaunchKernelGGL((svgp_bwd_mfma_kernel<MXF_K_RBF, false, true>), g, dim3(256), 0, st, a);
+    else if (full) hipLaunchKernelGGL((svgp_bwd_mfma_kernel<MXF_K_RBF, true, false>), g, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((svgp_bwd_mfma_kernel<MXF_K_RBF, false, false>), g, dim3(256), 0, st, a);
     hipLaunchKernelGGL(svgp_bwd_finish_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, M, Q, ard, (const float*)Zs, ls, (const double*)a.zacc, (const double*)a.dls3, dZ, dls, R,
                        (double)cs, var, kind == MXF_K_RBF ? dvar : (float*)nullptr);
     MXF_LAUNCH_CHECK(h);
@@ -1239,89 +1123,17 @@ int mxf_gram_bwd_internal(mxf_ctx* h, int kind, int dtype, int S, int64_t N, int
 // SVGP-fused reverse pass over Text = [H0; w^T] Kuf_all (rows 0..M-1: T, rows M..M+P-1: U); column-side output dXall is
 // WRITTEN (not accumulated); dZ, dls, dvar, R, scal are accumulated into (caller zeroes); dY written or (shared) accumulated.
 bool mxf_svgp_bwd_is_mfma(int kind, int dtype, int64_t SB, int64_t B, int Q, int P, const void* Text) {
-    static const int mf_env = MXF_KNOB("MXF_BWD_MFMA", 1);
     // RBF only (r04): the matrix-pipe pass forms r2 = |x|^2 + |z|^2 - 2 x.z in float32 -- absolute error ~1e-7 (|x|^2 + |z|^2).  The RBF weight is
     // smooth in r2; the Matern slopes are not (dk/dr2 = -k / 2r for Matern12): with inducing inputs next to data points -- Z = X[:M] is the
     // usual initialisation -- its dX / dZ came out 10-20 % off for Matern12 and 1e-3 off for Matern32 / 52 at Q = 3 ... 8, against 1e-6 ... 5e-5 from the
-    // difference-form pass (tests/probes/bwd_form_accuracy.py).  MXF_BWD_MFMA=2 (probe build) puts the Matern kinds back on it.
-    if (kind != MXF_K_RBF && mf_env != 2) return false;
-    return mf_env && dtype == MXF_F32 && P == 1 && Q <= 8 && SB % 4 == 0 && SB >= 16 && B % 16 == 0 && ((uintptr_t)Text % 16) == 0;
+    // difference-form pass (tests/probes/bwd_form_accuracy.py).
+    return kind == MXF_K_RBF && dtype == MXF_F32 && P == 1 && Q <= 8 && SB % 4 == 0 && SB >= 16 && B % 16 == 0 && ((uintptr_t)Text % 16) == 0;
 }
 
 // may T be handed over in 16-column blocks?  The matrix-pipe pass (RBF) requires it; the difference-form pass (Matern kinds, P > 1, Q > 8) reads
 // either layout for Q <= 16 -- so that those calls keep the wide blocked-output T product (11.3 instead of 13.4 ms at the bench shape)
 bool mxf_svgp_bwd_reads_blocked(int kind, int dtype, int64_t SB, int64_t B, int Q, int P, const void* Text) {
     return mxf_svgp_bwd_is_mfma(kind, dtype, SB, B, Q, P, Text) || (dtype == MXF_F32 && Q <= 16 && P <= PMAX_ALL && SB % 16 == 0);
-}
-
-// ---- r05: the reverse pass as the epilogue of the T product (mxf_fuse_args, internal.h; gemm_split.hip wide_body<..., FUSE>) ----------------------
-// dY = -c1 e and sum_n e_n^2 per sample (the separate pass did this on its first row band)
-__global__ __launch_bounds__(256) void fuse_resid_kernel(int64_t SB, int64_t B, const float* __restrict__ U, const float* __restrict__ Y, int64_t sY,
-                                                         const float* __restrict__ noise, double a1, float* __restrict__ dY, int dY_shared,
-                                                         double* __restrict__ scal) {
-    __shared__ double red[16];
-    const int64_t smp = blockIdx.y;
-    const float c1 = (float)a1 / noise[0];
-    double es = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < B; i += (int64_t)gridDim.x * 256) {
-        const int64_t n = smp * B + i;
-        const float e = Y[smp * sY + i] - U[n];
-        es += (double)e * (double)e;
-        if (dY) { const float gy = -c1 * e; if (dY_shared) atomic_add(dY + i, gy); else dY[n] = gy; }
-    }
-    es = block_sum<double>(es, red);
-    if (threadIdx.x == 0) atomic_add(scal + 2 * smp + 1, es);
-}
-
-int mxf_svgp_bwd_fuse_ok(int kind, int dtype, int64_t M, int64_t SB, int64_t B, int Q, int P) {
-    static const int env = (int)MXF_KNOB("MXF_SVGP_FUSE", 0);
-    return env && kind == MXF_K_RBF && dtype == MXF_F32 && P == 1 && Q <= 8 && (M % 256) == 0 && M >= 256 && (B % 256) == 0 && (SB % B) == 0 &&
-           SB / B <= 65535 && SB < 2147483647LL - 4096;
-}
-
-int mxf_svgp_bwd_fuse_prepare(mxf_ctx* h, int64_t M, int64_t SB, int64_t B, int Q, const float* Z, const float* X, const float* ls, int ard,
-                              const float* var, const float* U, const float* Y, int64_t sY, const float* w, const float* noise, double a1, float* dX,
-                              float* dY, int dY_shared, double* scal, const unsigned* h0max, mxf_fuse_args* out, hipStream_t st) {
-    const size_t nacc = ((size_t)M * 16 + 16) * sizeof(double);
-    const size_t need = nacc + (((size_t)M + (size_t)SB) * 8 + (size_t)SB + (size_t)M) * sizeof(float);      // + scaled coordinates, |x_n|^2, |z_m|^2
-    if (need > h->bwd_acc_bytes) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(st, &cap);
-        if (cap != hipStreamCaptureStatusNone) MXF_FAIL(h, -4, "svgp reverse pass: scratch must be allocated before a stream capture (run one eager step first)");
-        if (h->bwd_acc) { (void)hipDeviceSynchronize(); (void)hipFree(h->bwd_acc); h->bwd_acc = nullptr; h->bwd_acc_bytes = 0; ++h->ws_generation; }
-        if (hipMalloc((void**)&h->bwd_acc, need) != hipSuccess) { h->bwd_acc = nullptr; MXF_FAIL(h, -4, "svgp reverse pass: cannot allocate %zu bytes", need); }
-        h->bwd_acc_bytes = need;
-    }
-    MXF_HIP(h, hipMemsetAsync(h->bwd_acc, 0, nacc, st));
-    double* zacc = reinterpret_cast<double*>(h->bwd_acc);
-    float* Zs = reinterpret_cast<float*>(reinterpret_cast<char*>(h->bwd_acc) + nacc);
-    float* Xs = Zs + (size_t)M * 8;
-    float* Xn = Xs + (size_t)SB * 8;
-    float* Zn = Xn + (size_t)SB;
-    const float cs = 0.84932180028801904272f;
-    unsigned* mx = reinterpret_cast<unsigned*>(zacc + (size_t)M * 16 + 8);
-    float* centre = reinterpret_cast<float*>(zacc + (size_t)M * 16 + 9);
-    const int64_t nsamp = SB / B;
-    hipLaunchKernelGGL(bwd_centre_kernel, dim3((unsigned)Q), dim3(256), 0, st, M < 64 ? M : (int64_t)64, Q, Z, centre);
-    hipLaunchKernelGGL(bwd_prescale_kernel, dim3((unsigned)((M + 255) / 256), 1), dim3(256), 0, st, Z, M, Q, ls, ard, (const float*)centre, Zs, Zn, cs,
-                       w, (const float*)nullptr, (int64_t)0, mx);
-    hipLaunchKernelGGL(bwd_prescale_kernel, dim3((unsigned)((B + 255) / 256), (unsigned)nsamp), dim3(256), 0, st, X, B, Q, ls, ard, (const float*)centre, Xs, Xn, cs,
-                       U, Y, sY, mx + 1);
-    const int64_t gx = (B + 255) / 256 > 64 ? 64 : (B + 255) / 256;
-    hipLaunchKernelGGL(fuse_resid_kernel, dim3((unsigned)gx, (unsigned)nsamp), dim3(256), 0, st, SB, B, U, Y, sY, noise, a1, dY, dY_shared, scal);
-    MXF_LAUNCH_CHECK(h);
-    out->Zs = Zs; out->Zn = Zn; out->Xs = Xs; out->Xn = Xn; out->U = U; out->Y = Y; out->w = w; out->ls = ls; out->var = var; out->noise = noise;
-    out->dX = dX; out->zacc = zacc; out->dls3 = zacc + (size_t)M * 16; out->scal = scal; out->h0max = h0max; out->mx = mx;
-    out->B = B; out->sY = sY; out->Q = Q; out->ard = ard; out->a1 = a1;
-    return 0;
-}
-
-int mxf_svgp_bwd_fuse_finish(mxf_ctx* h, int64_t M, int Q, int ard, const float* ls, const float* var, const mxf_fuse_args* fz, float* dZ, float* dls,
-                             float* dvar, float* R, hipStream_t st) {
-    hipLaunchKernelGGL(svgp_bwd_finish_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, M, Q, ard, fz->Zs, ls, (const double*)fz->zacc,
-                       (const double*)fz->dls3, dZ, dls, R, (double)0.84932180028801904272f, var, dvar);
-    MXF_LAUNCH_CHECK(h);
-    return 0;
 }
 
 int mxf_svgp_bwd_fused_internal(mxf_ctx* h, int kind, int dtype, int64_t M, int64_t SB, int64_t B, int Q, int P, const void* Z,

@@ -12,10 +12,7 @@ int mxf_gemm_internal(mxf_ctx* h, int dtype, int ta, int tb, int64_t M, int64_t 
 // zero_upper = false: leave the strict upper triangle outside the 64 x 64 diagonal blocks as it was (callers that only read the lower part)
 // zero_info = false: the caller has zeroed `info` already (the SVGP composite clears its status words in one launch off the critical path)
 int mxf_potrf_internal(mxf_ctx* h, int dtype, int S, int64_t n, void* A, int64_t lda, int64_t sA, int* info, hipStream_t st, bool zero_upper = true,
-                       bool zero_info = true, void* Linv_eager = nullptr, int64_t ldie = 0, bool* eager_done = nullptr,
-                       void* Kacc = nullptr, int64_t ldk = 0, double kcoef = 0.0, bool* kacc_done = nullptr);
-// (Kacc, with Linv_eager: kcoef L^-T L^-1 (lower triangle) is accumulated into this ZEROED n x n buffer row block by row block of L^-1, next to
-//  the factorisation as well -- L^-T L^-1 = sum over row blocks b of Linv[b, :]^T Linv[b, :]; *kacc_done says whether it was)
+                       bool zero_info = true, void* Linv_eager = nullptr, int64_t ldie = 0, bool* eager_done = nullptr);
 // (Linv_eager: float64, S = 1, large n: L^-1 is formed into this (n x n, leading dimension ldie) buffer NEXT TO the factorisation, row block by row
 //  block on a third stream; *eager_done says whether it was -- if not, the caller runs mxf_trtri_internal as before)
 // rhs_lower: B is block-lower-triangular (trtri); only columns < (k+1)*64 of block row k are touched
@@ -44,27 +41,6 @@ int mxf_svgp_bwd_fused_internal(mxf_ctx* h, int kind, int dtype, int64_t M, int6
 //  accumulate its RBF weights as hi + lo f16; nullptr: float32 accumulation.  tmax: bit pattern of max |T| if the GEMM reported it
 //  (word != 0): the tight bound)
 
-// r05: the SVGP reverse pass FUSED into the epilogue of the T product (gemm_split.hip wide_body<..., FUSE>): the 256 x 256 accumulator tile IS T --
-// the pass's weights W = -(c1 variance) (T + w e) k, its row sums [B | S] = W [X | 1], R and its column sums [D | C] = W^T [Z | 1] are formed
-// from registers, T is never written (8.6 GB less written and 8.6 GB less read per 32-sample step, one bulk kernel less).  RBF, Q <= 8, one
-// output column, M % 256 == 0, B % 256 == 0.  Filled by mxf_svgp_bwd_fuse_prepare (gram_bwd.hip), consumed by mxf_gemm_split_internal.
-struct mxf_fuse_args {
-    const float* Zs; const float* Zn;    // scaled, centred inducing inputs (8 per row) and their squared norms
-    const float* Xs; const float* Xn;    // the same for the data columns
-    const float* U; const float* Y; const float* w; const float* ls; const float* var; const float* noise;
-    float* dX; double* zacc; double* dls3; double* scal;
-    const unsigned* h0max; const unsigned* mx;      // bit patterns: max |A operand| of the product, {max |w|, max |y - U|}
-    int64_t B, sY;
-    int Q, ard;
-    double a1;
-};
-int mxf_svgp_bwd_fuse_ok(int kind, int dtype, int64_t M, int64_t SB, int64_t B, int Q, int P);
-int mxf_svgp_bwd_fuse_prepare(mxf_ctx* h, int64_t M, int64_t SB, int64_t B, int Q, const float* Z, const float* X, const float* ls, int ard,
-                              const float* var, const float* U, const float* Y, int64_t sY, const float* w, const float* noise, double a1, float* dX,
-                              float* dY, int dY_shared, double* scal, const unsigned* h0max, mxf_fuse_args* out, hipStream_t st);
-int mxf_svgp_bwd_fuse_finish(mxf_ctx* h, int64_t M, int Q, int ard, const float* ls, const float* var, const mxf_fuse_args* fz, float* dZ, float* dls,
-                             float* dvar, float* R, hipStream_t st);
-
 // f32-accurate GEMM on the bf16 matrix pipe (three-term bf16 splitting, gemm_split.hip)
 size_t mxf_split_plane_elems(int64_t R, int64_t K);    // elements (bf16) of ONE plane of an (R x K) operand
 // operand formats of the split GEMM (gemm_split.hip): three bf16 terms / two scaled f16 terms
@@ -78,8 +54,7 @@ int mxf_gemm_split_internal(mxf_ctx* h, int64_t M, int64_t N, int64_t K, double 
                             int reserve_cus = 0, int mode = MXF_SPLIT_BF16X3, const float* ad0 = nullptr, int pow0 = 0,
                             const unsigned* maxbits = nullptr, const unsigned* maxbits2 = nullptr, int c_blocked = 0,
                             unsigned* maxout = nullptr, unsigned short* Cplanes = nullptr, int64_t pC = 0, int a_lower = 0,
-                            unsigned short* Ct = nullptr, int64_t pCt = 0, const float* avec = nullptr, float* Upart = nullptr,
-                            const mxf_fuse_args* fuse = nullptr);
+                            unsigned short* Ct = nullptr, int64_t pCt = 0, const float* avec = nullptr, float* Upart = nullptr);
 // (Ct: the planes output ALSO in the transposed orientation, ((m / 16) * N + n) * 16 + m % 16, plane stride pCt; avec (M floats) / Upart
 //  ((M / 128) x N floats): per 128-row band the sums of avec[m] * (hi + lo)(m, n), in the planes' units -- deterministic, summed by the caller)
 // (Cplanes != nullptr: the product is written as two f16 planes (hi + lo of alpha * A B^T, plane stride pC) in the layout of an (M x K' = N)
@@ -96,7 +71,7 @@ int mxf_gemm_bt_internal(mxf_ctx* h, int64_t M, int64_t N, int64_t K, double alp
 size_t mxf_gram_planes_scratch_bytes(int64_t R, int64_t Kn, int Q);
 int mxf_gram_planes_internal(mxf_ctx* h, int kind, int64_t R, int64_t Kn, int Q, const float* Xmin, const float* Xmaj, const float* ls,
                              int ard, const float* var, unsigned short* planes, int64_t pstride, float* scratch, hipStream_t st,
-                             int mode = 0 /* MXF_SPLIT_BF16X3 */, const float* wk = nullptr, int Pw = 0, float* U = nullptr, int64_t ldU = 0,
+                             int mode = MXF_SPLIT_F16X2, const float* wk = nullptr, int Pw = 0, float* U = nullptr, int64_t ldU = 0,
                              const float* majs = nullptr, const float* mins = nullptr, int64_t period = 1);
 // (majs / mins: optional per-row weights (period entries, index taken modulo period) on the major / minor index -- f16x2 lean kernel only)
 // (wk (Kn x Pw), U (Pw x ldU): optional fused product U[p][r] = sum_k wk[k][p] cov(xmin[r], xmaj[k]); see gram_planes_kernel)

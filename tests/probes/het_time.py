@@ -1,5 +1,5 @@
-"""Per-row noise (N, 1) SVGP training call at the bench shape: the streaming form (r04) against the generic materialised-dKuf path
-(probe build, MXF_SVGP_HET_STREAM=0) and the homoscedastic call.  usage: [MXF_GP_LIB=...probe.so MXF_SVGP_HET_STREAM=0] het_time.py [S]"""
+"""Per-row noise (N, 1) SVGP training call at the bench shape (the streaming form, r04) against the homoscedastic call.
+usage: het_time.py [S]"""
 import os
 import sys
 import numpy as np

@@ -1,5 +1,5 @@
 """The SVGP training call (float32, N = 65 536, M = 1 024, Q = 8, S samples) per kernel kind: the Matern kinds run the difference-form reverse pass
-since r04 (MXF_BWD_MFMA=2 in the probe build puts them back on the matrix-pipe pass).  usage: matern_step_time.py [S]"""
+since r04.  usage: matern_step_time.py [S]"""
 import os
 import sys
 import numpy as np

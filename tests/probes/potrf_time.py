@@ -1,14 +1,6 @@
-"""potrf time (float64) at n = 512 / 1024 / 2048 with and without the persistent tile-dataflow kernel (MXF_POTRF_TILES, read once per process).
-usage: potrf_time.py [sweep]"""
+"""potrf time and error (float64) at n = 512 ... 8192.  usage: potrf_time.py"""
 import os
-import subprocess
 import sys
-
-if len(sys.argv) > 1 and sys.argv[1] == 'sweep':
-    for v in ('1', '2', '0'):
-        out = subprocess.run([sys.executable, __file__], env=dict(os.environ, MXF_POTRF_TILES=v), capture_output=True, text=True).stdout
-        print('MXF_POTRF_TILES=%s | %s' % (v, ' | '.join(l.strip() for l in out.strip().splitlines())), flush=True)
-    sys.exit(0)
 
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
