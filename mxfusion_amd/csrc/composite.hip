@@ -283,11 +283,36 @@ __global__ void bcast_copy_kernel(int S, int64_t n, const T* __restrict__ src, i
 inline unsigned dotgrid(int64_t n) { int64_t b = (n + 255) / 256; if (b < 1) b = 1; if (b > 64) b = 64; return (unsigned)b; }
 inline unsigned gridn(int64_t n) { int64_t b = (n + 255) / 256; if (b < 1) b = 1; if (b > 4096) b = 4096; return (unsigned)b; }
 
-struct Carver {   // bump allocator over the handle's scratch
+struct Carver {   // bump allocator over the handle's scratch; with a null base it only counts
     char* base; size_t off = 0;
     explicit Carver(void* p) : base((char*)p) {}
-    template <typename U> U* take(size_t n) { U* p = (U*)(base + off); off += mxf_align(n * sizeof(U)); return p; }
+    template <typename U> U* take(size_t n) { U* p = base ? (U*)(base + off) : nullptr; off += mxf_align(n * sizeof(U)); return p; }
 };
+// A composite's scratch layout is ONE list of take() calls (`layout`), run once to count the bytes and once to carve them, so the two
+// cannot disagree.  false (need = the bytes asked for) when the scratch cannot be allocated.
+template <typename F>
+bool carve_scratch(mxf_ctx* h, F&& layout, size_t& need) {
+    Carver count(nullptr);
+    layout(count);
+    need = count.off;
+    void* ws = mxf_ws(h, need);
+    if (!ws) return false;
+    Carver cv(ws);
+    layout(cv);
+    return true;
+}
+// dst = (TO)src, n contiguous elements
+template <typename TI, typename TO>
+void copy_convert(int64_t n, const TI* src, TO* dst, hipStream_t s) {
+    hipLaunchKernelGGL((convert_kernel<TI, TO>), dim3(gridn(n)), dim3(256), 0, s, (int64_t)1, n, src, n, dst, n);
+}
+// f(float) or f(double) for a float32 / float64 call: the typed body behind each C entry point
+template <typename F>
+int by_dtype(mxf_ctx* h, const char* fn, int dtype, F&& f) {
+    if (dtype == MXF_F32) return f(0.f);
+    if (dtype == MXF_F64) return f(0.0);
+    MXF_FAIL(h, -2, "%s: bad dtype %d", fn, dtype);
+}
 
 // ================================================================================================ exact GP
 template <typename T>
@@ -295,22 +320,20 @@ int gp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t N, int Q, in
                     const T* noise, int64_t snoise, const T* ls, int ard, int64_t sls, const T* var, int64_t svar, double jitter,
                     T* logL, T* L, T* LinvY, int* info, int want_grad, T* dX, T* dY, T* dnoise, T* dls, T* dvar, hipStream_t st) {
     const int64_t NN = N * N, NP = N * P;
-    size_t need = mxf_align(S * sizeof(T)) + mxf_align(S * sizeof(double));
-    if (want_grad) need += 2 * mxf_align((size_t)S * NN * sizeof(T)) + mxf_align((size_t)S * NP * sizeof(T));
-    void* ws = mxf_ws(h, need);
-    if (!ws) MXF_FAIL(h, -4, "mxf_gp_logpdf: cannot allocate %zu bytes of scratch", need);
-    Carver cv(ws);
-    T* sld = cv.take<T>(S);
-    double* ss = cv.take<double>(S);
+    T* sld; double* ss; T* Linv = nullptr; T* dK = nullptr; T* alpha = nullptr;
+    size_t need;
+    const bool ok = carve_scratch(h, [&](Carver& cv) {
+        sld = cv.take<T>(S); ss = cv.take<double>(S);
+        if (want_grad) { Linv = cv.take<T>((size_t)S * NN); dK = cv.take<T>((size_t)S * NN); alpha = cv.take<T>((size_t)S * NP); }
+    }, need);
+    if (!ok) MXF_FAIL(h, -4, "mxf_gp_logpdf: cannot allocate %zu bytes of scratch", need);
     int rc;
     // K = k(X,X) + (noise + jitter) I   (gp_regression.py:55-60), built straight into the L buffer
     rc = mxf_gram(h, kind, dtype, S, N, N, Q, X, sX, nullptr, 0, ls, ard, sls, var, svar, noise, snoise, jitter, MXF_WRITE, L, N, NN, st);
     if (rc) return rc;
     // L^-1 Y (:66).  Large N with gradients: the reverse mode needs L^-1 anyway, and L^-1 Y as ONE product replaces N / 64 dependent
     // block steps (6.9 ms at N = 8192); small N keeps the reference's trsm.
-    T* Linv = nullptr;
     const bool via_inverse = want_grad && N >= 2048;
-    if (via_inverse) Linv = cv.take<T>((size_t)S * NN);
     // (r06) one matrix, few right-hand sides: the two skinny products with L^-1 as triangular streaming reads, 1/2 alpha alpha^T folded into
     // the symmetrisation of dK
     const bool tri_skinny = via_inverse && S == 1 && P <= 8;
@@ -341,12 +364,9 @@ int gp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t N, int Q, in
 
     // reverse mode: dlogL/dK = 1/2 (alpha alpha^T - P K^-1), alpha = K^-1 Y; dlogL/dY = -alpha
     if (!via_inverse) {
-        Linv = cv.take<T>((size_t)S * NN);
         rc = mxf_trtri_internal(h, dtype, S, N, L, N, NN, Linv, N, NN, st);
         if (rc) return rc;
     }
-    T* dK = cv.take<T>((size_t)S * NN);
-    T* alpha = cv.take<T>((size_t)S * NP);
     if (tri_skinny) {
         MXF_HIP(h, hipMemsetAsync(alpha, 0, sizeof(T) * NP, st));
         hipLaunchKernelGGL((trmv_lower_t_kernel<T>), dim3((unsigned)((N + 255) / 256), (unsigned)((N + 127) / 128)), dim3(256), 0, st, N, P, (const T*)Linv, N,
@@ -848,17 +868,6 @@ __global__ void svgp_finalize_hets_kernel(int S, int64_t B, int64_t M, const dou
     if (dvar_direct) dvar_direct[0] = a1 * (double)S * (-0.5 * hs[1]);
 }
 
-// |A|_1 of a symmetric (n x n) float64 matrix: max over rows of the absolute row sum (= column sum), into *out as a double (non-negative
-// doubles order like unsigned 64-bit integers: one atomicMax per workgroup; *out must be zeroed)
-__global__ __launch_bounds__(256) void norm1_sym_kernel(int64_t n, const double* __restrict__ A, int64_t lda, double* __restrict__ out) {
-    __shared__ double red[16];
-    const int64_t row = blockIdx.x;
-    double s = 0;
-    for (int64_t j = threadIdx.x; j < n; j += 256) s += fabs(A[row * lda + j]);
-    s = block_sum<double>(s, red);
-    if (threadIdx.x == 0) atomicMax(reinterpret_cast<unsigned long long*>(out), __builtin_bit_cast(unsigned long long, s));
-}
-
 // the training call's first launch on the caller's stream: its status words (LAPACK info of the two factorisations, the split scale word)
 // cleared in ONE launch instead of a hipMemsetAsync each in front of the kernels of the critical chain (~10 us apiece there)
 __global__ void svgp_init_kernel(int* __restrict__ info, int* __restrict__ info2, double* __restrict__ cond_dev) {
@@ -898,9 +907,10 @@ __global__ void cond_publish_kernel(double* __restrict__ cond_dev, double* __res
     cond_dev[0] = 0.0; cond_dev[1] = 0.0;                       // the next call's norm kernels accumulate with atomicMax: no memset in front of them
 }
 
-// |A|_1 (see norm1_sym_kernel) with 16 rows per workgroup -- one row per wave at a time (coalesced loads + a DPP wave sum, no barrier per
-// row) and ONE atomic per workgroup: n / 16 same-address atomics instead of n (they serialise: 1024 of them were most of the 80 us this
-// took on the critical path in front of the Cholesky factorisation).
+// |A|_1 of a symmetric (n x n) float64 matrix: max over rows of the absolute row sum (= column sum), into *out as a double (non-negative
+// doubles order like unsigned 64-bit integers: one atomicMax per workgroup; *out must be zeroed).  16 rows per workgroup -- one row per wave
+// at a time (coalesced loads + a DPP wave sum, no barrier per row) and ONE atomic per workgroup: n / 16 same-address atomics instead of n
+// (they serialise: 1024 of them were most of the 80 us one workgroup per row took on the critical path in front of the Cholesky factorisation).
 __global__ __launch_bounds__(256) void norm1_sym16_kernel(int64_t n, const double* __restrict__ A, int64_t lda, double* __restrict__ out) {
     __shared__ double wmax[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -921,229 +931,278 @@ __global__ __launch_bounds__(256) void norm1_sym16_kernel(int64_t n, const doubl
     }
 }
 
+// Which path one SVGP call takes, from shapes, strides, dtype and h->svgp_form, and the sizes every stage uses.  The stages rely on:
+//   use_split  => float32, want_grad, !het, SB % 16 == 0        whiten    => use_split
+//   bt_path    => use_split, !whiten                             bt_wh     => whiten
+//   het_stream => !het, float32                                  het_split => het, float32
+//   fused       = want_grad && !het: the streaming reverse pass, its accumulate-into outputs cleared at the start of the call
+struct SvgpPlan {
+    bool use_mat, ysamp, het_stream, het, fused, use_split, whiten, bt_path, bt_wh, het_split;
+    int SS, SYc, lsn;           // samples with columns of their own, Y samples per column, length-scales
+    int64_t SB, MM, MP;
+    double a1, bw;
+    size_t pl_big, pl_h0, gp_scr;
+    const float* split_var;
+};
+
+// One SVGP call: its arguments (in the order of the C ABI), its plan, its scratch and the stages that queue its launches.  The stages run in
+// enqueue order, which is priority order across the three streams -- the host needs ~5 us per launch and a step has ~280 of them.
 template <typename T>
-int svgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t B, int64_t M, int Q, int P, const T* X, int64_t sX, const T* Y,
-                      int64_t sY, const T* Z, const T* noise, int64_t nrows, int ncols, const T* mu, const T* W, const T* sdiag, const T* ls, int ard, const T* var,
-                      double jitter, double scaling, double gscale, T* logL, int* info, int want_grad, T* dX, T* dY, T* dZ, T* dnoise,
-                      T* dmu, T* dW, T* dSdiag, T* dls, T* dvar, hipStream_t st, SvgpMat<T> mat = SvgpMat<T>()) {
-    if (P > 8) MXF_FAIL(h, -3, "mxf_svgp_logpdf: P > 8 outputs not supported");
-    if ((nrows != 1 && nrows != B) || (ncols != 1 && ncols != P)) MXF_FAIL(h, -2, "mxf_svgp_logpdf: noise_var must be (1|B, 1|P)");
-    const bool use_mat = mat.Kuu != nullptr;
-    // sampled Y over shared X (hence shared Kuf, T, U): the S samples share the B columns -- generic path, the data term is quadratic in Y
-    const bool ysamp = S > 1 && sX == 0 && sY != 0;
-    if (ysamp && sY != B * P) MXF_FAIL(h, -2, "mxf_svgp_logpdf: Y samples must be contiguous");
-    // generic path: Kuf-side reverse mode through a materialised dKuf (not the streaming fused pass); also for Q > 16 inputs, which the
-    // register-tiled fused reverse pass does not cover (gram_bwd.hip: generic kernel)
-    // r04: per-row noise (B, 1) with one output column on the float32 split path runs the STREAMING form (het_* kernels above); every other
-    // heteroscedastic shape keeps the generic (materialised dKuf) path
-    const int64_t SBh = ((sX == 0) ? (int64_t)1 : (int64_t)S) * B;
-    const bool het_stream = sizeof(T) == 4 && want_grad && nrows == B && nrows > 1 && ncols == 1 && P == 1 && !use_mat && !ysamp && Q <= 8 &&
-                            (B % 16 == 0) && (M % 16 == 0) && M >= 128 && h->svgp_form == MXF_SVGP_EXPLICIT && mxf_svgp_bwd_is_mfma(kind, dtype, SBh, B, Q, P, X);
-    const bool het = (nrows > 1 || ncols > 1 || use_mat || ysamp || Q > 16) && !het_stream;
-    if (sX != 0 && sX != B * Q) MXF_FAIL(h, -2, "mxf_svgp_logpdf: X samples must be contiguous");
-    if (S > 1 && sX == 0 && sY == 0) MXF_FAIL(h, -3, "mxf_svgp_logpdf: S > 1 with neither X nor Y sampled");
-    const int SS = (sX == 0) ? 1 : S;   // samples that need their own columns
-    const int SYc = ysamp ? S : 1;     // Y samples per column
-    const int64_t SB = (int64_t)SS * B, MM = M * M, MP = M * P;
-    const int lsn = ard ? Q : 1;
-    const double a1 = gscale * scaling, bw = gscale * (double)S;
+struct SvgpCall : SvgpPlan {
     typedef double D;
+    mxf_ctx* h; int kind, dtype, S; int64_t B, M; int Q, P;
+    const T* X; int64_t sX; const T* Y; int64_t sY; const T* Z; const T* noise; int64_t nrows; int ncols;
+    const T* mu; const T* W; const T* sdiag; const T* ls; int ard; const T* var;
+    double jitter, scaling, gscale;
+    T* logL; int* info; int want_grad;
+    T* dX; T* dY; T* dZ; T* dnoise; T* dmu; T* dW; T* dSdiag; T* dls; T* dvar;
+    hipStream_t st;
+    SvgpMat<T> mat;
 
-    size_t need = 0;
-    auto acc = [&](size_t n, size_t es) { need += mxf_align(n * es); };
-    acc(M * Q, 8); acc(lsn, 8); acc(1, 8); acc(1, 8); acc(MP, 8); acc(MM, 8); acc(M, 8);   // f64 copies of the parameters
-    for (int i = 0; i < 9; ++i) acc(MM, 8);   // L, Linv, Ki, Su(Ls), Lsinv, Sui, KiSu, H0, tmp
-    acc(MP, 8); acc(16, 8); acc(2 * (size_t)S, 8); acc(8, sizeof(int));
-    acc((size_t)(M + P) * M, sizeof(T)); acc(MP, sizeof(T));
-    acc((size_t)(M + P) * SB, sizeof(T)); acc((size_t)SB, sizeof(T));
-    // float32 streaming: the two big GEMMs run on the 16-bit matrix pipe from split planes of their operands (gemm_split.hip), in the format
-    // of two scaled f16 terms (three products)
-    const bool use_split = want_grad && sizeof(T) == 4 && !het && (SB % 16 == 0) && (M % 16 == 0) && M >= 128 && Q <= 16;
-    constexpr int split_mode = MXF_SPLIT_F16X2;
-    const float split_ga = 1.f / 16384.f;     // Gram planes hold k / variance * 2^14 in the f16x2 format
-    const float* split_var = (const float*)var;
-    const size_t pl_big = mxf_split_plane_elems(M, SB), pl_h0 = mxf_split_plane_elems(M, M);     // == mxf_split_plane_elems(SB, M)
-    const size_t gp_scr = use_split ? mxf_gram_planes_scratch_bytes(SB, SB, Q) : 0;      // upper bound for either orientation
-    // float32 streaming form (mxf_svgp_configure): the whitened tier runs on the f16x2 split kernels' wide forms only
-    const bool whiten = sizeof(T) == 4 && want_grad && h->svgp_form == MXF_SVGP_WHITENED;
-    if (whiten && !(use_split && (M % 128) == 0 && (SB % 256) == 0))
-        MXF_FAIL(h, -3, "mxf_svgp_logpdf: the whitened float32 form needs M %% 128 == 0, S B %% 256 == 0, Q <= 16, homoscedastic noise (see mxf_svgp_whitened_ok)");
-    // (each branch mirrors one carve below, in the same order)
-    if (use_split) { acc(3 * pl_big, 2); acc(3 * pl_h0, 2); acc(3 * pl_big, 2); acc(gp_scr, 1); acc(gp_scr, 1); }
-    else { acc((size_t)M * SB, sizeof(T)); if (want_grad) acc((size_t)M * SB, sizeof(T)); }      // Kuf, Kfu in the streaming dtype
-    if (whiten) { acc(2 * pl_h0, 2); acc(MP, 8); acc(MP, sizeof(T)); acc(4, sizeof(float)); acc((size_t)(M / 128) * SB, sizeof(float)); }
-    // r06: ONE set of Kuf planes.  T = H0 Kuf reads the planes Psi2 reads (operand (m, k = n)) through gemm_bt.hip's transposing LDS read, and
-    // forms the row U = w^T Kuf on the way: the second planes pass (8.6 GB written between the two products, 1.8 ms of the 24 ms step with the
-    // matrix pipe idle) and its 8.6 GB buffer are gone.  Needs the explicit float32 form, one output column, whole 256 x 256 tiles.
-    const bool bt_path = use_split && !whiten && !het_stream && P == 1 && M <= 2048 && mxf_gemm_bt_ok(M, SB, M);
-    // the whitened tier likewise: T = Hh V reads the planes of V that Phi = V V^T reads (the V product's planes output IS the K-major layout),
-    // and forms U = a^T V on the way -- the V product no longer writes the planes of V^T (8.6 GB, its "second output") nor the partial sums of U
-    const bool bt_wh = whiten && P == 1 && M <= 2048 && mxf_gemm_bt_ok(M, SB, M);
-    if (bt_path || bt_wh) acc(2 * (size_t)M + 8, 2);
-    if (het_stream) { acc(B, 4); acc(B, 4); acc((size_t)(sY == 0 ? B : SB), 4); acc(4, 8); acc(S, 8); acc(4, 4); }
-    // r06: the generic (materialised-Gram / heteroscedastic) float32 path's two big products on the f16 matrix pipe as well: T = H0 Kuf through the
-    // K-major product from the planes of Kuf (split from the float32 Gram: one maxabs + one split pass, 0.17 ms at 512 x 131 072), and
-    // G' = Ksc Kuf^T from the planes of Ksc and the same Kuf planes -- f32-equivalent like the streaming path's products (three f16 products, f32
-    // accumulation) where the generic kernel ran true-f32 MFMAs at 100 TF: the deep GP's first layer 0.68 + 0.66 ms -> planes 0.35 + products 0.3.
-    const bool het_split = het && sizeof(T) == 4 && want_grad && mxf_gemm_bt_ok(M, SB, M) &&
-                           (int64_t)M * SB >= (int64_t)1 << 24;
-    if (het_split) { acc(2 * pl_h0, 2); acc(2 * pl_big, 2); acc(2 * pl_big, 2); acc(4, sizeof(unsigned)); }
-    if (want_grad) { acc(MM, sizeof(T)); acc(MP, sizeof(T)); acc((size_t)SB * P, sizeof(T)); for (int i = 0; i < 6; ++i) acc(MM, 8); acc(MP, 8); acc(MP, 8); acc(M * Q, 8); acc(lsn, 8); acc(4, 8); }
-    void* ws = mxf_ws(h, need);
-    if (!ws) MXF_FAIL(h, -4, "mxf_svgp_logpdf: cannot allocate %zu bytes of scratch", need);
-    Carver cv(ws);
-    D* Zd = cv.take<D>(M * Q); D* lsd = cv.take<D>(lsn); D* vard = cv.take<D>(1); D* noised = cv.take<D>(1);
-    D* mud = cv.take<D>(MP); D* Wd = cv.take<D>(MM); D* sd = cv.take<D>(M);
-    D* Lm = cv.take<D>(MM); D* Linv = cv.take<D>(MM); D* Ki = cv.take<D>(MM); D* Su = cv.take<D>(MM); D* Lsinv = cv.take<D>(MM);
-    D* Sui = cv.take<D>(MM); D* KiSu = cv.take<D>(MM); D* H0 = cv.take<D>(MM); D* tmp = cv.take<D>(MM);
-    D* wd = cv.take<D>(MP); D* sc = cv.take<D>(16); D* scal = cv.take<D>(2 * (size_t)S); int* info2 = cv.take<int>(8);
-    T* Aext = cv.take<T>((size_t)(M + P) * M); T* wT = cv.take<T>(MP);
-    T* Text = cv.take<T>((size_t)(M + P) * SB); T* qbuf = cv.take<T>((size_t)SB);
-    unsigned short* plKfu = nullptr; unsigned short* plH0 = nullptr; unsigned short* plKuf = nullptr;
-    T* Kuf = nullptr; T* Kfu = nullptr; T* Psi2 = nullptr; T* R = nullptr; T* Eb = nullptr;
-    float* gscr0 = nullptr; float* gscr1 = nullptr;
-    if (use_split) { plKfu = cv.take<unsigned short>(3 * pl_big); plH0 = cv.take<unsigned short>(3 * pl_h0); plKuf = cv.take<unsigned short>(3 * pl_big);
-                     gscr0 = (float*)cv.take<char>(gp_scr); gscr1 = (float*)cv.take<char>(gp_scr); }
-    else { Kuf = cv.take<T>((size_t)M * SB); if (want_grad) Kfu = cv.take<T>((size_t)M * SB); }
-    unsigned short* plLi = nullptr; D* ad = nullptr; T* aT = nullptr; float* sigf = nullptr;
-    float* upart = nullptr;
-    if (whiten) { plLi = cv.take<unsigned short>(2 * pl_h0); ad = cv.take<D>(MP); aT = cv.take<T>(MP); sigf = cv.take<float>(4); upart = cv.take<float>((size_t)(M / 128) * SB); }
-    unsigned short* wpl = nullptr;
-    if (bt_path || bt_wh) wpl = cv.take<unsigned short>(2 * (size_t)M + 8);
-    // whitened tier: the planes of V^T (operand (n, k = m) of T = Hh V) go into the THIRD plane slots of the two big buffers (sized for the
-    // three-plane bf16 format; the whitened tier runs two-plane f16x2 only) -- the V product writes them next to V's own planes while other
-    // workgroups still read the Kfu planes, so they cannot share that buffer's first two slots
-    unsigned short* plVt = whiten ? plKfu + 2 * pl_big : nullptr;
-    const int64_t pVt = whiten ? (int64_t)((plKuf + 2 * pl_big) - plVt) : 0;
-    float* hcs = nullptr; float* hrs = nullptr; float* hys = nullptr; D* hhs = nullptr; D* hbe2 = nullptr; float* hnz = nullptr;
-    if (het_stream) { hcs = cv.take<float>(B); hrs = cv.take<float>(B); hys = cv.take<float>((size_t)(sY == 0 ? B : SB)); hhs = cv.take<D>(4); hbe2 = cv.take<D>(S); hnz = cv.take<float>(4); }
-    unsigned short* hsA = nullptr; unsigned short* hsK = nullptr; unsigned short* hsS = nullptr; unsigned* hsw = nullptr;
-    if (het_split) { hsA = cv.take<unsigned short>(2 * pl_h0); hsK = cv.take<unsigned short>(2 * pl_big); hsS = cv.take<unsigned short>(2 * pl_big); hsw = cv.take<unsigned>(4); }
-    if (want_grad) { Psi2 = cv.take<T>(MM); R = cv.take<T>(MP); Eb = cv.take<T>((size_t)SB * P); }
-    D* G = nullptr; D* T1 = nullptr; D* AKi = nullptr; D* T2 = nullptr; D* dKuu = nullptr; D* dSu = nullptr;
-    D* Gw = nullptr; D* dmud = nullptr; D* dZc = nullptr; D* dlsc = nullptr; D* dvc = nullptr;
-    if (want_grad) {
-        G = cv.take<D>(MM); T1 = cv.take<D>(MM); AKi = cv.take<D>(MM); T2 = cv.take<D>(MM); dKuu = cv.take<D>(MM); dSu = cv.take<D>(MM);
-        Gw = cv.take<D>(MP); dmud = cv.take<D>(MP); dZc = cv.take<D>(M * Q); dlsc = cv.take<D>(lsn); dvc = cv.take<D>(4);
-    }
-    // sc: [0]=sumlogdiag L, [1]=sumlogdiag Ls, [2]=tr(Ki Su), [3]=mu.w, [4]=dnoise, [5]=dvar_direct
-    // the accounting above and the carve must stay in step (a dangling else once had them 4 GB apart)
-    if (cv.off > need) MXF_FAIL(h, -6, "mxf_svgp_logpdf: internal error, scratch carve %zu exceeds its accounting %zu", cv.off, need);
-#ifdef MXF_PROBES
-    if (cv.off != need) MXF_FAIL(h, -6, "mxf_svgp_logpdf: internal error, scratch carve %zu != accounting %zu", cv.off, need);
-#endif
+    // float32 mode: the symmetric products of the core -- Ki, H0 and X = Ki G Ki -- as lower tiles + mirror (half the work of a product that
+    // runs on the 88 CUs Psi2 leaves in the few-sample regime; the results become exactly symmetric), and the core's reverse mode in the X form.
+    // dKuu then comes out exactly symmetric, and its Gram reverse pass skips the row side (dk_symmetric): one condition for both.
+    // (The float64 path is the parity path and stays operation for operation what the trajectory tests were recorded with --
+    //  tests/test_svgp_notebook.py's 100-epoch float64 run moved its learned noise by 12 % with exactly symmetric Ki / H0, past its 10 % band.)
+    static constexpr bool sym_core = sizeof(T) == 4;
+    static constexpr int split_mode = MXF_SPLIT_F16X2;
+    static constexpr float split_ga = 1.f / 16384.f;     // Gram planes hold k / variance * 2^14 in the f16x2 format
 
-#define CONV(n, src, dst) hipLaunchKernelGGL((convert_kernel<T, D>), dim3(gridn(n)), dim3(256), 0, st, (int64_t)1, (int64_t)(n), src, (int64_t)(n), dst, (int64_t)(n))
-    // (W and diag(s) are converted on the second side stream, where Su is formed: two launches less in front of the Kuu chain)
-    // (everything the Kuu chain does not need itself -- noise, mu, W, diag(s), the scalar accumulators -- is prepared on the second side
-    //  stream, where Su is formed; the main stream waits for that stream's ev_su before it first touches them)
-    MXF_STAGE(h, "start", st);
-    if (!mxf_cond_init(h)) MXF_FAIL(h, -4, "mxf_svgp_logpdf: cannot allocate the condition words");
-    double* cond_slot = h->cond_host + 2 * h->cond_slot;
-    for (int i = 0; i < MXF_NT; ++i) h->tm.used[i] = false;
-    MXF_T0(h, MXF_T_CALL, st); MXF_T0(h, MXF_T_CHAIN, st);
-    if (!use_mat)
-        hipLaunchKernelGGL((svgp_prologue_kernel<T>), dim3(gridn(M * Q) > 64 ? 64 : gridn(M * Q)), dim3(256), 0, st, info, info2, h->cond_dev, (int64_t)(M * Q), Z, Zd,
-                           (int64_t)lsn, ls, lsd, var, vard, whiten ? sigf : (float*)nullptr);
-    else {
-        hipLaunchKernelGGL(svgp_init_kernel, dim3(1), dim3(64), 0, st, info, info2, h->cond_dev);
-        if (whiten) hipLaunchKernelGGL(svgp_sigma_kernel, dim3(1), dim3(64), 0, st, (const float*)var, sigf);
+    hipStream_t sd_ = nullptr, s2_ = nullptr;             // h->side, h->side2
+    double* cond_slot = nullptr;
+    int t_blocked = 0;
+
+    // scratch (carve; what a path does not take stays null)
+    D *Zd, *lsd, *vard, *noised, *mud, *Wd, *sd, *Lm, *Linv, *Ki, *Su, *Lsinv, *Sui, *KiSu, *H0, *tmp, *wd, *sc, *scal, *ad, *hhs, *hbe2;
+    D *G, *T1, *AKi, *T2, *dKuu, *dSu, *Gw, *dmud, *dZc, *dlsc, *dvc;
+    T *Aext, *wT, *Text, *qbuf, *Kuf, *Kfu, *Psi2, *R, *Eb, *aT;
+    unsigned short *plKfu, *plH0, *plKuf, *plLi, *wpl, *plVt, *hsA, *hsK, *hsS;
+    float *gscr0, *gscr1, *sigf, *upart, *hcs, *hrs, *hys, *hnz;
+    int* info2; unsigned* hsw; int64_t pVt;
+
+    // C = alpha op(A) op(B) + beta C for M x M float64 operands (lower: the lower tiles only)
+    int mm(int ta, int tb, double alpha, const D* A, const D* Bm, double beta, D* C, hipStream_t s_, int lower = 0) {
+        return mxf_gemm_internal(h, MXF_F64, ta, tb, M, M, M, alpha, A, M, 0, Bm, M, 0, beta, C, M, 0, 1, lower, s_);
     }
-    if (het_stream) {       // nmin, the row weights, sum log noise / sum beta, y' = r y -- before the fork: both side streams read them
-        MXF_HIP(h, hipMemsetAsync(info2 + 5, 0x7f, sizeof(int), st));                 // 0x7f7f7f7f: a huge finite float, above any noise variance
-        MXF_HIP(h, hipMemsetAsync(hhs, 0, 4 * sizeof(D), st));
-        MXF_HIP(h, hipMemsetAsync(hbe2, 0, (size_t)S * sizeof(D), st));
-        const unsigned pg = (unsigned)((B + 255) / 256 > 256 ? 256 : (B + 255) / 256);
-        hipLaunchKernelGGL(het_min_kernel, dim3(pg), dim3(256), 0, st, B, (const float*)noise, (unsigned*)(info2 + 5));
-        hipLaunchKernelGGL(het_prep_kernel, dim3(pg), dim3(256), 0, st, B, (const float*)noise, (const unsigned*)(info2 + 5), hcs, hrs, hhs, hnz, noised);
-        const int64_t ny = sY == 0 ? B : SB;
-        hipLaunchKernelGGL(het_scale_y_kernel, dim3(gridn(ny)), dim3(256), 0, st, ny, B, (const float*)Y, (const float*)hrs, hys);
+    template <typename U> void symmetrize(U* A, hipStream_t s_) {      // mirror the lower triangle of an M x M matrix
+        hipLaunchKernelGGL((symmetrize_kernel<U>), dim3((unsigned)((M + 31) / 32), (unsigned)((M + 31) / 32), 1), dim3(256), 0, s_, A, M, M, MM);
     }
-#undef CONV
-    int rc;
-    static const int64_t psi2_ka = MXF_KNOB("MXF_SVGP_PSI2_KA", -1);
-    static const bool psi2_ra_env = MXF_KNOB_SET("MXF_SVGP_PSI2_RA");
-    static const int psi2_ra = (int)MXF_KNOB("MXF_SVGP_PSI2_RA", 148);
-    static const int psi2_rb = MXF_KNOB("MXF_SVGP_PSI2_RB", 16);
-    // ---- core, float64, once; two independent chains run concurrently (main: Kuu -> L -> Ki, w; side: Kuf_all, Su -> Ls -> Su^-1) ----
-    if (!mxf_side_init(h)) MXF_FAIL(h, -5, "mxf_svgp_logpdf: cannot create the internal side stream");
-    hipStream_t sd_ = h->side;
-    if (use_mat) {
-        hipLaunchKernelGGL((convert_kernel<T, D>), dim3(gridn(MM)), dim3(256), 0, st, (int64_t)1, MM, mat.Kuu, MM, Lm, MM);
-        if (jitter != 0.0) hipLaunchKernelGGL(add_diag_kernel, dim3(gridn(M)), dim3(256), 0, st, M, Lm, jitter);
-        rc = 0;
-    } else {
-        rc = mxf_gram(h, kind, MXF_F64, 1, M, M, Q, Zd, 0, nullptr, 0, lsd, ard, 0, vard, 0, nullptr, 0, jitter, MXF_WRITE, Lm, M, MM, st);   // Kuu (+jitter) :69-72
+    // the accumulate-into gradient outputs: dY and (the caller's Gram not given) dZ, dls, dvar, dX; the core's float64 dZ, dls, dvar
+    int clear_grads(hipStream_t s_) {
+        if (dY) MXF_HIP(h, hipMemsetAsync(dY, 0, sizeof(T) * (size_t)(ysamp ? (int64_t)S * B : (sY == 0 ? B : SB)) * P, s_));
+        if (use_mat) return 0;
+        if (dZ) MXF_HIP(h, hipMemsetAsync(dZ, 0, sizeof(T) * M * Q, s_));
+        if (dls) MXF_HIP(h, hipMemsetAsync(dls, 0, sizeof(T) * lsn, s_));
+        if (dvar) MXF_HIP(h, hipMemsetAsync(dvar, 0, sizeof(T), s_));
+        if (dX) MXF_HIP(h, hipMemsetAsync(dX, 0, sizeof(T) * (size_t)SB * Q, s_));
+        return 0;
     }
-    if (rc) return rc;
-    MXF_HIP(h, hipEventRecord(h->ev_fork, st));
-    hipStream_t s2_ = h->side2;
-    MXF_HIP(h, hipStreamWaitEvent(sd_, h->ev_fork, 0));
-    MXF_HIP(h, hipStreamWaitEvent(s2_, h->ev_fork, 0));
-    // second side stream, first thing: Su (H0 on the critical path needs it; its Cholesky comes later and is off the critical path)
-    MXF_HIP(h, hipMemsetAsync(sc, 0, 16 * sizeof(D), s2_));
-    MXF_HIP(h, hipMemsetAsync(scal, 0, 2 * (size_t)S * sizeof(D), s2_));
-    // (r04) the accumulate-into outputs of the fused reverse pass and of the core's reverse mode are cleared HERE, on the second side stream at
-    // the start of the call (it joins the caller's stream before the reverse pass): nine fills that used to sit between the T product and the
-    // reverse pass on the critical path (~10 us of queue latency apiece: 0.1 ms of a 4.6 ms per-rank step)
-    const bool early_clear = want_grad && !het;
-    if (early_clear) {
-        if (dY) MXF_HIP(h, hipMemsetAsync(dY, 0, sizeof(T) * (size_t)(sY == 0 ? B : SB) * P, s2_));
-        if (dZ) MXF_HIP(h, hipMemsetAsync(dZ, 0, sizeof(T) * M * Q, s2_));
-        if (dls) MXF_HIP(h, hipMemsetAsync(dls, 0, sizeof(T) * lsn, s2_));
-        if (dvar) MXF_HIP(h, hipMemsetAsync(dvar, 0, sizeof(T), s2_));
-        if (dX) MXF_HIP(h, hipMemsetAsync(dX, 0, sizeof(T) * (size_t)SB * Q, s2_));
-        MXF_HIP(h, hipMemsetAsync(R, 0, sizeof(T) * MP, s2_));
-        if (!use_mat) {
-            MXF_HIP(h, hipMemsetAsync(dZc, 0, sizeof(D) * M * Q, s2_));
-            MXF_HIP(h, hipMemsetAsync(dlsc, 0, sizeof(D) * lsn, s2_));
-            MXF_HIP(h, hipMemsetAsync(dvc, 0, sizeof(D) * 4, s2_));
+    int clear_core_grads(hipStream_t s_) {
+        MXF_HIP(h, hipMemsetAsync(dZc, 0, sizeof(D) * M * Q, s_));
+        MXF_HIP(h, hipMemsetAsync(dlsc, 0, sizeof(D) * lsn, s_));
+        MXF_HIP(h, hipMemsetAsync(dvc, 0, sizeof(D) * 4, s_));
+        return 0;
+    }
+    void publish_cond() { hipLaunchKernelGGL(cond_publish_kernel, dim3(1), dim3(1), 0, st, h->cond_dev, cond_slot); }
+
+    // every path flag of the call, and the shape checks that go with them
+    int plan() {
+        constexpr bool f32 = sizeof(T) == 4;
+        if (P > 8) MXF_FAIL(h, -3, "mxf_svgp_logpdf: P > 8 outputs not supported");
+        if ((nrows != 1 && nrows != B) || (ncols != 1 && ncols != P)) MXF_FAIL(h, -2, "mxf_svgp_logpdf: noise_var must be (1|B, 1|P)");
+        use_mat = mat.Kuu != nullptr;
+        // sampled Y over shared X (hence shared Kuf, T, U): the S samples share the B columns -- generic path, the data term is quadratic in Y
+        ysamp = S > 1 && sX == 0 && sY != 0;
+        if (ysamp && sY != B * P) MXF_FAIL(h, -2, "mxf_svgp_logpdf: Y samples must be contiguous");
+        SS = (sX == 0) ? 1 : S;
+        SB = (int64_t)SS * B;
+        // generic path (het): Kuf-side reverse mode through a materialised dKuf (not the streaming fused pass); also for Q > 16 inputs, which the
+        // register-tiled fused reverse pass does not cover (gram_bwd.hip: generic kernel).  Per-row noise (B, 1) with one output column on the
+        // float32 split path runs the STREAMING form (het_stream: het_* kernels above); every other heteroscedastic shape keeps the generic path.
+        het_stream = f32 && want_grad && nrows == B && nrows > 1 && ncols == 1 && P == 1 && !use_mat && !ysamp && Q <= 8 && (B % 16 == 0) &&
+                     (M % 16 == 0) && M >= 128 && h->svgp_form == MXF_SVGP_EXPLICIT && mxf_svgp_bwd_is_mfma(kind, dtype, SB, B, Q, P, X);
+        het = (nrows > 1 || ncols > 1 || use_mat || ysamp || Q > 16) && !het_stream;
+        if (sX != 0 && sX != B * Q) MXF_FAIL(h, -2, "mxf_svgp_logpdf: X samples must be contiguous");
+        if (S > 1 && sX == 0 && sY == 0) MXF_FAIL(h, -3, "mxf_svgp_logpdf: S > 1 with neither X nor Y sampled");
+        SYc = ysamp ? S : 1;
+        MM = M * M; MP = M * P;
+        lsn = ard ? Q : 1;
+        a1 = gscale * scaling; bw = gscale * (double)S;
+        fused = want_grad && !het;
+        // float32 streaming: the two big GEMMs run on the 16-bit matrix pipe from split planes of their operands (gemm_split.hip), in the format
+        // of two scaled f16 terms (three products)
+        use_split = fused && f32 && (SB % 16 == 0) && (M % 16 == 0) && M >= 128 && Q <= 16;
+        pl_big = mxf_split_plane_elems(M, SB); pl_h0 = mxf_split_plane_elems(M, M);     // == mxf_split_plane_elems(SB, M)
+        gp_scr = use_split ? mxf_gram_planes_scratch_bytes(SB, SB, Q) : 0;      // upper bound for either orientation
+        split_var = (const float*)var;
+        // float32 streaming form (mxf_svgp_configure): the whitened tier runs on the f16x2 split kernels' wide forms only
+        whiten = f32 && want_grad && h->svgp_form == MXF_SVGP_WHITENED;
+        if (whiten && !(use_split && (M % 128) == 0 && (SB % 256) == 0))
+            MXF_FAIL(h, -3, "mxf_svgp_logpdf: the whitened float32 form needs M %% 128 == 0, S B %% 256 == 0, Q <= 16, homoscedastic noise (see mxf_svgp_whitened_ok)");
+        // ONE set of Kuf planes: T = H0 Kuf reads the planes Psi2 reads (operand (m, k = n)) through gemm_bt.hip's transposing LDS read, and forms
+        // the row U = w^T Kuf on the way (a second planes pass wrote 8.6 GB between the two products: 1.8 ms of the 24 ms step with the matrix pipe
+        // idle).  Needs the explicit float32 form, one output column, whole 256 x 256 tiles.
+        bt_path = use_split && !whiten && !het_stream && P == 1 && M <= 2048 && mxf_gemm_bt_ok(M, SB, M);
+        // the whitened tier likewise: T = Hh V reads the planes of V that Phi = V V^T reads (the V product's planes output IS the K-major layout),
+        // and forms U = a^T V on the way -- the V product writes neither the planes of V^T (8.6 GB) nor the partial sums of U
+        bt_wh = whiten && P == 1 && M <= 2048 && mxf_gemm_bt_ok(M, SB, M);
+        // the generic (materialised-Gram / heteroscedastic) float32 path's two big products on the f16 matrix pipe as well: T = H0 Kuf through the
+        // K-major product from the planes of Kuf (split from the float32 Gram: one maxabs + one split pass, 0.17 ms at 512 x 131 072), and
+        // G' = Ksc Kuf^T from the planes of Ksc and the same Kuf planes -- f32-equivalent like the streaming path's products (three f16 products, f32
+        // accumulation) where the generic kernel ran true-f32 MFMAs at 100 TF: the deep GP's first layer 0.68 + 0.66 ms -> planes 0.35 + products 0.3.
+        het_split = het && f32 && want_grad && mxf_gemm_bt_ok(M, SB, M) && (int64_t)M * SB >= (int64_t)1 << 24;
+        return 0;
+    }
+
+    // the scratch layout, one list: scratch() runs it once to count and once to carve
+    void carve(Carver& cv) {
+        Zd = cv.take<D>(M * Q); lsd = cv.take<D>(lsn); vard = cv.take<D>(1); noised = cv.take<D>(1);     // f64 copies of the parameters
+        mud = cv.take<D>(MP); Wd = cv.take<D>(MM); sd = cv.take<D>(M);
+        Lm = cv.take<D>(MM); Linv = cv.take<D>(MM); Ki = cv.take<D>(MM); Su = cv.take<D>(MM); Lsinv = cv.take<D>(MM);
+        Sui = cv.take<D>(MM); KiSu = cv.take<D>(MM); H0 = cv.take<D>(MM); tmp = cv.take<D>(MM);
+        wd = cv.take<D>(MP); sc = cv.take<D>(16); scal = cv.take<D>(2 * (size_t)S); info2 = cv.take<int>(8);
+        Aext = cv.take<T>((size_t)(M + P) * M); wT = cv.take<T>(MP);
+        Text = cv.take<T>((size_t)(M + P) * SB); qbuf = cv.take<T>((size_t)SB);
+        if (use_split) {
+            plKfu = cv.take<unsigned short>(3 * pl_big); plH0 = cv.take<unsigned short>(3 * pl_h0); plKuf = cv.take<unsigned short>(3 * pl_big);
+            gscr0 = (float*)cv.take<char>(gp_scr); gscr1 = (float*)cv.take<char>(gp_scr);
+        } else {
+            Kuf = cv.take<T>((size_t)M * SB);        // Kuf, Kfu in the streaming dtype
+            if (want_grad) Kfu = cv.take<T>((size_t)M * SB);
         }
+        if (whiten) { plLi = cv.take<unsigned short>(2 * pl_h0); ad = cv.take<D>(MP); aT = cv.take<T>(MP); sigf = cv.take<float>(4); upart = cv.take<float>((size_t)(M / 128) * SB); }
+        if (bt_path || bt_wh) wpl = cv.take<unsigned short>(2 * (size_t)M + 8);
+        if (het_stream) { hcs = cv.take<float>(B); hrs = cv.take<float>(B); hys = cv.take<float>((size_t)(sY == 0 ? B : SB)); hhs = cv.take<D>(4); hbe2 = cv.take<D>(S); hnz = cv.take<float>(4); }
+        if (het_split) { hsA = cv.take<unsigned short>(2 * pl_h0); hsK = cv.take<unsigned short>(2 * pl_big); hsS = cv.take<unsigned short>(2 * pl_big); hsw = cv.take<unsigned>(4); }
+        if (want_grad) {
+            Psi2 = cv.take<T>(MM); R = cv.take<T>(MP); Eb = cv.take<T>((size_t)SB * P);
+            G = cv.take<D>(MM); T1 = cv.take<D>(MM); AKi = cv.take<D>(MM); T2 = cv.take<D>(MM); dKuu = cv.take<D>(MM); dSu = cv.take<D>(MM);
+            Gw = cv.take<D>(MP); dmud = cv.take<D>(MP); dZc = cv.take<D>(M * Q); dlsc = cv.take<D>(lsn); dvc = cv.take<D>(4);
+        }
+        // sc: [0]=sumlogdiag L, [1]=sumlogdiag Ls, [2]=tr(Ki Su), [3]=mu.w, [4]=dnoise, [5]=dvar_direct, [6], [7]: whitened tier's q_n total
     }
-    if (!het && !het_stream) hipLaunchKernelGGL((convert_kernel<T, D>), dim3(1), dim3(256), 0, s2_, (int64_t)1, (int64_t)1, noise, (int64_t)1, noised, (int64_t)1);
-    hipLaunchKernelGGL((convert_kernel<T, D>), dim3(gridn(MP)), dim3(256), 0, s2_, (int64_t)1, (int64_t)MP, mu, (int64_t)MP, mud, (int64_t)MP);
-    hipLaunchKernelGGL((convert_kernel<T, D>), dim3(gridn(MM)), dim3(256), 0, s2_, (int64_t)1, (int64_t)MM, W, (int64_t)MM, Wd, (int64_t)MM);
-    hipLaunchKernelGGL((convert_kernel<T, D>), dim3(gridn(M)), dim3(256), 0, s2_, (int64_t)1, (int64_t)M, sdiag, (int64_t)M, sd, (int64_t)M);
-    hipLaunchKernelGGL((diag_embed_kernel<D>), dim3(gridn(MM)), dim3(256), 0, s2_, M, (const D*)sd, Su);
-    rc = mxf_gemm_internal(h, MXF_F64, 0, 1, M, M, M, 1.0, Wd, M, 0, Wd, M, 0, 1.0, Su, M, 0, 1, 0, s2_);       // Su = W W^T + diag(s) :76
-    if (rc) return rc;
-    MXF_HIP(h, hipEventRecord(h->ev_su, s2_));           // H0 needs Su only; its Cholesky (log-det, Su^-1 for the reverse mode) is OFF the critical path
-    MXF_STAGE(h, "Su formed (s2)", s2_);
-    // Enqueue order = priority order (the host needs ~5 us per launch and a step has ~280 of them): first the few launches that carry
-    // the bulk of the device work (Grams, Psi2), then the latency-critical Kuu chain, then the Su chain.
-    // ---- side stream: Kuf_all, Kfu_all, Psi2 --------------------------------------------------------------------------------
-    if (use_mat) {
-        // (r06: the caller's Gram is only ever read -- no copy into the scratch (268 MB, 0.13 ms at 512 x 131 072))
-        Kuf = const_cast<T*>(mat.Kuf);
-    } else if (whiten) {
-        // whitened tier: only the Kfu planes (operand (n, k = m) of V = L^-1 Kuf); they need nothing from the core, so they are written
-        // first; V, its transposition (+ U = a^T V) and Phi = V V^T follow on this stream once L^-1 exists (below, after the Kuu chain
-        // has been queued)
-        MXF_T0(h, MXF_T_PLANES_A, sd_);
-        rc = mxf_gram_planes_internal(h, kind, SB, M, Q, (const float*)X, (const float*)Z, (const float*)ls, ard, (const float*)var, plKfu,
-                                      (int64_t)pl_big, gscr1, sd_, split_mode);
-        if (rc) return rc;
-        MXF_T1(h, MXF_T_PLANES_A, sd_);
-        MXF_STAGE(h, "Kfu planes (sd)", sd_);
-    } else if (use_split) {
-        // float32 training step: the Grams are written directly as split planes (two scaled f16 terms = 4 bytes per element, never as f32):
-        // Kuf planes (operand (m, k = n)) feed Psi2 and come first so that Psi2 (MFMA bound) starts early; the Kfu planes (operand
-        // (n, k = m): T GEMM and the w^T Kuf row) are then written (HBM bound) on the second side stream NEXT TO Psi2.
-        MXF_T0(h, MXF_T_PLANES_A, sd_);
-        rc = mxf_gram_planes_internal(h, kind, M, SB, Q, (const float*)Z, (const float*)X, (const float*)ls, ard, (const float*)var, plKuf,
-                                      (int64_t)pl_big, gscr0, sd_, split_mode, nullptr, 0, nullptr, 0, het_stream ? (const float*)hcs : nullptr, nullptr, B);
-        if (rc) return rc;
-        MXF_T1(h, MXF_T_PLANES_A, sd_);
-        MXF_STAGE(h, "Kuf planes (sd)", sd_);
-        if (bt_path) MXF_HIP(h, hipEventRecord(h->ev_aux, sd_));     // the T product reads THESE planes
-        // (the Kfu planes -- operand (n, k = m) of the T GEMM -- are written later, on the second side stream, once w = Kuu^-1 mu exists:
-        //  the same pass then also forms the row U = w^T Kuf)
-    } else {
-        rc = mxf_gram(h, kind, dtype, 1, M, SB, Q, Z, 0, X, 0, ls, ard, 0, var, 0, nullptr, 0, 0.0, MXF_WRITE, Kuf, SB, 0, sd_);          // Kuf_all = k(Z, X_all) :73
-        if (rc) return rc;
+
+    int scratch() {
+        size_t need;
+        if (!carve_scratch(h, [&](Carver& cv) { carve(cv); }, need)) MXF_FAIL(h, -4, "mxf_svgp_logpdf: cannot allocate %zu bytes of scratch", need);
+        // whitened tier: the planes of V^T (operand (n, k = m) of T = Hh V) go into the THIRD plane slots of the two big buffers (sized for the
+        // three-plane bf16 format; the whitened tier runs two-plane f16x2 only) -- the V product writes them next to V's own planes while other
+        // workgroups still read the Kfu planes, so they cannot share that buffer's first two slots
+        if (whiten) { plVt = plKfu + 2 * pl_big; pVt = (int64_t)((plKuf + 2 * pl_big) - plVt); }
+        // (training step on the split path whose reverse pass runs on the matrix pipe: T is written in 16-column blocks, so that each 16 x 16
+        //  tile that pass reads is one contiguous KB instead of 16 pieces of 64 bytes, 4 SB bytes apart)
+        t_blocked = (use_split && mxf_svgp_bwd_reads_blocked(kind, dtype, SB, B, Q, P, Text)) ? 1 : 0;
+        return 0;
     }
-    if (!use_split) MXF_HIP(h, hipEventRecord(h->ev_aux, sd_));          // Kuf ready: the T GEMM waits for it
-    if (want_grad && !het && !whiten) {
+
+    // caller's stream: the status words, the float64 copies of the Kuu Gram's parameters; het_stream: the row weights
+    int prologue() {
+        MXF_STAGE(h, "start", st);
+        if (!mxf_cond_init(h)) MXF_FAIL(h, -4, "mxf_svgp_logpdf: cannot allocate the condition words");
+        cond_slot = h->cond_host + 2 * h->cond_slot;
+        for (int i = 0; i < MXF_NT; ++i) h->tm.used[i] = false;
+        MXF_T0(h, MXF_T_CALL, st); MXF_T0(h, MXF_T_CHAIN, st);
+        if (!use_mat)
+            hipLaunchKernelGGL((svgp_prologue_kernel<T>), dim3(gridn(M * Q) > 64 ? 64 : gridn(M * Q)), dim3(256), 0, st, info, info2, h->cond_dev, (int64_t)(M * Q), Z, Zd,
+                               (int64_t)lsn, ls, lsd, var, vard, whiten ? sigf : (float*)nullptr);
+        else {
+            hipLaunchKernelGGL(svgp_init_kernel, dim3(1), dim3(64), 0, st, info, info2, h->cond_dev);
+            if (whiten) hipLaunchKernelGGL(svgp_sigma_kernel, dim3(1), dim3(64), 0, st, (const float*)var, sigf);
+        }
+        if (het_stream) {       // nmin, the row weights, sum log noise / sum beta, y' = r y -- before the fork: both side streams read them
+            MXF_HIP(h, hipMemsetAsync(info2 + 5, 0x7f, sizeof(int), st));                 // 0x7f7f7f7f: a huge finite float, above any noise variance
+            MXF_HIP(h, hipMemsetAsync(hhs, 0, 4 * sizeof(D), st));
+            MXF_HIP(h, hipMemsetAsync(hbe2, 0, (size_t)S * sizeof(D), st));
+            const unsigned pg = (unsigned)((B + 255) / 256 > 256 ? 256 : (B + 255) / 256);
+            hipLaunchKernelGGL(het_min_kernel, dim3(pg), dim3(256), 0, st, B, (const float*)noise, (unsigned*)(info2 + 5));
+            hipLaunchKernelGGL(het_prep_kernel, dim3(pg), dim3(256), 0, st, B, (const float*)noise, (const unsigned*)(info2 + 5), hcs, hrs, hhs, hnz, noised);
+            const int64_t ny = sY == 0 ? B : SB;
+            hipLaunchKernelGGL(het_scale_y_kernel, dim3(gridn(ny)), dim3(256), 0, st, ny, B, (const float*)Y, (const float*)hrs, hys);
+        }
+        return 0;
+    }
+
+    // caller's stream: Kuu (+ jitter), then the fork of the two side streams.  The core runs in float64, once; two independent chains run
+    // concurrently (main: Kuu -> L -> Ki, w; side: Kuf_all, Su -> Ls -> Su^-1)
+    int kuu_fork() {
+        if (!mxf_side_init(h)) MXF_FAIL(h, -5, "mxf_svgp_logpdf: cannot create the internal side stream");
+        sd_ = h->side; s2_ = h->side2;
+        if (use_mat) {
+            copy_convert(MM, mat.Kuu, Lm, st);
+            if (jitter != 0.0) hipLaunchKernelGGL(add_diag_kernel, dim3(gridn(M)), dim3(256), 0, st, M, Lm, jitter);
+        } else {
+            const int rc = mxf_gram(h, kind, MXF_F64, 1, M, M, Q, Zd, 0, nullptr, 0, lsd, ard, 0, vard, 0, nullptr, 0, jitter, MXF_WRITE, Lm, M, MM, st);   // Kuu (+jitter) :69-72
+            if (rc) return rc;
+        }
+        MXF_HIP(h, hipEventRecord(h->ev_fork, st));
+        MXF_HIP(h, hipStreamWaitEvent(sd_, h->ev_fork, 0));
+        MXF_HIP(h, hipStreamWaitEvent(s2_, h->ev_fork, 0));
+        return 0;
+    }
+
+    // second side stream, first thing: Su (H0 on the critical path needs it; its Cholesky comes later and is off the critical path).  Everything
+    // the Kuu chain does not need itself -- noise, mu, W, diag(s), the scalar accumulators -- is prepared here too; the main stream waits for
+    // ev_su before it first touches them.
+    int su_side2() {
+        MXF_HIP(h, hipMemsetAsync(sc, 0, 16 * sizeof(D), s2_));
+        MXF_HIP(h, hipMemsetAsync(scal, 0, 2 * (size_t)S * sizeof(D), s2_));
+        // the accumulate-into outputs of the fused reverse pass and of the core's reverse mode are cleared HERE, on the second side stream at
+        // the start of the call (it joins the caller's stream before the reverse pass): between the T product and the reverse pass on the
+        // critical path these nine fills cost ~10 us of queue latency apiece (0.1 ms of a 4.6 ms per-rank step)
+        if (fused) {           // (fused: neither ysamp nor use_mat)
+            if (int rc = clear_grads(s2_)) return rc;
+            MXF_HIP(h, hipMemsetAsync(R, 0, sizeof(T) * MP, s2_));
+            if (int rc = clear_core_grads(s2_)) return rc;
+        }
+        if (!het && !het_stream) copy_convert((int64_t)1, noise, noised, s2_);
+        copy_convert(MP, mu, mud, s2_);
+        copy_convert(MM, W, Wd, s2_);
+        copy_convert(M, sdiag, sd, s2_);
+        hipLaunchKernelGGL((diag_embed_kernel<D>), dim3(gridn(MM)), dim3(256), 0, s2_, M, (const D*)sd, Su);
+        const int rc = mm(0, 1, 1.0, Wd, Wd, 1.0, Su, s2_);       // Su = W W^T + diag(s) :76
+        if (rc) return rc;
+        MXF_HIP(h, hipEventRecord(h->ev_su, s2_));           // H0 needs Su only; its Cholesky (log-det, Su^-1 for the reverse mode) is OFF the critical path
+        MXF_STAGE(h, "Su formed (s2)", s2_);
+        return 0;
+    }
+
+    // side stream: Kuf_all (as a Gram or as split planes; whitened: the Kfu planes), Kfu_all and Psi2.  Queued before the Kuu chain: these few
+    // launches carry the bulk of the device work.
+    int kuf_psi2() {
+        static const int64_t psi2_ka = MXF_KNOB("MXF_SVGP_PSI2_KA", -1);
+        static const bool psi2_ra_env = MXF_KNOB_SET("MXF_SVGP_PSI2_RA");
+        static const int psi2_ra = (int)MXF_KNOB("MXF_SVGP_PSI2_RA", 148);
+        static const int psi2_rb = MXF_KNOB("MXF_SVGP_PSI2_RB", 16);
+        int rc;
+        if (use_mat) {
+            Kuf = const_cast<T*>(mat.Kuf);          // the caller's Gram is only ever read (a copy into the scratch: 268 MB, 0.13 ms at 512 x 131 072)
+        } else if (whiten) {
+            // whitened tier: only the Kfu planes (operand (n, k = m) of V = L^-1 Kuf); they need nothing from the core, so they are written
+            // first; V, its transposition (+ U = a^T V) and Phi = V V^T follow on this stream once L^-1 exists (whiten_v_phi)
+            MXF_T0(h, MXF_T_PLANES_A, sd_);
+            rc = mxf_gram_planes_internal(h, kind, SB, M, Q, (const float*)X, (const float*)Z, (const float*)ls, ard, (const float*)var, plKfu,
+                                          (int64_t)pl_big, gscr1, sd_, split_mode);
+            if (rc) return rc;
+            MXF_T1(h, MXF_T_PLANES_A, sd_);
+            MXF_STAGE(h, "Kfu planes (sd)", sd_);
+        } else if (use_split) {
+            // float32 training step: the Grams are written directly as split planes (two scaled f16 terms = 4 bytes per element, never as f32):
+            // Kuf planes (operand (m, k = n)) feed Psi2 and come first so that Psi2 (MFMA bound) starts early; the Kfu planes (operand
+            // (n, k = m): T GEMM and the w^T Kuf row) are then written (HBM bound) on the second side stream NEXT TO Psi2 (su_chain), unless
+            // the T product reads these planes (bt_path).
+            MXF_T0(h, MXF_T_PLANES_A, sd_);
+            rc = mxf_gram_planes_internal(h, kind, M, SB, Q, (const float*)Z, (const float*)X, (const float*)ls, ard, (const float*)var, plKuf,
+                                          (int64_t)pl_big, gscr0, sd_, split_mode, nullptr, 0, nullptr, 0, het_stream ? (const float*)hcs : nullptr, nullptr, B);
+            if (rc) return rc;
+            MXF_T1(h, MXF_T_PLANES_A, sd_);
+            MXF_STAGE(h, "Kuf planes (sd)", sd_);
+            if (bt_path) MXF_HIP(h, hipEventRecord(h->ev_aux, sd_));     // the T product reads THESE planes
+        } else {
+            rc = mxf_gram(h, kind, dtype, 1, M, SB, Q, Z, 0, X, 0, ls, ard, 0, var, 0, nullptr, 0, 0.0, MXF_WRITE, Kuf, SB, 0, sd_);          // Kuf_all = k(Z, X_all) :73
+            if (rc) return rc;
+        }
+        if (!use_split) MXF_HIP(h, hipEventRecord(h->ev_aux, sd_));          // Kuf ready: the T GEMM waits for it
+        if (!fused || whiten) return 0;
         // Psi2 = Kuf Kuf^T depends on neither the core nor the T GEMM nor the reverse pass: it starts at once on the side stream,
         // lower blocks only, split-K.  float32: from the split planes of Kuf (gemm_split.hip); float64 / fallback: from the TRANSPOSED
         // Gram Kfu (S*B x M, rows = contiguous lines) as a TN GEMM (the NT form on Kuf reads 256 K-strided streams per workgroup).
@@ -1153,18 +1212,18 @@ int svgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t B, int64_t
         // (few samples per GPU: the whole product runs in the reduced-occupancy form -- the core chains are the critical path there and
         //  Psi2 is short; same-box at 4 samples: 5.46 -> 5.20 ms per step; at 32 samples a longer first phase costs 0.1-0.4 ms)
         const int64_t ka_dflt = (use_split ? 192 : 128) * M;
-        // r06, one set of planes (bt_path): nothing but the core chains runs next to Psi2 any more (the second planes pass used to take the
-        // CUs Psi2 left free and starve the chain behind it), so the whole product leaves them 32 CUs and there is no reduced first phase --
-        // the chains finish under Psi2 and T starts when Psi2 ends (same box, 32 samples: 23.5 -> 22.85 ms per step; 24 CUs: 23.8; 40: 22.9)
+        // one set of planes (bt_path): nothing but the core chains runs next to Psi2, so the whole product leaves them 32 CUs and there is no
+        // reduced first phase -- the chains finish under Psi2 and T starts when Psi2 ends (same box, 32 samples: 23.5 -> 22.85 ms per step with
+        // a second planes pass beside it before; 24 CUs: 23.8; 40: 22.9)
         const int64_t ka_req = psi2_ka >= 0 ? psi2_ka : (use_split && SB <= 2 * ka_dflt ? SB : (bt_path ? 0 : ka_dflt));
         const int rb_phase_b = (bt_path && !MXF_KNOB_SET("MXF_SVGP_PSI2_RB")) ? 32 : psi2_rb;
         const int64_t KA = (ka_req > 0 && ka_req < SB) ? ka_req / 32 * 32 : (ka_req > 0 ? SB : 0);
         MXF_T0(h, MXF_T_PSI2, sd_);
         if (use_split) {
             if (KA > 0) {
-                // 4 workgroups of the two-term kernel fit a CU: (256 - 202) * 4 = 216 workgroups = one per CU on 216 CUs.  r06, one-planes path: (256 - 214) * 4 = 168 workgroups -- with the second planes pass
-                // gone the chains are alone on what Psi2 leaves, and 88 CUs serve the few-sample step better than 40 (same box, 4 samples:
-                // 4.30 -> 4.21 ms; 210: 4.25-4.32, 218: 4.22-4.26, 224: 4.27; configs[3] at 4 samples 2.41 -> 2.37)
+                // 4 workgroups of the two-term kernel fit a CU: (256 - 202) * 4 = 216 workgroups = one per CU on 216 CUs.  One-planes path:
+                // (256 - 214) * 4 = 168 workgroups -- the chains are alone on what Psi2 leaves, and 88 CUs serve the few-sample step better than 40
+                // (same box, 4 samples: 4.30 -> 4.21 ms; 210: 4.25-4.32, 218: 4.22-4.26, 224: 4.27; configs[3] at 4 samples 2.41 -> 2.37)
                 rc = mxf_gemm_split_internal(h, M, M, KA, (double)split_ga * split_ga, plKuf, (int64_t)pl_big, plKuf, (int64_t)pl_big, 0.0, (float*)Psi2, M, 1, sd_,
                                              psi2_ra_env ? psi2_ra : (bt_path ? 214 : 202), split_mode, split_var, 2, nullptr);
                 if (rc) return rc;
@@ -1188,63 +1247,74 @@ int svgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t B, int64_t
                 if (rc) return rc;
             }
         }
-        hipLaunchKernelGGL((symmetrize_kernel<T>), dim3((unsigned)((M + 31) / 32), (unsigned)((M + 31) / 32), 1), dim3(256), 0, sd_, Psi2, M, M, MM);
+        symmetrize(Psi2, sd_);
         MXF_T1(h, MXF_T_PSI2, sd_);
         MXF_STAGE(h, "Psi2 (sd)", sd_);
         MXF_HIP(h, hipEventRecord(h->ev_join2, sd_));
+        return 0;
     }
-    // ---- main stream: Kuu -> L -> L^-1 -> Ki, w (the critical path up to the T GEMM) --------------------------------------------
-    // condition number of Kuu + jitter I (1-norm), for the float32 validity check of mxf_svgp_last_cond: |Kuu|_1 here, |Ki|_1 below
-    // r06: what the T product does not need leaves the caller's stream -- the two condition norms (64 workgroups walking 16 rows each: 0.05 ms
-    // alone, 0.22 ms in front of the factorisation while the planes pass holds every CU), mu.w, tr(Ki Su), log|Kuu| go to the second side
-    // stream; w = Ki mu is a one-wave-per-row kernel.  Kuu is copied for its norm (the factorisation works in place).
-    hipLaunchKernelGGL((convert_kernel<D, D>), dim3(gridn(MM)), dim3(256), 0, st, (int64_t)1, MM, (const D*)Lm, MM, Sui, MM);     // (Su^-1's buffer: written at the end of the Su chain, on the same stream as the norm)
-    MXF_HIP(h, hipEventRecord(h->ev_k1, st));
-    MXF_HIP(h, hipStreamWaitEvent(s2_, h->ev_k1, 0));
-    hipLaunchKernelGGL(norm1_sym16_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, s2_, M, (const double*)Sui, M, h->cond_dev);
-    rc = mxf_potrf_internal(h, MXF_F64, 1, M, Lm, M, MM, info, st, false, false);                     // L :83 (trtri / sumlogdiag read the lower triangle only)
-    if (rc) return rc;
-    MXF_STAGE(h, "potrf Kuu", st);
-    rc = mxf_trtri_internal(h, MXF_F64, 1, M, Lm, M, MM, Linv, M, MM, st);
-    if (rc) return rc;
-    MXF_STAGE(h, "trtri Kuu", st);
-    unsigned* limax = (unsigned*)(info2 + 4);           // bit pattern of max |L^-1| (whitened tier; word cleared by svgp_init_kernel)
-    if (whiten) {
+
+    // caller's stream: Kuu -> L -> L^-1 (the critical path up to the T GEMM); |Kuu|_1 on the second side stream
+    int kuu_chain() {
+        // condition number of Kuu + jitter I (1-norm), for the float32 validity check of mxf_svgp_last_cond: |Kuu|_1 here, |Ki|_1 in value_scalars.
+        // What the T product does not need leaves the caller's stream -- the two condition norms (64 workgroups walking 16 rows each: 0.05 ms
+        // alone, 0.22 ms in front of the factorisation while the planes pass holds every CU), mu.w, tr(Ki Su), log|Kuu| go to the second side
+        // stream.  Kuu is copied for its norm (the factorisation works in place) into Su^-1's buffer, which the end of the Su chain writes on the
+        // same stream as the norm.
+        copy_convert(MM, (const D*)Lm, Sui, st);
+        MXF_HIP(h, hipEventRecord(h->ev_k1, st));
+        MXF_HIP(h, hipStreamWaitEvent(s2_, h->ev_k1, 0));
+        hipLaunchKernelGGL(norm1_sym16_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, s2_, M, (const double*)Sui, M, h->cond_dev);
+        int rc = mxf_potrf_internal(h, MXF_F64, 1, M, Lm, M, MM, info, st, false, false);                     // L :83 (trtri / sumlogdiag read the lower triangle only)
+        if (rc) return rc;
+        MXF_STAGE(h, "potrf Kuu", st);
+        rc = mxf_trtri_internal(h, MXF_F64, 1, M, Lm, M, MM, Linv, M, MM, st);
+        if (rc) return rc;
+        MXF_STAGE(h, "trtri Kuu", st);
+        return 0;
+    }
+
+    // whitened tier: the planes of L^-1 and a = L^-1 mu on the caller's stream; V = L^-1 Kuf, U = a^T V and Phi = V V^T on the side stream
+    int whiten_v_phi() {
+        static const int psi2_rb = MXF_KNOB("MXF_SVGP_PSI2_RB", 16);
+        if (!whiten) return 0;
+        unsigned* limax = (unsigned*)(info2 + 4);           // bit pattern of max |L^-1| (word cleared by svgp_init_kernel)
         // L^-1 as f16x2 planes (the A operand of V = L^-1 Kuf); Aext is free until Hh is formed
         hipLaunchKernelGGL((convert_kernel<D, T>), dim3(gridn(MM)), dim3(256), 0, st, M, M, (const D*)Linv, M, Aext, M);
-        rc = mxf_maxabs_internal(h, M, M, (const float*)Aext, M, limax, st, false);
+        int rc = mxf_maxabs_internal(h, M, M, (const float*)Aext, M, limax, st, false);
         if (rc) return rc;
         rc = mxf_split_planes_internal(h, M, M, (const float*)Aext, M, plLi, st, MXF_SPLIT_F16X2, limax);
         if (rc) return rc;
         // a = L^-1 mu (float64, then the streaming dtype): the V product's epilogue forms U = a^T V from it
         MXF_HIP(h, hipStreamWaitEvent(st, h->ev_su, 0));                                              // mu (second side stream)
         hipLaunchKernelGGL((trmv_lower_kernel<D>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, M, P, (const D*)Linv, M, (const D*)mud, (int64_t)P, ad);
-        hipLaunchKernelGGL((convert_kernel<D, T>), dim3(gridn(MP)), dim3(256), 0, st, (int64_t)1, MP, (const D*)ad, MP, aT, MP);
+        copy_convert(MP, (const D*)ad, aT, st);
         MXF_HIP(h, hipEventRecord(h->ev_aux2, st));                                                   // L^-1 planes and a ready
         // side stream: V = L^-1 Kuf, written as the planes of the (m, k = n) operand holding V / sigma * 2^14 (|v_n|^2 <= k_nn = sigma^2):
         // acc = (s_L L^-1) (Kfu / sigma^2 2^14)^T  ->  acc sigma / s_L.  L^-1 is lower triangular: a row tile's k loop stops at its last row.
-        // The SAME launch writes the planes of V^T (the (n, k = m) operand of T = Hh V) and, for one output column, the 128-row partial sums
-        // of U = a^T V (r04 late: a separate transposition + U pass over the planes took 3.3 ms of the 35 ms step -- 17 GB of traffic).
+        // Without bt_wh the SAME launch writes the planes of V^T (the (n, k = m) operand of T = Hh V) and, for one output column, the 128-row
+        // partial sums of U = a^T V (a separate transposition + U pass over the planes took 3.3 ms of the 35 ms step -- 17 GB of traffic).
         MXF_HIP(h, hipStreamWaitEvent(sd_, h->ev_aux2, 0));
         MXF_T0(h, MXF_T_VGEMM, sd_);
         // (few samples per GPU: the Kuu chain on the caller's stream is the critical path -- both side-stream products leave it 40 CUs)
         const bool few = SB <= 2 * 192 * M;
-        if (bt_wh)      // planes of V only: T and U come from them (gemm_bt.hip)
-            rc = mxf_gemm_split_internal(h, M, SB, M, 1.0, plLi, (int64_t)pl_h0, plKfu, (int64_t)pl_big, 0.0, nullptr, SB, 0, sd_, few ? 40 : 0, split_mode, sigf, 1,
-                                         (const unsigned*)limax, nullptr, 0, nullptr, plKuf, (int64_t)pl_big, 1);
-        else
+        const bool vt = !bt_wh, u1 = vt && P == 1;      // (bt_wh: planes of V only -- T and U come from them, gemm_bt.hip)
         rc = mxf_gemm_split_internal(h, M, SB, M, 1.0, plLi, (int64_t)pl_h0, plKfu, (int64_t)pl_big, 0.0, nullptr, SB, 0, sd_, few ? 40 : 0, split_mode, sigf, 1,
-                                     (const unsigned*)limax, nullptr, 0, nullptr, plKuf, (int64_t)pl_big, 1, plVt, pVt, P == 1 ? (const float*)aT : nullptr,
-                                     P == 1 ? upart : nullptr);
+                                     (const unsigned*)limax, nullptr, 0, nullptr, plKuf, (int64_t)pl_big, 1, vt ? plVt : nullptr, vt ? pVt : 0,
+                                     u1 ? (const float*)aT : nullptr, u1 ? upart : nullptr);
         if (rc) return rc;
         MXF_T1(h, MXF_T_VGEMM, sd_);
         MXF_STAGE(h, "V = Linv Kuf (sd)", sd_);
         MXF_T0(h, MXF_T_PLANES_B, sd_);
-        if (bt_wh) rc = 0;
-        else if (P == 1) rc = mxf_upart_reduce_internal(h, SB, (int)(M / 128), upart, sigf, 1.f / 16384.f, (float*)(Text + M * SB), sd_);
-        else hipLaunchKernelGGL((wt_planes_kernel<8, 2>), dim3((unsigned)((SB + 255) / 256)), dim3(256), 0, sd_, M, SB, P, (const unsigned short*)plVt,
-                                pVt, (const float*)aT, (float*)(Text + M * SB), (const float*)sigf);
-        if (rc) return rc;
+        if (!bt_wh) {           // U = a^T V: the V product's partial sums reduced (P = 1), or one pass over the V^T planes
+            if (P == 1) {
+                rc = mxf_upart_reduce_internal(h, SB, (int)(M / 128), upart, sigf, 1.f / 16384.f, (float*)(Text + M * SB), sd_);
+                if (rc) return rc;
+            } else {
+                hipLaunchKernelGGL((wt_planes_kernel<8, 2>), dim3((unsigned)((SB + 255) / 256)), dim3(256), 0, sd_, M, SB, P, (const unsigned short*)plVt,
+                                   pVt, (const float*)aT, (float*)(Text + M * SB), (const float*)sigf);
+            }
+        }
         MXF_T1(h, MXF_T_PLANES_B, sd_);
         MXF_HIP(h, hipEventRecord(h->ev_aux, sd_));      // V^T planes and U ready: the T GEMM / the reverse pass wait for it
         // Phi = V V^T (lower tiles, split-K) = sigma^2 2^-28 (planes)(planes)^T
@@ -1252,381 +1322,389 @@ int svgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t B, int64_t
         rc = mxf_gemm_split_internal(h, M, M, SB, (double)split_ga * split_ga, plKuf, (int64_t)pl_big, plKuf, (int64_t)pl_big, 0.0, (float*)Psi2, M, 1, sd_,
                                      few ? 202 : psi2_rb, split_mode, split_var, 1, nullptr);
         if (rc) return rc;
-        hipLaunchKernelGGL((symmetrize_kernel<T>), dim3((unsigned)((M + 31) / 32), (unsigned)((M + 31) / 32), 1), dim3(256), 0, sd_, Psi2, M, M, MM);
+        symmetrize(Psi2, sd_);
         MXF_T1(h, MXF_T_PSI2, sd_);
         MXF_STAGE(h, "Phi (sd)", sd_);
+        return 0;
     }
-    // r06, float32 mode: the symmetric products of the core -- Ki here, H0 and X = Ki G Ki below -- as lower tiles + mirror (half the work of a
-    // product that runs on the 88 CUs Psi2 leaves in the few-sample regime; the results become exactly symmetric), and the core's reverse mode in
-    // the X form.  dKuu then comes out exactly symmetric, and its Gram reverse pass skips the row side (dk_symmetric): one condition for both.
-    // (The float64 path is the parity path and stays operation for operation what the trajectory tests were recorded with --
-    //  tests/test_svgp_notebook.py's 100-epoch float64 run moved its learned noise by 12 % with exactly symmetric Ki / H0, past its 10 % band.)
-    constexpr bool sym_core = sizeof(T) == 4;
-    const int symlow = sym_core ? 1 : 0;
-    rc = mxf_gemm_internal(h, MXF_F64, 1, 0, M, M, M, 1.0, Linv, M, 0, Linv, M, 0, 0.0, Ki, M, 0, 1, symlow, st);   // Ki = Linv^T Linv
-    if (rc) return rc;
-    if (symlow) hipLaunchKernelGGL((symmetrize_kernel<D>), dim3((unsigned)((M + 31) / 32), (unsigned)((M + 31) / 32), 1), dim3(256), 0, st, Ki, M, M, MM);
-    MXF_HIP(h, hipStreamWaitEvent(st, h->ev_su, 0));                                                  // Su, mu, noise, accumulators (second side stream)
-    hipLaunchKernelGGL((gemv_rows_kernel<D>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, M, P, (const D*)Ki, M, (const D*)mud, (int64_t)P, wd);   // w = Ki mu
-    hipLaunchKernelGGL((convert_kernel<D, T>), dim3(gridn(MP)), dim3(256), 0, st, (int64_t)1, MP, (const D*)wd, MP, wT, MP);      // w in the streaming dtype
-    MXF_STAGE(h, "Ki, w", st);
-    if (use_split && !whiten) MXF_HIP(h, hipEventRecord(h->ev_aux2, st));                             // w ready: the Kfu planes + U pass may start
-    // ---- second side stream: Su -> Ls -> Su^-1 ----------------------------------------------------------------------------------
-    // (a plain kernel, not hipMemcpyAsync: the runtime's copy path sat idle for ~1 ms before it started next to busy queues -- r02 timeline:
-    //  the Su chain did not begin until 1.66 ms although nothing in the Kuu chain feeds it)
-    hipLaunchKernelGGL((convert_kernel<D, D>), dim3(gridn(MM)), dim3(256), 0, s2_, (int64_t)1, MM, (const D*)Su, MM, tmp, MM);
-    rc = mxf_potrf_internal(h, MXF_F64, 1, M, tmp, M, MM, info2, s2_, false, false);                  // Ls = chol(Su) :84
-    if (rc) return rc;
-    MXF_STAGE(h, "potrf Su (s2)", s2_);
-    rc = mxf_sumlogdiag_internal(h, MXF_F64, 1, M, tmp, M, MM, sc + 1, s2_);
-    if (rc) return rc;
-    if (want_grad) {
-        rc = mxf_trtri_internal(h, MXF_F64, 1, M, tmp, M, MM, Lsinv, M, MM, s2_);
-        if (rc) return rc;
-        rc = mxf_gemm_internal(h, MXF_F64, 1, 0, M, M, M, 1.0, Lsinv, M, 0, Lsinv, M, 0, 0.0, Sui, M, 0, 1, 0, s2_);
-        if (rc) return rc;
-    }
-    MXF_STAGE(h, "Su^-1 (s2)", s2_);
-    MXF_HIP(h, hipEventRecord(h->ev_join, s2_));
-    if (use_split && !whiten && !bt_path) {
-        // Kfu planes (operand (n, k = m) of the T GEMM) + the row U = w^T Kuf in ONE pass, behind the Su chain on the second side stream:
-        // HBM-write bound.  (r03, tests/probes/svgp_stages.py: the pass starts when w = Kuu^-1 mu exists, and the Kuu chain -- potrf, trtri,
-        // Ki -- shares the chip with the Kuf planes pass and Psi2 and finishes just after Psi2: 0.9 / 1.4 / 1.6 ms at 4 samples against 0.6
-        // alone.  A stream of its own for this pass changes nothing: H0, hence the T GEMM, waits for the same chain.)
-        MXF_HIP(h, hipStreamWaitEvent(s2_, h->ev_aux2, 0));
-        MXF_T0(h, MXF_T_PLANES_B, s2_);
-        rc = mxf_gram_planes_internal(h, kind, SB, M, Q, (const float*)X, (const float*)Z, (const float*)ls, ard, (const float*)var, plKfu,
-                                      (int64_t)pl_big, gscr1, s2_, split_mode, (const float*)wT, P, (float*)(Text + M * SB), SB, nullptr,
-                                      het_stream ? (const float*)hrs : nullptr, B);
-        if (rc) return rc;
-        MXF_T1(h, MXF_T_PLANES_B, s2_);
-        MXF_STAGE(h, "Kfu planes + U (s2)", s2_);
-        MXF_HIP(h, hipEventRecord(h->ev_aux, s2_));      // Kfu planes and U ready: the T GEMM / the reverse pass wait for it
-    }
-    MXF_HIP(h, hipStreamWaitEvent(st, h->ev_su, 0));                                                  // Su formed (second side stream)
-    rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 1.0, Ki, M, 0, Su, M, 0, 0.0, KiSu, M, 0, 1, 0, st);
-    if (rc) return rc;
-    if (whiten) {
-        // Hh = L^-T (I - A_s A_s^T) = L^-T - Ki Su L^-T   (T = Hh V; |Hh| ~ sqrt(cond) where |H0| ~ cond)
-        hipLaunchKernelGGL((transpose_convert_kernel<D, D>), dim3(gridn(MM)), dim3(256), 0, st, M, M, (const D*)Linv, M, H0, M);
-        rc = mxf_gemm_internal(h, MXF_F64, 0, 1, M, M, M, -1.0, KiSu, M, 0, Linv, M, 0, 1.0, H0, M, 0, 1, 0, st);
-        if (rc) return rc;
-    } else {
-    hipLaunchKernelGGL((convert_kernel<D, D>), dim3(gridn(MM)), dim3(256), 0, st, (int64_t)1, MM, (const D*)Ki, MM, H0, MM);     // H0 <- Ki (a plain kernel: the runtime's copy engine path costs ~10x as much next to busy queues)
-    rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, -1.0, KiSu, M, 0, Ki, M, 0, 1.0, H0, M, 0, 1, symlow, st);     // H0 = Ki - Ki Su Ki
-    if (rc) return rc;
-    if (symlow) hipLaunchKernelGGL((symmetrize_kernel<D>), dim3((unsigned)((M + 31) / 32), (unsigned)((M + 31) / 32), 1), dim3(256), 0, st, H0, M, M, MM);
-    }
-    // A_ext = [H0 ; w^T] in the streaming dtype
-    // (the w^T row that used to follow H0 in A_ext was read by nothing since U = w^T Kuf left the product: its launch is gone)
-    const bool fused_h0max = use_split && sizeof(T) == 4;
-    if (fused_h0max) hipLaunchKernelGGL(convert_max_kernel, dim3((unsigned)(gridn(MM) > 256 ? 256 : gridn(MM))), dim3(256), 0, st, MM, (const D*)H0, (float*)Aext, (unsigned*)(info2 + 2));
-    else
-    hipLaunchKernelGGL((convert_kernel<D, T>), dim3(gridn(MM)), dim3(256), 0, st, M, M, (const D*)H0, M, Aext, M);
 
-    // ---- streaming part -----------------------------------------------------------------------------------
-    // [T; U] = [H0; w^T] Kuf_all
-    // (training step on the split path whose reverse pass runs on the matrix pipe: T is written in 16-column blocks, so that each 16 x 16
-    //  tile that pass reads is one contiguous KB instead of 16 pieces of 64 bytes, 4 SB bytes apart)
-    const int t_blocked = (use_split && want_grad && !het && SB % 16 == 0 && mxf_svgp_bwd_reads_blocked(kind, dtype, SB, B, Q, P, Text)) ? 1 : 0;
-    if (use_split) {
-        unsigned* h0max = (unsigned*)(info2 + 2);       // bit pattern of max |H0|: the power-of-two scale of its f16x2 planes
-        if (!fused_h0max) { rc = mxf_maxabs_internal(h, M, M, (const float*)Aext, M, h0max, st, false); if (rc) return rc; }      // (word cleared by svgp_init_kernel)
-        rc = mxf_split_planes_internal(h, M, M, (const float*)Aext, M, plH0, st, split_mode, h0max);
+    // caller's stream: Ki = L^-T L^-1, w = Ki mu (one wave per row) and its streaming-dtype copy
+    int ki_w() {
+        const int rc = mm(1, 0, 1.0, Linv, Linv, 0.0, Ki, st, sym_core);   // Ki = Linv^T Linv
         if (rc) return rc;
+        if (sym_core) symmetrize(Ki, st);
+        MXF_HIP(h, hipStreamWaitEvent(st, h->ev_su, 0));                                                  // Su, mu, noise, accumulators (second side stream)
+        hipLaunchKernelGGL((gemv_rows_kernel<D>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, M, P, (const D*)Ki, M, (const D*)mud, (int64_t)P, wd);   // w = Ki mu
+        copy_convert(MP, (const D*)wd, wT, st);                                                          // w in the streaming dtype
+        MXF_STAGE(h, "Ki, w", st);
+        if (use_split && !whiten) MXF_HIP(h, hipEventRecord(h->ev_aux2, st));                             // w ready: the Kfu planes + U pass may start
+        return 0;
     }
-    MXF_T1(h, MXF_T_CHAIN, st);
-    MXF_STAGE(h, "H0 planes", st);
-    MXF_HIP(h, hipEventRecord(h->ev_fork, st));                                                       // core (Ki, KiSu, H0, w) ready
-    // |Ki|_1, mu.w, tr(Ki Su), log|Kuu| behind the Su chain on the second side stream; the caller's stream picks them up behind the T product
-    MXF_HIP(h, hipStreamWaitEvent(s2_, h->ev_fork, 0));
-    hipLaunchKernelGGL(norm1_sym16_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, s2_, M, (const double*)Ki, M, h->cond_dev + 1);
-    hipLaunchKernelGGL((dot_kernel<D>), dim3(dotgrid(MP)), dim3(256), 0, s2_, MP, (const D*)mud, (const D*)wd, 1.0, sc + 3);
-    hipLaunchKernelGGL((dot_kernel<D>), dim3(dotgrid(MM)), dim3(256), 0, s2_, MM, (const D*)Ki, (const D*)Su, 1.0, sc + 2);
-    rc = mxf_sumlogdiag_internal(h, MXF_F64, 1, M, Lm, M, MM, sc + 0, s2_);
-    if (rc) return rc;
-    MXF_HIP(h, hipEventRecord(h->ev_k3, s2_));
-    MXF_HIP(h, hipStreamWaitEvent(st, h->ev_aux, 0));                                                 // Kuf_all from the side stream
-    // (in-step timing only: the T product is held until Psi2 has finished, so that `t_gemm` is the product's own duration -- untimed, its
-    //  first workgroups take the CUs Psi2's last work items free, and the event pair would count that queueing)
-    if (h->tm.on && bt_path && want_grad && !het) MXF_HIP(h, hipStreamWaitEvent(st, h->ev_join2, 0));
-    MXF_T0(h, MXF_T_TGEMM, st);
-    if (bt_wh)       // T = Hh V from the planes of V (scaled from max |Hh|; V / sigma 2^14), U = a^T V from the same fragments
-        rc = mxf_gemm_bt_internal(h, M, SB, M, (double)split_ga, plH0, (int64_t)pl_h0, plKuf, (int64_t)pl_big, M, (float*)Text, SB, t_blocked, st, 0,
-                                  sigf, (const unsigned*)(info2 + 2), (unsigned*)(info2 + 3), (const float*)aT, (float*)(Text + M * SB),
-                                  1.0 / 16384.0, wpl);
-    else if (whiten)      // T = Hh V: planes of Hh (scaled from max |Hh|) x planes of V^T (V / sigma 2^14)
-        rc = mxf_gemm_split_internal(h, M, SB, M, (double)split_ga, plH0, (int64_t)pl_h0, plVt, pVt, 0.0, (float*)Text, SB, 0, st, 0, split_mode,
-                                     sigf, 1, (const unsigned*)(info2 + 2), nullptr, t_blocked, (unsigned*)(info2 + 3));
-    else if (bt_path)     // T = H0 Kuf straight from the Kuf planes, U = w^T Kuf from the same fragments (gemm_bt.hip)
-        rc = mxf_gemm_bt_internal(h, M, SB, M, (double)split_ga, plH0, (int64_t)pl_h0, plKuf, (int64_t)pl_big, M, (float*)Text, SB, t_blocked, st, 0,
-                                  split_var, (const unsigned*)(info2 + 2), (unsigned*)(info2 + 3), (const float*)wT, (float*)(Text + M * SB),
-                                  1.0 / 16384.0, wpl);
-    else if (use_split)   // T = H0 Kuf = H0 Kfu^T on the 16-bit matrix pipe (f32-equivalent splitting, gemm_split.hip)
-        rc = mxf_gemm_split_internal(h, M, SB, M, (double)split_ga, plH0, (int64_t)pl_h0, plKfu, (int64_t)pl_big, 0.0, (float*)Text, SB, 0, st, 0, split_mode,
-                                     split_var, 1, (const unsigned*)(info2 + 2), nullptr, t_blocked,
-                                     (unsigned*)(info2 + 3));       // max |T| for the reverse pass (word cleared by svgp_init_kernel)
-    else if (het_split) {
-        rc = mxf_maxabs_internal(h, M, M, (const float*)Aext, M, hsw + 0, st);
-        if (!rc) rc = mxf_split_planes_internal(h, M, M, (const float*)Aext, M, hsA, st, MXF_SPLIT_F16X2, hsw + 0);
-        if (!rc) rc = mxf_maxabs_internal(h, M, SB, (const float*)Kuf, SB, hsw + 1, st);
-        if (!rc) rc = mxf_split_planes_internal(h, M, SB, (const float*)Kuf, SB, hsK, st, MXF_SPLIT_F16X2, hsw + 1);      // (m, k = n): the K-major operand of T, the row operand of G'
-        if (!rc) rc = mxf_gemm_bt_internal(h, M, SB, M, 1.0, hsA, (int64_t)pl_h0, hsK, (int64_t)pl_big, M, (float*)Text, SB, 0, st, 0, nullptr, hsw + 0, nullptr,
-                                           nullptr, nullptr, 1.0, nullptr, hsw + 1);
-    } else
-        rc = mxf_gemm_internal(h, dtype, 0, 0, M, SB, M, 1.0, Aext, M, 0, Kuf, SB, 0, 0.0, Text, SB, 0, 1, 0, st);   // T = H0 Kuf (MFMA)
-    if (rc) return rc;
-    MXF_T1(h, MXF_T_TGEMM, st);
-    MXF_STAGE(h, "T", st);
-    if (use_split) {
-        // (U = w^T Kuf was written by the Kfu planes pass)
-    } else {
+
+    // second side stream: Su -> Ls -> log|Su|, Su^-1; then (split path without bt_path) the Kfu planes and U = w^T Kuf
+    int su_chain() {
+        // (a plain kernel, not hipMemcpyAsync: the runtime's copy path sat idle for ~1 ms before it started next to busy queues -- r02 timeline:
+        //  the Su chain did not begin until 1.66 ms although nothing in the Kuu chain feeds it)
+        copy_convert(MM, (const D*)Su, tmp, s2_);
+        int rc = mxf_potrf_internal(h, MXF_F64, 1, M, tmp, M, MM, info2, s2_, false, false);                  // Ls = chol(Su) :84
+        if (rc) return rc;
+        MXF_STAGE(h, "potrf Su (s2)", s2_);
+        rc = mxf_sumlogdiag_internal(h, MXF_F64, 1, M, tmp, M, MM, sc + 1, s2_);
+        if (rc) return rc;
+        if (want_grad) {
+            rc = mxf_trtri_internal(h, MXF_F64, 1, M, tmp, M, MM, Lsinv, M, MM, s2_);
+            if (rc) return rc;
+            rc = mm(1, 0, 1.0, Lsinv, Lsinv, 0.0, Sui, s2_);
+            if (rc) return rc;
+        }
+        MXF_STAGE(h, "Su^-1 (s2)", s2_);
+        MXF_HIP(h, hipEventRecord(h->ev_join, s2_));
+        if (use_split && !whiten && !bt_path) {
+            // Kfu planes (operand (n, k = m) of the T GEMM) + the row U = w^T Kuf in ONE pass, behind the Su chain on the second side stream:
+            // HBM-write bound.  (r03, tests/probes/svgp_stages.py: the pass starts when w = Kuu^-1 mu exists, and the Kuu chain -- potrf, trtri,
+            // Ki -- shares the chip with the Kuf planes pass and Psi2 and finishes just after Psi2: 0.9 / 1.4 / 1.6 ms at 4 samples against 0.6
+            // alone.  A stream of its own for this pass changes nothing: H0, hence the T GEMM, waits for the same chain.)
+            MXF_HIP(h, hipStreamWaitEvent(s2_, h->ev_aux2, 0));
+            MXF_T0(h, MXF_T_PLANES_B, s2_);
+            rc = mxf_gram_planes_internal(h, kind, SB, M, Q, (const float*)X, (const float*)Z, (const float*)ls, ard, (const float*)var, plKfu,
+                                          (int64_t)pl_big, gscr1, s2_, split_mode, (const float*)wT, P, (float*)(Text + M * SB), SB, nullptr,
+                                          het_stream ? (const float*)hrs : nullptr, B);
+            if (rc) return rc;
+            MXF_T1(h, MXF_T_PLANES_B, s2_);
+            MXF_STAGE(h, "Kfu planes + U (s2)", s2_);
+            MXF_HIP(h, hipEventRecord(h->ev_aux, s2_));      // Kfu planes and U ready: the T GEMM / the reverse pass wait for it
+        }
+        return 0;
+    }
+
+    // caller's stream: Ki Su, H0 = Ki - Ki Su Ki (whitened: Hh = L^-T - Ki Su L^-T), A_ext = H0 in the streaming dtype (split path: its planes)
+    int h0_planes() {
+        MXF_HIP(h, hipStreamWaitEvent(st, h->ev_su, 0));                                                  // Su formed (second side stream)
+        int rc = mm(0, 0, 1.0, Ki, Su, 0.0, KiSu, st);
+        if (rc) return rc;
+        if (whiten) {
+            // Hh = L^-T (I - A_s A_s^T) = L^-T - Ki Su L^-T   (T = Hh V; |Hh| ~ sqrt(cond) where |H0| ~ cond)
+            hipLaunchKernelGGL((transpose_convert_kernel<D, D>), dim3(gridn(MM)), dim3(256), 0, st, M, M, (const D*)Linv, M, H0, M);
+            rc = mm(0, 1, -1.0, KiSu, Linv, 1.0, H0, st);
+            if (rc) return rc;
+        } else {
+            copy_convert(MM, (const D*)Ki, H0, st);     // H0 <- Ki (a plain kernel: the runtime's copy engine path costs ~10x as much next to busy queues)
+            rc = mm(0, 0, -1.0, KiSu, Ki, 1.0, H0, st, sym_core);     // H0 = Ki - Ki Su Ki
+            if (rc) return rc;
+            if (sym_core) symmetrize(H0, st);
+        }
+        if (use_split) {
+            // H0 -> float32 and the bit pattern of max |H0| (the power-of-two scale of its f16x2 planes; word cleared by svgp_init_kernel) in one launch
+            unsigned* h0max = (unsigned*)(info2 + 2);
+            hipLaunchKernelGGL(convert_max_kernel, dim3((unsigned)(gridn(MM) > 256 ? 256 : gridn(MM))), dim3(256), 0, st, MM, (const D*)H0, (float*)Aext, h0max);
+            rc = mxf_split_planes_internal(h, M, M, (const float*)Aext, M, plH0, st, split_mode, h0max);
+            if (rc) return rc;
+        } else {
+            hipLaunchKernelGGL((convert_kernel<D, T>), dim3(gridn(MM)), dim3(256), 0, st, M, M, (const D*)H0, M, Aext, M);
+        }
+        MXF_T1(h, MXF_T_CHAIN, st);
+        MXF_STAGE(h, "H0 planes", st);
+        MXF_HIP(h, hipEventRecord(h->ev_fork, st));                                                       // core (Ki, KiSu, H0, w) ready
+        return 0;
+    }
+
+    // second side stream, behind the Su chain: |Ki|_1, mu.w, tr(Ki Su), log|Kuu|; the caller's stream picks them up behind the T product
+    int value_scalars() {
+        MXF_HIP(h, hipStreamWaitEvent(s2_, h->ev_fork, 0));
+        hipLaunchKernelGGL(norm1_sym16_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, s2_, M, (const double*)Ki, M, h->cond_dev + 1);
+        hipLaunchKernelGGL((dot_kernel<D>), dim3(dotgrid(MP)), dim3(256), 0, s2_, MP, (const D*)mud, (const D*)wd, 1.0, sc + 3);
+        hipLaunchKernelGGL((dot_kernel<D>), dim3(dotgrid(MM)), dim3(256), 0, s2_, MM, (const D*)Ki, (const D*)Su, 1.0, sc + 2);
+        const int rc = mxf_sumlogdiag_internal(h, MXF_F64, 1, M, Lm, M, MM, sc + 0, s2_);
+        if (rc) return rc;
+        MXF_HIP(h, hipEventRecord(h->ev_k3, s2_));
+        return 0;
+    }
+
+    // caller's stream: [T; U] = [H0; w^T] Kuf_all
+    int t_product() {
+        MXF_HIP(h, hipStreamWaitEvent(st, h->ev_aux, 0));                                                 // Kuf_all from the side stream
+        // (in-step timing only: the T product is held until Psi2 has finished, so that `t_gemm` is the product's own duration -- untimed, its
+        //  first workgroups take the CUs Psi2's last work items free, and the event pair would count that queueing)
+        if (h->tm.on && bt_path) MXF_HIP(h, hipStreamWaitEvent(st, h->ev_join2, 0));
+        MXF_T0(h, MXF_T_TGEMM, st);
+        int rc;
+        // split path: planes of H0 (scaled from max |H0|) x planes of Kuf (k / variance 2^14).  The whitened tier is the same product with Hh for
+        // H0, V for Kuf (V / sigma 2^14), a for w.  Both write max |T| for the reverse pass (word cleared by svgp_init_kernel).
+        const float* ksc = whiten ? sigf : split_var;
+        if (bt_path || bt_wh)     // T = H0 Kuf straight from the planes Psi2 reads, U = w^T Kuf from the same fragments (gemm_bt.hip)
+            rc = mxf_gemm_bt_internal(h, M, SB, M, (double)split_ga, plH0, (int64_t)pl_h0, plKuf, (int64_t)pl_big, M, (float*)Text, SB, t_blocked, st, 0,
+                                      ksc, (const unsigned*)(info2 + 2), (unsigned*)(info2 + 3), whiten ? (const float*)aT : (const float*)wT,
+                                      (float*)(Text + M * SB), 1.0 / 16384.0, wpl);
+        else if (use_split)       // T = H0 Kuf = H0 Kfu^T on the 16-bit matrix pipe (f32-equivalent splitting, gemm_split.hip)
+            rc = mxf_gemm_split_internal(h, M, SB, M, (double)split_ga, plH0, (int64_t)pl_h0, whiten ? plVt : plKfu, whiten ? pVt : (int64_t)pl_big, 0.0,
+                                         (float*)Text, SB, 0, st, 0, split_mode, ksc, 1, (const unsigned*)(info2 + 2), nullptr, t_blocked, (unsigned*)(info2 + 3));
+        else if (het_split) {
+            rc = mxf_maxabs_internal(h, M, M, (const float*)Aext, M, hsw + 0, st);
+            if (!rc) rc = mxf_split_planes_internal(h, M, M, (const float*)Aext, M, hsA, st, MXF_SPLIT_F16X2, hsw + 0);
+            if (!rc) rc = mxf_maxabs_internal(h, M, SB, (const float*)Kuf, SB, hsw + 1, st);
+            if (!rc) rc = mxf_split_planes_internal(h, M, SB, (const float*)Kuf, SB, hsK, st, MXF_SPLIT_F16X2, hsw + 1);      // (m, k = n): the K-major operand of T, the row operand of G'
+            if (!rc) rc = mxf_gemm_bt_internal(h, M, SB, M, 1.0, hsA, (int64_t)pl_h0, hsK, (int64_t)pl_big, M, (float*)Text, SB, 0, st, 0, nullptr, hsw + 0, nullptr,
+                                               nullptr, nullptr, 1.0, nullptr, hsw + 1);
+        } else
+            rc = mxf_gemm_internal(h, dtype, 0, 0, M, SB, M, 1.0, Aext, M, 0, Kuf, SB, 0, 0.0, Text, SB, 0, 1, 0, st);   // T = H0 Kuf (MFMA)
+        if (rc) return rc;
+        MXF_T1(h, MXF_T_TGEMM, st);
+        MXF_STAGE(h, "T", st);
+        if (use_split) return 0;          // (U = w^T Kuf was written with the Kfu planes or by the T product)
         constexpr int VEC = Vec16<T>::n;
         dim3 gu((unsigned)((SB + 256 * VEC - 1) / (256 * VEC)));
-#ifndef MXF_NO_WTSPLIT
         if (gu.x <= 256 && M >= 64) {            // few columns: split the rows as well (the kernel then adds into U)
-            // (r06: up to one workgroup per CU -- 512 x 131 072, the deep GP's first layer, was 128 workgroups walking 512 dependent rows: 0.24 ms)
+            // (up to one workgroup per CU -- 512 x 131 072, the deep GP's first layer, was 128 workgroups walking 512 dependent rows: 0.24 ms)
             int64_t ch = 1024 / gu.x; if (ch > M / 16) ch = M / 16; if (ch > 64) ch = 64;
             if (ch > 1) { gu.y = (unsigned)ch; MXF_HIP(h, hipMemsetAsync(Text + M * SB, 0, sizeof(T) * (size_t)P * SB, st)); }
         }
-#endif
         if (P == 1) hipLaunchKernelGGL((wt_kuf_kernel<T, 1>), gu, dim3(256), 0, st, M, SB, P, (const T*)Kuf, (const T*)wT, Text + M * SB);
         else hipLaunchKernelGGL((wt_kuf_kernel<T, 8>), gu, dim3(256), 0, st, M, SB, P, (const T*)Kuf, (const T*)wT, Text + M * SB);   // U = w^T Kuf
+        return 0;
     }
-    // the part of the core reverse mode that depends on Psi2 only (not on R): dSu = -Ki G Ki + bP/2 (Su^-1 - Ki), dW = 2 dSu W,
-    // dSdiag = diag(dSu), T1 = G Ki Su.  Streaming path: queued on the side stream right behind Psi2, so it runs under the T GEMM /
-    // the reverse pass instead of in the step's tail.
-    // (r06) float32 mode: the whole R-independent part of the core's reverse mode -- dKuu0 included -- on the side stream, from X = Ki G Ki (below).
-    // float64 mode keeps the r05 flow: forming A_Ki = G - G Ki Su - ... FIRST and multiplying by Ki afterwards cancels before it amplifies; the X form
-    // multiplies first and loses ~2 digits on ill-conditioned Kuu (uncertain-input toy of tests/test_gpu_config4.py, cond ~ 1e6: float64 lengthscale
-    // gradient 8.6e-10 -> 5.8e-8 against the oracle) -- nothing next to float32 streaming (1e-5), but the float64 path is the parity path.
-    auto su_reverse = [&](hipStream_t s_, bool with_t1) -> int {
-        int r_ = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 1.0, Ki, M, 0, G, M, 0, 0.0, tmp, M, 0, 1, 0, s_);            // T3 = Ki G
-        if (r_) return r_;
-        hipLaunchKernelGGL((axpby_kernel<D>), dim3(gridn(MM)), dim3(256), 0, s_, MM, 1.0, (const D*)Sui, -1.0, (const D*)Ki, dSu);   // Sui - Ki
-        r_ = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, -1.0, tmp, M, 0, Ki, M, 0, 0.5 * bw * P, dSu, M, 0, 1, 0, s_);
-        if (r_) return r_;
+
+    // dW = 2 dSu W (into Lsinv's buffer, free by then) and dSdiag = diag(dSu), on stream s_
+    int dsu_outputs(hipStream_t s_) {
         if (dW) {
-            r_ = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 2.0, dSu, M, 0, Wd, M, 0, 0.0, Lsinv, M, 0, 1, 0, s_);     // dW = 2 dSu W (Lsinv buffer is free)
-            if (r_) return r_;
+            const int rc = mm(0, 0, 2.0, dSu, Wd, 0.0, Lsinv, s_);
+            if (rc) return rc;
             hipLaunchKernelGGL((add_convert_kernel<D, T>), dim3(gridn(MM)), dim3(256), 0, s_, MM, (T)1, (const D*)Lsinv, dW, 0);
         }
         if (dSdiag) hipLaunchKernelGGL((diag_extract_kernel<D, T>), dim3(gridn(M)), dim3(256), 0, s_, M, (const D*)dSu, M, dSdiag);
-        if (with_t1) r_ = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 1.0, G, M, 0, KiSu, M, 0, 0.0, T1, M, 0, 1, 0, s_);           // T1 = G Ki Su
-        return r_;
-    };
-    if (want_grad && !het && sym_core) {
-        // r06: the whole R-independent part of the core's reverse mode from X = Ki G Ki (G = c Psi2, c = P a1 beta / 2):
-        //   dSu   = -X + bP/2 (Su^-1 - Ki)                                  (as before)
-        //   dKuu0 = -Ki A0 Ki - bP/2 Ki,  A0 = G - T1 - T1^T - b (P/2 Su + 1/2 mu mu^T),  T1 = G Ki Su
-        //         = -X + Y + Y^T + b (P/2 Ki Su Ki + 1/2 w w^T) - bP/2 Ki,  Y = X (Ki Su)^T,  Ki Su Ki = Ki - H0 (explicit form)
-        // i.e. FOUR M^3 products (Ki G, . Ki, dSu W, X (Ki Su)^T) where the r05 flow took six (Ki G, . Ki, dSu W, G Ki Su, Ki A, . Ki), the last two
-        // of them in the step's tail behind the reverse pass.  Whitened form: X = c L^-T Phi L^-1 directly (Phi = V V^T; G = c L Phi L^T is never
-        // formed) + Ki Su Ki as a product: five instead of eight.  These products run on the CUs the T product leaves free (few samples: 40), so
-        // their number is the length of the side stream: stage stamps at 4 samples, r05 flow: Su reverse ends 3.70 ms, reverse pass 3.54, end 3.97.
-        MXF_HIP(h, hipStreamWaitEvent(sd_, h->ev_fork, 0));      // Ki, KiSu, H0 (main)
-        MXF_HIP(h, hipStreamWaitEvent(sd_, h->ev_join, 0));      // Su^-1; `tmp` (chol(Su)) is free from here on
-        D* Xb = whiten ? G : T2;
-        if (whiten) {
-            hipLaunchKernelGGL((scale_beta_kernel<T>), dim3(gridn(MM)), dim3(256), 0, sd_, MM, (const T*)Psi2, (const D*)noised, 0.5 * P * a1, T2);   // c Phi
-            hipLaunchKernelGGL((trace_kernel<D>), dim3(1), dim3(256), 0, sd_, M, (const D*)T2, M, (int64_t)0, sc + 6);                                 // c tr(Phi)
-            rc = mxf_gemm_internal(h, MXF_F64, 1, 0, M, M, M, 1.0, Linv, M, 0, T2, M, 0, 0.0, tmp, M, 0, 1, 0, sd_);       // L^-T (c Phi)
-            if (rc) return rc;
-            rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 1.0, tmp, M, 0, Linv, M, 0, 0.0, Xb, M, 0, 1, symlow, sd_);    // X = c L^-T Phi L^-1 (symmetric: lower tiles, mirrored)
-            if (rc) return rc;
-            hipLaunchKernelGGL((symmetrize_kernel<D>), dim3((unsigned)((M + 31) / 32), (unsigned)((M + 31) / 32), 1), dim3(256), 0, sd_, Xb, M, M, MM);
-            hipLaunchKernelGGL(dot_t_kernel, dim3(dotgrid(MM)), dim3(256), 0, sd_, M, (const D*)Su, (const D*)Xb, sc + 7);   // tr(Su X): the accurate total of the q_n
-        } else {
-            hipLaunchKernelGGL((scale_beta_kernel<T>), dim3(gridn(MM)), dim3(256), 0, sd_, MM, (const T*)Psi2, (const D*)noised, 0.5 * P * a1, G);
-            rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 1.0, Ki, M, 0, G, M, 0, 0.0, tmp, M, 0, 1, 0, sd_);           // Ki G
-            if (rc) return rc;
-            rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 1.0, tmp, M, 0, Ki, M, 0, 0.0, Xb, M, 0, 1, symlow, sd_);       // X = Ki G Ki (symmetric: lower tiles, mirrored)
-            if (rc) return rc;
-            hipLaunchKernelGGL((symmetrize_kernel<D>), dim3((unsigned)((M + 31) / 32), (unsigned)((M + 31) / 32), 1), dim3(256), 0, sd_, Xb, M, M, MM);
-        }
-        hipLaunchKernelGGL(dsu_kernel, dim3(gridn(MM)), dim3(256), 0, sd_, MM, (const D*)Xb, (const D*)Sui, (const D*)Ki, 0.5 * bw * P, dSu);
-        if (dW) {
-            rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 2.0, dSu, M, 0, Wd, M, 0, 0.0, Lsinv, M, 0, 1, 0, sd_);     // dW = 2 dSu W (Lsinv buffer is free)
-            if (rc) return rc;
-            hipLaunchKernelGGL((add_convert_kernel<D, T>), dim3(gridn(MM)), dim3(256), 0, sd_, MM, (T)1, (const D*)Lsinv, dW, 0);
-        }
-        if (dSdiag) hipLaunchKernelGGL((diag_extract_kernel<D, T>), dim3(gridn(M)), dim3(256), 0, sd_, M, (const D*)dSu, M, dSdiag);
-        rc = mxf_gemm_internal(h, MXF_F64, 0, 1, M, M, M, 1.0, Xb, M, 0, KiSu, M, 0, 0.0, T1, M, 0, 1, 0, sd_);             // Y = X (Ki Su)^T
-        if (rc) return rc;
-        if (whiten) {
-            rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 1.0, KiSu, M, 0, Ki, M, 0, 0.0, AKi, M, 0, 1, 0, sd_);        // Ki Su Ki (H0 holds Hh in this form)
-            if (rc) return rc;
-        }
-        hipLaunchKernelGGL(dkuu0_kernel, dim3(gridn(MM)), dim3(256), 0, sd_, M, P, (const D*)Xb, (const D*)T1, (const D*)Ki, whiten ? (const D*)AKi : (const D*)nullptr,
-                           (const D*)H0, (const D*)wd, bw, dKuu);
-    } else if (want_grad && !het) {
-        MXF_HIP(h, hipStreamWaitEvent(sd_, h->ev_fork, 0));      // Ki, KiSu (main)
-        MXF_HIP(h, hipStreamWaitEvent(sd_, h->ev_join, 0));      // Su^-1; `tmp` (chol(Su)) is free from here on
-        if (whiten) {
-            // G = d/dH0 = P a1 beta / 2 Psi2 with Psi2 = L Phi L^T in float64: the core's reverse mode then forms Ki G Ki = c L^-T Phi L^-1 --
-            // the float32 error of Phi is amplified by |L^-1|^2 ~ cond, that of a float32 Psi2 by |Ki|^2 ~ cond^2
-            hipLaunchKernelGGL((scale_beta_kernel<T>), dim3(gridn(MM)), dim3(256), 0, sd_, MM, (const T*)Psi2, (const D*)noised, 0.5 * P * a1, T2);
-            rc = mxf_tril_copy_internal(h, M, Lm, AKi, sd_);
-            if (rc) return rc;
-            rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 1.0, AKi, M, 0, T2, M, 0, 0.0, dKuu, M, 0, 1, 0, sd_);
-            if (rc) return rc;
-            rc = mxf_gemm_internal(h, MXF_F64, 0, 1, M, M, M, 1.0, dKuu, M, 0, AKi, M, 0, 0.0, G, M, 0, 1, 0, sd_);
-            if (rc) return rc;
-        } else
-        hipLaunchKernelGGL((scale_beta_kernel<T>), dim3(gridn(MM)), dim3(256), 0, sd_, MM, (const T*)Psi2, (const D*)noised, 0.5 * P * a1, G);
-        rc = su_reverse(sd_, true);
-        if (rc) return rc;
-        if (whiten) {      // c tr(Phi) and c tr(Su L^-T Phi L^-1) = tr((Ki Su) (Ki G)): the accurate total of the q_n (svgp_finalize_kernel)
-            hipLaunchKernelGGL((trace_kernel<D>), dim3(1), dim3(256), 0, sd_, M, (const D*)T2, M, (int64_t)0, sc + 6);
-            hipLaunchKernelGGL(dot_t_kernel, dim3(dotgrid(MM)), dim3(256), 0, sd_, M, (const D*)KiSu, (const D*)tmp, sc + 7);
-        }
-    }
-    if (want_grad && !het) {
-        MXF_STAGE(h, "Su reverse (sd)", sd_);
-        MXF_HIP(h, hipEventRecord(h->ev_join2, sd_));            // Psi2, G, T1, dSu outputs (float32 mode: dKuu0 as well)
-    }
-    MXF_HIP(h, hipStreamWaitEvent(st, h->ev_join, 0));      // Su chain complete (log-det for the value, Su^-1 for the reverse mode); hidden under the T GEMM
-    MXF_HIP(h, hipStreamWaitEvent(st, h->ev_k3, 0));      // ... and the condition norms and value scalars behind it
-    const int dY_shared = (sY == 0 && SS > 1) ? 1 : 0;
-    D* dnz = nullptr; D* dvdir = nullptr;
-    if (het) {
-        if (want_grad) {
-            dvdir = sc + 5;
-            if (dY) MXF_HIP(h, hipMemsetAsync(dY, 0, sizeof(T) * (size_t)(ysamp ? (int64_t)S * B : (sY == 0 ? B : SB)) * P, st));
-            if (dZ && !use_mat) MXF_HIP(h, hipMemsetAsync(dZ, 0, sizeof(T) * M * Q, st));
-            if (dls && !use_mat) MXF_HIP(h, hipMemsetAsync(dls, 0, sizeof(T) * lsn, st));
-            if (dvar && !use_mat) MXF_HIP(h, hipMemsetAsync(dvar, 0, sizeof(T), st));
-            if (dX && !use_mat) MXF_HIP(h, hipMemsetAsync(dX, 0, sizeof(T) * (size_t)SB * Q, st));
-            if (dnoise) MXF_HIP(h, hipMemsetAsync(dnoise, 0, sizeof(T) * (size_t)nrows * ncols, st));
-        }
-        T* Ksc = Kfu;   // the transposed-Gram slot is unused on this path
-        MXF_HIP(h, hipMemsetAsync(qbuf, 0, sizeof(T) * (size_t)SB, st));
-        hipLaunchKernelGGL((svgp_het_rows_kernel<T>), dim3((unsigned)((SB + 255) / 256), (unsigned)((M + HET_RCH - 1) / HET_RCH)), dim3(256), 0, st, SB, B, M,
-                           P, SYc, (const T*)Kuf, Text, Y, sY, (const T*)wT, noise, nrows, ncols, a1, want_grad, Ksc, qbuf);
-        hipLaunchKernelGGL((svgp_het_cols_kernel<T>), dim3((unsigned)((SB + 255) / 256)), dim3(256), 0, st, SB, B, M, P, SYc, (const T*)Text, Y, sY, noise,
-                           nrows, ncols, (const D*)vard, mat.Kdiag, a1, want_grad, (const T*)qbuf, Eb, dY, dY_shared, dnoise, mat.dKdiag, scal);
-        hipLaunchKernelGGL((svgp_het_finalize_kernel<T>), dim3(1), dim3(64), 0, st, S, M, P, (const D*)scal, (const D*)(sc + 0), (const D*)(sc + 1),
-                           (const D*)(sc + 2), (const D*)(sc + 3), scaling, a1, logL, dvdir);
-        MXF_LAUNCH_CHECK(h);
-        if (!want_grad) { hipLaunchKernelGGL(cond_publish_kernel, dim3(1), dim3(1), 0, st, h->cond_dev, cond_slot); return 0; }
-        // G' = 1/2 a1 Kuf diag(bs) Kuf^T (-> Psi2 slot), Gw = Kuf (a1 beta.e) (-> R slot), Kuf-side reverse mode from dKuf = Text
-        if (het_split) {
-            rc = mxf_maxabs_internal(h, M, SB, (const float*)Ksc, SB, hsw + 2, st);
-            if (!rc) rc = mxf_split_planes_internal(h, M, SB, (const float*)Ksc, SB, hsS, st, MXF_SPLIT_F16X2, hsw + 2);
-            if (!rc) rc = mxf_gemm_split_internal(h, M, M, SB, 1.0, hsS, (int64_t)pl_big, hsK, (int64_t)pl_big, 0.0, (float*)Psi2, M, 0, st, 0, MXF_SPLIT_F16X2, nullptr, 0,
-                                                  hsw + 2, hsw + 1);
-        } else
-        rc = mxf_gemm_internal(h, dtype, 0, 1, M, M, SB, 1.0, Ksc, SB, 0, Kuf, SB, 0, 0.0, Psi2, M, 0, 1, 0, st);
-        if (rc) return rc;
-        if (SB >= 4096 && M <= 65535) { hipLaunchKernelGGL((rowdot_kernel<T>), dim3((unsigned)M), dim3(256), 0, st, SB, P, (const T*)Kuf, SB, (const T*)Eb, R); rc = 0; }
-        else
-        rc = mxf_gemm_internal(h, dtype, 0, 0, M, P, SB, 1.0, Kuf, SB, 0, Eb, P, 0, 0.0, R, P, 0, 1, 0, st);
-        if (rc) return rc;
-        if (use_mat) {
-            if (mat.dKuf) MXF_HIP(h, hipMemcpyAsync(mat.dKuf, Text, sizeof(T) * (size_t)M * SB, hipMemcpyDeviceToDevice, st));
-        } else {
-            rc = mxf_gram_bwd_internal(h, kind, dtype, 1, M, SB, Q, Z, 0, X, 0, ls, ard, 0, var, 0, Text, SB, 0, dZ, dX, dls, dvar, st);
-            if (rc) return rc;
-        }
-    } else if (!want_grad) {
-        hipLaunchKernelGGL((svgp_mid_kernel<T>), dim3((unsigned)((SB + 255) / 256)), dim3(256), 0, st, SB, B, M, P, (const T*)Kuf, Text, Y, sY,
-                           (const T*)wT, noise, a1, 0, (T*)nullptr, (T*)nullptr, 0, scal);
-    } else {
-        dnz = sc + 4; dvdir = sc + 5;
-        // (dY, dZ, dls, dvar, dX, R were cleared on the second side stream at the start of the call: early_clear)
-        // one pass over T: q_n, |e_n|^2, dY, R = Kuf E, and the Kuf-side reverse mode (dX, dZ, dls, dvar) without materialising dKuf
-        MXF_T0(h, MXF_T_BWD, st);
-        rc = mxf_svgp_bwd_fused_internal(h, kind, dtype, M, SB, B, Q, P, Z, X, ls, ard, var, Text, het_stream ? (const T*)hys : Y, sY, wT,
-                                         het_stream ? (const T*)hnz : noise, a1, dZ, dX, dls, dvar,
-                                         dY, dY_shared, R, scal, st, t_blocked,
-                                         use_split ? (const unsigned*)(info2 + 2) : nullptr,
-                                         (const unsigned*)(info2 + 3));
-        if (rc) return rc;
-    }
-    if (want_grad && !het) MXF_T1(h, MXF_T_BWD, st);
-    MXF_STAGE(h, "reverse pass", st);
-    if (het_stream) {
-        // sum_n beta_n e_n^2 per sample and the per-row noise gradient: one more pass over the Kfu planes and T''
-        if (dnoise) MXF_HIP(h, hipMemsetAsync(dnoise, 0, sizeof(T) * (size_t)B, st));
-        hipLaunchKernelGGL(het_stats_kernel, dim3((unsigned)((SB / 16 + 3) / 4)), dim3(256), 0, st, SB, B, M, (const unsigned short*)plKfu, (int64_t)pl_big,
-                           (const float*)Text, (const float*)hys, sY, (const float*)noise, (const float*)hrs, (const float*)var, a1, want_grad,
-                           (float*)dnoise, hbe2);
-        hipLaunchKernelGGL((svgp_finalize_hets_kernel<T>), dim3(1), dim3(64), 0, st, S, B, M, (const D*)scal, (const D*)hbe2, (const D*)hhs, (const D*)noised,
-                           (const D*)vard, (const D*)(sc + 0), (const D*)(sc + 1), (const D*)(sc + 2), (const D*)(sc + 3), scaling, a1, logL, dvdir);
-        MXF_LAUNCH_CHECK(h);
-    } else if (!het) {
-        if (whiten) MXF_HIP(h, hipStreamWaitEvent(st, h->ev_join2, 0));      // Phi and the core's Su part (side stream): the value needs tr(C Phi)
-        hipLaunchKernelGGL((svgp_finalize_kernel<T>), dim3(1), dim3(64), 0, st, S, B, M, P, (const D*)scal, (const D*)noised, (const D*)vard,
-                           (const D*)(sc + 0), (const D*)(sc + 1), (const D*)(sc + 2), (const D*)(sc + 3), scaling, a1, logL, dnz, dvdir,
-                           whiten ? (const D*)(sc + 6) : (const D*)nullptr);
-        MXF_LAUNCH_CHECK(h);
-        if (!want_grad) { hipLaunchKernelGGL(cond_publish_kernel, dim3(1), dim3(1), 0, st, h->cond_dev, cond_slot); return 0; }
+        return 0;
     }
 
-    if (het) {
-        hipLaunchKernelGGL((convert_kernel<T, D>), dim3(gridn(MM)), dim3(256), 0, st, (int64_t)1, MM, (const T*)Psi2, MM, G, MM);
-        hipLaunchKernelGGL((convert_kernel<T, D>), dim3(gridn(MP)), dim3(256), 0, st, (int64_t)1, MP, (const T*)R, MP, Gw, MP);
-        // ---- core reverse mode (float64): the Su part on the side stream next to the Kuu part ---------------------------------
-        MXF_HIP(h, hipEventRecord(h->ev_fork, st));
-        MXF_HIP(h, hipStreamWaitEvent(sd_, h->ev_fork, 0));
-        rc = su_reverse(sd_, false);
+    // the part of the core reverse mode that depends on Psi2 only (not on R), in the float64 flow: dSu = -Ki G Ki + bP/2 (Su^-1 - Ki),
+    // dW = 2 dSu W, dSdiag = diag(dSu), with_t1: T1 = G Ki Su.  Forming A_Ki = G - G Ki Su - ... FIRST and multiplying by Ki afterwards cancels
+    // before it amplifies; the X form (float32) multiplies first and loses ~2 digits on ill-conditioned Kuu (uncertain-input toy of
+    // tests/test_gpu_config4.py, cond ~ 1e6: float64 lengthscale gradient 8.6e-10 -> 5.8e-8 against the oracle) -- nothing next to float32
+    // streaming (1e-5), but the float64 path is the parity path.
+    int su_reverse(hipStream_t s_, bool with_t1) {
+        int rc = mm(0, 0, 1.0, Ki, G, 0.0, tmp, s_);            // T3 = Ki G
         if (rc) return rc;
-        MXF_HIP(h, hipEventRecord(h->ev_join, sd_));
-        rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 1.0, G, M, 0, KiSu, M, 0, 0.0, T1, M, 0, 1, 0, st);           // T1 = G Ki Su
+        hipLaunchKernelGGL((axpby_kernel<D>), dim3(gridn(MM)), dim3(256), 0, s_, MM, 1.0, (const D*)Sui, -1.0, (const D*)Ki, dSu);   // Sui - Ki
+        rc = mm(0, 0, -1.0, tmp, Ki, 0.5 * bw * P, dSu, s_);
         if (rc) return rc;
-    } else {
-        MXF_HIP(h, hipStreamWaitEvent(st, h->ev_join2, 0));      // side stream: Psi2 -> G, T1, dSu / dW / dSdiag (already done)
-        hipLaunchKernelGGL((scale_beta_kernel<T>), dim3(gridn(MP)), dim3(256), 0, st, MP, (const T*)R, (const D*)noised, a1, Gw);
+        rc = dsu_outputs(s_);
+        if (rc) return rc;
+        if (with_t1) rc = mm(0, 0, 1.0, G, KiSu, 0.0, T1, s_);           // T1 = G Ki Su
+        return rc;
     }
-    // main: dKuu = -Ki A_Ki Ki - bP/2 Ki; dmu = Ki Gw - b w
-    if (!(sym_core && !het)) {
-    hipLaunchKernelGGL(aki_kernel, dim3(gridn(MM)), dim3(256), 0, st, M, P, (const D*)G, (const D*)T1, (const D*)Gw, (const D*)mud, (const D*)Su, bw, AKi);
-    rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 1.0, Ki, M, 0, AKi, M, 0, 0.0, T2, M, 0, 1, 0, st);           // T2 = Ki A_Ki
-    if (rc) return rc;
-    hipLaunchKernelGGL((convert_kernel<D, D>), dim3(gridn(MM)), dim3(256), 0, st, (int64_t)1, MM, (const D*)Ki, MM, dKuu, MM);
-    rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, -1.0, T2, M, 0, Ki, M, 0, -0.5 * bw * P, dKuu, M, 0, 1, 0, st);
-    if (rc) return rc;
-    }
-    hipLaunchKernelGGL((gemv_rows_kernel<D>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, M, P, (const D*)Ki, M, (const D*)Gw, (int64_t)P, dmud, -bw, (const D*)wd);
-    if (sym_core && !het) hipLaunchKernelGGL(dkuu_rank_kernel, dim3(gridn(MM)), dim3(256), 0, st, M, P, (const D*)dmud, (const D*)wd, bw, dKuu);
-    // Kuu-side reverse mode in float64, then added to the streaming-side gradients
-    FinishArgs fa;
-    fa.cnt = 0;
-    auto fin = [&](const D* src, const D* src2, void* dst, int64_t n, int acc) {
-        fa.src[fa.cnt] = src; fa.src2[fa.cnt] = src2; fa.dst[fa.cnt] = dst; fa.n[fa.cnt] = n; fa.acc[fa.cnt] = acc; ++fa.cnt;
-    };
-    if (dmu) fin(dmud, nullptr, dmu, MP, 0);
-    if (use_mat) {
-        if (mat.dKuu) fin(dKuu, nullptr, mat.dKuu, MM, 0);
-    } else {
-        if (!early_clear) {
-            MXF_HIP(h, hipMemsetAsync(dZc, 0, sizeof(D) * M * Q, st));
-            MXF_HIP(h, hipMemsetAsync(dlsc, 0, sizeof(D) * lsn, st));
-            MXF_HIP(h, hipMemsetAsync(dvc, 0, sizeof(D) * 4, st));
+
+    // side stream, fused path: the R-independent part of the core's reverse mode, right behind Psi2 -- it runs under the T GEMM / the reverse
+    // pass instead of in the step's tail
+    int core_reverse_side() {
+        if (!fused) return 0;
+        MXF_HIP(h, hipStreamWaitEvent(sd_, h->ev_fork, 0));      // Ki, KiSu, H0 (main)
+        MXF_HIP(h, hipStreamWaitEvent(sd_, h->ev_join, 0));      // Su^-1; `tmp` (chol(Su)) is free from here on
+        int rc;
+        if (!sym_core) {
+            hipLaunchKernelGGL((scale_beta_kernel<T>), dim3(gridn(MM)), dim3(256), 0, sd_, MM, (const T*)Psi2, (const D*)noised, 0.5 * P * a1, G);
+            rc = su_reverse(sd_, true);
+            if (rc) return rc;
+        } else {
+            // float32: the whole R-independent part, dKuu0 included, from X = Ki G Ki (G = c Psi2, c = P a1 beta / 2):
+            //   dSu   = -X + bP/2 (Su^-1 - Ki)
+            //   dKuu0 = -Ki A0 Ki - bP/2 Ki,  A0 = G - T1 - T1^T - b (P/2 Su + 1/2 mu mu^T),  T1 = G Ki Su
+            //         = -X + Y + Y^T + b (P/2 Ki Su Ki + 1/2 w w^T) - bP/2 Ki,  Y = X (Ki Su)^T,  Ki Su Ki = Ki - H0 (explicit form)
+            // i.e. FOUR M^3 products (Ki G, . Ki, dSu W, X (Ki Su)^T) where the float64 flow takes six (Ki G, . Ki, dSu W, G Ki Su, Ki A, . Ki), the
+            // last two of them in the step's tail behind the reverse pass.  Whitened form: X = c L^-T Phi L^-1 directly (Phi = V V^T; G = c L Phi L^T
+            // is never formed) + Ki Su Ki as a product: five instead of eight.  These products run on the CUs the T product leaves free (few samples:
+            // 40), so their number is the length of the side stream: stage stamps at 4 samples, six-product flow: Su reverse ends 3.70 ms, reverse
+            // pass 3.54, end 3.97.
+            // X = F^T Gc F (symmetric: lower tiles, mirrored) -- G = c Psi2 and F = Ki, or whitened: c Phi and F = L^-1
+            D* Xb = whiten ? G : T2;
+            D* Gc = whiten ? T2 : G;
+            const D* F = whiten ? Linv : Ki;
+            hipLaunchKernelGGL((scale_beta_kernel<T>), dim3(gridn(MM)), dim3(256), 0, sd_, MM, (const T*)Psi2, (const D*)noised, 0.5 * P * a1, Gc);
+            if (whiten) hipLaunchKernelGGL((trace_kernel<D>), dim3(1), dim3(256), 0, sd_, M, (const D*)T2, M, (int64_t)0, sc + 6);          // c tr(Phi)
+            rc = mm(whiten ? 1 : 0, 0, 1.0, F, Gc, 0.0, tmp, sd_);
+            if (rc) return rc;
+            rc = mm(0, 0, 1.0, tmp, F, 0.0, Xb, sd_, sym_core);
+            if (rc) return rc;
+            symmetrize(Xb, sd_);
+            if (whiten) hipLaunchKernelGGL(dot_t_kernel, dim3(dotgrid(MM)), dim3(256), 0, sd_, M, (const D*)Su, (const D*)Xb, sc + 7);   // tr(Su X): the accurate total of the q_n
+            hipLaunchKernelGGL(dsu_kernel, dim3(gridn(MM)), dim3(256), 0, sd_, MM, (const D*)Xb, (const D*)Sui, (const D*)Ki, 0.5 * bw * P, dSu);
+            rc = dsu_outputs(sd_);
+            if (rc) return rc;
+            rc = mm(0, 1, 1.0, Xb, KiSu, 0.0, T1, sd_);             // Y = X (Ki Su)^T
+            if (rc) return rc;
+            if (whiten) {
+                rc = mm(0, 0, 1.0, KiSu, Ki, 0.0, AKi, sd_);        // Ki Su Ki (H0 holds Hh in this form)
+                if (rc) return rc;
+            }
+            hipLaunchKernelGGL(dkuu0_kernel, dim3(gridn(MM)), dim3(256), 0, sd_, M, P, (const D*)Xb, (const D*)T1, (const D*)Ki, whiten ? (const D*)AKi : (const D*)nullptr,
+                               (const D*)H0, (const D*)wd, bw, dKuu);
         }
-        // (float32 mode: dKuu is formed from the mirrored X, Ki and H0, i.e. symmetric -- the row side of its reverse pass is skipped (sym_core);
-        //  float64 keeps both sides)
-        rc = mxf_gram_bwd_internal(h, kind, MXF_F64, 1, M, M, Q, Zd, 0, nullptr, 0, lsd, ard, 0, vard, 0, dKuu, M, 0, dZc, nullptr, dlsc, dvc, st,
-                                   (sym_core && !het) ? 1 : 0);
-        if (rc) return rc;
-        if (dZ) fin(dZc, nullptr, dZ, M * Q, 1);
-        if (dls) fin(dlsc, nullptr, dls, lsn, 1);
-        if (dvar) fin(dvc, sc + 5, dvar, 1, 1);
+        MXF_STAGE(h, "Su reverse (sd)", sd_);
+        MXF_HIP(h, hipEventRecord(h->ev_join2, sd_));            // Psi2, G, T1, dSu outputs (float32 mode: dKuu0 as well)
+        return 0;
     }
-    if (dnoise && !het && !het_stream) fin(sc + 4, nullptr, dnoise, 1, 0);
-    if (fa.cnt) {
-        int64_t nmax = 1;
-        for (int i = 0; i < fa.cnt; ++i) nmax = fa.n[i] > nmax ? fa.n[i] : nmax;
-        hipLaunchKernelGGL((svgp_finish_kernel<T>), dim3(gridn(nmax), (unsigned)fa.cnt), dim3(256), 0, st, fa);
+
+    // caller's stream: the pass over T (value terms and the Kuf-side reverse mode) and logL.  !want_grad: the call ends here.
+    int reverse_pass() {
+        MXF_HIP(h, hipStreamWaitEvent(st, h->ev_join, 0));      // Su chain complete (log-det for the value, Su^-1 for the reverse mode); hidden under the T GEMM
+        MXF_HIP(h, hipStreamWaitEvent(st, h->ev_k3, 0));      // ... and the condition norms and value scalars behind it
+        const int dY_shared = (sY == 0 && SS > 1) ? 1 : 0;
+        D* dnz = fused ? sc + 4 : nullptr;           // dnoise, dvar_direct
+        D* dvdir = want_grad ? sc + 5 : nullptr;
+        int rc;
+        if (het) {
+            if (want_grad) {
+                if ((rc = clear_grads(st))) return rc;
+                if (dnoise) MXF_HIP(h, hipMemsetAsync(dnoise, 0, sizeof(T) * (size_t)nrows * ncols, st));
+            }
+            T* Ksc = Kfu;   // the transposed-Gram slot is unused on this path
+            MXF_HIP(h, hipMemsetAsync(qbuf, 0, sizeof(T) * (size_t)SB, st));
+            hipLaunchKernelGGL((svgp_het_rows_kernel<T>), dim3((unsigned)((SB + 255) / 256), (unsigned)((M + HET_RCH - 1) / HET_RCH)), dim3(256), 0, st, SB, B, M,
+                               P, SYc, (const T*)Kuf, Text, Y, sY, (const T*)wT, noise, nrows, ncols, a1, want_grad, Ksc, qbuf);
+            hipLaunchKernelGGL((svgp_het_cols_kernel<T>), dim3((unsigned)((SB + 255) / 256)), dim3(256), 0, st, SB, B, M, P, SYc, (const T*)Text, Y, sY, noise,
+                               nrows, ncols, (const D*)vard, mat.Kdiag, a1, want_grad, (const T*)qbuf, Eb, dY, dY_shared, dnoise, mat.dKdiag, scal);
+            hipLaunchKernelGGL((svgp_het_finalize_kernel<T>), dim3(1), dim3(64), 0, st, S, M, P, (const D*)scal, (const D*)(sc + 0), (const D*)(sc + 1),
+                               (const D*)(sc + 2), (const D*)(sc + 3), scaling, a1, logL, dvdir);
+            MXF_LAUNCH_CHECK(h);
+            if (!want_grad) { publish_cond(); return 0; }
+            // G' = 1/2 a1 Kuf diag(bs) Kuf^T (-> Psi2 slot), Gw = Kuf (a1 beta.e) (-> R slot), Kuf-side reverse mode from dKuf = Text
+            if (het_split) {
+                rc = mxf_maxabs_internal(h, M, SB, (const float*)Ksc, SB, hsw + 2, st);
+                if (!rc) rc = mxf_split_planes_internal(h, M, SB, (const float*)Ksc, SB, hsS, st, MXF_SPLIT_F16X2, hsw + 2);
+                if (!rc) rc = mxf_gemm_split_internal(h, M, M, SB, 1.0, hsS, (int64_t)pl_big, hsK, (int64_t)pl_big, 0.0, (float*)Psi2, M, 0, st, 0, MXF_SPLIT_F16X2, nullptr, 0,
+                                                      hsw + 2, hsw + 1);
+            } else
+                rc = mxf_gemm_internal(h, dtype, 0, 1, M, M, SB, 1.0, Ksc, SB, 0, Kuf, SB, 0, 0.0, Psi2, M, 0, 1, 0, st);
+            if (rc) return rc;
+            if (SB >= 4096 && M <= 65535) hipLaunchKernelGGL((rowdot_kernel<T>), dim3((unsigned)M), dim3(256), 0, st, SB, P, (const T*)Kuf, SB, (const T*)Eb, R);
+            else {
+                rc = mxf_gemm_internal(h, dtype, 0, 0, M, P, SB, 1.0, Kuf, SB, 0, Eb, P, 0, 0.0, R, P, 0, 1, 0, st);
+                if (rc) return rc;
+            }
+            if (use_mat) {
+                if (mat.dKuf) MXF_HIP(h, hipMemcpyAsync(mat.dKuf, Text, sizeof(T) * (size_t)M * SB, hipMemcpyDeviceToDevice, st));
+            } else {
+                rc = mxf_gram_bwd_internal(h, kind, dtype, 1, M, SB, Q, Z, 0, X, 0, ls, ard, 0, var, 0, Text, SB, 0, dZ, dX, dls, dvar, st);
+                if (rc) return rc;
+            }
+        } else if (!want_grad) {
+            hipLaunchKernelGGL((svgp_mid_kernel<T>), dim3((unsigned)((SB + 255) / 256)), dim3(256), 0, st, SB, B, M, P, (const T*)Kuf, Text, Y, sY,
+                               (const T*)wT, noise, a1, 0, (T*)nullptr, (T*)nullptr, 0, scal);
+        } else {
+            // (dY, dZ, dls, dvar, dX, R were cleared on the second side stream at the start of the call: su_side2)
+            // one pass over T: q_n, |e_n|^2, dY, R = Kuf E, and the Kuf-side reverse mode (dX, dZ, dls, dvar) without materialising dKuf
+            MXF_T0(h, MXF_T_BWD, st);
+            rc = mxf_svgp_bwd_fused_internal(h, kind, dtype, M, SB, B, Q, P, Z, X, ls, ard, var, Text, het_stream ? (const T*)hys : Y, sY, wT,
+                                             het_stream ? (const T*)hnz : noise, a1, dZ, dX, dls, dvar,
+                                             dY, dY_shared, R, scal, st, t_blocked,
+                                             use_split ? (const unsigned*)(info2 + 2) : nullptr,
+                                             (const unsigned*)(info2 + 3));
+            if (rc) return rc;
+        }
+        if (fused) MXF_T1(h, MXF_T_BWD, st);
+        MXF_STAGE(h, "reverse pass", st);
+        if (het_stream) {
+            // sum_n beta_n e_n^2 per sample and the per-row noise gradient: one more pass over the Kfu planes and T''
+            if (dnoise) MXF_HIP(h, hipMemsetAsync(dnoise, 0, sizeof(T) * (size_t)B, st));
+            hipLaunchKernelGGL(het_stats_kernel, dim3((unsigned)((SB / 16 + 3) / 4)), dim3(256), 0, st, SB, B, M, (const unsigned short*)plKfu, (int64_t)pl_big,
+                               (const float*)Text, (const float*)hys, sY, (const float*)noise, (const float*)hrs, (const float*)var, a1, want_grad,
+                               (float*)dnoise, hbe2);
+            hipLaunchKernelGGL((svgp_finalize_hets_kernel<T>), dim3(1), dim3(64), 0, st, S, B, M, (const D*)scal, (const D*)hbe2, (const D*)hhs, (const D*)noised,
+                               (const D*)vard, (const D*)(sc + 0), (const D*)(sc + 1), (const D*)(sc + 2), (const D*)(sc + 3), scaling, a1, logL, dvdir);
+            MXF_LAUNCH_CHECK(h);
+        } else if (!het) {
+            if (whiten) MXF_HIP(h, hipStreamWaitEvent(st, h->ev_join2, 0));      // Phi and the core's Su part (side stream): the value needs tr(C Phi)
+            hipLaunchKernelGGL((svgp_finalize_kernel<T>), dim3(1), dim3(64), 0, st, S, B, M, P, (const D*)scal, (const D*)noised, (const D*)vard,
+                               (const D*)(sc + 0), (const D*)(sc + 1), (const D*)(sc + 2), (const D*)(sc + 3), scaling, a1, logL, dnz, dvdir,
+                               whiten ? (const D*)(sc + 6) : (const D*)nullptr);
+            MXF_LAUNCH_CHECK(h);
+            if (!want_grad) publish_cond();
+        }
+        return 0;
     }
-    MXF_STAGE(h, "core reverse", st);
-    hipLaunchKernelGGL(cond_publish_kernel, dim3(1), dim3(1), 0, st, h->cond_dev, cond_slot);
-    MXF_HIP(h, hipStreamWaitEvent(st, h->ev_join, 0));     // join the Su chain: every output is ordered on the caller's stream
-    MXF_T1(h, MXF_T_CALL, st);
-    MXF_STAGE(h, "end", st);
-    MXF_STAGE_DUMP(h);
-    MXF_LAUNCH_CHECK(h);
-    return 0;
+
+    // caller's stream (het: the Su part on the side stream): the rest of the core's reverse mode, dmu, the Kuu Gram's reverse pass and the
+    // gradient outputs in one launch; then the join of the side streams
+    int finish() {
+        int rc;
+        if (het) {
+            copy_convert(MM, (const T*)Psi2, G, st);
+            copy_convert(MP, (const T*)R, Gw, st);
+            MXF_HIP(h, hipEventRecord(h->ev_fork, st));
+            MXF_HIP(h, hipStreamWaitEvent(sd_, h->ev_fork, 0));
+            rc = su_reverse(sd_, false);
+            if (rc) return rc;
+            MXF_HIP(h, hipEventRecord(h->ev_join, sd_));
+            rc = mm(0, 0, 1.0, G, KiSu, 0.0, T1, st);           // T1 = G Ki Su
+            if (rc) return rc;
+        } else {
+            MXF_HIP(h, hipStreamWaitEvent(st, h->ev_join2, 0));      // side stream: Psi2 -> G, T1, dSu / dW / dSdiag (already done)
+            hipLaunchKernelGGL((scale_beta_kernel<T>), dim3(gridn(MP)), dim3(256), 0, st, MP, (const T*)R, (const D*)noised, a1, Gw);
+        }
+        // dKuu = -Ki A_Ki Ki - bP/2 Ki (float32 fused: dKuu0 from the side stream + the rank-2P term below); dmu = Ki Gw - b w
+        const bool sym_dkuu = sym_core && !het;
+        if (!sym_dkuu) {
+            hipLaunchKernelGGL(aki_kernel, dim3(gridn(MM)), dim3(256), 0, st, M, P, (const D*)G, (const D*)T1, (const D*)Gw, (const D*)mud, (const D*)Su, bw, AKi);
+            rc = mm(0, 0, 1.0, Ki, AKi, 0.0, T2, st);           // T2 = Ki A_Ki
+            if (rc) return rc;
+            copy_convert(MM, (const D*)Ki, dKuu, st);
+            rc = mm(0, 0, -1.0, T2, Ki, -0.5 * bw * P, dKuu, st);
+            if (rc) return rc;
+        }
+        hipLaunchKernelGGL((gemv_rows_kernel<D>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, M, P, (const D*)Ki, M, (const D*)Gw, (int64_t)P, dmud, -bw, (const D*)wd);
+        if (sym_dkuu) hipLaunchKernelGGL(dkuu_rank_kernel, dim3(gridn(MM)), dim3(256), 0, st, M, P, (const D*)dmud, (const D*)wd, bw, dKuu);
+        // Kuu-side reverse mode in float64, then added to the streaming-side gradients
+        FinishArgs fa;
+        fa.cnt = 0;
+        auto fin = [&](const D* src, const D* src2, void* dst, int64_t n, int acc) {
+            fa.src[fa.cnt] = src; fa.src2[fa.cnt] = src2; fa.dst[fa.cnt] = dst; fa.n[fa.cnt] = n; fa.acc[fa.cnt] = acc; ++fa.cnt;
+        };
+        if (dmu) fin(dmud, nullptr, dmu, MP, 0);
+        if (use_mat) {
+            if (mat.dKuu) fin(dKuu, nullptr, mat.dKuu, MM, 0);
+        } else {
+            if (!fused && (rc = clear_core_grads(st))) return rc;
+            // (sym_dkuu: dKuu is formed from the mirrored X, Ki and H0, i.e. symmetric -- the row side of its reverse pass is skipped)
+            rc = mxf_gram_bwd_internal(h, kind, MXF_F64, 1, M, M, Q, Zd, 0, nullptr, 0, lsd, ard, 0, vard, 0, dKuu, M, 0, dZc, nullptr, dlsc, dvc, st,
+                                       sym_dkuu ? 1 : 0);
+            if (rc) return rc;
+            if (dZ) fin(dZc, nullptr, dZ, M * Q, 1);
+            if (dls) fin(dlsc, nullptr, dls, lsn, 1);
+            if (dvar) fin(dvc, sc + 5, dvar, 1, 1);
+        }
+        if (dnoise && !het && !het_stream) fin(sc + 4, nullptr, dnoise, 1, 0);
+        if (fa.cnt) {
+            int64_t nmax = 1;
+            for (int i = 0; i < fa.cnt; ++i) nmax = fa.n[i] > nmax ? fa.n[i] : nmax;
+            hipLaunchKernelGGL((svgp_finish_kernel<T>), dim3(gridn(nmax), (unsigned)fa.cnt), dim3(256), 0, st, fa);
+        }
+        MXF_STAGE(h, "core reverse", st);
+        publish_cond();
+        MXF_HIP(h, hipStreamWaitEvent(st, h->ev_join, 0));     // join the Su chain: every output is ordered on the caller's stream
+        MXF_T1(h, MXF_T_CALL, st);
+        MXF_STAGE(h, "end", st);
+        MXF_STAGE_DUMP(h);
+        MXF_LAUNCH_CHECK(h);
+        return 0;
+    }
+};
+
+template <typename T>
+int svgp_logpdf_typed(SvgpCall<T>& c) {
+    if (int rc = c.plan()) return rc;
+    if (int rc = c.scratch()) return rc;
+    if (int rc = c.prologue()) return rc;               // st
+    if (int rc = c.kuu_fork()) return rc;               // st
+    if (int rc = c.su_side2()) return rc;               // side2
+    if (int rc = c.kuf_psi2()) return rc;               // side
+    if (int rc = c.kuu_chain()) return rc;              // st, side2
+    if (int rc = c.whiten_v_phi()) return rc;           // st, side
+    if (int rc = c.ki_w()) return rc;                   // st
+    if (int rc = c.su_chain()) return rc;               // side2
+    if (int rc = c.h0_planes()) return rc;              // st
+    if (int rc = c.value_scalars()) return rc;          // side2
+    if (int rc = c.t_product()) return rc;              // st
+    if (int rc = c.core_reverse_side()) return rc;      // side
+    if (int rc = c.reverse_pass()) return rc;           // st
+    if (!c.want_grad) return 0;
+    return c.finish();                                  // st, side
 }
 
 // ================================================================================================ sparse (Titsias) GP
@@ -1685,25 +1763,21 @@ int sgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int64_t B, int64_t M, int 
     typedef double D;
     const int64_t MM = M * M, MP = M * P;
     const int lsn = ard ? Q : 1;
-    size_t need = 0;
-    auto acc = [&](size_t n, size_t es) { need += mxf_align(n * es); };
-    acc(M * Q, 8); acc(lsn, 8); acc(1, 8); acc(1, 8);
-    for (int i = 0; i < 10; ++i) acc(MM, 8);
-    acc(MP, 8); acc(MP, 8); acc(MP, 8); acc(16, 8); acc(4, sizeof(int));
-    acc((size_t)M * B, sizeof(T)); acc((size_t)M * B, sizeof(T)); acc(MM, sizeof(T)); acc(MP, sizeof(T)); acc(MM, sizeof(T)); acc(MP, sizeof(T));
-    acc(M * Q, 8); acc(lsn, 8); acc(4, 8);
-    void* ws = mxf_ws(h, need);
-    if (!ws) MXF_FAIL(h, -4, "mxf_sgp_logpdf: cannot allocate %zu bytes of scratch", need);
-    Carver cv(ws);
-    D* Zd = cv.take<D>(M * Q); D* lsd = cv.take<D>(lsn); D* vard = cv.take<D>(1); D* noised = cv.take<D>(1);
-    D* Lm = cv.take<D>(MM); D* Linv = cv.take<D>(MM); D* Ki = cv.take<D>(MM); D* Cm = cv.take<D>(MM); D* Lcinv = cv.take<D>(MM);
-    D* Ci = cv.take<D>(MM); D* Psi2d = cv.take<D>(MM); D* KPK = cv.take<D>(MM); D* tmp = cv.take<D>(MM); D* GKuu = cv.take<D>(MM);
-    D* psi1d = cv.take<D>(MP); D* ad = cv.take<D>(MP); D* PA = cv.take<D>(MP); D* sc = cv.take<D>(16); int* info2 = cv.take<int>(4);
-    T* Kuf = cv.take<T>((size_t)M * B); T* Kfu = cv.take<T>((size_t)M * B); T* Psi2 = cv.take<T>(MM); T* psi1 = cv.take<T>(MP);
-    T* G2 = cv.take<T>(MM); T* Gpsi1 = cv.take<T>(MP);
-    D* dZc = cv.take<D>(M * Q); D* dlsc = cv.take<D>(lsn); D* dvc = cv.take<D>(4);
-#define CONV(n, src, dst) hipLaunchKernelGGL((convert_kernel<T, D>), dim3(gridn(n)), dim3(256), 0, st, (int64_t)1, (int64_t)(n), src, (int64_t)(n), dst, (int64_t)(n))
-    CONV(M * Q, Z, Zd); CONV(lsn, ls, lsd); CONV(1, var, vard); CONV(1, noise, noised);
+    D *Zd, *lsd, *vard, *noised, *Lm, *Linv, *Ki, *Cm, *Lcinv, *Ci, *Psi2d, *KPK, *tmp, *GKuu, *psi1d, *ad, *PA, *sc, *dZc, *dlsc, *dvc;
+    int* info2;
+    T *Kuf, *Kfu, *Psi2, *psi1, *G2, *Gpsi1;
+    size_t need;
+    const bool ok = carve_scratch(h, [&](Carver& cv) {
+        Zd = cv.take<D>(M * Q); lsd = cv.take<D>(lsn); vard = cv.take<D>(1); noised = cv.take<D>(1);
+        Lm = cv.take<D>(MM); Linv = cv.take<D>(MM); Ki = cv.take<D>(MM); Cm = cv.take<D>(MM); Lcinv = cv.take<D>(MM);
+        Ci = cv.take<D>(MM); Psi2d = cv.take<D>(MM); KPK = cv.take<D>(MM); tmp = cv.take<D>(MM); GKuu = cv.take<D>(MM);
+        psi1d = cv.take<D>(MP); ad = cv.take<D>(MP); PA = cv.take<D>(MP); sc = cv.take<D>(16); info2 = cv.take<int>(4);
+        Kuf = cv.take<T>((size_t)M * B); Kfu = cv.take<T>((size_t)M * B); Psi2 = cv.take<T>(MM); psi1 = cv.take<T>(MP);
+        G2 = cv.take<T>(MM); Gpsi1 = cv.take<T>(MP);
+        dZc = cv.take<D>(M * Q); dlsc = cv.take<D>(lsn); dvc = cv.take<D>(4);
+    }, need);
+    if (!ok) MXF_FAIL(h, -4, "mxf_sgp_logpdf: cannot allocate %zu bytes of scratch", need);
+    copy_convert(M * Q, Z, Zd, st); copy_convert((int64_t)lsn, ls, lsd, st); copy_convert((int64_t)1, var, vard, st); copy_convert((int64_t)1, noise, noised, st);
     MXF_HIP(h, hipMemsetAsync(sc, 0, 16 * sizeof(D), st));
     // (r04) cond_1(Kuu + jitter I) is published exactly as the SVGP call does (mxf_svgp_cond_slot / mxf_svgp_last_cond): the float32 form of
     // this bound feeds a float32 Psi2 into C = Kuu + Psi2 / s2 and K^-1 Psi2 K^-1 -- ELBO 7e-6 at cond 3e4, a non-PD C at 1e6 -- and the
@@ -1735,7 +1809,7 @@ int sgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int64_t B, int64_t M, int 
     hipLaunchKernelGGL((symmetrize_kernel<T>), dim3((unsigned)((M + 31) / 32), (unsigned)((M + 31) / 32), 1), dim3(256), 0, st, Psi2, M, M, MM);
     rc = mxf_gemm_internal(h, dtype, 0, 0, M, P, B, 1.0, Kuf, B, 0, Y, P, 0, 0.0, psi1, P, 0, 1, 0, st);
     if (rc) return rc;
-    CONV(MM, (const T*)Psi2, Psi2d); CONV(MP, (const T*)psi1, psi1d);
+    copy_convert(MM, (const T*)Psi2, Psi2d, st); copy_convert(MP, (const T*)psi1, psi1d, st);
     hipLaunchKernelGGL((sumsq_kernel<T>), dim3(1), dim3(256), 0, st, B * P, Y, (int64_t)0, sc + 6);
     // C = Kuu + Psi2/s2, Lc = chol(C), Ci, a = Ci psi1
     hipLaunchKernelGGL(sgp_add_psi2_kernel, dim3(gridn(MM)), dim3(256), 0, st, MM, Cm, (const D*)Psi2d, (const D*)noised);
@@ -1801,7 +1875,6 @@ int sgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int64_t B, int64_t M, int 
         hipLaunchKernelGGL((add_convert_kernel<D, T>), dim3(1), dim3(64), 0, st, (int64_t)1, (T)1, (const D*)(sc + 9), dvar, 1);
     }
     if (dnoise) hipLaunchKernelGGL((add_convert_kernel<D, T>), dim3(1), dim3(64), 0, st, (int64_t)1, (T)1, (const D*)(sc + 8), dnoise, 0);
-#undef CONV
     MXF_LAUNCH_CHECK(h);
     return 0;
 }
@@ -1819,18 +1892,12 @@ extern "C" int mxf_gp_logpdf(mxf_handle h, int kind, int dtype, int S, int64_t N
     if (S <= 0 || N <= 0 || Q <= 0 || P <= 0) MXF_FAIL(h, -2, "mxf_gp_logpdf: bad shape");
     if (!X || !Y || !noise_var || !lengthscale || !variance || !logL || !L || !LinvY) MXF_FAIL(h, -2, "mxf_gp_logpdf: null argument");
     if (kind > MXF_K_MATERN52) MXF_FAIL(h, -2, "mxf_gp_logpdf: stationary kernels only");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MXF_F32)
-        return gp_logpdf_typed<float>(h, kind, dtype, S, N, Q, P, (const float*)X, strideS_X, (const float*)Y, strideS_Y, (const float*)noise_var,
-                                      strideS_noise, (const float*)lengthscale, ard, strideS_ls, (const float*)variance, strideS_var, jitter,
-                                      (float*)logL, (float*)L, (float*)LinvY, info, want_grad, (float*)dX, (float*)dY, (float*)dnoise,
-                                      (float*)dls, (float*)dvar, st);
-    if (dtype == MXF_F64)
-        return gp_logpdf_typed<double>(h, kind, dtype, S, N, Q, P, (const double*)X, strideS_X, (const double*)Y, strideS_Y, (const double*)noise_var,
-                                       strideS_noise, (const double*)lengthscale, ard, strideS_ls, (const double*)variance, strideS_var, jitter,
-                                       (double*)logL, (double*)L, (double*)LinvY, info, want_grad, (double*)dX, (double*)dY, (double*)dnoise,
-                                       (double*)dls, (double*)dvar, st);
-    MXF_FAIL(h, -2, "mxf_gp_logpdf: bad dtype %d", dtype);
+    return by_dtype(h, "mxf_gp_logpdf", dtype, [&](auto t) {
+        typedef decltype(t) T;
+        return gp_logpdf_typed<T>(h, kind, dtype, S, N, Q, P, (const T*)X, strideS_X, (const T*)Y, strideS_Y, (const T*)noise_var, strideS_noise,
+                                  (const T*)lengthscale, ard, strideS_ls, (const T*)variance, strideS_var, jitter, (T*)logL, (T*)L, (T*)LinvY, info,
+                                  want_grad, (T*)dX, (T*)dY, (T*)dnoise, (T*)dls, (T*)dvar, (hipStream_t)stream);
+    });
 }
 
 static int svgp_dispatch(mxf_handle h, const char* fn, int kind, int dtype, int S, int64_t B, int64_t M, int Q, int P,
@@ -1844,20 +1911,14 @@ static int svgp_dispatch(mxf_handle h, const char* fn, int kind, int dtype, int 
     if (!X || !Y || !Z || !noise_var || !qU_mean || !qU_cov_W || !qU_cov_diag || !lengthscale || !variance || !logL)
         MXF_FAIL(h, -2, "%s: null argument", fn);
     if (kind > MXF_K_MATERN52) MXF_FAIL(h, -2, "%s: stationary kernels only", fn);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MXF_F32)
-        return svgp_logpdf_typed<float>(h, kind, dtype, S, B, M, Q, P, (const float*)X, strideS_X, (const float*)Y, strideS_Y, (const float*)Z,
-                                        (const float*)noise_var, noise_rows, noise_cols, (const float*)qU_mean, (const float*)qU_cov_W,
-                                        (const float*)qU_cov_diag, (const float*)lengthscale, ard, (const float*)variance, jitter, scaling, gscale,
-                                        (float*)logL, info, want_grad, (float*)dX, (float*)dY, (float*)dZ, (float*)dnoise, (float*)dmu, (float*)dW,
-                                        (float*)dSdiag, (float*)dls, (float*)dvar, st);
-    if (dtype == MXF_F64)
-        return svgp_logpdf_typed<double>(h, kind, dtype, S, B, M, Q, P, (const double*)X, strideS_X, (const double*)Y, strideS_Y, (const double*)Z,
-                                         (const double*)noise_var, noise_rows, noise_cols, (const double*)qU_mean, (const double*)qU_cov_W,
-                                         (const double*)qU_cov_diag, (const double*)lengthscale, ard, (const double*)variance, jitter, scaling,
-                                         gscale, (double*)logL, info, want_grad, (double*)dX, (double*)dY, (double*)dZ, (double*)dnoise,
-                                         (double*)dmu, (double*)dW, (double*)dSdiag, (double*)dls, (double*)dvar, st);
-    MXF_FAIL(h, -2, "%s: bad dtype %d", fn, dtype);
+    return by_dtype(h, fn, dtype, [&](auto t) {
+        typedef decltype(t) T;
+        SvgpCall<T> c{{}, h, kind, dtype, S, B, M, Q, P, (const T*)X, strideS_X, (const T*)Y, strideS_Y, (const T*)Z, (const T*)noise_var,
+                      noise_rows, noise_cols, (const T*)qU_mean, (const T*)qU_cov_W, (const T*)qU_cov_diag, (const T*)lengthscale, ard,
+                      (const T*)variance, jitter, scaling, gscale, (T*)logL, info, want_grad, (T*)dX, (T*)dY, (T*)dZ, (T*)dnoise, (T*)dmu,
+                      (T*)dW, (T*)dSdiag, (T*)dls, (T*)dvar, (hipStream_t)stream};
+        return svgp_logpdf_typed(c);
+    });
 }
 
 extern "C" int mxf_svgp_logpdf(mxf_handle h, int kind, int dtype, int S, int64_t B, int64_t M, int Q, int P,
@@ -1928,25 +1989,14 @@ extern "C" int mxf_svgp_logpdf_mat(mxf_handle h, int dtype, int S, int64_t B, in
     if (S > 1 && strideS_Y != B * P) MXF_FAIL(h, -2, "mxf_svgp_logpdf_mat: S > 1 needs contiguous Y samples (S, B, P)");
     const int64_t sYv = S > 1 ? strideS_Y : 0;
     if (!Kuu || !Kuf || !Kdiag || !Y || !noise_var || !qU_mean || !qU_cov_W || !qU_cov_diag || !logL) MXF_FAIL(h, -2, "mxf_svgp_logpdf_mat: null argument");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MXF_F32) {
-        SvgpMat<float> m; m.Kuu = (const float*)Kuu; m.Kuf = (const float*)Kuf; m.Kdiag = (const float*)Kdiag;
-        m.dKuu = (float*)dKuu; m.dKuf = (float*)dKuf; m.dKdiag = (float*)dKdiag;
-        return svgp_logpdf_typed<float>(h, MXF_K_RBF, dtype, S, B, M, 1, P, (const float*)Kuf /*unused X*/, 0, (const float*)Y, sYv, nullptr,
-                                        (const float*)noise_var, noise_rows, noise_cols, (const float*)qU_mean, (const float*)qU_cov_W,
-                                        (const float*)qU_cov_diag, nullptr, 0, nullptr, jitter, scaling, gscale, (float*)logL, info, want_grad,
-                                        nullptr, (float*)dY, nullptr, (float*)dnoise, (float*)dmu, (float*)dW, (float*)dSdiag, nullptr, nullptr, st, m);
-    }
-    if (dtype == MXF_F64) {
-        SvgpMat<double> m; m.Kuu = (const double*)Kuu; m.Kuf = (const double*)Kuf; m.Kdiag = (const double*)Kdiag;
-        m.dKuu = (double*)dKuu; m.dKuf = (double*)dKuf; m.dKdiag = (double*)dKdiag;
-        return svgp_logpdf_typed<double>(h, MXF_K_RBF, dtype, S, B, M, 1, P, (const double*)Kuf, 0, (const double*)Y, sYv, nullptr,
-                                         (const double*)noise_var, noise_rows, noise_cols, (const double*)qU_mean, (const double*)qU_cov_W,
-                                         (const double*)qU_cov_diag, nullptr, 0, nullptr, jitter, scaling, gscale, (double*)logL, info, want_grad,
-                                         nullptr, (double*)dY, nullptr, (double*)dnoise, (double*)dmu, (double*)dW, (double*)dSdiag, nullptr, nullptr,
-                                         st, m);
-    }
-    MXF_FAIL(h, -2, "mxf_svgp_logpdf_mat: bad dtype %d", dtype);
+    return by_dtype(h, "mxf_svgp_logpdf_mat", dtype, [&](auto t) {
+        typedef decltype(t) T;
+        SvgpCall<T> c{{}, h, MXF_K_RBF, dtype, S, B, M, 1, P, (const T*)Kuf /* unused X */, 0, (const T*)Y, sYv, nullptr, (const T*)noise_var,
+                      noise_rows, noise_cols, (const T*)qU_mean, (const T*)qU_cov_W, (const T*)qU_cov_diag, nullptr, 0, nullptr, jitter, scaling,
+                      gscale, (T*)logL, info, want_grad, nullptr, (T*)dY, nullptr, (T*)dnoise, (T*)dmu, (T*)dW, (T*)dSdiag, nullptr, nullptr,
+                      (hipStream_t)stream, {(const T*)Kuu, (const T*)Kuf, (const T*)Kdiag, (T*)dKuu, (T*)dKuf, (T*)dKdiag}};
+        return svgp_logpdf_typed(c);
+    });
 }
 
 extern "C" int mxf_sgp_logpdf(mxf_handle h, int kind, int dtype, int64_t B, int64_t M, int Q, int P, const void* X, const void* Y,
@@ -1957,15 +2007,10 @@ extern "C" int mxf_sgp_logpdf(mxf_handle h, int kind, int dtype, int64_t B, int6
     if (B <= 0 || M <= 0 || Q <= 0 || P <= 0) MXF_FAIL(h, -2, "mxf_sgp_logpdf: bad shape");
     if (!X || !Y || !Z || !noise_var || !lengthscale || !variance || !logL) MXF_FAIL(h, -2, "mxf_sgp_logpdf: null argument");
     if (kind > MXF_K_MATERN52) MXF_FAIL(h, -2, "mxf_sgp_logpdf: stationary kernels only");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MXF_F32)
-        return sgp_logpdf_typed<float>(h, kind, dtype, B, M, Q, P, (const float*)X, (const float*)Y, (const float*)Z, (const float*)noise_var,
-                                       (const float*)lengthscale, ard, (const float*)variance, jitter, gscale, (float*)logL, (float*)wv, (float*)L,
-                                       (float*)LA, info, want_grad, (float*)dX, (float*)dY, (float*)dZ, (float*)dnoise, (float*)dls, (float*)dvar, st);
-    if (dtype == MXF_F64)
-        return sgp_logpdf_typed<double>(h, kind, dtype, B, M, Q, P, (const double*)X, (const double*)Y, (const double*)Z, (const double*)noise_var,
-                                        (const double*)lengthscale, ard, (const double*)variance, jitter, gscale, (double*)logL, (double*)wv,
-                                        (double*)L, (double*)LA, info, want_grad, (double*)dX, (double*)dY, (double*)dZ, (double*)dnoise,
-                                        (double*)dls, (double*)dvar, st);
-    MXF_FAIL(h, -2, "mxf_sgp_logpdf: bad dtype %d", dtype);
+    return by_dtype(h, "mxf_sgp_logpdf", dtype, [&](auto t) {
+        typedef decltype(t) T;
+        return sgp_logpdf_typed<T>(h, kind, dtype, B, M, Q, P, (const T*)X, (const T*)Y, (const T*)Z, (const T*)noise_var, (const T*)lengthscale, ard,
+                                   (const T*)variance, jitter, gscale, (T*)logL, (T*)wv, (T*)L, (T*)LA, info, want_grad, (T*)dX, (T*)dY, (T*)dZ,
+                                   (T*)dnoise, (T*)dls, (T*)dvar, (hipStream_t)stream);
+    });
 }

@@ -91,12 +91,6 @@ __global__ __launch_bounds__(256) void upart_reduce_kernel(int64_t N, int nparts
     U[n] = s * (scale ? scale[0] : 1.f) * sc2;
 }
 
-// dst = tril(src) (float64, n x n): potrf leaves the strict upper triangle of its buffer as it was
-__global__ void tril_copy_kernel(int64_t n, const double* __restrict__ src, double* __restrict__ dst) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n * n; i += (int64_t)gridDim.x * blockDim.x)
-        dst[i] = (i % n <= i / n) ? src[i] : 0.0;
-}
-
 }  // namespace
 
 int mxf_planes_transpose_internal(mxf_ctx* h, int64_t R, int64_t K, const unsigned short* in, int64_t pin, unsigned short* out, int64_t pout,
@@ -113,14 +107,6 @@ int mxf_planes_transpose_internal(mxf_ctx* h, int64_t R, int64_t K, const unsign
 int mxf_upart_reduce_internal(mxf_ctx* h, int64_t N, int nparts, const float* Upart, const float* scale, float sc2, float* U, hipStream_t st) {
     if (N <= 0) return 0;
     hipLaunchKernelGGL(upart_reduce_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, N, nparts, Upart, scale, sc2, U);
-    MXF_LAUNCH_CHECK(h);
-    return 0;
-}
-
-int mxf_tril_copy_internal(mxf_ctx* h, int64_t n, const double* src, double* dst, hipStream_t st) {
-    int64_t b = (n * n + 255) / 256;
-    if (b > 4096) b = 4096;
-    hipLaunchKernelGGL(tril_copy_kernel, dim3((unsigned)b), dim3(256), 0, st, n, src, dst);
     MXF_LAUNCH_CHECK(h);
     return 0;
 }
