@@ -888,198 +888,283 @@ __global__ __launch_bounds__(512) void potrf_rows_kernel(double* __restrict__ A,
 }
 
 template <typename T>
-int trtri_typed(mxf_ctx* h, int dtype, int S, int64_t n, const T* L, int64_t ldl, int64_t sL, T* Li, int64_t ldi, int64_t sI, hipStream_t st);
-template <typename T>
-__global__ void zero_block_kernel(T* __restrict__ P, int64_t rows, int64_t cols, int64_t ld, int64_t stride);
+__global__ void zero_block_kernel(T* __restrict__ P, int64_t rows, int64_t cols, int64_t ld, int64_t stride) {
+    T* p = P + (int64_t)blockIdx.y * stride;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows * cols; i += (int64_t)gridDim.x * blockDim.x)
+        p[(i / cols) * ld + (i % cols)] = (T)0;
+}
 
-// Row block i (rows [c0, pe)) of L^-1 from the finished leading part of the factor (the merge step of trtri_typed with a first block of c0 rows
-// and a second of pe - c0), in three dependent pieces, so that each starts as soon as ITS inputs exist:
-//   p1: (L[i, :c0] I[:c0, :c0])^T into the upper mirror block -- needs the rows below the panel ending at c0 and the finished leading inverse,
-//       NOT the block's own panels (the bulk of the row block's work: 2 b2 c0^2 / 2 flops);
-//   the inverse of the diagonal block L[i, i] -- needs the block's own panels only (latency-bound small launches: a stream of its own);
-//   p2: X = -I_ii p1^T, then the mirror block zeroed again.
+// Kernel templates land in the code object in the order they are first used.  This list uses each instance once, in the order the code
+// object has always had, so that host code below can be rearranged without moving device code (the device assembly of a host-only change
+// then compares equal).  Host-side only; never read.
+[[maybe_unused]] const void* const chol_kernel_order[] = {
+    (const void*)potrf_panel_kernel<float>, (const void*)zero_upper_kernel<float>, (const void*)zero_upper_kernel<double>,
+    (const void*)zero_block_kernel<double>, (const void*)potrf_panel_kernel<double>,
+    (const void*)solve_cols_kernel<float, false>, (const void*)solve_cols_kernel<float, true>,
+    (const void*)solve_cols_kernel<double, false>, (const void*)solve_cols_kernel<double, true>,
+    (const void*)trtri_diag_kernel<float>, (const void*)zero_block_kernel<float>, (const void*)trtri_diag_kernel<double>,
+    (const void*)sumlogdiag_kernel<float>, (const void*)sumlogdiag_kernel<double>};
+
+// ---- triangular inverse ------------------------------------------------------------------------------------------------------------------
+// The merge step:  inv([L11 0; L21 L22]) = [I11 0; -I22 L21 I11, I22]  for `batch` pairs of a b1-row first and a b2-row second block (Lp / Ip:
+// the first pair's corner in the factor / the inverse, stL / stI: pair strides), given I11 and I22, in two MFMA GEMMs; the temporary
+// (L21 I11)^T lives in the (unused, finally zeroed) upper-triangular mirror block of the output, so no extra workspace is needed.
+// Both products have a triangular left operand: with `tri` only the non-zero k range of each row tile is multiplied.
+//   p1: tmpT (b1 x b2, in the mirror block) = I11^T L21^T -- needs I11 and L21, NOT I22 (the bulk of the work);
+//   p2: X21 = -I22 tmpT^T, then the mirror block zeroed again (it becomes part of the next level's I11 operand).
 template <typename T>
-int trtri_row_block_p1(mxf_ctx* h, int dtype, int64_t c0, int64_t pe, const T* L, int64_t ldl, T* Li, int64_t ldi, hipStream_t st) {
-    return mxf_gemm_internal(h, dtype, 1, 1, c0, pe - c0, c0, 1.0, Li, ldi, 0, L + c0 * ldl, ldl, 0, 0.0, Li + c0, ldi, 0, 1, 0, st, 0, 1);
+int trtri_merge_p1(mxf_ctx* h, int dtype, int64_t b1, int64_t b2, const T* Lp, int64_t ldl, int64_t stL, T* Ip, int64_t ldi, int64_t stI, int batch,
+                   bool tri, hipStream_t st) {
+    return mxf_gemm_internal(h, dtype, 1, 1, b1, b2, b1, 1.0, Ip, ldi, stI, Lp + b1 * ldl, ldl, stL, 0.0, Ip + b1, ldi, stI, batch, 0, st, 0, tri ? 1 : 0);
 }
 template <typename T>
-int trtri_row_block_p2(mxf_ctx* h, int dtype, int64_t c0, int64_t pe, T* Li, int64_t ldi, hipStream_t st) {
-    const int64_t b2 = pe - c0;
-    int rc = mxf_gemm_internal(h, dtype, 0, 1, b2, c0, b2, -1.0, Li + c0 * (ldi + 1), ldi, 0, Li + c0, ldi, 0, 0.0, Li + c0 * ldi, ldi, 0, 1, 0, st, 0, 2);
+int trtri_merge_p2(mxf_ctx* h, int dtype, int64_t b1, int64_t b2, T* Ip, int64_t ldi, int64_t stI, int batch, bool tri, hipStream_t st) {
+    int rc = mxf_gemm_internal(h, dtype, 0, 1, b2, b1, b2, -1.0, Ip + b1 * (ldi + 1), ldi, stI, Ip + b1, ldi, stI, 0.0, Ip + b1 * ldi, ldi, stI, batch, 0, st, 0,
+                               tri ? 2 : 0);
     if (rc) return rc;
-    hipLaunchKernelGGL((zero_block_kernel<T>), dim3((unsigned)((c0 * b2 + 255) / 256 > 1024 ? 1024 : (c0 * b2 + 255) / 256), 1), dim3(256), 0, st, Li + c0, c0, b2, ldi, (int64_t)0);
+    hipLaunchKernelGGL((zero_block_kernel<T>), dim3((unsigned)((b1 * b2 + 255) / 256 > 1024 ? 1024 : (b1 * b2 + 255) / 256), (unsigned)batch), dim3(256), 0, st,
+                       Ip + b1, b1, b2, ldi, stI);
     return 0;
 }
 
-// Ie != nullptr (float64, one matrix, the per-panel tile form with look-ahead): L^-1 is formed into Ie row block by row block on a third stream while
-// the factorisation goes on -- potrf(8192) is bound by its serial path (16 x (head update + chain + rows below)), the chip is ~40 % idle under it, and
-// trtri(8192) afterwards took 3.9 ms of a 15 ms MAP step.  *eager_done tells the caller whether Ie was filled (else: call trtri afterwards).
+// Log-depth blocked inverse of a lower-triangular matrix.  Level 0: all 64x64 diagonal blocks (one launch).  Level l merges pairs of
+// bs-blocks (all complete pairs of a matrix as one batch, then a ragged last pair).  From TRI_MIN-wide blocks on the products skip the zero
+// k range -- trtri(8192) 6.9 -> 5.0 ms; the small levels keep the plain split-K products, which fill the chip better.
+template <typename T>
+int trtri_typed(mxf_ctx* h, int dtype, int S, int64_t n, const T* L, int64_t ldl, int64_t sL, T* Li, int64_t ldi, int64_t sI, hipStream_t st) {
+    if (n > 65535) MXF_FAIL(h, -3, "mxf_trtri: n too large");
+    const int64_t nblk = (n + NB - 1) / NB;
+    hipLaunchKernelGGL((trtri_diag_kernel<T>), dim3((unsigned)nblk, S), dim3(64), 0, st, L, ldl, sL, Li, ldi, sI, n);
+    for (int64_t bs = NB; bs < n; bs *= 2) {
+        const int64_t npairs_full = n / (2 * bs);                 // pairs whose second block is complete
+        const int64_t rem0 = npairs_full * 2 * bs;                  // start of a possible ragged last pair
+        const int64_t b2 = n - rem0 - bs;                           // rows of its second block
+        const bool tri = bs >= TRI_MIN;
+        for (int s = 0; s < S; ++s) {
+            const T* Ls = L + (int64_t)s * sL;
+            T* Is = Li + (int64_t)s * sI;
+            if (npairs_full > 0) {
+                const int64_t stL = 2 * bs * (ldl + 1), stI = 2 * bs * (ldi + 1);
+                int rc = trtri_merge_p1<T>(h, dtype, bs, bs, Ls, ldl, stL, Is, ldi, stI, (int)npairs_full, tri, st);
+                if (!rc) rc = trtri_merge_p2<T>(h, dtype, bs, bs, Is, ldi, stI, (int)npairs_full, tri, st);
+                if (rc) return rc;
+            }
+            if (rem0 < n && b2 > 0) {
+                int rc = trtri_merge_p1<T>(h, dtype, bs, b2, Ls + rem0 * (ldl + 1), ldl, 0, Is + rem0 * (ldi + 1), ldi, 0, 1, tri, st);
+                if (!rc) rc = trtri_merge_p2<T>(h, dtype, bs, b2, Is + rem0 * (ldi + 1), ldi, 0, 1, tri, st);
+                if (rc) return rc;
+            }
+        }
+    }
+    if (n > 1) hipLaunchKernelGGL((zero_upper_kernel<T>), dim3((unsigned)((n + 255) / 256), (unsigned)n, S), dim3(256), 0, st, Li, n, ldi, sI);
+    MXF_LAUNCH_CHECK(h);
+    return 0;
+}
+
+// ---- potrf: the plan ------------------------------------------------------------------------------------------------------------------------
+// Which form a factorisation takes, decided once per call (potrf_plan).  float64 with n a multiple of 64: the tile kernel, one launch up to
+// MXF_POTRF_ONE_MAX = 512, one per outer panel of NBO columns beyond; float32 and ragged n: one panel-kernel launch per 64 columns.
+// The stages rely on:   one_launch => panel_tiles;   panel_tiles => T is double, n % NB == 0 and a workgroup per block row fits the device;
+//   eager => look => the handle's auxiliary streams and events exist (mxf_potrf_aux_init);   eager => panel_tiles and S == 1;
+//   split(c0) => panel_tiles.
+struct PotrfPlan {
+    int64_t n; int S;
+    bool panel_tiles;      // the tile kernel factors a whole outer panel in one launch
+    bool one_launch;       // ... and the whole matrix is one such panel, whatever its width
+    bool look;             // look-ahead: the trailing update is split between the caller's stream and potrf_aux (PotrfCall::trailing_update)
+    bool eager;            // L^-1 is formed next to the factorisation (PotrfCall::eager_row_block)
+    int64_t split_rows;    // an outer panel with at least this many block rows below it takes the split form (0: never)
+    int64_t rbw;           // eager: rows of a row block of the inverse
+
+    int64_t panel_end(int64_t c0) const { return !one_launch && c0 + NBO < n ? c0 + NBO : n; }
+    // does the outer panel at c0 take the split form (chain launch + rows-below launch)?
+    bool split(int64_t c0) const { return panel_tiles && split_rows > 0 && (n - panel_end(c0)) / NB >= split_rows; }
+    // eager: row block [rb0, pe) of L is final once the panel ending at pe has been factored (the rows above it in these columns are zero)
+    bool fires_at(int64_t pe) const { return pe % rbw == 0 || pe == n; }
+    int64_t next_fire(int64_t pe) const {
+        do pe = panel_end(pe); while (!fires_at(pe));
+        return pe;
+    }
+};
+
+// The tile kernel's workgroups hand tiles to each other through progress counters: every workgroup of a launch must be RESIDENT at once (one per
+// CU: 256 threads at one wave per SIMD, ~76 KB of LDS), or a waiting workgroup could hold the CU its producer needs.  The grid (block rows x
+// batch) is therefore bounded by the CU count of the device; larger problems take the launch-per-panel form.
+// Look-ahead (n >= 2048, not while the stream is being captured: the auxiliary streams are not part of the capture): at n = 8192 the 128 panel steps
+// (85 us each) otherwise serialise with 3.7 ms of trailing GEMMs.
+// Eager inverse (a buffer for it, one matrix, whole outer panels, at least 16 of them and 4 row blocks): potrf(8192) is bound by its serial path
+// (16 x (head update + chain + rows below)), the chip is ~40 % idle under it, and trtri(8192) afterwards took 3.9 ms of a 15 ms MAP step.  Row
+// blocks of MXF_POTRF_EAGER_INV = 2 outer panels (0: no eager inverse); DESIGN_HISTORY.md, "Variants measured and removed", has the other widths.
+PotrfPlan potrf_plan(mxf_ctx* h, size_t esize, int S, int64_t n, hipStream_t st, bool want_inverse) {
+    static const int ncu = [] { int dev = 0, v = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 64; return v; }();
+    static const int one_max = MXF_KNOB("MXF_POTRF_ONE_MAX", 512);     // (n = 2048 as ONE left-looking launch: 2.6 ms vs 1.9 -- the last block rows carry 32 i^2 columns of products each)
+    static const int split_rows = MXF_KNOB("MXF_POTRF_SPLIT_ROWS", 64);
+    static const int eager_panels = MXF_KNOB("MXF_POTRF_EAGER_INV", 2);
+    PotrfPlan p;
+    p.n = n; p.S = S; p.split_rows = split_rows; p.rbw = (int64_t)eager_panels * NBO;
+    p.panel_tiles = esize == 8 && n % NB == 0 && n >= 2 * NB && S <= 64 && (int64_t)(n / NB) * S <= ncu;
+    p.one_launch = p.panel_tiles && n <= one_max;
+    p.look = false;
+    if (!p.one_launch) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        (void)hipStreamIsCapturing(st, &cap);
+        p.look = n >= 2048 && cap == hipStreamCaptureStatusNone && mxf_potrf_aux_init(h);
+    }
+    p.eager = want_inverse && eager_panels && S == 1 && p.panel_tiles && p.look && n % NBO == 0 && n >= 16 * NBO && n >= 4 * p.rbw;
+    return p;
+}
+
+// ---- potrf: one call and its stages ---------------------------------------------------------------------------------------------------------
+// Events of potrf_aux that the caller's stream has not waited on yet.  Only trailing_update sets them, only wait_rest / wait_head clear them, and
+// join clears whatever is left: every recorded auxiliary event is waited on by the caller's stream before the call returns.
+struct PotrfPending {
+    bool rest = false;     // ev_pb: the rest of a trailing update (everything right of the next outer panel)
+    bool head = false;     // ev_ph: the update of the rows below the next outer panel's diagonal block
+};
+
+// One factorisation: its arguments, its plan and the stages that queue its launches, in enqueue order.  Streams: st (the caller's: the serial
+// path), and with look-ahead h->potrf_aux; with the eager inverse also h->potrf_inv and h->potrf_inv_diag.
+template <typename T>
+struct PotrfCall : PotrfPlan {
+    mxf_ctx* h; int dtype; T* A; int64_t lda, sA; int* info; hipStream_t st; T* Ie; int64_t ldie;
+    PotrfPending pend;
+
+    int wait_rest() { if (pend.rest) { MXF_HIP(h, hipStreamWaitEvent(st, h->ev_pb, 0)); pend.rest = false; } return 0; }
+    int wait_head() { if (pend.head) { MXF_HIP(h, hipStreamWaitEvent(st, h->ev_ph, 0)); pend.head = false; } return 0; }
+
+    // A[r0 : r0 + m, cc : cc + nc] -= A[r0 : r0 + m, k0 : k0 + K] A[cc : cc + nc, k0 : k0 + K]^T on stream q (lower: blocks on and below the diagonal only)
+    int update(int64_t r0, int64_t m, int64_t cc, int64_t nc, int64_t k0, int64_t K, int lower, hipStream_t q) {
+        return mxf_gemm_internal(h, dtype, 0, 1, m, nc, K, -1.0, A + r0 * lda + k0, lda, sA, A + cc * lda + k0, lda, sA, 1.0, A + r0 * lda + cc, lda, sA, S,
+                                 lower, q);
+    }
+
+    // Tile form (panel_tiles) of the outer panel at c0, on st.  Waits on ev_ph if pending.  One launch for all nbr block rows from c0 down, or
+    // (split) two: the panel's own npt block rows (the latency chain), then the rows below against the finished diagonal block, right-looking
+    // from registers in workgroups of 32 rows (potrf_rows_kernel; ~90 us of MFMA work each, nothing to wait for).  In one launch those rows sit
+    // resident and mostly idle for the whole chain, one CU each, and the look-ahead GEMM next to them (whose 133 KB of LDS cannot share a CU with a
+    // tile workgroup) runs on what is left.  The chain launch reads the diagonal block only, so in the split form the wait for the auxiliary
+    // stream's update of the rows below it comes behind that launch (that update ran next to the chain); every other form waits first.
+    int factor_panel_tiles(int64_t c0) {
+        const unsigned nbr = (unsigned)((n - c0) / NB), npt = (unsigned)((panel_end(c0) - c0) / NB);
+        const bool two = split(c0);
+        const unsigned na = two ? npt : nbr;
+        if (!two) { int rc = wait_head(); if (rc) return rc; }
+        int* progress = mxf_flags(h, (na + 1) * (unsigned)S);
+        if (!progress) MXF_FAIL(h, -4, "mxf_potrf: cannot allocate the workgroup hand-off counters");
+        double* pinv = mxf_potrf_inv(h, (size_t)npt * S * 1024);
+        if (!pinv) MXF_FAIL(h, -4, "mxf_potrf: cannot allocate the inverse-block scratch");
+        hipLaunchKernelGGL(potrf_tiles_kernel, dim3(na, (unsigned)S), dim3(256), 0, st, (double*)A, lda, sA, c0, (int)npt, info, progress, pinv, 0, 0);
+        int rc = wait_head();
+        if (rc) return rc;
+        if (two) hipLaunchKernelGGL(potrf_rows_kernel, dim3((nbr - npt) * 2, (unsigned)S), dim3(512), 0, st, (double*)A, lda, sA, c0, (int)npt, (int)npt, (const double*)pinv);
+        return 0;
+    }
+
+    // Panel-kernel form (float32, ragged n, more block rows than CUs) of the outer panel at c0, on st: per 64-wide block column the left-looking
+    // update with the panel's previous block columns, then one launch that factors the diagonal block and solves the rows below.  Waits on ev_ph
+    // if pending (never today: only split panels get their head update on the auxiliary stream, and those take the tile form).
+    int factor_panel_columns(int64_t c0) {
+        int rc = wait_head();
+        if (rc) return rc;
+        for (int64_t j0 = c0; j0 < panel_end(c0); j0 += NB) {
+            const int nb = (int)((j0 + NB < n) ? NB : n - j0);
+            if (j0 > c0 && (rc = update(j0, n - j0, j0, nb, c0, j0 - c0, 0, st))) return rc;
+            const int64_t below = n - (j0 + nb);
+            int* arrived = mxf_flags(h, (unsigned)S);
+            if (!arrived) MXF_FAIL(h, -4, "mxf_potrf: cannot allocate the workgroup hand-off counters");
+            hipLaunchKernelGGL((potrf_panel_kernel<T>), dim3((unsigned)(1 + (below + 127) / 128), S), dim3(128), 0, st, A, lda, sA, j0, nb, n, info, arrived);
+        }
+        return 0;
+    }
+
+    // Eager inverse, when the panels of row block [rb0, pe) have been factored (fires_at(pe)): the block's pieces of the merge step with a first
+    // block of rb0 rows, each queued as soon as ITS inputs exist.  Records ev_pi on st (L down to row pe and the rows below it are final).
+    //   potrf_inv_diag: waits ev_pi; the inverse of the diagonal block L[rb0:pe, rb0:pe] (needs the block's own panels only); records ev_pc.
+    //   potrf_inv: waits ev_pc; p2 of this block (its p1 was queued one firing earlier); waits ev_pi; p1 of the NEXT block, whose inputs -- the
+    //     rows below the panel that just ended and the finished leading inverse -- are complete now, panels before that block is factored.
+    // What is left behind the factorisation is the last block's diagonal inverse and p2.  join() brings potrf_inv back to st; potrf_inv_diag's
+    // work always ends in an ev_pc that potrf_inv has waited on.
+    int eager_row_block(int64_t pe) {
+        const int64_t rb0 = (pe - 1) / rbw * rbw;
+        hipStream_t qd = h->potrf_inv_diag, qp = h->potrf_inv;
+        MXF_HIP(h, hipEventRecord(h->ev_pi, st));
+        MXF_HIP(h, hipStreamWaitEvent(qd, h->ev_pi, 0));
+        int rc = trtri_typed<T>(h, dtype, 1, pe - rb0, A + rb0 * (lda + 1), lda, 0, Ie + rb0 * (ldie + 1), ldie, 0, qd);
+        if (rc) return rc;
+        MXF_HIP(h, hipEventRecord(h->ev_pc, qd));
+        MXF_HIP(h, hipStreamWaitEvent(qp, h->ev_pc, 0));       // (block 0: p1 of block 1 reads this inverse)
+        if (rb0 > 0 && (rc = trtri_merge_p2<T>(h, dtype, rb0, pe - rb0, Ie, ldie, 0, 1, true, qp))) return rc;
+        if (pe < n) {
+            MXF_HIP(h, hipStreamWaitEvent(qp, h->ev_pi, 0));   // the rows below the panel that just ended
+            rc = trtri_merge_p1<T>(h, dtype, pe, next_fire(pe) - pe, (const T*)A, lda, 0, Ie, ldie, 0, 1, true, qp);
+        }
+        return rc;
+    }
+
+    // Trailing update after the outer panel [c0, pe), pe < n, lower blocks only: A22 -= L21 L21^T with K = the panel's width.  Waits on ev_pb if
+    // pending (the previous rest update touched these columns).  Without look-ahead, or in front of the last panel: one product on st.
+    // With look-ahead: the part that touches the NEXT outer panel's columns [pe, pe2) first, so that panel's latency-bound factorisation starts
+    // right away, and the rest on potrf_aux next to that factorisation (records ev_pb, sets pend.rest):
+    //   next panel not split: its diagonal block and the rows below it on st; ev_pa recorded on st behind them and waited on by potrf_aux (the
+    //     rest starts behind the head products, not next to them);
+    //   next panel split: only its diagonal block (what its chain launch reads) on st; the rows below it -- read by potrf_rows_kernel only,
+    //     0.2 ms later -- on potrf_aux behind ev_pa, recorded on st in FRONT of the diagonal block's product (this panel's columns are final);
+    //     records ev_ph, sets pend.head (0.09 ms per panel off the serial path at n = 8192).
+    int trailing_update(int64_t c0) {
+        const int64_t pe = panel_end(c0), pe2 = panel_end(pe), K = pe - c0;
+        int rc = wait_rest();
+        if (rc) return rc;
+        if (!look || pe2 >= n) return update(pe, n - pe, pe, n - pe, c0, K, 1, st);
+        hipStream_t ax = h->potrf_aux;
+        const bool head_aux = split(pe);
+        if (head_aux) MXF_HIP(h, hipEventRecord(h->ev_pa, st));
+        if ((rc = update(pe, pe2 - pe, pe, pe2 - pe, c0, K, 1, st))) return rc;
+        if (head_aux) {
+            MXF_HIP(h, hipStreamWaitEvent(ax, h->ev_pa, 0));
+            if ((rc = update(pe2, n - pe2, pe, pe2 - pe, c0, K, 0, ax))) return rc;
+            MXF_HIP(h, hipEventRecord(h->ev_ph, ax));
+            pend.head = true;
+        } else {
+            if ((rc = update(pe2, n - pe2, pe, pe2 - pe, c0, K, 0, st))) return rc;
+            MXF_HIP(h, hipEventRecord(h->ev_pa, st));
+            MXF_HIP(h, hipStreamWaitEvent(ax, h->ev_pa, 0));
+        }
+        if ((rc = update(pe2, n - pe2, pe2, n - pe2, c0, K, 1, ax))) return rc;
+        MXF_HIP(h, hipEventRecord(h->ev_pb, ax));
+        pend.rest = true;
+        return 0;
+    }
+
+    // st waits for everything the call queued elsewhere: potrf_inv (records ev_pj there) and what is pending of potrf_aux.  (ev_ph is never
+    // pending here today: the last panel has no successor.)
+    int join() {
+        if (eager) {
+            MXF_HIP(h, hipEventRecord(h->ev_pj, h->potrf_inv));
+            MXF_HIP(h, hipStreamWaitEvent(st, h->ev_pj, 0));
+        }
+        int rc = wait_rest();
+        return rc ? rc : wait_head();
+    }
+};
+
+// Ie != nullptr: L^-1 may be formed into Ie next to the factorisation (PotrfPlan::eager); *eager_done tells the caller whether it was (else:
+// call trtri afterwards).
 template <typename T>
 int potrf_typed(mxf_ctx* h, int dtype, int S, int64_t n, T* A, int64_t lda, int64_t sA, int* info, hipStream_t st, bool zero_upper, bool zero_info,
                 T* Ie = nullptr, int64_t ldie = 0, bool* eager_done = nullptr) {
     if (eager_done) *eager_done = false;
     if (info && zero_info) MXF_HIP(h, hipMemsetAsync(info, 0, sizeof(int) * S, st));
-    // Look-ahead (n >= 2048): the trailing update after an outer panel is split into the part that touches the NEXT outer panel's columns
-    // (on the caller's stream, so that panel's latency-bound factorisation starts right away) and the rest (on an auxiliary stream, next to
-    // that factorisation).  At n = 8192 the 128 panel steps (85 us each) otherwise serialise with 3.7 ms of trailing GEMMs.
-    // float64: the tile kernel, one launch up to MXF_POTRF_ONE_MAX = 512, one per outer panel beyond; float32: the launch-per-panel form
-    // The tile kernel's workgroups hand tiles to each other through progress counters: every workgroup of a launch must be RESIDENT at once
-    // (one per CU: 256 threads at one wave per SIMD, ~76 KB of LDS), or a waiting workgroup could hold the CU its producer needs.  The grid
-    // (block rows x batch) is therefore bounded by the CU count of the device; larger problems take the launch-per-panel form below.
-    static const int ncu = [] { int dev = 0, v = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 64; return v; }();
-    const bool tiles_ok = sizeof(T) == 8 && n % NB == 0 && n >= 2 * NB && S <= 64;
-    if constexpr (sizeof(T) == 8) {
-        static const int one_max = MXF_KNOB("MXF_POTRF_ONE_MAX", 512);
-        if (tiles_ok && n <= one_max && (int64_t)(n / NB) * S <= ncu) {    // (n = 2048 as ONE left-looking launch: 2.6 ms vs 1.9 -- the last block rows carry 32 i^2 columns of products each)
-            const unsigned nbk = (unsigned)(n / NB);
-            int* progress = mxf_flags(h, (nbk + 1) * (unsigned)S);
-            if (!progress) MXF_FAIL(h, -4, "mxf_potrf: cannot allocate the workgroup hand-off counters");
-            double* pinv = mxf_potrf_inv(h, (size_t)nbk * S * 1024);
-            if (!pinv) MXF_FAIL(h, -4, "mxf_potrf: cannot allocate the inverse-block scratch");
-            hipLaunchKernelGGL(potrf_tiles_kernel, dim3(nbk, (unsigned)S), dim3(256), 0, st, A, lda, sA, (int64_t)0, (int)nbk, info, progress, pinv, 0, 0);
-            if (zero_upper) hipLaunchKernelGGL((zero_upper_kernel<T>), dim3((unsigned)((n + 255) / 256), (unsigned)n, S), dim3(256), 0, st, A, n, lda, sA);
-            MXF_LAUNCH_CHECK(h);
-            return 0;
-        }
+    PotrfCall<T> c{potrf_plan(h, sizeof(T), S, n, st, Ie != nullptr), h, dtype, A, lda, sA, info, st, Ie, ldie, {}};
+    int rc = 0;
+    for (int64_t c0 = 0, pe; c0 < n && !rc; c0 = pe) {
+        pe = c.panel_end(c0);
+        rc = c.panel_tiles ? c.factor_panel_tiles(c0) : c.factor_panel_columns(c0);
+        if (!rc && c.eager && c.fires_at(pe)) rc = c.eager_row_block(pe);
+        if (!rc && pe < n) rc = c.trailing_update(c0);
     }
-    const bool panel_tiles = tiles_ok && (int64_t)(n / NB) * S <= ncu;      // every block row's workgroup must be resident at once
-    static const int look_env = MXF_KNOB("MXF_POTRF_LOOKAHEAD", 2);
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(st, &cap);
-    const bool look = look_env && n >= 2048 && cap == hipStreamCaptureStatusNone && mxf_potrf_aux_init(h);
-    hipStream_t ax = look ? h->potrf_aux : st;
-    bool pending_b = false, pending_h = false;
-    // row blocks of FOUR outer panels (2048 rows), from four row blocks on.  Measured at n = 8192 (MAP step of the exact GP, two alternating rounds,
-    // profiles/r05_potrf_eager_inverse_ab.txt): off 15.0 ms; every panel 18.1 (208 more launches, and products of a few tiles each that hold CUs the
-    // chain's tile workgroups are waiting for); every second 14.6-14.7; every fourth 14.5; two halves 15.0; leaving the products 64 / 128 CUs less changes nothing
-    // r06: with the row blocks in split pieces (below) blocks of TWO panels are best: 14.10-14.15 ms against 14.42-14.44
-    // (four), 15.0 (three: ragged last block), 14.72 for the r05 form
-    static const int eager_env = MXF_KNOB("MXF_POTRF_EAGER_INV", 2);
-    const bool eager = Ie != nullptr && eager_env && sizeof(T) == 8 && S == 1 && panel_tiles && look && n % NBO == 0 && n >= 16 * NBO &&
-                       n >= 4 * (eager_env >= 100 ? n / 8 : (int64_t)eager_env * NBO);
-    static const int split_rows_g = MXF_KNOB("MXF_POTRF_SPLIT_ROWS", 64);
-    // does the outer panel at c0 take the split form (chain launch + rows-below launch)?
-    auto is_split = [&](int64_t c0_) {
-        const int64_t pe_ = (c0_ + NBO < n) ? c0_ + NBO : n;
-        const int64_t nbr_ = (n - c0_) / NB, npt_ = (pe_ - c0_) / NB;
-        return panel_tiles && split_rows_g > 0 && nbr_ - npt_ >= split_rows_g;
-    };
-    for (int64_t c0 = 0; c0 < n; c0 += NBO) {
-        const int64_t pe = (c0 + NBO < n) ? c0 + NBO : n;   // panel end
-        //  the auxiliary stream's head update of THIS panel's rows-below is consumed here unconditionally, whatever form the
-        // panel takes: the dependency must not hinge on is_split() implying the tile path.  In the split tile form the wait is deferred to
-        // just in front of the rows kernel (the chain launch reads the diagonal block only) -- `defer` below.
-        const bool defer_h = pending_h && sizeof(T) == 8 && panel_tiles && is_split(c0);
-        if (pending_h && !defer_h) { MXF_HIP(h, hipStreamWaitEvent(st, h->ev_ph, 0)); pending_h = false; }
-        if constexpr (sizeof(T) == 8) {
-            if (panel_tiles) {       // the whole outer panel in ONE launch (8 dependent panel steps + 7 left-looking GEMMs before)
-                const unsigned nbr = (unsigned)((n - c0) / NB), npt = (unsigned)((pe - c0) / NB);
-                // Many block rows below the panel: two launches -- the panel's own block rows (the latency chain, npt workgroups), then the
-                // rows below against the finished diagonal block, nothing to wait for (~90 us of MFMA work each).  In one launch those rows
-                // sit resident and mostly idle for the whole chain, one CU each, and the look-ahead GEMM next to them (whose 133 KB of LDS
-                // cannot share a CU with a tile workgroup) runs on what is left.
-                const bool split = is_split(c0);
-                const unsigned na = split ? npt : nbr;
-                int* progress = mxf_flags(h, (na + 1) * (unsigned)S);
-                if (!progress) MXF_FAIL(h, -4, "mxf_potrf: cannot allocate the workgroup hand-off counters");
-                double* pinv = mxf_potrf_inv(h, (size_t)npt * S * 1024);
-                if (!pinv) MXF_FAIL(h, -4, "mxf_potrf: cannot allocate the inverse-block scratch");
-                hipLaunchKernelGGL(potrf_tiles_kernel, dim3(na, (unsigned)S), dim3(256), 0, st, A, lda, sA, c0, (int)npt, info, progress, pinv, 0, 0);
-                // (the rows below this panel's diagonal block were updated on the auxiliary stream, next to the chain above)
-                if (pending_h) { MXF_HIP(h, hipStreamWaitEvent(st, h->ev_ph, 0)); pending_h = false; }
-                // r03: the rows below right-looking from registers, workgroups of 32 rows (see potrf_rows_kernel)
-                if (split) hipLaunchKernelGGL(potrf_rows_kernel, dim3((nbr - npt) * 2, (unsigned)S), dim3(512), 0, st, A, lda, sA, c0, (int)npt, (int)npt, (const double*)pinv);
-            }
-        }
-        // row block [rb0, pe) of L is final once the panel ending at pe has been factored (the rows above it in these columns are zero).  Row blocks
-        // of eager_rb outer panels (MXF_POTRF_EAGER_INV: 1 = every panel, 2 = every second, ..., 100 = two halves)
-        const int64_t rbw = eager_env >= 100 ? n / 2 : (int64_t)eager_env * NBO;
-        auto fires_at = [&](int64_t pe_) { return pe_ % rbw == 0 || pe_ == n; };
-        // r06: the row block's pieces separately (trtri_row_block_p1 / _p2).  When block b's panels end, its diagonal inverse goes to the third
-        // auxiliary stream, its p2 follows on the inverse stream, and p1 of block b + 1 -- whose inputs are complete at this point, four panels
-        // before that block is factored -- is queued right behind.  What is left behind the factorisation is the last block's diagonal inverse
-        // and p2 instead of its whole row block.
-        if (eager && fires_at(pe)) {
-            const int64_t rb0 = (pe - 1) / rbw * rbw;
-            MXF_HIP(h, hipEventRecord(h->ev_pi, st));
-            if constexpr (sizeof(T) == 8) {
-                hipStream_t qd = h->potrf_rows, qp = h->potrf_inv;
-                MXF_HIP(h, hipStreamWaitEvent(qd, h->ev_pi, 0));
-                int rc = trtri_typed<T>(h, dtype, 1, pe - rb0, A + rb0 * (lda + 1), lda, 0, Ie + rb0 * (ldie + 1), ldie, 0, qd);
-                if (rc) return rc;
-                MXF_HIP(h, hipEventRecord(h->ev_pc, qd));
-                MXF_HIP(h, hipStreamWaitEvent(qp, h->ev_pc, 0));       // (block 0: p1 of block 1 reads this inverse)
-                if (rb0 > 0) { rc = trtri_row_block_p2<T>(h, dtype, rb0, pe, Ie, ldie, qp); if (rc) return rc; }
-                if (pe < n) {
-                    MXF_HIP(h, hipStreamWaitEvent(qp, h->ev_pi, 0));   // the rows below the panel that just ended
-                    int64_t ne = pe + NBO;                           // the end of the next row block = the next firing point
-                    while (ne < n && !fires_at(ne)) ne += NBO;
-                    if (ne > n) ne = n;
-                    rc = trtri_row_block_p1<T>(h, dtype, pe, ne, A, lda, Ie, ldie, qp);
-                    if (rc) return rc;
-                }
-            }
-        }
-        for (int64_t j0 = c0; j0 < pe && !panel_tiles; j0 += NB) {
-            const int nb = (int)((j0 + NB < n) ? NB : n - j0);
-            if (j0 > c0) {   // left-looking update of block column j0 with the panel's previous block columns
-                int rc = mxf_gemm_internal(h, dtype, 0, 1, n - j0, nb, j0 - c0, -1.0, A + j0 * lda + c0, lda, sA,
-                                           A + j0 * lda + c0, lda, sA, 1.0, A + j0 * lda + j0, lda, sA, S, 0, st);
-                if (rc) return rc;
-            }
-            const int64_t below = n - (j0 + nb);
-            int* arrived = mxf_flags(h, (unsigned)S);
-            if (!arrived) MXF_FAIL(h, -4, "mxf_potrf: cannot allocate the workgroup hand-off counters");
-            hipLaunchKernelGGL((potrf_panel_kernel<T>), dim3((unsigned)(1 + (below + 127) / 128), S), dim3(128), 0, st, A, lda, sA, j0, nb, n, info,
-                               arrived);
-        }
-        if (pe < n) {   // trailing update, lower blocks only: A22 -= L21 L21^T with K = panel width
-            const int64_t pe2 = (pe + NBO < n) ? pe + NBO : n, K = pe - c0;
-            if (pending_b) { MXF_HIP(h, hipStreamWaitEvent(st, h->ev_pb, 0)); pending_b = false; }   // the previous rest-update touched these columns
-            if (!look || pe2 >= n) {
-                int rc = mxf_gemm_internal(h, dtype, 0, 1, n - pe, n - pe, K, -1.0, A + pe * lda + c0, lda, sA,
-                                           A + pe * lda + c0, lda, sA, 1.0, A + pe * lda + pe, lda, sA, S, 1, st);
-                if (rc) return rc;
-            } else {
-                // r03: when the NEXT panel takes the split form, only its diagonal block (what its chain launch reads) is updated on the caller's
-                // stream; the rows below it -- read by potrf_rows_kernel only, 0.2 ms later -- are updated on the auxiliary stream next to that
-                // chain (0.09 ms per panel off the serial path at n = 8192)
-                const bool head_aux = sizeof(T) == 8 && is_split(pe);
-                if (look_env != 2 || head_aux) MXF_HIP(h, hipEventRecord(h->ev_pa, st));  // the panel's columns (L21) are final
-                // next outer panel's columns: its diagonal block (lower) and the rows below it
-                int rc = mxf_gemm_internal(h, dtype, 0, 1, pe2 - pe, pe2 - pe, K, -1.0, A + pe * lda + c0, lda, sA,
-                                           A + pe * lda + c0, lda, sA, 1.0, A + pe * lda + pe, lda, sA, S, 1, st);
-                if (rc) return rc;
-                if (head_aux) {
-                    MXF_HIP(h, hipStreamWaitEvent(ax, h->ev_pa, 0));
-                    rc = mxf_gemm_internal(h, dtype, 0, 1, n - pe2, pe2 - pe, K, -1.0, A + pe2 * lda + c0, lda, sA,
-                                           A + pe * lda + c0, lda, sA, 1.0, A + pe2 * lda + pe, lda, sA, S, 0, ax);
-                    if (rc) return rc;
-                    MXF_HIP(h, hipEventRecord(h->ev_ph, ax));
-                    pending_h = true;
-                } else {
-                    rc = mxf_gemm_internal(h, dtype, 0, 1, n - pe2, pe2 - pe, K, -1.0, A + pe2 * lda + c0, lda, sA,
-                                           A + pe * lda + c0, lda, sA, 1.0, A + pe2 * lda + pe, lda, sA, S, 0, st);
-                    if (rc) return rc;
-                    if (look_env == 2) MXF_HIP(h, hipEventRecord(h->ev_pa, st));  // (2: the rest-update only starts once the head products are done)
-                    MXF_HIP(h, hipStreamWaitEvent(ax, h->ev_pa, 0));
-                }
-                // the rest on the auxiliary stream, next to the next panel's factorisation
-                rc = mxf_gemm_internal(h, dtype, 0, 1, n - pe2, n - pe2, K, -1.0, A + pe2 * lda + c0, lda, sA,
-                                       A + pe2 * lda + c0, lda, sA, 1.0, A + pe2 * lda + pe2, lda, sA, S, 1, ax);
-                if (rc) return rc;
-                MXF_HIP(h, hipEventRecord(h->ev_pb, ax));
-                pending_b = true;
-            }
-        }
-    }
-    if (eager) {
-        MXF_HIP(h, hipEventRecord(h->ev_pj, h->potrf_inv));
-        MXF_HIP(h, hipStreamWaitEvent(st, h->ev_pj, 0));
-        if (eager_done) *eager_done = true;
-    }
-    if (pending_b) MXF_HIP(h, hipStreamWaitEvent(st, h->ev_pb, 0));
-    if (pending_h) MXF_HIP(h, hipStreamWaitEvent(st, h->ev_ph, 0));      // (never pending here today: the last panel has no successor; kept so that the caller's stream always joins the auxiliary one)
+    if (!rc) rc = c.join();
+    if (rc) return rc;
+    if (eager_done) *eager_done = c.eager;
     if (n > 1 && zero_upper) {      // (internal callers that only ever read the lower triangle skip this pass)
         if (n > 65535) MXF_FAIL(h, -3, "mxf_potrf: n too large");
         hipLaunchKernelGGL((zero_upper_kernel<T>), dim3((unsigned)((n + 255) / 256), (unsigned)n, S), dim3(256), 0, st, A, n, lda, sA);
@@ -1142,65 +1227,6 @@ int mxf_trsm_internal(mxf_ctx* h, int dtype, int transpose, int S, int64_t n, in
     if (dtype == MXF_F64) return trsm_typed<double>(h, dtype, transpose, S, n, nrhs, (const double*)L, ldl, sL, (double*)B, ldb, sB, rhs_lower, st);
     MXF_FAIL(h, -2, "mxf_trsm: bad dtype %d", dtype);
 }
-
-namespace {
-
-template <typename T>
-__global__ void zero_block_kernel(T* __restrict__ P, int64_t rows, int64_t cols, int64_t ld, int64_t stride) {
-    T* p = P + (int64_t)blockIdx.y * stride;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows * cols; i += (int64_t)gridDim.x * blockDim.x)
-        p[(i / cols) * ld + (i % cols)] = (T)0;
-}
-
-// Log-depth blocked inverse of a lower-triangular matrix.  Level 0: all 64x64 diagonal blocks (one launch).  Level l merges pairs of
-// bs-blocks:  inv([L11 0; L21 L22]) = [I11 0; -I22 L21 I11, I22]  with two batched MFMA GEMMs; the temporary (L21 I11)^T lives in the
-// (unused, finally zeroed) upper-triangular mirror block of the output, so no extra workspace is needed.
-template <typename T>
-int trtri_typed(mxf_ctx* h, int dtype, int S, int64_t n, const T* L, int64_t ldl, int64_t sL, T* Li, int64_t ldi, int64_t sI, hipStream_t st) {
-    if (n > 65535) MXF_FAIL(h, -3, "mxf_trtri: n too large");
-    const int64_t nblk = (n + NB - 1) / NB;
-    hipLaunchKernelGGL((trtri_diag_kernel<T>), dim3((unsigned)nblk, S), dim3(64), 0, st, L, ldl, sL, Li, ldi, sI, n);
-    for (int64_t bs = NB; bs < n; bs *= 2) {
-        const int64_t npairs_full = n / (2 * bs);                 // pairs whose second block is complete
-        const int64_t rem0 = npairs_full * 2 * bs;                  // start of a possible ragged last pair
-        for (int s = 0; s < S; ++s) {
-            const T* Ls = L + (int64_t)s * sL;
-            T* Is = Li + (int64_t)s * sI;
-            if (npairs_full > 0) {
-                const int64_t stL = 2 * bs * (ldl + 1), stI = 2 * bs * (ldi + 1);
-                // tmpT (bs x bs, in the upper mirror block) = I11^T L21^T
-                // (both products have a triangular left operand: from TRI_MIN-wide blocks on only the non-zero k range of each row tile is
-                //  multiplied -- trtri(8192) 6.9 -> 5.0 ms; the small levels keep the plain split-K products, which fill the chip better)
-                int rc = mxf_gemm_internal(h, dtype, 1, 1, bs, bs, bs, 1.0, Is, ldi, stI, Ls + bs * ldl, ldl, stL, 0.0, Is + bs, ldi, stI,
-                                           (int)npairs_full, 0, st, 0, bs >= TRI_MIN ? 1 : 0);
-                if (rc) return rc;
-                // X21 = -I22 tmpT^T
-                rc = mxf_gemm_internal(h, dtype, 0, 1, bs, bs, bs, -1.0, Is + bs * (ldi + 1), ldi, stI, Is + bs, ldi, stI, 0.0, Is + bs * ldi, ldi,
-                                       stI, (int)npairs_full, 0, st, 0, bs >= TRI_MIN ? 2 : 0);
-                if (rc) return rc;
-                // the scratch blocks become part of the next level's I11 operand: they must be zero again
-                hipLaunchKernelGGL((zero_block_kernel<T>), dim3((unsigned)((bs * bs + 255) / 256 > 1024 ? 1024 : (bs * bs + 255) / 256), (unsigned)npairs_full),
-                                   dim3(256), 0, st, Is + bs, bs, bs, ldi, stI);
-            }
-            const int64_t b2 = n - rem0 - bs;                       // rows of the ragged second block of the last pair (if any)
-            if (rem0 < n && b2 > 0) {
-                const T* Lp = Ls + rem0 * (ldl + 1);
-                T* Ip = Is + rem0 * (ldi + 1);
-                int rc = mxf_gemm_internal(h, dtype, 1, 1, bs, b2, bs, 1.0, Ip, ldi, 0, Lp + bs * ldl, ldl, 0, 0.0, Ip + bs, ldi, 0, 1, 0, st, 0, bs >= TRI_MIN ? 1 : 0);
-                if (rc) return rc;
-                rc = mxf_gemm_internal(h, dtype, 0, 1, b2, bs, b2, -1.0, Ip + bs * (ldi + 1), ldi, 0, Ip + bs, ldi, 0, 0.0, Ip + bs * ldi, ldi, 0, 1, 0, st, 0, bs >= TRI_MIN ? 2 : 0);
-                if (rc) return rc;
-                hipLaunchKernelGGL((zero_block_kernel<T>), dim3((unsigned)((bs * b2 + 255) / 256 > 1024 ? 1024 : (bs * b2 + 255) / 256), 1), dim3(256), 0, st,
-                                   Ip + bs, bs, b2, ldi, (int64_t)0);
-            }
-        }
-    }
-    if (n > 1) hipLaunchKernelGGL((zero_upper_kernel<T>), dim3((unsigned)((n + 255) / 256), (unsigned)n, S), dim3(256), 0, st, Li, n, ldi, sI);
-    MXF_LAUNCH_CHECK(h);
-    return 0;
-}
-
-}  // namespace
 
 int mxf_trtri_internal(mxf_ctx* h, int dtype, int S, int64_t n, const void* L, int64_t ldl, int64_t sL, void* Linv, int64_t ldi,
                        int64_t sI, hipStream_t st) {

@@ -64,6 +64,10 @@ enum { MXF_T_PLANES_A = 0, MXF_T_PSI2 = 1, MXF_T_PLANES_B = 2, MXF_T_TGEMM = 3, 
 #define MXF_T0(h, i, s) do { if ((h)->tm.on) { (void)hipEventRecord((h)->tm.ev[2 * (i)], s); (h)->tm.used[i] = true; } } while (0)
 #define MXF_T1(h, i, s) do { if ((h)->tm.on) (void)hipEventRecord((h)->tm.ev[2 * (i) + 1], s); } while (0)
 
+// A device buffer grown on demand (mxf_grow) and a rotating ring of zeroed 32-bit counters (mxf_ring_take).
+struct mxf_buf { void* p = nullptr; size_t bytes = 0; };
+struct mxf_ring { unsigned* p = nullptr; unsigned cursor = 0; };
+
 struct mxf_ctx {
     mxf_timing tm;
 #ifdef MXF_PROBES
@@ -71,37 +75,36 @@ struct mxf_ctx {
 #endif
     int device = 0;
     std::string err;
-    void* ws = nullptr;     // scratch, grown on demand (hipMalloc; never inside graph capture)
-    size_t ws_bytes = 0;
-    hipStream_t side = nullptr;   // internal side streams: independent chains of the SVGP step run concurrently
-    hipStream_t side2 = nullptr;
-    hipStream_t potrf_aux = nullptr;                        // look-ahead stream of the blocked Cholesky (chol.hip)
-    bool potrf_aux_ready = false;                           // set only when EVERY auxiliary stream and event below exists
-    hipEvent_t ev_pa = nullptr, ev_pb = nullptr, ev_ph = nullptr;
-    hipStream_t potrf_inv = nullptr;                        // r05: the inverse of the factor, row block by row block NEXT TO the factorisation (chol.hip)
-    hipEvent_t ev_pi = nullptr, ev_pj = nullptr;
-    hipStream_t potrf_rows = nullptr;                       // r06: the rows FAR below an outer panel are solved here, next to the next panel's chain
-    hipEvent_t ev_pc = nullptr, ev_rb = nullptr;
+    // Scratch, never allocated inside a graph capture; mxf_each_buf lists them for mxf_workspace_bytes and mxf_destroy.
+    mxf_buf ws;                // general scratch (mxf_ws)
+    mxf_buf gram_ws;           // pre-scaled coordinates of mxf_gram (separate: composites hold `ws` while calling mxf_gram)
+    mxf_buf bwd_acc;           // MFMA reverse pass (gram_bwd.hip): float64 row-side sums [M][16] + 16, scaled coordinates
+    mxf_buf pinv;              // ring of 16 x 16 diagonal-block inverses handed from the factoring to the solving workgroups of potrf_tiles_kernel
+    size_t pinv_cursor = 0;    // (in doubles)
+    int64_t ws_generation = 0; // bumped whenever one of the buffers above is (re-)allocated: device pointers baked into a captured hipGraph are stale after that
+    // Internal streams and their events, created on first use, all of a set or none (mxf_side_set / mxf_potrf_set below).
+    bool side_ready = false;                        // the SVGP step's independent chains run concurrently (composite.hip)
+    hipStream_t side = nullptr, side2 = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_aux = nullptr, ev_aux2 = nullptr, ev_su = nullptr;
-    hipEvent_t ev_k1 = nullptr, ev_k3 = nullptr;   // r06: the SVGP call's condition norms and value scalars leave the caller's stream (composite.hip)
-    void* gram_ws = nullptr;   // pre-scaled coordinates of mxf_gram (separate: composites hold `ws` while calling mxf_gram)
-    size_t gram_ws_bytes = 0;
-    int64_t ws_generation = 0; // bumped whenever `ws` / `gram_ws` is freed and re-allocated: device pointers baked into a captured hipGraph are stale after that
+    hipEvent_t ev_k1 = nullptr, ev_k3 = nullptr;    // the SVGP call's condition norms and value scalars leave the caller's stream
+    bool potrf_aux_ready = false;                   // the blocked Cholesky (chol.hip: PotrfCall's stages say who records and waits on what)
+    hipStream_t potrf_aux = nullptr;                // look-ahead: the trailing update next to the next panel's factorisation
+    hipEvent_t ev_pa = nullptr, ev_pb = nullptr, ev_ph = nullptr;
+    hipStream_t potrf_inv = nullptr;                // eager inverse: the products of its row blocks
+    hipStream_t potrf_inv_diag = nullptr;           // eager inverse: the inverses of its diagonal blocks (latency-bound small launches)
+    hipEvent_t ev_pi = nullptr, ev_pj = nullptr, ev_pc = nullptr;
     double* cond_dev = nullptr; // [ |Kuu + jitter I|_1, |(Kuu + jitter I)^-1|_1 ] of the last SVGP training call (mxf_svgp_last_cond)
     double* cond_host = nullptr; // pinned, device-visible host words, MXF_COND_SLOTS x [running MAX, last] of the condition numbers the training calls published into their slot (mxf_svgp_cond_nowait / mxf_svgp_cond_slot)
     int svgp_form = 0;         // float32 streaming form of the next SVGP training calls (mxf_svgp_configure): 0 explicit inverse, 1 whitened
     int cond_slot = 0;         // the slot the next SVGP training calls publish their condition number into
-    void* bwd_acc = nullptr;   // scratch of the MFMA reverse pass (gram_bwd.hip): float64 row-side sums [M][16] + 16, scaled coordinates
-    size_t bwd_acc_bytes = 0;
     void* comm = nullptr;      // RCCL communicator of mxf_comm_init (comm.hip); nullptr on single-GPU handles
     int comm_nranks = 0, comm_rank = -1;
-    double* pinv = nullptr;    // ring of 16 x 16 diagonal-block inverses handed from the factoring to the solving workgroups of potrf_tiles_kernel
-    size_t pinv_elems = 0, pinv_cursor = 0;
-    int* flags = nullptr;      // zero-initialised arrival counters for in-kernel workgroup hand-offs (potrf panel); each use leaves 0 behind
-    unsigned flag_cursor = 0;
-    unsigned* gsync = nullptr; // zero-initialised rendezvous counters of the wide split GEMMs (pacing hints only; gemm_split.hip); each use leaves 0 behind
-    unsigned gsync_cursor = 0;
+    mxf_ring flags;            // arrival counters for in-kernel workgroup hand-offs (potrf panel); each use leaves 0 behind
+    mxf_ring gsync;            // rendezvous counters of the wide split GEMMs (pacing hints only; gemm_split.hip); each use leaves 0 behind
 };
+template <typename F> static inline void mxf_each_buf(mxf_ctx* h, F f) { for (mxf_buf* b : {&h->ws, &h->gram_ws, &h->bwd_acc, &h->pinv}) f(*b); }
+template <typename F> static inline void mxf_each_ring(mxf_ctx* h, F f) { for (mxf_ring* r : {&h->flags, &h->gsync}) f(*r); }
+
 constexpr int MXF_COND_SLOTS = 64;
 // the condition words of the SVGP training call: device accumulators + the pinned host slots (allocated on first use)
 static inline bool mxf_cond_init(mxf_ctx* h) {
@@ -115,47 +118,50 @@ static inline bool mxf_cond_init(mxf_ctx* h) {
     }
     return true;
 }
-constexpr unsigned MXF_NGSYNC = 1u << 18;
-// a fresh run of `count` zeroed rendezvous counters (rotating: a run is reused only after 2^18 / count later launches have been queued --
-// by then the launch that used it has long left them at zero); nullptr = none available (the caller then launches without rendezvous)
-static inline unsigned* mxf_gsync(mxf_ctx* h, unsigned count) {
-    if (count == 0 || count > MXF_NGSYNC / 4) return nullptr;
-    if (!h->gsync) {
-        if (hipMalloc((void**)&h->gsync, MXF_NGSYNC * sizeof(unsigned)) != hipSuccess) { h->gsync = nullptr; return nullptr; }
-        if (hipMemset(h->gsync, 0, MXF_NGSYNC * sizeof(unsigned)) != hipSuccess) return nullptr;
+
+// A fresh run of `count` zeroed counters from a ring of 2^18 (rotating: a run is reused only after 2^18 / count later launches have been
+// queued -- by then the launch that used it has long left them at zero); nullptr = none available.
+constexpr unsigned MXF_NRING = 1u << 18;
+static inline unsigned* mxf_ring_take(mxf_ring& r, unsigned count) {
+    if (!r.p) {
+        if (hipMalloc((void**)&r.p, MXF_NRING * sizeof(unsigned)) != hipSuccess) { r.p = nullptr; return nullptr; }
+        if (hipMemset(r.p, 0, MXF_NRING * sizeof(unsigned)) != hipSuccess) { (void)hipFree(r.p); r.p = nullptr; return nullptr; }
     }
-    if (h->gsync_cursor + count > MXF_NGSYNC) h->gsync_cursor = 0;
-    unsigned* p = h->gsync + h->gsync_cursor;
-    h->gsync_cursor += count;
+    if (count > MXF_NRING) return nullptr;
+    if (r.cursor + count > MXF_NRING) r.cursor = 0;
+    unsigned* p = r.p + r.cursor;
+    r.cursor += count;
     return p;
 }
-constexpr unsigned MXF_NFLAGS = 1u << 18;
-// a fresh run of `count` zeroed counters (rotating; a slot is reused only after 2^18 / count later launches have been queued)
-static inline int* mxf_flags(mxf_ctx* h, unsigned count) {
-    if (!h->flags) {
-        if (hipMalloc((void**)&h->flags, MXF_NFLAGS * sizeof(int)) != hipSuccess) { h->flags = nullptr; return nullptr; }
-        if (hipMemset(h->flags, 0, MXF_NFLAGS * sizeof(int)) != hipSuccess) return nullptr;
-    }
-    if (count > MXF_NFLAGS) return nullptr;
-    if (h->flag_cursor + count > MXF_NFLAGS) h->flag_cursor = 0;
-    int* p = h->flags + h->flag_cursor;
-    h->flag_cursor += count;
-    return p;
+// hand-off counters: the caller fails without them
+static inline int* mxf_flags(mxf_ctx* h, unsigned count) { return (int*)mxf_ring_take(h->flags, count); }
+// rendezvous counters: without them (or for a run longer than a quarter of the ring) the caller launches without rendezvous
+static inline unsigned* mxf_gsync(mxf_ctx* h, unsigned count) { return count == 0 || count > MXF_NRING / 4 ? nullptr : mxf_ring_take(h->gsync, count); }
+
+// At least `need` bytes in `b`.  A buffer that is too small is freed -- after a device synchronise: queued launches may still use it -- and
+// `want` >= need bytes are allocated (each buffer has its own head-room rule); every (re-)allocation bumps ws_generation.  nullptr: out of memory.
+static inline void* mxf_grow(mxf_ctx* h, mxf_buf& b, size_t need, size_t want) {
+    if (need <= b.bytes) return b.p;
+    if (b.p) { (void)hipDeviceSynchronize(); (void)hipFree(b.p); b = mxf_buf(); }
+    ++h->ws_generation;
+    if (hipMalloc(&b.p, want) != hipSuccess) { b.p = nullptr; return nullptr; }
+    b.bytes = want;
+    return b.p;
 }
+// scratch allocator: returns a pointer valid until the next call that needs more
+static inline void* mxf_ws(mxf_ctx* h, size_t bytes) { return mxf_grow(h, h->ws, bytes, bytes + (bytes >> 2) + (1u << 20)); }
+static inline void* mxf_gram_ws(mxf_ctx* h, size_t bytes) { return mxf_grow(h, h->gram_ws, bytes, bytes + (bytes >> 2) + (1u << 16)); }
 
 // ring allocator of the Cholesky tile kernel's inverse blocks: the ring holds at least two regions of the largest request, so a region is
 // reused no earlier than the launch after next ON THE SAME STREAM -- by then its readers (the previous launch) have finished in stream order.
 // (Two streams factoring through ONE handle would share the ring: the C ABI's rule is one handle per thread and calls not re-entrant.)
 static inline double* mxf_potrf_inv(mxf_ctx* h, size_t elems) {
-    if (elems * 2 > h->pinv_elems) {
-        if (h->pinv) { (void)hipDeviceSynchronize(); (void)hipFree(h->pinv); h->pinv = nullptr; h->pinv_elems = 0; }
-        size_t want = elems * 4 > ((size_t)4 << 20) ? elems * 4 : ((size_t)4 << 20);      // >= 32 MB
-        if (hipMalloc((void**)&h->pinv, want * sizeof(double)) != hipSuccess) { h->pinv = nullptr; return nullptr; }
-        h->pinv_elems = want; h->pinv_cursor = 0;
-        ++h->ws_generation;
-    }
-    if (h->pinv_cursor + elems > h->pinv_elems) h->pinv_cursor = 0;
-    double* p = h->pinv + h->pinv_cursor;
+    const size_t have = h->pinv.bytes;
+    const size_t want = elems * 4 > ((size_t)4 << 20) ? elems * 4 : ((size_t)4 << 20);      // >= 32 MB
+    double* ring = (double*)mxf_grow(h, h->pinv, elems * 2 * sizeof(double), want * sizeof(double));
+    if (!ring) return nullptr;
+    if (h->pinv.bytes != have /* a new ring */ || h->pinv_cursor + elems > h->pinv.bytes / sizeof(double)) h->pinv_cursor = 0;
+    double* p = ring + h->pinv_cursor;
     h->pinv_cursor += elems;
     return p;
 }
@@ -182,77 +188,30 @@ static inline double* mxf_potrf_inv(mxf_ctx* h, size_t elems) {
             MXF_FAIL(h, -100 - (int)_e, "%s:%d kernel launch -> %s", __FILE__, __LINE__, hipGetErrorString(_e)); \
     } while (0)
 
-// scratch allocator: returns a pointer valid until the next call that needs more
-static inline void* mxf_ws(mxf_ctx* h, size_t bytes) {
-    if (bytes <= h->ws_bytes) return h->ws;
-    if (h->ws) {
-        (void)hipDeviceSynchronize();
-        (void)hipFree(h->ws);
-        h->ws = nullptr;
-        h->ws_bytes = 0;
-    }
-    ++h->ws_generation;
-    size_t want = bytes + (bytes >> 2) + (1u << 20);
-    if (hipMalloc(&h->ws, want) != hipSuccess) {
-        h->ws = nullptr;
-        return nullptr;
-    }
-    h->ws_bytes = want;
-    return h->ws;
+// The handle's internal streams and events in sets that exist as a whole or not at all: mxf_async_init creates a set (a failure rolls back
+// what it had created, and a later call tries again), mxf_destroy releases the same lists.  Unused trailing slots are nullptr.
+struct mxf_async_set { bool* ready; hipStream_t* streams[3]; hipEvent_t* events[8]; };
+static inline mxf_async_set mxf_side_set(mxf_ctx* h) {
+    return {&h->side_ready, {&h->side, &h->side2}, {&h->ev_fork, &h->ev_join, &h->ev_join2, &h->ev_aux, &h->ev_aux2, &h->ev_su, &h->ev_k1, &h->ev_k3}};
 }
-
-static inline bool mxf_potrf_aux_init(mxf_ctx* h) {
-    if (h->potrf_aux_ready) return true;
-    // all or nothing: a partial failure leaves NO auxiliary stream / event behind (the callers gate look-ahead on the return value)
-    bool ok = hipStreamCreateWithFlags(&h->potrf_aux, hipStreamNonBlocking) == hipSuccess;
-    if (!ok) h->potrf_aux = nullptr;
-    ok = ok && hipStreamCreateWithFlags(&h->potrf_inv, hipStreamNonBlocking) == hipSuccess;
-    if (!ok) h->potrf_inv = nullptr;
-    ok = ok && hipStreamCreateWithFlags(&h->potrf_rows, hipStreamNonBlocking) == hipSuccess;
-    if (!ok) h->potrf_rows = nullptr;
-    hipEvent_t* evs[] = {&h->ev_pa, &h->ev_pb, &h->ev_ph, &h->ev_pi, &h->ev_pj, &h->ev_pc, &h->ev_rb};
-    for (hipEvent_t* e : evs)
-        if (ok && hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) { *e = nullptr; ok = false; }
-    if (!ok) {
-        for (hipEvent_t* e : evs) if (*e) { (void)hipEventDestroy(*e); *e = nullptr; }
-        if (h->potrf_rows) { (void)hipStreamDestroy(h->potrf_rows); h->potrf_rows = nullptr; }
-        if (h->potrf_inv) { (void)hipStreamDestroy(h->potrf_inv); h->potrf_inv = nullptr; }
-        if (h->potrf_aux) { (void)hipStreamDestroy(h->potrf_aux); h->potrf_aux = nullptr; }
-        return false;
-    }
-    h->potrf_aux_ready = true;
-    return true;
+static inline mxf_async_set mxf_potrf_set(mxf_ctx* h) {
+    return {&h->potrf_aux_ready, {&h->potrf_aux, &h->potrf_inv, &h->potrf_inv_diag}, {&h->ev_pa, &h->ev_pb, &h->ev_ph, &h->ev_pi, &h->ev_pj, &h->ev_pc}};
 }
-
-static inline bool mxf_side_init(mxf_ctx* h) {
-    if (h->side) return true;
-    if (hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking) != hipSuccess) { h->side = nullptr; return false; }
-    if (hipStreamCreateWithFlags(&h->side2, hipStreamNonBlocking) != hipSuccess) { h->side2 = nullptr; return false; }
-    if (hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_join2, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_aux, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_aux2, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_su, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_k1, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_k3, hipEventDisableTiming) != hipSuccess) return false;
-    return true;
+static inline void mxf_async_release(const mxf_async_set& g) {
+    for (hipEvent_t* e : g.events) if (e && *e) { (void)hipEventDestroy(*e); *e = nullptr; }
+    for (hipStream_t* s : g.streams) if (s && *s) { (void)hipStreamDestroy(*s); *s = nullptr; }
+    *g.ready = false;
 }
-
-static inline void* mxf_gram_ws(mxf_ctx* h, size_t bytes) {
-    if (bytes <= h->gram_ws_bytes) return h->gram_ws;
-    if (h->gram_ws) {
-        (void)hipDeviceSynchronize();
-        (void)hipFree(h->gram_ws);
-        h->gram_ws = nullptr;
-        h->gram_ws_bytes = 0;
-    }
-    ++h->ws_generation;
-    size_t want = bytes + (bytes >> 2) + (1u << 16);
-    if (hipMalloc(&h->gram_ws, want) != hipSuccess) { h->gram_ws = nullptr; return nullptr; }
-    h->gram_ws_bytes = want;
-    return h->gram_ws;
+static inline bool mxf_async_init(const mxf_async_set& g) {
+    if (*g.ready) return true;
+    bool ok = true;
+    for (hipStream_t* s : g.streams) if (s && ok && hipStreamCreateWithFlags(s, hipStreamNonBlocking) != hipSuccess) { *s = nullptr; ok = false; }
+    for (hipEvent_t* e : g.events) if (e && ok && hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) { *e = nullptr; ok = false; }
+    if (!ok) mxf_async_release(g);
+    return *g.ready = ok;
 }
+static inline bool mxf_side_init(mxf_ctx* h) { return mxf_async_init(mxf_side_set(h)); }
+static inline bool mxf_potrf_aux_init(mxf_ctx* h) { return mxf_async_init(mxf_potrf_set(h)); }
 
 static inline size_t mxf_esize(int dtype) { return dtype == MXF_F64 ? 8 : 4; }
 static inline size_t mxf_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }

@@ -19,42 +19,25 @@ extern "C" int mxf_create(int device, mxf_handle* out) {
 extern "C" int mxf_destroy(mxf_handle h) {
     if (!h) return -1;
     mxf_comm_release(h);
-    if (h->ws) (void)hipFree(h->ws);
-    if (h->gram_ws) (void)hipFree(h->gram_ws);
-    if (h->flags) (void)hipFree(h->flags);
-    if (h->gsync) (void)hipFree(h->gsync);
-    if (h->pinv) (void)hipFree(h->pinv);
+    mxf_each_buf(h, [](mxf_buf& b) { if (b.p) (void)hipFree(b.p); });
+    mxf_each_ring(h, [](mxf_ring& r) { if (r.p) (void)hipFree(r.p); });
     if (h->tm.made) for (int i = 0; i < 2 * MXF_NT; ++i) (void)hipEventDestroy(h->tm.ev[i]);
     if (h->cond_dev) (void)hipFree(h->cond_dev);
     if (h->cond_host) (void)hipHostFree(h->cond_host);
-    if (h->bwd_acc) (void)hipFree(h->bwd_acc);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    if (h->ev_join2) (void)hipEventDestroy(h->ev_join2);
-    if (h->ev_aux) (void)hipEventDestroy(h->ev_aux);
-    if (h->ev_aux2) (void)hipEventDestroy(h->ev_aux2);
-    if (h->ev_su) (void)hipEventDestroy(h->ev_su);
-    if (h->ev_k1) (void)hipEventDestroy(h->ev_k1);
-    if (h->ev_k3) (void)hipEventDestroy(h->ev_k3);
-    if (h->side) (void)hipStreamDestroy(h->side);
-    if (h->side2) (void)hipStreamDestroy(h->side2);
-    if (h->potrf_aux) (void)hipStreamDestroy(h->potrf_aux);
-    if (h->ev_pa) (void)hipEventDestroy(h->ev_pa);
-    if (h->ev_pb) (void)hipEventDestroy(h->ev_pb);
-    if (h->ev_ph) (void)hipEventDestroy(h->ev_ph);
-    if (h->potrf_inv) (void)hipStreamDestroy(h->potrf_inv);
-    if (h->ev_pi) (void)hipEventDestroy(h->ev_pi);
-    if (h->ev_pj) (void)hipEventDestroy(h->ev_pj);
-    if (h->potrf_rows) (void)hipStreamDestroy(h->potrf_rows);
-    if (h->ev_pc) (void)hipEventDestroy(h->ev_pc);
-    if (h->ev_rb) (void)hipEventDestroy(h->ev_rb);
+    mxf_async_release(mxf_side_set(h));
+    mxf_async_release(mxf_potrf_set(h));
     delete h;
     return 0;
 }
 
 extern "C" const char* mxf_last_error(mxf_handle h) { return h ? h->err.c_str() : "null handle"; }
 
-extern "C" int64_t mxf_workspace_bytes(mxf_handle h) { return h ? (int64_t)(h->ws_bytes + h->gram_ws_bytes + h->bwd_acc_bytes + h->pinv_elems * sizeof(double)) : -1; }
+extern "C" int64_t mxf_workspace_bytes(mxf_handle h) {
+    if (!h) return -1;
+    size_t sum = 0;
+    mxf_each_buf(h, [&](mxf_buf& b) { sum += b.bytes; });
+    return (int64_t)sum;
+}
 
 extern "C" int64_t mxf_workspace_generation(mxf_handle h) { return h ? h->ws_generation : -1; }
 

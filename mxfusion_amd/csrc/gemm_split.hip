@@ -961,7 +961,7 @@ int mxf_gemm_split_internal(mxf_ctx* h, int64_t M, int64_t N, int64_t K, double 
             const int64_t trips = kchunk / 3;
             int64_t period = sync_period_env;
             int64_t slots_per = trips / period;
-            while (slots_per * splitk > (int64_t)(MXF_NGSYNC / 8)) { period *= 2; slots_per = trips / period; }
+            while (slots_per * splitk > (int64_t)(MXF_NRING / 8)) { period *= 2; slots_per = trips / period; }
             if (slots_per >= 1) {
                 g.sync = mxf_gsync(h, (unsigned)(slots_per * splitk));
                 g.sync_n = (int)tiles; g.sync_period = (int)period; g.sync_slots = (int)slots_per;

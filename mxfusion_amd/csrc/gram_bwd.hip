@@ -1027,17 +1027,15 @@ int launch_mfma(mxf_ctx* h, int kind, int64_t M, int64_t SB, int64_t B, int Q, c
                 const unsigned* h0max, const unsigned* tmax) {
     const size_t nacc = ((size_t)M * 16 + 16) * sizeof(double);                                    // bytes, zeroed every call
     const size_t need = nacc + (((size_t)M + (size_t)SB) * 8 + (size_t)SB) * sizeof(float);        // + the scaled coordinates and |x_n|^2
-    if (need > h->bwd_acc_bytes) {
+    if (need > h->bwd_acc.bytes) {
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         (void)hipStreamIsCapturing(st, &cap);
         if (cap != hipStreamCaptureStatusNone) MXF_FAIL(h, -4, "svgp reverse pass: scratch must be allocated before a stream capture (run one eager step first)");
-        if (h->bwd_acc) { (void)hipDeviceSynchronize(); (void)hipFree(h->bwd_acc); h->bwd_acc = nullptr; h->bwd_acc_bytes = 0; ++h->ws_generation; }
-        if (hipMalloc((void**)&h->bwd_acc, need) != hipSuccess) { h->bwd_acc = nullptr; MXF_FAIL(h, -4, "svgp reverse pass: cannot allocate %zu bytes", need); }
-        h->bwd_acc_bytes = need;
+        if (!mxf_grow(h, h->bwd_acc, need, need)) MXF_FAIL(h, -4, "svgp reverse pass: cannot allocate %zu bytes", need);
     }
-    MXF_HIP(h, hipMemsetAsync(h->bwd_acc, 0, nacc, st));
-    double* zacc = reinterpret_cast<double*>(h->bwd_acc);
-    float* Zs = reinterpret_cast<float*>(reinterpret_cast<char*>(h->bwd_acc) + nacc);
+    MXF_HIP(h, hipMemsetAsync(h->bwd_acc.p, 0, nacc, st));
+    double* zacc = reinterpret_cast<double*>(h->bwd_acc.p);
+    float* Zs = reinterpret_cast<float*>(reinterpret_cast<char*>(h->bwd_acc.p) + nacc);
     float* Xs = Zs + (size_t)M * 8;
     float* Xn = Xs + (size_t)SB * 8;
     const float cs = kind == MXF_K_RBF ? 0.84932180028801904272f : 1.f;      // RBF: exp(-r2 / 2) = 2^-(cs^2 r2), the bare v_exp_f32 in the pass
