@@ -1220,18 +1220,19 @@ struct SvgpCall : SvgpPlan {
         const int64_t KA = (ka_req > 0 && ka_req < SB) ? ka_req / 32 * 32 : (ka_req > 0 ? SB : 0);
         MXF_T0(h, MXF_T_PSI2, sd_);
         if (use_split) {
+            const MxfSplitScale kuf2 = {.alpha = (double)split_ga * split_ga, .ad0 = split_var, .pow0 = 2};      // both operands are Kuf planes: k / variance 2^14
             if (KA > 0) {
                 // 4 workgroups of the two-term kernel fit a CU: (256 - 202) * 4 = 216 workgroups = one per CU on 216 CUs.  One-planes path:
                 // (256 - 214) * 4 = 168 workgroups -- the chains are alone on what Psi2 leaves, and 88 CUs serve the few-sample step better than 40
                 // (same box, 4 samples: 4.30 -> 4.21 ms; 210: 4.25-4.32, 218: 4.22-4.26, 224: 4.27; configs[3] at 4 samples 2.41 -> 2.37)
-                rc = mxf_gemm_split_internal(h, M, M, KA, (double)split_ga * split_ga, plKuf, (int64_t)pl_big, plKuf, (int64_t)pl_big, 0.0, (float*)Psi2, M, 1, sd_,
-                                             psi2_ra_env ? psi2_ra : (bt_path ? 214 : 202), split_mode, split_var, 2, nullptr);
+                rc = mxf_gemm_split_internal(h, sd_, split_mode, M, M, KA, kuf2, {plKuf, (int64_t)pl_big}, {plKuf, (int64_t)pl_big},
+                                             {.C = (float*)Psi2, .ldc = M, .lower_only = 1}, {.reserve_cus = psi2_ra_env ? psi2_ra : (bt_path ? 214 : 202)});
                 if (rc) return rc;
             }
             if (KA < SB) {
                 const unsigned short* pk = plKuf + (KA / 16) * M * 16;
-                rc = mxf_gemm_split_internal(h, M, M, SB - KA, (double)split_ga * split_ga, pk, (int64_t)pl_big, pk, (int64_t)pl_big, KA > 0 ? 1.0 : 0.0, (float*)Psi2, M, 1, sd_,
-                                             rb_phase_b, split_mode, split_var, 2, nullptr);
+                rc = mxf_gemm_split_internal(h, sd_, split_mode, M, M, SB - KA, kuf2, {pk, (int64_t)pl_big}, {pk, (int64_t)pl_big},
+                                             {.C = (float*)Psi2, .ldc = M, .beta = KA > 0 ? 1.0 : 0.0, .lower_only = 1}, {.reserve_cus = rb_phase_b});
                 if (rc) return rc;
             }
         } else {
@@ -1299,9 +1300,11 @@ struct SvgpCall : SvgpPlan {
         // (few samples per GPU: the Kuu chain on the caller's stream is the critical path -- both side-stream products leave it 40 CUs)
         const bool few = SB <= 2 * 192 * M;
         const bool vt = !bt_wh, u1 = vt && P == 1;      // (bt_wh: planes of V only -- T and U come from them, gemm_bt.hip)
-        rc = mxf_gemm_split_internal(h, M, SB, M, 1.0, plLi, (int64_t)pl_h0, plKfu, (int64_t)pl_big, 0.0, nullptr, SB, 0, sd_, few ? 40 : 0, split_mode, sigf, 1,
-                                     (const unsigned*)limax, nullptr, 0, nullptr, plKuf, (int64_t)pl_big, 1, vt ? plVt : nullptr, vt ? pVt : 0,
-                                     u1 ? (const float*)aT : nullptr, u1 ? upart : nullptr);
+        MxfSplitOut v = {.planes = plKuf, .pstride = (int64_t)pl_big, .a_lower = 1};
+        if (vt) { v.planes_t = plVt; v.pstride_t = pVt; }
+        if (u1) { v.avec = (const float*)aT; v.Upart = upart; }
+        rc = mxf_gemm_split_internal(h, sd_, split_mode, M, SB, M, {.alpha = 1.0, .ad0 = sigf, .pow0 = 1}, {plLi, (int64_t)pl_h0, (const unsigned*)limax},
+                                     {plKfu, (int64_t)pl_big}, v, {.reserve_cus = few ? 40 : 0});
         if (rc) return rc;
         MXF_T1(h, MXF_T_VGEMM, sd_);
         MXF_STAGE(h, "V = Linv Kuf (sd)", sd_);
@@ -1319,8 +1322,9 @@ struct SvgpCall : SvgpPlan {
         MXF_HIP(h, hipEventRecord(h->ev_aux, sd_));      // V^T planes and U ready: the T GEMM / the reverse pass wait for it
         // Phi = V V^T (lower tiles, split-K) = sigma^2 2^-28 (planes)(planes)^T
         MXF_T0(h, MXF_T_PSI2, sd_);
-        rc = mxf_gemm_split_internal(h, M, M, SB, (double)split_ga * split_ga, plKuf, (int64_t)pl_big, plKuf, (int64_t)pl_big, 0.0, (float*)Psi2, M, 1, sd_,
-                                     few ? 202 : psi2_rb, split_mode, split_var, 1, nullptr);
+        rc = mxf_gemm_split_internal(h, sd_, split_mode, M, M, SB, {.alpha = (double)split_ga * split_ga, .ad0 = split_var, .pow0 = 1},
+                                     {plKuf, (int64_t)pl_big}, {plKuf, (int64_t)pl_big}, {.C = (float*)Psi2, .ldc = M, .lower_only = 1},
+                                     {.reserve_cus = few ? 202 : psi2_rb});
         if (rc) return rc;
         symmetrize(Psi2, sd_);
         MXF_T1(h, MXF_T_PSI2, sd_);
@@ -1430,21 +1434,21 @@ struct SvgpCall : SvgpPlan {
         int rc;
         // split path: planes of H0 (scaled from max |H0|) x planes of Kuf (k / variance 2^14).  The whitened tier is the same product with Hh for
         // H0, V for Kuf (V / sigma 2^14), a for w.  Both write max |T| for the reverse pass (word cleared by svgp_init_kernel).
-        const float* ksc = whiten ? sigf : split_var;
+        const MxfSplitScale tscale = {.alpha = (double)split_ga, .ad0 = whiten ? sigf : split_var, .pow0 = 1};
+        const MxfPlanes h0 = {plH0, (int64_t)pl_h0, (const unsigned*)(info2 + 2)};
+        const MxfSplitOut tout = {.C = (float*)Text, .ldc = SB, .blocked = t_blocked, .maxout = (unsigned*)(info2 + 3)};
         if (bt_path || bt_wh)     // T = H0 Kuf straight from the planes Psi2 reads, U = w^T Kuf from the same fragments (gemm_bt.hip)
-            rc = mxf_gemm_bt_internal(h, M, SB, M, (double)split_ga, plH0, (int64_t)pl_h0, plKuf, (int64_t)pl_big, M, (float*)Text, SB, t_blocked, st, 0,
-                                      ksc, (const unsigned*)(info2 + 2), (unsigned*)(info2 + 3), whiten ? (const float*)aT : (const float*)wT,
-                                      (float*)(Text + M * SB), 1.0 / 16384.0, wpl);
+            rc = mxf_gemm_bt_internal(h, st, M, SB, M, tscale, h0, {plKuf, (int64_t)pl_big}, M, tout,
+                                      {.w = whiten ? (const float*)aT : (const float*)wT, .U = (float*)(Text + M * SB), .uscale = 1.0 / 16384.0, .wscratch = wpl});
         else if (use_split)       // T = H0 Kuf = H0 Kfu^T on the 16-bit matrix pipe (f32-equivalent splitting, gemm_split.hip)
-            rc = mxf_gemm_split_internal(h, M, SB, M, (double)split_ga, plH0, (int64_t)pl_h0, whiten ? plVt : plKfu, whiten ? pVt : (int64_t)pl_big, 0.0,
-                                         (float*)Text, SB, 0, st, 0, split_mode, ksc, 1, (const unsigned*)(info2 + 2), nullptr, t_blocked, (unsigned*)(info2 + 3));
+            rc = mxf_gemm_split_internal(h, st, split_mode, M, SB, M, tscale, h0, {whiten ? plVt : plKfu, whiten ? pVt : (int64_t)pl_big}, tout);
         else if (het_split) {
             rc = mxf_maxabs_internal(h, M, M, (const float*)Aext, M, hsw + 0, st);
             if (!rc) rc = mxf_split_planes_internal(h, M, M, (const float*)Aext, M, hsA, st, MXF_SPLIT_F16X2, hsw + 0);
             if (!rc) rc = mxf_maxabs_internal(h, M, SB, (const float*)Kuf, SB, hsw + 1, st);
             if (!rc) rc = mxf_split_planes_internal(h, M, SB, (const float*)Kuf, SB, hsK, st, MXF_SPLIT_F16X2, hsw + 1);      // (m, k = n): the K-major operand of T, the row operand of G'
-            if (!rc) rc = mxf_gemm_bt_internal(h, M, SB, M, 1.0, hsA, (int64_t)pl_h0, hsK, (int64_t)pl_big, M, (float*)Text, SB, 0, st, 0, nullptr, hsw + 0, nullptr,
-                                               nullptr, nullptr, 1.0, nullptr, hsw + 1);
+            if (!rc) rc = mxf_gemm_bt_internal(h, st, M, SB, M, {.alpha = 1.0}, {hsA, (int64_t)pl_h0, hsw + 0}, {hsK, (int64_t)pl_big, hsw + 1}, M,
+                                               {.C = (float*)Text, .ldc = SB});
         } else
             rc = mxf_gemm_internal(h, dtype, 0, 0, M, SB, M, 1.0, Aext, M, 0, Kuf, SB, 0, 0.0, Text, SB, 0, 1, 0, st);   // T = H0 Kuf (MFMA)
         if (rc) return rc;
@@ -1568,8 +1572,8 @@ struct SvgpCall : SvgpPlan {
             if (het_split) {
                 rc = mxf_maxabs_internal(h, M, SB, (const float*)Ksc, SB, hsw + 2, st);
                 if (!rc) rc = mxf_split_planes_internal(h, M, SB, (const float*)Ksc, SB, hsS, st, MXF_SPLIT_F16X2, hsw + 2);
-                if (!rc) rc = mxf_gemm_split_internal(h, M, M, SB, 1.0, hsS, (int64_t)pl_big, hsK, (int64_t)pl_big, 0.0, (float*)Psi2, M, 0, st, 0, MXF_SPLIT_F16X2, nullptr, 0,
-                                                      hsw + 2, hsw + 1);
+                if (!rc) rc = mxf_gemm_split_internal(h, st, MXF_SPLIT_F16X2, M, M, SB, {.alpha = 1.0}, {hsS, (int64_t)pl_big, hsw + 2}, {hsK, (int64_t)pl_big, hsw + 1},
+                                                      {.C = (float*)Psi2, .ldc = M});
             } else
                 rc = mxf_gemm_internal(h, dtype, 0, 1, M, M, SB, 1.0, Ksc, SB, 0, Kuf, SB, 0, 0.0, Psi2, M, 0, 1, 0, st);
             if (rc) return rc;

@@ -21,16 +21,10 @@
 // second planes pass; every other pass over Kuf happens before w exists.)
 #include "common.h"
 #include "internal.h"
-#include <string.h>
+#include "split_device.h"
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 struct BtArgs {
@@ -45,41 +39,11 @@ struct BtArgs {
     const unsigned* maxbits;             // alpha /= scale_from_maxbits(maxbits[0]) (the power-of-two scale of the A planes)
     const unsigned* maxbits2;            // the same for the Bt planes (nullptr: Gram planes, whose scale is known: alpha / ad0 carry it)
     unsigned* maxout;                    // atomicMax of the bit pattern of max |C| (nullptr: none)
-    unsigned* sync; int sync_n;          // rendezvous of the tm row tiles of a column strip (gemm_split.hip: wg_rendezvous)
+    unsigned* sync; int sync_n;          // rendezvous of the tm row tiles of a column strip (split_device.h: wg_rendezvous)
     int sync_every;                      // ... in every sync_every-th persistent round only: bounds the drift of the tiles that share a strip's lines in L2
     // U row: w as two f16 planes [2][16 K16] (hi, lo of w * scale_from_maxbits(uwmax[0])), U[n] = uscale * ad0[0] / that scale * sum
     const unsigned short* uw; const unsigned* uwmax; float* uout; float uscale;
 };
-
-__device__ __forceinline__ float bt_scale_from_maxbits(unsigned bits) {      // == gemm_split.hip's scale_from_maxbits
-    const int ex = (int)((bits >> 23) & 0xff);
-    if (ex == 0 || ex == 0xff) return 1.f;
-    int e = 14 - (ex - 126);
-    e = e > 100 ? 100 : (e < -100 ? -100 : e);
-    return __builtin_bit_cast(float, (unsigned)(e + 127) << 23);
-}
-
-__device__ __forceinline__ int bt_lds_unit(int row, int kh) { return row * 2 + (kh ^ ((row >> 3) & 1)); }
-
-constexpr unsigned long long BT_SYNC_LIMIT = 2000ull;       // wall_clock64 ticks (100 MHz): 20 us
-
-__device__ __forceinline__ void bt_rendezvous(unsigned* ctr, unsigned n, int& patience) {      // see gemm_split.hip: a bounded pacing hint
-    if (threadIdx.x == 0) {
-        if (patience > 0) {
-            __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned long long t0 = wall_clock64();
-            while (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < n) {
-                if (wall_clock64() - t0 > BT_SYNC_LIMIT) { --patience; break; }
-                __builtin_amdgcn_s_sleep(4);
-            }
-            if (__hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == 2u * n)
-                __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else if (__hip_atomic_fetch_add(ctr, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 2u == 2u * n) {
-            __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    __builtin_amdgcn_s_barrier();
-}
 
 // one LDS-DMA request: 64 lanes x 16 bytes from per-lane global addresses to the 1 KB at LDS byte address `lds` (wave-uniform, in M0)
 // (wave-uniform 64-bit base in SGPRs + a 32-bit per-lane byte offset: two address registers per thread for the whole kernel)
@@ -123,8 +87,8 @@ __global__ __launch_bounds__(512, 2) void gemm_f16x2_bt_kernel(BtArgs g) {
     }
     float alpha = g.alpha;
     if (g.ad0) alpha *= g.ad0[0];
-    if (g.maxbits) alpha /= bt_scale_from_maxbits(g.maxbits[0]);
-    if (g.maxbits2) alpha /= bt_scale_from_maxbits(g.maxbits2[0]);
+    if (g.maxbits) alpha /= scale_from_maxbits(g.maxbits[0]);
+    if (g.maxbits2) alpha /= scale_from_maxbits(g.maxbits2[0]);
 
     // A: thread t fills unit t of each plane's slab (row t >> 1; the XOR swizzle of the two k halves is applied to the source)
     const int drow = tid >> 1, dkh = (tid & 1) ^ ((drow >> 3) & 1);
@@ -137,7 +101,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f16x2_bt_kernel(BtArgs g) {
     // fragment reads: A units; Bt byte offset of this lane inside a plane image (instruction (y, h) adds (2 y + h) * 512)
     // (row = 128 wh + 32 x + li: the swizzle bit (row >> 3) & 1 does not depend on x, so fragment x sits 64 units behind fragment 0 -- one
     //  address register and immediate offsets)
-    const int ua0_ = bt_lds_unit(128 * wh + li, lk);
+    const int ua0_ = lds_unit(128 * wh + li, lk);
 #define ua_(x) (ua0_ + 64 * (x))
     const unsigned ldsA = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) void*)&sA[0][0][wave * 64]);
     const unsigned ldsB = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) void*)&sB[0][0][wave * 64]);
@@ -154,12 +118,8 @@ __global__ __launch_bounds__(512, 2) void gemm_f16x2_bt_kernel(BtArgs g) {
     const unsigned nwg = (unsigned)g.nwg, tmu = (unsigned)g.tm;
     const int nit = (int)((nwg - blockIdx.x + gridDim.x - 1) / gridDim.x);
     const int nsteps = nit * nk;
-    const unsigned q8 = nwg >> 3, r8 = nwg & 7;
-    auto item_of = [&](int i) -> unsigned {         // XCD-aware mapping: every XCD owns a contiguous run of items (gemm_split.hip)
-        const unsigned wid = blockIdx.x + (unsigned)i * gridDim.x;
-        const unsigned xcd = wid & 7, jx = wid >> 3;
-        return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + jx;
-    };
+    const unsigned q8 = nwg / 8, r8 = nwg % 8;
+    auto item_of = [&](int i) -> unsigned { return xcd_run_item(blockIdx.x + (unsigned)i * gridDim.x, q8, r8); };
     // request side
     int q_it = 0, q_kb = 0;
     unsigned q_slot = 0;
@@ -226,7 +186,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f16x2_bt_kernel(BtArgs g) {
             const unsigned tile_n = wid / tmu, tile_m = wid - tile_n * tmu;                                                         \
             m0 = (int64_t)tile_m * 256; n0 = (int64_t)tile_n * 256;                                                                 \
             uitem = WU && g.uout != nullptr && ((tile_n + (tile_n >> 3) + (tile_n >> 6)) % tmu) == tile_m;                          \
-            if (g.sync && (c_it % g.sync_every) == 0) bt_rendezvous(g.sync + wid / g.sync_n, (unsigned)g.sync_n, patience);         \
+            if (g.sync && (c_it % g.sync_every) == 0) wg_rendezvous(g.sync + wid / g.sync_n, (unsigned)g.sync_n, patience);         \
             _Pragma("unroll") for (int x = 0; x < 4; ++x)                                                                           \
                 _Pragma("unroll") for (int y = 0; y < 2; ++y)                                                                       \
                     _Pragma("unroll") for (int r = 0; r < 16; ++r) c[x][y][r] = 0.f;                                                \
@@ -272,8 +232,8 @@ __global__ __launch_bounds__(512, 2) void gemm_f16x2_bt_kernel(BtArgs g) {
                 if (lane < 32) { sU[256 * wh + 64 * wq + li] = ua0; sU[256 * wh + 64 * wq + 32 + li] = ua1; }
                 __syncthreads();
                 if (tid < 256) {
-                    float sc = g.uscale * (g.ad0 ? g.ad0[0] : 1.f) / bt_scale_from_maxbits(g.uwmax[0]);
-                    if (g.maxbits2) sc /= bt_scale_from_maxbits(g.maxbits2[0]);
+                    float sc = g.uscale * (g.ad0 ? g.ad0[0] : 1.f) / scale_from_maxbits(g.uwmax[0]);
+                    if (g.maxbits2) sc /= scale_from_maxbits(g.maxbits2[0]);
                     g.uout[n0 + tid] = (sU[tid] + sU[256 + tid]) * sc;
                 }
             }
@@ -346,7 +306,7 @@ __global__ __launch_bounds__(256) void bt_wsplit_kernel(int64_t K, int64_t Kp, c
     __syncthreads();
     for (int i = 0; i < 4; ++i) m = wm[i] > m ? wm[i] : m;
     if (threadIdx.x == 0) maxword[0] = m;
-    const float sc = bt_scale_from_maxbits(m);
+    const float sc = scale_from_maxbits(m);
     for (int64_t i = threadIdx.x; i < Kp; i += 256) {
         const float x = i < K ? w[i] * sc : 0.f;
         const _Float16 fh = (_Float16)x;
@@ -361,50 +321,74 @@ __global__ __launch_bounds__(256) void bt_wsplit_kernel(int64_t K, int64_t Kp, c
 bool mxf_gemm_bt_ok(int64_t M, int64_t N, int64_t K) { return M > 0 && N > 0 && K >= 48 && (M % 256) == 0 && (N % 256) == 0 && (K % 16) == 0; }
 
 // C (M x N) = alpha * ad0[0] / scale(maxbits) * A (M x K) * Bt (K x N) from f16x2 planes: A planes as in gemm_split.hip ((m, k): ((k / 16) * M
-// + m) * 16 + k % 16, plane stride pA), Bt = the planes of the (btR >= K rows, k' = N) operand ((n / 16) * btR + k) * 16 + n % 16, plane
-// stride pB.  c_blocked: C in 16-column blocks (ldc == N).  w (K floats, device) + U (N floats): U[n] = uscale * ad0[0] * sum_k w[k] Bt[k][n]
-// (Bt in the planes' units); wscratch: 2 K halves + one word, caller-owned.  reserve_cus: workgroups = 256 - reserve_cus (one per CU).
-int mxf_gemm_bt_internal(mxf_ctx* h, int64_t M, int64_t N, int64_t K, double alpha, const unsigned short* A, int64_t pA, const unsigned short* Bt,
-                         int64_t pB, int64_t btR, float* C, int64_t ldc, int c_blocked, hipStream_t st, int reserve_cus, const float* ad0,
-                         const unsigned* maxbits, unsigned* maxout, const float* w, float* U, double uscale, void* wscratch, const unsigned* maxbits2) {
-    if (c_blocked && M * 16 * 64 >= (1ll << 31)) MXF_FAIL(h, -3, "mxf_gemm_bt: too many rows for the blocked output");
+// + m) * 16 + k % 16), Bt = the planes of the (btR >= K rows, k' = N) operand ((n / 16) * btR + k) * 16 + n % 16.  out.blocked: C in 16-column
+// blocks (ldc == N).  u: w (K floats, device) + U (N floats), U[n] = uscale * ad0[0] * sum_k w[k] Bt[k][n] (Bt in the planes' units).
+// sched.reserve_cus: workgroups = 256 - reserve_cus (one per CU).
+namespace {
+
+// What bt_plan decides (no HIP call) and bt_launch carries out; g.sync is the one field bt_launch fills.  The kernel relies on:
+// M, N multiples of 256, K a multiple of 16 and >= 48 (every item has three k blocks), btR >= K, 32-bit byte offsets inside one k block of Bt
+// and one 16-column block of C, C 16-byte aligned with ldc % 4 == 0; uout != nullptr => the <true> instantiation, K <= 16 BT_KMAX16;
+// ncounters > 0 => a group is g.sync_n = tm consecutive items of one XCD's run taken in the same persistent round (strip_rendezvous_ok).
+struct BtPlan { BtArgs g; unsigned grid; unsigned ncounters; const float* w; unsigned short* wplanes; unsigned* wmax; };      // w*: the U row's bt_wsplit_kernel launch
+
+int bt_plan(mxf_ctx* h, int64_t M, int64_t N, int64_t K, const MxfSplitScale& sc, const MxfPlanes& A, const MxfPlanes& Bt, int64_t btR,
+            const MxfSplitOut& o, const MxfBtURow& u, const MxfSplitSched& sched, BtPlan& p) {
+    if (o.planes || o.planes_t || o.avec || o.a_lower || o.lower_only || o.beta != 0.0 || sc.pow0 < 0 || sc.pow0 > 1)
+        MXF_FAIL(h, -2, "mxf_gemm_bt: the output is C or blocked C of a full product with beta == 0, and ad0 enters once");
+    if (o.blocked && M * 16 * 64 >= (1ll << 31)) MXF_FAIL(h, -3, "mxf_gemm_bt: too many rows for the blocked output");
     if (btR * 16 * 32 >= (1ll << 31)) MXF_FAIL(h, -3, "mxf_gemm_bt: the K-major operand has too many rows");
     if (!mxf_gemm_bt_ok(M, N, K) || btR < K) MXF_FAIL(h, -2, "mxf_gemm_bt: needs M %% 256 == 0, N %% 256 == 0, K %% 16 == 0, K >= 48");
-    if (c_blocked && ldc != N) MXF_FAIL(h, -2, "mxf_gemm_bt: the blocked output layout needs ldc == N");
-    if ((ldc % 4) != 0 || (((uintptr_t)C) % 16) != 0) MXF_FAIL(h, -2, "mxf_gemm_bt: C must be 16-byte aligned with ldc %% 4 == 0");
-    if (U && (!w || !wscratch || K / 16 > BT_KMAX16)) MXF_FAIL(h, -2, "mxf_gemm_bt: the U row needs w, scratch and K <= %d", BT_KMAX16 * 16);
-    BtArgs g;
+    if (o.blocked && o.ldc != N) MXF_FAIL(h, -2, "mxf_gemm_bt: the blocked output layout needs ldc == N");
+    if ((o.ldc % 4) != 0 || (((uintptr_t)o.C) % 16) != 0) MXF_FAIL(h, -2, "mxf_gemm_bt: C must be 16-byte aligned with ldc %% 4 == 0");
+    if (u.U && (!u.w || !u.wscratch || K / 16 > BT_KMAX16)) MXF_FAIL(h, -2, "mxf_gemm_bt: the U row needs w, scratch and K <= %d", BT_KMAX16 * 16);
+    BtArgs& g = p.g;
     memset(&g, 0, sizeof(g));
-    g.A = A; g.Bt = Bt; g.C = C; g.M = M; g.N = N; g.K16 = K / 16; g.pA = pA; g.pB = pB; g.btR = btR;
-    g.alpha = (float)alpha; g.c_blk = c_blocked; g.ldc = ldc; g.tm = M / 256; g.tn = N / 256; g.nwg = g.tm * g.tn;
-    g.ad0 = ad0; g.maxbits = maxbits; g.maxbits2 = maxbits2; g.maxout = maxout;
-    if (U) {
-        unsigned short* wp = (unsigned short*)wscratch;
-        unsigned* wmax = (unsigned*)(wp + 2 * K);
-        hipLaunchKernelGGL(bt_wsplit_kernel, dim3(1), dim3(256), 0, st, K, K, w, wp, wmax);
-        g.uw = wp; g.uwmax = wmax; g.uout = U; g.uscale = (float)uscale;
+    g.A = A.p; g.pA = A.stride; g.maxbits = A.maxbits; g.Bt = Bt.p; g.pB = Bt.stride; g.maxbits2 = Bt.maxbits; g.btR = btR;
+    g.M = M; g.N = N; g.K16 = K / 16; g.tm = M / 256; g.tn = N / 256; g.nwg = g.tm * g.tn;
+    g.alpha = (float)sc.alpha; g.ad0 = sc.pow0 ? sc.ad0 : nullptr;
+    g.C = o.C; g.ldc = o.ldc; g.c_blk = o.blocked; g.maxout = o.maxout;
+    p.w = u.w; p.wplanes = nullptr; p.wmax = nullptr;
+    if (u.U) {          // caller's scratch: the two f16 planes of w (2 K halves), then its max-abs word
+        p.wplanes = (unsigned short*)u.wscratch; p.wmax = (unsigned*)(p.wplanes + 2 * K);
+        g.uw = p.wplanes; g.uwmax = p.wmax; g.uout = u.U; g.uscale = (float)u.uscale;
     }
-    int64_t grid = (int64_t)(256 - (reserve_cus > 0 ? reserve_cus : 0)) / 8 * 8;
+    int64_t grid = (int64_t)(256 - (sched.reserve_cus > 0 ? sched.reserve_cus : 0)) / 8 * 8;
     if (grid < 8) grid = 8;
     if (g.nwg <= grid) grid = g.nwg;
-    // The tm row tiles of a column strip (tm consecutive items of one XCD's run, taken in the same persistent round by tm different
-    // workgroups) share the strip's Bt lines in their XCD's L2 -- as long as they run in step.  Nothing keeps them there: with no pacing
-    // at all they drift apart and every one fetches the strip from HBM itself (r06 PMC: 50 GB of traffic per launch against 26 GB of
-    // operands + output).  A bounded rendezvous (gemm_split.hip) at the start of an item re-aligns them.  Same box, T shape, traffic per
+    p.grid = (unsigned)grid;
+    // The tm row tiles of a column strip share the strip's Bt lines in their XCD's L2 -- as long as they run in step.  Nothing keeps them
+    // there: with no pacing at all they drift apart and every one fetches the strip from HBM itself (r06 PMC: 50 GB of traffic per launch
+    // against 26 GB of operands + output).  A bounded rendezvous (wg_rendezvous) at the start of an item re-aligns them.  Same box, T shape, traffic per
     // launch | 32-sample step: never 49.9 GB | 22.04-22.09 ms; every item 23.1 GB | 22.31; every 4th round 32.1 GB | 22.07; 8th 33.0 | 22.02-22.06;
     // 16th 34.1 | 22.06 (tests/probes/r06_bt_sync.sh).  Every fourth round: two thirds of the avoidable traffic gone at no cost in time.
     // (MXF_BT_SYNC = rounds between two rendezvous, 0 = never; probe builds.)
     static const int sync_env = (int)MXF_KNOB("MXF_BT_SYNC", 4);
-    const int64_t q = g.nwg / 8, per_xcd = grid / 8;
-    if (sync_env && g.tm >= 2 && g.nwg % 8 == 0 && g.nwg >= 16 && q % g.tm == 0 && per_xcd % g.tm == 0 && (g.nwg <= grid || g.nwg % grid == 0)) {
-        g.sync = mxf_gsync(h, (unsigned)(g.nwg / g.tm));
-        g.sync_n = (int)g.tm;
-        g.sync_every = sync_env > 0 ? sync_env : 1;
+    p.ncounters = 0;
+    if (sync_env && strip_rendezvous_ok(g.tm, g.nwg, grid)) {
+        p.ncounters = (unsigned)(g.nwg / g.tm);
+        g.sync_n = (int)g.tm; g.sync_every = sync_env > 0 ? sync_env : 1;
     }
-    if (U) hipLaunchKernelGGL((gemm_f16x2_bt_kernel<true>), dim3((unsigned)grid), dim3(512), 0, st, g);
-    else hipLaunchKernelGGL((gemm_f16x2_bt_kernel<false>), dim3((unsigned)grid), dim3(512), 0, st, g);
+    return 0;
+}
+
+int bt_launch(mxf_ctx* h, hipStream_t st, BtPlan& p) {
+    BtArgs& g = p.g;
+    if (g.uout) hipLaunchKernelGGL(bt_wsplit_kernel, dim3(1), dim3(256), 0, st, g.K16 * 16, g.K16 * 16, p.w, p.wplanes, p.wmax);
+    if (p.ncounters) g.sync = mxf_gsync(h, p.ncounters);       // (nullptr: the kernel goes without the rendezvous)
+    if (g.uout) hipLaunchKernelGGL((gemm_f16x2_bt_kernel<true>), dim3(p.grid), dim3(512), 0, st, g);
+    else hipLaunchKernelGGL((gemm_f16x2_bt_kernel<false>), dim3(p.grid), dim3(512), 0, st, g);
     MXF_LAUNCH_CHECK(h);
     return 0;
+}
+
+}  // namespace
+
+int mxf_gemm_bt_internal(mxf_ctx* h, hipStream_t st, int64_t M, int64_t N, int64_t K, MxfSplitScale scale, MxfPlanes A, MxfPlanes Bt, int64_t btR,
+                         MxfSplitOut out, MxfBtURow u, MxfSplitSched sched) {
+    BtPlan p;
+    const int rc = bt_plan(h, M, N, K, scale, A, Bt, btR, out, u, sched, p);
+    return rc ? rc : bt_launch(h, st, p);
 }
 
 // C ABI: C (M x N) = alpha * A (M x K) * Bt (K x N) from split operands -- A_planes = mxf_f16x2_split of A (M x K), Bt_planes = mxf_f16x2_split
@@ -420,7 +404,8 @@ extern "C" int mxf_gemm_f16x2_planes_kmajor(mxf_handle h, int64_t M, int64_t N, 
         ws = mxf_ws(h, mxf_align((2 * (size_t)K + 8) * 2));
         if (!ws) MXF_FAIL(h, -4, "mxf_gemm_f16x2_planes_kmajor: cannot allocate scratch");
     }
-    return mxf_gemm_bt_internal(h, M, N, K, alpha, (const unsigned short*)A_planes, (int64_t)mxf_split_plane_elems(M, K), (const unsigned short*)Bt_planes,
-                                (int64_t)mxf_split_plane_elems(K, N), K, (float*)C, N, blocked ? 1 : 0, (hipStream_t)stream, 0, nullptr,
-                                (const unsigned*)A_maxword, nullptr, (const float*)w, (float*)U, 1.0, ws, (const unsigned*)Bt_maxword);
+    return mxf_gemm_bt_internal(h, (hipStream_t)stream, M, N, K, {.alpha = alpha},
+                                {(const unsigned short*)A_planes, (int64_t)mxf_split_plane_elems(M, K), (const unsigned*)A_maxword},
+                                {(const unsigned short*)Bt_planes, (int64_t)mxf_split_plane_elems(K, N), (const unsigned*)Bt_maxword}, K,
+                                {.C = (float*)C, .ldc = N, .blocked = blocked ? 1 : 0}, {.w = (const float*)w, .U = (float*)U, .wscratch = ws});
 }

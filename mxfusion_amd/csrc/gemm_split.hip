@@ -24,29 +24,16 @@
 // of a general operand comes from its max-abs word (mxf_maxabs_internal), read by the splitter and by the GEMM epilogue.
 #include "common.h"
 #include "internal.h"
-#include <stdlib.h>
-#include <string.h>
+#include "split_device.h"
 
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int SBM = 128, SBN = 128, SNT = 256;   // one 16-wide k block per MFMA step
 
 // ------------------------------------------------------------------------------------------------ f32 -> three bf16 planes
 // X (R x K, row stride ld) -> planes; K is padded with zeros to a multiple of 16 (Kp).  One block: 64 rows x 64 k.
-// power-of-two scale that puts |x| <= max at [2^13, 2^14]; max given as the bit pattern of a non-negative float
-__device__ __forceinline__ float scale_from_maxbits(unsigned bits) {
-    const int ex = (int)((bits >> 23) & 0xff);                 // biased exponent of the maximum: max in [2^(ex-127), 2^(ex-126))
-    if (ex == 0 || ex == 0xff) return 1.f;                      // zero / denormal / non-finite maximum: leave unscaled
-    int e = 14 - (ex - 126);                                    // max * 2^e in [2^13, 2^14)
-    e = e > 100 ? 100 : (e < -100 ? -100 : e);
-    return __builtin_bit_cast(float, (unsigned)(e + 127) << 23);
-}
-
 template <int NP>
 __global__ __launch_bounds__(256) void split_planes_kernel(int64_t R, int64_t K, const float* __restrict__ X, int64_t ld,
                                                            unsigned short* __restrict__ P, int64_t pstride, const unsigned* __restrict__ maxbits) {
@@ -149,7 +136,7 @@ struct SplitArgs {
     int64_t M, N, K16;          // K16 = number of 16-wide k blocks
     int64_t pA, pB, ldc;
     float alpha, beta;
-    int splitk, lower_only, atomic, nprod, use_dma;
+    int splitk, lower_only, atomic, nprod, use_dma;     // splitk, use_dma: no kernel reads them; nprod: always 6 -- kept, as removing a field moves every kernel's arguments
     int c_blk;                  // C in 16-column blocks: element (row, col) at ((col / 16) * M + row) * 16 + col % 16 (the SVGP reverse pass reads T so)
     int64_t kchunk;             // k blocks per split
     int64_t tm, tn, ntiles, nwg;
@@ -176,10 +163,8 @@ struct SplitArgs {
     // Upart[(m / 128) * N + n] = sum over the 128-row band of avec[m] * (hi + lo)(m, n)  (the whitened SVGP tier's V^T and a^T V)
     unsigned short* Ct; int64_t pCt;
     const float* avec; float* Upart;
-    int cp_nt;                           // bit 0: the planes, bit 1: the transposed planes are stored non-temporally (0 in every launch)
+    int cp_nt;                           // bit 0: the planes, bit 1: the transposed planes are stored non-temporally (0 in every launch; kept: removing a field moves every kernel's arguments)
 };
-
-__device__ __forceinline__ int lds_unit(int row, int kh) { return row * 2 + (kh ^ ((row >> 3) & 1)); }
 
 template <bool DMA, int NP>
 __global__ __launch_bounds__(SNT, (NP == 2 && !DMA) ? 4 : 3) void gemm_split_kernel(SplitArgs g) {
@@ -190,11 +175,7 @@ __global__ __launch_bounds__(SNT, (NP == 2 && !DMA) ? 4 : 3) void gemm_split_ker
     __shared__ u32x4 smem[NST][2][NP][256];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
-    int64_t wid = blockIdx.x;
-    {   // XCD-aware mapping (see gemm.hip)
-        const int64_t q = g.nwg / 8, r = g.nwg % 8, xcd = wid % 8, j = wid / 8;
-        wid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int64_t wid = xcd_run_item((int64_t)blockIdx.x, g.nwg);
     const int64_t split = wid / g.ntiles;
     int64_t t = wid % g.ntiles;
     int64_t tile_m, tile_n;
@@ -372,31 +353,9 @@ __global__ __launch_bounds__(SNT, (NP == 2 && !DMA) ? 4 : 3) void gemm_split_ker
 // L2 locality by rendezvous (r03).  The workgroups that share operand lines -- the row tiles of one column strip of T (same B strip, and
 // with the whole XCD in step also the same A k-window), the tiles of one k split of Psi2 -- are dealt to ONE XCD, but nothing kept them in
 // step: each walks its own k loop, they drift apart by more than the 4 MB L2 holds, and every operand line was fetched ~3 times from the
-// fabric (r02 PMC: 26.2 GB for 8.6 GB of planes).  wg_rendezvous() is a BOUNDED spin on one counter per group (at the start of a work item
-// for T, every `sync_period` loop trips for the long-K products): a pacing hint, never needed for correctness -- a workgroup that waited
-// SYNC_LIMIT for its partners goes on alone and stops waiting after its second time-out, so a launch next to kernels that hold some CUs,
-// or two such launches on different streams, cannot deadlock.  Every workgroup adds exactly 2 to its group's counter (arrive + depart,
-// or both at once when it no longer waits); the add that completes 2 n resets the word, so the counters are zero between launches.
+// fabric (r02 PMC: 26.2 GB for 8.6 GB of planes).  wg_rendezvous() (split_device.h) is a bounded spin on one counter per group -- at the start of a work
+// item for T, every `sync_period` loop trips for the long-K products: a pacing hint, never needed for correctness.
 constexpr int WBN = 256;
-constexpr unsigned long long SYNC_LIMIT = 2000ull;       // wall_clock64 ticks (100 MHz): 20 us
-
-__device__ __forceinline__ void wg_rendezvous(unsigned* ctr, unsigned n, int& patience) {
-    if (threadIdx.x == 0) {
-        if (patience > 0) {
-            __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned long long t0 = wall_clock64();
-            while (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < n) {
-                if (wall_clock64() - t0 > SYNC_LIMIT) { --patience; break; }
-                __builtin_amdgcn_s_sleep(4);
-            }
-            if (__hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == 2u * n)
-                __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else if (__hip_atomic_fetch_add(ctr, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 2u == 2u * n) {
-            __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    __builtin_amdgcn_s_barrier();        // bare: requests in flight (LDS-DMA, the previous item's stores) stay in flight
-}
 
 __device__ __forceinline__ u32x4 gload16(unsigned voff, const void* sbase) {
     u32x4 r;
@@ -437,11 +396,7 @@ __device__ __forceinline__ void wide_body(const SplitArgs& g) {
     const int nsub = (CPL && g.pair) ? 2 : 1;
     for (int64_t wid0 = blockIdx.x; wid0 < g.nwg; wid0 += gridDim.x)
     for (int sub = 0; sub < nsub; ++sub) {
-    int64_t wid = wid0;
-    {   // XCD-aware mapping: every XCD owns a contiguous run of tiles
-        const int64_t q = g.nwg / 8, r = g.nwg % 8, xcd = wid % 8, j = wid / 8;
-        wid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int64_t wid = xcd_run_item(wid0, g.nwg);      // every XCD owns a contiguous run of tiles
     const int64_t split = wid / g.ntiles;
     int64_t t = wid % g.ntiles;
     int64_t tile_m, tile_n;
@@ -657,13 +612,10 @@ __device__ __forceinline__ void wide_body(const SplitArgs& g) {
     if (g.maxbits2) alpha /= scale_from_maxbits(g.maxbits2[0]);
     const bool atomic = g.atomic != 0;
     // D = B A^T: accumulator register r of tile (x, y) is C[m0 + 32 XT wh + 32 x + (lane & 31)][n0 + 64 wq + 32 y + 8 (r >> 2) + 4 (lane >> 5) + (r & 3)]
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     if constexpr (CPL) {
         // planes output: lane (li, lk) holds columns 8 q + 4 lk .. + 3 of quad q.  v_permlane32_swap trades quad q + 1 of the lanes lk = 0 for
         // quad q of the lanes lk = 1: afterwards lane lk owns EIGHT consecutive columns 8 (q + lk) .. + 7 (q even) = one 16-byte unit per
         // plane, and a store instruction covers 32 rows x 32 bytes = 1 KB contiguous of the 16-column block.
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
-        typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
         // a of this tile's rows, fetched BEFORE the plane stores are issued and parked in LDS behind the wave tiles: a vector load later in
         // the epilogue waits for vmcnt(0), i.e. for this item's stores to retire (16 such stalls per item cost 1.8 ms of the whitened step)
         float* alds = reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(&smem[0][0][0]) + (NTH / 64) * (32 * 68));
@@ -728,7 +680,6 @@ __device__ __forceinline__ void wide_body(const SplitArgs& g) {
                                 const f16x2 fo = pl == 0 ? fh : __builtin_convertvector(v - __builtin_convertvector(fh, f32x2), f16x2);
                                 w2[d] = __builtin_bit_cast(unsigned, fo);
                             }
-                            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
                             const u32x2 wv = {w2[0], w2[1]};
                             *reinterpret_cast<u32x2*>(wl + li * RS + 32 * y + 8 * q + 4 * lk) = wv;
                         }
@@ -855,135 +806,157 @@ int mxf_split_planes_internal(mxf_ctx* h, int64_t R, int64_t K, const float* X, 
     return 0;
 }
 
-// C (M x N) = alpha * A (M x K) * B (N x K)^T + beta * C from split planes; pA / pB = plane strides in elements.  A k sub-range
-// [k0, k0+K) of a (R x Ktot) operand is the pointer planes + (k0 / 16) * R * 16 with the FULL operand's plane stride.
-int mxf_gemm_split_internal(mxf_ctx* h, int64_t M, int64_t N, int64_t K, double alpha, const unsigned short* A, int64_t pA,
-                            const unsigned short* B, int64_t pB, double beta, float* C, int64_t ldc, int lower_only, hipStream_t st,
-                            int reserve_cus, int mode, const float* ad0, int pow0, const unsigned* maxbits, const unsigned* maxbits2, int c_blocked,
-                            unsigned* maxout, unsigned short* Cplanes, int64_t pC, int a_lower, unsigned short* Ct, int64_t pCt,
-                            const float* avec, float* Upart) {
-    if (M <= 0 || N <= 0) return 0;
-    SplitArgs g;
-    g.c_blk = c_blocked; g.maxout = nullptr;
-    g.Cp = Cplanes; g.pC = pC; g.a_lower = a_lower; g.rot_div = 0;
-    g.Ct = Ct; g.pCt = pCt; g.avec = avec; g.Upart = Upart;
-    g.cp_nt = 0;
-    if ((Ct && !Cplanes) || (avec && (!Ct || !Upart))) MXF_FAIL(h, -2, "mxf_gemm_split: the transposed planes come with the planes output, the partial sums with both");
-    if (Cplanes) {
-        if (mode != MXF_SPLIT_F16X2 || (M % 128) != 0 || (N % WBN) != 0 || beta != 0.0 || lower_only || c_blocked)
-            MXF_FAIL(h, -2, "mxf_gemm_split: the planes output needs the f16x2 format, M %% 128 == 0, N %% 256 == 0, beta == 0 and a full product");
-        g.c_blk = 2;
-    } else if (a_lower) MXF_FAIL(h, -2, "mxf_gemm_split: a_lower is implemented for the planes output only");
-    if (c_blocked && (N % 16 != 0 || beta != 0.0 || lower_only || ldc != N)) MXF_FAIL(h, -2, "mxf_gemm_split: the blocked output layout needs N %% 16 == 0, ldc == N, beta == 0 and a full product");
-    g.ad0 = ad0; g.pow0 = pow0; g.maxbits = maxbits; g.maxbits2 = maxbits2;
-    g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K16 = (K + 15) / 16;
-    g.pA = pA; g.pB = pB; g.ldc = ldc;
-    g.alpha = (float)alpha; g.beta = (float)beta; g.lower_only = lower_only;
-    g.nprod = 6;            // all six products of the three-plane format (the two-plane format's three are a subset)
-    g.use_dma = 1;
-    // the wide kernels take the planes-output products, the long-K lower-triangle products (Psi2) and the products written in 16-column
-    // blocks (T of the training step).  Their epilogue puts ROWS on lanes: fine for a blocked C (rows are 64 bytes apart) and for the small
-    // square Psi2, 16-byte pieces 4 N bytes apart for a wide row-major C -- the T shape then takes 16.7 ms instead of 13.4 on the 128 x 128
-    // kernel, blocked it takes 12.3.
-    const bool wide = Cplanes != nullptr ||
-                      ((lower_only || c_blocked) && mode == MXF_SPLIT_F16X2 && (M % 128) == 0 && (N % WBN) == 0 && (ldc % 4) == 0 &&
-                       (((uintptr_t)C) % 16) == 0 && (!lower_only || M == N));
-    // rows per tile of the wide kernel: 256 (eight waves, two row halves: two per SIMD) when the shape allows, else 128 (four waves, two
-    // workgroups per CU)
-    const int NH = (wide && (M % 256) == 0) ? 2 : 1;
-    const int64_t WBMh = 128 * NH;
-    int64_t tm = (M + SBM - 1) / SBM, tn = (N + SBN - 1) / SBN;
-    if (lower_only && tm != tn) MXF_FAIL(h, -2, "mxf_gemm_split: lower_only needs a square output");
-    int64_t tiles = lower_only ? tm * (tm + 1) / 2 : tm * tn;
-    if (wide) {
-        tm = M / WBMh; tn = N / WBN;
-        tiles = 0;
-        if (lower_only) { for (int64_t r = 0; r < tm; ++r) tiles += (WBMh * r + WBMh - 1) / WBN + 1; }
-        else tiles = tm * tn;
+// ------------------------------------------------------------------------------------------------ the launcher: plan, then launch
+// C (M x N) = alpha * A (M x K) * B (N x K)^T + beta * C from split planes.  A k sub-range [k0, k0+K) of a (R x Ktot) operand is the pointer
+// planes + (k0 / 16) * R * 16 with the FULL operand's plane stride.
+namespace {
+
+enum SplitKernel { SK_WIDE_256PL, SK_WIDE_128PL, SK_WIDE_256LO, SK_WIDE_256, SK_WIDE_128, SK_TILE_DMA_F16, SK_TILE_F16, SK_TILE_DMA_BF16, SK_TILE_BF16 };
+
+// What split_plan decides (no HIP call, the handle only takes the error text) and split_launch carries out.  Fields of g become valid in the
+// order of the plan's paragraphs; g.sync is the one field split_launch fills.  What the kernels rely on:
+//   * planes output (g.c_blk == 2)  =>  f16x2, M % 128 == 0, N % 256 == 0, beta == 0, a full product, a wide kernel, no split-K (g.atomic == 0);
+//   * g.pair  =>  planes output, a_lower, tm >= 2 and tn >= 2, no rendezvous; the tm roles of a pair sit in one persistent round when the grid allows;
+//   * a wide kernel  =>  f16x2, M % (its tile rows) == 0, N % 256 == 0, C 16-byte aligned with ldc % 4 == 0 (or planes), lower_only => M == N;
+//   * SK_TILE_DMA_*  =>  M and N multiples of 128;  blocked C  =>  N % 16 == 0, ldc == N, beta == 0, a full product;
+//   * g.atomic (split-K)  =>  C holds beta * C before the kernel adds to it: beta == 1, or `prescale`;
+//   * ncounters > 0, g.sync_period == 0  =>  full product, no split-K: a group is g.sync_n = tm consecutive items of one XCD's run, taken in the
+//     same persistent round (strip_rendezvous_ok);  g.sync_period > 0  =>  split-K with every item resident: the g.sync_n = tiles items of
+//     a k split meet every sync_period trips, g.sync_slots times;
+//   * g.maxout != nullptr  =>  a wide kernel's plain store path (row-major or blocked C, beta == 0, no split-K, full product).
+// ncounters: rendezvous counters split_launch fetches (0: none); prescale: C *= beta in a launch of its own before the split-K kernel adds to it
+struct SplitPlan { SplitArgs g; SplitKernel kernel; unsigned grid, block, ncounters; bool prescale; };
+
+// every rejection of an output description, in one place
+int split_check_output(mxf_ctx* h, int mode, int64_t M, int64_t N, const MxfSplitOut& o) {
+    if (o.planes && o.C) MXF_FAIL(h, -2, "mxf_gemm_split: one output, C or planes");
+    if ((o.planes_t && !o.planes) || (o.avec && (!o.planes_t || !o.Upart))) MXF_FAIL(h, -2, "mxf_gemm_split: the transposed planes come with the planes output, the partial sums with both");
+    if (o.planes && (mode != MXF_SPLIT_F16X2 || (M % 128) != 0 || (N % WBN) != 0 || o.beta != 0.0 || o.lower_only || o.blocked))
+        MXF_FAIL(h, -2, "mxf_gemm_split: the planes output needs the f16x2 format, M %% 128 == 0, N %% 256 == 0, beta == 0 and a full product");
+    if (!o.planes && o.a_lower) MXF_FAIL(h, -2, "mxf_gemm_split: a_lower is implemented for the planes output only");
+    if (o.blocked && (N % 16 != 0 || o.beta != 0.0 || o.lower_only || o.ldc != N)) MXF_FAIL(h, -2, "mxf_gemm_split: the blocked output layout needs N %% 16 == 0, ldc == N, beta == 0 and a full product");
+    if (o.lower_only && (M + SBM - 1) / SBM != (N + SBN - 1) / SBN) MXF_FAIL(h, -2, "mxf_gemm_split: lower_only needs a square output");
+    return 0;
+}
+
+// wide kernels: the persistent grid, then the rendezvous policy (wg_rendezvous) for it
+void split_plan_wide(SplitPlan& p, int64_t rows, int reserve_cus) {
+    SplitArgs& g = p.g;
+    const bool planes = g.c_blk == 2;
+    const int64_t tm = g.tm, splitk = g.splitk;
+    // persistent: as many workgroups as fit the chip (the kernel's occupancy: 1 per CU with 256-row tiles, else 2) walk the work items; fewer
+    // items than that: one each.  (planes-output products honour reserve_cus: a caller that runs a latency-bound chain next to this product
+    // leaves it some CUs)
+    static const int64_t wide_grid_env = MXF_KNOB("MXF_SPLIT_WIDE_GRID", 0);
+    int64_t wide_grid = wide_grid_env > 0 ? wide_grid_env : (planes ? (256 - reserve_cus) / 8 * 8 : 256) * (rows == 256 ? 1 : 2);
+    // paired items: the tm roles of a pair must be resident in the same persistent round -- workgroups per XCD a multiple of tm
+    if (g.pair && wide_grid / 8 >= tm) wide_grid = (wide_grid / 8) / tm * tm * 8;
+    const int64_t grid = (wide_grid >= 8 && g.nwg > wide_grid) ? wide_grid / 8 * 8 : g.nwg;
+    p.grid = (unsigned)grid;
+    // rendezvous groups: the row tiles of one column strip (full products) / the tiles of one k split (split-K products).  Triangular
+    // planes-output products go without: the row tiles of a strip carry unequal work -- unpaired, the row tile rotates with the persistent
+    // round instead; strip pairs (g.pair) stay in step by construction, every role does tm + 1 units (r05: the pairing alone takes the fabric
+    // fetch from 21.5 to 13.5 GB, with or without a rendezvous, and the product is 0.1 ms faster without one).
+    static const int sync_period_env = (int)MXF_KNOB("MXF_SPLIT_SYNC_PERIOD", 16);
+    if (planes && g.a_lower) {
+        if (!g.pair) g.rot_div = (grid / 8) / tm > 0 ? (grid / 8) / tm : 1;
+    } else if (!g.lower_only && splitk == 1) {
+        if (strip_rendezvous_ok(tm, g.nwg, grid)) { p.ncounters = (unsigned)(g.nwg / tm); g.sync_n = (int)tm; }
+    } else if (splitk > 1 && g.nwg <= grid && g.ntiles >= 2 && sync_period_env > 0) {
+        // every tile of a k split is resident at once: they meet every `period` trips of three k blocks
+        const int64_t trips = g.kchunk / 3;
+        int64_t period = sync_period_env;
+        int64_t slots_per = trips / period;
+        while (slots_per * splitk > (int64_t)(MXF_NRING / 8)) { period *= 2; slots_per = trips / period; }
+        if (slots_per >= 1) {
+            p.ncounters = (unsigned)(slots_per * splitk);
+            g.sync_n = (int)g.ntiles; g.sync_period = (int)period; g.sync_slots = (int)slots_per;
+        }
     }
-    int splitk = 1;
-    // split-K target: ~one wave of workgroups (3 fit a CU; 3 or 4 per CU measure the same per step, 6 and more are slower; the wide kernel: 2,
-    // its 256-row form 1).  A caller that reserves more than half of the chip wants a FEW workgroups next to other work -- phase A of Psi2,
-    // sized for the four-per-CU kernel: ~216 workgroups, one per CU on 216 CUs, whichever kernel runs.
-    const int64_t slots = wide ? (reserve_cus >= 128 ? (int64_t)(256 - reserve_cus) * 4 : (int64_t)(256 - reserve_cus) * (WBMh == 256 ? 1 : 2))
-                               : (int64_t)(256 - reserve_cus) * (mode == MXF_SPLIT_F16X2 ? 4 : 3);
-    if (tiles < slots && g.K16 >= 16 && !Cplanes) {
-        int64_t sk = slots / tiles;
+}
+
+int split_plan(mxf_ctx* h, int mode, int64_t M, int64_t N, int64_t K, const MxfSplitScale& sc, const MxfPlanes& A, const MxfPlanes& B,
+               const MxfSplitOut& o, const MxfSplitSched& sched, SplitPlan& p) {
+    const int rc = split_check_output(h, mode, M, N, o);
+    if (rc) return rc;
+    const bool planes = o.planes != nullptr, f16 = mode == MXF_SPLIT_F16X2, lower = o.lower_only != 0;
+    SplitArgs& g = p.g;
+    // ---- passed through: operands, epilogue scale, output (the planes epilogue reads neither C nor ldc; ldc = N as for a blocked C)
+    g.A = A.p; g.pA = A.stride; g.maxbits = A.maxbits; g.B = B.p; g.pB = B.stride; g.maxbits2 = B.maxbits;
+    g.M = M; g.N = N; g.K16 = (K + 15) / 16;
+    g.alpha = (float)sc.alpha; g.ad0 = sc.ad0; g.pow0 = sc.pow0;
+    g.C = o.C; g.ldc = planes ? N : o.ldc; g.beta = (float)o.beta; g.lower_only = o.lower_only; g.c_blk = planes ? 2 : o.blocked;
+    g.Cp = o.planes; g.pC = o.pstride; g.a_lower = o.a_lower; g.Ct = o.planes_t; g.pCt = o.pstride_t; g.avec = o.avec; g.Upart = o.Upart;
+    g.nprod = 6; g.use_dma = 1; g.cp_nt = 0;
+    // ---- kernel.  The wide kernels take the planes-output products, the long-K lower-triangle products (Psi2) and the products written in
+    // 16-column blocks (T of the training step).  Their epilogue puts ROWS on lanes: fine for a blocked C (rows are 64 bytes apart) and for the
+    // small square Psi2, 16-byte pieces 4 N bytes apart for a wide row-major C -- the T shape then takes 16.7 ms instead of 13.4 on the
+    // 128 x 128 kernel, blocked it takes 12.3.  Rows per wide tile: 256 (eight waves, two per SIMD) when the shape allows, else 128.
+    const bool wide = planes || ((lower || o.blocked) && f16 && (M % 128) == 0 && (N % WBN) == 0 && (o.ldc % 4) == 0 && (((uintptr_t)o.C) % 16) == 0 &&
+                                 (!lower || M == N));
+    const int64_t rows = wide && (M % 256) == 0 ? 256 : 128, cols = wide ? WBN : SBN;
+    const bool dma = (M % SBM) == 0 && (N % SBN) == 0;
+    if (wide) p.kernel = rows == 256 ? (planes ? SK_WIDE_256PL : lower ? SK_WIDE_256LO : SK_WIDE_256) : (planes ? SK_WIDE_128PL : SK_WIDE_128);
+    else p.kernel = f16 ? (dma ? SK_TILE_DMA_F16 : SK_TILE_F16) : (dma ? SK_TILE_DMA_BF16 : SK_TILE_BF16);
+    p.block = wide ? (unsigned)(2 * rows) : (unsigned)SNT;
+    // ---- tiling (lower_only: the tiles that touch the lower triangle, row by row)
+    const int64_t tm = (M + rows - 1) / rows, tn = (N + cols - 1) / cols;
+    int64_t tiles = lower ? 0 : tm * tn;
+    for (int64_t r = 0; lower && r < tm; ++r) tiles += (rows * r + rows - 1) / cols + 1;
+    // ---- split-K.  Target: ~one wave of workgroups (128 x 128 kernel: 3 fit a CU, 4 of the two-term form; 3 or 4 per CU measure the same per
+    // step, 6 and more are slower; the wide kernel: 2, its 256-row form 1).  A caller that reserves more than half of the chip wants a FEW
+    // workgroups next to other work -- phase A of Psi2, sized for the four-per-CU kernel: ~216 workgroups, one per CU on 216 CUs, whichever
+    // kernel runs.
+    const int64_t cus = 256 - sched.reserve_cus;
+    const int64_t slots = cus * (!wide ? (f16 ? 4 : 3) : sched.reserve_cus >= 128 ? 4 : rows == 256 ? 1 : 2);
+    int64_t sk = 1;
+    if (tiles < slots && g.K16 >= 16 && !planes) {
+        sk = slots / tiles;
         if (sk * tiles < (slots * 3) / 4) sk = (2 * slots) / tiles;
-        const int64_t maxsplit = g.K16 / 8 > 0 ? g.K16 / 8 : 1;
-        if (sk > maxsplit) sk = maxsplit;
-        if (sk < 1) sk = 1;
-        splitk = (int)sk;
+        if (sk > g.K16 / 8) sk = g.K16 / 8;           // at least 8 k blocks per split (K16 >= 16: the bound is >= 2)
     }
-    int64_t kchunk = (g.K16 + splitk - 1) / splitk;
-    if (kchunk < 1) kchunk = 1;
-    splitk = (int)((g.K16 + kchunk - 1) / kchunk);
-    if (splitk < 1) splitk = 1;
+    const int64_t kchunk = g.K16 > sk ? (g.K16 + (int)sk - 1) / (int)sk : 1;
+    const int splitk = g.K16 > kchunk ? (int)((g.K16 + kchunk - 1) / kchunk) : 1;
     g.splitk = splitk; g.kchunk = kchunk; g.atomic = splitk > 1;
     g.tm = tm; g.tn = tn; g.ntiles = tiles; g.nwg = tiles * splitk;
-    // triangular planes-output products walk PAIRS of column strips (SplitArgs::pair)
-    g.pair = (wide && Cplanes && a_lower && tm >= 2 && tn >= 2) ? 1 : 0;
+    // ---- triangular planes-output products walk PAIRS of column strips (SplitArgs::pair)
+    g.pair = (planes && o.a_lower && tm >= 2 && tn >= 2) ? 1 : 0;
     if (g.pair) { g.ntiles = tm * ((tn + 1) / 2); g.nwg = g.ntiles; }
-    g.sync = nullptr; g.sync_n = 1; g.sync_period = 0; g.sync_slots = 0;
     if (g.nwg > 2147483647LL) MXF_FAIL(h, -3, "mxf_gemm_split: grid too large");
-    if (g.atomic && beta != 1.0) {
-        if (M > 65535) MXF_FAIL(h, -3, "mxf_gemm_split: split-K path needs M<=65535");
-        dim3 gs((unsigned)((N + 255) / 256), (unsigned)M);
-        hipLaunchKernelGGL(split_scale_kernel, gs, dim3(256), 0, st, C, M, N, ldc, (float)beta, lower_only);
-    }
-    const bool dma = (M % SBM) == 0 && (N % SBN) == 0;
+    p.prescale = g.atomic && o.beta != 1.0;
+    if (p.prescale && M > 65535) MXF_FAIL(h, -3, "mxf_gemm_split: split-K path needs M<=65535");
+    // ---- grid and rendezvous
+    g.sync = nullptr; g.sync_n = 1; g.sync_period = 0; g.sync_slots = 0; g.rot_div = 0; g.maxout = nullptr;
+    p.ncounters = 0; p.grid = (unsigned)g.nwg;
     if (wide) {
-        g.maxout = (splitk == 1 && beta == 0.0 && !lower_only) ? maxout : nullptr;       // (other paths leave the word as it is: the caller sees 0)
-        // persistent: as many workgroups as fit the chip (the kernel's occupancy) walk the work items; fewer items than that: one each
-        static const int64_t wide_grid_env = MXF_KNOB("MXF_SPLIT_WIDE_GRID", 0);
-        // (planes-output products honour reserve_cus: a caller that runs a latency-bound chain next to this product leaves it some CUs)
-        int64_t wide_grid = wide_grid_env > 0 ? wide_grid_env : (WBMh == 256 ? (Cplanes ? (256 - reserve_cus) / 8 * 8 : 256) : (Cplanes ? (256 - reserve_cus) / 8 * 8 * 2 : 512));
-        // paired items: the tm roles of a pair must be resident in the same persistent round -- workgroups per XCD a multiple of tm
-        if (g.pair && wide_grid / 8 >= tm) wide_grid = (wide_grid / 8) / tm * tm * 8;
-        const int64_t grid = (wide_grid >= 8 && g.nwg > wide_grid) ? wide_grid / 8 * 8 : g.nwg;
-        // rendezvous groups (wg_rendezvous): the row tiles of one column strip (full products) / the tiles of one k split (split-K products).
-        // Strip pairs (g.pair) go without: they stay in step by construction -- every role does tm + 1 units (r05: the pairing alone takes the
-        // fabric fetch from 21.5 to 13.5 GB, with or without a rendezvous, and the product is 0.1 ms faster without one).
-        static const int sync_period_env = (int)MXF_KNOB("MXF_SPLIT_SYNC_PERIOD", 16);
-        if (Cplanes && a_lower) {
-            if (!g.pair) g.rot_div = (grid / 8) / tm > 0 ? (grid / 8) / tm : 1;       // (no rendezvous: the row tiles of a strip carry unequal work)
-        } else if (!lower_only && splitk == 1 && g.nwg % 8 == 0 && g.nwg >= 16) {
-            const int64_t q = g.nwg / 8, per_xcd = grid / 8;        // work items / resident workgroups per XCD
-            const int64_t n = tm;
-            // a group = n consecutive work items of one XCD's run, taken in the same persistent round by n different workgroups
-            const bool ok = n >= 2 && q % n == 0 && per_xcd % n == 0 && (g.nwg <= grid || g.nwg % grid == 0);
-            if (ok) {
-                g.sync = mxf_gsync(h, (unsigned)(g.nwg / n));
-                g.sync_n = (int)n; g.sync_period = 0; g.sync_slots = 0;
-            }
-        } else if (splitk > 1 && g.nwg <= grid && tiles >= 2 && sync_period_env > 0) {
-            // every tile of a k split is resident at once: they meet every `period` trips of three k blocks
-            const int64_t trips = kchunk / 3;
-            int64_t period = sync_period_env;
-            int64_t slots_per = trips / period;
-            while (slots_per * splitk > (int64_t)(MXF_NRING / 8)) { period *= 2; slots_per = trips / period; }
-            if (slots_per >= 1) {
-                g.sync = mxf_gsync(h, (unsigned)(slots_per * splitk));
-                g.sync_n = (int)tiles; g.sync_period = (int)period; g.sync_slots = (int)slots_per;
-            }
-        }
-        if (Cplanes && NH == 2) hipLaunchKernelGGL(gemm_f16x2_wide_kernel_256pl, dim3((unsigned)grid), dim3(512), 0, st, g);
-        else if (Cplanes) hipLaunchKernelGGL(gemm_f16x2_wide_kernel_128pl, dim3((unsigned)grid), dim3(256), 0, st, g);
-        else if (NH == 2 && lower_only) hipLaunchKernelGGL(gemm_f16x2_wide_kernel_256lo, dim3((unsigned)grid), dim3(512), 0, st, g);
-        else if (NH == 2) hipLaunchKernelGGL(gemm_f16x2_wide_kernel_256, dim3((unsigned)grid), dim3(512), 0, st, g);
-        else hipLaunchKernelGGL(gemm_f16x2_wide_kernel_128, dim3((unsigned)grid), dim3(256), 0, st, g);
-        MXF_LAUNCH_CHECK(h);
-        return 0;
+        g.maxout = (splitk == 1 && o.beta == 0.0 && !lower) ? o.maxout : nullptr;       // (other paths leave the word as it is: the caller sees 0)
+        split_plan_wide(p, rows, sched.reserve_cus);
     }
-    if (mode == MXF_SPLIT_F16X2) {
-        if (dma) hipLaunchKernelGGL((gemm_split_kernel<true, 2>), dim3((unsigned)g.nwg), dim3(SNT), 0, st, g);
-        else hipLaunchKernelGGL((gemm_split_kernel<false, 2>), dim3((unsigned)g.nwg), dim3(SNT), 0, st, g);
-    } else {
-        if (dma) hipLaunchKernelGGL((gemm_split_kernel<true, 3>), dim3((unsigned)g.nwg), dim3(SNT), 0, st, g);
-        else hipLaunchKernelGGL((gemm_split_kernel<false, 3>), dim3((unsigned)g.nwg), dim3(SNT), 0, st, g);
-    }
+    return 0;
+}
+
+int split_launch(mxf_ctx* h, hipStream_t st, SplitPlan& p) {
+    SplitArgs& g = p.g;
+    if (p.prescale)
+        hipLaunchKernelGGL(split_scale_kernel, dim3((unsigned)((g.N + 255) / 256), (unsigned)g.M), dim3(256), 0, st, g.C, g.M, g.N, g.ldc, g.beta, g.lower_only);
+    if (p.ncounters) g.sync = mxf_gsync(h, p.ncounters);
+    if (!g.sync) { g.sync_n = 1; g.sync_period = 0; g.sync_slots = 0; }       // no counters: no rendezvous (it is a pacing hint)
+    static void (*const kernels[])(SplitArgs) = {      // in SplitKernel's order
+        gemm_f16x2_wide_kernel_256pl, gemm_f16x2_wide_kernel_128pl, gemm_f16x2_wide_kernel_256lo, gemm_f16x2_wide_kernel_256, gemm_f16x2_wide_kernel_128,
+        gemm_split_kernel<true, 2>, gemm_split_kernel<false, 2>, gemm_split_kernel<true, 3>, gemm_split_kernel<false, 3>};
+    hipLaunchKernelGGL(kernels[p.kernel], dim3(p.grid), dim3(p.block), 0, st, g);
     MXF_LAUNCH_CHECK(h);
     return 0;
+}
+
+}  // namespace
+
+int mxf_gemm_split_internal(mxf_ctx* h, hipStream_t st, int mode, int64_t M, int64_t N, int64_t K, MxfSplitScale scale, MxfPlanes A, MxfPlanes B,
+                            MxfSplitOut out, MxfSplitSched sched) {
+    if (M <= 0 || N <= 0) return 0;
+    SplitPlan p;
+    const int rc = split_plan(h, mode, M, N, K, scale, A, B, out, sched, p);
+    return rc ? rc : split_launch(h, st, p);
 }
 
 // C ABI (f32 only): operands given as plain f32 matrices; they are split into the handle's scratch and multiplied.
@@ -1003,7 +976,8 @@ extern "C" int mxf_gemm_f32x3(mxf_handle h, int64_t M, int64_t N, int64_t K, dou
     if (rc) return rc;
     rc = mxf_split_planes_internal(h, N, K, (const float*)B, ldb, pb, st);
     if (rc) return rc;
-    return mxf_gemm_split_internal(h, M, N, K, alpha, pa, (int64_t)ea, pb, (int64_t)eb, beta, (float*)C, ldc, lower_only, st, 0);
+    return mxf_gemm_split_internal(h, st, MXF_SPLIT_BF16X3, M, N, K, {.alpha = alpha}, {pa, (int64_t)ea}, {pb, (int64_t)eb},
+                                   {.C = (float*)C, .ldc = ldc, .beta = beta, .lower_only = lower_only});
 }
 
 // The same product from two scaled f16 terms per operand and three MFMA products (see the header of this file): each operand is scaled
@@ -1030,8 +1004,8 @@ extern "C" int mxf_gemm_f16x2(mxf_handle h, int64_t M, int64_t N, int64_t K, dou
     if (rc) return rc;
     rc = mxf_split_planes_internal(h, N, K, (const float*)B, ldb, pb, st, MXF_SPLIT_F16X2, mx + 1);
     if (rc) return rc;
-    return mxf_gemm_split_internal(h, M, N, K, alpha, pa, (int64_t)ea, pb, (int64_t)eb, beta, (float*)C, ldc, lower_only, st, 0, MXF_SPLIT_F16X2,
-                                   nullptr, 0, mx, mx + 1);
+    return mxf_gemm_split_internal(h, st, MXF_SPLIT_F16X2, M, N, K, {.alpha = alpha}, {pa, (int64_t)ea, mx}, {pb, (int64_t)eb, mx + 1},
+                                   {.C = (float*)C, .ldc = ldc, .beta = beta, .lower_only = lower_only});
 }
 
 // the two halves of mxf_gemm_f16x2 for callers that reuse split operands: planes = 2 * mxf_f32x3_plane_elems(R, K) 16-bit elements,
@@ -1049,10 +1023,10 @@ extern "C" int mxf_gemm_f16x2_planes(mxf_handle h, int64_t M, int64_t N, int64_t
     if (!h) return -1;
     if (M <= 0 || N <= 0 || K <= 0 || !A_planes || !B_planes || !A_maxword || !B_maxword || !C) MXF_FAIL(h, -2, "mxf_gemm_f16x2_planes: bad argument");
     const int blocked = lower_only == 2;            // lower_only = 2: full product, C in 16-column blocks (include/mxf_gp.h)
-    return mxf_gemm_split_internal(h, M, N, K, alpha, (const unsigned short*)A_planes, (int64_t)mxf_split_plane_elems(M, K),
-                                   (const unsigned short*)B_planes, (int64_t)mxf_split_plane_elems(N, K), beta, (float*)C, blocked ? N : ldc,
-                                   blocked ? 0 : lower_only, (hipStream_t)stream, 0, MXF_SPLIT_F16X2, nullptr, 0, (const unsigned*)A_maxword,
-                                   (const unsigned*)B_maxword, blocked);
+    return mxf_gemm_split_internal(h, (hipStream_t)stream, MXF_SPLIT_F16X2, M, N, K, {.alpha = alpha},
+                                   {(const unsigned short*)A_planes, (int64_t)mxf_split_plane_elems(M, K), (const unsigned*)A_maxword},
+                                   {(const unsigned short*)B_planes, (int64_t)mxf_split_plane_elems(N, K), (const unsigned*)B_maxword},
+                                   {.C = (float*)C, .ldc = blocked ? N : ldc, .beta = beta, .lower_only = blocked ? 0 : lower_only, .blocked = blocked});
 }
 
 // the two halves of mxf_gemm_f32x3 for callers that reuse split operands: planes = 3 * mxf_f32x3_plane_elems(R, K) bf16 (uint16) elements
@@ -1068,7 +1042,8 @@ extern "C" int mxf_gemm_f32x3_planes(mxf_handle h, int64_t M, int64_t N, int64_t
                                      double beta, void* C, int64_t ldc, int lower_only, void* stream) {
     if (!h) return -1;
     if (M <= 0 || N <= 0 || K <= 0 || !A_planes || !B_planes || !C) MXF_FAIL(h, -2, "mxf_gemm_f32x3_planes: bad argument");
-    return mxf_gemm_split_internal(h, M, N, K, alpha, (const unsigned short*)A_planes, (int64_t)mxf_split_plane_elems(M, K),
-                                   (const unsigned short*)B_planes, (int64_t)mxf_split_plane_elems(N, K), beta, (float*)C, ldc, lower_only,
-                                   (hipStream_t)stream, 0);
+    return mxf_gemm_split_internal(h, (hipStream_t)stream, MXF_SPLIT_BF16X3, M, N, K, {.alpha = alpha},
+                                   {(const unsigned short*)A_planes, (int64_t)mxf_split_plane_elems(M, K)},
+                                   {(const unsigned short*)B_planes, (int64_t)mxf_split_plane_elems(N, K)},
+                                   {.C = (float*)C, .ldc = ldc, .beta = beta, .lower_only = lower_only});
 }

@@ -49,25 +49,36 @@ size_t mxf_split_plane_elems(int64_t R, int64_t K);    // elements (bf16) of ONE
 int mxf_maxabs_internal(mxf_ctx* h, int64_t R, int64_t K, const float* x, int64_t ld, unsigned* out, hipStream_t st, bool zero = true);   // out[0] = bit pattern of max |x| (zero = false: the caller cleared the word)
 int mxf_split_planes_internal(mxf_ctx* h, int64_t R, int64_t K, const float* X, int64_t ld, unsigned short* planes, hipStream_t st,
                               int mode = MXF_SPLIT_BF16X3, const unsigned* maxbits = nullptr);
-int mxf_gemm_split_internal(mxf_ctx* h, int64_t M, int64_t N, int64_t K, double alpha, const unsigned short* A, int64_t pA,
-                            const unsigned short* B, int64_t pB, double beta, float* C, int64_t ldc, int lower_only, hipStream_t st,
-                            int reserve_cus = 0, int mode = MXF_SPLIT_BF16X3, const float* ad0 = nullptr, int pow0 = 0,
-                            const unsigned* maxbits = nullptr, const unsigned* maxbits2 = nullptr, int c_blocked = 0,
-                            unsigned* maxout = nullptr, unsigned short* Cplanes = nullptr, int64_t pC = 0, int a_lower = 0,
-                            unsigned short* Ct = nullptr, int64_t pCt = 0, const float* avec = nullptr, float* Upart = nullptr);
-// (Ct: the planes output ALSO in the transposed orientation, ((m / 16) * N + n) * 16 + m % 16, plane stride pCt; avec (M floats) / Upart
-//  ((M / 128) x N floats): per 128-row band the sums of avec[m] * (hi + lo)(m, n), in the planes' units -- deterministic, summed by the caller)
-// (Cplanes != nullptr: the product is written as two f16 planes (hi + lo of alpha * A B^T, plane stride pC) in the layout of an (M x K' = N)
-//  operand, ((n / 16) * M + m) * 16 + n % 16 -- C / ldc are ignored; a_lower: A is lower triangular, the k loop of a row tile stops at its last row)
-// (maxout: the wide kernel's plain products raise this word (atomicMax) to the bit pattern of max |C|; every other path leaves it untouched)
-// gemm_bt.hip (r06): the same product with the second operand stored K-MAJOR -- C (M x N) = alpha * ad0[0] / scale(maxbits) * A (M x K) Bt (K x N),
+// The split GEMMs take plain descriptors (aggregates, every member defaulted): a call site names each optional thing it passes.
+struct MxfPlanes {                          // one split operand
+    const unsigned short* p = nullptr;      // its planes, element (r, k) at ((k / 16) * R + r) * 16 + k % 16
+    int64_t stride = 0;                     // plane stride in elements
+    const unsigned* maxbits = nullptr;      // f16x2 operand split with the scale of this max-abs word (mxf_maxabs_internal): the epilogue divides by it
+};                                          //   (nullptr: bf16x3, or a scale the caller folds into alpha / ad0, e.g. Gram planes k / variance * 2^14)
+struct MxfSplitScale { double alpha = 1.0; const float* ad0 = nullptr; int pow0 = 0; };      // the product times alpha * ad0[0]^pow0 (ad0: device scalar)
+struct MxfSplitSched { int reserve_cus = 0; };      // CUs the launch leaves to work on other streams
+struct MxfSplitOut {                        // ONE of: C (row-major, or in 16-column blocks) / planes
+    // lower_only: square output, only tiles / entries on or below the diagonal; blocked: element (m, n) at ((n / 16) * M + m) * 16 + n % 16 (ldc == N)
+    float* C = nullptr; int64_t ldc = 0; double beta = 0.0; int lower_only = 0, blocked = 0;
+    unsigned* maxout = nullptr;             // raised (atomicMax) to the bit pattern of max |C| by the kernels whose plain store path supports it; others leave it untouched
+    // the product as two f16 planes (hi + lo of alpha * A B^T) in the layout of an (M x K' = N) operand, ((n / 16) * M + m) * 16 + n % 16
+    unsigned short* planes = nullptr; int64_t pstride = 0;
+    int a_lower = 0;                        // (planes only) A is lower triangular: the k loop of a row tile stops at its last row
+    // (planes only) ALSO in the transposed orientation, ((m / 16) * N + n) * 16 + m % 16; with avec (M floats) / Upart ((M / 128) x N floats): per
+    // 128-row band the sums of avec[m] * (hi + lo)(m, n), in the planes' units -- deterministic, summed by the caller (mxf_upart_reduce_internal)
+    unsigned short* planes_t = nullptr; int64_t pstride_t = 0; const float* avec = nullptr; float* Upart = nullptr;
+};
+// C (M x N) = alpha * A (M x K) B (N x K)^T + beta * C  (gemm_split.hip); mode: the operand format of both
+int mxf_gemm_split_internal(mxf_ctx* h, hipStream_t st, int mode, int64_t M, int64_t N, int64_t K, MxfSplitScale scale, MxfPlanes A, MxfPlanes B,
+                            MxfSplitOut out, MxfSplitSched sched = {});
+// gemm_bt.hip (r06): the same product, f16x2, with the second operand stored K-MAJOR -- C (M x N) = alpha * ad0[0] / scales * A (M x K) Bt (K x N),
 // Bt = the planes of the (btR >= K rows, k' = N) operand, element (k, n) at ((n / 16) * btR + k) * 16 + n % 16: the T product of the SVGP step
-// reads the SAME Kuf planes as Psi2.  w / U / wscratch (2 K halves + one word): optional row U[n] = uscale * ad0[0] * sum_k w[k] Bt[k][n].
+// reads the SAME Kuf planes as Psi2.  scale.pow0 is 0 or 1; out: C or blocked C with maxout, beta == 0, a full product.
+// optional row U[n] = uscale * ad0[0] / scale(Bt) * sum_k w[k] Bt[k][n]; wscratch: 2 K halves + one word, caller-owned
+struct MxfBtURow { const float* w = nullptr; float* U = nullptr; double uscale = 1.0; void* wscratch = nullptr; };
 bool mxf_gemm_bt_ok(int64_t M, int64_t N, int64_t K);
-int mxf_gemm_bt_internal(mxf_ctx* h, int64_t M, int64_t N, int64_t K, double alpha, const unsigned short* A, int64_t pA, const unsigned short* Bt,
-                         int64_t pB, int64_t btR, float* C, int64_t ldc, int c_blocked, hipStream_t st, int reserve_cus = 0, const float* ad0 = nullptr,
-                         const unsigned* maxbits = nullptr, unsigned* maxout = nullptr, const float* w = nullptr, float* U = nullptr,
-                         double uscale = 1.0, void* wscratch = nullptr, const unsigned* maxbits2 = nullptr);
+int mxf_gemm_bt_internal(mxf_ctx* h, hipStream_t st, int64_t M, int64_t N, int64_t K, MxfSplitScale scale, MxfPlanes A, MxfPlanes Bt, int64_t btR,
+                         MxfSplitOut out, MxfBtURow u = {}, MxfSplitSched sched = {});
 size_t mxf_gram_planes_scratch_bytes(int64_t R, int64_t Kn, int Q);
 int mxf_gram_planes_internal(mxf_ctx* h, int kind, int64_t R, int64_t Kn, int Q, const float* Xmin, const float* Xmaj, const float* ls,
                              int ard, const float* var, unsigned short* planes, int64_t pstride, float* scratch, hipStream_t st,

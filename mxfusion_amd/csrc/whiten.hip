@@ -10,10 +10,9 @@
 // is bounded by |L^-1| ~ sqrt(cond) and |v_n|^2 <= k_nn, so the error grows like sqrt(cond) 2^-24.
 #include "common.h"
 #include "internal.h"
+#include "split_device.h"
 
 namespace {
-
-typedef unsigned int w_u32x4 __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------------------------------------------- planes transposition
 // in : two f16 planes of an (R x K) operand, element (r, k) at ((k / 16) * R + r) * 16 + k % 16       (R = M rows, K = SB columns)
@@ -42,8 +41,8 @@ __global__ __launch_bounds__(256) void planes_transpose_kernel(int64_t R, int64_
         for (int i = 0; i < 2; ++i) {
             const int u = t + 256 * i, kb = u >> 7, rl = (u & 127) >> 1, half = u & 1;
             const int64_t off = ((k0 / 16 + kb) * R + r0 + rl) * 16 + half * 8;
-            const w_u32x4 vh = *reinterpret_cast<const w_u32x4*>(in + off);
-            const w_u32x4 vl = *reinterpret_cast<const w_u32x4*>(in + pin + off);
+            const u32x4 vh = *reinterpret_cast<const u32x4*>(in + off);
+            const u32x4 vl = *reinterpret_cast<const u32x4*>(in + pin + off);
             const float ar = PT > 0 ? a[r0 + rl] : 0.f;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -60,11 +59,11 @@ __global__ __launch_bounds__(256) void planes_transpose_kernel(int64_t R, int64_
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int u = t + 256 * i, rb = u >> 7, kl = (u & 127) >> 1, half = u & 1;
-            const w_u32x4 vh = *reinterpret_cast<const w_u32x4*>(&tile[0][kl * TRS + rb * 16 + half * 8]);
-            const w_u32x4 vl = *reinterpret_cast<const w_u32x4*>(&tile[1][kl * TRS + rb * 16 + half * 8]);
+            const u32x4 vh = *reinterpret_cast<const u32x4*>(&tile[0][kl * TRS + rb * 16 + half * 8]);
+            const u32x4 vl = *reinterpret_cast<const u32x4*>(&tile[1][kl * TRS + rb * 16 + half * 8]);
             const int64_t off = ((r0 / 16 + rb) * K + k0 + kl) * 16 + half * 8;
-            __builtin_nontemporal_store(vh, reinterpret_cast<w_u32x4*>(out + off));
-            __builtin_nontemporal_store(vl, reinterpret_cast<w_u32x4*>(out + pout + off));
+            __builtin_nontemporal_store(vh, reinterpret_cast<u32x4*>(out + off));
+            __builtin_nontemporal_store(vl, reinterpret_cast<u32x4*>(out + pout + off));
         }
         __syncthreads();
     }
@@ -123,11 +122,11 @@ extern "C" int mxf_gemm_f16x2_planes_out(mxf_handle h, int64_t M, int64_t N, int
         upart = (float*)mxf_ws(h, sizeof(float) * (size_t)(M / 128) * (size_t)N);
         if (!upart) MXF_FAIL(h, -4, "mxf_gemm_f16x2_planes_out: cannot allocate the partial sums");
     }
-    int rc = mxf_gemm_split_internal(h, M, N, K, alpha, (const unsigned short*)A_planes, (int64_t)mxf_split_plane_elems(M, K), (const unsigned short*)B_planes,
-                                     (int64_t)mxf_split_plane_elems(N, K), 0.0, nullptr, N, 0, (hipStream_t)stream, 0, MXF_SPLIT_F16X2, nullptr, 0,
-                                     (const unsigned*)A_maxword, (const unsigned*)B_maxword, 0, nullptr, (unsigned short*)C_planes,
-                                     (int64_t)mxf_split_plane_elems(M, N), a_lower, (unsigned short*)Ct_planes, (int64_t)mxf_split_plane_elems(N, M),
-                                     (const float*)a, upart);
+    int rc = mxf_gemm_split_internal(h, (hipStream_t)stream, MXF_SPLIT_F16X2, M, N, K, {.alpha = alpha},
+                                     {(const unsigned short*)A_planes, (int64_t)mxf_split_plane_elems(M, K), (const unsigned*)A_maxword},
+                                     {(const unsigned short*)B_planes, (int64_t)mxf_split_plane_elems(N, K), (const unsigned*)B_maxword},
+                                     {.planes = (unsigned short*)C_planes, .pstride = (int64_t)mxf_split_plane_elems(M, N), .a_lower = a_lower,
+                                      .planes_t = (unsigned short*)Ct_planes, .pstride_t = (int64_t)mxf_split_plane_elems(N, M), .avec = (const float*)a, .Upart = upart});
     if (rc || !U) return rc;
     return mxf_upart_reduce_internal(h, N, (int)(M / 128), upart, nullptr, 1.f, (float*)U, (hipStream_t)stream);
 }
