@@ -312,6 +312,36 @@ int mxf_normal_logpdf(mxf_handle h, int dtype, int S, int64_t n, const void* x,
 int mxf_normal_reparam_bwd(mxf_handle h, int dtype, int S, int64_t n, const void* var, const void* eps,
                            const void* dx, void* dmean_acc, void* dvar_acc, void* stream);
 
+/* Log-densities of the univariate family, x the random variable, (a, b) the two parameters in the reference's order:
+ *   MXF_D_GAMMA     (alpha, beta)      (a-1) log x - b x - lgamma(a) + a log b                      Gamma.log_pdf_impl (gamma.py:45-59)
+ *   MXF_D_GAMMA_MV  (mean, variance)   Gamma with b = mean/variance, a = mean b                     GammaMeanVariance (gamma.py:127-159)
+ *   MXF_D_BETA      (alpha, beta)      (a-1) log x + (b-1) log(1-x) - lgamma(a) - lgamma(b) + lgamma(a+b)   Beta.log_pdf_impl (beta.py:46-68)
+ *   MXF_D_LAPLACE   (location, scale)  -log(2b) - |x-a|/b                                           Laplace.log_pdf_impl (laplace.py:37-55)
+ *   MXF_D_UNIFORM   (low, high)        -log(b-a) where a <= x < b, else -inf                        Uniform.log_pdf_impl (uniform.py:38-62)
+ * mxf_univariate_logpdf has the contract of mxf_normal_logpdf: out += scale * sum_{s,i} log p(x[s,i] | a[i], b[i]) (factor_graph.py:223),
+ * optional reverse mode accumulated into dx (S,n), da (n_a), db (n_b), all scaled by `scale`; n_a, n_b in {1, n}; any output may be null.
+ * Gradients are closed forms (digamma for the Gamma and Beta parameters; GAMMA_MV chained to mean and variance; Laplace d/dx =
+ * -sign(x-a)/b with sign(0) = 0; Uniform dx = 0, da = 1/(b-a), db = -1/(b-a) inside the support; outside it nothing is added to any
+ * gradient, whatever the weight).  A sum that holds an element outside the Uniform's support is -inf for scale > 0, +inf for scale < 0
+ * and NaN (0 * inf) for scale == 0.                                                                                                    */
+enum { MXF_D_GAMMA = 0, MXF_D_GAMMA_MV = 1, MXF_D_BETA = 2, MXF_D_LAPLACE = 3, MXF_D_UNIFORM = 4 };
+int mxf_univariate_logpdf(mxf_handle h, int kind, int dtype, int S, int64_t n, const void* x,
+                          const void* a, int64_t n_a, const void* b, int64_t n_b, double scale,
+                          void* out_acc, void* dx_acc, void* da_acc, void* db_acc, void* stream);
+
+/* The un-reduced log-density that Distribution.log_pdf returns: out[s,i] = scale * log p(x[s,i] | a, b), WRITTEN.  A parameter has no
+ * sample axis (strideS = 0, n_a in {1, n}) or a full one (strideS = n, n_a = n: a is (S,n)).  Forward only.                            */
+int mxf_univariate_logpdf_elem(mxf_handle h, int kind, int dtype, int S, int64_t n, const void* x,
+                               const void* a, int64_t n_a, int64_t strideS_a, const void* b, int64_t n_b, int64_t strideS_b,
+                               double scale, void* out, void* stream);
+
+/* Reverse mode of mxf_univariate_logpdf_elem -- the reduced kernel's gradients with the cotangent cot (S,n) in the place of `scale`:
+ * dx[s,i] += scale * cot[s,i] * dlogp/dx, and likewise da, db: summed over s for a parameter without sample axis ((n_a) elements, a
+ * single-element one also over i), (S,n) for a parameter with one.  Any output may be null.                                            */
+int mxf_univariate_logpdf_bwd(mxf_handle h, int kind, int dtype, int S, int64_t n, const void* x,
+                              const void* a, int64_t n_a, int64_t strideS_a, const void* b, int64_t n_b, int64_t strideS_b,
+                              const void* cot, double scale, void* dx_acc, void* da_acc, void* db_acc, void* stream);
+
 /* MXNet Adam as driven by gluon.Trainer.step (batch_loop.py:46-60, minibatch_loop.py:71-91):
  * g*=rescale; m=b1 m+(1-b1)g; v=b2 v+(1-b2)g^2; w -= lr*sqrt(1-b2^t)/(1-b1^t) * m/(sqrt(v)+eps)      */
 int mxf_adam_step(mxf_handle h, int dtype, int64_t n, void* w, const void* g, void* m, void* v,

@@ -1,7 +1,7 @@
 """Noise source for reparameterised sampling: the injection seam of
 mxfusion/components/distributions/random_gen.py:21-98 (tests use a mock that replays a caller-supplied
-buffer, util/testutils.py:58-93).  Drawing the N(0,1) noise itself is plumbing (torch's Philox on the device);
-everything downstream of eps is HIP."""
+buffer, util/testutils.py:58-93).  Drawing the noise itself (N(0,1), uniform, Laplace, Gamma) is plumbing (torch's generators on
+the device); everything downstream of it is HIP."""
 import torch
 
 
@@ -9,6 +9,25 @@ class RandomGenerator(object):
     @staticmethod
     def sample_normal(loc=0, scale=1, shape=None, dtype=None, out=None, ctx=None, F=None):
         raise NotImplementedError
+
+    @staticmethod
+    def sample_gamma(alpha=1, beta=1, shape=None, dtype=None, out=None, ctx=None, F=None):
+        raise NotImplementedError
+
+    @staticmethod
+    def sample_uniform(low=0., high=1., shape=None, dtype=None, out=None, ctx=None, F=None):
+        raise NotImplementedError
+
+    @staticmethod
+    def sample_laplace(location=0., scale=1., shape=None, dtype=None, out=None, ctx=None, F=None):
+        raise NotImplementedError
+
+
+def _numel(shape):
+    n = 1
+    for s in shape or ():
+        n *= int(s)
+    return n
 
 
 class TorchRandomGenerator(RandomGenerator):
@@ -22,6 +41,33 @@ class TorchRandomGenerator(RandomGenerator):
             eps = eps + loc
         return eps
 
+    @staticmethod
+    def sample_gamma(alpha=1, beta=1, shape=None, dtype=None, out=None, ctx=None, F=None):
+        """random_gen.py:141-160: alpha the shape, beta the RATE; array parameters of shape (x, y) give (x, y) + shape draws."""
+        from ...common import config
+        shape = tuple(shape or ())
+        if not isinstance(alpha, torch.Tensor):
+            alpha = torch.full((), float(alpha), dtype=config.torch_dtype(dtype), device=ctx or config.get_default_device())
+        beta = torch.as_tensor(beta, dtype=alpha.dtype, device=alpha.device)
+        alpha, beta = torch.broadcast_tensors(alpha, beta)
+        full = tuple(alpha.shape) + shape
+        tail = (Ellipsis,) + (None,) * len(shape)
+        return torch.distributions.Gamma(alpha[tail].expand(full), beta[tail].expand(full), validate_args=False).sample()
+
+    @staticmethod
+    def sample_uniform(low=0., high=1., shape=None, dtype=None, out=None, ctx=None, F=None):
+        """random_gen.py:163-183: uniform on [low, high)."""
+        from ...common import config
+        u = torch.rand(tuple(shape or ()), dtype=config.torch_dtype(dtype), device=ctx or config.get_default_device())
+        return u * (high - low) + low
+
+    @staticmethod
+    def sample_laplace(location=0., scale=1., shape=None, dtype=None, out=None, ctx=None, F=None):
+        """random_gen.py:186-219: U uniform on [-1/2, 1/2), location - scale sign(U) log(1 - 2 |U|); the one U = -1/2 the generator can
+        return would be log 0, an infinite draw: the argument of the logarithm is kept at the smallest normal number."""
+        U = TorchRandomGenerator.sample_uniform(low=-0.5, high=0.5, shape=shape, dtype=dtype, ctx=ctx)
+        return location - scale * torch.sign(U) * torch.log((1 - 2 * torch.abs(U)).clamp_min(torch.finfo(U.dtype).tiny))
+
 
 MXNetRandomGenerator = TorchRandomGenerator   # source-compatible alias
 
@@ -33,13 +79,25 @@ class MockRandomGenerator(RandomGenerator):
         self._samples = samples.reshape(-1)
         self._pos = 0
 
-    def sample_normal(self, loc=0, scale=1, shape=None, dtype=None, out=None, ctx=None, F=None):
-        n = 1
-        for s in shape:
-            n *= int(s)
+    def _replay(self, shape):
+        shape = tuple(shape)
+        n = _numel(shape)
         idx = (torch.arange(n, device=self._samples.device) + self._pos) % self._samples.numel()
         self._pos = (self._pos + n) % self._samples.numel()
-        return self._samples[idx].reshape(tuple(shape)).clone()
+        return self._samples[idx].reshape(shape).clone()
+
+    def sample_normal(self, loc=0, scale=1, shape=None, dtype=None, out=None, ctx=None, F=None):
+        return self._replay(shape)
+
+    def sample_gamma(self, alpha=1, beta=1, shape=None, dtype=None, out=None, ctx=None, F=None):
+        """testutils.py:83-87: the buffer in the shape of the draw, alpha's shape followed by `shape`."""
+        return self._replay((tuple(alpha.shape) if isinstance(alpha, torch.Tensor) else ()) + tuple(shape or ()))
+
+    def sample_uniform(self, low=0., high=1., shape=None, dtype=None, out=None, ctx=None, F=None):
+        return self._replay(shape)
+
+    def sample_laplace(self, location=0., scale=1., shape=None, dtype=None, out=None, ctx=None, F=None):
+        return self._replay(shape)
 
 
 MockMXNetRandomGenerator = MockRandomGenerator

@@ -330,6 +330,23 @@ __device__ __forceinline__ T block_sum(T v, T* smem /* >= 16 */) {
 __device__ __forceinline__ void atomic_add(float* p, float v) { unsafeAtomicAdd(p, v); }
 __device__ __forceinline__ void atomic_add(double* p, double v) { unsafeAtomicAdd(p, v); }
 
+// kernels that end in ONE same-address atomic per workgroup (the scalar sums of normal_logpdf_kernel and univariate_logpdf_kernel): 2048 of them serialise at the L2
+// (~15 ns apiece: 33 us for the 2 M-element log-pdf of a 4-sample step, of which the data take 6) -- two workgroups per CU
+static inline unsigned grid_for_reduce(int64_t n) {
+    int64_t b = (n + 255) / 256;
+    if (b < 1) b = 1;
+    if (b > 512) b = 512;
+    return (unsigned)b;
+}
+
+// grid-stride elementwise kernels without such an atomic
+static inline unsigned grid_for(int64_t n) {
+    int64_t b = (n + 255) / 256;
+    if (b < 1) b = 1;
+    if (b > 2048) b = 2048;
+    return (unsigned)b;
+}
+
 // C-ABI entry points implemented across translation units share these internal (typed) launchers
 
 // ---- float64 exponentials of the Gram kernels (arguments are never positive) ------------------------------------------------------

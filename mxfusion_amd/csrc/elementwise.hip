@@ -150,20 +150,6 @@ __global__ void diag_of_kernel(int64_t total, int64_t n, const T* __restrict__ g
     }
 }
 
-// kernels that end in ONE same-address atomic per workgroup (the scalar sums of normal_logpdf_kernel): 2048 of them serialise at the L2
-// (~15 ns apiece: 33 us for the 2 M-element log-pdf of a 4-sample step, of which the data take 6) -- two workgroups per CU
-inline unsigned grid_for_reduce(int64_t n) {
-    int64_t b = (n + 255) / 256;
-    if (b < 1) b = 1;
-    if (b > 512) b = 512;
-    return (unsigned)b;
-}
-inline unsigned grid_for(int64_t n) {
-    int64_t b = (n + 255) / 256;
-    if (b < 1) b = 1;
-    if (b > 2048) b = 2048;
-    return (unsigned)b;
-}
 
 }  // namespace
 

@@ -152,6 +152,11 @@ class InferenceParameters(object):
             return self._flat.detach()[o:o + n].view(shape)
         return self._fixed[u]
 
+    def grad(self, key):
+        """Gradient of the last backward pass w.r.t. the stored (unconstrained) value of a trainable parameter: a view of the flat gradient."""
+        o, n, shape = self._slices[key.uuid if isinstance(key, Variable) else key]
+        return self._flat.grad[o:o + n].view(shape)
+
     def __contains__(self, key):
         u = key.uuid if isinstance(key, Variable) else key
         return u in self._slices or u in self._fixed

@@ -353,6 +353,66 @@ def normal_logpdf_(x, mean, var, scale, out_acc, dx_acc=None, dmean_acc=None, dv
     return out_acc
 
 
+D_KIND = {'gamma': _lib.D_GAMMA, 'gamma_mv': _lib.D_GAMMA_MV, 'beta': _lib.D_BETA, 'laplace': _lib.D_LAPLACE, 'uniform': _lib.D_UNIFORM}
+
+
+def _uni_check(x, *others):
+    """the univariate entry points take raw pointers: every operand contiguous, on x's device, of x's dtype"""
+    _require_gpu(x)
+    for t in (x,) + others:
+        if t is None:
+            continue
+        if t.dtype != x.dtype or t.device != x.device:
+            raise TypeError('univariate log-pdf: every operand must have the dtype and device of x (%s, %s); got %s, %s'
+                            % (x.dtype, x.device, t.dtype, t.device))
+        if not t.is_contiguous():
+            raise ValueError('univariate log-pdf: operands must be contiguous')
+
+
+def _uni_param(p, S, n):
+    """(number of elements per sample, sample stride) of a parameter: 1 or n elements without a sample axis, or (S, n) with one"""
+    if p.numel() in (1, n):
+        return p.numel(), 0
+    if p.numel() == S * n:
+        return n, n
+    raise ValueError('univariate log-pdf: a parameter has 1, n or S*n elements (n = %d, S = %d), got %d' % (n, S, p.numel()))
+
+
+def univariate_logpdf_(kind, x, a, b, scale, out_acc, dx_acc=None, da_acc=None, db_acc=None):
+    """out_acc += scale * sum_{s,i} log p(x[s,i] | a[i], b[i]) for kind in D_KIND (+ reverse mode into the *_acc buffers); x (S, n...),
+    a and b of 1 or n elements (mxf_univariate_logpdf)."""
+    _uni_check(x, a, b, out_acc, dx_acc, da_acc, db_acc)
+    S = x.shape[0]
+    n = x.numel() // S
+    _lib.call('mxf_univariate_logpdf', _h(x), D_KIND[kind] if isinstance(kind, str) else kind, _dt(x), S, n, _p(x), _p(a), a.numel(),
+              _p(b), b.numel(), float(scale), _p(out_acc), _p(dx_acc), _p(da_acc), _p(db_acc), _stream())
+    return out_acc
+
+
+def univariate_logpdf_elem(kind, x, a, b, scale=1.0):
+    """scale * log p(x[s,i] | a, b), shaped like x (S, n...); a and b of 1 or n elements, or S*n (a sample axis of their own)
+    (mxf_univariate_logpdf_elem)."""
+    _uni_check(x, a, b)
+    S = x.shape[0]
+    n = x.numel() // S
+    (n_a, ss_a), (n_b, ss_b) = _uni_param(a, S, n), _uni_param(b, S, n)
+    out = torch.empty_like(x)
+    _lib.call('mxf_univariate_logpdf_elem', _h(x), D_KIND[kind] if isinstance(kind, str) else kind, _dt(x), S, n, _p(x), _p(a), n_a, ss_a,
+              _p(b), n_b, ss_b, float(scale), _p(out), _stream())
+    return out
+
+
+def univariate_logpdf_bwd_(kind, x, a, b, cot, scale, dx_acc=None, da_acc=None, db_acc=None):
+    """Reverse mode of univariate_logpdf_elem: dx_acc (S, n...), da_acc, db_acc (shaped like a, b) += scale * cot * d log p / d(.)
+    (mxf_univariate_logpdf_bwd)."""
+    _uni_check(x, a, b, cot, dx_acc, da_acc, db_acc)
+    S = x.shape[0]
+    n = x.numel() // S
+    (n_a, ss_a), (n_b, ss_b) = _uni_param(a, S, n), _uni_param(b, S, n)
+    _lib.call('mxf_univariate_logpdf_bwd', _h(x), D_KIND[kind] if isinstance(kind, str) else kind, _dt(x), S, n, _p(x), _p(a), n_a, ss_a,
+              _p(b), n_b, ss_b, _p(cot), float(scale), _p(dx_acc), _p(da_acc), _p(db_acc), _stream())
+
+
 def adam_step_(w, g, m, v, lr, t, beta1=0.9, beta2=0.999, epsilon=1e-8, rescale_grad=1.0):
     _lib.call('mxf_adam_step', _h(w), _dt(w), w.numel(), _p(w), _p(g), _p(m), _p(v), float(lr), float(beta1), float(beta2),
               float(epsilon), float(rescale_grad), int(t), _stream())
