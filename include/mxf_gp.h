@@ -342,6 +342,37 @@ int mxf_univariate_logpdf_bwd(mxf_handle h, int kind, int dtype, int S, int64_t 
                               const void* a, int64_t n_a, int64_t strideS_a, const void* b, int64_t n_b, int64_t strideS_b,
                               const void* cot, double scale, void* dx_acc, void* da_acc, void* db_acc, void* stream);
 
+/* Multivariate normal of order n <= 32 over x (S, B, n), mean (S|1, B|1, n) and A (S|1, B|1, n, n): A is the covariance (form 0) or the
+ * precision (form 1).  A larger n is status -3 from every entry point, and no buffer is touched (such matrices take mxf_potrf /
+ * mxf_trsm).  Replaces MultivariateNormal.log_pdf_impl (components/distributions/normal.py:157-178: linalg.potrf, linalg.trsm,
+ * linalg.sumlogdiag) and MultivariateNormalMeanPrecision.log_pdf_impl (normal.py:369-394: the per-row F.dot loop and log_determinant),
+ * and MXNet autograd through them.  Launch-bound at the sizes of a prior: one launch each, two for the reverse mode with dA.
+ *
+ * mxf_mvn_factor: the S_A * B_A distinct matrices of A (row stride lda, sample and batch strides in elements; an axis that A is shared
+ * over has extent 1) -> F (S_A, B_A, n, n) dense, lower with a zero upper triangle: L^-1 of A = L L^T (form 0) or L itself (form 1), and
+ * logdet (S_A, B_A) = sum_i log L_ii.  info: device int[S_A * B_A], zeroed by the caller; a matrix whose j-th pivot is not positive gets
+ * info = j (1-based, its first such pivot, as mxf_potrf), NaN in logdet and NaN from that column on in F.  The call still returns 0.
+ * float32 forms the pivot sums and the log-determinant in double.                                                                      */
+int mxf_mvn_factor(mxf_handle h, int dtype, int form, int S_A, int64_t B_A, int n, const void* A, int64_t lda, int64_t strideS_A,
+                   int64_t strideB_A, void* F, void* logdet, int* info, void* stream);
+
+/* out[s,b] = scale * log N(x[s,b] | mean, A), WRITTEN, from the factor stage's F and logdet; S_A in {1, S}, B_A in {1, B} say which axes
+ * the matrices have.  x: rows of n contiguous elements, batch stride n, sample stride strideS_x (0: shared by the samples); mean: sample
+ * and batch stride, either may be 0.  form 0: z = L^-1 (x - mean), -1/2 |z|^2 - logdet - n/2 log 2 pi (normal.py:173-178);
+ * form 1: z = L^T (x - mean), + logdet (normal.py:384-394).                                                                            */
+int mxf_mvn_logpdf(mxf_handle h, int dtype, int form, int S, int64_t B, int n, const void* x, int64_t strideS_x, const void* mean,
+                   int64_t strideS_mean, int64_t strideB_mean, const void* F, const void* logdet, int S_A, int64_t B_A, double scale,
+                   void* out, void* stream);
+
+/* Reverse mode of mxf_mvn_logpdf with the cotangent cot (S, B): w = scale * cot[s,b], alpha = A^-1 (x - mean) (form 1: A (x - mean)),
+ *   dx -= w alpha,  dmean += w alpha,  dA += 1/2 w (alpha alpha^T - A^-1)   (form 1: dA += 1/2 w (A^-1 - d d^T), d = x - mean)
+ * ACCUMULATED into dense buffers shaped like their operands -- dx (S|1, B, n), dmean (S|1, B|1, n), dA (S_A, B_A, n, n), symmetric -- and
+ * summed over the axes an operand is shared over.  The term in A^-1 is added once per distinct matrix with the summed weight.  Any
+ * output may be null.                                                                                                                   */
+int mxf_mvn_logpdf_bwd(mxf_handle h, int dtype, int form, int S, int64_t B, int n, const void* x, int64_t strideS_x, const void* mean,
+                       int64_t strideS_mean, int64_t strideB_mean, const void* F, int S_A, int64_t B_A, const void* cot, double scale,
+                       void* dx_acc, void* dmean_acc, void* dA_acc, void* stream);
+
 /* MXNet Adam as driven by gluon.Trainer.step (batch_loop.py:46-60, minibatch_loop.py:71-91):
  * g*=rescale; m=b1 m+(1-b1)g; v=b2 v+(1-b2)g^2; w -= lr*sqrt(1-b2^t)/(1-b1^t) * m/(sqrt(v)+eps)      */
 int mxf_adam_step(mxf_handle h, int dtype, int64_t n, void* w, const void* g, void* m, void* v,

@@ -413,6 +413,74 @@ def univariate_logpdf_bwd_(kind, x, a, b, cot, scale, dx_acc=None, da_acc=None, 
               _p(b), n_b, ss_b, _p(cot), float(scale), _p(dx_acc), _p(da_acc), _p(db_acc), _stream())
 
 
+MVN_MAX_ORDER = 32      # the order up to which the mxf_mvn_* entry points run (MVN_MAX of mvn.hip)
+
+
+def _mvn_check(ref, *others):
+    """the mxf_mvn_* entry points take raw pointers: every operand on ref's device and of its dtype"""
+    _require_gpu(ref)
+    for t in others:
+        if t is not None and (t.dtype != ref.dtype or t.device != ref.device):
+            raise TypeError('multivariate normal: every operand must have the dtype and device of the first (%s, %s); got %s, %s'
+                            % (ref.dtype, ref.device, t.dtype, t.device))
+
+
+def _mvn_axis(t, dim):
+    """(extent, stride in elements) of a leading axis; an axis of extent 1 or an expanded one (stride 0) is a broadcast: (1, 0)"""
+    return (1, 0) if t.shape[dim] == 1 or t.stride(dim) == 0 else (int(t.shape[dim]), int(t.stride(dim)))
+
+
+def _mvn_rows(x, mean):
+    """x (S|1, B, n) and mean (S|1, B|1, n) as the entry points take them -- rows of n contiguous elements, x at batch stride n -- and their
+    strides.  An operand that already has that layout, expanded axes included, is passed as it is."""
+    n = x.shape[-1]
+    if x.stride(2) != 1 or (x.shape[1] > 1 and x.stride(1) != n):
+        x = x.contiguous()
+    if mean.stride(2) != 1:
+        mean = mean.contiguous()
+    return x, _mvn_axis(x, 0)[1], mean, _mvn_axis(mean, 0)[1], _mvn_axis(mean, 1)[1]
+
+
+def mvn_factor(A, form=0):
+    """(F, logdet, info) of A (S|1, B|1, n, n), n <= 32 (mxf_mvn_factor): per distinct matrix -- an expanded axis counts as 1 -- the lower
+    factor F (S_A, B_A, n, n) of the covariance inverted (form 0) or of the precision itself (form 1), logdet (S_A, B_A) = sum log L_ii and
+    the int32 info word (0, or the 1-based index of the first pivot that is not positive)."""
+    _mvn_check(A)
+    if A.stride(-1) != 1:
+        A = A.contiguous()
+    n = A.shape[-1]
+    (S_A, ss), (B_A, sb) = _mvn_axis(A, 0), _mvn_axis(A, 1)
+    F = torch.empty((S_A, B_A, n, n), dtype=A.dtype, device=A.device)
+    logdet = torch.empty((S_A, B_A), dtype=A.dtype, device=A.device)
+    info = torch.zeros((S_A, B_A), dtype=torch.int32, device=A.device)
+    _lib.call('mxf_mvn_factor', _h(A), _dt(A), int(form), S_A, B_A, n, _p(A), A.stride(-2), ss, sb, _p(F), _p(logdet), _p(info), _stream())
+    return F, logdet, info
+
+
+def mvn_logpdf(x, mean, F, logdet, form=0, scale=1.0):
+    """scale * log N(x[s,b] | mean, A) (S, B) from mvn_factor's F and logdet; x (S|1, B, n), mean (S|1, B|1, n) (mxf_mvn_logpdf)."""
+    _mvn_check(x, mean, F, logdet)
+    S, B, n = max(x.shape[0], mean.shape[0], F.shape[0]), x.shape[1], x.shape[2]
+    x, ss_x, mean, ss_m, sb_m = _mvn_rows(x, mean)
+    out = torch.empty((S, B), dtype=x.dtype, device=x.device)
+    _lib.call('mxf_mvn_logpdf', _h(x), _dt(x), int(form), S, B, n, _p(x), ss_x, _p(mean), ss_m, sb_m, _p(F), _p(logdet), F.shape[0],
+              F.shape[1], float(scale), _p(out), _stream())
+    return out
+
+
+def mvn_logpdf_bwd_(x, mean, F, cot, form=0, scale=1.0, dx_acc=None, dmean_acc=None, dA_acc=None):
+    """Reverse mode of mvn_logpdf: dx_acc (S|1, B, n), dmean_acc (S|1, B|1, n), dA_acc (S_A, B_A, n, n) -- dense, shaped like their operands
+    with the shared axes at extent 1 -- += the gradients under the cotangent cot (S, B) (mxf_mvn_logpdf_bwd)."""
+    _mvn_check(x, mean, F, cot, dx_acc, dmean_acc, dA_acc)
+    for t in (cot, dx_acc, dmean_acc, dA_acc):
+        if t is not None and not t.is_contiguous():
+            raise ValueError('multivariate normal: the cotangent and the gradient buffers must be contiguous')
+    S, B, n = cot.shape[0], x.shape[1], x.shape[2]
+    x, ss_x, mean, ss_m, sb_m = _mvn_rows(x, mean)
+    _lib.call('mxf_mvn_logpdf_bwd', _h(x), _dt(x), int(form), S, B, n, _p(x), ss_x, _p(mean), ss_m, sb_m, _p(F), F.shape[0], F.shape[1],
+              _p(cot), float(scale), _p(dx_acc), _p(dmean_acc), _p(dA_acc), _stream())
+
+
 def adam_step_(w, g, m, v, lr, t, beta1=0.9, beta2=0.999, epsilon=1e-8, rescale_grad=1.0):
     _lib.call('mxf_adam_step', _h(w), _dt(w), w.numel(), _p(w), _p(g), _p(m), _p(v), float(lr), float(beta1), float(beta2),
               float(epsilon), float(rescale_grad), int(t), _stream())

@@ -1,0 +1,106 @@
+"""CPU tests of MultivariateNormal and MultivariateNormalMeanPrecision: the classes import and construct with the reference's names, argument
+order and defaults (mxfusion/components/distributions/normal.py:119-237, :332-456), the entry points are declared, bound and exported,
+and nothing runs without a GPU."""
+import ctypes
+import inspect
+import os
+
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_SYMBOLS = ('mxf_mvn_factor', 'mxf_mvn_logpdf', 'mxf_mvn_logpdf_bwd')
+
+
+def _classes():
+    from mxfusion_amd.components.distributions import MultivariateNormal, MultivariateNormalMeanPrecision
+    return (MultivariateNormal, 'covariance'), (MultivariateNormalMeanPrecision, 'precision')
+
+
+def test_entry_points_are_declared_bound_and_exported():
+    from mxfusion_amd import _lib, ops
+    header = open(os.path.join(ROOT, 'include', 'mxf_gp.h')).read()
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    for name in NEW_SYMBOLS:
+        assert name + '(' in header and name in _lib.ALL_SYMBOLS and getattr(lib, name, None) is not None, name
+    for cite in ('normal.py:157-178', 'normal.py:369-394'):
+        assert cite in header, cite
+    assert ops.MVN_MAX_ORDER == 32
+    for wrapper in ('mvn_factor', 'mvn_logpdf', 'mvn_logpdf_bwd_'):
+        assert callable(getattr(ops, wrapper))
+
+
+def test_constructor_signatures_are_the_reference_ones():
+    for cls, matrix in _classes():
+        assert list(inspect.signature(cls.__init__).parameters) == ['self', 'mean', matrix, 'rand_gen', 'minibatch_ratio', 'dtype', 'ctx']
+        sig = inspect.signature(cls.define_variable)
+        assert list(sig.parameters) == ['shape', 'mean', matrix, 'rand_gen', 'minibatch_ratio', 'dtype', 'ctx']
+        assert sig.parameters['mean'].default == 0. and sig.parameters[matrix].default is None and sig.parameters['minibatch_ratio'].default == 1.
+        assert sig.parameters['shape'].default is inspect.Parameter.empty
+
+
+def test_construct_wiring_and_names():
+    from mxfusion_amd import Variable
+    from mxfusion_amd.components.distributions import Distribution
+    from mxfusion_amd.components.variables.variable import VariableType
+    for cls, matrix in _classes():
+        mean, mat = Variable(shape=(3,)), Variable(shape=(3, 3))
+        f = cls(mean, mat, dtype='float64')
+        assert isinstance(f, Distribution)
+        assert f.input_names == ['mean', matrix] and f.output_names == ['random_variable']
+        assert [n for n, _ in f.inputs] == ['mean', matrix] and f.inputs[0][1] is mean and f.inputs[1][1] is mat
+        assert getattr(f, matrix) is mat and f.mean is mean and f.outputs == [] and f.log_pdf_scaling == 1
+        v = cls.define_variable(shape=(4, 3), mean=mean, dtype='float64', **{matrix: mat})
+        assert v.factor.inputs[1][1] is mat and v.shape == (4, 3) and v.type == VariableType.RANDVAR
+        assert [n for n, _ in v.factor.outputs] == ['random_variable'] and v.factor.random_variable is v
+
+
+def test_define_variable_defaults_to_the_identity():
+    for cls, matrix in _classes():
+        for dtype, tdt in (('float64', torch.float64), ('float32', torch.float32), (None, torch.float32)):
+            f = cls.define_variable(shape=(7, 4), dtype=dtype).factor
+            mean, mat = f.inputs[0][1], f.inputs[1][1]
+            assert mat.isConstant and mat.constant.dtype == tdt and torch.equal(mat.constant, torch.eye(4, dtype=tdt))
+            assert mean.isConstant and mean.constant == 0.
+
+
+def test_replicate_self():
+    """factor.py:121-143 through normal.py:144-155: same class, names and UUID; no inputs or outputs yet; the distribution's settings kept"""
+    from mxfusion_amd.components.distributions.random_gen import MockRandomGenerator
+    gen = MockRandomGenerator(torch.zeros(4))
+    for cls, matrix in _classes():
+        f = cls.define_variable(shape=(3,), rand_gen=gen, dtype='float64').factor
+        f.log_pdf_scaling = 8
+        rep = f.replicate_self()
+        assert type(rep) is cls and rep is not f and rep.uuid == f.uuid
+        assert rep.input_names == ['mean', matrix] and rep.output_names == ['random_variable'] and rep.input_names is not f.input_names
+        assert rep.inputs == [] and rep.outputs == []
+        assert rep._rand_gen is gen and rep.dtype == 'float64' and rep.log_pdf_scaling == 8
+        assert len(f.inputs) == 2 and len(f.outputs) == 1                        # the original keeps its wiring
+
+
+def test_leading_dimensions_flatten_into_one_batch_axis():
+    """the operand shapes the kernels are given: (S|1, B|1, ...), an expanded leading axis back at extent 1"""
+    from mxfusion_amd.components.distributions.mvn import _flatten
+    x = torch.zeros(2, 5, 7, 3)
+    assert tuple(_flatten(x, (5, 7), (3,), full=True).shape) == (2, 35, 3)
+    assert tuple(_flatten(torch.zeros(1, 1), (5, 7), (3,)).shape) == (1, 1, 3)                                   # a scalar mean
+    assert tuple(_flatten(torch.zeros(1, 7, 3), (5, 7), (3,)).shape) == (1, 35, 3)                               # shared over one of two
+    assert tuple(_flatten(torch.eye(3)[None], (5, 7), (3, 3)).shape) == (1, 1, 3, 3)
+    assert tuple(_flatten(torch.eye(3)[None].expand(2, 3, 3), (5, 7), (3, 3)).shape) == (1, 1, 3, 3)             # expanded, not sampled
+    assert tuple(_flatten(torch.zeros(2, 5, 7, 3, 3), (5, 7), (3, 3)).shape) == (2, 35, 3, 3)
+    assert tuple(_flatten(torch.zeros(1, 3), (), (3,), full=True).shape) == (1, 1, 3)
+    with pytest.raises(ValueError):
+        _flatten(torch.eye(3), (), (3, 3))                                                                       # no sample axis
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason='checks the no-GPU behaviour')
+def test_no_cpu_fallback():
+    from mxfusion_amd import _lib
+    for cls, matrix in _classes():
+        for n in (3, 40):                                                      # the fused path and the dense one
+            f = cls.define_variable(shape=(2, n), dtype='float64').factor
+            variables = {f.inputs[0][1].uuid: torch.zeros(1, 1, dtype=torch.float64), f.inputs[1][1].uuid: torch.eye(n, dtype=torch.float64)[None],
+                         f.random_variable.uuid: torch.ones(1, 2, n, dtype=torch.float64)}
+            with pytest.raises(_lib.MXFError):
+                f.log_pdf(F=None, variables=variables)
