@@ -373,6 +373,32 @@ int mxf_mvn_logpdf_bwd(mxf_handle h, int dtype, int form, int S, int64_t B, int 
                        int64_t strideS_mean, int64_t strideB_mean, const void* F, int S_A, int64_t B_A, const void* cot, double scale,
                        void* dx_acc, void* dmean_acc, void* dA_acc, void* stream);
 
+/* Wishart density of order n <= 32 over X (S|1, B, n, n) with the scale matrices V (S|1, B|1, n, n) and the degrees of freedom
+ * dof (S|1, B|1), all symmetric positive definite resp. > n - 1:
+ *   out[s,b] = scale * (1/2 [(dof - n - 1) log|X| - tr(V^-1 X) - dof n log 2 - dof log|V|] - log Gamma_n(dof / 2)),  WRITTEN,
+ *   log Gamma_n(a) = n (n - 1) / 4 log pi + sum_{k=1..n} lgamma(a + (1 - k) / 2).
+ * Replaces Wishart.log_pdf_impl (components/distributions/wishart.py:62-96) and the per-element loops it calls (util/special.py:21-132:
+ * log_determinant, solve, trace, log_multivariate_gamma), and MXNet autograd through them.  Launch-bound at the sizes of a prior: one
+ * launch each (float32 reverse mode with shared operands: a fill and a fold more).  A larger n is status -3 and no buffer is touched.
+ * Strides are in elements.  X: rows of n contiguous elements at row stride ldx, the B matrices of a sample n * ldx apart, sample stride
+ * strideS_X (0: shared by the samples).  V: row stride ldv, sample and batch strides; S_V in {1, S} and B_V in {1, B} say which axes it
+ * has.  dof: sample and batch stride, either may be 0.  Only the lower triangles of X and V are read.  float32 operands are factorised in
+ * double.  info: device int[S * B], zeroed by the caller; a row gets j (1-based) when the j-th pivot of its V is not positive, else n + j
+ * for the j-th pivot of its X, else 2 n + 1 when dof <= n - 1, and its value is NaN.  The call still returns 0.                         */
+int mxf_wishart_logpdf(mxf_handle h, int dtype, int S, int64_t B, int n, const void* X, int64_t ldx, int64_t strideS_X, const void* dof,
+                       int64_t strideS_dof, int64_t strideB_dof, const void* V, int64_t ldv, int64_t strideS_V, int64_t strideB_V, int S_V,
+                       int64_t B_V, double scale, void* out, int* info, void* stream);
+
+/* Reverse mode of mxf_wishart_logpdf with the cotangent cot (S, B), w = scale * cot[s,b] (wishart.py:62-96 under autograd):
+ *   dX += w [1/2 (dof - n - 1) X^-1 - 1/2 V^-1],   dV += w [1/2 V^-1 X V^-1 - 1/2 dof V^-1],
+ *   ddof += w [1/2 (log|X| - n log 2 - log|V|) - 1/2 sum_{k=1..n} psi((dof + 1 - k) / 2)]
+ * ACCUMULATED into dense buffers shaped like their operands with the shared axes at extent 1 -- dX (S|1, B, n, n) and dV (S_V, B_V, n, n),
+ * full symmetric matrices, ddof (S|1, B|1) -- and summed, in double for either dtype, over the axes an operand is shared over.  A row that
+ * fails as above contributes NaN.  Any output may be null.                                                                             */
+int mxf_wishart_logpdf_bwd(mxf_handle h, int dtype, int S, int64_t B, int n, const void* X, int64_t ldx, int64_t strideS_X, const void* dof,
+                           int64_t strideS_dof, int64_t strideB_dof, const void* V, int64_t ldv, int64_t strideS_V, int64_t strideB_V, int S_V,
+                           int64_t B_V, const void* cot, double scale, void* dX_acc, void* ddof_acc, void* dV_acc, void* stream);
+
 /* MXNet Adam as driven by gluon.Trainer.step (batch_loop.py:46-60, minibatch_loop.py:71-91):
  * g*=rescale; m=b1 m+(1-b1)g; v=b2 v+(1-b2)g^2; w -= lr*sqrt(1-b2^t)/(1-b1^t) * m/(sqrt(v)+eps)      */
 int mxf_adam_step(mxf_handle h, int dtype, int64_t n, void* w, const void* g, void* m, void* v,

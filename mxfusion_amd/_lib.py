@@ -42,6 +42,8 @@ SIGNATURES = {
     'mxf_mvn_factor': [_i, _i, _i, _i64, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
     'mxf_mvn_logpdf': [_i, _i, _i, _i64, _i, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _i, _i64, _d, _vp, _vp],
     'mxf_mvn_logpdf_bwd': [_i, _i, _i, _i64, _i, _vp, _i64, _vp, _i64, _i64, _vp, _i, _i64, _vp, _d, _vp, _vp, _vp, _vp],
+    'mxf_wishart_logpdf': [_i, _i, _i64, _i, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _i, _i64, _d, _vp, _vp, _vp],
+    'mxf_wishart_logpdf_bwd': [_i, _i, _i64, _i, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _i, _i64, _vp, _d, _vp, _vp, _vp, _vp],
     'mxf_normal_reparam_bwd': [_i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
     'mxf_adam_step': [_i, _i64, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _d, _i, _vp],
     'mxf_sgd_step': [_i, _i64, _vp, _vp, _vp, _d, _d, _d, _d, _vp],

@@ -7,5 +7,6 @@ from .beta import Beta  # noqa: F401
 from .laplace import Laplace  # noqa: F401
 from .uniform import Uniform  # noqa: F401
 from .mvn import MultivariateNormal, MultivariateNormalMeanPrecision  # noqa: F401
+from .wishart import Wishart  # noqa: F401
 from .random_gen import RandomGenerator, TorchRandomGenerator, MockRandomGenerator  # noqa: F401
 from .gp import GaussianProcess, ConditionalGaussianProcess  # noqa: F401

@@ -8,32 +8,16 @@
 // Replaces: MultivariateNormal.log_pdf_impl (components/distributions/normal.py:157-178), MultivariateNormalMeanPrecision.log_pdf_impl
 // (normal.py:369-394) and MXNet autograd through linalg.potrf / linalg.trsm / linalg.sumlogdiag on (S, B, n, n) operands.
 #include "common.h"
+#include "smallmat.h"
 
 namespace {
 
-constexpr int MVN_MAX = 32;             // largest order: a lane per row (or column) of a matrix
-constexpr int MVN_LD = MVN_MAX + 1;     // LDS row stride: lanes walking down a column fall into different banks
 constexpr int MVN_WAVES = 4;            // wavefronts (matrices) per workgroup of the per-matrix kernels
 constexpr int MVN_ROWS = 8;             // half-waves (rows) per workgroup of the per-row kernels
 
-// the tiles of one matrix, double for either T: a float32 factor is rounded once, when it is stored
-struct MvnTiles { double l[MVN_MAX * MVN_LD]; double x[MVN_MAX * MVN_LD]; };
-
-// x = l^-1 (both lower, in LDS) by forward substitution; lane c owns column c of x and touches no other, so no barrier is needed inside.
-// Rows above the diagonal come out as exact zeros.  Lanes >= n stay out.
-__device__ __forceinline__ void mvn_invert_lower(const double* l, double* x, int n, int lane) {
-    if (lane >= n) return;
-    for (int i = 0; i < n; ++i) {
-        double acc = i == lane ? 1.0 : 0.0;
-        for (int k = 0; k < i; ++k) acc -= l[i * MVN_LD + k] * x[k * MVN_LD + lane];
-        x[i * MVN_LD + lane] = acc / l[i * MVN_LD + i];
-    }
-}
-
-// Matrix m = sa * B_A + ba of A (S_A, B_A, n, n) -> F[m] (n x n, dense) and logdet[m].  Left-looking Cholesky, a column per step: lane i
-// forms A_ij - sum_k L_ik L_jk, lane j's value is the pivot; sums, pivots and the log-determinant are double for either T.  A pivot that
-// is not positive sets info[m] = j + 1 once and turns the rest of the matrix and its log-determinant into NaN; nothing traps, every loop
-// is bounded by n.
+// Matrix m = sa * B_A + ba of A (S_A, B_A, n, n) -> F[m] (n x n, dense) and logdet[m].  Left-looking Cholesky, a column per step
+// (smallmat_cholesky): sums, pivots and the log-determinant are double for either T.  A pivot that is not positive sets info[m] = j + 1
+// once and turns the rest of the matrix and its log-determinant into NaN; nothing traps, every loop is bounded by n.
 // Every wave of a workgroup takes the same number of trips (the barriers are reached by all four); a wave without a matrix loads and
 // stores nothing.
 template <typename T>
@@ -52,21 +36,8 @@ __global__ __launch_bounds__(256) void mvn_factor_kernel(int form, int64_t M, in
             for (int i = 0; i < n; ++i) l[i * MVN_LD + lane] = lane <= i ? (double)a[(int64_t)i * lda + lane] : 0.0;
         }
         __syncthreads();
-        double ld = 0.0;
-        int bad = 0;
-        for (int j = 0; j < n; ++j) {
-            double s = 0.0;
-            if (mine && lane >= j) {
-                s = l[lane * MVN_LD + j];
-                for (int k = 0; k < j; ++k) s -= l[lane * MVN_LD + k] * l[j * MVN_LD + k];
-            }
-            const double piv = __shfl(s, j, 64);
-            if (!(piv > 0.0) && !bad) bad = j + 1;
-            const double d = bad ? (double)NAN : sqrt(piv);
-            ld += log(d);
-            if (mine && lane >= j) l[lane * MVN_LD + j] = lane == j ? d : s / d;
-            __syncthreads();
-        }
+        int bad;
+        const double ld = smallmat_cholesky<64>(l, n, lane, mine, bad);
         if (form == 0) mvn_invert_lower(l, x, n, mine ? lane : n);
         if (mine) {
             const double* src = form == 0 ? x : l;          // x: this lane's own column; l: complete since the last barrier

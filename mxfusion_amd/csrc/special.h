@@ -1,5 +1,6 @@
-// Special functions of the univariate log-densities (univariate.hip): log-gamma and digamma for x > 0, float and double, callable from
-// host and device code -- the host side exists so that tests/host/special_check.cpp can hold them to SciPy without a GPU.
+// Special functions of the univariate log-densities (univariate.hip) and of the Wishart density (wishart.hip): log-gamma and digamma for
+// x > 0 and their multivariate forms, float and double, callable from host and device code -- the host side exists so that
+// tests/host/special_check.cpp and tests/host/mvgamma_check.cpp can hold them to SciPy without a GPU.
 // No tables in memory, no inline assembly.
 #pragma once
 #include <math.h>
@@ -38,4 +39,23 @@ MXF_HD inline T mxf_digamma(T x) {
     p = (T)(-1.0 / 120.0) + r2 * p;         // B_4 / 4
     p = (T)(1.0 / 12.0) + r2 * p;           // B_2 / 2
     return (log(y) - (T)0.5 * r - r2 * p) - lift;
+}
+
+// log Gamma_n(a) = n (n - 1) / 4 log pi + sum_{k=1..n} lgamma(a + (1 - k) / 2), a > (n - 1) / 2: the multivariate gamma function of the
+// Wishart density (util/special.py:21-132 of the reference forms it element by element).  The terms run from lgamma(a) ~ a log a down to
+// lgamma of the margin a - (n - 1) / 2, which is large again near zero: terms and sum are double for either T, and T sees one rounding,
+// as univariate.hip does for its lgamma differences.
+template <typename T>
+MXF_HD inline T mxf_lmvgamma(T a, int n) {
+    double s = 0.25 * n * (n - 1) * 1.1447298858494001741 /* log pi */;
+    for (int k = 0; k < n; ++k) s += mxf_lgamma((double)a - 0.5 * k);
+    return (T)s;
+}
+
+// d/da log Gamma_n(a) = sum_{k=1..n} psi(a + (1 - k) / 2): psi changes sign at 1.4616, so the sum cancels; double as above.
+template <typename T>
+MXF_HD inline T mxf_mvdigamma(T a, int n) {
+    double s = 0.0;
+    for (int k = 0; k < n; ++k) s += mxf_digamma<double>((double)a - 0.5 * k);
+    return (T)s;
 }

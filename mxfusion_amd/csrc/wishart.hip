@@ -1,0 +1,254 @@
+// Wishart log-density for thousands of small matrices (gfx950): order n <= 32, X (S|1, B, n, n) under V (S|1, B|1, n, n) and nu (S|1, B|1).
+//   mxf_wishart_logpdf      one wavefront per row (s, b): its half-waves factorise X[s,b] and V side by side in LDS (lanes 0..31 and
+//                           32..63, a tile each), lanes 0..n-1 form Y = L_V^-1 L_X a column each, tr(V^-1 X) = |Y|_F^2
+//   mxf_wishart_logpdf_bwd  the same rows with the cotangent: both factors again (a few thousand FMAs), both inverses side by side,
+//                           Z = L_V^-T Y, and X^-1, V^-1 and Z Z^T = V^-1 X V^-1 a row per lane; sums over shared axes are formed in
+//                           double for either dtype
+// The tiles are double for either dtype: a float32 operand is widened when it is loaded and a float32 result is rounded once.
+// One wavefront per workgroup: four tiles are 33 KB of LDS, and a barrier is the wave's own.  Both calls are launch-bound at the sizes of
+// a prior.
+//
+// Replaces: Wishart.log_pdf_impl (components/distributions/wishart.py:62-96) over the per-element loops of util/special.py:21-132
+// (log_determinant, solve, trace, log_multivariate_gamma) and MXNet autograd through them.
+#include "common.h"
+#include "smallmat.h"
+#include "special.h"
+
+namespace {
+
+constexpr int WISH_TILE = MVN_MAX * MVN_LD;
+constexpr double WISH_LOG_2 = 0.69314718055994530942, WISH_LOG_PI = 1.1447298858494001741;
+
+template <typename T>
+struct WishRows {
+    int S;
+    int64_t B;
+    int n;
+    const T* X; int64_t ldx, ss_X;
+    const T* dof; int64_t ss_d, sb_d;
+    const T* V; int64_t ldv, ss_V, sb_V;
+    int S_V; int64_t B_V;
+    double scale;
+};
+
+// the row (s, b) of a wavefront after the factor step
+struct WishRow {
+    int64_t s, b;
+    double nu, ldX, ldV;      // sum log diag of the two factors: half their log-determinants
+    int fail;                 // the info word: 0, j + 1 (V), n + j + 1 (X), 2 n + 1 (nu <= n - 1); the first that applies
+};
+
+// Lower triangles of X[s,b] -> tx and of its V -> tv, then both Cholesky factors in place: lanes 0..31 hold X, lanes 32..63 hold V,
+// lane c of a half the column c on the way in and the row c in the factor step.
+template <typename T>
+__device__ __forceinline__ WishRow wish_factor(const WishRows<T>& a, int64_t row, double* tx, double* tv, int lane) {
+    const int half = lane >> 5, c = lane & 31, n = a.n;
+    WishRow r;
+    r.s = row / a.B;
+    r.b = row % a.B;
+    const bool mine = c < n;
+    double* t = half ? tv : tx;
+    if (mine) {
+        const T* src = half ? a.V + (a.S_V == 1 ? 0 : r.s) * a.ss_V + (a.B_V == 1 ? 0 : r.b) * a.sb_V : a.X + r.s * a.ss_X + r.b * n * a.ldx;
+        const int64_t ld = half ? a.ldv : a.ldx;
+        for (int i = 0; i < n; ++i) t[i * MVN_LD + c] = c <= i ? (double)src[i * ld + c] : 0.0;
+    }
+    __syncthreads();
+    int bad;
+    const double ld = smallmat_cholesky<32>(t, n, c, mine, bad);
+    r.ldX = __shfl(ld, 0, 64);
+    r.ldV = __shfl(ld, 32, 64);
+    const int badX = __shfl(bad, 0, 64), badV = __shfl(bad, 32, 64);
+    r.nu = (double)a.dof[r.s * a.ss_d + r.b * a.sb_d];
+    r.fail = badV ? badV : badX ? n + badX : !(r.nu > (double)(n - 1)) ? 2 * n + 1 : 0;
+    return r;
+}
+
+// out[s,b] = scale * (1/2 [(nu - n - 1) log|X| - tr(V^-1 X) - nu n log 2 - nu log|V|] - log Gamma_n(nu / 2)); a failed row is NaN.
+// log Gamma_n is mxf_lmvgamma's sum (special.h) with a term per lane.
+template <typename T>
+__global__ __launch_bounds__(64) void wishart_logpdf_kernel(WishRows<T> a, T* __restrict__ out, int* __restrict__ info) {
+    __shared__ double tiles[2 * WISH_TILE];
+    double *tx = tiles, *tv = tiles + WISH_TILE;
+    const int lane = threadIdx.x, n = a.n;
+    const int64_t rows = (int64_t)a.S * a.B;
+    for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
+        const WishRow r = wish_factor(a, row, tx, tv, lane);
+        const double q = wave_sum(lane < n ? smallmat_solve_lower(tv, tx, n, lane) : 0.0);
+        const double lg = wave_sum(lane < n ? mxf_lgamma(0.5 * (r.nu - lane)) : 0.0) + 0.25 * n * (n - 1) * WISH_LOG_PI;
+        if (lane == 0) {
+            const double v = 0.5 * (2.0 * (r.nu - n - 1) * r.ldX - q - r.nu * n * WISH_LOG_2 - 2.0 * r.nu * r.ldV) - lg;
+            out[row] = r.fail ? (T)NAN : (T)(a.scale * v);
+            if (r.fail) info[row] = r.fail;
+        }
+        __syncthreads();                               // the tiles are loaded again on the next trip
+    }
+}
+
+// A gradient whose operand is broadcast over an axis is summed over it with atomics into a DOUBLE accumulator (the gradient itself for
+// double, scratch that wishart_fold_kernel adds for float32); the others are read-modify-writes of elements this wavefront alone owns.
+template <typename T>
+__device__ __forceinline__ void wish_add(bool shared, T* dst, double* sum, int64_t e, double v) {
+    if (shared) atomic_add(sum + e, v); else dst[e] += (T)v;
+}
+
+// With w = scale * cot[s,b] (NaN for a failed row):
+//   dX += w [1/2 (nu - n - 1) X^-1 - 1/2 V^-1],   dV += w [1/2 V^-1 X V^-1 - 1/2 nu V^-1],
+//   dnu += w [1/2 (log|X| - n log 2 - log|V|) - 1/2 sum_k psi((nu + 1 - k) / 2)]
+// X^-1 = Wx^T Wx and V^-1 = Wv^T Wv from the inverted factors, V^-1 X V^-1 = Z Z^T with Z = Wv^T Y.  Tiles: tx holds L_X, then Y, then Z;
+// tv L_V; ix Wx; iv Wv.  In the closing loop lane c of half h forms the rows j = h, h + 2, ... of column c of the three symmetric
+// matrices (consecutive lanes, consecutive addresses).
+template <typename T>
+__global__ __launch_bounds__(64) void wishart_logpdf_bwd_kernel(WishRows<T> a, const T* __restrict__ cot, T* dX, T* ddof, T* dV, double* sX,
+                                                                double* sd, double* sV) {
+    __shared__ double tiles[4 * WISH_TILE];
+    double *tx = tiles, *tv = tiles + WISH_TILE, *ix = tiles + 2 * WISH_TILE, *iv = tiles + 3 * WISH_TILE;
+    const int lane = threadIdx.x, half = lane >> 5, c = lane & 31, n = a.n;
+    const int64_t rows = (int64_t)a.S * a.B;
+    const bool X_shared = a.ss_X == 0 && a.S > 1;
+    const bool d_shared = (a.ss_d == 0 && a.S > 1) || (a.sb_d == 0 && a.B > 1);
+    const bool V_shared = (a.S_V == 1 && a.S > 1) || (a.B_V == 1 && a.B > 1);
+    for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
+        const WishRow r = wish_factor(a, row, tx, tv, lane);
+        const double w = r.fail ? (double)NAN : a.scale * (double)cot[row];
+        if (ddof) {
+            const double psi = wave_sum(lane < n ? mxf_digamma<double>(0.5 * (r.nu - lane)) : 0.0);     // mxf_mvdigamma's sum, a term per lane
+            if (lane == 0) {
+                const int64_t e = (a.ss_d ? r.s : 0) * (a.sb_d ? a.B : 1) + (a.sb_d ? r.b : 0);        // ddof is dense (S|1, B|1)
+                wish_add(d_shared, ddof, sd, e, w * (r.ldX - 0.5 * n * WISH_LOG_2 - r.ldV - 0.5 * psi));
+            }
+        }
+        if (dX || dV) {
+            if (half || dX) mvn_invert_lower(half ? tv : tx, half ? iv : ix, n, c);
+            __syncthreads();                           // Wv is read across columns below
+            if (dV && lane < n) {                      // column c of Y in place of L_X's, then of Z in place of Y's: Z_ic needs Y_kc for k >= i only
+                smallmat_solve_lower(tv, tx, n, c);
+                for (int i = 0; i < n; ++i) {
+                    double acc = 0.0;
+                    for (int k = i > c ? i : c; k < n; ++k) acc += iv[k * MVN_LD + i] * tx[k * MVN_LD + c];
+                    tx[i * MVN_LD + c] = acc;
+                }
+            }
+            __syncthreads();
+            if (c < n) {
+                const int64_t gX = ((a.ss_X ? r.s : 0) * a.B + r.b) * n * n;
+                const int64_t gV = ((a.S_V == 1 ? 0 : r.s) * a.B_V + (a.B_V == 1 ? 0 : r.b)) * n * n;
+                for (int j = half; j < n; j += 2) {
+                    double vinv = 0.0, xinv = 0.0, sand = 0.0;
+                    for (int k = j > c ? j : c; k < n; ++k) vinv += iv[k * MVN_LD + j] * iv[k * MVN_LD + c];
+                    if (dX) {
+                        for (int k = j > c ? j : c; k < n; ++k) xinv += ix[k * MVN_LD + j] * ix[k * MVN_LD + c];
+                        wish_add(X_shared, dX, sX, gX + j * n + c, w * (0.5 * (r.nu - n - 1) * xinv - 0.5 * vinv));
+                    }
+                    if (dV) {
+                        for (int k = 0; k < n; ++k) sand += tx[j * MVN_LD + k] * tx[c * MVN_LD + k];
+                        wish_add(V_shared, dV, sV, gV + j * n + c, w * (0.5 * sand - 0.5 * r.nu * vinv));
+                    }
+                }
+            }
+        }
+        __syncthreads();                               // the tiles are loaded again on the next trip
+    }
+}
+
+// dst[i] += src[i]: the double sums of the shared float32 gradients into the caller's buffers
+__global__ __launch_bounds__(256) void wishart_fold_kernel(int64_t n, const double* __restrict__ src, float* __restrict__ dst) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) dst[i] += (float)src[i];
+}
+
+struct WishCall {
+    int dtype, S; int64_t B; int n;
+    const void* X; int64_t ldx, ss_X;
+    const void* dof; int64_t ss_d, sb_d;
+    const void* V; int64_t ldv, ss_V, sb_V; int S_V; int64_t B_V;
+    double scale;
+};
+
+int check_common(mxf_handle h, const char* name, int dtype, int n) {
+    if (dtype != MXF_F32 && dtype != MXF_F64) MXF_FAIL(h, -2, "%s: bad dtype %d", name, dtype);
+    if (n < 1 || n > MVN_MAX) MXF_FAIL(h, -3, "%s: order n = %d is outside 1..%d (larger matrices take mxf_potrf / mxf_trsm)", name, n, MVN_MAX);
+    return 0;
+}
+
+int check_rows(mxf_handle h, const char* name, const WishCall& c) {
+    if (!c.X || !c.dof || !c.V) MXF_FAIL(h, -2, "%s: null operand", name);
+    if ((c.S_V != 1 && c.S_V != c.S) || (c.B_V != 1 && c.B_V != c.B))
+        MXF_FAIL(h, -2, "%s: the scale matrices have 1 or S samples and 1 or B batch entries, got (%d, %lld)", name, c.S_V, (long long)c.B_V);
+    if (c.ldx < c.n || c.ldv < c.n) MXF_FAIL(h, -2, "%s: ldx %lld or ldv %lld < n = %d", name, (long long)c.ldx, (long long)c.ldv, c.n);
+    if (c.ss_X < 0 || c.ss_d < 0 || c.sb_d < 0 || c.ss_V < 0 || c.sb_V < 0) MXF_FAIL(h, -2, "%s: negative stride", name);
+    return 0;
+}
+
+template <typename T>
+WishRows<T> rows_of(const WishCall& c) {
+    return {c.S, c.B, c.n, (const T*)c.X, c.ldx, c.ss_X, (const T*)c.dof, c.ss_d, c.sb_d, (const T*)c.V, c.ldv, c.ss_V, c.sb_V, c.S_V, c.B_V, c.scale};
+}
+
+// a workgroup (one wavefront) per row, grid-stride above 4096 rows
+unsigned grid_of(const WishCall& c) {
+    const int64_t rows = (int64_t)c.S * c.B;
+    return (unsigned)(rows < 4096 ? rows : 4096);
+}
+
+// The gradients of operands shared over an axis are summed in double: in place for double; for float32 in zeroed scratch of the handle
+// ([dX | ddof | dV], only what is shared and wanted) that wishart_fold_kernel adds to the caller's buffers.
+template <typename T>
+int launch_bwd(mxf_handle h, const WishCall& c, const void* cot, void* dX, void* ddof, void* dV, hipStream_t st) {
+    const int64_t n = c.n;
+    const bool X_sh = dX && c.ss_X == 0 && c.S > 1, d_sh = ddof && ((c.ss_d == 0 && c.S > 1) || (c.sb_d == 0 && c.B > 1));
+    const bool V_sh = dV && ((c.S_V == 1 && c.S > 1) || (c.B_V == 1 && c.B > 1));
+    const int64_t nX = X_sh ? c.B * n * n : 0, nd = d_sh ? (c.ss_d ? c.S : 1) * (c.sb_d ? c.B : 1) : 0, nV = V_sh ? c.S_V * c.B_V * n * n : 0;
+    double *sX = (double*)dX, *sd = (double*)ddof, *sV = (double*)dV;
+    const bool scratch = sizeof(T) == 4 && nX + nd + nV > 0;
+    if (scratch) {
+        double* ws = (double*)mxf_ws(h, (size_t)(nX + nd + nV) * sizeof(double));
+        if (!ws) MXF_FAIL(h, -4, "mxf_wishart_logpdf_bwd: out of memory for %lld scratch doubles", (long long)(nX + nd + nV));
+        MXF_HIP(h, hipMemsetAsync(ws, 0, (size_t)(nX + nd + nV) * sizeof(double), st));
+        sX = ws; sd = ws + nX; sV = ws + nX + nd;
+    }
+    hipLaunchKernelGGL((wishart_logpdf_bwd_kernel<T>), dim3(grid_of(c)), dim3(64), 0, st, rows_of<T>(c), (const T*)cot, (T*)dX, (T*)ddof,
+                       (T*)dV, sX, sd, sV);
+    const int64_t counts[3] = {nX, nd, nV};
+    const double* sums[3] = {sX, sd, sV};
+    void* dsts[3] = {dX, ddof, dV};
+    for (int i = 0; scratch && i < 3; ++i)
+        if (counts[i]) hipLaunchKernelGGL(wishart_fold_kernel, dim3(grid_for(counts[i])), dim3(256), 0, st, counts[i], sums[i], (float*)dsts[i]);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int mxf_wishart_logpdf(mxf_handle h, int dtype, int S, int64_t B, int n, const void* X, int64_t ldx, int64_t strideS_X,
+                                  const void* dof, int64_t strideS_dof, int64_t strideB_dof, const void* V, int64_t ldv, int64_t strideS_V,
+                                  int64_t strideB_V, int S_V, int64_t B_V, double scale, void* out, int* info, void* stream) {
+    if (!h) return -1;
+    const WishCall c = {dtype, S, B, n, X, ldx, strideS_X, dof, strideS_dof, strideB_dof, V, ldv, strideS_V, strideB_V, S_V, B_V, scale};
+    if (int rc = check_common(h, "mxf_wishart_logpdf", dtype, n)) return rc;
+    if (S <= 0 || B <= 0) return 0;
+    if (int rc = check_rows(h, "mxf_wishart_logpdf", c)) return rc;
+    if (!out || !info) MXF_FAIL(h, -2, "mxf_wishart_logpdf: null out or info");
+    if (dtype == MXF_F32)
+        hipLaunchKernelGGL((wishart_logpdf_kernel<float>), dim3(grid_of(c)), dim3(64), 0, (hipStream_t)stream, rows_of<float>(c), (float*)out, info);
+    else
+        hipLaunchKernelGGL((wishart_logpdf_kernel<double>), dim3(grid_of(c)), dim3(64), 0, (hipStream_t)stream, rows_of<double>(c), (double*)out, info);
+    MXF_LAUNCH_CHECK(h);
+    return 0;
+}
+
+extern "C" int mxf_wishart_logpdf_bwd(mxf_handle h, int dtype, int S, int64_t B, int n, const void* X, int64_t ldx, int64_t strideS_X,
+                                      const void* dof, int64_t strideS_dof, int64_t strideB_dof, const void* V, int64_t ldv,
+                                      int64_t strideS_V, int64_t strideB_V, int S_V, int64_t B_V, const void* cot, double scale, void* dX_acc,
+                                      void* ddof_acc, void* dV_acc, void* stream) {
+    if (!h) return -1;
+    const WishCall c = {dtype, S, B, n, X, ldx, strideS_X, dof, strideS_dof, strideB_dof, V, ldv, strideS_V, strideB_V, S_V, B_V, scale};
+    if (int rc = check_common(h, "mxf_wishart_logpdf_bwd", dtype, n)) return rc;
+    if (S <= 0 || B <= 0) return 0;
+    if (int rc = check_rows(h, "mxf_wishart_logpdf_bwd", c)) return rc;
+    if (!cot) MXF_FAIL(h, -2, "mxf_wishart_logpdf_bwd: null cotangent");
+    if (!dX_acc && !ddof_acc && !dV_acc) return 0;
+    if (int rc = dtype == MXF_F32 ? launch_bwd<float>(h, c, cot, dX_acc, ddof_acc, dV_acc, (hipStream_t)stream)
+                                  : launch_bwd<double>(h, c, cot, dX_acc, ddof_acc, dV_acc, (hipStream_t)stream))
+        return rc;
+    MXF_LAUNCH_CHECK(h);
+    return 0;
+}

@@ -481,6 +481,52 @@ def mvn_logpdf_bwd_(x, mean, F, cot, form=0, scale=1.0, dx_acc=None, dmean_acc=N
               _p(cot), float(scale), _p(dx_acc), _p(dmean_acc), _p(dA_acc), _stream())
 
 
+def _wishart_operands(X, dof, V):
+    """X (S|1, B, n, n), dof (S|1, B|1) and V (S|1, B|1, n, n) as the mxf_wishart_* entry points take them, and the arguments that describe
+    them: rows of n contiguous elements, X's matrices n rows apart.  An operand that already has that layout, expanded axes included, is
+    passed as it is."""
+    n = X.shape[-1]
+    if X.dim() != 4 or V.dim() != 4 or dof.dim() != 2 or X.shape[-2] != n or tuple(V.shape[-2:]) != (n, n):
+        raise ValueError('Wishart: X (S|1, B, n, n), dof (S|1, B|1), V (S|1, B|1, n, n); got %s, %s, %s'
+                         % (tuple(X.shape), tuple(dof.shape), tuple(V.shape)))
+    if X.stride(3) != 1 or X.stride(2) < n or (X.shape[1] > 1 and X.stride(1) != n * X.stride(2)):
+        X = X.contiguous()
+    if V.stride(3) != 1 or V.stride(2) < n:
+        V = V.contiguous()
+    (S_V, ss_V), (B_V, sb_V) = _mvn_axis(V, 0), _mvn_axis(V, 1)
+    (S_X, ss_X), (S_d, ss_d), (B_d, sb_d) = _mvn_axis(X, 0), _mvn_axis(dof, 0), _mvn_axis(dof, 1)
+    S, B = max(S_X, S_d, S_V), X.shape[1]
+    if any(e not in (1, S) for e in (S_X, S_d, S_V)) or any(e not in (1, B) for e in (B_d, B_V)):
+        raise ValueError('Wishart: operands of %s, %s, %s do not broadcast to (%d, %d) rows' % (tuple(X.shape), tuple(dof.shape), tuple(V.shape), S, B))
+    args = (_p(X), X.stride(2), ss_X, _p(dof), ss_d, sb_d, _p(V), V.stride(2), ss_V, sb_V, S_V, B_V)
+    return X, V, S, B, n, args, ((S_X, B, n, n), (S_d, B_d), (S_V, B_V, n, n))
+
+
+def wishart_logpdf(X, dof, V, scale=1.0):
+    """(scale * log W(X[s,b] | V, dof) (S, B), info (S, B) int32) for n <= 32; X (S|1, B, n, n), dof (S|1, B|1), V (S|1, B|1, n, n), an
+    expanded axis counting as shared (mxf_wishart_logpdf).  info: 0, j for V's j-th pivot, n + j for X's, 2 n + 1 for dof <= n - 1."""
+    _mvn_check(X, dof, V)
+    X, V, S, B, n, args, _ = _wishart_operands(X, dof, V)
+    out = torch.empty((S, B), dtype=X.dtype, device=X.device)
+    info = torch.zeros((S, B), dtype=torch.int32, device=X.device)
+    _lib.call('mxf_wishart_logpdf', _h(X), _dt(X), S, B, n, *args, float(scale), _p(out), _p(info), _stream())
+    return out, info
+
+
+def wishart_logpdf_bwd_(X, dof, V, cot, scale=1.0, dX_acc=None, ddof_acc=None, dV_acc=None):
+    """Reverse mode of wishart_logpdf: dX_acc (S|1, B, n, n), ddof_acc (S|1, B|1), dV_acc (S_V, B_V, n, n) -- dense, shaped like their
+    operands with the shared axes at extent 1 -- += the gradients under the cotangent cot (S, B) (mxf_wishart_logpdf_bwd)."""
+    _mvn_check(X, dof, V, cot, dX_acc, ddof_acc, dV_acc)
+    for t in (cot, dX_acc, ddof_acc, dV_acc):
+        if t is not None and not t.is_contiguous():
+            raise ValueError('Wishart: the cotangent and the gradient buffers must be contiguous')
+    X, V, S, B, n, args, shapes = _wishart_operands(X, dof, V)
+    for t, shape in zip((cot, dX_acc, ddof_acc, dV_acc), ((S, B),) + shapes):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError('Wishart: a buffer of shape %s where the operands ask for %s' % (tuple(t.shape), shape))
+    _lib.call('mxf_wishart_logpdf_bwd', _h(X), _dt(X), S, B, n, *args, _p(cot), float(scale), _p(dX_acc), _p(ddof_acc), _p(dV_acc), _stream())
+
+
 def adam_step_(w, g, m, v, lr, t, beta1=0.9, beta2=0.999, epsilon=1e-8, rescale_grad=1.0):
     _lib.call('mxf_adam_step', _h(w), _dt(w), w.numel(), _p(w), _p(g), _p(m), _p(v), float(lr), float(beta1), float(beta2),
               float(epsilon), float(rescale_grad), int(t), _stream())
