@@ -318,13 +318,14 @@ int mxf_normal_reparam_bwd(mxf_handle h, int dtype, int S, int64_t n, const void
  *   MXF_D_BETA      (alpha, beta)      (a-1) log x + (b-1) log(1-x) - lgamma(a) - lgamma(b) + lgamma(a+b)   Beta.log_pdf_impl (beta.py:46-68)
  *   MXF_D_LAPLACE   (location, scale)  -log(2b) - |x-a|/b                                           Laplace.log_pdf_impl (laplace.py:37-55)
  *   MXF_D_UNIFORM   (low, high)        -log(b-a) where a <= x < b, else -inf                        Uniform.log_pdf_impl (uniform.py:38-62)
+ *   MXF_D_BERNOULLI (prob_true, -)     x log a + (1-x) log(1-a); b is unused, pass a again          Bernoulli.log_pdf_impl (bernoulli.py:62-78)
  * mxf_univariate_logpdf has the contract of mxf_normal_logpdf: out += scale * sum_{s,i} log p(x[s,i] | a[i], b[i]) (factor_graph.py:223),
  * optional reverse mode accumulated into dx (S,n), da (n_a), db (n_b), all scaled by `scale`; n_a, n_b in {1, n}; any output may be null.
  * Gradients are closed forms (digamma for the Gamma and Beta parameters; GAMMA_MV chained to mean and variance; Laplace d/dx =
  * -sign(x-a)/b with sign(0) = 0; Uniform dx = 0, da = 1/(b-a), db = -1/(b-a) inside the support; outside it nothing is added to any
- * gradient, whatever the weight).  A sum that holds an element outside the Uniform's support is -inf for scale > 0, +inf for scale < 0
+ * gradient, whatever the weight; Bernoulli dx = log a - log(1-a), da = x/a - (1-x)/(1-a), db = 0).  A sum that holds an element outside the Uniform's support is -inf for scale > 0, +inf for scale < 0
  * and NaN (0 * inf) for scale == 0.                                                                                                    */
-enum { MXF_D_GAMMA = 0, MXF_D_GAMMA_MV = 1, MXF_D_BETA = 2, MXF_D_LAPLACE = 3, MXF_D_UNIFORM = 4 };
+enum { MXF_D_GAMMA = 0, MXF_D_GAMMA_MV = 1, MXF_D_BETA = 2, MXF_D_LAPLACE = 3, MXF_D_UNIFORM = 4, MXF_D_BERNOULLI = 5 };
 int mxf_univariate_logpdf(mxf_handle h, int kind, int dtype, int S, int64_t n, const void* x,
                           const void* a, int64_t n_a, const void* b, int64_t n_b, double scale,
                           void* out_acc, void* dx_acc, void* da_acc, void* db_acc, void* stream);
@@ -398,6 +399,48 @@ int mxf_wishart_logpdf(mxf_handle h, int dtype, int S, int64_t B, int n, const v
 int mxf_wishart_logpdf_bwd(mxf_handle h, int dtype, int S, int64_t B, int n, const void* X, int64_t ldx, int64_t strideS_X, const void* dof,
                            int64_t strideS_dof, int64_t strideB_dof, const void* V, int64_t ldv, int64_t strideS_V, int64_t strideB_V, int S_V,
                            int64_t B_V, const void* cot, double scale, void* dX_acc, void* ddof_acc, void* dV_acc, void* stream);
+
+/* Categorical and Dirichlet: log-densities that reduce along a class axis.  Rows are (s, b), s < S samples and b < B batch entries, of
+ * K >= 1 contiguous elements; strides are in elements and dense where not 0: a sample or batch stride of 0 shares the operand over that
+ * axis.  One group of 4 (K <= 4), 16 (K <= 16) or 64 lanes per row, reductions over K on wave shuffles.  Launch-bound at the size of a
+ * prior, bandwidth-bound at the size of a classification likelihood: one launch each (float32 reverse mode with a parameter shared over
+ * the batch axis: a fill and a fold more).
+ *
+ * mxf_categorical_logpdf: out[s,b] = scale * lp[x[s,b]] (one_hot = 0) or scale * sum_k x[s,b,k] lp_k (one_hot = 1), WRITTEN, with
+ * lp = logp - logsumexp(logp) along K (normalize = 1; the row maximum is subtracted first, a row of all -inf is NaN) or lp = logp.
+ * logp (S|1, B|1, K).  one_hot = 0: x (S|1, B), class indices held in the floating type, truncated toward zero and clipped to
+ * [0, K - 1] (the default mode of MXNet's pick).  one_hot = 1: x (S|1, B, K).  Replaces Categorical.log_pdf_impl
+ * (components/distributions/categorical.py:83-106: log_softmax, pick / broadcast_mul and sum).                                        */
+int mxf_categorical_logpdf(mxf_handle h, int dtype, int S, int64_t B, int K, const void* logp, int64_t strideS_lp, int64_t strideB_lp,
+                           const void* x, int64_t strideS_x, int one_hot, int normalize, double scale, void* out, void* stream);
+
+/* Reverse mode of mxf_categorical_logpdf with the cotangent cot (S, B), w = scale * cot[s,b] (categorical.py:83-106 under autograd):
+ *   dlogp_k += w (t_k - p_k sum_j t_j), p = exp(lp)  (normalize = 1)   or   w t_k  (normalize = 0),     dx_k += w lp_k  (one_hot = 1)
+ * with t the one-hot row of the clipped index, or x itself when one_hot = 1.  ACCUMULATED into dense buffers shaped like their operands
+ * with the shared axes at extent 1 -- dlogp (S|1, B|1, K), dx (S|1, B, K) -- and summed over the axes an operand is shared over (over
+ * the batch axis in double for either dtype).  dx_acc must be null when one_hot = 0 (an index has no gradient): status -2.  Any output
+ * may be null.                                                                                                                         */
+int mxf_categorical_logpdf_bwd(mxf_handle h, int dtype, int S, int64_t B, int K, const void* logp, int64_t strideS_lp, int64_t strideB_lp,
+                               const void* x, int64_t strideS_x, int one_hot, int normalize, const void* cot, double scale,
+                               void* dlogp_acc, void* dx_acc, void* stream);
+
+/* mxf_dirichlet_logpdf: x (S|1, B, K), alpha (S|1, B|1, K),
+ *   out[s,b] = scale * (sum_k (alpha_k - 1) log xt_k + lgamma(sum_k alpha_k) - sum_k lgamma(alpha_k)),  WRITTEN,
+ * xt = x / sum_k |x_k| (normalize = 1) or x.  The three lgamma sums are formed in double for either dtype.  A row with an x_k <= 0 or
+ * an alpha_k <= 0 is NaN, the others are unaffected, and the call still returns 0.  Replaces Dirichlet.log_pdf_impl
+ * (components/distributions/dirichlet.py:43-65: norm, broadcast_power, prod and the log of a quotient of gamma products, which
+ * overflows from alpha ~ 170; the value is the same).                                                                                 */
+int mxf_dirichlet_logpdf(mxf_handle h, int dtype, int S, int64_t B, int K, const void* x, int64_t strideS_x, const void* alpha,
+                         int64_t strideS_a, int64_t strideB_a, int normalize, double scale, void* out, void* stream);
+
+/* Reverse mode of mxf_dirichlet_logpdf with the cotangent cot (S, B), w = scale * cot[s,b] (dirichlet.py:43-65 under autograd):
+ *   dalpha_k += w (log xt_k + psi(sum_j alpha_j) - psi(alpha_k)),
+ *   dx_j += w ((alpha_j - 1) / x_j - [normalize] sum_k (alpha_k - 1) / sum_k |x_k|)
+ * ACCUMULATED and summed over shared axes as in mxf_categorical_logpdf_bwd: dx (S|1, B, K), dalpha (S|1, B|1, K).  A row that fails as
+ * above contributes NaN.  Any output may be null.                                                                                     */
+int mxf_dirichlet_logpdf_bwd(mxf_handle h, int dtype, int S, int64_t B, int K, const void* x, int64_t strideS_x, const void* alpha,
+                             int64_t strideS_a, int64_t strideB_a, int normalize, const void* cot, double scale, void* dx_acc,
+                             void* dalpha_acc, void* stream);
 
 /* MXNet Adam as driven by gluon.Trainer.step (batch_loop.py:46-60, minibatch_loop.py:71-91):
  * g*=rescale; m=b1 m+(1-b1)g; v=b2 v+(1-b2)g^2; w -= lr*sqrt(1-b2^t)/(1-b1^t) * m/(sqrt(v)+eps)      */

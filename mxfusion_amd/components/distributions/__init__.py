@@ -8,5 +8,8 @@ from .laplace import Laplace  # noqa: F401
 from .uniform import Uniform  # noqa: F401
 from .mvn import MultivariateNormal, MultivariateNormalMeanPrecision  # noqa: F401
 from .wishart import Wishart  # noqa: F401
+from .categorical import Categorical  # noqa: F401
+from .dirichlet import Dirichlet  # noqa: F401
+from .bernoulli import Bernoulli  # noqa: F401
 from .random_gen import RandomGenerator, TorchRandomGenerator, MockRandomGenerator  # noqa: F401
 from .gp import GaussianProcess, ConditionalGaussianProcess  # noqa: F401

@@ -22,6 +22,14 @@ class RandomGenerator(object):
     def sample_laplace(location=0., scale=1., shape=None, dtype=None, out=None, ctx=None, F=None):
         raise NotImplementedError
 
+    @staticmethod
+    def sample_multinomial(data, shape=None, get_prob=False, dtype=None, F=None):
+        raise NotImplementedError
+
+    @staticmethod
+    def sample_bernoulli(prob_true=0.5, dtype=None, shape=None, F=None):
+        raise NotImplementedError
+
 
 def _numel(shape):
     n = 1
@@ -68,6 +76,32 @@ class TorchRandomGenerator(RandomGenerator):
         U = TorchRandomGenerator.sample_uniform(low=-0.5, high=0.5, shape=shape, dtype=dtype, ctx=ctx)
         return location - scale * torch.sign(U) * torch.log((1 - 2 * torch.abs(U)).clamp_min(torch.finfo(U.dtype).tiny))
 
+    @staticmethod
+    def sample_multinomial(data, shape=None, get_prob=False, dtype=None, F=None):
+        """random_gen.py:101-124: data (..., K) holds PROBABILITIES along its last axis (each row is normalised by the sampler); one class
+        index per row, data.shape[:-1], or with `shape` that many per row, data.shape[:-1] + shape.  dtype None: int64.  get_prob: also the
+        log-probability of each draw."""
+        from ...common import config
+        K = int(data.shape[-1])
+        extra = tuple(shape) if shape is not None and not isinstance(shape, int) else (() if shape is None else (int(shape),))
+        idx = torch.multinomial(data.reshape(-1, K), max(_numel(extra), 1), replacement=True).reshape(tuple(data.shape[:-1]) + extra)
+        out = idx if dtype is None else idx.to(dtype if isinstance(dtype, torch.dtype) else config.torch_dtype(dtype))
+        if not get_prob:
+            return out
+        rows = data.reshape(tuple(data.shape[:-1]) + (1,) * len(extra) + (K,)).expand(tuple(idx.shape) + (K,))
+        logp = torch.log(torch.gather(rows, -1, idx.unsqueeze(-1)).squeeze(-1) / data.sum(-1).reshape(tuple(data.shape[:-1]) + (1,) * len(extra)))
+        return out, logp
+
+    @staticmethod
+    def sample_bernoulli(prob_true=0.5, dtype=None, shape=None, F=None):
+        """random_gen.py:127-138 as it is meant: uniform < prob_true, true with probability prob_true (the reference's `>` is true with
+        probability 1 - prob_true).  1 / 0 in `dtype`."""
+        from ...common import config
+        dt = dtype if isinstance(dtype, torch.dtype) else config.torch_dtype(dtype)
+        device = prob_true.device if isinstance(prob_true, torch.Tensor) else config.get_default_device()
+        u = torch.rand(tuple(shape or ()), dtype=dt if dt.is_floating_point else torch.float32, device=device)
+        return (u < prob_true).to(dt)
+
 
 MXNetRandomGenerator = TorchRandomGenerator   # source-compatible alias
 
@@ -97,6 +131,14 @@ class MockRandomGenerator(RandomGenerator):
         return self._replay(shape)
 
     def sample_laplace(self, location=0., scale=1., shape=None, dtype=None, out=None, ctx=None, F=None):
+        return self._replay(shape)
+
+    def sample_multinomial(self, data, shape=None, get_prob=False, dtype=None, F=None):
+        """testutils.py:77-78: the buffer in the shape of one draw per row, data.shape[:-1]."""
+        return self._replay(tuple(data.shape[:-1]))
+
+    def sample_bernoulli(self, prob_true=0.5, dtype=None, shape=None, F=None):
+        """testutils.py:80-81."""
         return self._replay(shape)
 
 

@@ -1,0 +1,9 @@
+// The closing step of the float32 reverse modes that sum a shared operand's gradient in double (mvn.hip, wishart.hip, simplex.hip): the
+// sums, formed with atomics in zeroed handle scratch, are added to the caller's float32 buffer with one rounding per element.
+#pragma once
+#include "common.h"
+
+// dst[i] += src[i]
+static __global__ __launch_bounds__(256) void mxf_fold_kernel(int64_t n, const double* __restrict__ src, float* __restrict__ dst) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) dst[i] += (float)src[i];
+}

@@ -8,6 +8,7 @@
 // Replaces: MultivariateNormal.log_pdf_impl (components/distributions/normal.py:157-178), MultivariateNormalMeanPrecision.log_pdf_impl
 // (normal.py:369-394) and MXNet autograd through linalg.potrf / linalg.trsm / linalg.sumlogdiag on (S, B, n, n) operands.
 #include "common.h"
+#include "fold.h"
 #include "smallmat.h"
 
 namespace {
@@ -232,13 +233,8 @@ void launch_logpdf(const MvnCall& c, void* out, hipStream_t st) {
                        (T)(0.5 * c.n * 1.8378770664093454836 /* log 2 pi */), (T*)out);
 }
 
-// dst[i] += src[i]: the double sums of the shared float32 gradients into the caller's buffers
-__global__ __launch_bounds__(256) void mvn_fold_kernel(int64_t n, const double* __restrict__ src, float* __restrict__ dst) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) dst[i] += (float)src[i];
-}
-
 // The gradients of operands shared over an axis are summed in double: in place for double; for float32 in zeroed scratch of the handle
-// ([dx | dmean | dA], only what is shared and wanted) that mvn_fold_kernel and mvn_inverse_bwd_kernel add to the caller's buffers.
+// ([dx | dmean | dA], only what is shared and wanted) that mxf_fold_kernel (fold.h) and mvn_inverse_bwd_kernel add to the caller's buffers.
 template <typename T>
 int launch_bwd(mxf_handle h, const MvnCall& c, const void* cot, void* dx, void* dmean, void* dA, hipStream_t st) {
     const int64_t rows = (int64_t)c.S * c.B, n = c.n;
@@ -258,8 +254,8 @@ int launch_bwd(mxf_handle h, const MvnCall& c, const void* cot, void* dx, void* 
     if (dA)
         hipLaunchKernelGGL((mvn_inverse_bwd_kernel<T>), dim3(grid_for((int64_t)c.S_A * c.B_A * 64)), dim3(256), 0, st, c.form, c.S, c.B, c.n,
                            (const T*)c.F, c.S_A, c.B_A, (const T*)cot, c.scale, (T*)dA, scratch && nA ? (const double*)sA : nullptr);
-    if (scratch && nx) hipLaunchKernelGGL(mvn_fold_kernel, dim3(grid_for(nx)), dim3(256), 0, st, nx, (const double*)sx, (float*)dx);
-    if (scratch && nm) hipLaunchKernelGGL(mvn_fold_kernel, dim3(grid_for(nm)), dim3(256), 0, st, nm, (const double*)sm, (float*)dmean);
+    if (scratch && nx) hipLaunchKernelGGL(mxf_fold_kernel, dim3(grid_for(nx)), dim3(256), 0, st, nx, (const double*)sx, (float*)dx);
+    if (scratch && nm) hipLaunchKernelGGL(mxf_fold_kernel, dim3(grid_for(nm)), dim3(256), 0, st, nm, (const double*)sm, (float*)dmean);
     return 0;
 }
 

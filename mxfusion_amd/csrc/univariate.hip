@@ -1,9 +1,10 @@
-// Log-densities of the univariate family (gfx950): Gamma, Gamma by mean and variance, Beta, Laplace, Uniform.  Built like
+// Log-densities of the univariate family (gfx950): Gamma, Gamma by mean and variance, Beta, Laplace, Uniform, Bernoulli.  Built like
 // normal_logpdf_kernel (elementwise.hip): thread i owns element i for all S samples, per-element parameter gradients need no atomics,
 // single-element parameters are block-reduced, one atomic per workgroup per scalar.  Launch-bound at the sizes of a prior.
 //
 // Replaces: Gamma / GammaMeanVariance.log_pdf_impl (components/distributions/gamma.py:45-59, :127-159), Beta.log_pdf_impl
-// (beta.py:46-68), Laplace.log_pdf_impl (laplace.py:37-55), Uniform.log_pdf_impl (uniform.py:38-62) + the sum(mean_S(.)) of
+// (beta.py:46-68), Laplace.log_pdf_impl (laplace.py:37-55), Uniform.log_pdf_impl (uniform.py:38-62), Bernoulli.log_pdf_impl
+// (bernoulli.py:62-78) + the sum(mean_S(.)) of
 // models/factor_graph.py:223, and MXNet autograd through them.
 #include "common.h"
 #include "special.h"
@@ -33,6 +34,8 @@ struct UniDist {
         } else if constexpr (KIND == MXF_D_LAPLACE) {
             inv = (T)1 / b;
             c = -log((T)2 * b);
+        } else if constexpr (KIND == MXF_D_BERNOULLI) {
+            c = 0;                                       // a is prob_true; b is unused (the caller passes a again)
         } else {
             inv = (T)1 / (b - a);
             c = -log(b - a);
@@ -63,6 +66,12 @@ struct UniDist {
             gx = -sg * inv;
             ga = sg * inv;
             gb = (fabs(d) * inv - (T)1) * inv;
+        } else if constexpr (KIND == MXF_D_BERNOULLI) {
+            const T la = log(a), l1a = log1p(-a);
+            lp = x * la + ((T)1 - x) * l1a;
+            gx = la - l1a;
+            ga = x / a - ((T)1 - x) / ((T)1 - a);
+            gb = 0;
         } else {
             const bool in = a <= x && x < b;
             lp = in ? c : -(T)INFINITY;
@@ -159,6 +168,7 @@ void launch(int kind, const UniArgs& u, bool elem, hipStream_t st) {
         case MXF_D_GAMMA_MV: launch_kind<T, MXF_D_GAMMA_MV>(u, elem, st); break;
         case MXF_D_BETA: launch_kind<T, MXF_D_BETA>(u, elem, st); break;
         case MXF_D_LAPLACE: launch_kind<T, MXF_D_LAPLACE>(u, elem, st); break;
+        case MXF_D_BERNOULLI: launch_kind<T, MXF_D_BERNOULLI>(u, elem, st); break;
         default: launch_kind<T, MXF_D_UNIFORM>(u, elem, st); break;
     }
 }
@@ -167,7 +177,7 @@ void launch(int kind, const UniArgs& u, bool elem, hipStream_t st) {
 int run(mxf_handle h, const char* name, int kind, int dtype, const UniArgs& u, bool elem, void* stream) {
     if (!h) return -1;
     if (u.n <= 0 || u.S <= 0) return 0;
-    if (kind < MXF_D_GAMMA || kind > MXF_D_UNIFORM) MXF_FAIL(h, -2, "%s: unknown distribution kind %d", name, kind);
+    if (kind < MXF_D_GAMMA || kind > MXF_D_BERNOULLI) MXF_FAIL(h, -2, "%s: unknown distribution kind %d", name, kind);
     if (dtype != MXF_F32 && dtype != MXF_F64) MXF_FAIL(h, -2, "%s: bad dtype %d", name, dtype);
     if (!u.x || !u.a || !u.b) MXF_FAIL(h, -2, "%s: null x or parameter", name);
     if ((u.n_a != 1 && u.n_a != u.n) || (u.n_b != 1 && u.n_b != u.n)) MXF_FAIL(h, -2, "%s: the parameters must have 1 or n elements", name);

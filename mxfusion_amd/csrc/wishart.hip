@@ -11,6 +11,7 @@
 // Replaces: Wishart.log_pdf_impl (components/distributions/wishart.py:62-96) over the per-element loops of util/special.py:21-132
 // (log_determinant, solve, trace, log_multivariate_gamma) and MXNet autograd through them.
 #include "common.h"
+#include "fold.h"
 #include "smallmat.h"
 #include "special.h"
 
@@ -86,7 +87,7 @@ __global__ __launch_bounds__(64) void wishart_logpdf_kernel(WishRows<T> a, T* __
 }
 
 // A gradient whose operand is broadcast over an axis is summed over it with atomics into a DOUBLE accumulator (the gradient itself for
-// double, scratch that wishart_fold_kernel adds for float32); the others are read-modify-writes of elements this wavefront alone owns.
+// double, scratch that mxf_fold_kernel (fold.h) adds for float32); the others are read-modify-writes of elements this wavefront alone owns.
 template <typename T>
 __device__ __forceinline__ void wish_add(bool shared, T* dst, double* sum, int64_t e, double v) {
     if (shared) atomic_add(sum + e, v); else dst[e] += (T)v;
@@ -151,11 +152,6 @@ __global__ __launch_bounds__(64) void wishart_logpdf_bwd_kernel(WishRows<T> a, c
     }
 }
 
-// dst[i] += src[i]: the double sums of the shared float32 gradients into the caller's buffers
-__global__ __launch_bounds__(256) void wishart_fold_kernel(int64_t n, const double* __restrict__ src, float* __restrict__ dst) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) dst[i] += (float)src[i];
-}
-
 struct WishCall {
     int dtype, S; int64_t B; int n;
     const void* X; int64_t ldx, ss_X;
@@ -191,7 +187,7 @@ unsigned grid_of(const WishCall& c) {
 }
 
 // The gradients of operands shared over an axis are summed in double: in place for double; for float32 in zeroed scratch of the handle
-// ([dX | ddof | dV], only what is shared and wanted) that wishart_fold_kernel adds to the caller's buffers.
+// ([dX | ddof | dV], only what is shared and wanted) that mxf_fold_kernel adds to the caller's buffers.
 template <typename T>
 int launch_bwd(mxf_handle h, const WishCall& c, const void* cot, void* dX, void* ddof, void* dV, hipStream_t st) {
     const int64_t n = c.n;
@@ -212,7 +208,7 @@ int launch_bwd(mxf_handle h, const WishCall& c, const void* cot, void* dX, void*
     const double* sums[3] = {sX, sd, sV};
     void* dsts[3] = {dX, ddof, dV};
     for (int i = 0; scratch && i < 3; ++i)
-        if (counts[i]) hipLaunchKernelGGL(wishart_fold_kernel, dim3(grid_for(counts[i])), dim3(256), 0, st, counts[i], sums[i], (float*)dsts[i]);
+        if (counts[i]) hipLaunchKernelGGL(mxf_fold_kernel, dim3(grid_for(counts[i])), dim3(256), 0, st, counts[i], sums[i], (float*)dsts[i]);
     return 0;
 }
 

@@ -353,7 +353,8 @@ def normal_logpdf_(x, mean, var, scale, out_acc, dx_acc=None, dmean_acc=None, dv
     return out_acc
 
 
-D_KIND = {'gamma': _lib.D_GAMMA, 'gamma_mv': _lib.D_GAMMA_MV, 'beta': _lib.D_BETA, 'laplace': _lib.D_LAPLACE, 'uniform': _lib.D_UNIFORM}
+D_KIND = {'gamma': _lib.D_GAMMA, 'gamma_mv': _lib.D_GAMMA_MV, 'beta': _lib.D_BETA, 'laplace': _lib.D_LAPLACE, 'uniform': _lib.D_UNIFORM,
+          'bernoulli': _lib.D_BERNOULLI}
 
 
 def _uni_check(x, *others):
@@ -525,6 +526,99 @@ def wishart_logpdf_bwd_(X, dof, V, cot, scale=1.0, dX_acc=None, ddof_acc=None, d
         if t is not None and tuple(t.shape) != shape:
             raise ValueError('Wishart: a buffer of shape %s where the operands ask for %s' % (tuple(t.shape), shape))
     _lib.call('mxf_wishart_logpdf_bwd', _h(X), _dt(X), S, B, n, *args, _p(cot), float(scale), _p(dX_acc), _p(ddof_acc), _p(dV_acc), _stream())
+
+
+def _simplex_check(what, ref, *others):
+    """the mxf_categorical_* and mxf_dirichlet_* entry points take raw pointers: every operand on ref's device and of its dtype"""
+    _require_gpu(ref)
+    _dt(ref)
+    for t in others:
+        if t is not None and (t.dtype != ref.dtype or t.device != ref.device):
+            raise TypeError('%s: every operand must have the dtype and device of the first (%s, %s); got %s, %s'
+                            % (what, ref.dtype, ref.device, t.dtype, t.device))
+
+
+def _simplex_operand(t, shared_axes):
+    """(t, strideS, strideB) of an operand (S|1, B|1, ...) as those entry points take it: dense, with the axes it is shared over -- of
+    extent 1, or expanded (stride 0), among shared_axes -- at stride 0.  An operand that already has that layout is passed as it is; a
+    copy never materialises a shared axis."""
+    for d in shared_axes:
+        if t.shape[d] > 1 and t.stride(d) == 0:
+            t = t.narrow(d, 0, 1)
+    if not t.is_contiguous():
+        t = t.contiguous()
+    S_t, B_t = int(t.shape[0]), int(t.shape[1])
+    row = t.numel() // max(S_t * B_t, 1)
+    return t, (0 if S_t == 1 else B_t * row), (0 if B_t == 1 else row)
+
+
+def _simplex_operands(what, x, p, labels, cot=None):
+    """x (S|1, B, K) (labels: (S|1, B)) and the parameter p (S|1, B|1, K) of a row-wise log-pdf, with S, B, K and the strides.  S is the
+    largest sample extent among the operands as they are given (an expanded axis counts with its extent) and the cotangent."""
+    if p.dim() != 3 or x.dim() != (2 if labels else 3) or (not labels and x.shape[2] != p.shape[2]):
+        raise ValueError('%s: x %s and a parameter (S|1, B|1, K); got %s, %s'
+                         % (what, '(S|1, B)' if labels else '(S|1, B, K)', tuple(x.shape), tuple(p.shape)))
+    B, K = int(x.shape[1]), int(p.shape[2])
+    S = max(int(x.shape[0]), int(p.shape[0]), 1 if cot is None else int(cot.shape[0]))
+    x, ss_x, _ = _simplex_operand(x, (0,))
+    p, ss_p, sb_p = _simplex_operand(p, (0, 1))
+    if x.shape[0] not in (1, S) or p.shape[0] not in (1, S) or p.shape[1] not in (1, B):
+        raise ValueError('%s: operands of %s, %s do not broadcast to (%d, %d) rows' % (what, tuple(x.shape), tuple(p.shape), S, B))
+    return x, ss_x, p, ss_p, sb_p, S, B, K
+
+
+def _simplex_buffers(what, cot, S, B, grads):
+    """the cotangent (S, B) and the gradient buffers, each against the shape of its operand: contiguous and of that shape"""
+    for t, shape in ((cot, (S, B)),) + tuple(grads):
+        if t is None:
+            continue
+        if not t.is_contiguous():
+            raise ValueError('%s: the cotangent and the gradient buffers must be contiguous' % what)
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError('%s: a buffer of shape %s where the operands ask for %s' % (what, tuple(t.shape), tuple(shape)))
+
+
+def categorical_logpdf(logp, x, one_hot=False, normalize=True, scale=1.0):
+    """scale * log p(x[s,b] | logp) (S, B): logp (S|1, B|1, K), softmax-normalised along K if `normalize`; x (S|1, B) class indices held in
+    logp's dtype (clipped to [0, K - 1]), or with one_hot (S|1, B, K) rows.  An axis of extent 1 or an expanded one is shared
+    (mxf_categorical_logpdf)."""
+    _simplex_check('Categorical', logp, x)
+    x, ss_x, logp, ss_p, sb_p, S, B, K = _simplex_operands('Categorical', x, logp, not one_hot)
+    out = torch.empty((S, B), dtype=logp.dtype, device=logp.device)
+    _lib.call('mxf_categorical_logpdf', _h(logp), _dt(logp), S, B, K, _p(logp), ss_p, sb_p, _p(x), ss_x, int(bool(one_hot)),
+              int(bool(normalize)), float(scale), _p(out), _stream())
+    return out
+
+
+def categorical_logpdf_bwd_(logp, x, cot, one_hot=False, normalize=True, scale=1.0, dlogp_acc=None, dx_acc=None):
+    """Reverse mode of categorical_logpdf: dlogp_acc (S|1, B|1, K) and, with one_hot only, dx_acc (S|1, B, K) -- dense, shaped like their
+    operands with the shared axes at extent 1 -- += the gradients under the cotangent cot (S, B) (mxf_categorical_logpdf_bwd)."""
+    _simplex_check('Categorical', logp, x, cot, dlogp_acc, dx_acc)
+    x, ss_x, logp, ss_p, sb_p, S, B, K = _simplex_operands('Categorical', x, logp, not one_hot, cot)
+    _simplex_buffers('Categorical', cot, S, B, ((dlogp_acc, tuple(logp.shape)), (dx_acc, tuple(x.shape))))
+    _lib.call('mxf_categorical_logpdf_bwd', _h(logp), _dt(logp), S, B, K, _p(logp), ss_p, sb_p, _p(x), ss_x, int(bool(one_hot)),
+              int(bool(normalize)), _p(cot), float(scale), _p(dlogp_acc), _p(dx_acc), _stream())
+
+
+def dirichlet_logpdf(x, alpha, normalize=True, scale=1.0):
+    """scale * log Dir(x[s,b] | alpha) (S, B): x (S|1, B, K), divided by its 1-norm along K if `normalize`; alpha (S|1, B|1, K).  An axis of
+    extent 1 or an expanded one is shared.  A row with an x_k <= 0 or an alpha_k <= 0 is NaN (mxf_dirichlet_logpdf)."""
+    _simplex_check('Dirichlet', x, alpha)
+    x, ss_x, alpha, ss_a, sb_a, S, B, K = _simplex_operands('Dirichlet', x, alpha, False)
+    out = torch.empty((S, B), dtype=x.dtype, device=x.device)
+    _lib.call('mxf_dirichlet_logpdf', _h(x), _dt(x), S, B, K, _p(x), ss_x, _p(alpha), ss_a, sb_a, int(bool(normalize)), float(scale),
+              _p(out), _stream())
+    return out
+
+
+def dirichlet_logpdf_bwd_(x, alpha, cot, normalize=True, scale=1.0, dx_acc=None, dalpha_acc=None):
+    """Reverse mode of dirichlet_logpdf: dx_acc (S|1, B, K), dalpha_acc (S|1, B|1, K) -- dense, shaped like their operands with the shared
+    axes at extent 1 -- += the gradients under the cotangent cot (S, B) (mxf_dirichlet_logpdf_bwd)."""
+    _simplex_check('Dirichlet', x, alpha, cot, dx_acc, dalpha_acc)
+    x, ss_x, alpha, ss_a, sb_a, S, B, K = _simplex_operands('Dirichlet', x, alpha, False, cot)
+    _simplex_buffers('Dirichlet', cot, S, B, ((dx_acc, tuple(x.shape)), (dalpha_acc, tuple(alpha.shape))))
+    _lib.call('mxf_dirichlet_logpdf_bwd', _h(x), _dt(x), S, B, K, _p(x), ss_x, _p(alpha), ss_a, sb_a, int(bool(normalize)), _p(cot),
+              float(scale), _p(dx_acc), _p(dalpha_acc), _stream())
 
 
 def adam_step_(w, g, m, v, lr, t, beta1=0.9, beta2=0.999, epsilon=1e-8, rescale_grad=1.0):
