@@ -442,6 +442,26 @@ int mxf_dirichlet_logpdf_bwd(mxf_handle h, int dtype, int S, int64_t B, int K, c
                              int64_t strideS_a, int64_t strideB_a, int normalize, const void* cot, double scale, void* dx_acc,
                              void* dalpha_acc, void* stream);
 
+/* A dense neural-network layer with the sample axis (dense.hip): X (S|1, N, I) with rows ldx >= I elements apart, W (S|1, O, I)
+ * row-major and dense (the layout of torch.nn.Linear.weight), b (S|1, O) or null; a sample stride of 0 shares the operand over the
+ * samples.  act: 0 identity, 1 tanh, 2 relu, 3 sigmoid.  Widths 1 <= I, O <= 128; anything else is status -3 (the caller's to route to
+ * mxf_gemm).  One launch for all S samples; every element of W[s] and b[s] is fetched once per workgroup of 32 (float) or 16 (double)
+ * rows.
+ *
+ * mxf_dense_fwd: Y[s,n,:] = act(X[s,n,:] W[s]^T + b[s]), WRITTEN to the dense Y (S, N, O).  Replaces the per-sample loop of
+ * FunctionEvaluation.eval over a Gluon Dense block (components/functions/function_evaluation.py:77-96).                                */
+int mxf_dense_fwd(mxf_handle h, int dtype, int S, int64_t N, int I, int O, int act, const void* X, int64_t ldx, int64_t strideS_x,
+                  const void* W, int64_t strideS_w, const void* b, int64_t strideS_b, void* Y, void* stream);
+
+/* Reverse mode of mxf_dense_fwd from its result Y (every supported act' is a function of Y) and the cotangent dY (S, N, O), both dense:
+ *   G = dY act'(Y),   dX[s] += G W[s],   dW[s] += G^T X[s],   db[s] += sum_n G
+ * ACCUMULATED into dense buffers shaped like their operands with a shared sample axis at extent 1 -- dX (S|1, N, I), dW (S|1, O, I),
+ * db (S|1, O); strideS_b says whether db is shared (0) or own (O).  The sums over the rows, and over s where the operand is shared, are
+ * formed in double for either dtype (float32: zeroed handle scratch and a fold more for dW and db).  Any output may be null.           */
+int mxf_dense_bwd(mxf_handle h, int dtype, int S, int64_t N, int I, int O, int act, const void* X, int64_t ldx, int64_t strideS_x,
+                  const void* W, int64_t strideS_w, int64_t strideS_b, const void* Y, const void* dY, void* dX_acc, void* dW_acc,
+                  void* db_acc, void* stream);
+
 /* MXNet Adam as driven by gluon.Trainer.step (batch_loop.py:46-60, minibatch_loop.py:71-91):
  * g*=rescale; m=b1 m+(1-b1)g; v=b2 v+(1-b2)g^2; w -= lr*sqrt(1-b2^t)/(1-b1^t) * m/(sqrt(v)+eps)      */
 int mxf_adam_step(mxf_handle h, int dtype, int64_t n, void* w, const void* g, void* m, void* v,

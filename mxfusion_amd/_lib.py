@@ -11,6 +11,8 @@ F32, F64 = 0, 1
 K_RBF, K_MATERN12, K_MATERN32, K_MATERN52, K_LINEAR, K_BIAS, K_WHITE = range(7)
 WRITE, ACC_ADD, ACC_MUL = 0, 1, 2
 D_GAMMA, D_GAMMA_MV, D_BETA, D_LAPLACE, D_UNIFORM, D_BERNOULLI = range(6)
+ACT_IDENTITY, ACT_TANH, ACT_RELU, ACT_SIGMOID = range(4)
+DENSE_MAX_WIDTH = 128
 
 _c = ctypes
 _vp, _i, _i64, _d = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_double
@@ -48,6 +50,8 @@ SIGNATURES = {
     'mxf_categorical_logpdf_bwd': [_i, _i, _i64, _i, _vp, _i64, _i64, _vp, _i64, _i, _i, _vp, _d, _vp, _vp, _vp],
     'mxf_dirichlet_logpdf': [_i, _i, _i64, _i, _vp, _i64, _vp, _i64, _i64, _i, _d, _vp, _vp],
     'mxf_dirichlet_logpdf_bwd': [_i, _i, _i64, _i, _vp, _i64, _vp, _i64, _i64, _i, _vp, _d, _vp, _vp, _vp],
+    'mxf_dense_fwd': [_i, _i, _i64, _i, _i, _i, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
+    'mxf_dense_bwd': [_i, _i, _i64, _i, _i, _i, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
     'mxf_normal_reparam_bwd': [_i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
     'mxf_adam_step': [_i, _i64, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _d, _i, _vp],
     'mxf_sgd_step': [_i, _i64, _vp, _vp, _vp, _d, _d, _d, _d, _vp],

@@ -621,6 +621,84 @@ def dirichlet_logpdf_bwd_(x, alpha, cot, normalize=True, scale=1.0, dx_acc=None,
               float(scale), _p(dx_acc), _p(dalpha_acc), _stream())
 
 
+ACT = {None: _lib.ACT_IDENTITY, 'identity': _lib.ACT_IDENTITY, 'tanh': _lib.ACT_TANH, 'relu': _lib.ACT_RELU, 'sigmoid': _lib.ACT_SIGMOID}
+
+
+def _dense_act(act):
+    return ACT[act] if act is None or isinstance(act, str) else int(act)
+
+
+def _dense_operands(X, W, b):
+    """X (S|1, N, I), W (S|1, O, I), b (S|1, O) or None as the mxf_dense_* entry points take them: rows of X contiguous and ldx apart, W and
+    b dense; an expanded sample axis counts as shared and is never materialised."""
+    if X.dim() != 3 or W.dim() != 3 or W.shape[2] != X.shape[2] or (b is not None and (b.dim() != 2 or b.shape[1] != W.shape[1])):
+        raise ValueError('dense: X (S|1, N, I), W (S|1, O, I), b (S|1, O); got %s, %s, %s'
+                         % (tuple(X.shape), tuple(W.shape), None if b is None else tuple(b.shape)))
+    share = lambda t: t.narrow(0, 0, 1) if t is not None and t.shape[0] > 1 and t.stride(0) == 0 else t
+    X, W, b = share(X), _c(share(W)), _c(share(b))
+    N, I = int(X.shape[1]), int(X.shape[2])
+    if X.stride(2) != 1 or (N > 1 and X.stride(1) < I) or (X.shape[0] > 1 and X.stride(0) < (N - 1) * X.stride(1) + I):
+        X = X.contiguous()
+    S = num_samples(X, W, b)
+    if any(t is not None and t.shape[0] not in (1, S) for t in (X, W, b)):
+        raise ValueError('dense: sample extents %s do not broadcast' % [t.shape[0] for t in (X, W, b) if t is not None])
+    return X, W, b, S, N, I, int(W.shape[1]), (X.stride(1) if N > 1 else I)
+
+
+def _dense_fits(I, O):
+    return 1 <= I <= _lib.DENSE_MAX_WIDTH and 1 <= O <= _lib.DENSE_MAX_WIDTH
+
+
+def _dense_dact(act, Y):
+    return {_lib.ACT_IDENTITY: lambda: None, _lib.ACT_TANH: lambda: 1 - Y * Y, _lib.ACT_RELU: lambda: (Y > 0).to(Y.dtype),
+            _lib.ACT_SIGMOID: lambda: Y * (1 - Y)}[act]()
+
+
+def dense(X, W, b=None, act=None):
+    """Y[s] = act(X[s] W[s]^T + b[s]) (S, N, O) for all samples in one launch (mxf_dense_fwd): X (S|1, N, I), W (S|1, O, I) in the layout of
+    torch.nn.Linear.weight, b (S|1, O) or None, act None / 'identity', 'tanh', 'relu', 'sigmoid'.  Widths beyond the kernel's (128) go
+    through gemm and elementwise torch."""
+    _simplex_check('dense', X, W, b)
+    act = _dense_act(act)
+    X, W, b, S, N, I, O, ldx = _dense_operands(X, W, b)
+    if not _dense_fits(I, O):
+        Z = gemm(X, W, transB=True)
+        if b is not None:
+            Z = Z + b.unsqueeze(1)
+        return {_lib.ACT_IDENTITY: lambda z: z, _lib.ACT_TANH: torch.tanh, _lib.ACT_RELU: torch.relu, _lib.ACT_SIGMOID: torch.sigmoid}[act](Z)
+    Y = torch.empty((S, N, O), dtype=X.dtype, device=X.device)
+    _lib.call('mxf_dense_fwd', _h(X), _dt(X), S, N, I, O, act, _p(X), ldx, _ss(X), _p(W), _ss(W), _p(b), _ss(b), _p(Y), _stream())
+    return Y
+
+
+def dense_bwd_(X, W, Y, dY, act=None, dX_acc=None, dW_acc=None, db_acc=None):
+    """Reverse mode of dense from its result Y and the cotangent dY (S, N, O): dX_acc (S|1, N, I), dW_acc (S|1, O, I), db_acc (S|1, O) --
+    dense, shaped like their operands with a shared sample axis at extent 1 -- += the gradients (mxf_dense_bwd)."""
+    _simplex_check('dense', X, W, Y, dY, dX_acc, dW_acc, db_acc)
+    act = _dense_act(act)
+    X, W, _, S, N, I, O, ldx = _dense_operands(X, W, None)
+    S = max(S, int(Y.shape[0]))
+    _simplex_buffers('dense', None, S, N, ((dX_acc, (X.shape[0], N, I)), (dW_acc, tuple(W.shape))))
+    if tuple(Y.shape) != (S, N, O) or tuple(dY.shape) != (S, N, O) or not Y.is_contiguous() or not dY.is_contiguous():
+        raise ValueError('dense: Y and dY must be contiguous (S, N, O) = %s; got %s, %s' % ((S, N, O), tuple(Y.shape), tuple(dY.shape)))
+    if db_acc is not None and (not db_acc.is_contiguous() or tuple(db_acc.shape) not in ((1, O), (S, O))):
+        raise ValueError('dense: db_acc must be contiguous (S|1, O); got %s' % (tuple(db_acc.shape),))
+    ss_b = 0 if db_acc is None or db_acc.shape[0] == 1 else O
+    if not _dense_fits(I, O):
+        d = _dense_dact(act, Y)
+        G = dY if d is None else dY * d
+        fold = lambda t, acc: acc.add_(t.sum(0, keepdim=True) if acc.shape[0] == 1 and t.shape[0] > 1 else t)
+        if dX_acc is not None:
+            fold(gemm(G, W), dX_acc)
+        if dW_acc is not None:
+            fold(gemm(G, X, transA=True), dW_acc)
+        if db_acc is not None:
+            fold(G.sum(1), db_acc)
+        return
+    _lib.call('mxf_dense_bwd', _h(X), _dt(X), S, N, I, O, act, _p(X), ldx, _ss(X), _p(W), _ss(W), ss_b, _p(Y), _p(dY),
+              _p(dX_acc), _p(dW_acc), _p(db_acc), _stream())
+
+
 def adam_step_(w, g, m, v, lr, t, beta1=0.9, beta2=0.999, epsilon=1e-8, rescale_grad=1.0):
     _lib.call('mxf_adam_step', _h(w), _dt(w), w.numel(), _p(w), _p(g), _p(m), _p(v), float(lr), float(beta1), float(beta2),
               float(epsilon), float(rescale_grad), int(t), _stream())
