@@ -8,8 +8,8 @@ and its gradient comes back summed.  The result is (S, ...) without the class ax
 import torch
 
 from ... import ops
-from .mvn import _flatten, _numel
-from .univariate import UnivariateDistribution, _carve
+from ._fused import _flatten, carved_grads
+from .univariate import UnivariateDistribution
 
 
 class _CategoricalLogPdfFn(torch.autograd.Function):
@@ -25,10 +25,7 @@ class _CategoricalLogPdfFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         logp, x = ctx.saved_tensors
-        shapes = (tuple(logp.shape), tuple(x.shape))
-        need = [ctx.needs_input_grad[3], ctx.needs_input_grad[4] and ctx.one_hot]
-        grads = _carve([_numel(s) if w else 0 for s, w in zip(shapes, need)], logp)
-        grads = [None if t is None else t.view(s) for t, s in zip(grads, shapes)]
+        grads = carved_grads((logp.shape, x.shape), (ctx.needs_input_grad[3], ctx.needs_input_grad[4] and ctx.one_hot), logp)
         ops.categorical_logpdf_bwd_(logp, x, g.contiguous(), ctx.one_hot, ctx.normalize, ctx.scale, *grads)
         return (None, None, None) + tuple(grads)
 

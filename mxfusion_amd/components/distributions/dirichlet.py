@@ -9,8 +9,7 @@ import torch
 
 from ... import ops
 from .distribution import Distribution
-from .mvn import _flatten, _numel
-from .univariate import _carve
+from ._fused import _flatten, carved_grads
 
 
 class _DirichletLogPdfFn(torch.autograd.Function):
@@ -26,10 +25,7 @@ class _DirichletLogPdfFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, alpha = ctx.saved_tensors
-        shapes = (tuple(x.shape), tuple(alpha.shape))
-        need = [ctx.needs_input_grad[i] for i in (1, 2)]
-        grads = _carve([_numel(s) if w else 0 for s, w in zip(shapes, need)], x)
-        grads = [None if t is None else t.view(s) for t, s in zip(grads, shapes)]
+        grads = carved_grads((x.shape, alpha.shape), ctx.needs_input_grad[1:3], x)
         ops.dirichlet_logpdf_bwd_(x, alpha, g.contiguous(), ctx.normalize, 1.0, *grads)
         return (None,) + tuple(grads)
 

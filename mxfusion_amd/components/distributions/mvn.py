@@ -14,43 +14,7 @@ from ... import ops
 from ...common import config
 from .distribution import Distribution
 from .gp._linalg import CholLogPdfFn, chol, gemm, trsm
-from .univariate import _carve
-
-
-def _numel(shape):
-    n = 1
-    for s in shape:
-        n *= int(s)
-    return n
-
-
-def _unexpand(t, ndims):
-    """a leading axis that is an expanded view (stride 0) back to extent 1: the kernels broadcast it, and autograd sums its gradient"""
-    for d in range(ndims):
-        if t.shape[d] > 1 and t.stride(d) == 0:
-            t = t.narrow(d, 0, 1)
-    return t
-
-
-def _flatten(t, lead, tail, full=False):
-    """t (S|1, ..., *tail-broadcastable) -> (S|1, B|1, *tail): leading dimensions aligned with `lead` from the right and flattened into one
-    batch axis, which stays at extent 1 where t has nothing but ones there (unless `full`)."""
-    k = len(tail)
-    if t.dim() < 1 + k:
-        raise ValueError('multivariate normal: an operand of shape %s has no sample axis in front of %d trailing dimension(s)'
-                         % (tuple(t.shape), k))
-    want = 1 + len(lead) + k
-    if t.dim() < want:
-        t = t.reshape((t.shape[0],) + (1,) * (want - t.dim()) + tuple(t.shape[1:]))
-    t = _unexpand(t, t.dim() - k)
-    mid = tuple(t.shape[1:t.dim() - k])
-    if tuple(t.shape[t.dim() - k:]) != tuple(tail):
-        t = t.expand(tuple(t.shape[:t.dim() - k]) + tuple(tail))
-    if all(m == 1 for m in mid) and not (full and _numel(lead) > 1):
-        return t.reshape((t.shape[0], 1) + tuple(tail))
-    if mid != tuple(lead):
-        t = t.expand((t.shape[0],) + tuple(lead) + tuple(tail))
-    return t.reshape((t.shape[0], _numel(lead)) + tuple(tail))
+from ._fused import _flatten, _numel, carved_grads, replicate
 
 
 class _MvnLogPdfFn(torch.autograd.Function):
@@ -70,10 +34,7 @@ class _MvnLogPdfFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _):
         x, mean, F = ctx.saved_tensors
-        shapes = (tuple(x.shape), tuple(mean.shape), tuple(F.shape))
-        need = [ctx.needs_input_grad[i] for i in (2, 3, 4)]
-        grads = _carve([_numel(s) if w else 0 for s, w in zip(shapes, need)], x)
-        grads = [None if t is None else t.view(s) for t, s in zip(grads, shapes)]
+        grads = carved_grads((x.shape, mean.shape, F.shape), ctx.needs_input_grad[2:5], x)
         ops.mvn_logpdf_bwd_(x, mean, F, g.contiguous(), ctx.form, ctx.scale, *grads)
         return (None, None) + tuple(grads)
 
@@ -132,14 +93,8 @@ class _MultivariateNormalBase(Distribution):
                                                       output_names=['random_variable'], rand_gen=rand_gen, dtype=dtype, ctx=ctx)
 
     def replicate_self(self, attribute_map=None):
-        """normal.py:144-155, :356-367 over factor.py:121-143: a factor of the same class with the same names and UUID and no inputs or
-        outputs yet, for a replicated graph to wire up."""
-        rep = self.__class__.__new__(self.__class__)
-        Distribution.__init__(rep, None, None, list(self.input_names), list(self.output_names), rand_gen=self._rand_gen, dtype=self.dtype,
-                              ctx=self.ctx)
-        rep.uuid = self.uuid
-        rep.log_pdf_scaling = self.log_pdf_scaling
-        return rep
+        """normal.py:144-155, :356-367"""
+        return replicate(self)
 
     def _log_pdf(self, mean, matrix, random_variable):
         n = int(matrix.shape[-1])

@@ -4,6 +4,7 @@ mode; this is q(X) and p(X) of the Monte-Carlo ELBO path."""
 import torch
 
 from ... import ops
+from ._fused import _carve
 from .distribution import Distribution
 from ..variables.variable import Variable
 
@@ -19,14 +20,9 @@ class _NormalLogPdfSumFn(torch.autograd.Function):
         m1, v1 = mean.reshape(-1), var.reshape(-1)
         # the kernel accumulates into its outputs: ONE zero-filled buffer carved into (out, dm, dv, dx) instead of four fills per call
         # (the step's head and tail are paced by the number of launches, ~5 us each)
-        sizes = [1, m1.numel() if need[1] else 0, v1.numel() if need[2] else 0, x.numel() if need[0] else 0]
-        buf = torch.zeros(sum(sizes) + 12, dtype=x.dtype, device=x.device)
-        off = [0, 4, 4 + (sizes[1] + 3) // 4 * 4]                       # 16-byte aligned starts
-        off.append(off[2] + (sizes[2] + 3) // 4 * 4)
-        out = buf[0:1]
-        dm = buf[off[1]:off[1] + sizes[1]] if need[1] else None
-        dv = buf[off[2]:off[2] + sizes[2]] if need[2] else None
-        dx = buf[off[3]:off[3] + sizes[3]].view(x.shape) if need[0] else None
+        out, dm, dv, dx = _carve([1, m1.numel() if need[1] else 0, v1.numel() if need[2] else 0, x.numel() if need[0] else 0], x)
+        if dx is not None:
+            dx = dx.view(x.shape)
         ops.normal_logpdf_(x, m1, v1, float(scaling) / S, out, dx, dm, dv)
         ctx.grads = (dx, dm, dv, mean.shape, var.shape)
         return out.reshape(())
@@ -51,9 +47,7 @@ class _NormalReparamFn(torch.autograd.Function):
     def backward(ctx, dx):
         var, eps = ctx.saved_tensors
         ms, vs = ctx.shapes
-        n = var.numel()
-        buf = torch.zeros(2 * ((n + 3) // 4 * 4), dtype=var.dtype, device=var.device)
-        dm, dv = buf[:n], buf[(n + 3) // 4 * 4:(n + 3) // 4 * 4 + n]
+        dm, dv = _carve([var.numel()] * 2, var)
         ops.normal_reparam_bwd_(var.reshape(-1), eps, dx.contiguous(), dm, dv)
         return dm.reshape(ms), dv.reshape(vs), None
 

@@ -5,18 +5,8 @@ and whether the reference multiplies its log-pdf by `log_pdf_scaling` (`_scaled`
 import torch
 
 from ... import ops
+from ._fused import _carve, carved_grads
 from .distribution import Distribution
-
-
-def _carve(sizes, like):
-    """ONE zero-filled buffer carved into len(sizes) accumulators with 16-byte aligned starts (size 0: None), as _NormalLogPdfSumFn does:
-    the kernels accumulate into their outputs, and a fill per output would be a launch per output."""
-    starts, off = [], 0
-    for s in sizes:
-        starts.append(off)
-        off += (s + 3) // 4 * 4
-    buf = torch.zeros(max(off, 1), dtype=like.dtype, device=like.device)
-    return [buf[o:o + s] if s else None for o, s in zip(starts, sizes)]
 
 
 class _UnivariateLogPdfSumFn(torch.autograd.Function):
@@ -54,10 +44,9 @@ class _UnivariateLogPdfFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, a, b = ctx.saved_tensors
-        need = [ctx.needs_input_grad[i] for i in (2, 3, 4)]
-        dx, da, db = _carve([t.numel() if w else 0 for t, w in zip((x, a, b), need)], x)
-        ops.univariate_logpdf_bwd_(ctx.kind, x, a, b, g.contiguous(), ctx.scale, dx, da, db)
-        return (None, None) + tuple(None if d is None else d.view(t.shape) for d, t in zip((dx, da, db), (x, a, b)))
+        grads = carved_grads((x.shape, a.shape, b.shape), ctx.needs_input_grad[2:5], x)
+        ops.univariate_logpdf_bwd_(ctx.kind, x, a, b, g.contiguous(), ctx.scale, *grads)
+        return (None, None) + tuple(grads)
 
 
 class UnivariateDistribution(Distribution):

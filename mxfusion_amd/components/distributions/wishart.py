@@ -14,8 +14,7 @@ from ... import ops
 from ...common import config
 from .distribution import Distribution
 from .gp._linalg import chol, coldot, gemm, trsm
-from .mvn import _flatten, _numel
-from .univariate import _carve
+from ._fused import _flatten, _numel, carved_grads, replicate
 
 
 class _WishartLogPdfFn(torch.autograd.Function):
@@ -33,10 +32,7 @@ class _WishartLogPdfFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _):
         X, nu, V = ctx.saved_tensors
-        shapes = (tuple(X.shape), tuple(nu.shape), tuple(V.shape))
-        need = [ctx.needs_input_grad[i] for i in (1, 2, 3)]
-        grads = _carve([_numel(s) if w else 0 for s, w in zip(shapes, need)], X)
-        grads = [None if t is None else t.view(s) for t, s in zip(grads, shapes)]
+        grads = carved_grads((X.shape, nu.shape, V.shape), ctx.needs_input_grad[1:4], X)
         ops.wishart_logpdf_bwd_(X, nu, V, g.contiguous(), ctx.scale, *grads)
         return (None,) + tuple(grads)
 
@@ -81,14 +77,8 @@ class Wishart(Distribution):
                                       output_names=['random_variable'], rand_gen=rand_gen, dtype=dtype, ctx=ctx)
 
     def replicate_self(self, attribute_map=None):
-        """wishart.py:49-60 over factor.py:121-143: a factor of the same class with the same names and UUID and no inputs or outputs yet,
-        for a replicated graph to wire up."""
-        rep = self.__class__.__new__(self.__class__)
-        Distribution.__init__(rep, None, None, list(self.input_names), list(self.output_names), rand_gen=self._rand_gen, dtype=self.dtype,
-                              ctx=self.ctx)
-        rep.uuid = self.uuid
-        rep.log_pdf_scaling = self.log_pdf_scaling
-        return rep
+        """wishart.py:49-60"""
+        return replicate(self)
 
     def _dof(self, degrees_of_freedom, like):
         """the degrees of freedom as a floating tensor with a sample axis; an integer one is cast to the distribution's dtype (wishart.py:82)"""

@@ -12,6 +12,7 @@ import copy
 import torch
 
 from ... import _lib, ops
+from ..distributions._fused import carved_grads
 from ..factor import Factor
 from ..variables.variable import Variable, VariableType
 from .function_evaluation import FunctionEvaluation
@@ -63,15 +64,8 @@ class _DenseFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dY):
         X, W, Y = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        shapes = [tuple(X.shape) if need[0] else None, tuple(W.shape) if need[1] else None, ctx.b_shape if need[2] else None]
-        # the kernel accumulates: ONE zero-filled buffer carved into (dX, dW, db), 16-byte aligned starts
-        sizes = [0 if s is None else (int(torch.Size(s).numel()) + 3) // 4 * 4 for s in shapes]
-        buf = torch.zeros(max(sum(sizes), 1), dtype=Y.dtype, device=Y.device)
-        grads, off = [], 0
-        for s, n in zip(shapes, sizes):
-            grads.append(None if s is None else buf[off:off + int(torch.Size(s).numel())].view(s))
-            off += n
+        need = [w and s is not None for w, s in zip(ctx.needs_input_grad, (X.shape, W.shape, ctx.b_shape))]
+        grads = carved_grads((X.shape, W.shape, ctx.b_shape or ()), need, Y)
         if any(g is not None for g in grads):
             ops.dense_bwd_(X, W, Y, dY.contiguous(), ctx.act, *grads)
         return grads[0], grads[1], grads[2], None
@@ -79,7 +73,7 @@ class _DenseFn(torch.autograd.Function):
 
 def _unexpand(t):
     """an operand whose sample axis is expanded (stride 0) as its one shared block"""
-    return t.narrow(0, 0, 1) if t.shape[0] > 1 and t.stride(0) == 0 else t
+    return ops._shared_axes(t, (0,), None)[0]
 
 
 class TorchFunctionEvaluation(FunctionEvaluation):

@@ -6,8 +6,7 @@
 //   [i][column] with a row padded to 33 (conflict-free both for the staging writes, consecutive i, and for the reads, consecutive columns):
 //   every element of W[s] and b[s] is fetched once per workgroup.  Thread (tx = column, ty) sums over i for TN / 8 rows in registers.
 //   Reverse: G = dY act'(Y) [TN][O] and the X tile are staged; db and dW are sums over the tile's rows of G and of G^T X, one element per
-//   thread and trip, added with atomics to a DOUBLE accumulator (the caller's buffer for double, zeroed handle scratch that
-//   mxf_fold2_kernel adds for float32): the sum over the row tiles, and over s where W or b is shared, is formed in double for either
+//   thread and trip, added with atomics to a DOUBLE accumulator (shared_grad.h): the sum over the row tiles, and over s where W or b is shared, is formed in double for either
 //   dtype.  dX = G W[s] takes W through LDS in chunks of 16 rows; thread (i, half) holds TN / 2 rows.  Where X is shared over the samples
 //   a workgroup loops over s itself and sums its dX in double registers: one plain += per element.
 // Plain FMAs for both dtypes (the layer is paced by its launch, not by its arithmetic).
@@ -15,7 +14,7 @@
 // Replaces: the per-sample loop of FunctionEvaluation.eval over a Gluon Dense block (components/functions/function_evaluation.py:77-96:
 // FullyConnected + Activation per sample, concat) and MXNet autograd through it.
 #include "common.h"
-#include "fold.h"
+#include "shared_grad.h"
 
 namespace {
 
@@ -105,6 +104,8 @@ __global__ __launch_bounds__(256) void dense_fwd_kernel(DenseArgs<T> a, T* __res
     }
 }
 
+// The gradients' indices come from shared_row (shared_grad.h), whose rows are (s, b): dX (S|1, N, I) takes the data row n as b with B = N;
+// dW (S|1, O, I) and db (S|1, O) have the sample axis alone, b = 0 of B = 1, and the whole per-sample block as their row.
 // by_rows: X is shared over the samples and dX is wanted: the workgroup owns a row tile and loops over s.  sW, sB: double accumulators
 // laid out as dW (S|1, O, I) and db (S|1, O).
 template <typename T>
@@ -137,14 +138,14 @@ __global__ __launch_bounds__(256) void dense_bwd_kernel(DenseArgs<T> a, const T*
             for (int o = threadIdx.x; o < a.O; o += 256) {
                 T v = 0;
                 for (int r = 0; r < TN; ++r) v += Gs[r * a.O + o];
-                atomic_add(sB + (a.ss_b ? s : 0) * a.O + o, (double)v);
+                atomic_add(sB + shared_row(a.ss_b, true, s, 0, 1, a.O) + o, (double)v);
             }
         if (sW)
             for (int idx = threadIdx.x; idx < a.O * a.I; idx += 256) {
                 const int o = idx / a.I, i = idx - o * a.I;
                 T v = 0;
                 for (int r = 0; r < TN; ++r) v = fma(Gs[r * a.O + o], Xs[r * a.I + i], v);
-                atomic_add(sW + (a.ss_w ? s : 0) * (int64_t)a.O * a.I + idx, (double)v);
+                atomic_add(sW + shared_row(a.ss_w, true, s, 0, 1, (int64_t)a.O * a.I) + idx, (double)v);
             }
         if (dX) {
             T acc[RX];
@@ -168,7 +169,7 @@ __global__ __launch_bounds__(256) void dense_bwd_kernel(DenseArgs<T> a, const T*
                 for (int r = 0; r < RX; ++r) {
                     const int64_t n = n0 + half + 2 * r;
                     if (by_rows) tot[r] += (double)acc[r];
-                    else if (n < a.N) dX[((a.ss_x ? s : 0) * a.N + n) * a.I + xi] += acc[r];
+                    else if (n < a.N) dX[shared_row(a.ss_x, true, s, n, a.N, a.I) + xi] += acc[r];
                 }
             }
         }
@@ -231,21 +232,13 @@ int launch_bwd(mxf_handle h, const DenseCall& c, const void* Y, const void* dY, 
     int64_t tiles;
     if (int rc = check_operands(h, c, &tiles, DenseTile<T>::rows)) return rc;
     const bool by_rows = dX && c.ss_x == 0 && c.S > 1;
-    const int64_t nw = dW ? (c.ss_w ? c.S : 1) * (int64_t)c.O * c.I : 0, nb = db ? (c.ss_b ? c.S : 1) * (int64_t)c.O : 0;
-    double *sW = (double*)dW, *sB = (double*)db;
-    const bool scratch = sizeof(T) == 4 && nw + nb > 0;
-    if (scratch) {
-        double* sp = (double*)mxf_ws(h, (size_t)(nw + nb) * sizeof(double));
-        if (!sp) MXF_FAIL(h, -4, "%s: out of memory for %lld scratch doubles", c.name, (long long)(nw + nb));
-        MXF_HIP(h, hipMemsetAsync(sp, 0, (size_t)(nw + nb) * sizeof(double), st));
-        sW = dW ? sp : nullptr;
-        sB = db ? sp + nw : nullptr;
-    }
+    SharedSums sums;          // dW and db are sums over the row tiles: in double whenever they are wanted, shared over s or not
+    if (int rc = shared_sums_open<T>(h, c.name, {{dW, shared_numel(c.ss_w, true, c.S, 1, (int64_t)c.O * c.I)}, {db, shared_numel(c.ss_b, true, c.S, 1, c.O)}},
+                                     st, &sums))
+        return rc;
     hipLaunchKernelGGL(dense_bwd_kernel<T>, dim3((unsigned)(by_rows ? tiles : tiles * c.S)), dim3(256), 0, st, args_of<T>(c, tiles),
-                       (const T*)Y, (const T*)dY, (T*)dX, sW, sB, by_rows ? 1 : 0);
-    if (scratch)
-        hipLaunchKernelGGL(mxf_fold2_kernel, dim3(grid_for(nw + nb)), dim3(256), 0, st, nw, (const double*)(dW ? sW : sB), (float*)dW, nb,
-                           (float*)db);
+                       (const T*)Y, (const T*)dY, (T*)dX, sums.acc[0], sums.acc[1], by_rows ? 1 : 0);
+    shared_sums_close(sums, st);
     return 0;
 }
 

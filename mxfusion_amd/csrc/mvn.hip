@@ -8,7 +8,7 @@
 // Replaces: MultivariateNormal.log_pdf_impl (components/distributions/normal.py:157-178), MultivariateNormalMeanPrecision.log_pdf_impl
 // (normal.py:369-394) and MXNet autograd through linalg.potrf / linalg.trsm / linalg.sumlogdiag on (S, B, n, n) operands.
 #include "common.h"
-#include "fold.h"
+#include "shared_grad.h"
 #include "smallmat.h"
 
 namespace {
@@ -113,18 +113,18 @@ __global__ __launch_bounds__(256) void mvn_logpdf_kernel(MvnRows<T> a, T c, T* _
 
 // With w = scale * cot[s,b] and alpha = K^-1 d:  dx -= w alpha,  dmean += w alpha,  dA += 1/2 w alpha alpha^T (covariance form) or
 // -1/2 w d d^T (precision form).  A gradient whose operand is broadcast over an axis is summed over it with atomics into a DOUBLE
-// accumulator (sx, sm, sA: the gradient itself for double, scratch that the closing kernels fold in for float32 -- a float32 sum of
-// hundreds of rows in arrival order would lose digits that the operands have); the others are plain read-modify-writes of elements this
-// half-wave alone owns.  The term in K^-1 is mvn_inverse_bwd_kernel's.
+// accumulator (sx, sm, sA: shared_grad.h); the others are plain read-modify-writes of elements this half-wave alone owns.  The term in
+// K^-1 is mvn_inverse_bwd_kernel's.
 template <typename T>
 __global__ __launch_bounds__(256) void mvn_logpdf_bwd_kernel(MvnRows<T> a, const T* __restrict__ cot, T* dx, T* dmean, T* dA, double* sx,
                                                              double* sm, double* sA) {
     const int i = threadIdx.x & 31, sub = threadIdx.x >> 5, n = a.n;
     const int64_t rows = (int64_t)a.S * a.B;
-    const bool x_shared = a.ss_x == 0 && a.S > 1;
-    const bool m_shared = (a.ss_m == 0 && a.S > 1) || (a.sb_m == 0 && a.B > 1);
-    const bool A_shared = (a.S_A == 1 && a.S > 1) || (a.B_A == 1 && a.B > 1);
-    const int64_t db_m = a.sb_m ? n : 0, ds_m = a.ss_m ? (a.sb_m ? a.B : 1) * n : 0;     // dmean is dense (S|1, B|1, n)
+    const bool x_shared = shared_over(a.ss_x, true, a.S, a.B), m_shared = shared_over(a.ss_m, a.sb_m, a.S, a.B);
+    const bool A_shared = shared_over(a.S_A != 1, a.B_A != 1, a.S, a.B);
+    // dmean's row index, shared_row(ss_m, sb_m, s, b, B, n), is linear in (s, b): its two steps, taken once (in the loop it costs the
+    // double kernel two scalar registers and a wave of occupancy)
+    const int64_t ds_m = shared_row(a.ss_m, a.sb_m, 1, 0, a.B, n), db_m = shared_row(a.ss_m, a.sb_m, 0, 1, a.B, n);
     for (int64_t base = (int64_t)blockIdx.x * MVN_ROWS; base < rows; base += (int64_t)gridDim.x * MVN_ROWS) {
         const MvnRow<T> row(a, base + sub, rows, i);
         const T* Fm = a.F + row.m * n * n;
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256) void mvn_logpdf_bwd_kernel(MvnRows<T> a, const
         const T z = mvn_matvec(Fm, a.form == 1, row.d, n, i, row.on);
         const T alpha = mvn_matvec(Fm, a.form == 0, z, n, i, row.on);       // L^-T z, or L z
         if (row.on && dx) {
-            const int64_t e = (a.ss_x ? row.s : 0) * a.B * n + row.b * n + i;
+            const int64_t e = shared_row(a.ss_x, true, row.s, row.b, a.B, n) + i;
             if (x_shared) atomic_add(sx + e, (double)(-w * alpha)); else dx[e] -= w * alpha;
         }
         if (row.on && dmean) {
@@ -233,29 +233,25 @@ void launch_logpdf(const MvnCall& c, void* out, hipStream_t st) {
                        (T)(0.5 * c.n * 1.8378770664093454836 /* log 2 pi */), (T*)out);
 }
 
-// The gradients of operands shared over an axis are summed in double: in place for double; for float32 in zeroed scratch of the handle
-// ([dx | dmean | dA], only what is shared and wanted) that mxf_fold_kernel (fold.h) and mvn_inverse_bwd_kernel add to the caller's buffers.
+// dx, dmean and dA where their operand is shared over an axis are summed in double (shared_grad.h); mvn_inverse_bwd_kernel adds dA's float32
+// sums itself, before its own rounding.
 template <typename T>
 int launch_bwd(mxf_handle h, const MvnCall& c, const void* cot, void* dx, void* dmean, void* dA, hipStream_t st) {
     const int64_t rows = (int64_t)c.S * c.B, n = c.n;
-    const bool x_sh = dx && c.ss_x == 0 && c.S > 1, m_sh = dmean && ((c.ss_m == 0 && c.S > 1) || (c.sb_m == 0 && c.B > 1));
-    const bool A_sh = dA && ((c.S_A == 1 && c.S > 1) || (c.B_A == 1 && c.B > 1));
-    const int64_t nx = x_sh ? c.B * n : 0, nm = m_sh ? (c.ss_m ? c.S : 1) * (c.sb_m ? c.B : 1) * n : 0, nA = A_sh ? c.S_A * c.B_A * n * n : 0;
-    double *sx = (double*)dx, *sm = (double*)dmean, *sA = (double*)dA;
-    const bool scratch = sizeof(T) == 4 && nx + nm + nA > 0;
-    if (scratch) {
-        double* ws = (double*)mxf_ws(h, (size_t)(nx + nm + nA) * sizeof(double));
-        if (!ws) MXF_FAIL(h, -4, "mxf_mvn_logpdf_bwd: out of memory for %lld scratch doubles", (long long)(nx + nm + nA));
-        MXF_HIP(h, hipMemsetAsync(ws, 0, (size_t)(nx + nm + nA) * sizeof(double), st));
-        sx = ws; sm = ws + nx; sA = ws + nx + nm;
-    }
+    const bool own_sA = c.S_A != 1, own_bA = c.B_A != 1;
+    SharedSums sums;
+    if (int rc = shared_sums_open<T>(h, "mxf_mvn_logpdf_bwd",
+                                     {{dx, shared_over(c.ss_x, true, c.S, c.B) ? shared_numel(c.ss_x, true, c.S, c.B, n) : 0},
+                                      {dmean, shared_over(c.ss_m, c.sb_m, c.S, c.B) ? shared_numel(c.ss_m, c.sb_m, c.S, c.B, n) : 0},
+                                      {dA, shared_over(own_sA, own_bA, c.S, c.B) ? shared_numel(own_sA, own_bA, c.S, c.B, n * n) : 0, true}},
+                                     st, &sums))
+        return rc;
     hipLaunchKernelGGL((mvn_logpdf_bwd_kernel<T>), dim3(grid_for(rows * 32)), dim3(256), 0, st, rows_of<T>(c), (const T*)cot, (T*)dx,
-                       (T*)dmean, (T*)dA, sx, sm, sA);
+                       (T*)dmean, (T*)dA, sums.acc[0], sums.acc[1], sums.acc[2]);
     if (dA)
         hipLaunchKernelGGL((mvn_inverse_bwd_kernel<T>), dim3(grid_for((int64_t)c.S_A * c.B_A * 64)), dim3(256), 0, st, c.form, c.S, c.B, c.n,
-                           (const T*)c.F, c.S_A, c.B_A, (const T*)cot, c.scale, (T*)dA, scratch && nA ? (const double*)sA : nullptr);
-    if (scratch && nx) hipLaunchKernelGGL(mxf_fold_kernel, dim3(grid_for(nx)), dim3(256), 0, st, nx, (const double*)sx, (float*)dx);
-    if (scratch && nm) hipLaunchKernelGGL(mxf_fold_kernel, dim3(grid_for(nm)), dim3(256), 0, st, nm, (const double*)sm, (float*)dmean);
+                           (const T*)c.F, c.S_A, c.B_A, (const T*)cot, c.scale, (T*)dA, sizeof(T) == 4 ? (const double*)sums.acc[2] : nullptr);
+    shared_sums_close(sums, st);
     return 0;
 }
 

@@ -4,8 +4,8 @@
 //   workgroup of 256 threads 256 / W.  Lanes stride over K with step W; every reduction over K is a butterfly of shuffles inside the group
 //   (no LDS, no barrier).  Every lane of a wavefront reaches every shuffle: a group without a row, and a lane without an element, loads
 //   and stores nothing and contributes the neutral element.
-//   Reverse mode: a gradient whose operand is shared over the batch axis is summed with atomics into a DOUBLE accumulator (the caller's
-//   buffer for double, zeroed handle scratch that mxf_fold_kernel adds for float32), as in mvn.hip.  Where a wanted gradient is shared
+//   Reverse mode: a gradient whose operand is shared over the batch axis is summed with atomics into a DOUBLE accumulator
+//   (shared_grad.h), as in mvn.hip.  Where a wanted gradient is shared
 //   over the samples only, a group owns the batch entry b and loops over s itself: the sum over s is a plain += of elements that this
 //   lane alone touches.
 // All four calls are launch-bound at the size of a prior and bandwidth-bound at the size of a classification likelihood (the passes over
@@ -14,7 +14,7 @@
 // Replaces: Categorical.log_pdf_impl (components/distributions/categorical.py:83-106: log_softmax, pick / broadcast_mul + sum),
 // Dirichlet.log_pdf_impl (dirichlet.py:43-65: norm, broadcast_power, prod, gamma) and MXNet autograd through them.
 #include "common.h"
-#include "fold.h"
+#include "shared_grad.h"
 #include "special.h"
 
 namespace {
@@ -60,11 +60,6 @@ struct SimplexItem {
         ns = a.by_batch ? a.S : 1;
     }
 };
-
-// the dense index of element 0 of row (s, b) in a gradient buffer (S|1, B|1, K) whose operand has the strides (ss, sb)
-__device__ __forceinline__ int64_t simplex_dense(int64_t s, int64_t b, int64_t ss, int64_t sb, int64_t B, int K) {
-    return ((ss ? s : 0) * (sb ? B : 1) + (sb ? b : 0)) * K;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Categorical.  The row's log-probabilities are lp_k = (logp_k - m) - log sum_j exp(logp_j - m) with m the row maximum (normalize), or
@@ -127,7 +122,7 @@ __global__ __launch_bounds__(256) void categorical_logpdf_bwd_kernel(SimplexArgs
     constexpr int G = 256 / W;
     const int l = threadIdx.x % W, g = threadIdx.x / W;
     const int64_t items = a.by_batch ? a.B : (int64_t)a.S * a.B;
-    const bool p_atomic = a.sb_p == 0 && a.B > 1;
+    const bool p_atomic = shared_over(true, a.sb_p, a.S, a.B);          // (the sum over s alone is by_batch's loop)
     for (int64_t base = (int64_t)blockIdx.x * G; base < items; base += (int64_t)gridDim.x * G) {
         const SimplexItem it(a, base + g, items);
         for (int64_t s = it.s0; s < it.s0 + it.ns; ++s) {
@@ -140,7 +135,7 @@ __global__ __launch_bounds__(256) void categorical_logpdf_bwd_kernel(SimplexArgs
             }
             if (!it.live) continue;
             const T w = a.scale * cot[s * a.B + it.b];
-            const int64_t gp = simplex_dense(s, it.b, a.ss_p, a.sb_p, a.B, a.K), gx = simplex_dense(s, it.b, a.ss_x, 1, a.B, a.K);
+            const int64_t gp = shared_row(a.ss_p, a.sb_p, s, it.b, a.B, a.K), gx = shared_row(a.ss_x, true, s, it.b, a.B, a.K);
             for (int k = l; k < a.K; k += W) {
                 if (dlp) {
                     const T t = a.one_hot ? row.x[k] : (k == row.idx ? (T)1 : (T)0);
@@ -222,14 +217,14 @@ __global__ __launch_bounds__(256) void dirichlet_logpdf_bwd_kernel(SimplexArgs<T
     constexpr int G = 256 / W;
     const int l = threadIdx.x % W, g = threadIdx.x / W;
     const int64_t items = a.by_batch ? a.B : (int64_t)a.S * a.B;
-    const bool p_atomic = a.sb_p == 0 && a.B > 1;
+    const bool p_atomic = shared_over(true, a.sb_p, a.S, a.B);          // (the sum over s alone is by_batch's loop)
     for (int64_t base = (int64_t)blockIdx.x * G; base < items; base += (int64_t)gridDim.x * G) {
         const SimplexItem it(a, base + g, items);
         for (int64_t s = it.s0; s < it.s0 + it.ns; ++s) {
             const DirRow<T, W> row(a, s, it.b, it.live, l);
             if (!it.live) continue;
             const T w = row.bad ? (T)NAN : a.scale * cot[s * a.B + it.b];
-            const int64_t gp = simplex_dense(s, it.b, a.ss_p, a.sb_p, a.B, a.K), gx = simplex_dense(s, it.b, a.ss_x, 1, a.B, a.K);
+            const int64_t gp = shared_row(a.ss_p, a.sb_p, s, it.b, a.B, a.K), gx = shared_row(a.ss_x, true, s, it.b, a.B, a.K);
             const double pull = a.normalize ? (row.sumA - (double)a.K) / (double)row.n1 : 0.0;     // both terms of dx in double: they cancel (K = 1: exactly)
             double psiS = 0.0;
             for (int k = l - W; k < a.K; k += W) {         // the first trip (k < 0) is psi(sum alpha): one copy of the digamma code for both
@@ -296,24 +291,19 @@ void launch_fwd(const SimplexCall& c, bool dirichlet, void* out, hipStream_t st)
     else SIMPLEX_LAUNCH(categorical_logpdf_kernel, T, c.K, rows, st, a, (T*)out);
 }
 
-// dp, dx: the gradient buffers of the parameter and of x (either may be null).  The parameter's gradient is summed in double where it is
-// shared over the batch axis: in place for double, in zeroed scratch of the handle that mxf_fold_kernel adds for float32.
+// dp, dx: the gradient buffers of the parameter and of x (either may be null).  The parameter's gradient is summed in double
+// (shared_grad.h) where it is shared over the batch axis.
 template <typename T>
 int launch_bwd(mxf_handle h, const SimplexCall& c, bool dirichlet, const void* cot, void* dp, void* dx, hipStream_t st) {
-    const bool p_atomic = dp && c.sb_p == 0 && c.B > 1;
+    const bool p_atomic = dp && shared_over(true, c.sb_p, c.S, c.B);
     const bool by_batch = (dp && !p_atomic && c.ss_p == 0 && c.S > 1) || (dx && c.ss_x == 0 && c.S > 1);
-    const int64_t items = by_batch ? c.B : (int64_t)c.S * c.B, np = p_atomic ? (c.ss_p ? c.S : 1) * (int64_t)c.K : 0;
-    double* sp = (double*)dp;
-    const bool scratch = sizeof(T) == 4 && np > 0;
-    if (scratch) {
-        sp = (double*)mxf_ws(h, (size_t)np * sizeof(double));
-        if (!sp) MXF_FAIL(h, -4, "%s: out of memory for %lld scratch doubles", c.name, (long long)np);
-        MXF_HIP(h, hipMemsetAsync(sp, 0, (size_t)np * sizeof(double), st));
-    }
+    const int64_t items = by_batch ? c.B : (int64_t)c.S * c.B;
+    SharedSums sums;
+    if (int rc = shared_sums_open<T>(h, c.name, {{dp, p_atomic ? shared_numel(c.ss_p, false, c.S, c.B, c.K) : 0}}, st, &sums)) return rc;
     const SimplexArgs<T> a = args_of<T>(c, by_batch);
-    if (dirichlet) SIMPLEX_LAUNCH(dirichlet_logpdf_bwd_kernel, T, c.K, items, st, a, (const T*)cot, (T*)dx, (T*)dp, sp);
-    else SIMPLEX_LAUNCH(categorical_logpdf_bwd_kernel, T, c.K, items, st, a, (const T*)cot, (T*)dp, (T*)dx, sp);
-    if (scratch) hipLaunchKernelGGL(mxf_fold_kernel, dim3(grid_for(np)), dim3(256), 0, st, np, (const double*)sp, (float*)dp);
+    if (dirichlet) SIMPLEX_LAUNCH(dirichlet_logpdf_bwd_kernel, T, c.K, items, st, a, (const T*)cot, (T*)dx, (T*)dp, sums.acc[0]);
+    else SIMPLEX_LAUNCH(categorical_logpdf_bwd_kernel, T, c.K, items, st, a, (const T*)cot, (T*)dp, (T*)dx, sums.acc[0]);
+    shared_sums_close(sums, st);
     return 0;
 }
 

@@ -11,7 +11,7 @@
 // Replaces: Wishart.log_pdf_impl (components/distributions/wishart.py:62-96) over the per-element loops of util/special.py:21-132
 // (log_determinant, solve, trace, log_multivariate_gamma) and MXNet autograd through them.
 #include "common.h"
-#include "fold.h"
+#include "shared_grad.h"
 #include "smallmat.h"
 #include "special.h"
 
@@ -86,8 +86,8 @@ __global__ __launch_bounds__(64) void wishart_logpdf_kernel(WishRows<T> a, T* __
     }
 }
 
-// A gradient whose operand is broadcast over an axis is summed over it with atomics into a DOUBLE accumulator (the gradient itself for
-// double, scratch that mxf_fold_kernel (fold.h) adds for float32); the others are read-modify-writes of elements this wavefront alone owns.
+// A gradient whose operand is broadcast over an axis is summed over it with atomics into a DOUBLE accumulator (shared_grad.h); the others
+// are read-modify-writes of elements this wavefront alone owns.
 template <typename T>
 __device__ __forceinline__ void wish_add(bool shared, T* dst, double* sum, int64_t e, double v) {
     if (shared) atomic_add(sum + e, v); else dst[e] += (T)v;
@@ -106,17 +106,15 @@ __global__ __launch_bounds__(64) void wishart_logpdf_bwd_kernel(WishRows<T> a, c
     double *tx = tiles, *tv = tiles + WISH_TILE, *ix = tiles + 2 * WISH_TILE, *iv = tiles + 3 * WISH_TILE;
     const int lane = threadIdx.x, half = lane >> 5, c = lane & 31, n = a.n;
     const int64_t rows = (int64_t)a.S * a.B;
-    const bool X_shared = a.ss_X == 0 && a.S > 1;
-    const bool d_shared = (a.ss_d == 0 && a.S > 1) || (a.sb_d == 0 && a.B > 1);
-    const bool V_shared = (a.S_V == 1 && a.S > 1) || (a.B_V == 1 && a.B > 1);
+    const bool X_shared = shared_over(a.ss_X, true, a.S, a.B), d_shared = shared_over(a.ss_d, a.sb_d, a.S, a.B);
+    const bool V_shared = shared_over(a.S_V != 1, a.B_V != 1, a.S, a.B);
     for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
         const WishRow r = wish_factor(a, row, tx, tv, lane);
         const double w = r.fail ? (double)NAN : a.scale * (double)cot[row];
         if (ddof) {
             const double psi = wave_sum(lane < n ? mxf_digamma<double>(0.5 * (r.nu - lane)) : 0.0);     // mxf_mvdigamma's sum, a term per lane
             if (lane == 0) {
-                const int64_t e = (a.ss_d ? r.s : 0) * (a.sb_d ? a.B : 1) + (a.sb_d ? r.b : 0);        // ddof is dense (S|1, B|1)
-                wish_add(d_shared, ddof, sd, e, w * (r.ldX - 0.5 * n * WISH_LOG_2 - r.ldV - 0.5 * psi));
+                wish_add(d_shared, ddof, sd, shared_row(a.ss_d, a.sb_d, r.s, r.b, a.B, 1), w * (r.ldX - 0.5 * n * WISH_LOG_2 - r.ldV - 0.5 * psi));
             }
         }
         if (dX || dV) {
@@ -132,8 +130,7 @@ __global__ __launch_bounds__(64) void wishart_logpdf_bwd_kernel(WishRows<T> a, c
             }
             __syncthreads();
             if (c < n) {
-                const int64_t gX = ((a.ss_X ? r.s : 0) * a.B + r.b) * n * n;
-                const int64_t gV = ((a.S_V == 1 ? 0 : r.s) * a.B_V + (a.B_V == 1 ? 0 : r.b)) * n * n;
+                const int64_t gX = shared_row(a.ss_X, true, r.s, r.b, a.B, n * n), gV = shared_row(a.S_V != 1, a.B_V != 1, r.s, r.b, a.B, n * n);
                 for (int j = half; j < n; j += 2) {
                     double vinv = 0.0, xinv = 0.0, sand = 0.0;
                     for (int k = j > c ? j : c; k < n; ++k) vinv += iv[k * MVN_LD + j] * iv[k * MVN_LD + c];
@@ -186,29 +183,21 @@ unsigned grid_of(const WishCall& c) {
     return (unsigned)(rows < 4096 ? rows : 4096);
 }
 
-// The gradients of operands shared over an axis are summed in double: in place for double; for float32 in zeroed scratch of the handle
-// ([dX | ddof | dV], only what is shared and wanted) that mxf_fold_kernel adds to the caller's buffers.
+// dX, ddof and dV where their operand is shared over an axis are summed in double (shared_grad.h)
 template <typename T>
 int launch_bwd(mxf_handle h, const WishCall& c, const void* cot, void* dX, void* ddof, void* dV, hipStream_t st) {
-    const int64_t n = c.n;
-    const bool X_sh = dX && c.ss_X == 0 && c.S > 1, d_sh = ddof && ((c.ss_d == 0 && c.S > 1) || (c.sb_d == 0 && c.B > 1));
-    const bool V_sh = dV && ((c.S_V == 1 && c.S > 1) || (c.B_V == 1 && c.B > 1));
-    const int64_t nX = X_sh ? c.B * n * n : 0, nd = d_sh ? (c.ss_d ? c.S : 1) * (c.sb_d ? c.B : 1) : 0, nV = V_sh ? c.S_V * c.B_V * n * n : 0;
-    double *sX = (double*)dX, *sd = (double*)ddof, *sV = (double*)dV;
-    const bool scratch = sizeof(T) == 4 && nX + nd + nV > 0;
-    if (scratch) {
-        double* ws = (double*)mxf_ws(h, (size_t)(nX + nd + nV) * sizeof(double));
-        if (!ws) MXF_FAIL(h, -4, "mxf_wishart_logpdf_bwd: out of memory for %lld scratch doubles", (long long)(nX + nd + nV));
-        MXF_HIP(h, hipMemsetAsync(ws, 0, (size_t)(nX + nd + nV) * sizeof(double), st));
-        sX = ws; sd = ws + nX; sV = ws + nX + nd;
-    }
+    const int64_t nn = (int64_t)c.n * c.n;
+    const bool own_sV = c.S_V != 1, own_bV = c.B_V != 1;
+    SharedSums sums;
+    if (int rc = shared_sums_open<T>(h, "mxf_wishart_logpdf_bwd",
+                                     {{dX, shared_over(c.ss_X, true, c.S, c.B) ? shared_numel(c.ss_X, true, c.S, c.B, nn) : 0},
+                                      {ddof, shared_over(c.ss_d, c.sb_d, c.S, c.B) ? shared_numel(c.ss_d, c.sb_d, c.S, c.B, 1) : 0},
+                                      {dV, shared_over(own_sV, own_bV, c.S, c.B) ? shared_numel(own_sV, own_bV, c.S, c.B, nn) : 0}},
+                                     st, &sums))
+        return rc;
     hipLaunchKernelGGL((wishart_logpdf_bwd_kernel<T>), dim3(grid_of(c)), dim3(64), 0, st, rows_of<T>(c), (const T*)cot, (T*)dX, (T*)ddof,
-                       (T*)dV, sX, sd, sV);
-    const int64_t counts[3] = {nX, nd, nV};
-    const double* sums[3] = {sX, sd, sV};
-    void* dsts[3] = {dX, ddof, dV};
-    for (int i = 0; scratch && i < 3; ++i)
-        if (counts[i]) hipLaunchKernelGGL(mxf_fold_kernel, dim3(grid_for(counts[i])), dim3(256), 0, st, counts[i], sums[i], (float*)dsts[i]);
+                       (T*)dV, sums.acc[0], sums.acc[1], sums.acc[2]);
+    shared_sums_close(sums, st);
     return 0;
 }
 

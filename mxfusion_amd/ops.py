@@ -51,6 +51,46 @@ def num_samples(*ts):
     return max([t.shape[0] for t in ts if t is not None] + [1])
 
 
+def _same_kind(what, ref, *others, contiguous=False):
+    """The entry points take raw pointers: ref on a GPU and float32 or float64, every other operand (None: absent) on its device and of
+    its dtype; with `contiguous`, all of them contiguous.  `what` names the family in the message."""
+    _require_gpu(ref)
+    _dt(ref)
+    for t in (ref,) + others:
+        if t is None:
+            continue
+        if t.dtype != ref.dtype or t.device != ref.device:
+            raise TypeError('%s: every operand must have the dtype and device of the first (%s, %s); got %s, %s'
+                            % (what, ref.dtype, ref.device, t.dtype, t.device))
+        if contiguous and not t.is_contiguous():
+            raise ValueError('%s: operands must be contiguous' % what)
+
+
+def _shared_axes(t, axes, fits=torch.Tensor.is_contiguous):
+    """(t, [(extent, stride in elements) for each of `axes`]) of an operand that may be shared over those leading axes.  An axis of extent
+    1 or an expanded one (stride 0) is shared and reported as (1, 0); an expanded one is narrowed to extent 1 first, so that the copy made
+    where t does not fit the kernel's layout (`fits`; None: every layout does) never materialises a shared axis.  An operand that fits is
+    passed as it is."""
+    for d in axes:
+        if t.shape[d] > 1 and t.stride(d) == 0:
+            t = t.narrow(d, 0, 1)
+    if fits is not None and not fits(t):
+        t = t.contiguous()
+    return t, [(1, 0) if t.shape[d] == 1 else (int(t.shape[d]), int(t.stride(d))) for d in axes]
+
+
+def _check_buffers(what, *pairs):
+    """(buffer or None, shape) pairs -- the cotangent, and each gradient buffer against its operand's shape with the shared axes at extent
+    1: contiguous and of that shape"""
+    for t, shape in pairs:
+        if t is None:
+            continue
+        if not t.is_contiguous():
+            raise ValueError('%s: the cotangent and the gradient buffers must be contiguous' % what)
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError('%s: a buffer of shape %s where the operands ask for %s' % (what, tuple(t.shape), tuple(shape)))
+
+
 def gram(kind, X, X2, lengthscale, variance, ard, diag_add=None, jitter=0.0, out=None, mode=WRITE):
     """K(X, X2) with the sample axis: X (S|1,N,Q), X2 (S|1,N2,Q) or None, lengthscale (S|1,Q|1),
     variance (S|1,1), diag_add (S|1,1) -> (S,N,N2).  Kernel.K (kernels/kernel.py:96-123)."""
@@ -357,19 +397,6 @@ D_KIND = {'gamma': _lib.D_GAMMA, 'gamma_mv': _lib.D_GAMMA_MV, 'beta': _lib.D_BET
           'bernoulli': _lib.D_BERNOULLI}
 
 
-def _uni_check(x, *others):
-    """the univariate entry points take raw pointers: every operand contiguous, on x's device, of x's dtype"""
-    _require_gpu(x)
-    for t in (x,) + others:
-        if t is None:
-            continue
-        if t.dtype != x.dtype or t.device != x.device:
-            raise TypeError('univariate log-pdf: every operand must have the dtype and device of x (%s, %s); got %s, %s'
-                            % (x.dtype, x.device, t.dtype, t.device))
-        if not t.is_contiguous():
-            raise ValueError('univariate log-pdf: operands must be contiguous')
-
-
 def _uni_param(p, S, n):
     """(number of elements per sample, sample stride) of a parameter: 1 or n elements without a sample axis, or (S, n) with one"""
     if p.numel() in (1, n):
@@ -382,7 +409,7 @@ def _uni_param(p, S, n):
 def univariate_logpdf_(kind, x, a, b, scale, out_acc, dx_acc=None, da_acc=None, db_acc=None):
     """out_acc += scale * sum_{s,i} log p(x[s,i] | a[i], b[i]) for kind in D_KIND (+ reverse mode into the *_acc buffers); x (S, n...),
     a and b of 1 or n elements (mxf_univariate_logpdf)."""
-    _uni_check(x, a, b, out_acc, dx_acc, da_acc, db_acc)
+    _same_kind('univariate log-pdf', x, a, b, out_acc, dx_acc, da_acc, db_acc, contiguous=True)
     S = x.shape[0]
     n = x.numel() // S
     _lib.call('mxf_univariate_logpdf', _h(x), D_KIND[kind] if isinstance(kind, str) else kind, _dt(x), S, n, _p(x), _p(a), a.numel(),
@@ -393,7 +420,7 @@ def univariate_logpdf_(kind, x, a, b, scale, out_acc, dx_acc=None, da_acc=None, 
 def univariate_logpdf_elem(kind, x, a, b, scale=1.0):
     """scale * log p(x[s,i] | a, b), shaped like x (S, n...); a and b of 1 or n elements, or S*n (a sample axis of their own)
     (mxf_univariate_logpdf_elem)."""
-    _uni_check(x, a, b)
+    _same_kind('univariate log-pdf', x, a, b, contiguous=True)
     S = x.shape[0]
     n = x.numel() // S
     (n_a, ss_a), (n_b, ss_b) = _uni_param(a, S, n), _uni_param(b, S, n)
@@ -406,7 +433,7 @@ def univariate_logpdf_elem(kind, x, a, b, scale=1.0):
 def univariate_logpdf_bwd_(kind, x, a, b, cot, scale, dx_acc=None, da_acc=None, db_acc=None):
     """Reverse mode of univariate_logpdf_elem: dx_acc (S, n...), da_acc, db_acc (shaped like a, b) += scale * cot * d log p / d(.)
     (mxf_univariate_logpdf_bwd)."""
-    _uni_check(x, a, b, cot, dx_acc, da_acc, db_acc)
+    _same_kind('univariate log-pdf', x, a, b, cot, dx_acc, da_acc, db_acc, contiguous=True)
     S = x.shape[0]
     n = x.numel() // S
     (n_a, ss_a), (n_b, ss_b) = _uni_param(a, S, n), _uni_param(b, S, n)
@@ -417,40 +444,22 @@ def univariate_logpdf_bwd_(kind, x, a, b, cot, scale, dx_acc=None, da_acc=None, 
 MVN_MAX_ORDER = 32      # the order up to which the mxf_mvn_* entry points run (MVN_MAX of mvn.hip)
 
 
-def _mvn_check(ref, *others):
-    """the mxf_mvn_* entry points take raw pointers: every operand on ref's device and of its dtype"""
-    _require_gpu(ref)
-    for t in others:
-        if t is not None and (t.dtype != ref.dtype or t.device != ref.device):
-            raise TypeError('multivariate normal: every operand must have the dtype and device of the first (%s, %s); got %s, %s'
-                            % (ref.dtype, ref.device, t.dtype, t.device))
-
-
-def _mvn_axis(t, dim):
-    """(extent, stride in elements) of a leading axis; an axis of extent 1 or an expanded one (stride 0) is a broadcast: (1, 0)"""
-    return (1, 0) if t.shape[dim] == 1 or t.stride(dim) == 0 else (int(t.shape[dim]), int(t.stride(dim)))
-
-
 def _mvn_rows(x, mean):
     """x (S|1, B, n) and mean (S|1, B|1, n) as the entry points take them -- rows of n contiguous elements, x at batch stride n -- and their
     strides.  An operand that already has that layout, expanded axes included, is passed as it is."""
     n = x.shape[-1]
-    if x.stride(2) != 1 or (x.shape[1] > 1 and x.stride(1) != n):
-        x = x.contiguous()
-    if mean.stride(2) != 1:
-        mean = mean.contiguous()
-    return x, _mvn_axis(x, 0)[1], mean, _mvn_axis(mean, 0)[1], _mvn_axis(mean, 1)[1]
+    x, ((_, ss_x),) = _shared_axes(x, (0,), lambda t: t.stride(2) == 1 and (t.shape[1] == 1 or t.stride(1) == n))
+    mean, ((_, ss_m), (_, sb_m)) = _shared_axes(mean, (0, 1), lambda t: t.stride(2) == 1)
+    return x, ss_x, mean, ss_m, sb_m
 
 
 def mvn_factor(A, form=0):
     """(F, logdet, info) of A (S|1, B|1, n, n), n <= 32 (mxf_mvn_factor): per distinct matrix -- an expanded axis counts as 1 -- the lower
     factor F (S_A, B_A, n, n) of the covariance inverted (form 0) or of the precision itself (form 1), logdet (S_A, B_A) = sum log L_ii and
     the int32 info word (0, or the 1-based index of the first pivot that is not positive)."""
-    _mvn_check(A)
-    if A.stride(-1) != 1:
-        A = A.contiguous()
+    _same_kind('multivariate normal', A)
     n = A.shape[-1]
-    (S_A, ss), (B_A, sb) = _mvn_axis(A, 0), _mvn_axis(A, 1)
+    A, ((S_A, ss), (B_A, sb)) = _shared_axes(A, (0, 1), lambda t: t.stride(-1) == 1)
     F = torch.empty((S_A, B_A, n, n), dtype=A.dtype, device=A.device)
     logdet = torch.empty((S_A, B_A), dtype=A.dtype, device=A.device)
     info = torch.zeros((S_A, B_A), dtype=torch.int32, device=A.device)
@@ -460,7 +469,7 @@ def mvn_factor(A, form=0):
 
 def mvn_logpdf(x, mean, F, logdet, form=0, scale=1.0):
     """scale * log N(x[s,b] | mean, A) (S, B) from mvn_factor's F and logdet; x (S|1, B, n), mean (S|1, B|1, n) (mxf_mvn_logpdf)."""
-    _mvn_check(x, mean, F, logdet)
+    _same_kind('multivariate normal', x, mean, F, logdet)
     S, B, n = max(x.shape[0], mean.shape[0], F.shape[0]), x.shape[1], x.shape[2]
     x, ss_x, mean, ss_m, sb_m = _mvn_rows(x, mean)
     out = torch.empty((S, B), dtype=x.dtype, device=x.device)
@@ -472,12 +481,10 @@ def mvn_logpdf(x, mean, F, logdet, form=0, scale=1.0):
 def mvn_logpdf_bwd_(x, mean, F, cot, form=0, scale=1.0, dx_acc=None, dmean_acc=None, dA_acc=None):
     """Reverse mode of mvn_logpdf: dx_acc (S|1, B, n), dmean_acc (S|1, B|1, n), dA_acc (S_A, B_A, n, n) -- dense, shaped like their operands
     with the shared axes at extent 1 -- += the gradients under the cotangent cot (S, B) (mxf_mvn_logpdf_bwd)."""
-    _mvn_check(x, mean, F, cot, dx_acc, dmean_acc, dA_acc)
-    for t in (cot, dx_acc, dmean_acc, dA_acc):
-        if t is not None and not t.is_contiguous():
-            raise ValueError('multivariate normal: the cotangent and the gradient buffers must be contiguous')
+    _same_kind('multivariate normal', x, mean, F, cot, dx_acc, dmean_acc, dA_acc)
     S, B, n = cot.shape[0], x.shape[1], x.shape[2]
     x, ss_x, mean, ss_m, sb_m = _mvn_rows(x, mean)
+    _check_buffers('multivariate normal', (cot, (S, B)), (dx_acc, x.shape), (dmean_acc, mean.shape), (dA_acc, F.shape))
     _lib.call('mxf_mvn_logpdf_bwd', _h(x), _dt(x), int(form), S, B, n, _p(x), ss_x, _p(mean), ss_m, sb_m, _p(F), F.shape[0], F.shape[1],
               _p(cot), float(scale), _p(dx_acc), _p(dmean_acc), _p(dA_acc), _stream())
 
@@ -490,24 +497,22 @@ def _wishart_operands(X, dof, V):
     if X.dim() != 4 or V.dim() != 4 or dof.dim() != 2 or X.shape[-2] != n or tuple(V.shape[-2:]) != (n, n):
         raise ValueError('Wishart: X (S|1, B, n, n), dof (S|1, B|1), V (S|1, B|1, n, n); got %s, %s, %s'
                          % (tuple(X.shape), tuple(dof.shape), tuple(V.shape)))
-    if X.stride(3) != 1 or X.stride(2) < n or (X.shape[1] > 1 and X.stride(1) != n * X.stride(2)):
-        X = X.contiguous()
-    if V.stride(3) != 1 or V.stride(2) < n:
-        V = V.contiguous()
-    (S_V, ss_V), (B_V, sb_V) = _mvn_axis(V, 0), _mvn_axis(V, 1)
-    (S_X, ss_X), (S_d, ss_d), (B_d, sb_d) = _mvn_axis(X, 0), _mvn_axis(dof, 0), _mvn_axis(dof, 1)
+    rows = lambda t: t.stride(3) == 1 and t.stride(2) >= n
+    X, ((S_X, ss_X),) = _shared_axes(X, (0,), lambda t: rows(t) and (t.shape[1] == 1 or t.stride(1) == n * t.stride(2)))
+    V, ((S_V, ss_V), (B_V, sb_V)) = _shared_axes(V, (0, 1), rows)
+    dof, ((S_d, ss_d), (B_d, sb_d)) = _shared_axes(dof, (0, 1), None)
     S, B = max(S_X, S_d, S_V), X.shape[1]
     if any(e not in (1, S) for e in (S_X, S_d, S_V)) or any(e not in (1, B) for e in (B_d, B_V)):
         raise ValueError('Wishart: operands of %s, %s, %s do not broadcast to (%d, %d) rows' % (tuple(X.shape), tuple(dof.shape), tuple(V.shape), S, B))
     args = (_p(X), X.stride(2), ss_X, _p(dof), ss_d, sb_d, _p(V), V.stride(2), ss_V, sb_V, S_V, B_V)
-    return X, V, S, B, n, args, ((S_X, B, n, n), (S_d, B_d), (S_V, B_V, n, n))
+    return (X, dof, V), S, B, n, args, ((S_X, B, n, n), (S_d, B_d), (S_V, B_V, n, n))
 
 
 def wishart_logpdf(X, dof, V, scale=1.0):
     """(scale * log W(X[s,b] | V, dof) (S, B), info (S, B) int32) for n <= 32; X (S|1, B, n, n), dof (S|1, B|1), V (S|1, B|1, n, n), an
     expanded axis counting as shared (mxf_wishart_logpdf).  info: 0, j for V's j-th pivot, n + j for X's, 2 n + 1 for dof <= n - 1."""
-    _mvn_check(X, dof, V)
-    X, V, S, B, n, args, _ = _wishart_operands(X, dof, V)
+    _same_kind('Wishart', X, dof, V)
+    (X, dof, V), S, B, n, args, _ = _wishart_operands(X, dof, V)          # bound here: `args` holds their addresses, a copy lives until the call
     out = torch.empty((S, B), dtype=X.dtype, device=X.device)
     info = torch.zeros((S, B), dtype=torch.int32, device=X.device)
     _lib.call('mxf_wishart_logpdf', _h(X), _dt(X), S, B, n, *args, float(scale), _p(out), _p(info), _stream())
@@ -517,44 +522,23 @@ def wishart_logpdf(X, dof, V, scale=1.0):
 def wishart_logpdf_bwd_(X, dof, V, cot, scale=1.0, dX_acc=None, ddof_acc=None, dV_acc=None):
     """Reverse mode of wishart_logpdf: dX_acc (S|1, B, n, n), ddof_acc (S|1, B|1), dV_acc (S_V, B_V, n, n) -- dense, shaped like their
     operands with the shared axes at extent 1 -- += the gradients under the cotangent cot (S, B) (mxf_wishart_logpdf_bwd)."""
-    _mvn_check(X, dof, V, cot, dX_acc, ddof_acc, dV_acc)
-    for t in (cot, dX_acc, ddof_acc, dV_acc):
-        if t is not None and not t.is_contiguous():
-            raise ValueError('Wishart: the cotangent and the gradient buffers must be contiguous')
-    X, V, S, B, n, args, shapes = _wishart_operands(X, dof, V)
-    for t, shape in zip((cot, dX_acc, ddof_acc, dV_acc), ((S, B),) + shapes):
-        if t is not None and tuple(t.shape) != shape:
-            raise ValueError('Wishart: a buffer of shape %s where the operands ask for %s' % (tuple(t.shape), shape))
+    _same_kind('Wishart', X, dof, V, cot, dX_acc, ddof_acc, dV_acc)
+    (X, dof, V), S, B, n, args, shapes = _wishart_operands(X, dof, V)     # bound here: `args` holds their addresses
+    _check_buffers('Wishart', *zip((cot, dX_acc, ddof_acc, dV_acc), ((S, B),) + shapes))
     _lib.call('mxf_wishart_logpdf_bwd', _h(X), _dt(X), S, B, n, *args, _p(cot), float(scale), _p(dX_acc), _p(ddof_acc), _p(dV_acc), _stream())
 
 
-def _simplex_check(what, ref, *others):
-    """the mxf_categorical_* and mxf_dirichlet_* entry points take raw pointers: every operand on ref's device and of its dtype"""
-    _require_gpu(ref)
-    _dt(ref)
-    for t in others:
-        if t is not None and (t.dtype != ref.dtype or t.device != ref.device):
-            raise TypeError('%s: every operand must have the dtype and device of the first (%s, %s); got %s, %s'
-                            % (what, ref.dtype, ref.device, t.dtype, t.device))
-
-
 def _simplex_operand(t, shared_axes):
-    """(t, strideS, strideB) of an operand (S|1, B|1, ...) as those entry points take it: dense, with the axes it is shared over -- of
-    extent 1, or expanded (stride 0), among shared_axes -- at stride 0.  An operand that already has that layout is passed as it is; a
-    copy never materialises a shared axis."""
-    for d in shared_axes:
-        if t.shape[d] > 1 and t.stride(d) == 0:
-            t = t.narrow(d, 0, 1)
-    if not t.is_contiguous():
-        t = t.contiguous()
-    S_t, B_t = int(t.shape[0]), int(t.shape[1])
-    row = t.numel() // max(S_t * B_t, 1)
-    return t, (0 if S_t == 1 else B_t * row), (0 if B_t == 1 else row)
+    """(t, strideS, strideB) of an operand (S|1, B|1, ...) as those entry points take it: dense, the axes it is shared over -- of extent 1,
+    or expanded, among shared_axes -- at stride 0 (_shared_axes: passed as it is where it has that layout, never materialised)"""
+    t, _ = _shared_axes(t, shared_axes)
+    return t, (0 if t.shape[0] == 1 else int(t.stride(0))), (0 if t.shape[1] == 1 else int(t.stride(1)))
 
 
 def _simplex_operands(what, x, p, labels, cot=None):
-    """x (S|1, B, K) (labels: (S|1, B)) and the parameter p (S|1, B|1, K) of a row-wise log-pdf, with S, B, K and the strides.  S is the
-    largest sample extent among the operands as they are given (an expanded axis counts with its extent) and the cotangent."""
+    """x (S|1, B, K) (labels: (S|1, B)) and the parameter p (S|1, B|1, K) of a row-wise log-pdf as those entry points take them -- dense,
+    the axes they are shared over at stride 0 -- with S, B, K and the strides.  S is the largest sample extent among the operands as they
+    are given (an expanded axis counts with its extent) and the cotangent."""
     if p.dim() != 3 or x.dim() != (2 if labels else 3) or (not labels and x.shape[2] != p.shape[2]):
         raise ValueError('%s: x %s and a parameter (S|1, B|1, K); got %s, %s'
                          % (what, '(S|1, B)' if labels else '(S|1, B, K)', tuple(x.shape), tuple(p.shape)))
@@ -567,22 +551,11 @@ def _simplex_operands(what, x, p, labels, cot=None):
     return x, ss_x, p, ss_p, sb_p, S, B, K
 
 
-def _simplex_buffers(what, cot, S, B, grads):
-    """the cotangent (S, B) and the gradient buffers, each against the shape of its operand: contiguous and of that shape"""
-    for t, shape in ((cot, (S, B)),) + tuple(grads):
-        if t is None:
-            continue
-        if not t.is_contiguous():
-            raise ValueError('%s: the cotangent and the gradient buffers must be contiguous' % what)
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError('%s: a buffer of shape %s where the operands ask for %s' % (what, tuple(t.shape), tuple(shape)))
-
-
 def categorical_logpdf(logp, x, one_hot=False, normalize=True, scale=1.0):
     """scale * log p(x[s,b] | logp) (S, B): logp (S|1, B|1, K), softmax-normalised along K if `normalize`; x (S|1, B) class indices held in
     logp's dtype (clipped to [0, K - 1]), or with one_hot (S|1, B, K) rows.  An axis of extent 1 or an expanded one is shared
     (mxf_categorical_logpdf)."""
-    _simplex_check('Categorical', logp, x)
+    _same_kind('Categorical', logp, x)
     x, ss_x, logp, ss_p, sb_p, S, B, K = _simplex_operands('Categorical', x, logp, not one_hot)
     out = torch.empty((S, B), dtype=logp.dtype, device=logp.device)
     _lib.call('mxf_categorical_logpdf', _h(logp), _dt(logp), S, B, K, _p(logp), ss_p, sb_p, _p(x), ss_x, int(bool(one_hot)),
@@ -593,9 +566,9 @@ def categorical_logpdf(logp, x, one_hot=False, normalize=True, scale=1.0):
 def categorical_logpdf_bwd_(logp, x, cot, one_hot=False, normalize=True, scale=1.0, dlogp_acc=None, dx_acc=None):
     """Reverse mode of categorical_logpdf: dlogp_acc (S|1, B|1, K) and, with one_hot only, dx_acc (S|1, B, K) -- dense, shaped like their
     operands with the shared axes at extent 1 -- += the gradients under the cotangent cot (S, B) (mxf_categorical_logpdf_bwd)."""
-    _simplex_check('Categorical', logp, x, cot, dlogp_acc, dx_acc)
+    _same_kind('Categorical', logp, x, cot, dlogp_acc, dx_acc)
     x, ss_x, logp, ss_p, sb_p, S, B, K = _simplex_operands('Categorical', x, logp, not one_hot, cot)
-    _simplex_buffers('Categorical', cot, S, B, ((dlogp_acc, tuple(logp.shape)), (dx_acc, tuple(x.shape))))
+    _check_buffers('Categorical', (cot, (S, B)), (dlogp_acc, logp.shape), (dx_acc, x.shape))
     _lib.call('mxf_categorical_logpdf_bwd', _h(logp), _dt(logp), S, B, K, _p(logp), ss_p, sb_p, _p(x), ss_x, int(bool(one_hot)),
               int(bool(normalize)), _p(cot), float(scale), _p(dlogp_acc), _p(dx_acc), _stream())
 
@@ -603,7 +576,7 @@ def categorical_logpdf_bwd_(logp, x, cot, one_hot=False, normalize=True, scale=1
 def dirichlet_logpdf(x, alpha, normalize=True, scale=1.0):
     """scale * log Dir(x[s,b] | alpha) (S, B): x (S|1, B, K), divided by its 1-norm along K if `normalize`; alpha (S|1, B|1, K).  An axis of
     extent 1 or an expanded one is shared.  A row with an x_k <= 0 or an alpha_k <= 0 is NaN (mxf_dirichlet_logpdf)."""
-    _simplex_check('Dirichlet', x, alpha)
+    _same_kind('Dirichlet', x, alpha)
     x, ss_x, alpha, ss_a, sb_a, S, B, K = _simplex_operands('Dirichlet', x, alpha, False)
     out = torch.empty((S, B), dtype=x.dtype, device=x.device)
     _lib.call('mxf_dirichlet_logpdf', _h(x), _dt(x), S, B, K, _p(x), ss_x, _p(alpha), ss_a, sb_a, int(bool(normalize)), float(scale),
@@ -614,9 +587,9 @@ def dirichlet_logpdf(x, alpha, normalize=True, scale=1.0):
 def dirichlet_logpdf_bwd_(x, alpha, cot, normalize=True, scale=1.0, dx_acc=None, dalpha_acc=None):
     """Reverse mode of dirichlet_logpdf: dx_acc (S|1, B, K), dalpha_acc (S|1, B|1, K) -- dense, shaped like their operands with the shared
     axes at extent 1 -- += the gradients under the cotangent cot (S, B) (mxf_dirichlet_logpdf_bwd)."""
-    _simplex_check('Dirichlet', x, alpha, cot, dx_acc, dalpha_acc)
+    _same_kind('Dirichlet', x, alpha, cot, dx_acc, dalpha_acc)
     x, ss_x, alpha, ss_a, sb_a, S, B, K = _simplex_operands('Dirichlet', x, alpha, False, cot)
-    _simplex_buffers('Dirichlet', cot, S, B, ((dx_acc, tuple(x.shape)), (dalpha_acc, tuple(alpha.shape))))
+    _check_buffers('Dirichlet', (cot, (S, B)), (dx_acc, x.shape), (dalpha_acc, alpha.shape))
     _lib.call('mxf_dirichlet_logpdf_bwd', _h(x), _dt(x), S, B, K, _p(x), ss_x, _p(alpha), ss_a, sb_a, int(bool(normalize)), _p(cot),
               float(scale), _p(dx_acc), _p(dalpha_acc), _stream())
 
@@ -634,11 +607,10 @@ def _dense_operands(X, W, b):
     if X.dim() != 3 or W.dim() != 3 or W.shape[2] != X.shape[2] or (b is not None and (b.dim() != 2 or b.shape[1] != W.shape[1])):
         raise ValueError('dense: X (S|1, N, I), W (S|1, O, I), b (S|1, O); got %s, %s, %s'
                          % (tuple(X.shape), tuple(W.shape), None if b is None else tuple(b.shape)))
-    share = lambda t: t.narrow(0, 0, 1) if t is not None and t.shape[0] > 1 and t.stride(0) == 0 else t
-    X, W, b = share(X), _c(share(W)), _c(share(b))
     N, I = int(X.shape[1]), int(X.shape[2])
-    if X.stride(2) != 1 or (N > 1 and X.stride(1) < I) or (X.shape[0] > 1 and X.stride(0) < (N - 1) * X.stride(1) + I):
-        X = X.contiguous()
+    X = _shared_axes(X, (0,), lambda t: t.stride(2) == 1 and (N == 1 or t.stride(1) >= I)
+                     and (t.shape[0] == 1 or t.stride(0) >= (N - 1) * t.stride(1) + I))[0]
+    W, b = _shared_axes(W, (0,))[0], None if b is None else _shared_axes(b, (0,))[0]
     S = num_samples(X, W, b)
     if any(t is not None and t.shape[0] not in (1, S) for t in (X, W, b)):
         raise ValueError('dense: sample extents %s do not broadcast' % [t.shape[0] for t in (X, W, b) if t is not None])
@@ -658,7 +630,7 @@ def dense(X, W, b=None, act=None):
     """Y[s] = act(X[s] W[s]^T + b[s]) (S, N, O) for all samples in one launch (mxf_dense_fwd): X (S|1, N, I), W (S|1, O, I) in the layout of
     torch.nn.Linear.weight, b (S|1, O) or None, act None / 'identity', 'tanh', 'relu', 'sigmoid'.  Widths beyond the kernel's (128) go
     through gemm and elementwise torch."""
-    _simplex_check('dense', X, W, b)
+    _same_kind('dense', X, W, b)
     act = _dense_act(act)
     X, W, b, S, N, I, O, ldx = _dense_operands(X, W, b)
     if not _dense_fits(I, O):
@@ -674,16 +646,12 @@ def dense(X, W, b=None, act=None):
 def dense_bwd_(X, W, Y, dY, act=None, dX_acc=None, dW_acc=None, db_acc=None):
     """Reverse mode of dense from its result Y and the cotangent dY (S, N, O): dX_acc (S|1, N, I), dW_acc (S|1, O, I), db_acc (S|1, O) --
     dense, shaped like their operands with a shared sample axis at extent 1 -- += the gradients (mxf_dense_bwd)."""
-    _simplex_check('dense', X, W, Y, dY, dX_acc, dW_acc, db_acc)
+    _same_kind('dense', X, W, Y, dY, dX_acc, dW_acc, db_acc)
     act = _dense_act(act)
     X, W, _, S, N, I, O, ldx = _dense_operands(X, W, None)
     S = max(S, int(Y.shape[0]))
-    _simplex_buffers('dense', None, S, N, ((dX_acc, (X.shape[0], N, I)), (dW_acc, tuple(W.shape))))
-    if tuple(Y.shape) != (S, N, O) or tuple(dY.shape) != (S, N, O) or not Y.is_contiguous() or not dY.is_contiguous():
-        raise ValueError('dense: Y and dY must be contiguous (S, N, O) = %s; got %s, %s' % ((S, N, O), tuple(Y.shape), tuple(dY.shape)))
-    if db_acc is not None and (not db_acc.is_contiguous() or tuple(db_acc.shape) not in ((1, O), (S, O))):
-        raise ValueError('dense: db_acc must be contiguous (S|1, O); got %s' % (tuple(db_acc.shape),))
-    ss_b = 0 if db_acc is None or db_acc.shape[0] == 1 else O
+    ss_b = 0 if db_acc is None or db_acc.shape[0] == 1 else O          # b itself is not passed: db_acc says whether it is shared
+    _check_buffers('dense', (Y, (S, N, O)), (dY, (S, N, O)), (dX_acc, (X.shape[0], N, I)), (dW_acc, W.shape), (db_acc, (S if ss_b else 1, O)))
     if not _dense_fits(I, O):
         d = _dense_dact(act, Y)
         G = dY if d is None else dY * d

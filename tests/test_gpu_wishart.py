@@ -278,6 +278,32 @@ def test_direct_call_accumulates_and_skips_a_missing_buffer():
         assert nerr(_sym(got) if got.ndim == 4 else got, w) <= F64_BAR
 
 
+def test_operands_that_do_not_fit_the_layout_are_copied_and_the_copies_outlive_the_launch():
+    """X and V as views whose last stride is 2: the wrappers copy them, and the copies have to stay alive until the kernel has read them
+    (the output and info buffers are allocated after the copies): bit for bit the results of the contiguous operands"""
+    from mxfusion_amd import ops
+    (X, nu, V, cot), _, _ = case('float64', 5, 3, 5, 'nu_per_row')          # nothing is shared: no sum in arrival order
+    Xd, nud, Vd, cotd = _dev(X, 'float64'), _dev(nu, 'float64'), _dev(V, 'float64'), _dev(cot, 'float64')
+
+    def wide(t):
+        buf = torch.full(tuple(t.shape[:-1]) + (2 * t.shape[-1],), float('nan'), dtype=t.dtype, device=t.device)
+        buf[..., ::2] = t
+        return buf[..., ::2]
+    Xw, Vw = wide(Xd), wide(Vd)
+    assert Xw.stride(-1) == 2 and Vw.stride(-1) == 2
+    want, want_info = ops.wishart_logpdf(Xd, nud, Vd)
+    grads = [torch.zeros_like(t) for t in (Xd, nud, Vd)]
+    ops.wishart_logpdf_bwd_(Xd, nud, Vd, cotd, 1.0, *grads)
+    for _ in range(3):                                   # (the allocator hands a freed block to the next request of its size)
+        got, info = ops.wishart_logpdf(Xw, nud, Vw)
+        g2 = [torch.zeros_like(t) for t in (Xd, nud, Vd)]
+        ops.wishart_logpdf_bwd_(Xw, nud, Vw, cotd, 1.0, *g2)
+        torch.cuda.synchronize()
+        assert torch.equal(got, want) and torch.equal(info, want_info) and int(info.abs().max()) == 0
+        for a, b in zip(g2, grads):
+            assert torch.equal(a, b)
+
+
 # ---- draws -------------------------------------------------------------------------------------------------------------------------------
 
 def _bartlett(V, buf, S, lead, n, dt):

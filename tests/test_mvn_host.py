@@ -81,7 +81,7 @@ def test_replicate_self():
 
 def test_leading_dimensions_flatten_into_one_batch_axis():
     """the operand shapes the kernels are given: (S|1, B|1, ...), an expanded leading axis back at extent 1"""
-    from mxfusion_amd.components.distributions.mvn import _flatten
+    from mxfusion_amd.components.distributions._fused import _flatten
     x = torch.zeros(2, 5, 7, 3)
     assert tuple(_flatten(x, (5, 7), (3,), full=True).shape) == (2, 35, 3)
     assert tuple(_flatten(torch.zeros(1, 1), (5, 7), (3,)).shape) == (1, 1, 3)                                   # a scalar mean
