@@ -139,7 +139,10 @@ __global__ __launch_bounds__(256) void gram_bwd_kernel(GramBwdArgs<T> a) {
             for (int i = tid; i < TRB * QT; i += 256) {
                 const int r = i / QT, q = i % QT;
                 const int64_t row = rt + r;
-                xs[i] = (row < rend && q < Q) ? (X[row * Q + q] - (KIND != MXF_K_LINEAR ? X[q] : (T)0)) / ls[a.ard ? q : 0] : (T)0;
+                // times the rounded reciprocal, exactly as z above (il): a row and a column at the SAME point then give d = 0 exactly.  Dividing
+                // here left d = +-1 ulp of x / l between coincident points -- in float32 outside the Matern clip (r2 ~ 1e-13 > 1e-14), where the
+                // Matern12 slope -k / 2r turns it into a spurious unit-size term g k var d / r on dX / dX2 (Z = X[:M], duplicated rows)
+                xs[i] = (row < rend && q < Q) ? (X[row * Q + q] - (KIND != MXF_K_LINEAR ? X[q] : (T)0)) * ((T)1 / ls[a.ard ? q : 0]) : (T)0;
             }
             if (FUSED) {
                 for (int i = tid; i < TRB * PMAX; i += 256) {

@@ -210,12 +210,19 @@ def gram2(kind1, kind2, op, X, X2, ls1, var1, ard1, ls2, var2, ard2, K, diag_add
              _p(K), ld(K), K.stride(0), st)
 
 
-def gram_bwd(kind, X, X2, ls, var, ard, dK):
-    """mxf_gram_bwd from a view dK (S, N, N2); returns freshly zeroed (dX, dX2, dls, dvar), contiguous"""
+def gram_bwd(kind, X, X2, ls, var, ard, dK, out=None):
+    """mxf_gram_bwd from a view dK (S, N, N2); returns freshly zeroed (dX, dX2, dls, dvar), contiguous.
+    out: the caller's own output buffers (dX, dX2, dls, dvar), contiguous and shaped like the primals, passed as they are -- the call
+    ACCUMULATES into them, and None is a null pointer (that gradient is not computed)"""
     lib, h, dt, st = _ctx(dK)
     S, N, N2 = dK.shape
     z = lambda t: None if t is None else torch.zeros(tuple(t.shape), dtype=t.dtype, device=t.device)
-    dX, dX2, dls, dvar = z(X), z(X2), z(ls), z(var)
+    if out is None:
+        dX, dX2, dls, dvar = z(X), z(X2), z(ls), z(var)
+    else:
+        dX, dX2, dls, dvar = out
+        for o, p in zip(out, (X, X2, ls, var)):
+            assert o is None or (p is not None and o.is_contiguous() and o.shape == p.shape and o.dtype == p.dtype), 'gram_bwd: output buffer'
     # contiguous outputs: their sample strides are implied by the shapes, as for the inputs
     assert X.is_contiguous() and (X2 is None or X2.is_contiguous()), 'gram_bwd writes dX / dX2 with the strides of X / X2'
     lib.call('mxf_gram_bwd', h, kind, dt, S, N, N2, X.shape[-1], _p(X), _xs(X), _p(X2), _xs(X2), _p(ls), int(bool(ard)), _xs(ls), _p(var), _xs(var),

@@ -396,7 +396,7 @@ def test_gram2_layouts(dtype, tol, k1, k2, N, N2, Q, layout):
 @pytest.mark.parametrize('kind', list(KINDS))
 @pytest.mark.parametrize('dtype,tol', [(F64, 1e-9), (F32, 2e-4)])
 def test_gram_bwd_layouts(dtype, tol, kind, N, N2, Q, S, ard, variant):
-    """Tolerance of test_gram_bwd_vs_autograd: rtol = tol, atol = tol max(1, max |ref|) (Matern12 with Q = 1: 1e-6, as there)."""
+    """Tolerance of test_gram_bwd_vs_autograd: rtol = tol, atol = tol max(1, max |ref|)."""
     rng = np.random.RandomState(N + Q)
     r = (lambda a: a.astype(np.float32).astype(np.float64)) if dtype == F32 else (lambda a: a)
     X = r(rng.uniform(-2, 2, (S, N, Q)))
@@ -407,13 +407,16 @@ def test_gram_bwd_layouts(dtype, tol, kind, N, N2, Q, S, ard, variant):
     tX, tls, tvar = [O.T(a).clone().requires_grad_(True) for a in (X, ls, var)]
     tX2 = None if X2 is None else O.T(X2).clone().requires_grad_(True)
     (k.K(tX, tX2, **{k.name + '_lengthscale': tls, k.name + '_variance': tvar}) * O.T(dK)).sum().backward()
-    if kind == 'matern12' and Q == 1:
-        tol = max(tol, 1e-6)
+    refs = (tX.grad, None if tX2 is None else tX2.grad, tls.grad, tvar.grad)
+    if kind == 'matern12' and Q == 1:      # refereed by the difference-form closed form, as in test_gram_bwd_vs_autograd
+        import _gram_ref
+        g, _ = _gram_ref.gram_bwd_ref(kind, X, X2, ls, var, dK, dtype=_gram_ref.HI)
+        refs = [None if g[n] is None else torch.as_tensor(g[n].astype(np.float64)) for n in ('dX', 'dX2', 'dls', 'dvar')]
     ddK = st.carve_as(dK, variant, NAN, dtype=dtype)
     sdK = st.snapshot(ddK)
     out = st.gram_bwd(KINDS[kind][0], _flat(X, dtype), None if X2 is None else _flat(X2, dtype), _flat(ls, dtype), _flat(var, dtype), ard, ddK)
     st.assert_unchanged(ddK, sdK, 'dK')
-    for got, ref, name in zip(out, (tX.grad, None if tX2 is None else tX2.grad, tls.grad, tvar.grad), ('dX', 'dX2', 'dls', 'dvar')):
+    for got, ref, name in zip(out, refs, ('dX', 'dX2', 'dls', 'dvar')):
         if ref is None:
             assert got is None
             continue

@@ -66,6 +66,11 @@ def test_duplicated_points_zero_distance(kind):
     (k.K(tX, **{k.name + '_lengthscale': tls, k.name + '_variance': tvar}) * O.T(dK)).sum().backward()
     assert np.allclose(dvar.cpu().numpy(), tvar.grad.numpy(), rtol=1e-9, atol=1e-9)
     assert np.allclose(dls.cpu().numpy(), tls.grad.numpy(), rtol=1e-7, atol=1e-7)
+    # dX against the difference-form closed form with the clip conventions (tests/_gram_ref.py), per element, at the bar of
+    # tests/test_gpu_gram_bwd_axes.py (the oracle's expansion-form distances are noise between coincident points)
+    import _gram_ref
+    g, sc = _gram_ref.gram_bwd_ref(kind, X, None, ls, var, dK, dtype=_gram_ref.HI)
+    assert _gram_ref.worst_ratio(dX.cpu().numpy(), g['dX'], sc['dX'], 2.0 ** -53) <= _gram_ref.BAR_C['f64']
 
 
 def test_wide_inputs_beyond_the_tiled_kernels():
