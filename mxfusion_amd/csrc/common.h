@@ -78,7 +78,7 @@ struct mxf_ctx {
     // Scratch, never allocated inside a graph capture; mxf_each_buf lists them for mxf_workspace_bytes and mxf_destroy.
     mxf_buf ws;                // general scratch (mxf_ws)
     mxf_buf gram_ws;           // pre-scaled coordinates of mxf_gram (separate: composites hold `ws` while calling mxf_gram)
-    mxf_buf bwd_acc;           // MFMA reverse pass (gram_bwd.hip): float64 row-side sums [M][16] + 16, scaled coordinates
+    mxf_buf bwd_acc;           // MFMA reverse pass (svgp_bwd_mfma.hip; layout: gram_bwd_plan.h): float64 row-side sums [M][16] + 16, scaled coordinates
     mxf_buf pinv;              // ring of 16 x 16 diagonal-block inverses handed from the factoring to the solving workgroups of potrf_tiles_kernel
     size_t pinv_cursor = 0;    // (in doubles)
     int64_t ws_generation = 0; // bumped whenever one of the buffers above is (re-)allocated: device pointers baked into a captured hipGraph are stale after that
@@ -329,6 +329,9 @@ __device__ __forceinline__ T block_sum(T v, T* smem /* >= 16 */) {
 
 __device__ __forceinline__ void atomic_add(float* p, float v) { unsafeAtomicAdd(p, v); }
 __device__ __forceinline__ void atomic_add(double* p, double v) { unsafeAtomicAdd(p, v); }
+// the same into LDS (workgroup scope)
+__device__ __forceinline__ void lds_add(float* p, float v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+__device__ __forceinline__ void lds_add(double* p, double v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
 // kernels that end in ONE same-address atomic per workgroup (the scalar sums of normal_logpdf_kernel and univariate_logpdf_kernel): 2048 of them serialise at the L2
 // (~15 ns apiece: 33 us for the 2 M-element log-pdf of a 4-sample step, of which the data take 6) -- two workgroups per CU

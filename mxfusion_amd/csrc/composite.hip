@@ -392,10 +392,10 @@ int gp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t N, int Q, in
     // outputs are per sample (S, ...) even when the primal is broadcast: use per-sample strides for the outputs
     // by running one sample at a time when the primal stride is 0
     for (int s = 0; s < S; ++s) {
-        rc = mxf_gram_bwd_internal(h, kind, dtype, 1, N, N, Q, X + (int64_t)s * sX, 0, nullptr, 0, ls + (int64_t)s * sls, ard, 0,
-                                   var + (int64_t)s * svar, 0, dK + (int64_t)s * NN, N, NN,
-                                   dX ? dX + (int64_t)s * N * Q : nullptr, nullptr, dls ? dls + (int64_t)s * lsn : nullptr,
-                                   dvar ? dvar + s : nullptr, st, 1 /* dK was symmetrised above */);
+        rc = mxf_gram_bwd_internal(h, st, {.kind = kind, .dtype = dtype, .N = N, .Q = Q, .X = X + (int64_t)s * sX, .ls = ls + (int64_t)s * sls, .ard = ard,
+                                           .var = var + (int64_t)s * svar, .dK = dK + (int64_t)s * NN, .lddk = N, .sdK = NN,
+                                           .dX = dX ? dX + (int64_t)s * N * Q : nullptr, .dls = dls ? dls + (int64_t)s * lsn : nullptr,
+                                           .dvar = dvar ? dvar + s : nullptr, .dk_symmetric = true /* dK was symmetrised above */});
         if (rc) return rc;
     }
     MXF_LAUNCH_CHECK(h);
@@ -1585,7 +1585,8 @@ struct SvgpCall : SvgpPlan {
             if (use_mat) {
                 if (mat.dKuf) MXF_HIP(h, hipMemcpyAsync(mat.dKuf, Text, sizeof(T) * (size_t)M * SB, hipMemcpyDeviceToDevice, st));
             } else {
-                rc = mxf_gram_bwd_internal(h, kind, dtype, 1, M, SB, Q, Z, 0, X, 0, ls, ard, 0, var, 0, Text, SB, 0, dZ, dX, dls, dvar, st);
+                rc = mxf_gram_bwd_internal(h, st, {.kind = kind, .dtype = dtype, .N = M, .N2 = SB, .Q = Q, .X = Z, .X2 = X, .ls = ls, .ard = ard, .var = var,
+                                                   .dK = Text, .lddk = SB, .dX = dZ, .dX2 = dX, .dls = dls, .dvar = dvar});
                 if (rc) return rc;
             }
         } else if (!want_grad) {
@@ -1595,11 +1596,11 @@ struct SvgpCall : SvgpPlan {
             // (dY, dZ, dls, dvar, dX, R were cleared on the second side stream at the start of the call: su_side2)
             // one pass over T: q_n, |e_n|^2, dY, R = Kuf E, and the Kuf-side reverse mode (dX, dZ, dls, dvar) without materialising dKuf
             MXF_T0(h, MXF_T_BWD, st);
-            rc = mxf_svgp_bwd_fused_internal(h, kind, dtype, M, SB, B, Q, P, Z, X, ls, ard, var, Text, het_stream ? (const T*)hys : Y, sY, wT,
-                                             het_stream ? (const T*)hnz : noise, a1, dZ, dX, dls, dvar,
-                                             dY, dY_shared, R, scal, st, t_blocked,
-                                             use_split ? (const unsigned*)(info2 + 2) : nullptr,
-                                             (const unsigned*)(info2 + 3));
+            rc = mxf_svgp_bwd_fused_internal(h, st, {.kind = kind, .dtype = dtype, .M = M, .SB = SB, .B = B, .Q = Q, .P = P, .Z = Z, .Xall = X, .ls = ls, .ard = ard,
+                                                     .var = var, .Text = Text, .Y = het_stream ? (const T*)hys : Y, .sY = sY, .w = wT,
+                                                     .noise = het_stream ? (const T*)hnz : noise, .a1 = a1, .dZ = dZ, .dXall = dX, .dls = dls, .dvar = dvar,
+                                                     .dY = dY, .dY_shared = dY_shared, .R = R, .scal = scal, .t_blocked = t_blocked,
+                                                     .h0max = use_split ? (const unsigned*)(info2 + 2) : nullptr, .tmax = (const unsigned*)(info2 + 3)});
             if (rc) return rc;
         }
         if (fused) MXF_T1(h, MXF_T_BWD, st);
@@ -1666,8 +1667,8 @@ struct SvgpCall : SvgpPlan {
         } else {
             if (!fused && (rc = clear_core_grads(st))) return rc;
             // (sym_dkuu: dKuu is formed from the mirrored X, Ki and H0, i.e. symmetric -- the row side of its reverse pass is skipped)
-            rc = mxf_gram_bwd_internal(h, kind, MXF_F64, 1, M, M, Q, Zd, 0, nullptr, 0, lsd, ard, 0, vard, 0, dKuu, M, 0, dZc, nullptr, dlsc, dvc, st,
-                                       sym_dkuu ? 1 : 0);
+            rc = mxf_gram_bwd_internal(h, st, {.kind = kind, .dtype = MXF_F64, .N = M, .Q = Q, .X = Zd, .ls = lsd, .ard = ard, .var = vard, .dK = dKuu, .lddk = M,
+                                               .dX = dZc, .dls = dlsc, .dvar = dvc, .dk_symmetric = sym_dkuu});
             if (rc) return rc;
             if (dZ) fin(dZc, nullptr, dZ, M * Q, 1);
             if (dls) fin(dlsc, nullptr, dls, lsn, 1);
@@ -1860,7 +1861,8 @@ int sgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int64_t B, int64_t M, int 
     if (dls) MXF_HIP(h, hipMemsetAsync(dls, 0, sizeof(T) * lsn, st));
     if (dvar) MXF_HIP(h, hipMemsetAsync(dvar, 0, sizeof(T), st));
     if (dX) MXF_HIP(h, hipMemsetAsync(dX, 0, sizeof(T) * B * Q, st));
-    rc = mxf_gram_bwd_internal(h, kind, dtype, 1, M, B, Q, Z, 0, X, 0, ls, ard, 0, var, 0, dKuf, B, 0, dZ, dX, dls, dvar, st);
+    rc = mxf_gram_bwd_internal(h, st, {.kind = kind, .dtype = dtype, .N = M, .N2 = B, .Q = Q, .X = Z, .X2 = X, .ls = ls, .ard = ard, .var = var,
+                                       .dK = dKuf, .lddk = B, .dX = dZ, .dX2 = dX, .dls = dls, .dvar = dvar});
     if (rc) return rc;
     if (dY) {
         rc = mxf_gemm_internal(h, dtype, 1, 0, B, P, M, 1.0, Kuf, B, 0, Gpsi1, P, 0, 0.0, dY, P, 0, 1, 0, st);     // Kuf^T dpsi1
@@ -1870,7 +1872,8 @@ int sgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int64_t B, int64_t M, int 
     MXF_HIP(h, hipMemsetAsync(dZc, 0, sizeof(D) * M * Q, st));
     MXF_HIP(h, hipMemsetAsync(dlsc, 0, sizeof(D) * lsn, st));
     MXF_HIP(h, hipMemsetAsync(dvc, 0, sizeof(D) * 4, st));
-    rc = mxf_gram_bwd_internal(h, kind, MXF_F64, 1, M, M, Q, Zd, 0, nullptr, 0, lsd, ard, 0, vard, 0, GKuu, M, 0, dZc, nullptr, dlsc, dvc, st);
+    rc = mxf_gram_bwd_internal(h, st, {.kind = kind, .dtype = MXF_F64, .N = M, .Q = Q, .X = Zd, .ls = lsd, .ard = ard, .var = vard, .dK = GKuu, .lddk = M,
+                                       .dX = dZc, .dls = dlsc, .dvar = dvc});
     if (rc) return rc;
     if (dZ) hipLaunchKernelGGL((add_convert_kernel<D, T>), dim3(gridn(M * Q)), dim3(256), 0, st, M * Q, (T)1, (const D*)dZc, dZ, 1);
     if (dls) hipLaunchKernelGGL((add_convert_kernel<D, T>), dim3(gridn(lsn)), dim3(64), 0, st, (int64_t)lsn, (T)1, (const D*)dlsc, dls, 1);

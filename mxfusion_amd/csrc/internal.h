@@ -22,24 +22,39 @@ int mxf_trtri_internal(mxf_ctx* h, int dtype, int S, int64_t n, const void* L, i
                        int64_t sI, hipStream_t st);
 int mxf_sumlogdiag_internal(mxf_ctx* h, int dtype, int S, int64_t n, const void* L, int64_t ldl, int64_t sL, void* out, hipStream_t st);
 
-int mxf_gram_bwd_internal(mxf_ctx* h, int kind, int dtype, int S, int64_t N, int64_t N2, int Q, const void* X, int64_t sX,
-                          const void* X2, int64_t sX2, const void* ls, int ard, int64_t sls, const void* var, int64_t svar,
-                          const void* dK, int64_t lddk, int64_t sdK, void* dX, void* dX2, void* dls, void* dvar, hipStream_t st, int dk_symmetric = 0);
-// (dk_symmetric, square case only: the caller vouches that dK is symmetric -- the row-side sums are skipped and the column side counts twice)
+// The Gram reverse passes take plain descriptors (aggregates, every member defaulted, as the split GEMMs' below): a call site names what it passes.
+// Plain reverse mode of a stationary Gram (gram_bwd.hip): dK -> dX, dX2, dls, dvar, all ACCUMULATED into; outputs may be nullptr.
+struct MxfGramBwd {
+    int kind = 0, dtype = 0;
+    int S = 1; int64_t N = 0, N2 = 0; int Q = 0;        // S samples of an (N x N2) Gram over Q coordinates
+    const void* X = nullptr; int64_t sX = 0;            // (N x Q); the s* members are per-sample strides in elements, 0 = shared by the samples
+    const void* X2 = nullptr; int64_t sX2 = 0;          // (N2 x Q); nullptr: the square Gram of X with itself (N2 is ignored, both roles flow into dX)
+    const void* ls = nullptr; int ard = 0; int64_t sls = 0; const void* var = nullptr; int64_t svar = 0;
+    const void* dK = nullptr; int64_t lddk = 0, sdK = 0;
+    void* dX = nullptr; void* dX2 = nullptr; void* dls = nullptr; void* dvar = nullptr;
+    bool dk_symmetric = false;      // square case only: the caller vouches that dK is symmetric -- the row-side sums are skipped and the column side counts twice
+};
+int mxf_gram_bwd_internal(mxf_ctx* h, hipStream_t st, const MxfGramBwd& d);
 
-// true if mxf_svgp_bwd_fused_internal takes the matrix-pipe pass for these arguments; that pass reads T in 16-column blocks
-// (element (m, n) at ((n / 16) * M + m) * 16 + n % 16: mxf_gemm_split_internal's c_blocked output) when called with t_blocked = 1
+// SVGP-fused reverse pass over Text = [H0; w^T] Kuf_all (rows 0..M-1: T, rows M..M+P-1: U), which never materialises dKuf.  dXall is WRITTEN
+// (not accumulated); dZ, dls, dvar, R, scal are accumulated into (the caller zeroes them); dY is written or (dY_shared) accumulated.
+struct MxfSvgpBwd {
+    int kind = 0, dtype = 0;
+    int64_t M = 0, SB = 0, B = 0; int Q = 0, P = 0;     // M inducing points, SB = samples x B columns, P outputs
+    const void* Z = nullptr; const void* Xall = nullptr; const void* ls = nullptr; int ard = 0; const void* var = nullptr; const void* Text = nullptr;
+    const void* Y = nullptr; int64_t sY = 0;            // (B x P) per sample, sample stride sY (0: shared)
+    const void* w = nullptr; const void* noise = nullptr; double a1 = 0.0; void* dZ = nullptr; void* dXall = nullptr; void* dls = nullptr; void* dvar = nullptr;
+    void* dY = nullptr; int dY_shared = 0; void* R = nullptr; double* scal = nullptr;
+    int t_blocked = 0;              // T in 16-column blocks, element (m, n) at ((n / 16) * M + m) * 16 + n % 16 (mxf_gemm_split_internal's blocked output)
+    // h0max: bit pattern of max |H0| when T = H0 Kuf came from the f16x2 split GEMM -- the operand bound that lets the matrix-pipe pass
+    // accumulate its weights as hi + lo f16; nullptr: float32 accumulation.  tmax: bit pattern of max |T| if the GEMM reported it (word != 0): the tight bound
+    const unsigned* h0max = nullptr; const unsigned* tmax = nullptr;
+};
+// true if mxf_svgp_bwd_fused_internal takes the matrix-pipe pass (svgp_bwd_mfma.hip) for these arguments, not the difference-form one of gram_bwd.hip
 bool mxf_svgp_bwd_is_mfma(int kind, int dtype, int64_t SB, int64_t B, int Q, int P, const void* Text);
 bool mxf_svgp_bwd_reads_blocked(int kind, int dtype, int64_t SB, int64_t B, int Q, int P, const void* Text);
-// SVGP-fused reverse pass over Text = [H0; w^T] Kuf_all (never materialises dKuf); see gram_bwd.hip
-int mxf_svgp_bwd_fused_internal(mxf_ctx* h, int kind, int dtype, int64_t M, int64_t SB, int64_t B, int Q, int P, const void* Z,
-                                const void* Xall, const void* ls, int ard, const void* var, const void* Text, const void* Y,
-                                int64_t sY, const void* w, const void* noise, double a1, void* dZ, void* dXall, void* dls,
-                                void* dvar, void* dY, int dY_shared, void* R, double* scal, hipStream_t st, int t_blocked = 0,
-                                const unsigned* h0max = nullptr, const unsigned* tmax = nullptr);
-// (h0max: bit pattern of max |H0| when T = H0 Kuf came from the f16x2 split GEMM -- the operand bound that lets the matrix-pipe pass
-//  accumulate its RBF weights as hi + lo f16; nullptr: float32 accumulation.  tmax: bit pattern of max |T| if the GEMM reported it
-//  (word != 0): the tight bound)
+int mxf_svgp_bwd_fused_internal(mxf_ctx* h, hipStream_t st, const MxfSvgpBwd& d);
+int mxf_svgp_bwd_mfma_internal(mxf_ctx* h, hipStream_t st, const MxfSvgpBwd& d);      // svgp_bwd_mfma.hip; the caller has asked mxf_svgp_bwd_is_mfma
 
 // f32-accurate GEMM on the bf16 matrix pipe (three-term bf16 splitting, gemm_split.hip)
 size_t mxf_split_plane_elems(int64_t R, int64_t K);    // elements (bf16) of ONE plane of an (R x K) operand

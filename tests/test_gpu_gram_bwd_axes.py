@@ -213,7 +213,7 @@ def test_coincident_points(kind, N, N2, Q, ard, pattern, dtype):
 
 
 # ---- several column tiles per workgroup ---------------------------------------------------------------------------------------------------
-# launch_q (gram_bwd.hip) gives a workgroup CT = ceil(tiles * row bands * S / 4096) column tiles of 256: 243 tiles x 1 band x 17 samples = 4131
+# gram_bwd_plan (gram_bwd_plan.h) gives a workgroup CT = ceil(tiles * row bands * S / 4096) column tiles of 256: 243 tiles x 1 band x 17 samples = 4131
 # -> CT = 2, and 243 is odd: the last workgroup of each sample meets tile0 >= N2 and stops early.  dK is 17 x 64 x 61957 float32 = 270 MB.
 CT_S, CT_N, CT_N2, CT_Q = 17, 64, 242 * 256 + 5, 2
 
