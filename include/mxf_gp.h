@@ -462,6 +462,49 @@ int mxf_dense_bwd(mxf_handle h, int dtype, int S, int64_t N, int I, int O, int a
                   const void* W, int64_t strideS_w, int64_t strideS_b, const void* Y, const void* dY, void* dX_acc, void* dW_acc,
                   void* db_acc, void* stream);
 
+/* The model operators' arithmetic (ewise.hip): one broadcast map over up to MXF_EW_MAX_RANK axes -- the sample axis included, counted
+ * after the caller has merged what can be merged -- for all samples in one launch.
+ *   op: 0 add, 1 subtract, 2 multiply, 3 divide, 4 power, 5 square, 6 exp, 7 log   (5..7: y and stride_y are ignored and may be null)
+ * extent[0] is the sample axis S; stride_x / stride_y are in elements, and a stride of 0 (or an extent of 1) shares the operand over that
+ * axis.  extent and the strides are HOST arrays of `rank` entries, read during the call and passed to the kernel by value.  Strides are
+ * not negative; anything else goes (a transposed view, an odd start: the kernel uses 16-byte accesses where a chunk is aligned and
+ * contiguous and scalar ones elsewhere).  exp, log and pow are the device library's accurate functions.
+ * Status -2: bad arguments (dtype, op, rank < 1, a null operand or array, a negative extent or stride).  Status -3: rank above
+ * MXF_EW_MAX_RANK, or more than 2^31 * 16 output elements, or an operand spanning more than that; no buffer is touched (the caller's to
+ * route elsewhere).
+ *
+ * mxf_ewise_fwd: z = op(x, y), WRITTEN, z dense row-major over extent.  Replaces add .. log of
+ * components/functions/operators/operator_impl.py:27-85 run once per sample by the loop of FunctionEvaluation.eval
+ * (components/functions/function_evaluation.py:72-96).                                                                                 */
+#define MXF_EW_MAX_RANK 5
+int mxf_ewise_fwd(mxf_handle h, int op, int dtype, int rank, const int64_t* extent, const void* x, const int64_t* stride_x,
+                  const void* y, const int64_t* stride_y, void* z, void* stream);
+
+/* Reverse mode of mxf_ewise_fwd with the cotangent dz, dense over extent (operator_impl.py:27-85 under MXNet autograd, one sample at a
+ * time: function_evaluation.py:72-96):
+ *   add dz, dz | subtract dz, -dz | multiply dz y, dz x | divide dz / y, -dz x / y^2 | power dz y x^(y-1), dz x^y log x |
+ *   square 2 x dz | exp dz exp x | log dz / x
+ * ACCUMULATED into dx_acc and dy_acc: dense, shaped like their operand with every shared axis at extent 1.  An operand without a shared
+ * axis gets plain stores; a shared operand's gradient is the sum over its shared axes, formed in double for either dtype (float32: zeroed
+ * handle scratch and a fold more) after a workgroup has reduced what it holds for one element.  For power a wanted dy at x <= 0 is NaN or
+ * infinite, as log x is.  Either output may be null.                                                                                   */
+int mxf_ewise_bwd(mxf_handle h, int op, int dtype, int rank, const int64_t* extent, const void* x, const int64_t* stride_x,
+                  const void* y, const int64_t* stride_y, const void* dz, void* dx_acc, void* dy_acc, void* stream);
+
+/* The reductions behind the sample axis (ewise.hip).  kind: 0 sum, 1 mean, 2 prod.  x dense (outer, R, inner) -> y dense (outer, inner),
+ * WRITTEN; R >= 1.  inner == 1: a wave per row up to R = 512, a workgroup per row beyond; inner > 1: lanes along inner, a loop over R.
+ * Every kind accumulates in double for either dtype.  Status -3 beyond 2^31 * 16 elements.  Replaces sum, mean and prod of
+ * operator_impl.py:27-85 under the per-sample loop of function_evaluation.py:72-96.                                                     */
+int mxf_reduce_fwd(mxf_handle h, int kind, int dtype, int64_t outer, int64_t R, int64_t inner, const void* x, void* y, void* stream);
+
+/* Reverse mode of mxf_reduce_fwd with the cotangent dy (outer, inner), ACCUMULATED into dx_acc (outer, R, inner) (operator_impl.py:27-85
+ * under autograd, function_evaluation.py:72-96): sum dy; mean dy / R; prod dy times the product of the other entries, formed from
+ * exclusive prefix and suffix products (double, handle scratch; the forward's regimes) and never by dividing -- a row with one zero or
+ * several is right.
+ * x is read by prod only.  A null dx_acc: nothing to do.                                                                               */
+int mxf_reduce_bwd(mxf_handle h, int kind, int dtype, int64_t outer, int64_t R, int64_t inner, const void* x, const void* dy,
+                   void* dx_acc, void* stream);
+
 /* MXNet Adam as driven by gluon.Trainer.step (batch_loop.py:46-60, minibatch_loop.py:71-91):
  * g*=rescale; m=b1 m+(1-b1)g; v=b2 v+(1-b2)g^2; w -= lr*sqrt(1-b2^t)/(1-b1^t) * m/(sqrt(v)+eps)      */
 int mxf_adam_step(mxf_handle h, int dtype, int64_t n, void* w, const void* g, void* m, void* v,

@@ -13,9 +13,14 @@ WRITE, ACC_ADD, ACC_MUL = 0, 1, 2
 D_GAMMA, D_GAMMA_MV, D_BETA, D_LAPLACE, D_UNIFORM, D_BERNOULLI = range(6)
 ACT_IDENTITY, ACT_TANH, ACT_RELU, ACT_SIGMOID = range(4)
 DENSE_MAX_WIDTH = 128
+EW_ADD, EW_SUBTRACT, EW_MULTIPLY, EW_DIVIDE, EW_POWER, EW_SQUARE, EW_EXP, EW_LOG = range(8)
+EW_MAX_RANK = 5            # MXF_EW_MAX_RANK
+EW_MAX_ELEMS = 1 << 35     # the output, and the span of an operand
+RED_SUM, RED_MEAN, RED_PROD = range(3)
 
 _c = ctypes
 _vp, _i, _i64, _d = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_double
+_p64 = _c.POINTER(_c.c_int64)          # a host array of extents or strides
 
 # name -> argtypes (after the handle); every entry point include/mxf_gp.h declares is listed here
 SIGNATURES = {
@@ -52,6 +57,10 @@ SIGNATURES = {
     'mxf_dirichlet_logpdf_bwd': [_i, _i, _i64, _i, _vp, _i64, _vp, _i64, _i64, _i, _vp, _d, _vp, _vp, _vp],
     'mxf_dense_fwd': [_i, _i, _i64, _i, _i, _i, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
     'mxf_dense_bwd': [_i, _i, _i64, _i, _i, _i, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+    'mxf_ewise_fwd': [_i, _i, _i, _p64, _vp, _p64, _vp, _p64, _vp, _vp],
+    'mxf_ewise_bwd': [_i, _i, _i, _p64, _vp, _p64, _vp, _p64, _vp, _vp, _vp, _vp],
+    'mxf_reduce_fwd': [_i, _i, _i64, _i64, _i64, _vp, _vp, _vp],
+    'mxf_reduce_bwd': [_i, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
     'mxf_normal_reparam_bwd': [_i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
     'mxf_adam_step': [_i, _i64, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _d, _i, _vp],
     'mxf_sgd_step': [_i, _i64, _vp, _vp, _vp, _d, _d, _d, _d, _vp],

@@ -97,6 +97,45 @@ class Variable(object):
                 object.__setattr__(new, k, copy.deepcopy(v, memo))
         return new
 
+    __array_ufunc__ = None        # numpy leaves `array (op) Variable` to the reflected forms below instead of broadcasting over the array
+
+    # ---- arithmetic (variable.py:247-265): each builds the named operator; a number or an array on the other side becomes a constant ----
+    def _operator(self, name, other, reflected=False):
+        from ..functions.operators import operators
+        if not isinstance(other, (Variable, int, float, np.ndarray, torch.Tensor)) or isinstance(other, bool):
+            return NotImplemented
+        return getattr(operators, name)(other, self) if reflected else getattr(operators, name)(self, other)
+
+    def __add__(self, y):
+        return self._operator('add', y)
+
+    def __radd__(self, y):
+        return self._operator('add', y, True)
+
+    def __sub__(self, y):
+        return self._operator('subtract', y)
+
+    def __rsub__(self, y):
+        return self._operator('subtract', y, True)
+
+    def __mul__(self, y):
+        return self._operator('multiply', y)
+
+    def __rmul__(self, y):
+        return self._operator('multiply', y, True)
+
+    def __truediv__(self, y):
+        return self._operator('divide', y)
+
+    def __rtruediv__(self, y):
+        return self._operator('divide', y, True)
+
+    def __pow__(self, y):
+        return self._operator('power', y)
+
+    def __rpow__(self, y):
+        return self._operator('power', y, True)
+
     def __hash__(self):
         return hash(self.uuid)
 

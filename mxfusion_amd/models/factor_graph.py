@@ -107,6 +107,22 @@ class FactorGraph(object):
                     share(a)
         return copy.deepcopy(self, memo)
 
+    def extract_distribution_of(self, variable):
+        """factor_graph.py:394-413: a copy of `variable` (same UUID) with nothing but its parent subgraph attached, copied too: the factor
+        it comes from, that factor's inputs, and so on upwards.  The copies belong to no graph; arrays are shared as in clone."""
+        top = self.clone()[variable]
+        seen, todo = set(), [top]
+        while todo:
+            v = todo.pop()
+            if id(v) in seen:
+                continue
+            seen.add(id(v))
+            v.graph = None
+            if v.factor is not None:
+                v.factor.graph = None
+                todo.extend(u for _, u in list(v.factor.inputs) + list(v.factor.outputs))
+        return top
+
     def __getitem__(self, key):
         uuid = key.uuid if isinstance(key, Variable) else key
         return self._variables[uuid]

@@ -667,6 +667,195 @@ def dense_bwd_(X, W, Y, dY, act=None, dX_acc=None, dW_acc=None, db_acc=None):
               _p(dX_acc), _p(dW_acc), _p(db_acc), _stream())
 
 
+EW_OP = {'add': _lib.EW_ADD, 'subtract': _lib.EW_SUBTRACT, 'multiply': _lib.EW_MULTIPLY, 'divide': _lib.EW_DIVIDE, 'power': _lib.EW_POWER,
+         'square': _lib.EW_SQUARE, 'exp': _lib.EW_EXP, 'log': _lib.EW_LOG}
+RED_KIND = {'sum': _lib.RED_SUM, 'mean': _lib.RED_MEAN, 'prod': _lib.RED_PROD}
+
+_EW_TORCH = {_lib.EW_ADD: torch.add, _lib.EW_SUBTRACT: torch.sub, _lib.EW_MULTIPLY: torch.mul, _lib.EW_DIVIDE: torch.div, _lib.EW_POWER: torch.pow,
+             _lib.EW_SQUARE: torch.square, _lib.EW_EXP: torch.exp, _lib.EW_LOG: torch.log}
+
+
+def _ew_op(op):
+    return EW_OP[op] if isinstance(op, str) else int(op)
+
+
+def ewise_operands(x, y=None):
+    """x (S|1, ...) and y (S|1, ...) or None as the broadcast map takes them, through views alone: of one rank -- the shorter one gets axes of
+    extent 1 behind its sample axis, the numpy rule as BroadcastToOperator applies it -- and with every expanded (stride-0) axis back at
+    extent 1, so that what came out of broadcast_to is never materialised and its gradient has the shape of what went in."""
+    ts = [t for t in (x, y) if t is not None]
+    if any(t.dim() < 1 for t in ts):
+        raise ValueError('ewise: an operand without a sample axis')
+    rank = max(t.dim() for t in ts)
+    out = []
+    for t in ts:
+        if t.dim() < rank:
+            t = t.reshape((t.shape[0],) + (1,) * (rank - t.dim()) + tuple(t.shape[1:]))
+        out.append(_shared_axes(t, range(rank), None)[0])
+    return out[0], (out[1] if y is not None else None)
+
+
+def _ewise_plan(x, y):
+    """(output shape, extents, strides of x, strides of y) of the map over ewise_operands' x and y, the axes of extent 1 dropped and adjacent
+    axes merged where both operands traverse them the same way: each dense over the run, or shared over all of it"""
+    ts = [x] if y is None else [x, y]
+    shape = tuple(max(int(t.shape[d]) for t in ts) for d in range(x.dim()))
+    for t in ts:
+        if any(t.shape[d] not in (1, shape[d]) for d in range(x.dim())):
+            raise ValueError('ewise: operands of %s do not broadcast' % ', '.join(str(tuple(u.shape)) for u in ts))
+    axes = []          # [extent, stride of each operand]
+    for d, e in enumerate(shape):
+        if e == 1:
+            continue
+        cur = [e] + [0 if t.shape[d] == 1 else int(t.stride(d)) for t in ts]
+        if axes and all((p == 0 and c == 0) or (c != 0 and p == c * e) for p, c in zip(axes[-1][1:], cur[1:])):
+            axes[-1] = [axes[-1][0] * e] + cur[1:]
+        else:
+            axes.append(cur)
+    if not axes:
+        axes = [[1] + [0] * len(ts)]
+    return shape, [a[0] for a in axes], [a[1] for a in axes], ([a[2] for a in axes] if y is not None else None)
+
+
+def _ewise_fits(extent, sx, sy):
+    span = lambda s: sum((e - 1) * k for e, k in zip(extent, s))
+    n = 1
+    for e in extent:
+        n *= e
+    return len(extent) <= _lib.EW_MAX_RANK and n <= _lib.EW_MAX_ELEMS and span(sx) <= _lib.EW_MAX_ELEMS and (sy is None or span(sy) <= _lib.EW_MAX_ELEMS)
+
+
+def _i64s(values):
+    return (_lib._c.c_int64 * len(values))(*values)
+
+
+def _ewise_prepare(what, op, x, y):
+    op = _ew_op(op)
+    if op > _lib.EW_POWER:
+        y = None
+    elif y is None:
+        raise ValueError('%s: op %d takes two operands' % (what, op))
+    _same_kind(what, x, y)
+    x, y = ewise_operands(x, y)
+    return (op, x, y) + _ewise_plan(x, y)
+
+
+def ewise_fits(x, y=None):
+    """whether the kernel takes the map over these operands (mxf_ewise_* would not answer -3); ewise and ewise_bwd_ go through the torch
+    expression on the device where it does not"""
+    x, y = ewise_operands(x, y)
+    return _ewise_fits(*_ewise_plan(x, y)[1:])
+
+
+def ewise(op, x, y=None):
+    """z = op(x, y) (S, ...) for all samples in one launch (mxf_ewise_fwd): op 'add', 'subtract', 'multiply', 'divide', 'power' on x (S|1, ...)
+    and y (S|1, ...), broadcast by the numpy rule behind the sample axis, or 'square', 'exp', 'log' on x alone.  An axis of extent 1 or an
+    expanded one is shared; a non-contiguous operand is passed as it is, never copied.  More than five axes after merging go through the
+    torch expression on the device."""
+    op, x, y, shape, extent, sx, sy = _ewise_prepare('ewise', op, x, y)
+    if not _ewise_fits(extent, sx, sy):
+        return _EW_TORCH[op](x, y).contiguous() if y is not None else _EW_TORCH[op](x)
+    z = torch.empty(shape, dtype=x.dtype, device=x.device)
+    if z.numel():
+        _lib.call('mxf_ewise_fwd', _h(x), op, _dt(x), len(extent), _i64s(extent), _p(x), _i64s(sx), _p(y), None if sy is None else _i64s(sy),
+                  _p(z), _stream())
+    return z
+
+
+def _ewise_grads_torch(op, x, y, dz):
+    if op == _lib.EW_ADD:
+        return dz, dz
+    if op == _lib.EW_SUBTRACT:
+        return dz, -dz
+    if op == _lib.EW_MULTIPLY:
+        return dz * y, dz * x
+    if op == _lib.EW_DIVIDE:
+        return dz / y, -dz * x / (y * y)
+    if op == _lib.EW_POWER:
+        return dz * y * torch.pow(x, y - 1), dz * torch.pow(x, y) * torch.log(x)
+    return {_lib.EW_SQUARE: lambda: 2 * x * dz, _lib.EW_EXP: lambda: dz * torch.exp(x), _lib.EW_LOG: lambda: dz / x}[op](), None
+
+
+def ewise_bwd_(op, x, y, dz, dx_acc=None, dy_acc=None):
+    """Reverse mode of ewise under the cotangent dz (S, ...): dx_acc and dy_acc -- dense, shaped like ewise_operands' x and y, every shared
+    axis at extent 1 -- += the gradients, summed over the shared axes in double (mxf_ewise_bwd).  Either may be None."""
+    _same_kind('ewise', x, dz, dx_acc, dy_acc)
+    op, x, y, shape, extent, sx, sy = _ewise_prepare('ewise', op, x, y)
+    if y is None:
+        dy_acc = None
+    _check_buffers('ewise', (dz, shape), (dx_acc, x.shape), (dy_acc, None if y is None else y.shape))
+    if dx_acc is None and dy_acc is None:
+        return
+    if not _ewise_fits(extent, sx, sy):
+        for g, acc in zip(_ewise_grads_torch(op, x, y, dz), (dx_acc, dy_acc)):
+            if acc is not None:
+                acc.add_(g.sum_to_size(acc.shape))
+        return
+    if dz.numel():
+        _lib.call('mxf_ewise_bwd', _h(x), op, _dt(x), len(extent), _i64s(extent), _p(x), _i64s(sx), _p(y), None if sy is None else _i64s(sy),
+                  _p(dz), _p(dx_acc), _p(dy_acc), _stream())
+
+
+def _reduce_plan(x, axes):
+    """x (S, ...) and the per-sample axes to reduce (None: all) -> (x as the kernel takes it: contiguous, the reduced axes one run, the
+    permutation that made it so or None, outer, R, inner, the result's shape)"""
+    nd = x.dim() - 1
+    if axes is None:
+        axes = tuple(range(nd))
+        out_shape = (x.shape[0], 1)
+    else:
+        axes = (axes,) if isinstance(axes, int) else tuple(axes)
+        axes = tuple(sorted(a + nd if a < 0 else a for a in axes))
+        if not axes or len(set(axes)) != len(axes) or axes[0] < 0 or axes[-1] >= nd:
+            raise ValueError('reduce: axes %s of a per-sample array of %d dimension(s)' % (axes, nd))
+        out_shape = tuple(x.shape[d] for d in range(x.dim()) if d == 0 or d - 1 not in axes)
+    full = [a + 1 for a in axes]
+    perm = None
+    if full and full != list(range(full[0], full[0] + len(full))):
+        perm = [d for d in range(x.dim()) if d not in full] + full
+        x = x.permute(perm)
+        full = list(range(x.dim() - len(full), x.dim()))
+    x = x.contiguous()
+    lo, hi = (full[0], full[-1] + 1) if full else (x.dim(), x.dim())
+    return x, perm, _numel(x.shape[:lo]), _numel(x.shape[lo:hi]), _numel(x.shape[hi:]), out_shape
+
+
+def _numel(shape):
+    n = 1
+    for s in shape:
+        n *= int(s)
+    return n
+
+
+def reduce(kind, x, axes=None):
+    """'sum', 'mean' or 'prod' of x (S, ...) over the per-sample axes `axes` -- an int, a tuple, or None for all of them -- for all samples in
+    one launch (mxf_reduce_fwd).  With axes the result drops them; with None it is (S, 1).  Axes that are not adjacent are brought together
+    by a permuted copy first."""
+    _same_kind('reduce', x)
+    kind = RED_KIND[kind] if isinstance(kind, str) else int(kind)
+    xc, _, outer, R, inner, out_shape = _reduce_plan(x, axes)
+    out = torch.empty(out_shape, dtype=x.dtype, device=x.device)
+    if out.numel():
+        _lib.call('mxf_reduce_fwd', _h(xc), kind, _dt(xc), outer, R, inner, _p(xc), _p(out), _stream())
+    return out
+
+
+def reduce_bwd_(kind, x, axes, dy, dx_acc):
+    """Reverse mode of reduce under the cotangent dy (shaped like the result): dx_acc, contiguous and shaped like x, += the gradient
+    (mxf_reduce_bwd); prod never divides."""
+    _same_kind('reduce', x, dy, dx_acc)
+    kind = RED_KIND[kind] if isinstance(kind, str) else int(kind)
+    xc, perm, outer, R, inner, out_shape = _reduce_plan(x, axes)
+    _check_buffers('reduce', (dy, out_shape), (dx_acc, x.shape))
+    if not dx_acc.numel():
+        return
+    acc = dx_acc if perm is None else torch.zeros(xc.shape, dtype=x.dtype, device=x.device)
+    _lib.call('mxf_reduce_bwd', _h(xc), kind, _dt(xc), outer, R, inner, _p(xc), _p(dy), _p(acc), _stream())
+    if perm is not None:
+        inverse = [perm.index(d) for d in range(len(perm))]
+        dx_acc.add_(acc.permute(inverse))
+
+
 def adam_step_(w, g, m, v, lr, t, beta1=0.9, beta2=0.999, epsilon=1e-8, rescale_grad=1.0):
     _lib.call('mxf_adam_step', _h(w), _dt(w), w.numel(), _p(w), _p(g), _p(m), _p(v), float(lr), float(beta1), float(beta2),
               float(epsilon), float(rescale_grad), int(t), _stream())
