@@ -343,6 +343,36 @@ int mxf_univariate_logpdf_bwd(mxf_handle h, int kind, int dtype, int S, int64_t 
                               const void* a, int64_t n_a, int64_t strideS_a, const void* b, int64_t n_b, int64_t strideS_b,
                               const void* cot, double scale, void* dx_acc, void* da_acc, void* db_acc, void* stream);
 
+/* Per-sample sums for the score-function estimators (Ranganath et al. 2014, Algorithm 1): out[s] += scale * sum_i log p(x[s,i] | a, b) for
+ * s < S, out (S) ACCUMULATED INTO (caller zeroes it, like the reduced kernels).  x is (S, n); a parameter is a single element
+ * (n_a = 1, strideS = 0), per element (n_a = n, strideS = 0) or per sample and element (n_a = n, strideS = n) -- the layouts of
+ * mxf_univariate_logpdf_elem.  The reduced entry points bake the 1/S mean of factor_graph.py:223 into ONE scalar (factor_graph.py:192-238);
+ * an estimator that weights each sample by f_s = log p - log q needs the S values apart.  The reference's own ScoreFunctionInference
+ * (inference/score_function.py:70-77) multiplies two values that are sample means already and has no per-sample quantity to replace;
+ * mxfusion_amd/inference/score_function.py implements the paper's estimator on these.  A sample with an element outside the Uniform's
+ * support gets -inf (scale > 0); the other samples are not touched by it.
+ * mxf_univariate_logpdf_ps_bwd is the reverse mode with the per-sample weights w (S elements, device, dtype of the call):
+ * dx[s,i] += scale * w[s] * dlogp/dx, and likewise da, db -- summed over s for a parameter without sample axis ((n_a) elements, a
+ * single-element one also over i), (S,n) for a parameter with one.  Any output may be null.  The support rules of mxf_univariate_logpdf
+ * hold unchanged (outside the Uniform's support nothing is added; Laplace sign(0) = 0; Bernoulli db = 0).                              */
+int mxf_univariate_logpdf_ps(mxf_handle h, int kind, int dtype, int S, int64_t n, const void* x,
+                             const void* a, int64_t n_a, int64_t strideS_a, const void* b, int64_t n_b, int64_t strideS_b,
+                             double scale, void* out_acc, void* stream);
+int mxf_univariate_logpdf_ps_bwd(mxf_handle h, int kind, int dtype, int S, int64_t n, const void* x,
+                                 const void* a, int64_t n_a, int64_t strideS_a, const void* b, int64_t n_b, int64_t strideS_b,
+                                 const void* w, double scale, void* dx_acc, void* da_acc, void* db_acc, void* stream);
+
+/* The same pair for the Normal by mean and variance (Normal.log_pdf_impl, normal.py:52-70): out[s] += scale * sum_i logN(x[s,i] | mean,
+ * var), and dx, dmean, dvar += scale * w[s] * dlogN/d(.).  Unlike mxf_normal_logpdf, mean and var may carry a sample axis (strideS = n):
+ * the likelihood whose mean is a function of sampled latent variables, r = f(x; w_s) of shape (S, N, 1), is the large operand of this
+ * path.                                                                                                                                 */
+int mxf_normal_logpdf_ps(mxf_handle h, int dtype, int S, int64_t n, const void* x,
+                         const void* mean, int64_t n_mean, int64_t strideS_mean, const void* var, int64_t n_var, int64_t strideS_var,
+                         double scale, void* out_acc, void* stream);
+int mxf_normal_logpdf_ps_bwd(mxf_handle h, int dtype, int S, int64_t n, const void* x,
+                             const void* mean, int64_t n_mean, int64_t strideS_mean, const void* var, int64_t n_var, int64_t strideS_var,
+                             const void* w, double scale, void* dx_acc, void* dmean_acc, void* dvar_acc, void* stream);
+
 /* Multivariate normal of order n <= 32 over x (S, B, n), mean (S|1, B|1, n) and A (S|1, B|1, n, n): A is the covariance (form 0) or the
  * precision (form 1).  A larger n is status -3 from every entry point, and no buffer is touched (such matrices take mxf_potrf /
  * mxf_trsm).  Replaces MultivariateNormal.log_pdf_impl (components/distributions/normal.py:157-178: linalg.potrf, linalg.trsm,

@@ -46,6 +46,10 @@ SIGNATURES = {
     'mxf_univariate_logpdf': [_i, _i, _i, _i64, _vp, _vp, _i64, _vp, _i64, _d, _vp, _vp, _vp, _vp, _vp],
     'mxf_univariate_logpdf_elem': [_i, _i, _i, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _d, _vp, _vp],
     'mxf_univariate_logpdf_bwd': [_i, _i, _i, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _d, _vp, _vp, _vp, _vp],
+    'mxf_univariate_logpdf_ps': [_i, _i, _i, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _d, _vp, _vp],
+    'mxf_univariate_logpdf_ps_bwd': [_i, _i, _i, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _d, _vp, _vp, _vp, _vp],
+    'mxf_normal_logpdf_ps': [_i, _i, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _d, _vp, _vp],
+    'mxf_normal_logpdf_ps_bwd': [_i, _i, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _d, _vp, _vp, _vp, _vp],
     'mxf_mvn_factor': [_i, _i, _i, _i64, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
     'mxf_mvn_logpdf': [_i, _i, _i, _i64, _i, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _i, _i64, _d, _vp, _vp],
     'mxf_mvn_logpdf_bwd': [_i, _i, _i, _i64, _i, _vp, _i64, _vp, _i64, _i64, _vp, _i, _i64, _vp, _d, _vp, _vp, _vp, _vp],

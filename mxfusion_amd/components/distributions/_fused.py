@@ -53,6 +53,54 @@ def carved_grads(shapes, need, like):
     return [None if t is None else t.view(tuple(s)) for t, s in zip(grads, shapes)]
 
 
+# Which route Distribution.log_pdf_per_sample takes for Normal and the univariate family: the per-sample HIP reductions
+# (mxf_normal_logpdf_ps*, mxf_univariate_logpdf_ps*) where S * n >= PER_SAMPLE_KERNEL_MIN_ELEMS, below it the un-reduced log_pdf summed over
+# every axis but the first.  Measured on the MI355X in both size classes ("Score-function inference"); 0 sends every
+# size to the kernels, None none.
+PER_SAMPLE_KERNEL_MIN_ELEMS = 0
+
+
+def per_sample_kernels(S, n):
+    return PER_SAMPLE_KERNEL_MIN_ELEMS is not None and S * n >= PER_SAMPLE_KERNEL_MIN_ELEMS
+
+
+class _LogPdfPerSampleFn(torch.autograd.Function):
+    """scale * sum_i log p(x[s,i] | a, b), (S,).  x (S, n...); a, b: 1 or n elements, or (S, n...) with a sample axis of their own.  The
+    reverse mode hands the incoming (S,) cotangent to the kernel as its per-sample weights."""
+
+    @staticmethod
+    def forward(ctx, kind, scale, x, a, b):
+        ctx.kind, ctx.scale = kind, float(scale)
+        ctx.save_for_backward(x, a, b)
+        return ops.logpdf_per_sample_(kind, x, a, b, scale, torch.zeros(x.shape[0], dtype=x.dtype, device=x.device))
+
+    @staticmethod
+    def backward(ctx, g):
+        x, a, b = ctx.saved_tensors
+        grads = carved_grads((x.shape, a.shape, b.shape), ctx.needs_input_grad[2:5], x)
+        if any(t is not None for t in grads):
+            ops.logpdf_per_sample_bwd_(ctx.kind, x, a, b, g.contiguous(), ctx.scale, *grads)
+        return (None, None) + tuple(grads)
+
+
+def spread_operands(x, a, b):
+    """x (S|1, ...) and the parameters a, b (S|1, ...), each broadcastable against it, in the layouts of the elementwise kernels: x
+    (S, ...) contiguous; a parameter flat with one element, per element (no sample axis), or (S, ...) with one"""
+    S = max(int(x.shape[0]), int(a.shape[0]), int(b.shape[0]))
+    rest = tuple(x.shape[1:])
+
+    def spread(p):
+        if p.numel() == 1:
+            return p.reshape(1)
+        return p[0].expand(rest).contiguous() if p.shape[0] == 1 else p.expand((S,) + rest).contiguous()
+    return x.expand((S,) + rest).contiguous(), spread(a), spread(b)
+
+
+def log_pdf_per_sample(kind, scale, x, a, b):
+    """(S,) sums of scale * log p over every axis but the first, on the per-sample kernels; operands as spread_operands takes them"""
+    return _LogPdfPerSampleFn.apply(kind, scale, *spread_operands(x, a, b))
+
+
 def replicate(dist):
     """(factor.py:121-143) a factor of dist's class with the same names and UUID and no inputs or outputs yet, for a replicated graph to
     wire up.  For a class without constructor state of its own: nothing but what Distribution holds is carried over."""

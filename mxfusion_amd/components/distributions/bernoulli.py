@@ -27,6 +27,10 @@ class Bernoulli(UnivariateDistribution):
         pa = pa.contiguous()
         return _UnivariateLogPdfSumFn.apply(self._kind, x.contiguous(), pa, pa.detach(), self._scale())
 
+    def _per_sample_operands(self, variables):
+        p = variables[self.inputs[0][1].uuid]
+        return p, p.detach(), self._observed(variables[self.random_variable.uuid], p)
+
     def log_pdf_impl(self, prob_true, random_variable, F=None):
         """bernoulli.py:62-78."""
         return self._log_pdf(prob_true, prob_true.detach(), self._observed(random_variable, prob_true))

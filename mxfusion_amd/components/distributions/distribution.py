@@ -35,6 +35,13 @@ class Distribution(Factor):
         kw['random_variable'] = variables[self.random_variable.uuid]
         return self.log_pdf_impl(F=F, **kw)
 
+    def log_pdf_per_sample(self, F, variables):
+        """(S,) log-density of each sample: log_pdf summed over every axis but the first.  (No reference counterpart: factor_graph.py:223
+        reduces every factor to one scalar.  Normal and the univariate family override this with fused kernels.)  The sample extent is 1
+        where no operand carries samples."""
+        lp = self.log_pdf(F=F, variables=variables)
+        return lp.reshape(lp.shape[0], -1).sum(dim=1)
+
     def draw_samples(self, F, variables, num_samples=1, targets=None, always_return_tuple=False):
         kw = self._fetch(variables)
         from ...util.inference import realize_shape

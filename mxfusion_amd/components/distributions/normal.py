@@ -4,6 +4,7 @@ mode; this is q(X) and p(X) of the Monte-Carlo ELBO path."""
 import torch
 
 from ... import ops
+from . import _fused
 from ._fused import _carve
 from .distribution import Distribution
 from ..variables.variable import Variable
@@ -76,6 +77,15 @@ class Normal(Distribution):
         if m is None or v is None:   # sampled mean/variance: generic (elementwise torch, still on device)
             return self.log_pdf(F, variables).mean(dim=0).sum()
         return _NormalLogPdfSumFn.apply(x.contiguous(), m, v, self.log_pdf_scaling)
+
+    def log_pdf_per_sample(self, F, variables):
+        """(S,) sums of log_pdf over every axis but the first in one kernel (mxf_normal_logpdf_ps); mean and variance may be sampled."""
+        x = variables[self.random_variable.uuid]
+        mean, var = variables[self.inputs[0][1].uuid], variables[self.inputs[1][1].uuid]
+        S = max(int(x.shape[0]), int(mean.shape[0]), int(var.shape[0]))
+        if not _fused.per_sample_kernels(S, x.numel() // int(x.shape[0])):
+            return super(Normal, self).log_pdf_per_sample(F, variables)
+        return _fused.log_pdf_per_sample('normal', self.log_pdf_scaling, x, mean, var)
 
     def log_pdf_impl(self, mean, variance, random_variable, F=None):
         import math

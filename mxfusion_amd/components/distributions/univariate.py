@@ -5,6 +5,7 @@ and whether the reference multiplies its log-pdf by `log_pdf_scaling` (`_scaled`
 import torch
 
 from ... import ops
+from . import _fused
 from ._fused import _carve, carved_grads
 from .distribution import Distribution
 
@@ -81,15 +82,23 @@ class UnivariateDistribution(Distribution):
 
     def _log_pdf(self, a, b, random_variable):
         """(S, ...) log-pdf of random_variable (S|1, ...) under a, b (S|1, ...), each broadcastable against it."""
-        x = random_variable
-        S = max(int(x.shape[0]), int(a.shape[0]), int(b.shape[0]))
-        rest = tuple(x.shape[1:])
+        return _UnivariateLogPdfFn.apply(self._kind, self._scale(), *_fused.spread_operands(random_variable, a, b))
 
-        def spread(p):
-            if p.numel() == 1:
-                return p.reshape(1)
-            return p[0].expand(rest).contiguous() if p.shape[0] == 1 else p.expand((S,) + rest).contiguous()
-        return _UnivariateLogPdfFn.apply(self._kind, self._scale(), x.expand((S,) + rest).contiguous(), spread(a), spread(b))
+    def _per_sample_operands(self, variables):
+        """(a, b, x) as log_pdf_impl receives them"""
+        a, b = (variables[v.uuid] for _, v in self.inputs)
+        return a, b, variables[self.random_variable.uuid]
+
+    def log_pdf_per_sample(self, F, variables):
+        """(S,) sums of log_pdf over every axis but the first in one kernel (mxf_univariate_logpdf_ps), `log_pdf_scaling` where log_pdf_impl
+        applies it."""
+        if self._kind is None:                # a subclass without a kernel of this family
+            return super(UnivariateDistribution, self).log_pdf_per_sample(F, variables)
+        a, b, x = self._per_sample_operands(variables)
+        S = max(int(x.shape[0]), int(a.shape[0]), int(b.shape[0]))
+        if not _fused.per_sample_kernels(S, x.numel() // int(x.shape[0])):
+            return super(UnivariateDistribution, self).log_pdf_per_sample(F, variables)
+        return _fused.log_pdf_per_sample(self._kind, self._scale(), x, a, b)
 
     def _sample_inputs(self, p):
         return dict(dtype=p.dtype if isinstance(p, torch.Tensor) else self.dtype, ctx=p.device if isinstance(p, torch.Tensor) else self.ctx)

@@ -5,8 +5,10 @@
 //
 // Replaces: PositiveTransformation (components/variables/var_trans.py:63-91), Normal.log_pdf_impl /
 // draw_samples_impl (components/distributions/normal.py:52-92) + the sum(mean_S(.)) of
-// models/factor_graph.py:223, and gluon.Trainer.step(adam) of inference/batch_loop.py:46-60.
+// models/factor_graph.py:223, and gluon.Trainer.step(adam) of inference/batch_loop.py:46-60.  The per-sample Normal (mxf_normal_logpdf_ps*)
+// is the Normal kind of the kernels in unidist.h.
 #include "common.h"
+#include "unidist.h"
 
 namespace {
 
@@ -210,6 +212,31 @@ extern "C" int mxf_normal_logpdf(mxf_handle h, int dtype, int S, int64_t n, cons
     DISPATCH(h, dtype, "mxf_normal_logpdf",
              hipLaunchKernelGGL((normal_logpdf_kernel<float>), dim3(grid_for_reduce(n)), dim3(256), 0, st, S, n, (const float*)x, (const float*)mean, n_mean, (const float*)var, n_var, (float)scale, (float*)out_acc, (float*)dx_acc, (float*)dmean_acc, (float*)dvar_acc),
              hipLaunchKernelGGL((normal_logpdf_kernel<double>), dim3(grid_for_reduce(n)), dim3(256), 0, st, S, n, (const double*)x, (const double*)mean, n_mean, (const double*)var, n_var, scale, (double*)out_acc, (double*)dx_acc, (double*)dmean_acc, (double*)dvar_acc));
+}
+
+// the per-sample sums and their reverse mode: univariate_ps_kernel / univariate_logpdf_kernel (unidist.h) with the Normal's evaluation struct
+static int normal_ps_run(mxf_handle h, const char* name, int dtype, const UniArgs& u, int mode, void* stream) {
+    if (const int rc = uni_check(h, name, dtype, u)) return rc < 0 ? rc : 0;
+    if (dtype == MXF_F32) uni_launch_kind<float, MXF_D_NORMAL_>(u, mode, (hipStream_t)stream);
+    else uni_launch_kind<double, MXF_D_NORMAL_>(u, mode, (hipStream_t)stream);
+    MXF_LAUNCH_CHECK(h);
+    return 0;
+}
+
+extern "C" int mxf_normal_logpdf_ps(mxf_handle h, int dtype, int S, int64_t n, const void* x, const void* mean, int64_t n_mean,
+                                    int64_t strideS_mean, const void* var, int64_t n_var, int64_t strideS_var, double scale, void* out_acc,
+                                    void* stream) {
+    if (h && n > 0 && S > 0 && !out_acc) MXF_FAIL(h, -2, "mxf_normal_logpdf_ps: null out");
+    const UniArgs u = {S, n, x, mean, n_mean, strideS_mean, var, n_var, strideS_var, scale, nullptr, 0, 0, out_acc, nullptr, nullptr, nullptr};
+    return normal_ps_run(h, "mxf_normal_logpdf_ps", dtype, u, UNI_PER_SAMPLE, stream);
+}
+
+extern "C" int mxf_normal_logpdf_ps_bwd(mxf_handle h, int dtype, int S, int64_t n, const void* x, const void* mean, int64_t n_mean,
+                                        int64_t strideS_mean, const void* var, int64_t n_var, int64_t strideS_var, const void* w, double scale,
+                                        void* dx_acc, void* dmean_acc, void* dvar_acc, void* stream) {
+    if (h && n > 0 && S > 0 && !w) MXF_FAIL(h, -2, "mxf_normal_logpdf_ps_bwd: null weights");
+    const UniArgs u = {S, n, x, mean, n_mean, strideS_mean, var, n_var, strideS_var, scale, w, 1, 0, nullptr, dx_acc, dmean_acc, dvar_acc};
+    return normal_ps_run(h, "mxf_normal_logpdf_ps_bwd", dtype, u, UNI_REDUCED, stream);
 }
 
 extern "C" int mxf_adam_step(mxf_handle h, int dtype, int64_t n, void* w, const void* g, void* m, void* v, double lr, double beta1,

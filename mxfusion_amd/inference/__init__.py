@@ -2,6 +2,7 @@ from .inference import Inference, TransferInference  # noqa: F401
 from .grad_based_inference import GradBasedInference, GradTransferInference  # noqa: F401
 from .inference_alg import InferenceAlgorithm, SamplingAlgorithm  # noqa: F401
 from .variational import VariationalInference, StochasticVariationalInference  # noqa: F401
+from .score_function import ScoreFunctionInference, ScoreFunctionRBInference  # noqa: F401
 from .map import MAP  # noqa: F401
 from .meanfield import create_Gaussian_meanfield  # noqa: F401
 from .batch_loop import BatchInferenceLoop, DistributedBatchInferenceLoop  # noqa: F401

@@ -162,6 +162,32 @@ class FactorGraph(object):
         obs = {(o.uuid if isinstance(o, Variable) else o) for o in observed}
         return [v for v in self._variables.values() if v.type == VariableType.RANDVAR and v.uuid not in obs]
 
+    def _successor_variables(self, v):
+        """the outputs of every factor that has v among its inputs"""
+        return [o for f in self._factors if any(u.uuid == v.uuid for _, u in f.inputs) for _, o in f.outputs]
+
+    def _predecessor_variables(self, v):
+        f = self._variables.get(v.uuid, v).factor
+        return [u for _, u in f.inputs] if f is not None else []
+
+    def get_descendants(self, node):
+        """factor_graph.py:351-357: the set of the node and every variable reachable from it through the factors of this graph."""
+        seen, todo = {}, [self._variables.get(node.uuid, node)]
+        while todo:
+            v = todo.pop()
+            if v.uuid not in seen:
+                seen[v.uuid] = v
+                todo.extend(self._successor_variables(v))
+        return set(seen.values())
+
+    def get_markov_blanket(self, node):
+        """factor_graph.py:331-349: the node, its predecessors, its successors and those successors' other predecessors."""
+        successors = self._successor_variables(node)
+        blanket = [self._variables.get(node.uuid, node)] + self._predecessor_variables(node) + successors
+        for s in successors:
+            blanket.extend(self._predecessor_variables(s))
+        return set(blanket)
+
     def get_parameters(self, excluded=None, include_inherited=True):
         excluded = excluded or set()
         out = []
@@ -200,6 +226,35 @@ class FactorGraph(object):
                     module_targets = [v.uuid for _, v in f.outputs if v.uuid in targets]
                 if len(module_targets) > 0:
                     logL = logL + expectation(F, f.log_pdf(F=F, variables=variables, targets=module_targets)).sum()
+            else:
+                raise ModelSpecificationError("There is an object in the factor graph that isn't a factor.")
+        return logL
+
+    def log_pdf_per_sample(self, F, variables, targets=None):
+        """(S,) log-density of each sample: the factor walk and the `targets` rule of log_pdf without its mean over the samples -- what a
+        score-function estimator weights sample by sample.  (No reference counterpart: factor_graph.py:223 reduces every factor to one
+        scalar.)  A Module contributes the (S,) vector its log_pdf returns; a factor whose value has sample extent 1 is broadcast."""
+        from ..components.distributions.distribution import Distribution
+        from ..components.functions.function_evaluation import FunctionEvaluation
+        from ..modules.module import Module
+        if targets is not None:
+            targets = {t.uuid if isinstance(t, Variable) else t for t in targets}
+        logL = 0.
+        for f in self.ordered_factors:
+            if isinstance(f, FunctionEvaluation):
+                outcome = f.eval(F=F, variables=variables, always_return_tuple=True)
+                for v, (_, ov) in zip(outcome, f.outputs):
+                    variables[ov.uuid] = v
+            elif isinstance(f, Distribution):
+                if targets is None or f.random_variable.uuid in targets:
+                    logL = logL + f.log_pdf_per_sample(F=F, variables=variables)
+            elif isinstance(f, Module):
+                if targets is None:
+                    module_targets = [v.uuid for _, v in f.outputs if v.uuid in variables]
+                else:
+                    module_targets = [v.uuid for _, v in f.outputs if v.uuid in targets]
+                if len(module_targets) > 0:
+                    logL = logL + f.log_pdf(F=F, variables=variables, targets=module_targets).reshape(-1)
             else:
                 raise ModelSpecificationError("There is an object in the factor graph that isn't a factor.")
         return logL

@@ -441,6 +441,34 @@ def univariate_logpdf_bwd_(kind, x, a, b, cot, scale, dx_acc=None, da_acc=None, 
               _p(b), n_b, ss_b, _p(cot), float(scale), _p(dx_acc), _p(da_acc), _p(db_acc), _stream())
 
 
+def _ps_operands(what, kind, x, a, b, *buffers):
+    """(entry-point prefix, leading arguments, S, n, parameter layouts) of the per-sample log-pdfs: kind 'normal' or a key of D_KIND"""
+    _same_kind(what, x, a, b, *buffers, contiguous=True)
+    S = x.shape[0]
+    n = x.numel() // S
+    lead = (_h(x),) if kind == 'normal' else (_h(x), D_KIND[kind] if isinstance(kind, str) else kind)
+    return ('mxf_normal_logpdf_ps' if kind == 'normal' else 'mxf_univariate_logpdf_ps'), lead + (_dt(x), S, n), S, _uni_param(a, S, n), \
+        _uni_param(b, S, n)
+
+
+def logpdf_per_sample_(kind, x, a, b, scale, out_acc):
+    """out_acc[s] += scale * sum_i log p(x[s,i] | a, b): kind 'normal' (a the mean, b the variance: mxf_normal_logpdf_ps) or a key of D_KIND
+    (mxf_univariate_logpdf_ps); x (S, n...), a and b of 1 or n elements, or S*n (a sample axis of their own); out_acc (S,)."""
+    name, lead, S, (n_a, ss_a), (n_b, ss_b) = _ps_operands('per-sample log-pdf', kind, x, a, b, out_acc)
+    _check_buffers('per-sample log-pdf', (out_acc, (S,)))
+    _lib.call(name, *lead, _p(x), _p(a), n_a, ss_a, _p(b), n_b, ss_b, float(scale), _p(out_acc), _stream())
+    return out_acc
+
+
+def logpdf_per_sample_bwd_(kind, x, a, b, w, scale, dx_acc=None, da_acc=None, db_acc=None):
+    """Reverse mode of logpdf_per_sample_ with the per-sample weights w (S,): dx_acc (S, n...), da_acc, db_acc (shaped like a, b) +=
+    scale * w[s] * d log p / d(.)  (mxf_normal_logpdf_ps_bwd / mxf_univariate_logpdf_ps_bwd)."""
+    name, lead, S, (n_a, ss_a), (n_b, ss_b) = _ps_operands('per-sample log-pdf', kind, x, a, b, w, dx_acc, da_acc, db_acc)
+    _check_buffers('per-sample log-pdf', (w, (S,)), (dx_acc, x.shape), (da_acc, a.shape), (db_acc, b.shape))
+    _lib.call(name + '_bwd', *lead, _p(x), _p(a), n_a, ss_a, _p(b), n_b, ss_b, _p(w), float(scale), _p(dx_acc), _p(da_acc), _p(db_acc),
+              _stream())
+
+
 MVN_MAX_ORDER = 32      # the order up to which the mxf_mvn_* entry points run (MVN_MAX of mvn.hip)
 
 
