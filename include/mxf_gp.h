@@ -312,6 +312,30 @@ int mxf_normal_logpdf(mxf_handle h, int dtype, int S, int64_t n, const void* x,
 int mxf_normal_reparam_bwd(mxf_handle h, int dtype, int S, int64_t n, const void* var, const void* eps,
                            const void* dx, void* dmean_acc, void* dvar_acc, void* stream);
 
+/* x[s,i] = mean[i] + eps[s,i] / sqrt(precision[i]) -- NormalMeanPrecision.draw_samples_impl (normal.py:286-306); the operand layout of
+ * mxf_normal_reparam: mean and precision flat with n elements, eps and x (S, n).  mxf_normal_reparam_prec_bwd is its reverse mode into
+ * caller-zeroed buffers: dmean += sum_s dx ; dprecision += -1/2 sum_s dx * eps * precision^(-3/2); either may be null.                  */
+int mxf_normal_reparam_prec(mxf_handle h, int dtype, int S, int64_t n, const void* mean, const void* precision,
+                            const void* eps, void* x, void* stream);
+int mxf_normal_reparam_prec_bwd(mxf_handle h, int dtype, int S, int64_t n, const void* precision, const void* eps,
+                                const void* dx, void* dmean_acc, void* dprecision_acc, void* stream);
+
+/* Variable transformations of several parameters in one launch (transform.hip): segment k of the flat buffers x, y holds sizes[k]
+ * elements, one segment after the other, and is mapped by kinds[k] with the parameters p0[k], p1[k]:
+ *   MXF_TR_SOFTPLUS  (p0 = offset)                  y = log(1 + exp(x)) + p0,  dy/dx = sigmoid(x)          Softplus (var_trans.py:53-91)
+ *   MXF_TR_LOGISTIC  (p0 = lower, p1 = upper-lower) y = p0 + p1 sigmoid(x),    dy/dx = p1 s (1 - s)        Logistic (var_trans.py:105-147)
+ * kinds, sizes, p0, p1 are HOST arrays of nseg entries read at call time (like the extent arrays of mxf_ewise_fwd): the segment table
+ * travels in the kernel arguments, MXF_TR_MAX_SEG segments per launch (a longer list takes further launches), so a call makes no copy and
+ * captures into a hipGraph.  sigmoid(x) is e / (1 + e) or 1 / (1 + e) with e = exp(-|x|), its slope e / (1 + e)^2 (no s (1 - s)
+ * cancellation); an e below the smallest normal number counts as 0.  A Logistic y is clamped to [lower, upper] rounded inwards to the
+ * working dtype: for |x| large y is the bound and the slope 0.  y is WRITTEN; mxf_transform_bwd adds dy * dy/dx into dx_acc.             */
+enum { MXF_TR_SOFTPLUS = 0, MXF_TR_LOGISTIC = 1 };
+#define MXF_TR_MAX_SEG 32
+int mxf_transform_fwd(mxf_handle h, int dtype, int nseg, const int* kinds, const int64_t* sizes, const double* p0, const double* p1,
+                      const void* x, void* y, void* stream);
+int mxf_transform_bwd(mxf_handle h, int dtype, int nseg, const int* kinds, const int64_t* sizes, const double* p0, const double* p1,
+                      const void* x, const void* dy, void* dx_acc, void* stream);
+
 /* Log-densities of the univariate family, x the random variable, (a, b) the two parameters in the reference's order:
  *   MXF_D_GAMMA     (alpha, beta)      (a-1) log x - b x - lgamma(a) + a log b                      Gamma.log_pdf_impl (gamma.py:45-59)
  *   MXF_D_GAMMA_MV  (mean, variance)   Gamma with b = mean/variance, a = mean b                     GammaMeanVariance (gamma.py:127-159)
@@ -319,13 +343,15 @@ int mxf_normal_reparam_bwd(mxf_handle h, int dtype, int S, int64_t n, const void
  *   MXF_D_LAPLACE   (location, scale)  -log(2b) - |x-a|/b                                           Laplace.log_pdf_impl (laplace.py:37-55)
  *   MXF_D_UNIFORM   (low, high)        -log(b-a) where a <= x < b, else -inf                        Uniform.log_pdf_impl (uniform.py:38-62)
  *   MXF_D_BERNOULLI (prob_true, -)     x log a + (1-x) log(1-a); b is unused, pass a again          Bernoulli.log_pdf_impl (bernoulli.py:62-78)
+ *   MXF_D_NORMAL_PREC (mean, precision)  (log b - log 2 pi) / 2 - b (x-a)^2 / 2                       NormalMeanPrecision.log_pdf_impl (normal.py:266-284)
  * mxf_univariate_logpdf has the contract of mxf_normal_logpdf: out += scale * sum_{s,i} log p(x[s,i] | a[i], b[i]) (factor_graph.py:223),
  * optional reverse mode accumulated into dx (S,n), da (n_a), db (n_b), all scaled by `scale`; n_a, n_b in {1, n}; any output may be null.
  * Gradients are closed forms (digamma for the Gamma and Beta parameters; GAMMA_MV chained to mean and variance; Laplace d/dx =
  * -sign(x-a)/b with sign(0) = 0; Uniform dx = 0, da = 1/(b-a), db = -1/(b-a) inside the support; outside it nothing is added to any
- * gradient, whatever the weight; Bernoulli dx = log a - log(1-a), da = x/a - (1-x)/(1-a), db = 0).  A sum that holds an element outside the Uniform's support is -inf for scale > 0, +inf for scale < 0
+ * gradient, whatever the weight; Bernoulli dx = log a - log(1-a), da = x/a - (1-x)/(1-a), db = 0; NORMAL_PREC dx = -b (x-a), da = b (x-a),
+ * db = (1/b - (x-a)^2) / 2).  A sum that holds an element outside the Uniform's support is -inf for scale > 0, +inf for scale < 0
  * and NaN (0 * inf) for scale == 0.                                                                                                    */
-enum { MXF_D_GAMMA = 0, MXF_D_GAMMA_MV = 1, MXF_D_BETA = 2, MXF_D_LAPLACE = 3, MXF_D_UNIFORM = 4, MXF_D_BERNOULLI = 5 };
+enum { MXF_D_GAMMA = 0, MXF_D_GAMMA_MV = 1, MXF_D_BETA = 2, MXF_D_LAPLACE = 3, MXF_D_UNIFORM = 4, MXF_D_BERNOULLI = 5, MXF_D_NORMAL_PREC = 6 };
 int mxf_univariate_logpdf(mxf_handle h, int kind, int dtype, int S, int64_t n, const void* x,
                           const void* a, int64_t n_a, const void* b, int64_t n_b, double scale,
                           void* out_acc, void* dx_acc, void* da_acc, void* db_acc, void* stream);

@@ -10,7 +10,9 @@ LIB_PATH = os.environ.get('MXF_GP_LIB', os.path.join(_HERE, 'libmxf_gp.so'))   #
 F32, F64 = 0, 1
 K_RBF, K_MATERN12, K_MATERN32, K_MATERN52, K_LINEAR, K_BIAS, K_WHITE = range(7)
 WRITE, ACC_ADD, ACC_MUL = 0, 1, 2
-D_GAMMA, D_GAMMA_MV, D_BETA, D_LAPLACE, D_UNIFORM, D_BERNOULLI = range(6)
+D_GAMMA, D_GAMMA_MV, D_BETA, D_LAPLACE, D_UNIFORM, D_BERNOULLI, D_NORMAL_PREC = range(7)
+TR_SOFTPLUS, TR_LOGISTIC = range(2)
+TR_MAX_SEG = 32            # MXF_TR_MAX_SEG: segments per launch; a longer list takes further launches inside the call
 ACT_IDENTITY, ACT_TANH, ACT_RELU, ACT_SIGMOID = range(4)
 DENSE_MAX_WIDTH = 128
 EW_ADD, EW_SUBTRACT, EW_MULTIPLY, EW_DIVIDE, EW_POWER, EW_SQUARE, EW_EXP, EW_LOG = range(8)
@@ -21,6 +23,7 @@ RED_SUM, RED_MEAN, RED_PROD = range(3)
 _c = ctypes
 _vp, _i, _i64, _d = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_double
 _p64 = _c.POINTER(_c.c_int64)          # a host array of extents or strides
+_pi, _pd = _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)       # host arrays of a segment table
 
 # name -> argtypes (after the handle); every entry point include/mxf_gp.h declares is listed here
 SIGNATURES = {
@@ -66,6 +69,10 @@ SIGNATURES = {
     'mxf_reduce_fwd': [_i, _i, _i64, _i64, _i64, _vp, _vp, _vp],
     'mxf_reduce_bwd': [_i, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
     'mxf_normal_reparam_bwd': [_i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+    'mxf_normal_reparam_prec': [_i, _i, _i64, _vp, _vp, _vp, _vp, _vp],
+    'mxf_normal_reparam_prec_bwd': [_i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+    'mxf_transform_fwd': [_i, _i, _pi, _p64, _pd, _pd, _vp, _vp, _vp],
+    'mxf_transform_bwd': [_i, _i, _pi, _p64, _pd, _pd, _vp, _vp, _vp, _vp],
     'mxf_adam_step': [_i, _i64, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _d, _i, _vp],
     'mxf_sgd_step': [_i, _i64, _vp, _vp, _vp, _d, _d, _d, _d, _vp],
     'mxf_opt_step': [_i, _i, _i64, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _d, _vp],

@@ -1,5 +1,5 @@
 from .distribution import Distribution  # noqa: F401
-from .normal import Normal  # noqa: F401
+from .normal import Normal, NormalMeanPrecision  # noqa: F401
 from .pointmass import PointMass  # noqa: F401
 from .univariate import UnivariateDistribution  # noqa: F401
 from .gamma import Gamma, GammaMeanVariance  # noqa: F401

@@ -1,12 +1,14 @@
 """Normal distribution (mxfusion/components/distributions/normal.py:24-116).  log_pdf and reparameterised
 sampling run as HIP kernels (mxf_normal_logpdf / mxf_normal_reparam, elementwise.hip) with fused reverse
-mode; this is q(X) and p(X) of the Monte-Carlo ELBO path."""
+mode; this is q(X) and p(X) of the Monte-Carlo ELBO path.  NormalMeanPrecision (normal.py:239-329) is the kind 'normal_prec' of the
+univariate family (mxf_univariate_logpdf*) with a draw of its own (mxf_normal_reparam_prec)."""
 import torch
 
 from ... import ops
 from . import _fused
 from ._fused import _carve
 from .distribution import Distribution
+from .univariate import UnivariateDistribution
 from ..variables.variable import Variable
 
 
@@ -51,6 +53,23 @@ class _NormalReparamFn(torch.autograd.Function):
         dm, dv = _carve([var.numel()] * 2, var)
         ops.normal_reparam_bwd_(var.reshape(-1), eps, dx.contiguous(), dm, dv)
         return dm.reshape(ms), dv.reshape(vs), None
+
+
+class _NormalReparamPrecFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mean, precision, eps):
+        ctx.save_for_backward(precision, eps)
+        ctx.shapes = (mean.shape, precision.shape)
+        return ops.normal_reparam_prec(mean.reshape(-1), precision.reshape(-1), eps)
+
+    @staticmethod
+    def backward(ctx, dx):
+        precision, eps = ctx.saved_tensors
+        ms, ps = ctx.shapes
+        dm, dp = _carve([precision.numel() if w else 0 for w in ctx.needs_input_grad[:2]], precision)
+        if dm is not None or dp is not None:
+            ops.normal_reparam_prec_bwd_(precision.reshape(-1), eps, dx.contiguous(), dm, dp)
+        return None if dm is None else dm.reshape(ms), None if dp is None else dp.reshape(ps), None
 
 
 class Normal(Distribution):
@@ -109,5 +128,40 @@ class Normal(Distribution):
     @staticmethod
     def define_variable(mean=0., variance=1., shape=None, rand_gen=None, dtype=None, ctx=None):
         normal = Normal(mean=mean, variance=variance, rand_gen=rand_gen, dtype=dtype, ctx=ctx)
+        normal._generate_outputs(shape=shape)
+        return normal.random_variable
+
+
+class NormalMeanPrecision(UnivariateDistribution):
+    """The normal distribution by mean and precision (normal.py:239-329): the likelihood of the conjugate Gamma-prior-on-precision model.
+    log-pdf on mxf_univariate_logpdf*, times `log_pdf_scaling` as in the reference."""
+    _kind = 'normal_prec'
+    _scaled = True
+
+    def __init__(self, mean, precision, rand_gen=None, dtype=None, ctx=None):
+        super(NormalMeanPrecision, self).__init__(inputs=[('mean', mean), ('precision', precision)], outputs=None,
+                                                  input_names=['mean', 'precision'], output_names=['random_variable'],
+                                                  rand_gen=rand_gen, dtype=dtype, ctx=ctx)
+
+    def log_pdf_impl(self, mean, precision, random_variable, F=None):
+        """normal.py:266-284."""
+        return self._log_pdf(mean, precision, random_variable)
+
+    def draw_samples_impl(self, mean, precision, rv_shape, num_samples=1, F=None):
+        """normal.py:286-306: mean + eps / sqrt(precision), differentiable in both parameters."""
+        out_shape = (num_samples,) + tuple(rv_shape)
+        eps = self._rand_gen.sample_normal(shape=out_shape, **self._sample_inputs(mean))
+        if mean.shape[0] == 1 and precision.shape[0] == 1:
+            n = 1
+            for s in rv_shape:
+                n *= int(s)
+            m = mean[0].expand(tuple(rv_shape)).contiguous() if mean.numel() != n else mean[0]
+            p = precision[0].expand(tuple(rv_shape)).contiguous() if precision.numel() != n else precision[0]
+            return _NormalReparamPrecFn.apply(m, p, eps.reshape(num_samples, -1).contiguous()).reshape(out_shape)
+        return eps / torch.sqrt(precision) + mean
+
+    @staticmethod
+    def define_variable(mean=0., precision=1., shape=None, rand_gen=None, dtype=None, ctx=None):
+        normal = NormalMeanPrecision(mean=mean, precision=precision, rand_gen=rand_gen, dtype=dtype, ctx=ctx)
         normal._generate_outputs(shape=shape)
         return normal.random_variable

@@ -4,7 +4,7 @@
 // allows, grid-stride, one atomic per block for the scalar sums.
 //
 // Replaces: PositiveTransformation (components/variables/var_trans.py:63-91), Normal.log_pdf_impl /
-// draw_samples_impl (components/distributions/normal.py:52-92) + the sum(mean_S(.)) of
+// draw_samples_impl (components/distributions/normal.py:52-92), NormalMeanPrecision.draw_samples_impl (normal.py:286-306) + the sum(mean_S(.)) of
 // models/factor_graph.py:223, and gluon.Trainer.step(adam) of inference/batch_loop.py:46-60.  The per-sample Normal (mxf_normal_logpdf_ps*)
 // is the Normal kind of the kernels in unidist.h.
 #include "common.h"
@@ -53,6 +53,32 @@ __global__ void reparam_bwd_kernel(int S, int64_t n, const T* __restrict__ var, 
         }
         if (dmean) dmean[i] += gm;
         if (dvar) dvar[i] += gv * (T)0.5 / sqrt(var[i]);
+    }
+}
+
+// the draw by mean and precision: x = mean + eps / sqrt(precision)
+template <typename T>
+__global__ void reparam_prec_kernel(int S, int64_t n, const T* __restrict__ mean, const T* __restrict__ prec, const T* __restrict__ eps,
+                                    T* __restrict__ x) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const T m = mean[i], isd = (T)1 / sqrt(prec[i]);
+        for (int s = 0; s < S; ++s) x[(int64_t)s * n + i] = fma(eps[(int64_t)s * n + i], isd, m);
+    }
+}
+
+// d x / d precision = -eps precision^(-3/2) / 2
+template <typename T>
+__global__ void reparam_prec_bwd_kernel(int S, int64_t n, const T* __restrict__ prec, const T* __restrict__ eps, const T* __restrict__ dx,
+                                        T* __restrict__ dmean, T* __restrict__ dprec) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        T gm = 0, gp = 0;
+        for (int s = 0; s < S; ++s) {
+            const T g = dx[(int64_t)s * n + i];
+            gm += g;
+            gp = fma(g, eps[(int64_t)s * n + i], gp);
+        }
+        if (dmean) dmean[i] += gm;
+        if (dprec) { const T p = prec[i]; dprec[i] += gp * (T)-0.5 / (p * sqrt(p)); }
     }
 }
 
@@ -200,6 +226,28 @@ extern "C" int mxf_normal_reparam_bwd(mxf_handle h, int dtype, int S, int64_t n,
     DISPATCH(h, dtype, "mxf_normal_reparam_bwd",
              hipLaunchKernelGGL((reparam_bwd_kernel<float>), dim3(grid_for(n)), dim3(256), 0, st, S, n, (const float*)var, (const float*)eps, (const float*)dx, (float*)dmean_acc, (float*)dvar_acc),
              hipLaunchKernelGGL((reparam_bwd_kernel<double>), dim3(grid_for(n)), dim3(256), 0, st, S, n, (const double*)var, (const double*)eps, (const double*)dx, (double*)dmean_acc, (double*)dvar_acc));
+}
+
+extern "C" int mxf_normal_reparam_prec(mxf_handle h, int dtype, int S, int64_t n, const void* mean, const void* precision, const void* eps,
+                                       void* x, void* stream) {
+    if (!h) return -1;
+    if (n <= 0 || S <= 0) return 0;
+    if (!mean || !precision || !eps || !x) MXF_FAIL(h, -2, "mxf_normal_reparam_prec: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    DISPATCH(h, dtype, "mxf_normal_reparam_prec",
+             hipLaunchKernelGGL((reparam_prec_kernel<float>), dim3(grid_for(n)), dim3(256), 0, st, S, n, (const float*)mean, (const float*)precision, (const float*)eps, (float*)x),
+             hipLaunchKernelGGL((reparam_prec_kernel<double>), dim3(grid_for(n)), dim3(256), 0, st, S, n, (const double*)mean, (const double*)precision, (const double*)eps, (double*)x));
+}
+
+extern "C" int mxf_normal_reparam_prec_bwd(mxf_handle h, int dtype, int S, int64_t n, const void* precision, const void* eps, const void* dx,
+                                           void* dmean_acc, void* dprecision_acc, void* stream) {
+    if (!h) return -1;
+    if (n <= 0 || S <= 0) return 0;
+    if (!precision || !eps || !dx) MXF_FAIL(h, -2, "mxf_normal_reparam_prec_bwd: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    DISPATCH(h, dtype, "mxf_normal_reparam_prec_bwd",
+             hipLaunchKernelGGL((reparam_prec_bwd_kernel<float>), dim3(grid_for(n)), dim3(256), 0, st, S, n, (const float*)precision, (const float*)eps, (const float*)dx, (float*)dmean_acc, (float*)dprecision_acc),
+             hipLaunchKernelGGL((reparam_prec_bwd_kernel<double>), dim3(grid_for(n)), dim3(256), 0, st, S, n, (const double*)precision, (const double*)eps, (const double*)dx, (double*)dmean_acc, (double*)dprecision_acc));
 }
 
 extern "C" int mxf_normal_logpdf(mxf_handle h, int dtype, int S, int64_t n, const void* x, const void* mean, int64_t n_mean,

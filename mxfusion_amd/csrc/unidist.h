@@ -1,5 +1,5 @@
 // The elementwise two-parameter log-densities (gfx950) that univariate.hip (Gamma, Gamma by mean and variance, Beta, Laplace, Uniform,
-// Bernoulli) and elementwise.hip (the per-sample Normal) are built from: one evaluation struct per kind, the three kernels over it and
+// Bernoulli, Normal by mean and precision) and elementwise.hip (the per-sample Normal) are built from: one evaluation struct per kind, the three kernels over it and
 // their launcher.  Everything is in an unnamed namespace: each file instantiates the kinds of its own entry points and nothing is shared
 // at link time.
 #pragma once
@@ -19,7 +19,7 @@ struct UniDist {
     T a, b;         // GAMMA_MV: the (alpha, beta) that the mean and variance stand for
     T c;            // the terms of log p without x
     T ca, cb;       // d c / d a, d c / d b
-    T inv;          // LAPLACE 1/scale, UNIFORM 1/(high - low), GAMMA_MV and NORMAL 1/variance
+    T inv;          // LAPLACE 1/scale, UNIFORM 1/(high - low), GAMMA_MV and NORMAL 1/variance, NORMAL_PREC 1/precision (with grad only)
 
     __device__ __forceinline__ void set(T pa, T pb, bool grad) {
         a = pa; b = pb; ca = cb = inv = 0;
@@ -39,6 +39,9 @@ struct UniDist {
         } else if constexpr (KIND == MXF_D_NORMAL_) {    // the terms of normal_logpdf_kernel (elementwise.hip)
             inv = (T)1 / b;
             c = (T)(-0.5 * 1.8378770664093453) - (T)0.5 * log(b);
+        } else if constexpr (KIND == MXF_D_NORMAL_PREC) {
+            if (grad) inv = (T)1 / b;
+            c = (T)0.5 * log(b) - (T)(0.5 * 1.8378770664093453);
         } else {
             inv = (T)1 / (b - a);
             c = -log(b - a);
@@ -81,6 +84,12 @@ struct UniDist {
             gx = -d * inv;
             ga = d * inv;
             gb = (T)0.5 * (d * d * inv * inv - inv);
+        } else if constexpr (KIND == MXF_D_NORMAL_PREC) {
+            const T d = x - a;
+            lp = c - (T)0.5 * b * d * d;
+            gx = -b * d;
+            ga = b * d;
+            gb = (T)0.5 * (inv - d * d);
         } else {
             const bool in = a <= x && x < b;
             lp = in ? c : -(T)INFINITY;

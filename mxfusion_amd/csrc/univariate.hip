@@ -1,10 +1,11 @@
-// Log-densities of the univariate family (gfx950): Gamma, Gamma by mean and variance, Beta, Laplace, Uniform, Bernoulli.  Built like
+// Log-densities of the univariate family (gfx950): Gamma, Gamma by mean and variance, Beta, Laplace, Uniform, Bernoulli, Normal by mean
+// and precision.  Built like
 // normal_logpdf_kernel (elementwise.hip): thread i owns element i for all S samples, per-element parameter gradients need no atomics,
 // single-element parameters are block-reduced, one atomic per workgroup per scalar.  Launch-bound at the sizes of a prior.
 //
 // Replaces: Gamma / GammaMeanVariance.log_pdf_impl (components/distributions/gamma.py:45-59, :127-159), Beta.log_pdf_impl
 // (beta.py:46-68), Laplace.log_pdf_impl (laplace.py:37-55), Uniform.log_pdf_impl (uniform.py:38-62), Bernoulli.log_pdf_impl
-// (bernoulli.py:62-78) + the sum(mean_S(.)) of
+// (bernoulli.py:62-78), NormalMeanPrecision.log_pdf_impl (normal.py:266-284) + the sum(mean_S(.)) of
 // models/factor_graph.py:223, and MXNet autograd through them.  The evaluation struct and the kernels are in unidist.h, which the per-sample
 // Normal of elementwise.hip shares; mxf_univariate_logpdf_ps* are the per-sample sums of the score-function estimators (no reference
 // counterpart: inference/score_function.py:70-77 multiplies two scalars that are sample means already).
@@ -20,6 +21,7 @@ void launch(int kind, const UniArgs& u, int mode, hipStream_t st) {
         case MXF_D_BETA: uni_launch_kind<T, MXF_D_BETA>(u, mode, st); break;
         case MXF_D_LAPLACE: uni_launch_kind<T, MXF_D_LAPLACE>(u, mode, st); break;
         case MXF_D_BERNOULLI: uni_launch_kind<T, MXF_D_BERNOULLI>(u, mode, st); break;
+        case MXF_D_NORMAL_PREC: uni_launch_kind<T, MXF_D_NORMAL_PREC>(u, mode, st); break;
         default: uni_launch_kind<T, MXF_D_UNIFORM>(u, mode, st); break;
     }
 }
@@ -28,7 +30,7 @@ void launch(int kind, const UniArgs& u, int mode, hipStream_t st) {
 int run(mxf_handle h, const char* name, int kind, int dtype, const UniArgs& u, int mode, void* stream) {
     if (!h) return -1;
     if (u.n <= 0 || u.S <= 0) return 0;
-    if (kind < MXF_D_GAMMA || kind > MXF_D_BERNOULLI) MXF_FAIL(h, -2, "%s: unknown distribution kind %d", name, kind);
+    if (kind < MXF_D_GAMMA || kind > MXF_D_NORMAL_PREC) MXF_FAIL(h, -2, "%s: unknown distribution kind %d", name, kind);
     if (const int rc = uni_check(h, name, dtype, u)) return rc < 0 ? rc : 0;
     if (dtype == MXF_F32) launch<float>(kind, u, mode, (hipStream_t)stream);
     else launch<double>(kind, u, mode, (hipStream_t)stream);

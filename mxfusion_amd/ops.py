@@ -383,6 +383,60 @@ def normal_reparam_bwd_(var, eps, dx, dmean_acc, dvar_acc):
               _p(dmean_acc), _p(dvar_acc), _stream())
 
 
+def normal_reparam_prec(mean, precision, eps):
+    """x[s] = mean + eps[s] / sqrt(precision); mean/precision (n...), eps (S, n...)  (mxf_normal_reparam_prec)."""
+    _same_kind('normal_reparam_prec', eps, mean, precision)
+    mean, precision, eps = _c(mean), _c(precision), _c(eps)
+    n = eps.numel() // eps.shape[0] if eps.shape[0] else 0
+    if mean.numel() != n or precision.numel() != n:
+        raise ValueError('normal_reparam_prec: mean and precision have the %d elements of one sample of eps; got %d and %d'
+                         % (n, mean.numel(), precision.numel()))
+    x = torch.empty_like(eps)
+    _lib.call('mxf_normal_reparam_prec', _h(eps), _dt(eps), eps.shape[0], n, _p(mean), _p(precision), _p(eps), _p(x), _stream())
+    return x
+
+
+def normal_reparam_prec_bwd_(precision, eps, dx, dmean_acc, dprecision_acc):
+    """Reverse mode of normal_reparam_prec, added into the (n,) buffers; either may be None (mxf_normal_reparam_prec_bwd)."""
+    _same_kind('normal_reparam_prec', eps, precision, dx, dmean_acc, dprecision_acc)
+    n = precision.numel()
+    if eps.numel() != eps.shape[0] * n or dx.numel() != eps.numel():
+        raise ValueError('normal_reparam_prec: eps and dx are (S, n) for a precision of n = %d elements' % n)
+    _check_buffers('normal_reparam_prec', (dmean_acc, (n,)), (dprecision_acc, (n,)))
+    _lib.call('mxf_normal_reparam_prec_bwd', _h(eps), _dt(eps), eps.shape[0], n, _p(_c(precision)), _p(_c(eps)), _p(_c(dx)),
+              _p(dmean_acc), _p(dprecision_acc), _stream())
+
+
+TR_KIND = {'softplus': _lib.TR_SOFTPLUS, 'logistic': _lib.TR_LOGISTIC}
+
+
+def _transform_table(what, segments, x, *others):
+    """the host arrays of a segment table; segments: (kind, size, p0, p1) per segment of the flat x, one after the other"""
+    _same_kind(what, x, *others, contiguous=True)
+    n = len(segments)
+    kinds = (_lib._c.c_int * n)(*[TR_KIND[k] if isinstance(k, str) else int(k) for k, _, _, _ in segments])
+    sizes = (_lib._c.c_int64 * n)(*[int(s) for _, s, _, _ in segments])
+    if min(sizes, default=0) < 0 or sum(sizes) != x.numel() or any(t.numel() != x.numel() for t in others):
+        raise ValueError('%s: the segment sizes must add up to the %d elements of every buffer' % (what, x.numel()))
+    return n, kinds, sizes, (_lib._c.c_double * n)(*[float(p) for _, _, p, _ in segments]), \
+        (_lib._c.c_double * n)(*[float(p) for _, _, _, p in segments])
+
+
+def transform(segments, x):
+    """y, shaped like the contiguous x: segment k of the flat x mapped by its kind -- 'softplus' (p0 the offset) or 'logistic' (p0 the lower
+    bound, p1 = upper - lower); segments: (kind, size, p0, p1) each.  One launch per _lib.TR_MAX_SEG segments (mxf_transform_fwd)."""
+    y = torch.empty_like(x)
+    _lib.call('mxf_transform_fwd', _h(x), _dt(x), *_transform_table('transform', segments, x, y), _p(x), _p(y), _stream())
+    return y
+
+
+def transform_bwd_(segments, x, dy, dx_acc):
+    """dx_acc += dy * (d transform / d x), segment by segment (mxf_transform_bwd)."""
+    _lib.call('mxf_transform_bwd', _h(x), _dt(x), *_transform_table('transform', segments, x, dy, dx_acc), _p(x), _p(dy), _p(dx_acc),
+              _stream())
+    return dx_acc
+
+
 def normal_logpdf_(x, mean, var, scale, out_acc, dx_acc=None, dmean_acc=None, dvar_acc=None):
     """out_acc += scale * sum_{s,i} log N(x[s,i]|mean[i],var[i]) (+ reverse mode into the *_acc buffers)."""
     x, mean, var = _c(x), _c(mean), _c(var)
@@ -394,7 +448,7 @@ def normal_logpdf_(x, mean, var, scale, out_acc, dx_acc=None, dmean_acc=None, dv
 
 
 D_KIND = {'gamma': _lib.D_GAMMA, 'gamma_mv': _lib.D_GAMMA_MV, 'beta': _lib.D_BETA, 'laplace': _lib.D_LAPLACE, 'uniform': _lib.D_UNIFORM,
-          'bernoulli': _lib.D_BERNOULLI}
+          'bernoulli': _lib.D_BERNOULLI, 'normal_prec': _lib.D_NORMAL_PREC}
 
 
 def _uni_param(p, S, n):
