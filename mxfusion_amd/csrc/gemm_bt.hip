@@ -1,5 +1,7 @@
 // f16x2 split product whose second operand is stored K-MAJOR:  C (M x N) = alpha * A (M x K) * Bt (K x N),  f32-equivalent accuracy
-// (two scaled f16 terms per operand, three v_mfma_f32_32x32x16_f16 products: gemm_split.hip's format and arithmetic).
+// (two scaled f16 terms per operand and three f16 MFMA products per fragment pair -- hi' lo, lo' hi, hi' hi: gemm_split.hip's format; since r07
+// on v_mfma_f32_16x16x32_f16, where gemm_split.hip multiplies with v_mfma_f32_32x32x16_f16: the 32 products of one instruction are summed inside
+// the pipe, so the two kernels agree to rounding, not bit for bit).
 //
 // Why (r06): the SVGP training call (svgp_regression.py:85-90) needs Kuf twice -- as the (m, k = n) operand of Psi2 = Kuf Kuf^T and as the
 // (n, k = m) operand of T = H0 Kuf -- and until r05 wrote it twice, 8.6 GB of planes each; the second pass (1.8 ms, HBM-write bound) sat
@@ -8,16 +10,30 @@
 // wants, per lane, eight CONSECUTIVE k of one column n; the tile has them 32 bytes apart.  gfx950's transposing LDS read does the turn:
 //   * LDS-DMA (global_load_lds_dwordx4, lane-linear destination, free per-lane source) builds an image of 128-byte chunks [4 k][16 n];
 //   * ds_read_b64_tr_b16: within a 16-lane group lane p ADDRESSES row p / 4, columns 4 (p % 4) .. + 3 of a chunk and RECEIVES column p of
-//     its four rows -- two reads give the lane its eight k.  The chunks of one instruction's four lane groups are consecutive (512
-//     contiguous bytes per instruction: conflict free).
-// A (shared by the workgroup's eight waves) goes through LDS exactly as in gemm_split.hip's 256 x 256 kernel; so does Bt now, which ends
-// that kernel's per-wave register ring of B fragments (48 registers) and its eight-fold redundant fragment fetch.  Four-slot ring of
-// (A 16 KB + Bt 16 KB), requests three k blocks ahead as one stream ACROSS work items, one barrier per k block, every load an LDS-DMA
-// request (4 per thread and k block).  What bounds it, and the alternatives that were measured: DESIGN.md section 4.2.
+//     its four rows -- two reads give the lane its eight k.
+// A (shared by the workgroup's eight waves) and Bt both go through LDS, every load an LDS-DMA request, as one stream ACROSS work items.
+//
+// Why the 16x16x32 shape (r07): on the 32x32x16 shape this kernel was bound by the clock the chip holds under the instruction mix (DESIGN.md
+// section 4.2: busy x clock constant over three structures, all-zero operands 18.5 % faster on the same binary).  Same tiles, same request
+// stream, same LDS bytes per flop (24 16-byte reads per wave and 32 k) on the K = 32 shape: 10.5 against 11.3 ms on the T shape, same box,
+// alternating (profiles/r07_bt_shape_ab.txt).  What the instruction forces:
+//   * an MFMA consumes TWO consecutive 16-k blocks (lane = column / row lane % 16, k group lane / 16: lanes 0-31 take the first block,
+//     lanes 32-63 the second), so the ring is two PAIR slots of (2 blocks x (A 16 KB + Bt 16 KB)) and a stream position is a pair of blocks;
+//   * A image: unit = 2 row + k half, NO swizzle (ds_read_b128 serves lanes {0-3, 12-15, 20-27} | {4-11, 16-19, 28-31} | the same + 32 in one
+//     cycle each: with lane = 16 (k half) + row the plain image puts each group on 16 distinct units modulo 16; the XOR of gemm_split.hip's
+//     32-row fragments would make it 2-way);
+//   * Bt image: chunk c = (n16 block c >> 2, read h = (c >> 1) & 1, k half c & 1) holds k = 8 (c & 1) + 4 h + 0..3: the two chunks of a
+//     32-lane half of one ds_read_b64_tr_b16 are neighbours (256 contiguous bytes: conflict free), lanes 32-63 read the same place of
+//     the pair's second block;
+//   * requests: a pair (8 per thread) goes out in the MIDDLE of a step, behind a barrier that follows the step's last fragment read, into
+//     the slot that step is reading -- two slots hold up to two pairs (128 KB) in flight or unread, and a pair has the rest of that step and the
+//     whole next one to land (the r06 ring of four 16-k slots: three blocks = 96 KB, three block times).  Two barriers per pair, as before;
+//   * an item with an odd number of blocks ends in a PEELED step whose second block is a second request for its last block (nothing past
+//     K16 is read, the request count per step stays 8) and whose Bt fragments are zeroed in lanes 32-63: those products add exactly 0.
 //
 // U (optional, P = 1 of the SVGP call): the row  U[n] = uscale * sum_k w[k] Bt[k][n]  rides on the fragments that are in registers anyway:
 // for every column strip ONE of its tm row-tile workgroups (rotating) also forms v_dot2_f32_f16 sums of its Bt fragments with the f16
-// hi / lo planes of w (three products, like the MFMAs), its two row halves taking alternate k blocks.  (Until r05 U was a by-product of the
+// hi / lo planes of w (three products, like the MFMAs), its two row halves taking alternate block pairs.  (Until r05 U was a by-product of the
 // second planes pass; every other pass over Kuf happens before w exists.)
 #include "common.h"
 #include "internal.h"
@@ -63,24 +79,24 @@ __device__ __forceinline__ float bt_dot8(u32x4 a, u32x4 b, float acc) {
 
 constexpr int BT_KMAX16 = 128;           // U row: w planes of up to 2048 k live in LDS
 
-// 256 x 256 tile, 512 threads: wave = 4 h + w owns rows [128 h, + 128) x columns [64 w, + 64) = 4 x 2 MFMA tiles (128 accumulators).
+// 256 x 256 tile, 512 threads: wave = 4 h + w owns rows [128 h, + 128) x columns [64 w, + 64) = 8 x 4 MFMA tiles of 16 x 16 (128 accumulators).
 template <bool WU>
 __global__ __launch_bounds__(512, 2) void gemm_f16x2_bt_kernel(BtArgs g) {
     constexpr int NU = 512;                          // 16-byte units of one plane's (256 x 16) slab
-    __shared__ u32x4 sA[4][2][NU];                   // [ring slot][plane][unit]: A rows, gemm_split.hip's swizzled image
-    __shared__ u32x4 sB[4][2][NU];                   // Bt: chunk c = ((wq * 2 + y) * 2 + h) * 4 + grp of 128 bytes [4 k][16 n]
-    __shared__ u32x4 sW[WU ? 2 * BT_KMAX16 * 2 : 1]; // w planes [plane][16 K16 halves]
+    __shared__ u32x4 sA[2][2][2][NU];                // [pair slot][block of the pair][plane][unit]: A rows, unit = 2 row + k half
+    __shared__ u32x4 sB[2][2][2][NU];                // Bt: chunk c = (nb * 2 + h) * 2 + k half of 128 bytes [4 k][16 n]
+    __shared__ u32x4 sW[WU ? 2 * BT_KMAX16 * 2 : 1]; // w planes [plane][16 K16 halves], zero up to a whole pair
     __shared__ float sU[WU ? 512 : 1];               // the two row halves' shares of U for the item's 256 columns
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wq = wave & 3, wh = wave >> 2;
-    const int li = lane & 31, lk = lane >> 5;
+    const int lj = lane & 15, lg = lane >> 4;        // row / column inside a 16 x 16 tile; k group (8 k) of the pair's 32
     int patience = 2;
     float cmax = 0.f;
     if constexpr (WU) {
         if (g.uout) {
-            const int nunits = (int)(g.K16 * 2);          // 16-byte units per plane
-            for (int i = tid; i < 2 * nunits; i += 512) {
-                const int p = i / nunits, u = i % nunits;
-                sW[p * (BT_KMAX16 * 2) + u] = *reinterpret_cast<const u32x4*>(g.uw + (int64_t)p * g.K16 * 16 + u * 8);
+            const int nunits = (int)(g.K16 * 2), npad = (nunits + 3) & ~3;          // 16-byte units per plane; a tail step reads units of the missing block
+            for (int i = tid; i < 2 * npad; i += 512) {
+                const int p = i / npad, u = i % npad;
+                sW[p * (BT_KMAX16 * 2) + u] = u < nunits ? *reinterpret_cast<const u32x4*>(g.uw + (int64_t)p * g.K16 * 16 + u * 8) : u32x4{0u, 0u, 0u, 0u};
             }
         }
         __syncthreads();
@@ -90,146 +106,141 @@ __global__ __launch_bounds__(512, 2) void gemm_f16x2_bt_kernel(BtArgs g) {
     if (g.maxbits) alpha /= scale_from_maxbits(g.maxbits[0]);
     if (g.maxbits2) alpha /= scale_from_maxbits(g.maxbits2[0]);
 
-    // A: thread t fills unit t of each plane's slab (row t >> 1; the XOR swizzle of the two k halves is applied to the source)
-    const int drow = tid >> 1, dkh = (tid & 1) ^ ((drow >> 3) & 1);
-    // Bt: thread t fills unit t = 8 c + s of the image: chunk c = (wq', y, h, grp), piece s = (row j = s >> 1 of the chunk, n half s & 1)
+    // A: thread t fills unit t of each plane's slab = bytes [16 t, + 16) of the block's 8 KB in memory (row t >> 1, k half t & 1)
+    // Bt: thread t fills unit t = 8 c + s of the image: chunk c, piece s = (row j = s >> 1 of the chunk, n half s & 1)
     const int bc = tid >> 3, bs = tid & 7;
-    const int b_nb = 4 * (bc >> 4) + 2 * ((bc >> 3) & 1) + (bc & 1);              // n16 block inside the strip: 4 wq' + 2 y + (grp & 1)
-    const int b_kl = 8 * ((bc >> 1) & 1) + 4 * ((bc >> 2) & 1) + (bs >> 1);       // k inside the block: 8 (grp >> 1) + 4 h + j
+    const int b_nb = bc >> 2;                                                     // n16 block inside the strip
+    const int b_kl = 8 * (bc & 1) + 4 * ((bc >> 1) & 1) + (bs >> 1);              // k inside the block: 8 (k half) + 4 h + j
     const unsigned voff_b = (unsigned)((((int64_t)b_nb * g.btR + b_kl) * 16 + 8 * (bs & 1)) * 2);      // bytes (host checks 16 btR * 32 < 2^31)
-    const unsigned voff_a = (unsigned)((drow * 16 + dkh * 8) * 2);
-    // fragment reads: A units; Bt byte offset of this lane inside a plane image (instruction (y, h) adds (2 y + h) * 512)
-    // (row = 128 wh + 32 x + li: the swizzle bit (row >> 3) & 1 does not depend on x, so fragment x sits 64 units behind fragment 0 -- one
-    //  address register and immediate offsets)
-    const int ua0_ = lds_unit(128 * wh + li, lk);
-#define ua_(x) (ua0_ + 64 * (x))
-    const unsigned ldsA = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) void*)&sA[0][0][wave * 64]);
-    const unsigned ldsB = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) void*)&sB[0][0][wave * 64]);
-    const unsigned toff_blk = (unsigned)((((int64_t)(4 * wq) * g.M + 128 * wh + li) * 16 + 4 * lk) * 4);      // bytes (host: 16 M * 64 < 2^31)
-    const int rb_h = (wq * 2048 + (lane >> 4) * 128 + ((lane & 15) >> 2) * 32 + (lane & 3) * 8) / 2;      // in halves
+    const unsigned voff_a = (unsigned)(tid * 16);
+    // fragment reads, relative to a pair slot's plane 0: A unit of tile x = 0 (tile x: + 32 units, plane 1: + NU, lanes 32-63: the second block);
+    // Bt byte offset of this lane (instruction (t, h) adds 512 t + 256 h; ds_read_b64_tr_b16: lane 4 q + p of a 16-lane group addresses row q,
+    // columns 4 p .. + 3 of its chunk)
+    const int ua0_ = (128 * wh + lj) * 2 + (lg & 1) + (lg >> 1) * (2 * NU);
+    const unsigned ldsA = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) void*)&sA[0][0][0][wave * 64]);
+    const unsigned ldsB = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) void*)&sB[0][0][0][wave * 64]);
+    const unsigned toff_blk = (unsigned)((((int64_t)(4 * wq) * g.M + 128 * wh + lj) * 16 + 4 * lg) * 4);      // bytes (host: 16 M * 64 < 2^31)
+    const int rb_h = (wq * 2048 + (lg >> 1) * 16384 + (lg & 1) * 128 + (lj >> 2) * 32 + (lj & 3) * 8) / 2;      // in halves
 
-    // One STREAM of k blocks over all of this workgroup's items (blockIdx.x, + gridDim.x, ...): the requests run three blocks ahead of the
-    // multiplies ACROSS item boundaries, so an item's first blocks arrive under the previous item's last multiplies and its epilogue -- a
-    // per-item pipeline fill (two memory latencies with nothing in flight, ~3 % of a K = 1024 item) never happens.  Ring slot = stream
-    // position modulo 4 (the fragments are read from LDS, so nothing here needs a compile-time ring index).
+    // One STREAM of block pairs over all of this workgroup's items (blockIdx.x, + gridDim.x, ...): the requests run ahead of the multiplies
+    // ACROSS item boundaries, so an item's first pairs arrive under the previous item's last multiplies and its epilogue -- a per-item
+    // pipeline fill (two memory latencies with nothing in flight, ~3 % of a K = 1024 item) never happens.  Slot = stream position modulo 2.
     // (32-bit index arithmetic throughout: the 64-bit divisions of a first form expanded to branchy software routines in the per-item paths,
     //  with spill reloads whose compiler-inserted s_waitcnt vmcnt(0) drained the request stream once per item)
-    const int nk = (int)g.K16;
+    const int nk = (int)g.K16, np = (nk + 1) / 2;
     const unsigned nwg = (unsigned)g.nwg, tmu = (unsigned)g.tm;
     const int nit = (int)((nwg - blockIdx.x + gridDim.x - 1) / gridDim.x);
-    const int nsteps = nit * nk;
+    const int nsteps = nit * np;
     const unsigned q8 = nwg / 8, r8 = nwg % 8;
     auto item_of = [&](int i) -> unsigned { return xcd_run_item(blockIdx.x + (unsigned)i * gridDim.x, q8, r8); };
-    // request side
-    int q_it = 0, q_kb = 0;
+    int q_it = 0, q_p = 0;
     unsigned q_slot = 0;
     const unsigned short* qa = nullptr;
     const unsigned short* qb = nullptr;
     auto q_enter = [&]() {
         const unsigned wid = item_of(q_it);
-        const unsigned tn_ = wid / tmu, tm_ = wid - tn_ * tmu;      // the row tiles of one column strip are neighbours
-        qa = g.A + (int64_t)tm_ * 256 * 16;           // wave-uniform bases: SGPRs
+        const unsigned tn_ = wid / tmu, tm_ = wid - tn_ * tmu;
+        qa = g.A + (int64_t)tm_ * 256 * 16;
         qb = g.Bt + ((int64_t)tn_ * 16) * g.btR * 16;
     };
+    // one pair: EIGHT requests per thread, always (an odd item's last pair asks for its one block twice)
     // (inline asm, not __builtin_amdgcn_global_load_lds: with the builtin the compiler tracks the LDS-DMA writes itself and puts an
     //  s_waitcnt vmcnt(0) in front of the fragment reads at the loop header -- it cannot see the counted waits below --, i.e. one full
     //  memory latency per trip with nothing in flight)
     auto q_issue = [&]() {
-        bt_dma16(qa + (int64_t)q_kb * g.M * 16, voff_a, ldsA + q_slot * 16384);
-        bt_dma16(qa + g.pA + (int64_t)q_kb * g.M * 16, voff_a, ldsA + q_slot * 16384 + 8192);
-        bt_dma16(qb + (int64_t)q_kb * 256, voff_b, ldsB + q_slot * 16384);
-        bt_dma16(qb + g.pB + (int64_t)q_kb * 256, voff_b, ldsB + q_slot * 16384 + 8192);
-        q_slot = (q_slot + 1) & 3;
-        if (++q_kb == nk) { q_kb = 0; ++q_it; if (q_it < nit) q_enter(); }
+        const int kb0 = 2 * q_p, kb1 = kb0 + 1 < nk ? kb0 + 1 : kb0;
+        const unsigned la = ldsA + q_slot * 32768, lb = ldsB + q_slot * 32768;
+        bt_dma16(qa + (int64_t)kb0 * g.M * 16, voff_a, la);
+        bt_dma16(qa + g.pA + (int64_t)kb0 * g.M * 16, voff_a, la + 8192);
+        bt_dma16(qb + (int64_t)kb0 * 256, voff_b, lb);
+        bt_dma16(qb + g.pB + (int64_t)kb0 * 256, voff_b, lb + 8192);
+        bt_dma16(qa + (int64_t)kb1 * g.M * 16, voff_a, la + 16384);
+        bt_dma16(qa + g.pA + (int64_t)kb1 * g.M * 16, voff_a, la + 16384 + 8192);
+        bt_dma16(qb + (int64_t)kb1 * 256, voff_b, lb + 16384);
+        bt_dma16(qb + g.pB + (int64_t)kb1 * 256, voff_b, lb + 16384 + 8192);
+        q_slot ^= 1;
+        if (++q_p == np) { q_p = 0; ++q_it; if (q_it < nit) q_enter(); }
     };
-    // all but the block requested last (4 requests) have landed -- this wave's share; the barrier extends it to the workgroup.  (vmcnt
-    // retires in order and counts the epilogue's stores too: a wait behind an epilogue also drains that item's stores -- conservative.)
+    // this wave's share of everything but the youngest NSTR requests has landed; the barrier extends it to the workgroup.  (vmcnt retires in
+    // order and counts the epilogue's stores too: a wait behind an epilogue also drains that item's stores -- conservative.)
 #define BT_WAIT(NSTR) do { asm volatile("s_waitcnt vmcnt(" NSTR ")" ::: "memory"); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); } while (0)
 #define HF(v) __builtin_bit_cast(f16x8, v)
 #define BT_TR(ptr) __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(ptr)))
-    f32x16 c[4][2];
-    float ua0 = 0.f, ua1 = 0.f;
-    int c_kb = 0, c_it = 0;
+    f32x4 c[8][4];
+    float ua[4] = {0.f, 0.f, 0.f, 0.f};
     int64_t m0 = 0, n0 = 0;
     unsigned c_slot = 0;
     bool uitem = false;
-    // FOUR ring slots: the requests run THREE blocks ahead, a step reads its own fragments (Bt + A fragment 0 at the top, the other A
-    // fragments two multiplies ahead of their use).  (r06 PMC of the first form -- three slots, all sixteen fragments read behind the barrier:
-    // matrix pipe 0.54 busy at 1.80 GHz, i.e. stalled, not power-bound; the r05 kernel, whose B fragments sat in a register ring: 0.69 at
-    // 1.56; this form: 0.64 at 1.62.)
-    u32x4 fb0[2][2], fa0[2];
-    u32x4 dga[6];      // the A fragments 1-3 of the current block
-#define BT_READ_B(FB, SLOTV)                                                                                                        \
+    u32x4 fb[4][2];
+#define BT_A(x, p) sa_[(p) * NU + ua0_ + 32 * (x)]
+#define BT_MM(x, AH, AL)                                                                                                           \
     do {                                                                                                                            \
-        _Pragma("unroll") for (int p = 0; p < 2; ++p) {                                                                             \
-            const unsigned short* sb_ = reinterpret_cast<const unsigned short*>(&sB[SLOTV][p][0]) + rb_h;                           \
-            _Pragma("unroll") for (int y = 0; y < 2; ++y) {                                                                         \
-                const u32x2 v0_ = BT_TR(sb_ + (2 * y) * 256), v1_ = BT_TR(sb_ + (2 * y + 1) * 256);                                 \
-                FB[y][p] = u32x4{v0_[0], v0_[1], v1_[0], v1_[1]};                                                                   \
-            }                                                                                                                       \
+        _Pragma("unroll") for (int t = 0; t < 4; ++t) {                                                                             \
+            c[x][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(HF(fb[t][0]), HF(AL), c[x][t], 0, 0, 0);          /* hi' lo */         \
+            c[x][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(HF(fb[t][1]), HF(AH), c[x][t], 0, 0, 0);          /* lo' hi */         \
+            c[x][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(HF(fb[t][0]), HF(AH), c[x][t], 0, 0, 0);          /* hi' hi */         \
         }                                                                                                                           \
-    } while (0)
-#define BT_READ_A0(FA, SLOTV) do { FA[0] = sA[SLOTV][0][ua_(0)]; FA[1] = sA[SLOTV][1][ua_(0)]; } while (0)
-#define BT_MM(x, AH, AL, FB)                                                                                                        \
-    do {                                                                                                                            \
-        _Pragma("unroll") for (int y = 0; y < 2; ++y) {                                                                             \
-            c[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_f16(HF(FB[y][0]), HF(AL), c[x][y], 0, 0, 0);          /* hi' lo */         \
-            c[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_f16(HF(FB[y][1]), HF(AH), c[x][y], 0, 0, 0);          /* lo' hi */         \
-            c[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_f16(HF(FB[y][0]), HF(AH), c[x][y], 0, 0, 0);          /* hi' hi */         \
-        }                                                                                                                           \
-    } while (0)
-    // one stream position: FB / FA receive block s_'s Bt fragments and A fragment 0
-#define BT_STEP(FB, FA)                                                                                                   \
-    do {                                                                                                                            \
-        if (c_kb == 0) {                             /* a new item (workgroup-uniform) */                                           \
-            const unsigned wid = item_of(c_it);                                                                                     \
-            const unsigned tile_n = wid / tmu, tile_m = wid - tile_n * tmu;                                                         \
-            m0 = (int64_t)tile_m * 256; n0 = (int64_t)tile_n * 256;                                                                 \
-            uitem = WU && g.uout != nullptr && ((tile_n + (tile_n >> 3) + (tile_n >> 6)) % tmu) == tile_m;                          \
-            if (g.sync && (c_it % g.sync_every) == 0) wg_rendezvous(g.sync + wid / g.sync_n, (unsigned)g.sync_n, patience);         \
-            _Pragma("unroll") for (int x = 0; x < 4; ++x)                                                                           \
-                _Pragma("unroll") for (int y = 0; y < 2; ++y)                                                                       \
-                    _Pragma("unroll") for (int r = 0; r < 16; ++r) c[x][y][r] = 0.f;                                                \
-            ua0 = 0.f; ua1 = 0.f;                                                                                                   \
-        }                                                                                                                           \
-        const bool more = s_ + 3 < nsteps;                                                                                          \
-        if (more) q_issue();                         /* block s_ + 3 into the slot block s_ - 1 left */                             \
-        asm volatile("" ::: "memory");               /* the fragment reads stay behind the requests */                              \
-        const unsigned nslot = (c_slot + 1) & 3;                                                                                    \
-        BT_READ_B(FB, c_slot);                                                                                                      \
-        BT_READ_A0(FA, c_slot);                                                                                                     \
-        if constexpr (WU) {                                                                                                         \
-            if (uitem && (((int)c_kb & 1) == wh)) {      /* wave-uniform; FIRST: few registers are live here */                        \
-                const u32x4 wh_ = sW[2 * (int)c_kb + lk], wl_ = sW[BT_KMAX16 * 2 + 2 * (int)c_kb + lk];                             \
-                ua0 = bt_dot8(FB[0][1], wh_, ua0); ua0 = bt_dot8(FB[0][0], wl_, ua0); ua0 = bt_dot8(FB[0][0], wh_, ua0);            \
-                ua1 = bt_dot8(FB[1][1], wh_, ua1); ua1 = bt_dot8(FB[1][0], wl_, ua1); ua1 = bt_dot8(FB[1][0], wh_, ua1);            \
-            }                                                                                                                       \
-        }                                                                                                                           \
-        /* the A fragments are requested two multiplies ahead of their use                                                           */ \
-        dga[0] = sA[c_slot][0][ua_(1)]; dga[1] = sA[c_slot][1][ua_(1)]; dga[2] = sA[c_slot][0][ua_(2)]; dga[3] = sA[c_slot][1][ua_(2)];      \
-        u32x4 a1h = dga[0], a1l = dga[1];                                                                                           \
-        u32x4 a2h = dga[2], a2l = dga[3];                                                                                           \
-        BT_MM(0, FA[0], FA[1], FB);                                                                                                 \
         __builtin_amdgcn_sched_barrier(0);           /* (pins the order: the scheduler otherwise hoists every read to the top) */    \
-        dga[4] = sA[c_slot][0][ua_(3)]; dga[5] = sA[c_slot][1][ua_(3)];                                                             \
-        u32x4 a3h = dga[4], a3l = dga[5];                                                                                           \
-        BT_MM(1, a1h, a1l, FB);                                                                                                     \
-        __builtin_amdgcn_sched_barrier(0);                                                                                          \
-        BT_MM(2, a2h, a2l, FB);                                                                                                     \
-        __builtin_amdgcn_sched_barrier(0);                                                                                          \
-        BT_MM(3, a3h, a3l, FB);                                                                                                     \
-        __builtin_amdgcn_sched_barrier(0);                                                                                          \
-        if (more) BT_WAIT("8"); else if (s_ + 2 < nsteps) BT_WAIT("4"); else BT_WAIT("0");      /* block s_ + 1 */                  \
-        c_slot = nslot;                                                                                                             \
-        if (++c_kb == nk) { c_kb = 0; ++c_it; finish_item(); }                                                                      \
-        ++s_;                                                                                                                       \
+    } while (0)
+    // One stream position = pair c_p of the current item, in slot c_slot.  On entry the pair has landed (workgroup-wide) and pair s_ + 1 is
+    // requested; TAIL: the item's last, single block.
+#define BT_STEP(TAIL)                                                                                                              \
+    do {                                                                                                                            \
+        const u32x4* const sa_ = &sA[c_slot][0][0][0];                                                                              \
+        _Pragma("unroll") for (int p = 0; p < 2; ++p) {                                                                             \
+            const unsigned short* sb_ = reinterpret_cast<const unsigned short*>(&sB[c_slot][0][p][0]) + rb_h;                       \
+            _Pragma("unroll") for (int t = 0; t < 4; ++t) {                                                                         \
+                const u32x2 v0_ = BT_TR(sb_ + t * 256), v1_ = BT_TR(sb_ + t * 256 + 128);                                           \
+                fb[t][p] = u32x4{v0_[0], v0_[1], v1_[0], v1_[1]};                                                                   \
+                if (TAIL) fb[t][p] &= kmask;         /* lanes 32-63 hold the copy of the last block: their products must add 0 */   \
+            }                                                                                                                       \
+        }                                                                                                                           \
+        u32x4 a0h = BT_A(0, 0), a0l = BT_A(0, 1), a1h = BT_A(1, 0), a1l = BT_A(1, 1);                                           \
+        if constexpr (WU) {                                                                                                         \
+            if (uitem && ((c_p & 1) == wh)) {        /* wave-uniform; FIRST: few registers are live here */                         \
+                const u32x4 wh_ = sW[4 * c_p + lg], wl_ = sW[BT_KMAX16 * 2 + 4 * c_p + lg];                                         \
+                _Pragma("unroll") for (int t = 0; t < 4; ++t) {                                                                     \
+                    ua[t] = bt_dot8(fb[t][1], wh_, ua[t]); ua[t] = bt_dot8(fb[t][0], wl_, ua[t]); ua[t] = bt_dot8(fb[t][0], wh_, ua[t]); \
+                }                                                                                                                   \
+            }                                                                                                                       \
+        }                                                                                                                           \
+        /* the A fragments are requested two multiplies ahead of their use */                                                       \
+        u32x4 a2h = BT_A(2, 0), a2l = BT_A(2, 1);                                                                                 \
+        BT_MM(0, a0h, a0l);                                                                                                        \
+        u32x4 a3h = BT_A(3, 0), a3l = BT_A(3, 1);                                                                                 \
+        BT_MM(1, a1h, a1l);                                                                                                        \
+        u32x4 a4h = BT_A(4, 0), a4l = BT_A(4, 1);                                                                                 \
+        BT_MM(2, a2h, a2l);                                                                                                        \
+        u32x4 a5h = BT_A(5, 0), a5l = BT_A(5, 1);                                                                                 \
+        BT_MM(3, a3h, a3l);                                                                                                        \
+        u32x4 a6h = BT_A(6, 0), a6l = BT_A(6, 1);                                                                                 \
+        BT_MM(4, a4h, a4l);                                                                                                        \
+        u32x4 a7h = BT_A(7, 0), a7l = BT_A(7, 1);                                                                                 \
+        BT_MM(5, a5h, a5l);                                                                                                        \
+        /* every fragment of this pair is read: once all eight waves' reads have returned, its slot takes pair s_ + 2 */             \
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                          \
+        __builtin_amdgcn_s_barrier();                                                                                               \
+        asm volatile("" ::: "memory");                                                                                              \
+        const bool more = s_ + 2 < nsteps;                                                                                          \
+        if (more) q_issue();                                                                                                        \
+        asm volatile("" ::: "memory");                                                                                              \
+        BT_MM(6, a6h, a6l);                                                                                                        \
+        BT_MM(7, a7h, a7l);                                                                                                        \
+        /* pair s_ + 1 (requested in the middle of step s_ - 1, or in the prologue) must have landed.  Outstanding per thread, oldest first: \
+           its 8 requests, the 32 stores of an epilogue that ran since (conservative: they are waited for too), the 8 requests of pair     \
+           s_ + 2 if this step made them: all but the youngest 8, or all.  (Behind the last step nothing is outstanding but stores.) */    \
+        if (more) BT_WAIT("8"); else BT_WAIT("0");                                                                                  \
+        c_slot ^= 1; ++c_p; ++s_;                                                                                                   \
     } while (0)
     auto finish_item = [&]() {
         if constexpr (WU) {
             if (uitem) {          // workgroup-uniform
-                ua0 += __shfl_xor(ua0, 32, 64);              // the two k halves of the fragment
-                ua1 += __shfl_xor(ua1, 32, 64);
-                if (lane < 32) { sU[256 * wh + 64 * wq + li] = ua0; sU[256 * wh + 64 * wq + 32 + li] = ua1; }
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    ua[t] += __shfl_xor(ua[t], 16, 64);      // the four k groups of the fragment
+                    ua[t] += __shfl_xor(ua[t], 32, 64);
+                    if (lane < 16) sU[256 * wh + 64 * wq + 16 * t + lj] = ua[t];
+                }
                 __syncthreads();
                 if (tid < 256) {
                     float sc = g.uscale * (g.ad0 ? g.ad0[0] : 1.f) / scale_from_maxbits(g.uwmax[0]);
@@ -238,53 +249,65 @@ __global__ __launch_bounds__(512, 2) void gemm_f16x2_bt_kernel(BtArgs g) {
                 }
             }
         }
-        // D = Bt^T A^T: accumulator register r of tile (x, y) is C[m0 + 128 wh + 32 x + li][n0 + 64 wq + 32 y + 8 (r >> 2) + 4 lk + (r & 3)]
+        // D = Bt^T A^T: accumulator register r of tile (x, t) is C[m0 + 128 wh + 16 x + lj][n0 + 64 wq + 16 t + 4 lg + r]
         if (g.c_blk) {
-            // blocked layout, element (row, col) at ((col / 16) * M + row) * 16 + col % 16: one 32-bit per-thread byte offset (toff_blk) + a
-            // wave-uniform base per (x, y, q) -- the 32 store addresses cost one register, not 64
+            // blocked layout, element (row, col) at ((col / 16) * M + row) * 16 + col % 16: a 16 x 16 tile of C is one contiguous KB, the wave's
+            // 64 stores of 16 bytes cover it; one 32-bit per-thread byte offset (toff_blk) + a wave-uniform base per (x, t)
             char* const cb = reinterpret_cast<char*>(g.C) + ((n0 >> 4) * g.M + m0) * 64;
 #pragma unroll
-            for (int x = 0; x < 4; ++x)
+            for (int x = 0; x < 8; ++x)
 #pragma unroll
-                for (int y = 0; y < 2; ++y)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        char* const sb = cb + ((int64_t)(2 * y + (q >> 1)) * g.M + 32 * x) * 64 + 32 * (q & 1);      // wave-uniform
-                        const f32x4 v = {alpha * c[x][y][4 * q], alpha * c[x][y][4 * q + 1], alpha * c[x][y][4 * q + 2], alpha * c[x][y][4 * q + 3]};
-                        *reinterpret_cast<f32x4*>(sb + toff_blk) = v;
-                        if (g.maxout) cmax = fmaxf(fmaxf(cmax, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
-                    }
+                for (int t = 0; t < 4; ++t) {
+                    char* const sb = cb + ((int64_t)t * g.M + 16 * x) * 64;      // wave-uniform
+                    const f32x4 v = {alpha * c[x][t][0], alpha * c[x][t][1], alpha * c[x][t][2], alpha * c[x][t][3]};
+                    *reinterpret_cast<f32x4*>(sb + toff_blk) = v;
+                    if (g.maxout) cmax = fmaxf(fmaxf(cmax, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+                }
         } else {
 #pragma unroll
-            for (int x = 0; x < 4; ++x) {
-                const int64_t row = m0 + 128 * wh + 32 * x + li;
+            for (int x = 0; x < 8; ++x) {
+                const int64_t row = m0 + 128 * wh + 16 * x + lj;
 #pragma unroll
-                for (int y = 0; y < 2; ++y)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int64_t col = n0 + 64 * wq + 32 * y + 8 * q + 4 * lk;
-                        float* p = g.C + row * g.ldc + col;
-                        const f32x4 v = {alpha * c[x][y][4 * q], alpha * c[x][y][4 * q + 1], alpha * c[x][y][4 * q + 2], alpha * c[x][y][4 * q + 3]};
-                        *reinterpret_cast<f32x4*>(p) = v;
-                        if (g.maxout) cmax = fmaxf(fmaxf(cmax, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
-                    }
+                for (int t = 0; t < 4; ++t) {
+                    const int64_t col = n0 + 64 * wq + 16 * t + 4 * lg;
+                    float* p = g.C + row * g.ldc + col;
+                    const f32x4 v = {alpha * c[x][t][0], alpha * c[x][t][1], alpha * c[x][t][2], alpha * c[x][t][3]};
+                    *reinterpret_cast<f32x4*>(p) = v;
+                    if (g.maxout) cmax = fmaxf(fmaxf(cmax, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+                }
             }
         }
     };
+    const unsigned kmask = lane < 32 ? ~0u : 0u;
     if (nsteps > 0) {
         q_enter();
         q_issue();
-        q_issue();
-        q_issue();                                   // (K >= 48: every item has at least three blocks)
-        BT_WAIT("8");                                // block 0 landed
+        // pair 0 landed: all but the 8 requests of pair 1, if there is one (K >= 48: every item has at least two pairs)
+        if (nsteps > 1) { q_issue(); BT_WAIT("8"); } else BT_WAIT("0");
     }
     int s_ = 0;
-    while (s_ < nsteps) BT_STEP(fb0, fa0);
-#undef ua_
+    for (int c_it = 0; c_it < nit; ++c_it) {
+        {                                            // a new item (workgroup-uniform)
+            const unsigned wid = item_of(c_it);
+            const unsigned tile_n = wid / tmu, tile_m = wid - tile_n * tmu;
+            m0 = (int64_t)tile_m * 256; n0 = (int64_t)tile_n * 256;
+            uitem = WU && g.uout != nullptr && ((tile_n + (tile_n >> 3) + (tile_n >> 6)) % tmu) == tile_m;
+            if (g.sync && (c_it % g.sync_every) == 0) wg_rendezvous(g.sync + wid / g.sync_n, (unsigned)g.sync_n, patience);
+#pragma unroll
+            for (int x = 0; x < 8; ++x)
+#pragma unroll
+                for (int t = 0; t < 4; ++t) c[x][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int t = 0; t < 4; ++t) ua[t] = 0.f;
+        }
+        int c_p = 0;
+        while (c_p < nk / 2) BT_STEP(false);
+        if (nk & 1) BT_STEP(true);                  // the peeled tail: no branch sits in the steady-state loop
+        finish_item();
+    }
 #undef BT_STEP
 #undef BT_MM
-#undef BT_READ_A0
-#undef BT_READ_B
+#undef BT_A
 #undef BT_TR
 #undef HF
 #undef BT_WAIT
@@ -327,7 +350,7 @@ bool mxf_gemm_bt_ok(int64_t M, int64_t N, int64_t K) { return M > 0 && N > 0 && 
 namespace {
 
 // What bt_plan decides (no HIP call) and bt_launch carries out; g.sync is the one field bt_launch fills.  The kernel relies on:
-// M, N multiples of 256, K a multiple of 16 and >= 48 (every item has three k blocks), btR >= K, 32-bit byte offsets inside one k block of Bt
+// M, N multiples of 256, K a multiple of 16 and >= 48 (every item has at least two block pairs), btR >= K, 32-bit byte offsets inside one k block of Bt
 // and one 16-column block of C, C 16-byte aligned with ldc % 4 == 0; uout != nullptr => the <true> instantiation, K <= 16 BT_KMAX16;
 // ncounters > 0 => a group is g.sync_n = tm consecutive items of one XCD's run taken in the same persistent round (strip_rendezvous_ok).
 struct BtPlan { BtArgs g; unsigned grid; unsigned ncounters; const float* w; unsigned short* wplanes; unsigned* wmax; };      // w*: the U row's bt_wsplit_kernel launch
