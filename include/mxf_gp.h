@@ -399,6 +399,42 @@ int mxf_normal_logpdf_ps_bwd(mxf_handle h, int dtype, int S, int64_t n, const vo
                              const void* mean, int64_t n_mean, int64_t strideS_mean, const void* var, int64_t n_var, int64_t strideS_var,
                              const void* w, double scale, void* dx_acc, void* dmean_acc, void* dvar_acc, void* stream);
 
+/* Expected log-likelihood of a non-Gaussian observation model under Gaussian marginals, the data term of the sparse variational GP bound
+ *   ELBO = c sum_{n,p} E_{N(f; m[n,p], v[n])}[log p(y[n,p] | f)] - KL(q(u) || p(u))
+ * (Hensman, Matthews, Ghahramani 2015, "Scalable Variational Gaussian Process Classification").  No reference counterpart: the reference's
+ * SVGP is regression with Gaussian noise only (svgp_regression.py:43-109).  With g(f) = log p(y | f) and mu(f) = E[y | f]:
+ *   MXF_LIK_BERNOULLI_LOGIT   y in {0, 1}      g = log sigmoid((2y - 1) f)           mu = sigmoid(f)
+ *   MXF_LIK_BERNOULLI_PROBIT  y in {0, 1}      g = log Phi((2y - 1) f)               mu = Phi(f)
+ *   MXF_LIK_POISSON_EXP       y = 0, 1, 2, ... g = y f - exp(f) - lgamma(y + 1)      mu = exp(f)
+ * all finite and accurate over |f| <= 40 in both precisions (mxfusion_amd/csrc/likelihood.h has the tail forms).
+ * The expectation is Gauss-Hermite quadrature: nodes and weights are HOST arrays of nq <= MXF_LIK_MAX_NODES doubles, the rule of
+ * numpy.polynomial.hermite.hermgauss as it comes (weight function exp(-x^2)); E[g] ~ sum_k w_k / sqrt(pi) g(m + sqrt(2 max(v, 0)) x_k).
+ * They travel in the kernel arguments: a call allocates nothing, copies nothing and captures into a hipGraph.  A negative v counts as 0.
+ * y (S|1, n, P), m (S|1, n, P) and v (S|1, n), the variance of a row shared by its P columns, are dense; strideS_* is the sample stride in
+ * elements (n P, n P, n), or 0 for an operand shared by the S samples -- shared labels under sampled m, v is the common case.
+ *
+ * mxf_lik_expect: out[s] += scale * sum_{i,p} E[g], out (S) ACCUMULATED INTO, and in the same pass the reverse mode, also accumulated, with
+ * w = scale, or scale * cot[s] given the per-sample weights cot (S, device, dtype of the call):
+ *   dm[s,i,p] += w sum_k w_k g'(f_k)            the exact derivative of the quadrature sum
+ *   dv[s,i]   += w / 2 sum_p sum_k w_k g''(f_k)  Price's theorem, d/dv E[g] = E[g''] / 2
+ * The Price form is the derivative of the exact expectation, so it differs from the derivative of the quadrature sum by the quadrature
+ * error (1e-6 of the value at nq = 20 for |m| <= 3, v <= 4; tests/test_likelihood_host.py has the figure); the chain rule through
+ * sqrt(v) is 0 / 0 at v = 0 and loses four digits of a float32 at v = 1e-8.  dm (S, n, P) and dv (S, n) always carry the sample axis:
+ * the caller of a shared m or v sums them over s.  out, dm, dv may each be null.
+ * mxf_lik_expect_elem: out[s,i,p] = scale * E[g], (S, n, P), WRITTEN.  Forward only.
+ * mxf_lik_moments: e1[s,i,p] = E[mu(f)], e2[s,i,p] = E[mu(f)^2], (S, n, P), WRITTEN: the predictive mean E[y] = e1 and variance
+ * e1 - e1^2 (Bernoulli kinds) or e1 + e2 - e1^2 (Poisson).                                                                              */
+enum { MXF_LIK_BERNOULLI_LOGIT = 0, MXF_LIK_BERNOULLI_PROBIT = 1, MXF_LIK_POISSON_EXP = 2 };
+#define MXF_LIK_MAX_NODES 64
+int mxf_lik_expect(mxf_handle h, int kind, int dtype, int S, int64_t n, int P, const void* y, int64_t strideS_y,
+                   const void* m, int64_t strideS_m, const void* v, int64_t strideS_v, int nq, const double* nodes, const double* weights,
+                   const void* cot, double scale, void* out_acc, void* dm_acc, void* dv_acc, void* stream);
+int mxf_lik_expect_elem(mxf_handle h, int kind, int dtype, int S, int64_t n, int P, const void* y, int64_t strideS_y,
+                        const void* m, int64_t strideS_m, const void* v, int64_t strideS_v, int nq, const double* nodes,
+                        const double* weights, double scale, void* out, void* stream);
+int mxf_lik_moments(mxf_handle h, int kind, int dtype, int S, int64_t n, int P, const void* m, int64_t strideS_m,
+                    const void* v, int64_t strideS_v, int nq, const double* nodes, const double* weights, void* e1, void* e2, void* stream);
+
 /* Multivariate normal of order n <= 32 over x (S, B, n), mean (S|1, B|1, n) and A (S|1, B|1, n, n): A is the covariance (form 0) or the
  * precision (form 1).  A larger n is status -3 from every entry point, and no buffer is touched (such matrices take mxf_potrf /
  * mxf_trsm).  Replaces MultivariateNormal.log_pdf_impl (components/distributions/normal.py:157-178: linalg.potrf, linalg.trsm,

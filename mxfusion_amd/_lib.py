@@ -12,6 +12,8 @@ K_RBF, K_MATERN12, K_MATERN32, K_MATERN52, K_LINEAR, K_BIAS, K_WHITE = range(7)
 WRITE, ACC_ADD, ACC_MUL = 0, 1, 2
 D_GAMMA, D_GAMMA_MV, D_BETA, D_LAPLACE, D_UNIFORM, D_BERNOULLI, D_NORMAL_PREC = range(7)
 TR_SOFTPLUS, TR_LOGISTIC = range(2)
+LIK_BERNOULLI_LOGIT, LIK_BERNOULLI_PROBIT, LIK_POISSON_EXP = range(3)
+LIK_MAX_NODES = 64         # MXF_LIK_MAX_NODES: quadrature nodes per call
 TR_MAX_SEG = 32            # MXF_TR_MAX_SEG: segments per launch; a longer list takes further launches inside the call
 ACT_IDENTITY, ACT_TANH, ACT_RELU, ACT_SIGMOID = range(4)
 DENSE_MAX_WIDTH = 128
@@ -53,6 +55,9 @@ SIGNATURES = {
     'mxf_univariate_logpdf_ps_bwd': [_i, _i, _i, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _d, _vp, _vp, _vp, _vp],
     'mxf_normal_logpdf_ps': [_i, _i, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _d, _vp, _vp],
     'mxf_normal_logpdf_ps_bwd': [_i, _i, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _d, _vp, _vp, _vp, _vp],
+    'mxf_lik_expect': [_i, _i, _i, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i, _pd, _pd, _vp, _d, _vp, _vp, _vp, _vp],
+    'mxf_lik_expect_elem': [_i, _i, _i, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i, _pd, _pd, _d, _vp, _vp],
+    'mxf_lik_moments': [_i, _i, _i, _i64, _i, _vp, _i64, _vp, _i64, _i, _pd, _pd, _vp, _vp, _vp],
     'mxf_mvn_factor': [_i, _i, _i, _i64, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
     'mxf_mvn_logpdf': [_i, _i, _i, _i64, _i, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _i, _i64, _d, _vp, _vp],
     'mxf_mvn_logpdf_bwd': [_i, _i, _i, _i64, _i, _vp, _i64, _vp, _i64, _i64, _vp, _i, _i64, _vp, _d, _vp, _vp, _vp, _vp],

@@ -1,0 +1,111 @@
+// Link functions of the non-Gaussian SVGP likelihoods (likelihood.hip): g(f) = log p(y | f), g'(f), g''(f) and mu(f) = E[y | f] of
+//   MXF_LIK_BERNOULLI_LOGIT   g = log sigmoid((2y - 1) f)          mu = sigmoid(f)
+//   MXF_LIK_BERNOULLI_PROBIT  g = log Phi((2y - 1) f)              mu = Phi(f)
+//   MXF_LIK_POISSON_EXP       g = y f - exp(f) - lgamma(y + 1)     mu = exp(f)
+// float and double, callable from host and device code -- the host side exists so that tests/host/lik_check.cpp can hold them to SciPy
+// without a GPU.  No tables in memory, no inline assembly.  Every value is finite and accurate over |f| <= 40 in both precisions:
+//
+// log sigmoid(z) = min(z, 0) - log1p(exp(-|z|)) and its derivatives from the one e = exp(-|z|): no 1 - sigmoid cancellation.
+//
+// log Phi(z), lambda(z) = phi(z) / Phi(z) and lambda' = -lambda (z + lambda):
+//   z >= 0        Phi = 1 - q with q = erfc(z / sqrt 2) / 2, log Phi = log1p(-q); lambda and z + lambda are sums of positive terms.
+//   -5 <= z < 0   log(erfc(-z / sqrt 2) / 2) directly; R = Phi / phi is the Mills ratio, lambda = 1 / R and lambda - t = lambda (1 - t R) with
+//                 t = -z: at t = 5 the subtraction 1 - t R = 0.036 costs a factor 28 on R's 4e-15.
+//   z < -5        erfc underflows (float32: z = -13, float64: z = -38) and 1 - t R cancels without bound, so the Mills ratio comes from its
+//                 continued fraction  R = 1 / (t + C),  C = 1 / (t + 2 / (t + 3 / (t + ...))):  lambda = t + C, lambda - t = C and
+//                 log Phi = -t^2 / 2 - log(2 pi) / 2 - log(t + C) are sums of positive terms.  Evaluated bottom-up to depth 10 + 450 / t^2 (28 at
+//                 t = 5, 10 at t = 40), two levels more than the depth at which it is within 2e-15 of the exact ratio.
+//   The z < 0 forms run in double for either T: in float32 the rounding of z / sqrt 2 alone moves erfc by z^2 2^-25, 2e-6 at z = -8, which
+//   the ratio phi / Phi and 1 - t R amplify further.  z >= 0 stays in T.
+//
+// The Poisson terms y f, exp(f) and lgamma(y + 1) are each far larger than their sum near its maximum (y = 50, f = 4: 200 - 54.6 - 148.5),
+// so they are formed in double for either T, as unidist.h does for its lgamma differences; lgamma(y + 1) once per set().
+#pragma once
+#include "special.h"
+
+#define MXF_LIK_KIND_LOGIT 0       // the numbers of MXF_LIK_* (include/mxf_gp.h), for translation units that do not see that header
+#define MXF_LIK_KIND_PROBIT 1
+#define MXF_LIK_KIND_POISSON 2
+
+// log sigmoid(z) and its first two derivatives in z
+template <typename T>
+MXF_HD inline void mxf_log_sigmoid(T z, T& l, T& d1, T& d2) {
+    const T e = exp(-fabs(z)), r = (T)1 / ((T)1 + e);
+    l = (z < (T)0 ? z : (T)0) - log1p(e);
+    d1 = z < (T)0 ? r : e * r;              // sigmoid(-z)
+    d2 = -e * r * r;                        // -sigmoid(z) sigmoid(-z)
+}
+
+template <typename T>
+MXF_HD inline T mxf_sigmoid(T z) {
+    const T e = exp(-fabs(z)), r = (T)1 / ((T)1 + e);
+    return z < (T)0 ? e * r : r;
+}
+
+// z < 0: log Phi(z), lambda(z) and c = lambda(z) + z > 0, in double
+MXF_HD inline void mxf_probit_left(double z, double& l, double& lam, double& c) {
+    const double t = -z;
+    if (t <= 5.0) {
+        const double Phi = 0.5 * erfc(t * 0.70710678118654752440), phi = 0.39894228040143267794 * exp(-0.5 * t * t);
+        l = log(Phi);
+        lam = phi / Phi;
+        c = lam * (1.0 - t * (Phi / phi));
+    } else {
+        const int n = 10 + (int)(450.0 / (t * t));
+        c = 0.0;
+        for (int k = n; k >= 1; --k) c = (double)k / (t + c);
+        lam = t + c;
+        l = -0.5 * t * t - 0.91893853320467274178 - log(lam);
+    }
+}
+
+// log Phi(z) and its first two derivatives in z
+template <typename T>
+MXF_HD inline void mxf_log_ndtr(T z, T& l, T& d1, T& d2) {
+    if (z < (T)0) {
+        double ld, lam, c;
+        mxf_probit_left((double)z, ld, lam, c);
+        l = (T)ld; d1 = (T)lam; d2 = (T)(-lam * c);
+    } else {
+        const T q = (T)0.5 * erfc(z * (T)0.70710678118654752440), lam = (T)0.39894228040143267794 * exp((T)-0.5 * z * z) / ((T)1 - q);
+        l = log1p(-q);
+        d1 = lam;
+        d2 = -lam * (z + lam);
+    }
+}
+
+template <typename T>
+MXF_HD inline T mxf_ndtr(T z) { return (T)0.5 * erfc(-z * (T)0.70710678118654752440); }
+
+// One observation y: set() holds what does not depend on f, eval() gives g = log p(y | f), g' and g''.
+template <typename T, int KIND>
+struct MxfLik {
+    T y;        // POISSON: the count; Bernoulli kinds: the sign 2y - 1
+    double c;   // POISSON: lgamma(y + 1)
+
+    MXF_HD inline void set(T y_) {
+        if constexpr (KIND == MXF_LIK_KIND_POISSON) { y = y_; c = mxf_lgamma((double)y_ + 1.0); }
+        else { y = (T)2 * y_ - (T)1; c = 0.0; }
+    }
+
+    MXF_HD inline void eval(T f, T& g, T& g1, T& g2) const {
+        if constexpr (KIND == MXF_LIK_KIND_LOGIT) {
+            mxf_log_sigmoid<T>(y * f, g, g1, g2);
+            g1 *= y;
+        } else if constexpr (KIND == MXF_LIK_KIND_PROBIT) {
+            mxf_log_ndtr<T>(y * f, g, g1, g2);
+            g1 *= y;
+        } else {
+            const double e = exp((double)f);
+            g = (T)((double)y * (double)f - e - c);
+            g1 = (T)((double)y - e);
+            g2 = (T)(-e);
+        }
+    }
+
+    MXF_HD static inline T mu(T f) {
+        if constexpr (KIND == MXF_LIK_KIND_LOGIT) return mxf_sigmoid<T>(f);
+        else if constexpr (KIND == MXF_LIK_KIND_PROBIT) return mxf_ndtr<T>(f);
+        else return exp(f);
+    }
+};

@@ -523,6 +523,68 @@ def logpdf_per_sample_bwd_(kind, x, a, b, w, scale, dx_acc=None, da_acc=None, db
               _stream())
 
 
+LIK_KIND = {'bernoulli_logit': _lib.LIK_BERNOULLI_LOGIT, 'bernoulli_probit': _lib.LIK_BERNOULLI_PROBIT, 'poisson_exp': _lib.LIK_POISSON_EXP}
+_lik_rules = {}
+
+
+def lik_nodes(num_nodes):
+    """(nq, nodes, weights): the Gauss-Hermite rule of numpy.polynomial.hermite.hermgauss as host arrays of doubles, kept per order"""
+    nq = int(num_nodes)
+    if not 1 <= nq <= _lib.LIK_MAX_NODES:
+        raise ValueError('likelihood expectation: 1 <= num_nodes <= %d, got %d' % (_lib.LIK_MAX_NODES, nq))
+    if nq not in _lik_rules:
+        import numpy as np
+        x, w = np.polynomial.hermite.hermgauss(nq)
+        _lik_rules[nq] = (nq, (_lib._c.c_double * nq)(*x), (_lib._c.c_double * nq)(*w))
+    return _lik_rules[nq]
+
+
+def _lik_operands(what, y, m, v, *buffers):
+    """(S, n, P, [(pointer, sample stride) of y, m, v]) of the likelihood expectations: m (S|1, n, P), v (S|1, n), y like m or None"""
+    _same_kind(what, m, v, y, *buffers, contiguous=True)
+    if m.dim() != 3 or v.dim() != 2 or v.shape[1] != m.shape[1] or (y is not None and (y.dim() != 3 or y.shape[1:] != m.shape[1:])):
+        raise ValueError('%s: y and m are (S|1, n, P) and v is (S|1, n); got %s, %s, %s'
+                         % (what, None if y is None else tuple(y.shape), tuple(m.shape), tuple(v.shape)))
+    S = num_samples(y, m, v)
+    if any(t is not None and t.shape[0] not in (1, S) for t in (y, m, v)):
+        raise ValueError('%s: the sample axes must be 1 or %d' % (what, S))
+    n, P = int(m.shape[1]), int(m.shape[2])
+    return S, n, P, [a for t in (y, m, v) if t is not None for a in (_p(t), 0 if t.shape[0] == 1 else t.stride(0))]
+
+
+def _lik_kind(kind):
+    return LIK_KIND[kind] if isinstance(kind, str) else int(kind)
+
+
+def lik_expect_(kind, y, m, v, scale, out_acc, dm_acc=None, dv_acc=None, cot=None, num_nodes=20):
+    """out_acc[s] += scale * sum_{i,p} E_{N(f; m[s,i,p], v[s,i])}[log p(y[s,i,p] | f)] for kind in LIK_KIND by Gauss-Hermite quadrature, and the
+    reverse mode in the same pass: dm_acc (S, n, P) += w sum_k w_k g'(f_k), dv_acc (S, n) += w / 2 sum_p sum_k w_k g''(f_k) with w = scale, or
+    scale * cot[s] given per-sample weights cot (S,).  y, m (S|1, n, P), v (S|1, n); the gradient buffers always carry the sample axis
+    (mxf_lik_expect)."""
+    S, n, P, strided = _lik_operands('likelihood expectation', y, m, v, out_acc, dm_acc, dv_acc, cot)
+    _check_buffers('likelihood expectation', (out_acc, (S,)), (cot, (S,)), (dm_acc, (S, n, P)), (dv_acc, (S, n)))
+    _lib.call('mxf_lik_expect', _h(m), _lik_kind(kind), _dt(m), S, n, P, *strided, *lik_nodes(num_nodes), _p(cot), float(scale), _p(out_acc),
+              _p(dm_acc), _p(dv_acc), _stream())
+    return out_acc
+
+
+def lik_expect_elem(kind, y, m, v, scale=1.0, num_nodes=20):
+    """scale * E_{N(f; m, v)}[log p(y | f)] per element, (S, n, P) (mxf_lik_expect_elem)."""
+    S, n, P, strided = _lik_operands('likelihood expectation', y, m, v)
+    out = torch.empty((S, n, P), dtype=m.dtype, device=m.device)
+    _lib.call('mxf_lik_expect_elem', _h(m), _lik_kind(kind), _dt(m), S, n, P, *strided, *lik_nodes(num_nodes), float(scale), _p(out), _stream())
+    return out
+
+
+def lik_moments(kind, m, v, num_nodes=20):
+    """(E[mu(f)], E[mu(f)^2]) under N(f; m, v) per element, each (S, n, P), mu(f) = E[y | f] the inverse link (mxf_lik_moments)."""
+    S, n, P, strided = _lik_operands('likelihood moments', None, m, v)
+    e1 = torch.empty((S, n, P), dtype=m.dtype, device=m.device)
+    e2 = torch.empty_like(e1)
+    _lib.call('mxf_lik_moments', _h(m), _lik_kind(kind), _dt(m), S, n, P, *strided, *lik_nodes(num_nodes), _p(e1), _p(e2), _stream())
+    return e1, e2
+
+
 MVN_MAX_ORDER = 32      # the order up to which the mxf_mvn_* entry points run (MVN_MAX of mvn.hip)
 
 
