@@ -191,7 +191,10 @@ int mxf_gemm_f32x3(mxf_handle h, int64_t M, int64_t N, int64_t K, double alpha, 
 /* The same product from TWO scaled f16 terms per operand and THREE matrix-pipe products (hi hi' + hi lo' + lo hi'; each operand is
  * scaled by the power of two that puts its largest magnitude at [2^13, 2^14), so the low term keeps its 11 bits over 2^18 of dynamic
  * range): the f32 MFMA's product accuracy at 3/16 of its cost.  This is the form the SVGP training step uses for Psi2 = Kuf Kuf^T and
- * T = H0 Kuf (MXF_SPLIT_MODE=bf16x3 selects the three-term form there).  Normwise f32 accuracy.                                      */
+ * T = H0 Kuf (MXF_SPLIT_MODE=bf16x3 selects the three-term form there).  Normwise f32 accuracy.
+ * Supported range: the exponent of the scale is clamped to +-100, so the stated accuracy holds for an operand whose largest magnitude
+ * lies in [2^-87, 2^114); a smaller maximum is scaled by 2^100 only and keeps fewer bits (its planes sit below 2^13), a larger one
+ * overflows f16 from about 2^116.  A zero, denormal or non-finite maximum leaves the operand unscaled (scale 1).                       */
 int mxf_gemm_f16x2(mxf_handle h, int64_t M, int64_t N, int64_t K, double alpha, const void* A, int64_t lda, const void* B, int64_t ldb,
                    double beta, void* C, int64_t ldc, int lower_only, void* stream);
 /* Its two halves: mxf_f16x2_split writes the two planes of an (R x K) operand (2 * mxf_f32x3_plane_elems(R, K) 16-bit elements) and
@@ -224,6 +227,24 @@ int mxf_gemm_f16x2_planes_out(mxf_handle h, int64_t M, int64_t N, int64_t K, dou
                               int a_lower, void* stream);
 int mxf_f16x2_planes_transpose(mxf_handle h, int64_t R, int64_t K, const void* planes_in, void* planes_out, const void* a, const void* scale,
                                void* U, void* stream);
+
+/* The first stage of every float32 SVGP training step on its own: the Gram matrix cov(xmin[r], xmaj[k]) (r < R, k < Kn) of float32 inputs
+ * under a stationary kind (RBF, Matern12/32/52), written DIRECTLY as the two f16 planes of the (R x Kn) operand (planes: 2 *
+ * mxf_f32x3_plane_elems(R, Kn) 16-bit elements, 16-byte aligned; element (r, k) of a plane at ((k / 16) * R + r) * 16 + k % 16, the
+ * columns Kn .. of the last 16-block zero).  The planes hold cov / variance * 2^14 as hi + lo (unit-variance covariances are <= 1, so the
+ * format's power-of-two scale needs no reduction): dense = (hi + lo) * variance[0] * 2^-14, lo the exact f32 residual of hi rounded to f16.
+ * Squared distances are formed difference first, scale after (sum_q (x_q - z_q)^2 (c / l_q)^2), so they do not depend on where the inputs
+ * sit.  Xmin (R x Q), Xmaj (Kn x Q), lengthscale (Q if ard else 1), variance (1): device float32, contiguous; Q <= 16.
+ *   w (Kn x Pw, 1 <= Pw <= 8) and U (Pw rows of ldU >= R floats), both or neither: the same pass forms U[p][r] = sum_k w[k][p] cov(r, k)
+ *     (variance included) from the f32 covariances in registers, k in index order.
+ *   majs / mins (each `period` device floats, or NULL): every covariance is multiplied by majs[k % period] and / or mins[r % period]
+ *     before it is split and before it enters U -- the planes of K diag(s) / diag(s) K for the streaming heteroscedastic bound.
+ * The padded copies of the coordinates live in the handle's Gram scratch (where mxf_gram keeps its pre-scaled ones): no caller buffer,
+ * and like every handle call not re-entrant.  -2: bad shape, a null pointer, a non-stationary kind, period < 1, w without U; -3: Q > 16
+ * or Pw > 8.  No reference counterpart (the reference materialises Kuf in float32, svgp_regression.py:73-75).                          */
+int mxf_gram_planes(mxf_handle h, int kind, int64_t R, int64_t Kn, int Q, const void* Xmin, const void* Xmaj, const void* lengthscale,
+                    int ard, const void* variance, void* planes, const void* w, int Pw, void* U, int64_t ldU, const void* majs,
+                    const void* mins, int64_t period, void* stream);
 
 /* The two halves of mxf_gemm_f32x3 for callers that reuse split operands (the SVGP step splits Kuf once for two products):
  * mxf_f32x3_split writes the three bf16 planes of an (R x K) float32 matrix (k16-blocked, see gemm_split.hip) into `planes`

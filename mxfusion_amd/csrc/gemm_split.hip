@@ -982,7 +982,9 @@ extern "C" int mxf_gemm_f32x3(mxf_handle h, int64_t M, int64_t N, int64_t K, dou
 
 // The same product from two scaled f16 terms per operand and three MFMA products (see the header of this file): each operand is scaled
 // by the power of two that puts its largest magnitude at [2^13, 2^14).  Normwise f32 accuracy; an element more than 2^18 below its
-// operand's maximum keeps fewer than 22 bits (absolute error <= 2^-39 of the maximum).
+// operand's maximum keeps fewer than 22 bits (absolute error <= 2^-39 of the maximum).  Range (scale_from_maxbits clamps the exponent of
+// the scale to +-100): full accuracy for a maximum in [2^-87, 2^114); below, the operand is scaled by 2^100 only and keeps fewer bits;
+// f16 overflow from about 2^116.  The planes and the max word are bit-determined by the operand (tests/test_gpu_split_planes.py).
 extern "C" int mxf_gemm_f16x2(mxf_handle h, int64_t M, int64_t N, int64_t K, double alpha, const void* A, int64_t lda, const void* B,
                               int64_t ldb, double beta, void* C, int64_t ldc, int lower_only, void* stream) {
     if (!h) return -1;

@@ -732,3 +732,28 @@ int mxf_gram_planes_internal(mxf_ctx* h, int kind, int64_t R, int64_t Kn, int Q,
     }
     MXF_FAIL(h, -2, "gram planes: stationary kernels only (kind %d)", kind);
 }
+
+// C ABI of the planes pass (include/mxf_gp.h): argument checks, the padded raw coordinates in the handle's Gram scratch (where mxf_gram keeps
+// its pre-scaled ones), then mxf_gram_planes_internal as the SVGP step calls it
+extern "C" int mxf_gram_planes(mxf_handle h, int kind, int64_t R, int64_t Kn, int Q, const void* Xmin, const void* Xmaj,
+                               const void* lengthscale, int ard, const void* variance, void* planes, const void* w, int Pw, void* U,
+                               int64_t ldU, const void* majs, const void* mins, int64_t period, void* stream) {
+    if (!h) return -1;
+    if (R <= 0 || Kn <= 0 || Q <= 0) MXF_FAIL(h, -2, "mxf_gram_planes: bad shape R=%lld Kn=%lld Q=%d", (long long)R, (long long)Kn, Q);
+    if (Q > 16) MXF_FAIL(h, -3, "mxf_gram_planes: Q = %d > 16 not supported", Q);
+    if (kind != MXF_K_RBF && kind != MXF_K_MATERN12 && kind != MXF_K_MATERN32 && kind != MXF_K_MATERN52)
+        MXF_FAIL(h, -2, "mxf_gram_planes: stationary kernels only (kind %d)", kind);
+    if (!Xmin || !Xmaj || !lengthscale || !variance || !planes) MXF_FAIL(h, -2, "mxf_gram_planes: null Xmin, Xmaj, lengthscale, variance or planes");
+    if (((uintptr_t)planes) % 16 != 0) MXF_FAIL(h, -2, "mxf_gram_planes: planes must be 16-byte aligned");
+    if ((w != nullptr) != (U != nullptr)) MXF_FAIL(h, -2, "mxf_gram_planes: w and U go together");
+    if (w && (Pw < 1 || Pw > 8)) MXF_FAIL(h, -3, "mxf_gram_planes: the fused row needs 1 <= Pw <= 8 (got %d)", Pw);
+    if (w && ldU < R) MXF_FAIL(h, -2, "mxf_gram_planes: ldU < R");
+    if (period < 1) MXF_FAIL(h, -2, "mxf_gram_planes: period %lld < 1", (long long)period);
+    const size_t need = mxf_gram_planes_scratch_bytes(R, Kn, Q);
+    float* scratch = (float*)mxf_gram_ws(h, need);
+    if (!scratch) MXF_FAIL(h, -4, "mxf_gram_planes: cannot allocate %zu bytes for the padded coordinates", need);
+    return mxf_gram_planes_internal(h, kind, R, Kn, Q, (const float*)Xmin, (const float*)Xmaj, (const float*)lengthscale, ard,
+                                    (const float*)variance, (unsigned short*)planes, (int64_t)mxf_split_plane_elems(R, Kn), scratch,
+                                    (hipStream_t)stream, MXF_SPLIT_F16X2, (const float*)w, w ? Pw : 0, (float*)U, ldU, (const float*)majs,
+                                    (const float*)mins, period);
+}

@@ -245,6 +245,34 @@ def planes_to_dense(planes, R, K):
     return dec(0) + dec(1)
 
 
+def gram_planes(kind, Xmin, Xmaj, ls, var, ard, w=None, majs=None, mins=None, period=1):
+    """The Gram matrix cov(Xmin[r], Xmaj[k]) of float32 inputs written directly as two f16 planes (mxf_gram_planes, the first stage of the
+    float32 SVGP step): Xmin (R, Q), Xmaj (Kn, Q), ls (Q,) if ard else (1,), var (1,).  Returns the int16 planes tensor --
+    planes_to_dense(planes, R, Kn) * var / 2**14 is the Gram matrix -- and, with w (Kn, Pw <= 8), also U (Pw, R) = w^T K^T from the same
+    pass.  majs / mins (period,): every covariance times majs[k % period] and / or mins[r % period]."""
+    f = lambda t: None if t is None else _c(t).reshape(-1)
+    Xmin, Xmaj, ls, var, w, majs, mins = _c(Xmin), _c(Xmaj), f(ls), f(var), _c(w), f(majs), f(mins)
+    _same_kind('gram_planes', Xmin, Xmaj, ls, var, w, majs, mins)
+    if Xmin.dtype != torch.float32 or Xmin.dim() != 2 or Xmaj.dim() != 2 or Xmaj.shape[1] != Xmin.shape[1]:
+        raise ValueError('gram_planes: float32 Xmin (R, Q) and Xmaj (Kn, Q)')
+    (R, Q), Kn = Xmin.shape, Xmaj.shape[0]
+    if ls.numel() != (Q if ard else 1) or var.numel() != 1:
+        raise ValueError('gram_planes: lengthscale of %d entries and one variance' % (Q if ard else 1))
+    if w is not None and (w.dim() != 2 or w.shape[0] != Kn):
+        raise ValueError('gram_planes: w (Kn, Pw)')
+    period = int(period)
+    for s in (majs, mins):
+        if s is not None and s.numel() < period:
+            raise ValueError('gram_planes: majs / mins hold `period` entries')
+    planes = torch.empty(2 * _lib.load().mxf_f32x3_plane_elems(R, Kn), dtype=torch.int16, device=Xmin.device)
+    Pw = 0 if w is None else w.shape[1]
+    U = None if w is None else torch.empty((Pw, R), dtype=torch.float32, device=Xmin.device)
+    if R > 0 and Kn > 0:
+        _lib.call('mxf_gram_planes', _h(Xmin), KIND[kind] if isinstance(kind, str) else kind, R, Kn, Q, _p(Xmin), _p(Xmaj), _p(ls),
+                  int(bool(ard)), _p(var), _p(planes), _p(w), Pw, _p(U), R, _p(majs), _p(mins), period, _stream())
+    return planes if w is None else (planes, U)
+
+
 def f32x3_split(X):
     """Three-term bf16 split planes of a 2-D float32 matrix (operand format of gemm_f32x3_planes); returns an int16 tensor."""
     X = _c(X)
