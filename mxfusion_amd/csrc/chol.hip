@@ -915,12 +915,13 @@ __global__ void zero_block_kernel(T* __restrict__ P, int64_t rows, int64_t cols,
 template <typename T>
 int trtri_merge_p1(mxf_ctx* h, int dtype, int64_t b1, int64_t b2, const T* Lp, int64_t ldl, int64_t stL, T* Ip, int64_t ldi, int64_t stI, int batch,
                    bool tri, hipStream_t st) {
-    return mxf_gemm_internal(h, dtype, 1, 1, b1, b2, b1, 1.0, Ip, ldi, stI, Lp + b1 * ldl, ldl, stL, 0.0, Ip + b1, ldi, stI, batch, 0, st, 0, tri ? 1 : 0);
+    return mxf_gemm_internal(h, st, {.dtype = dtype, .ta = 1, .tb = 1, .M = b1, .N = b2, .K = b1, .A = {Ip, ldi, stI}, .B = {Lp + b1 * ldl, ldl, stL},
+                                     .C = {Ip + b1, ldi, stI}, .batch = batch, .tri = tri ? MXF_TRI_UPPER : MXF_TRI_NONE});
 }
 template <typename T>
 int trtri_merge_p2(mxf_ctx* h, int dtype, int64_t b1, int64_t b2, T* Ip, int64_t ldi, int64_t stI, int batch, bool tri, hipStream_t st) {
-    int rc = mxf_gemm_internal(h, dtype, 0, 1, b2, b1, b2, -1.0, Ip + b1 * (ldi + 1), ldi, stI, Ip + b1, ldi, stI, 0.0, Ip + b1 * ldi, ldi, stI, batch, 0, st, 0,
-                               tri ? 2 : 0);
+    int rc = mxf_gemm_internal(h, st, {.dtype = dtype, .tb = 1, .M = b2, .N = b1, .K = b2, .alpha = -1.0, .A = {Ip + b1 * (ldi + 1), ldi, stI}, .B = {Ip + b1, ldi, stI},
+                                       .C = {Ip + b1 * ldi, ldi, stI}, .batch = batch, .tri = tri ? MXF_TRI_LOWER : MXF_TRI_NONE});
     if (rc) return rc;
     hipLaunchKernelGGL((zero_block_kernel<T>), dim3((unsigned)((b1 * b2 + 255) / 256 > 1024 ? 1024 : (b1 * b2 + 255) / 256), (unsigned)batch), dim3(256), 0, st,
                        Ip + b1, b1, b2, ldi, stI);
@@ -1034,8 +1035,8 @@ struct PotrfCall : PotrfPlan {
 
     // A[r0 : r0 + m, cc : cc + nc] -= A[r0 : r0 + m, k0 : k0 + K] A[cc : cc + nc, k0 : k0 + K]^T on stream q (lower: blocks on and below the diagonal only)
     int update(int64_t r0, int64_t m, int64_t cc, int64_t nc, int64_t k0, int64_t K, int lower, hipStream_t q) {
-        return mxf_gemm_internal(h, dtype, 0, 1, m, nc, K, -1.0, A + r0 * lda + k0, lda, sA, A + cc * lda + k0, lda, sA, 1.0, A + r0 * lda + cc, lda, sA, S,
-                                 lower, q);
+        return mxf_gemm_internal(h, q, {.dtype = dtype, .tb = 1, .M = m, .N = nc, .K = K, .alpha = -1.0, .A = {A + r0 * lda + k0, lda, sA}, .B = {A + cc * lda + k0, lda, sA},
+                                        .beta = 1.0, .C = {A + r0 * lda + cc, lda, sA}, .batch = S, .lower_only = lower});
     }
 
     // Tile form (panel_tiles) of the outer panel at c0, on st.  Waits on ev_ph if pending.  One launch for all nbr block rows from c0 down, or
@@ -1184,8 +1185,8 @@ int trsm_typed(mxf_ctx* h, int dtype, int transpose, int S, int64_t n, int64_t n
             const int nb = (int)((k0 + NB < n) ? NB : n - k0);
             const int64_t ncols = rhs_lower ? ((k0 + nb < nrhs) ? k0 + nb : nrhs) : nrhs;
             if (k0 > 0) {
-                int rc = mxf_gemm_internal(h, dtype, 0, 0, nb, ncols, k0, -1.0, L + k0 * ldl, ldl, sL, B, ldb, sB, 1.0,
-                                           B + k0 * ldb, ldb, sB, S, 0, st);
+                int rc = mxf_gemm_internal(h, st, {.dtype = dtype, .M = nb, .N = ncols, .K = k0, .alpha = -1.0, .A = {L + k0 * ldl, ldl, sL}, .B = {B, ldb, sB},
+                                                   .beta = 1.0, .C = {B + k0 * ldb, ldb, sB}, .batch = S});
                 if (rc) return rc;
             }
             hipLaunchKernelGGL((solve_cols_kernel<T, false>), dim3((unsigned)((ncols + 255) / 256), S), dim3(256), 0, st, L, ldl, sL, B,
@@ -1197,8 +1198,8 @@ int trsm_typed(mxf_ctx* h, int dtype, int transpose, int S, int64_t n, int64_t n
             const int nb = (int)((k0 + NB < n) ? NB : n - k0);
             const int64_t rem = n - (k0 + nb);
             if (rem > 0) {   // B_k -= L[k+1:, k]^T B[k+1:]
-                int rc = mxf_gemm_internal(h, dtype, 1, 0, nb, nrhs, rem, -1.0, L + (k0 + nb) * ldl + k0, ldl, sL,
-                                           B + (k0 + nb) * ldb, ldb, sB, 1.0, B + k0 * ldb, ldb, sB, S, 0, st);
+                int rc = mxf_gemm_internal(h, st, {.dtype = dtype, .ta = 1, .M = nb, .N = nrhs, .K = rem, .alpha = -1.0, .A = {L + (k0 + nb) * ldl + k0, ldl, sL},
+                                                   .B = {B + (k0 + nb) * ldb, ldb, sB}, .beta = 1.0, .C = {B + k0 * ldb, ldb, sB}, .batch = S});
                 if (rc) return rc;
             }
             hipLaunchKernelGGL((solve_cols_kernel<T, true>), dim3((unsigned)((nrhs + 255) / 256), S), dim3(256), 0, st, L, ldl, sL, B,

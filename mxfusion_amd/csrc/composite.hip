@@ -347,7 +347,7 @@ int gp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t N, int Q, in
         if (rc) return rc;
         if (tri_skinny) hipLaunchKernelGGL((trmv_lower_kernel<T>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, N, P, (const T*)Linv, N, Y, (int64_t)P, LinvY);
         else {
-        rc = mxf_gemm_internal(h, dtype, 0, 0, N, P, N, 1.0, Linv, N, NN, Y, P, sY, 0.0, LinvY, P, NP, S, 0, st);
+        rc = mxf_gemm_internal(h, st, {.dtype = dtype, .M = N, .N = P, .K = N, .A = {Linv, N, NN}, .B = {Y, P, sY}, .C = {LinvY, P, NP}, .batch = S});
         if (rc) return rc;
         }
     } else {
@@ -367,19 +367,25 @@ int gp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t N, int Q, in
         rc = mxf_trtri_internal(h, dtype, S, N, L, N, NN, Linv, N, NN, st);
         if (rc) return rc;
     }
+    // per sample, lower triangle: dK = -P/2 Linv^T Linv + beta dK (L^-1 lower triangular: tile (i, j <= i) needs k >= i only)
+    auto kinv_term = [&](double beta) {
+        return mxf_gemm_internal(h, st, {.dtype = dtype, .ta = 1, .M = N, .N = N, .K = N, .alpha = -0.5 * P, .A = {Linv, N, NN}, .B = {Linv, N, NN},
+                                         .beta = beta, .C = {dK, N, NN}, .batch = S, .lower_only = 1, .tri = MXF_TRI_UPPER});
+    };
     if (tri_skinny) {
         MXF_HIP(h, hipMemsetAsync(alpha, 0, sizeof(T) * NP, st));
         hipLaunchKernelGGL((trmv_lower_t_kernel<T>), dim3((unsigned)((N + 255) / 256), (unsigned)((N + 127) / 128)), dim3(256), 0, st, N, P, (const T*)Linv, N,
                            (const T*)LinvY, alpha);                                                                 // alpha = Linv^T LinvY
-        rc = mxf_gemm_internal(h, dtype, 1, 0, N, N, N, -0.5 * P, Linv, N, NN, Linv, N, NN, 0.0, dK, N, NN, S, 1, st, 0, 1);
+        rc = kinv_term(0.0);
         if (rc) return rc;
         hipLaunchKernelGGL((symmetrize_rankp_kernel<T>), dim3((unsigned)((N + 31) / 32), (unsigned)((N + 31) / 32)), dim3(256), 0, st, dK, N, N, (const T*)alpha, P, (T)0.5);
     } else {
-    rc = mxf_gemm_internal(h, dtype, 1, 0, N, P, N, 1.0, Linv, N, NN, LinvY, P, NP, 0.0, alpha, P, NP, S, 0, st);   // alpha = Linv^T LinvY
+    rc = mxf_gemm_internal(h, st, {.dtype = dtype, .ta = 1, .M = N, .N = P, .K = N, .A = {Linv, N, NN}, .B = {LinvY, P, NP}, .C = {alpha, P, NP}, .batch = S});   // alpha = Linv^T LinvY
     if (rc) return rc;
-    rc = mxf_gemm_internal(h, dtype, 0, 1, N, N, P, 0.5, alpha, P, NP, alpha, P, NP, 0.0, dK, N, NN, S, 1, st);     // 1/2 alpha alpha^T (lower)
+    rc = mxf_gemm_internal(h, st, {.dtype = dtype, .tb = 1, .M = N, .N = N, .K = P, .alpha = 0.5, .A = {alpha, P, NP}, .B = {alpha, P, NP}, .C = {dK, N, NN},
+                                   .batch = S, .lower_only = 1});                                                  // 1/2 alpha alpha^T (lower)
     if (rc) return rc;
-    rc = mxf_gemm_internal(h, dtype, 1, 0, N, N, N, -0.5 * P, Linv, N, NN, Linv, N, NN, 1.0, dK, N, NN, S, 1, st, 0, 1);  // - P/2 Linv^T Linv (lower; L^-1 lower triangular: tile (i, j <= i) needs k >= i only)
+    rc = kinv_term(1.0);                                                                                            // - P/2 Linv^T Linv (lower)
     if (rc) return rc;
     hipLaunchKernelGGL((symmetrize_kernel<T>), dim3((unsigned)((N + 31) / 32), (unsigned)((N + 31) / 32), S), dim3(256), 0, st, dK, N, N, NN);
     }
@@ -982,7 +988,8 @@ struct SvgpCall : SvgpPlan {
 
     // C = alpha op(A) op(B) + beta C for M x M float64 operands (lower: the lower tiles only)
     int mm(int ta, int tb, double alpha, const D* A, const D* Bm, double beta, D* C, hipStream_t s_, int lower = 0) {
-        return mxf_gemm_internal(h, MXF_F64, ta, tb, M, M, M, alpha, A, M, 0, Bm, M, 0, beta, C, M, 0, 1, lower, s_);
+        return mxf_gemm_internal(h, s_, {.dtype = MXF_F64, .ta = ta, .tb = tb, .M = M, .N = M, .K = M, .alpha = alpha, .A = {A, M}, .B = {Bm, M}, .beta = beta,
+                                         .C = {C, M}, .lower_only = lower});
     }
     template <typename U> void symmetrize(U* A, hipStream_t s_) {      // mirror the lower triangle of an M x M matrix
         hipLaunchKernelGGL((symmetrize_kernel<U>), dim3((unsigned)((M + 31) / 32), (unsigned)((M + 31) / 32), 1), dim3(256), 0, s_, A, M, M, MM);
@@ -1239,12 +1246,13 @@ struct SvgpCall : SvgpPlan {
             rc = mxf_gram(h, kind, dtype, 1, SB, M, Q, X, 0, Z, 0, ls, ard, 0, var, 0, nullptr, 0, 0.0, MXF_WRITE, Kfu, M, 0, sd_);
             if (rc) return rc;
             if (KA > 0) {
-                rc = mxf_gemm_internal(h, dtype, 1, 0, M, M, KA, 1.0, Kfu, M, 0, Kfu, M, 0, 0.0, Psi2, M, 0, 1, 1, sd_, psi2_ra);
+                rc = mxf_gemm_internal(h, sd_, {.dtype = dtype, .ta = 1, .M = M, .N = M, .K = KA, .A = {Kfu, M}, .B = {Kfu, M}, .C = {Psi2, M}, .lower_only = 1,
+                                                .reserve_cus = psi2_ra});
                 if (rc) return rc;
             }
             if (KA < SB) {
-                rc = mxf_gemm_internal(h, dtype, 1, 0, M, M, SB - KA, 1.0, Kfu + KA * M, M, 0, Kfu + KA * M, M, 0, KA > 0 ? 1.0 : 0.0, Psi2, M, 0, 1, 1,
-                                       sd_, psi2_rb);
+                rc = mxf_gemm_internal(h, sd_, {.dtype = dtype, .ta = 1, .M = M, .N = M, .K = SB - KA, .A = {Kfu + KA * M, M}, .B = {Kfu + KA * M, M},
+                                                .beta = KA > 0 ? 1.0 : 0.0, .C = {Psi2, M}, .lower_only = 1, .reserve_cus = psi2_rb});
                 if (rc) return rc;
             }
         }
@@ -1450,7 +1458,7 @@ struct SvgpCall : SvgpPlan {
             if (!rc) rc = mxf_gemm_bt_internal(h, st, M, SB, M, {.alpha = 1.0}, {hsA, (int64_t)pl_h0, hsw + 0}, {hsK, (int64_t)pl_big, hsw + 1}, M,
                                                {.C = (float*)Text, .ldc = SB});
         } else
-            rc = mxf_gemm_internal(h, dtype, 0, 0, M, SB, M, 1.0, Aext, M, 0, Kuf, SB, 0, 0.0, Text, SB, 0, 1, 0, st);   // T = H0 Kuf (MFMA)
+            rc = mxf_gemm_internal(h, st, {.dtype = dtype, .M = M, .N = SB, .K = M, .A = {Aext, M}, .B = {Kuf, SB}, .C = {Text, SB}});   // T = H0 Kuf (MFMA)
         if (rc) return rc;
         MXF_T1(h, MXF_T_TGEMM, st);
         MXF_STAGE(h, "T", st);
@@ -1575,11 +1583,11 @@ struct SvgpCall : SvgpPlan {
                 if (!rc) rc = mxf_gemm_split_internal(h, st, MXF_SPLIT_F16X2, M, M, SB, {.alpha = 1.0}, {hsS, (int64_t)pl_big, hsw + 2}, {hsK, (int64_t)pl_big, hsw + 1},
                                                       {.C = (float*)Psi2, .ldc = M});
             } else
-                rc = mxf_gemm_internal(h, dtype, 0, 1, M, M, SB, 1.0, Ksc, SB, 0, Kuf, SB, 0, 0.0, Psi2, M, 0, 1, 0, st);
+                rc = mxf_gemm_internal(h, st, {.dtype = dtype, .tb = 1, .M = M, .N = M, .K = SB, .A = {Ksc, SB}, .B = {Kuf, SB}, .C = {Psi2, M}});
             if (rc) return rc;
             if (SB >= 4096 && M <= 65535) hipLaunchKernelGGL((rowdot_kernel<T>), dim3((unsigned)M), dim3(256), 0, st, SB, P, (const T*)Kuf, SB, (const T*)Eb, R);
             else {
-                rc = mxf_gemm_internal(h, dtype, 0, 0, M, P, SB, 1.0, Kuf, SB, 0, Eb, P, 0, 0.0, R, P, 0, 1, 0, st);
+                rc = mxf_gemm_internal(h, st, {.dtype = dtype, .M = M, .N = P, .K = SB, .A = {Kuf, SB}, .B = {Eb, P}, .C = {R, P}});
                 if (rc) return rc;
             }
             if (use_mat) {
@@ -1789,6 +1797,10 @@ int sgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int64_t B, int64_t M, int 
     // module's guard widens the call to float64 above its limit
     if (!mxf_cond_init(h)) MXF_FAIL(h, -4, "mxf_sgp_logpdf: cannot allocate the condition words");
     MXF_HIP(h, hipMemsetAsync(h->cond_dev, 0, 2 * sizeof(double), st));
+    // the float64 core products: C (M x n) = op(A) (M x M) Bm (M x n)
+    auto mm64 = [&](int ta, const D* A, const D* Bm, int64_t n, D* C) {
+        return mxf_gemm_internal(h, st, {.dtype = MXF_F64, .ta = ta, .M = M, .N = n, .K = M, .A = {A, M}, .B = {Bm, n}, .C = {C, n}});
+    };
     int rc;
     rc = mxf_gram(h, kind, MXF_F64, 1, M, M, Q, Zd, 0, nullptr, 0, lsd, ard, 0, vard, 0, nullptr, 0, jitter, MXF_WRITE, Lm, M, MM, st);   // Kuu :69-72
     if (rc) return rc;
@@ -1798,7 +1810,7 @@ int sgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int64_t B, int64_t M, int 
     if (rc) return rc;
     rc = mxf_trtri_internal(h, MXF_F64, 1, M, Lm, M, MM, Linv, M, MM, st);
     if (rc) return rc;
-    rc = mxf_gemm_internal(h, MXF_F64, 1, 0, M, M, M, 1.0, Linv, M, 0, Linv, M, 0, 0.0, Ki, M, 0, 1, 0, st);
+    rc = mm64(1, Linv, Linv, M, Ki);
     if (rc) return rc;
     hipLaunchKernelGGL(norm1_sym16_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, st, M, (const double*)Ki, M, h->cond_dev + 1);
     hipLaunchKernelGGL(cond_publish_kernel, dim3(1), dim3(1), 0, st, h->cond_dev, h->cond_host + 2 * h->cond_slot);
@@ -1809,10 +1821,10 @@ int sgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int64_t B, int64_t M, int 
     if (rc) return rc;
     rc = mxf_gram(h, kind, dtype, 1, B, M, Q, X, 0, Z, 0, ls, ard, 0, var, 0, nullptr, 0, 0.0, MXF_WRITE, Kfu, M, 0, st);
     if (rc) return rc;
-    rc = mxf_gemm_internal(h, dtype, 1, 0, M, M, B, 1.0, Kfu, M, 0, Kfu, M, 0, 0.0, Psi2, M, 0, 1, 1, st);
+    rc = mxf_gemm_internal(h, st, {.dtype = dtype, .ta = 1, .M = M, .N = M, .K = B, .A = {Kfu, M}, .B = {Kfu, M}, .C = {Psi2, M}, .lower_only = 1});
     if (rc) return rc;
     hipLaunchKernelGGL((symmetrize_kernel<T>), dim3((unsigned)((M + 31) / 32), (unsigned)((M + 31) / 32), 1), dim3(256), 0, st, Psi2, M, M, MM);
-    rc = mxf_gemm_internal(h, dtype, 0, 0, M, P, B, 1.0, Kuf, B, 0, Y, P, 0, 0.0, psi1, P, 0, 1, 0, st);
+    rc = mxf_gemm_internal(h, st, {.dtype = dtype, .M = M, .N = P, .K = B, .A = {Kuf, B}, .B = {Y, P}, .C = {psi1, P}});
     if (rc) return rc;
     copy_convert(MM, (const T*)Psi2, Psi2d, st); copy_convert(MP, (const T*)psi1, psi1d, st);
     hipLaunchKernelGGL((sumsq_kernel<T>), dim3(1), dim3(256), 0, st, B * P, Y, (int64_t)0, sc + 6);
@@ -1824,11 +1836,11 @@ int sgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int64_t B, int64_t M, int 
     if (rc) return rc;
     rc = mxf_trtri_internal(h, MXF_F64, 1, M, Cm, M, MM, Lcinv, M, MM, st);
     if (rc) return rc;
-    rc = mxf_gemm_internal(h, MXF_F64, 1, 0, M, M, M, 1.0, Lcinv, M, 0, Lcinv, M, 0, 0.0, Ci, M, 0, 1, 0, st);
+    rc = mm64(1, Lcinv, Lcinv, M, Ci);
     if (rc) return rc;
-    rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, P, M, 1.0, Ci, M, 0, psi1d, P, 0, 0.0, ad, P, 0, 1, 0, st);
+    rc = mm64(0, Ci, psi1d, P, ad);
     if (rc) return rc;
-    rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, P, M, 1.0, Psi2d, M, 0, ad, P, 0, 0.0, PA, P, 0, 1, 0, st);
+    rc = mm64(0, Psi2d, ad, P, PA);
     if (rc) return rc;
     hipLaunchKernelGGL((dot_kernel<D>), dim3(dotgrid(MP)), dim3(256), 0, st, MP, (const D*)psi1d, (const D*)ad, 1.0, sc + 2);
     hipLaunchKernelGGL((dot_kernel<D>), dim3(dotgrid(MM)), dim3(256), 0, st, MM, (const D*)Ki, (const D*)Psi2d, 1.0, sc + 3);
@@ -1839,23 +1851,23 @@ int sgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int64_t B, int64_t M, int 
     // posterior side products (:99-106): L, LA = L^-1 chol(C)
     if (Lout) hipLaunchKernelGGL((convert_kernel<D, T>), dim3(gridn(MM)), dim3(256), 0, st, M, M, (const D*)Lm, M, Lout, M);
     if (LAout) {
-        rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 1.0, Linv, M, 0, Cm, M, 0, 0.0, tmp, M, 0, 1, 0, st);
+        rc = mm64(0, Linv, Cm, M, tmp);
         if (rc) return rc;
         hipLaunchKernelGGL((convert_kernel<D, T>), dim3(gridn(MM)), dim3(256), 0, st, M, M, (const D*)tmp, M, LAout, M);
     }
     MXF_LAUNCH_CHECK(h);
     if (!want_grad) return 0;
-    rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 1.0, Ki, M, 0, Psi2d, M, 0, 0.0, tmp, M, 0, 1, 0, st);
+    rc = mm64(0, Ki, Psi2d, M, tmp);
     if (rc) return rc;
-    rc = mxf_gemm_internal(h, MXF_F64, 0, 0, M, M, M, 1.0, tmp, M, 0, Ki, M, 0, 0.0, KPK, M, 0, 1, 0, st);
+    rc = mm64(0, tmp, Ki, M, KPK);
     if (rc) return rc;
     hipLaunchKernelGGL((sgp_grads_kernel<T>), dim3(gridn(MM)), dim3(256), 0, st, M, P, (const D*)Ci, (const D*)Ki, (const D*)KPK, (const D*)ad,
                        (const D*)noised, gscale, G2, GKuu, Gpsi1);
     // dKuf = 2 dPsi2 Kuf + dpsi1 Y^T  (into the Kfu buffer), then the Gram reverse mode
     T* dKuf = Kfu;
-    rc = mxf_gemm_internal(h, dtype, 0, 0, M, B, M, 1.0, G2, M, 0, Kuf, B, 0, 0.0, dKuf, B, 0, 1, 0, st);
+    rc = mxf_gemm_internal(h, st, {.dtype = dtype, .M = M, .N = B, .K = M, .A = {G2, M}, .B = {Kuf, B}, .C = {dKuf, B}});
     if (rc) return rc;
-    rc = mxf_gemm_internal(h, dtype, 0, 1, M, B, P, 1.0, Gpsi1, P, 0, Y, P, 0, 1.0, dKuf, B, 0, 1, 0, st);
+    rc = mxf_gemm_internal(h, st, {.dtype = dtype, .tb = 1, .M = M, .N = B, .K = P, .A = {Gpsi1, P}, .B = {Y, P}, .beta = 1.0, .C = {dKuf, B}});
     if (rc) return rc;
     if (dZ) MXF_HIP(h, hipMemsetAsync(dZ, 0, sizeof(T) * M * Q, st));
     if (dls) MXF_HIP(h, hipMemsetAsync(dls, 0, sizeof(T) * lsn, st));
@@ -1865,7 +1877,7 @@ int sgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int64_t B, int64_t M, int 
                                        .dK = dKuf, .lddk = B, .dX = dZ, .dX2 = dX, .dls = dls, .dvar = dvar});
     if (rc) return rc;
     if (dY) {
-        rc = mxf_gemm_internal(h, dtype, 1, 0, B, P, M, 1.0, Kuf, B, 0, Gpsi1, P, 0, 0.0, dY, P, 0, 1, 0, st);     // Kuf^T dpsi1
+        rc = mxf_gemm_internal(h, st, {.dtype = dtype, .ta = 1, .M = B, .N = P, .K = M, .A = {Kuf, B}, .B = {Gpsi1, P}, .C = {dY, P}});     // Kuf^T dpsi1
         if (rc) return rc;
         hipLaunchKernelGGL((sgp_dy_kernel<T>), dim3(gridn(B * P)), dim3(256), 0, st, B * P, Y, noise, gscale, dY);
     }

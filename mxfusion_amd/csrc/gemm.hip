@@ -14,21 +14,16 @@
 //   C/D f64 16x16: col = l&15, row = (l>>4) + 4*r, r in [0,4)
 #include "common.h"
 #include "internal.h"
+#include "gemm_plan.h"
 #include <stdlib.h>
+#include <type_traits>
 
 namespace {
 
-#ifndef MXF_GEMM_BK
-#define MXF_GEMM_BK 32
-#endif
 #ifndef MXF_GEMM_WPS
 #define MXF_GEMM_WPS 2
 #endif
-#ifndef MXF_GEMM_WAVES
-#define MXF_GEMM_WAVES 8
-#endif
-constexpr int BM = 128, BN = 128, BK = MXF_GEMM_BK;
-constexpr int NWAVE = MXF_GEMM_WAVES;          // 4: 2x2 waves of 64x64;  8: 2x4 waves of 64x32 (half the accumulators -> 4 waves/SIMD)
+using namespace mxf_gemm_tiles;                // BM, BN, BK, NWAVE, DBK, SBM_, SBK_: shared with the plan
 constexpr int NT = 64 * NWAVE;
 constexpr int WN = (NWAVE == 8) ? 32 : 64;     // wave tile width
 
@@ -329,7 +324,7 @@ __global__ __launch_bounds__(NT, (NWAVE == 8 ? (sizeof(T) == 4 ? 4 : 2) : (sizeo
 // An operand stored the other way round (K x M with the rows of the tile contiguous: A of a transposed-A product, B of a plain-B one) comes
 // in as its 16 k rows of 1 KB, one DMA instruction each, at an LDS row stride of 144 doubles (1 KB + 128 B: the two k values a half wave
 // reads fall on the two halves of the banks).  AKM / BKM: operand stored as (k, m).
-constexpr int DBK = 16, DKM_LD = 144;
+constexpr int DKM_LD = 144;
 template <bool AKM, bool BKM>
 __global__ __launch_bounds__(512, 2) void gemm_f64_dma_kernel(GemmArgs<double> g) {
     constexpr int ASZ = AKM ? DBK * DKM_LD : 128 * DBK, BSZ = BKM ? DBK * DKM_LD : 128 * DBK;
@@ -485,7 +480,7 @@ __global__ void scale_kernel(T* C, int64_t M, int64_t N, int64_t ldc, int64_t sC
 // 64 x 64 block tile, BK = 16, 4 waves of 32 x 32 (2 x 2 v_mfma_f64_16x16x4_f64), 34 KB of LDS and < 64 VGPRs: four of these fit a CU NEXT
 // TO the big streaming kernels (the 128 x 128 kernel needs a whole CU's LDS and registers, so its workgroups used to wait for a CU to
 // drain), 4x more tiles for a 1024^2 output, and the 64-wide panel updates of potrf waste no half tile.  Guarded scalar loaders only.
-constexpr int SBM_ = 64, SBK_ = 16, SLD_ = 66;
+constexpr int SLD_ = 66;
 template <bool TA, bool TB>
 __global__ __launch_bounds__(256) void gemm_small_f64_kernel(GemmArgs<double> g) {
     __shared__ double sm[2][2][SBK_ * SLD_];
@@ -580,140 +575,53 @@ __global__ __launch_bounds__(256) void gemm_small_f64_kernel(GemmArgs<double> g)
             }
 }
 
-// launch of the small-tile variant; returns false when the problem should take the 128 x 128 kernel instead
-template <typename T>
-bool gemm_small_launch(mxf_ctx*, GemmArgs<T>&, int, int, int64_t, int64_t, int64_t, double, int, int, hipStream_t, int&) { return false; }
-template <>
-bool gemm_small_launch<double>(mxf_ctx* h, GemmArgs<double>& g, int ta, int tb, int64_t M, int64_t N, int64_t K, double beta, int batch, int lower_only,
-                               hipStream_t st, int& rc) {
-    const int64_t t128 = ((M + 127) / 128) * ((N + 127) / 128) * batch;
-    if (t128 > 64 || M > 65535) return false;       // the big kernel fills at least a quarter of the chip: keep it
-    // r06: a LONG contraction over a small output (the float64 step's Psi2 = Kuf Kuf^T: 1024 x 1024 x 2.1 M) is throughput-bound, not
-    // latency-bound -- it belongs on the 128 x 128 LDS-DMA kernel with split-K (probe knob MXF_GEMM_SMALL_KMAX: contraction length above
-    // which the small-tile kernel steps aside)
-    static const int64_t kmax_env = MXF_KNOB("MXF_GEMM_SMALL_KMAX", 16384);
-    if (K > kmax_env && !g.k_from_m && M >= 512 && N >= 512) return false;      // (skinny outputs -- K^T y, M x P -- stay: the 128 x 128 tiles would idle)
-    const int64_t tm = (M + SBM_ - 1) / SBM_, tn = (N + SBM_ - 1) / SBM_;
-    if (lower_only && tm != tn) return false;
-    const int64_t tiles = (lower_only ? tm * (tm + 1) / 2 : tm * tn) * batch;
-    int64_t splitk = 1;
-    const int64_t slots = 1024;                                      // 4 workgroups per CU
-    if (tiles < slots && K >= 128 && !g.k_from_m) { splitk = slots / tiles; const int64_t mx = K / 64 > 0 ? K / 64 : 1; if (splitk > mx) splitk = mx; if (splitk < 1) splitk = 1; }
-    int64_t kchunk = SBK_;
-    if (K > 0) { kchunk = (K + splitk - 1) / splitk; kchunk = (kchunk + SBK_ - 1) / SBK_ * SBK_; splitk = (K + kchunk - 1) / kchunk; } else splitk = 1;
-    g.splitk = (int)splitk; g.kchunk = kchunk; g.atomic = splitk > 1;
-    g.tm = tm; g.tn = tn; g.ntiles = lower_only ? tm * (tm + 1) / 2 : tm * tn; g.nwg = g.ntiles * batch * splitk;
-    g.xc_max = 0; g.rev_m = 0;
-    rc = 0;
-    if (g.atomic && beta != 1.0) {
-        dim3 gs((unsigned)((N + 255) / 256), (unsigned)M, (unsigned)batch);
-        hipLaunchKernelGGL((scale_kernel<double>), gs, dim3(256), 0, st, g.C, M, N, g.ldc, g.sC, beta, lower_only);
-    }
-    dim3 grid((unsigned)g.nwg, 1, 1);
-    if (!ta && !tb) hipLaunchKernelGGL((gemm_small_f64_kernel<false, false>), grid, dim3(256), 0, st, g);
-    else if (!ta && tb) hipLaunchKernelGGL((gemm_small_f64_kernel<false, true>), grid, dim3(256), 0, st, g);
-    else if (ta && !tb) hipLaunchKernelGGL((gemm_small_f64_kernel<true, false>), grid, dim3(256), 0, st, g);
-    else hipLaunchKernelGGL((gemm_small_f64_kernel<true, true>), grid, dim3(256), 0, st, g);
-    if (hipGetLastError() != hipSuccess) rc = -5;
-    return true;
+// the one place a runtime (a, b) becomes template arguments: f(std::bool_constant<a>, std::bool_constant<b>)
+template <typename F>
+void with_bools(bool a, bool b, F f) {
+    if (a) { if (b) f(std::true_type{}, std::true_type{}); else f(std::true_type{}, std::false_type{}); }
+    else { if (b) f(std::false_type{}, std::true_type{}); else f(std::false_type{}, std::false_type{}); }
 }
 
+// fill GemmArgs from the descriptor and the plan (gemm_plan.h), pre-scale C if the plan says so, launch the kernel it chose
 template <typename T>
-int gemm_typed(mxf_ctx* h, int ta, int tb, int64_t M, int64_t N, int64_t K, double alpha, const void* A, int64_t lda,
-               int64_t sA, const void* B, int64_t ldb, int64_t sB, double beta, void* C, int64_t ldc, int64_t sC,
-               int batch, int lower_only, hipStream_t st, int reserve_cus, int k_from_m) {
+int gemm_typed(mxf_ctx* h, hipStream_t st, const MxfGemm& d) {
+    static const int64_t small_kmax = MXF_KNOB("MXF_GEMM_SMALL_KMAX", 16384);
     GemmArgs<T> g;
-    g.k_from_m = (k_from_m == 1 && ta) ? 1 : ((k_from_m == 2 && !ta) ? 2 : 0);     // the caller vouches for the triangular operand
-    g.A = (const T*)A; g.B = (const T*)B; g.C = (T*)C;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.sA = sA; g.sB = sB; g.sC = sC;
-    g.alpha = (T)alpha; g.beta = (T)beta; g.lower_only = lower_only;
-    {
-        constexpr int VEC = Vec16<T>::n;
-        auto ok = [&](const void* p, int64_t ld, int64_t st) { return ((uintptr_t)p % 16 == 0) && (ld % VEC == 0) && (st % VEC == 0); };
-        g.vecA = ok(A, lda, sA); g.vecB = ok(B, ldb, sB);
+    g.A = (const T*)d.A.p; g.B = (const T*)d.B.p; g.C = (T*)d.C.p;
+    g.M = d.M; g.N = d.N; g.K = d.K; g.lda = d.A.ld; g.ldb = d.B.ld; g.ldc = d.C.ld; g.sA = d.A.stride; g.sB = d.B.stride; g.sC = d.C.stride;
+    g.alpha = (T)d.alpha; g.beta = (T)d.beta; g.lower_only = d.lower_only;
+    auto vec_ok = [](const MxfMat& m) { constexpr int VEC = Vec16<T>::n; return ((uintptr_t)m.p % 16 == 0) && (m.ld % VEC == 0) && (m.stride % VEC == 0); };
+    g.vecA = vec_ok(d.A); g.vecB = vec_ok(d.B);
+    g.k_from_m = gemm_tri_normalise(d.tri, d.ta);     // the caller vouches for the triangular operand
+    const GemmPlan p = gemm_plan(sizeof(T), d.M, d.N, d.K, d.batch, d.lower_only, d.reserve_cus, g.k_from_m, g.vecA, g.vecB, d.beta, small_kmax);
+    if (p.refusal) MXF_FAIL(h, p.rc, "mxf_gemm: %s", p.refusal);
+    g.splitk = p.splitk; g.kchunk = p.kchunk; g.atomic = p.atomic;
+    g.tm = p.tm; g.tn = p.tn; g.ntiles = p.ntiles; g.nwg = p.nwg; g.xc_max = p.xc_max; g.rev_m = p.rev_m;
+    if (p.prescale) {
+        dim3 gs((unsigned)((d.N + 255) / 256), (unsigned)d.M, (unsigned)d.batch);
+        hipLaunchKernelGGL((scale_kernel<T>), gs, dim3(256), 0, st, g.C, d.M, d.N, g.ldc, g.sC, g.beta, d.lower_only);
+        MXF_LAUNCH_CHECK(h);
     }
-    {   // latency-bound float64 products of the (M x M) core: small-tile variant
-        int rc_small = 0;
-        if (gemm_small_launch<T>(h, g, ta, tb, M, N, K, beta, batch, lower_only, st, rc_small)) {
-            if (rc_small) MXF_FAIL(h, -5, "mxf_gemm: small-tile launch failed");
-            return 0;
-        }
-    }
-    const int64_t tm = (M + BM - 1) / BM, tn = (N + BN - 1) / BN;
-    // split K when the output grid cannot fill 256 CUs and K is long
-    const int64_t tiles = (lower_only ? tm * (tm + 1) / 2 : tm * tn) * batch;   // EXACT count (an estimate of 32 for 36 tiles cost 35 %)
-    // split K when the output grid cannot fill the chip.  Resident slots: 256 CUs x (2 workgroups f32 | 1 f64); pick the
-    // split so that the grid is (just under) a whole number of rounds -- 576 workgroups on 512 slots would run a
-    // half-empty second round (measured: Psi2 33 ms -> 19 ms with 504).
-    int splitk = 1;
-    // reserve_cus: leave that many CUs without a workgroup of this (register-saturating) kernel, so that latency-bound
-    // kernels of a concurrent stream can still be scheduled (the split-K grid is sized to the remaining CUs)
-    const int64_t slots = (256 - reserve_cus) * (sizeof(T) == 4 ? 2 : 1);
-    if (tiles < slots && K >= 256 && !g.k_from_m) {
-        const int64_t maxsplit = K / 128 > 0 ? K / 128 : 1;     // small latency-bound GEMMs of the (M x M) core split too
-        int64_t sk = slots / tiles;
-        if (sk * tiles < (slots * 3) / 4) sk = (2 * slots) / tiles;   // one round would leave >25% of the slots idle: use two
-        if (sk > maxsplit) sk = maxsplit;
-        if (sk < 1) sk = 1;
-        splitk = (int)sk;
-    }
-    int64_t kchunk = BK;
-    if (K > 0) {
-        kchunk = (K + splitk - 1) / splitk;
-        kchunk = (kchunk + BK - 1) / BK * BK;
-        splitk = (int)((K + kchunk - 1) / kchunk);
-    } else {
-        splitk = 1;      // empty contraction: C = beta C
-    }
-    g.splitk = splitk; g.kchunk = kchunk; g.atomic = splitk > 1;
-    if (lower_only && tm != tn) MXF_FAIL(h, -2, "mxf_gemm: lower_only needs a square output");
-    g.tm = tm; g.tn = tn;
-    g.ntiles = lower_only ? tm * (tm + 1) / 2 : tm * tn;
-    g.nwg = g.ntiles * batch * splitk;
-    g.xc_max = 0;
-    g.rev_m = 1;
-    if (lower_only && g.k_from_m == 1 && splitk == 1 && tm >= 16) {
-        for (int64_t x = 0; x < 8; ++x) {
-            int64_t cnt = 0;
-            for (int64_t r = x; r < tm; r += 8) cnt += r + 1;
-            if (cnt > g.xc_max) g.xc_max = cnt;
-        }
-        g.nwg = 8 * g.xc_max * batch;
-    }
-    if (g.nwg > 2147483647LL) MXF_FAIL(h, -3, "mxf_gemm: grid too large");
-    if (g.atomic && beta != 1.0) {     // beta == 1 (the potrf / trsm updates): C is accumulated into as is, nothing to pre-scale
-        dim3 gs((unsigned)((N + 255) / 256), (unsigned)M, (unsigned)batch);
-        if (M > 65535) MXF_FAIL(h, -3, "mxf_gemm: split-K path needs M<=65535");
-        hipLaunchKernelGGL((scale_kernel<T>), gs, dim3(256), 0, st, (T*)C, M, N, ldc, sC, (T)beta, lower_only);
-    }
-    dim3 grid((unsigned)g.nwg, 1, 1);
+    const dim3 grid((unsigned)g.nwg, 1, 1);
     if constexpr (sizeof(T) == 8) {
-        if (g.vecA && g.vecB && M % BM == 0 && N % BN == 0 && K % DBK == 0 && kchunk % DBK == 0 && NWAVE == 8) {
-            if (!ta && tb) hipLaunchKernelGGL((gemm_f64_dma_kernel<false, false>), grid, dim3(512), 0, st, g);
-            else if (ta && !tb) hipLaunchKernelGGL((gemm_f64_dma_kernel<true, true>), grid, dim3(512), 0, st, g);
-            else if (ta && tb) hipLaunchKernelGGL((gemm_f64_dma_kernel<true, false>), grid, dim3(512), 0, st, g);
-            else hipLaunchKernelGGL((gemm_f64_dma_kernel<false, true>), grid, dim3(512), 0, st, g);
-            MXF_LAUNCH_CHECK(h);
-            return 0;
-        }
+        if (p.kernel == MXF_GEMM_SMALL_F64)
+            with_bools(d.ta, d.tb, [&](auto ta, auto tb) { hipLaunchKernelGGL((gemm_small_f64_kernel<ta.value, tb.value>), grid, dim3(256), 0, st, g); });
+        else if (p.kernel == MXF_GEMM_DMA_F64)      // operand stored as (k, m): a transposed A, a plain B
+            with_bools(d.ta, !d.tb, [&](auto akm, auto bkm) { hipLaunchKernelGGL((gemm_f64_dma_kernel<akm.value, bkm.value>), grid, dim3(512), 0, st, g); });
     }
-    if (!ta && !tb) hipLaunchKernelGGL((gemm_kernel<T, false, false>), grid, dim3(NT), 0, st, g);
-    else if (!ta && tb) hipLaunchKernelGGL((gemm_kernel<T, false, true>), grid, dim3(NT), 0, st, g);
-    else if (ta && !tb) hipLaunchKernelGGL((gemm_kernel<T, true, false>), grid, dim3(NT), 0, st, g);
-    else hipLaunchKernelGGL((gemm_kernel<T, true, true>), grid, dim3(NT), 0, st, g);
+    if (p.kernel == MXF_GEMM_GENERIC)
+        with_bools(d.ta, d.tb, [&](auto ta, auto tb) { hipLaunchKernelGGL((gemm_kernel<T, ta.value, tb.value>), grid, dim3(NT), 0, st, g); });
     MXF_LAUNCH_CHECK(h);
     return 0;
 }
 
 }  // namespace
 
-int mxf_gemm_internal(mxf_ctx* h, int dtype, int ta, int tb, int64_t M, int64_t N, int64_t K, double alpha,
-                      const void* A, int64_t lda, int64_t sA, const void* B, int64_t ldb, int64_t sB, double beta,
-                      void* C, int64_t ldc, int64_t sC, int batch, int lower_only, hipStream_t st, int reserve_cus, int k_from_m) {
-    if (M <= 0 || N <= 0 || batch <= 0) return 0;
-    if (dtype == MXF_F32) return gemm_typed<float>(h, ta, tb, M, N, K, alpha, A, lda, sA, B, ldb, sB, beta, C, ldc, sC, batch, lower_only, st, reserve_cus, k_from_m);
-    if (dtype == MXF_F64) return gemm_typed<double>(h, ta, tb, M, N, K, alpha, A, lda, sA, B, ldb, sB, beta, C, ldc, sC, batch, lower_only, st, reserve_cus, k_from_m);
-    MXF_FAIL(h, -2, "mxf_gemm: bad dtype %d", dtype);
+int mxf_gemm_internal(mxf_ctx* h, hipStream_t st, const MxfGemm& d) {
+    if (d.M <= 0 || d.N <= 0 || d.batch <= 0) return 0;
+    if (d.dtype == MXF_F32) return gemm_typed<float>(h, st, d);
+    if (d.dtype == MXF_F64) return gemm_typed<double>(h, st, d);
+    MXF_FAIL(h, -2, "mxf_gemm: bad dtype %d", d.dtype);
 }
 
 extern "C" int mxf_gemm(mxf_handle h, int dtype, int transA, int transB, int64_t M, int64_t N, int64_t K,
@@ -723,6 +631,6 @@ extern "C" int mxf_gemm(mxf_handle h, int dtype, int transA, int transB, int64_t
     if (!h) return -1;
     if (M < 0 || N < 0 || K < 0 || batch < 0) MXF_FAIL(h, -2, "mxf_gemm: negative dimension");
     if ((M > 0 && N > 0 && batch > 0) && (!A || !B || !C) && K > 0) MXF_FAIL(h, -2, "mxf_gemm: null operand");
-    return mxf_gemm_internal(h, dtype, transA, transB, M, N, K, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc,
-                             strideC, batch, 0, (hipStream_t)stream);
+    return mxf_gemm_internal(h, (hipStream_t)stream, {.dtype = dtype, .ta = transA, .tb = transB, .M = M, .N = N, .K = K, .alpha = alpha,
+                                                      .A = {A, lda, strideA}, .B = {B, ldb, strideB}, .beta = beta, .C = {C, ldc, strideC}, .batch = batch});
 }

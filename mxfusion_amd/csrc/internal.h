@@ -1,13 +1,25 @@
 // Internal (non-exported) typed launchers shared between translation units of libmxf_gp.so.
 #pragma once
 #include "common.h"
+#include "gemm_plan.h"      // MXF_TRI_*
 
 void mxf_comm_release(mxf_ctx* h);      // comm.hip: destroys the handle's RCCL communicator, if any
 
-// C = alpha op(A) op(B) + beta C; lower_only: skip blocks / entries strictly above the diagonal (syrk-style update)
-int mxf_gemm_internal(mxf_ctx* h, int dtype, int ta, int tb, int64_t M, int64_t N, int64_t K, double alpha,
-                      const void* A, int64_t lda, int64_t sA, const void* B, int64_t ldb, int64_t sB, double beta,
-                      void* C, int64_t ldc, int64_t sC, int batch, int lower_only, hipStream_t st, int reserve_cus = 0, int k_from_m = 0);
+// C = alpha op(A) op(B) + beta C (gemm.hip; row-major).  A plain descriptor (an aggregate, every member defaulted): a call site names what it
+// passes, in declaration order, and omits what is default.
+struct MxfMat  { const void* p = nullptr; int64_t ld = 0, stride = 0; };   // stride: per batch entry, 0 = shared
+struct MxfMatW { void* p = nullptr;       int64_t ld = 0, stride = 0; };
+struct MxfGemm {
+    int dtype = 0, ta = 0, tb = 0;
+    int64_t M = 0, N = 0, K = 0;
+    double alpha = 1.0; MxfMat A, B; double beta = 0.0; MxfMatW C;
+    int batch = 1;
+    int lower_only = 0;        // square output: skip blocks / entries strictly above the diagonal (syrk-style update)
+    int reserve_cus = 0;       // CUs left to the kernels of other streams (sizes the split-K grid)
+    int tri = MXF_TRI_NONE;    // the caller vouches: MXF_TRI_UPPER, op(A) = A^T of a lower-triangular A (counts only with ta); MXF_TRI_LOWER, op(A) = A itself,
+                               // lower triangular (only without ta); the k loops then skip the zero part
+};
+int mxf_gemm_internal(mxf_ctx* h, hipStream_t st, const MxfGemm& d);
 
 // zero_upper = false: leave the strict upper triangle outside the 64 x 64 diagonal blocks as it was (callers that only read the lower part)
 // zero_info = false: the caller has zeroed `info` already (the SVGP composite clears its status words in one launch off the critical path)

@@ -62,6 +62,13 @@ __global__ void pcast_kernel(int64_t n, const TI* __restrict__ src, TO* __restri
 
 bool stationary(int kind) { return kind == MXF_K_RBF || kind == MXF_K_MATERN12 || kind == MXF_K_MATERN32 || kind == MXF_K_MATERN52; }
 
+// per sample s: vout_s (Nt x Nt) += alpha V_s^T X_s, V_s and X_s the s-th blocks of Nt columns of the folded (K x S Nt) operands
+template <typename T>
+int cov_update(mxf_ctx* h, hipStream_t st, int dtype, int S, int64_t Nt, int64_t K, double alpha, const T* V, const T* X, T* vout) {
+    return mxf_gemm_internal(h, st, {.dtype = dtype, .ta = 1, .M = Nt, .N = Nt, .K = K, .alpha = alpha, .A = {V, S * Nt, Nt}, .B = {X, S * Nt, Nt},
+                                     .beta = 1.0, .C = {vout, Nt, Nt * Nt}, .batch = S});
+}
+
 template <typename T>
 int gp_predict_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t N, int64_t Nt, int Q, int P, const T* Xc, const T* Xt, const T* ls, int ard,
                      const T* var, const T* L, int64_t ldl, const T* LinvY, const T* noise, int noise_free, int full_cov, T* mean, T* vout,
@@ -74,7 +81,7 @@ int gp_predict_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t N, int64_t 
     if (rc) return rc;
     rc = mxf_trsm_internal(h, dtype, 0, 1, N, C, L, ldl, 0, V, C, 0, 0, st);                                                      // V = L^-1 Kxt :161
     if (rc) return rc;
-    rc = mxf_gemm_internal(h, dtype, 1, 0, C, P, N, 1.0, V, C, 0, LinvY, P, 0, 0.0, mean, P, 0, 1, 0, st);                         // V^T LinvY :162
+    rc = mxf_gemm_internal(h, st, {.dtype = dtype, .ta = 1, .M = C, .N = P, .K = N, .A = {V, C}, .B = {LinvY, P}, .C = {mean, P}});  // V^T LinvY :162
     if (rc) return rc;
     if (!full_cov) {
         rc = mxf_coldot(h, dtype, 1, N, C, V, C, 0, V, C, 0, cd, st);                                                             // :181
@@ -84,7 +91,7 @@ int gp_predict_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t N, int64_t 
         // per sample: K(Xt_s, Xt_s) - V_s^T V_s (+ noise I)  :186-190
         rc = mxf_gram(h, kind, dtype, S, Nt, Nt, Q, Xt, Nt * Q, nullptr, 0, ls, ard, 0, var, 0, nullptr, 0, 0.0, MXF_WRITE, vout, Nt, Nt * Nt, st);
         if (rc) return rc;
-        rc = mxf_gemm_internal(h, dtype, 1, 0, Nt, Nt, N, -1.0, V, C, Nt, V, C, Nt, 1.0, vout, Nt, Nt * Nt, S, 0, st);
+        rc = cov_update(h, st, dtype, S, Nt, N, -1.0, V, V, vout);
         if (rc) return rc;
         if (!noise_free) hipLaunchKernelGGL((add_diag_scalar_kernel<T>), dim3(gridn(C)), dim3(256), 0, st, (int64_t)S, Nt, vout, noise, (T)0);
     }
@@ -106,7 +113,7 @@ int svgp_predict_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t M, int64_
     T* V = wv + M * P; T* tmp = V + (size_t)M * C; T* cd1 = tmp + (size_t)M * C; T* cd2 = cd1 + C;
     // everything that does not depend on the test inputs (:141-155)
     hipLaunchKernelGGL((diag_embed_kernel<T>), dim3(gridn(MM)), dim3(256), 0, st, M, sdiag, Su);
-    int rc = mxf_gemm_internal(h, dtype, 0, 1, M, M, M, 1.0, W, M, 0, W, M, 0, 1.0, Su, M, 0, 1, 0, st);                             // S = W W^T + diag :145
+    int rc = mxf_gemm_internal(h, st, {.dtype = dtype, .tb = 1, .M = M, .N = M, .K = M, .A = {W, M}, .B = {W, M}, .beta = 1.0, .C = {Su, M}});  // S = W W^T + diag :145
     if (rc) return rc;
     rc = mxf_gram(h, kind, dtype, 1, M, M, Q, Z, 0, nullptr, 0, ls, ard, 0, var, 0, nullptr, 0, jitter, MXF_WRITE, Lm, M, 0, st);     // Kuu (+ jitter) :146-148
     if (rc) return rc;
@@ -120,7 +127,7 @@ int svgp_predict_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t M, int64_
     MXF_HIP(h, hipMemcpyAsync(Linvmu, mu, sizeof(T) * M * P, hipMemcpyDeviceToDevice, st));
     rc = mxf_trsm_internal(h, dtype, 0, 1, M, P, Lm, M, 0, Linvmu, P, 0, 0, st);                                                     // L^-1 mu :152
     if (rc) return rc;
-    rc = mxf_gemm_internal(h, dtype, 0, 1, M, M, M, 1.0, LinvLs, M, 0, LinvLs, M, 0, 0.0, LSL, M, 0, 1, 0, st);                      // (L^-1 Ls)(L^-1 Ls)^T :153
+    rc = mxf_gemm_internal(h, st, {.dtype = dtype, .tb = 1, .M = M, .N = M, .K = M, .A = {LinvLs, M}, .B = {LinvLs, M}, .C = {LSL, M}});  // (L^-1 Ls)(L^-1 Ls)^T :153
     if (rc) return rc;
     MXF_HIP(h, hipMemcpyAsync(wv, Linvmu, sizeof(T) * M * P, hipMemcpyDeviceToDevice, st));
     rc = mxf_trsm_internal(h, dtype, 1, 1, M, P, Lm, M, 0, wv, P, 0, 0, st);                                                         // L^-T L^-1 mu :154
@@ -128,11 +135,11 @@ int svgp_predict_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t M, int64_
     // test inputs
     rc = mxf_gram(h, kind, dtype, 1, M, C, Q, Z, 0, Xt, 0, ls, ard, 0, var, 0, nullptr, 0, 0.0, MXF_WRITE, V, C, 0, st);             // Kxt :157
     if (rc) return rc;
-    rc = mxf_gemm_internal(h, dtype, 1, 0, C, P, M, 1.0, V, C, 0, wv, P, 0, 0.0, mean, P, 0, 1, 0, st);                               // Kxt^T wv :158
+    rc = mxf_gemm_internal(h, st, {.dtype = dtype, .ta = 1, .M = C, .N = P, .K = M, .A = {V, C}, .B = {wv, P}, .C = {mean, P}});      // Kxt^T wv :158
     if (rc) return rc;
     rc = mxf_trsm_internal(h, dtype, 0, 1, M, C, Lm, M, 0, V, C, 0, 0, st);                                                          // V = L^-1 Kxt :162
     if (rc) return rc;
-    rc = mxf_gemm_internal(h, dtype, 0, 0, M, C, M, 1.0, LSL, M, 0, V, C, 0, 0.0, tmp, C, 0, 1, 0, st);                               // :165
+    rc = mxf_gemm_internal(h, st, {.dtype = dtype, .M = M, .N = C, .K = M, .A = {LSL, M}, .B = {V, C}, .C = {tmp, C}});               // :165
     if (rc) return rc;
     if (!full_cov) {
         rc = mxf_coldot(h, dtype, 1, M, C, V, C, 0, V, C, 0, cd1, st);
@@ -143,9 +150,9 @@ int svgp_predict_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t M, int64_
     } else {
         rc = mxf_gram(h, kind, dtype, S, Nt, Nt, Q, Xt, Nt * Q, nullptr, 0, ls, ard, 0, var, 0, nullptr, 0, 0.0, MXF_WRITE, vout, Nt, Nt * Nt, st);
         if (rc) return rc;
-        rc = mxf_gemm_internal(h, dtype, 1, 0, Nt, Nt, M, -1.0, V, C, Nt, V, C, Nt, 1.0, vout, Nt, Nt * Nt, S, 0, st);               // :176-178
+        rc = cov_update(h, st, dtype, S, Nt, M, -1.0, V, V, vout);                                                                  // :176-178
         if (rc) return rc;
-        rc = mxf_gemm_internal(h, dtype, 1, 0, Nt, Nt, M, 1.0, V, C, Nt, tmp, C, Nt, 1.0, vout, Nt, Nt * Nt, S, 0, st);
+        rc = cov_update(h, st, dtype, S, Nt, M, 1.0, V, tmp, vout);
         if (rc) return rc;
         if (!noise_free) hipLaunchKernelGGL((add_diag_scalar_kernel<T>), dim3(gridn(C)), dim3(256), 0, st, (int64_t)S, Nt, vout, noise, (T)0);
     }

@@ -32,7 +32,7 @@ def _np(v):
 
 
 # ======================================================================================================================== mxf_gemm
-# Kernel reached by each shape (gemm.hip: gemm_typed / gemm_small_launch; t128 = ceil(M/128) ceil(N/128) batch, batch = 2):
+# Kernel reached by each shape (gemm_plan.h: gemm_plan; t128 = ceil(M/128) ceil(N/128) batch, batch = 2):
 #   float64, t128 <= 64                      -> gemm_small_f64_kernel (64 x 64 tiles, guarded scalar loaders); K >= 128 -> split-K + scale_kernel
 #   float64, t128 > 64, M % 128 == N % 128 == 0, K % 16 == 0, BOTH operands vectorisable (pointer % 16, ld % 2, stride % 2)
 #                                            -> gemm_f64_dma_kernel (LDS-DMA); one misaligned operand -> gemm_kernel<double>
