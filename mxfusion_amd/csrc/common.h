@@ -377,3 +377,13 @@ __device__ __forceinline__ double mxf_exp_nonpos_f64(double x) {   // e^x, x <= 
     p = fma(p, r, 1.0 / 24.0); p = fma(p, r, 1.0 / 6.0); p = fma(p, r, 0.5); p = fma(p, r, 1.0); p = fma(p, r, 1.0);
     return ldexp(p, (int)n);
 }
+// the covariance functions' scalar pieces in both precisions (gram.hip, gram2.hip)
+template <typename T> __device__ __forceinline__ T fast_exp2_neg(T x);   // 2^(-x), x >= 0
+template <> __device__ __forceinline__ float fast_exp2_neg<float>(float x) { return __builtin_amdgcn_exp2f(-x); }
+template <> __device__ __forceinline__ double fast_exp2_neg<double>(double x) { return mxf_exp2_neg_f64(x); }
+template <typename T> __device__ __forceinline__ T t_sqrt(T x);
+template <> __device__ __forceinline__ float t_sqrt<float>(float x) { return __builtin_sqrtf(x); }
+template <> __device__ __forceinline__ double t_sqrt<double>(double x) { return sqrt(x); }
+template <typename T> __device__ __forceinline__ T t_exp(T x);           // e^x, only called with x <= 0
+template <> __device__ __forceinline__ float t_exp<float>(float x) { return __expf(x); }
+template <> __device__ __forceinline__ double t_exp<double>(double x) { return mxf_exp_nonpos_f64(x); }

@@ -313,6 +313,17 @@ int by_dtype(mxf_ctx* h, const char* fn, int dtype, F&& f) {
     if (dtype == MXF_F64) return f(0.0);
     MXF_FAIL(h, -2, "%s: bad dtype %d", fn, dtype);
 }
+// The sparse models' two Grams, hyper-parameters shared by the samples.  Kuu = k(Z, Z) + jitter I (M x M) in float64:
+inline int kuu_f64(mxf_ctx* h, hipStream_t st, int kind, int64_t M, int Q, const double* Zd, const double* lsd, int ard, const double* vard, double jitter,
+                   double* Kuu) {
+    return mxf_gram_internal(h, st, {.kind = kind, .dtype = MXF_F64, .N = M, .Q = Q, .X = Zd, .ls = lsd, .ard = ard, .var = vard, .jitter = jitter,
+                                     .K = {Kuu, M, M * M}});
+}
+// ... and K = k(A, B) (n x n2, dense rows)
+inline int cross_gram(mxf_ctx* h, hipStream_t st, int kind, int dtype, int Q, int64_t n, const void* A, int64_t n2, const void* B, const void* ls, int ard,
+                      const void* var, void* K) {
+    return mxf_gram_internal(h, st, {.kind = kind, .dtype = dtype, .N = n, .N2 = n2, .Q = Q, .X = A, .X2 = B, .ls = ls, .ard = ard, .var = var, .K = {K, n2}});
+}
 
 // ================================================================================================ exact GP
 template <typename T>
@@ -329,7 +340,8 @@ int gp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t N, int Q, in
     if (!ok) MXF_FAIL(h, -4, "mxf_gp_logpdf: cannot allocate %zu bytes of scratch", need);
     int rc;
     // K = k(X,X) + (noise + jitter) I   (gp_regression.py:55-60), built straight into the L buffer
-    rc = mxf_gram(h, kind, dtype, S, N, N, Q, X, sX, nullptr, 0, ls, ard, sls, var, svar, noise, snoise, jitter, MXF_WRITE, L, N, NN, st);
+    rc = mxf_gram_internal(h, st, {.kind = kind, .dtype = dtype, .S = S, .N = N, .Q = Q, .X = X, .sX = sX, .ls = ls, .ard = ard, .sls = sls, .var = var,
+                                   .svar = svar, .diag_add = noise, .sdiag = snoise, .jitter = jitter, .K = {L, N, NN}});
     if (rc) return rc;
     // L^-1 Y (:66).  Large N with gradients: the reverse mode needs L^-1 anyway, and L^-1 Y as ONE product replaces N / 64 dependent
     // block steps (6.9 ms at N = 8192); small N keeps the reference's trsm.
@@ -1138,7 +1150,7 @@ struct SvgpCall : SvgpPlan {
             copy_convert(MM, mat.Kuu, Lm, st);
             if (jitter != 0.0) hipLaunchKernelGGL(add_diag_kernel, dim3(gridn(M)), dim3(256), 0, st, M, Lm, jitter);
         } else {
-            const int rc = mxf_gram(h, kind, MXF_F64, 1, M, M, Q, Zd, 0, nullptr, 0, lsd, ard, 0, vard, 0, nullptr, 0, jitter, MXF_WRITE, Lm, M, MM, st);   // Kuu (+jitter) :69-72
+            const int rc = kuu_f64(h, st, kind, M, Q, Zd, lsd, ard, vard, jitter, Lm);   // Kuu (+jitter) :69-72
             if (rc) return rc;
         }
         MXF_HIP(h, hipEventRecord(h->ev_fork, st));
@@ -1187,8 +1199,8 @@ struct SvgpCall : SvgpPlan {
             // whitened tier: only the Kfu planes (operand (n, k = m) of V = L^-1 Kuf); they need nothing from the core, so they are written
             // first; V, its transposition (+ U = a^T V) and Phi = V V^T follow on this stream once L^-1 exists (whiten_v_phi)
             MXF_T0(h, MXF_T_PLANES_A, sd_);
-            rc = mxf_gram_planes_internal(h, kind, SB, M, Q, (const float*)X, (const float*)Z, (const float*)ls, ard, (const float*)var, plKfu,
-                                          (int64_t)pl_big, gscr1, sd_, split_mode);
+            rc = mxf_gram_planes_internal(h, sd_, {.kind = kind, .R = SB, .Kn = M, .Q = Q, .Xmin = (const float*)X, .Xmaj = (const float*)Z, .ls = (const float*)ls,
+                                                   .ard = ard, .var = (const float*)var, .planes = plKfu, .pstride = (int64_t)pl_big, .scratch = gscr1});
             if (rc) return rc;
             MXF_T1(h, MXF_T_PLANES_A, sd_);
             MXF_STAGE(h, "Kfu planes (sd)", sd_);
@@ -1198,14 +1210,15 @@ struct SvgpCall : SvgpPlan {
             // (n, k = m): T GEMM and the w^T Kuf row) are then written (HBM bound) on the second side stream NEXT TO Psi2 (su_chain), unless
             // the T product reads these planes (bt_path).
             MXF_T0(h, MXF_T_PLANES_A, sd_);
-            rc = mxf_gram_planes_internal(h, kind, M, SB, Q, (const float*)Z, (const float*)X, (const float*)ls, ard, (const float*)var, plKuf,
-                                          (int64_t)pl_big, gscr0, sd_, split_mode, nullptr, 0, nullptr, 0, het_stream ? (const float*)hcs : nullptr, nullptr, B);
+            rc = mxf_gram_planes_internal(h, sd_, {.kind = kind, .R = M, .Kn = SB, .Q = Q, .Xmin = (const float*)Z, .Xmaj = (const float*)X, .ls = (const float*)ls,
+                                                   .ard = ard, .var = (const float*)var, .planes = plKuf, .pstride = (int64_t)pl_big, .scratch = gscr0,
+                                                   .majs = het_stream ? (const float*)hcs : nullptr, .period = B});
             if (rc) return rc;
             MXF_T1(h, MXF_T_PLANES_A, sd_);
             MXF_STAGE(h, "Kuf planes (sd)", sd_);
             if (bt_path) MXF_HIP(h, hipEventRecord(h->ev_aux, sd_));     // the T product reads THESE planes
         } else {
-            rc = mxf_gram(h, kind, dtype, 1, M, SB, Q, Z, 0, X, 0, ls, ard, 0, var, 0, nullptr, 0, 0.0, MXF_WRITE, Kuf, SB, 0, sd_);          // Kuf_all = k(Z, X_all) :73
+            rc = cross_gram(h, sd_, kind, dtype, Q, M, Z, SB, X, ls, ard, var, Kuf);          // Kuf_all = k(Z, X_all) :73
             if (rc) return rc;
         }
         if (!use_split) MXF_HIP(h, hipEventRecord(h->ev_aux, sd_));          // Kuf ready: the T GEMM waits for it
@@ -1243,7 +1256,7 @@ struct SvgpCall : SvgpPlan {
                 if (rc) return rc;
             }
         } else {
-            rc = mxf_gram(h, kind, dtype, 1, SB, M, Q, X, 0, Z, 0, ls, ard, 0, var, 0, nullptr, 0, 0.0, MXF_WRITE, Kfu, M, 0, sd_);
+            rc = cross_gram(h, sd_, kind, dtype, Q, SB, X, M, Z, ls, ard, var, Kfu);
             if (rc) return rc;
             if (KA > 0) {
                 rc = mxf_gemm_internal(h, sd_, {.dtype = dtype, .ta = 1, .M = M, .N = M, .K = KA, .A = {Kfu, M}, .B = {Kfu, M}, .C = {Psi2, M}, .lower_only = 1,
@@ -1378,9 +1391,10 @@ struct SvgpCall : SvgpPlan {
             // alone.  A stream of its own for this pass changes nothing: H0, hence the T GEMM, waits for the same chain.)
             MXF_HIP(h, hipStreamWaitEvent(s2_, h->ev_aux2, 0));
             MXF_T0(h, MXF_T_PLANES_B, s2_);
-            rc = mxf_gram_planes_internal(h, kind, SB, M, Q, (const float*)X, (const float*)Z, (const float*)ls, ard, (const float*)var, plKfu,
-                                          (int64_t)pl_big, gscr1, s2_, split_mode, (const float*)wT, P, (float*)(Text + M * SB), SB, nullptr,
-                                          het_stream ? (const float*)hrs : nullptr, B);
+            rc = mxf_gram_planes_internal(h, s2_, {.kind = kind, .R = SB, .Kn = M, .Q = Q, .Xmin = (const float*)X, .Xmaj = (const float*)Z, .ls = (const float*)ls,
+                                                   .ard = ard, .var = (const float*)var, .planes = plKfu, .pstride = (int64_t)pl_big, .scratch = gscr1,
+                                                   .w = (const float*)wT, .Pw = P, .U = (float*)(Text + M * SB), .ldU = SB,
+                                                   .mins = het_stream ? (const float*)hrs : nullptr, .period = B});
             if (rc) return rc;
             MXF_T1(h, MXF_T_PLANES_B, s2_);
             MXF_STAGE(h, "Kfu planes + U (s2)", s2_);
@@ -1802,7 +1816,7 @@ int sgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int64_t B, int64_t M, int 
         return mxf_gemm_internal(h, st, {.dtype = MXF_F64, .ta = ta, .M = M, .N = n, .K = M, .A = {A, M}, .B = {Bm, n}, .C = {C, n}});
     };
     int rc;
-    rc = mxf_gram(h, kind, MXF_F64, 1, M, M, Q, Zd, 0, nullptr, 0, lsd, ard, 0, vard, 0, nullptr, 0, jitter, MXF_WRITE, Lm, M, MM, st);   // Kuu :69-72
+    rc = kuu_f64(h, st, kind, M, Q, Zd, lsd, ard, vard, jitter, Lm);   // Kuu :69-72
     if (rc) return rc;
     hipLaunchKernelGGL(norm1_sym16_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, st, M, (const double*)Lm, M, h->cond_dev);
     MXF_HIP(h, hipMemcpyAsync(Cm, Lm, MM * sizeof(D), hipMemcpyDeviceToDevice, st));
@@ -1817,9 +1831,9 @@ int sgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int64_t B, int64_t M, int 
     rc = mxf_sumlogdiag_internal(h, MXF_F64, 1, M, Lm, M, MM, sc + 0, st);
     if (rc) return rc;
     // streaming statistics: Psi2 = Kuf Kuf^T (TN on the transposed Gram), psi1 = Kuf Y, ups = |Y|^2
-    rc = mxf_gram(h, kind, dtype, 1, M, B, Q, Z, 0, X, 0, ls, ard, 0, var, 0, nullptr, 0, 0.0, MXF_WRITE, Kuf, B, 0, st);                 // Kuf :74
+    rc = cross_gram(h, st, kind, dtype, Q, M, Z, B, X, ls, ard, var, Kuf);                 // Kuf :74
     if (rc) return rc;
-    rc = mxf_gram(h, kind, dtype, 1, B, M, Q, X, 0, Z, 0, ls, ard, 0, var, 0, nullptr, 0, 0.0, MXF_WRITE, Kfu, M, 0, st);
+    rc = cross_gram(h, st, kind, dtype, Q, B, X, M, Z, ls, ard, var, Kfu);
     if (rc) return rc;
     rc = mxf_gemm_internal(h, st, {.dtype = dtype, .ta = 1, .M = M, .N = M, .K = B, .A = {Kfu, M}, .B = {Kfu, M}, .C = {Psi2, M}, .lower_only = 1});
     if (rc) return rc;

@@ -14,12 +14,21 @@
 //     never re-read by this kernel).
 #include "common.h"
 #include "internal.h"
+#include "gram_plan.h"
+#include <limits.h>
 #include <stdlib.h>
 #include <type_traits>
 
 namespace {
 
-constexpr int TR = 64;   // rows of X per block
+// f(std::integral_constant<int, V>) for the V among VS that equals v; NO_CASE: none does
+constexpr int NO_CASE = INT_MIN;
+template <int... VS, typename F>
+int dispatch(int v, F&& f) {
+    int rc = NO_CASE;
+    (void)((v == VS && ((rc = f(std::integral_constant<int, VS>{})), true)) || ...);
+    return rc;
+}
 
 template <typename T>
 struct GramArgs {
@@ -28,21 +37,10 @@ struct GramArgs {
     T* K;
     int64_t N, N2, ldk;
     int64_t sX, sX2, sls, svar, sdadd, sK;
-    int Q, ard, square, mode, vecst, tr, nt;
+    int Q, ard, square, mode, vecst, tr;
     unsigned ncb;          // column blocks (grid.x = ncb * row blocks, column block fastest)
     T jitter;
 };
-
-template <typename T> __device__ __forceinline__ T fast_exp2_neg(T x);   // 2^(-x), x >= 0
-template <> __device__ __forceinline__ float fast_exp2_neg<float>(float x) { return __builtin_amdgcn_exp2f(-x); }
-template <> __device__ __forceinline__ double fast_exp2_neg<double>(double x) { return mxf_exp2_neg_f64(x); }
-
-template <typename T> __device__ __forceinline__ T t_sqrt(T x);
-template <> __device__ __forceinline__ float t_sqrt<float>(float x) { return __builtin_sqrtf(x); }
-template <> __device__ __forceinline__ double t_sqrt<double>(double x) { return sqrt(x); }
-template <typename T> __device__ __forceinline__ T t_exp(T x);
-template <> __device__ __forceinline__ float t_exp<float>(float x) { return __expf(x); }
-template <> __device__ __forceinline__ double t_exp<double>(double x) { return mxf_exp_nonpos_f64(x); }   // only called with x <= 0
 
 // coordinate pre-scale so that the RBF epilogue is a bare exp2:  exp(-r2/2) = 2^-(c^2 r2), c^2 = log2(e)/2
 template <typename T, int KIND> __device__ __forceinline__ T coord_scale() {
@@ -75,15 +73,15 @@ __device__ __forceinline__ double exp2_64ths_tab(double t, const double* __restr
     return ldexp(p * tab[mi & 63], mi >> 6);
 }
 
-// NW = waves per workgroup.  The x rows are read through wave-uniform (scalar) loads straight from the pre-scaled copy: no LDS, no
-// barrier, and with NW = 1 every wave is its own workgroup, dispatched and retired independently (measured on MI355X, f32 RBF N=65536:
+// One-wave workgroups.  The x rows are read through wave-uniform (scalar) loads straight from the pre-scaled copy: no LDS, no
+// barrier, and every wave is its own workgroup, dispatched and retired independently (measured on MI355X, f32 RBF N=65536:
 // 4-wave blocks with an LDS x tile 5.67 TB/s, 4-wave blocks with scalar x 5.86, single-wave blocks with scalar x 6.52 TB/s --
 // tests/probes/gram_variants.hip).
 // FAST: plain overwrite (MXF_WRITE), 16-byte-aligned rows and N2 a multiple of VEC -- every store is one full 16-byte store and the
 // accumulate / ragged-edge code (and its registers: 86 -> <= 64 VGPRs, i.e. 8 waves per SIMD) is compiled out.
-template <typename T, int QT, int KIND, int NW, bool FAST>
-__global__ __launch_bounds__(NW * 64) void gram_kernel(GramArgs<T> a, const T* __restrict__ Xs_all, const T* __restrict__ Zs_all,
-                                                       T* __restrict__ K_all) {
+template <typename T, int QT, int KIND, bool FAST>
+__global__ __launch_bounds__(64) void gram_kernel(GramArgs<T> a, const T* __restrict__ Xs_all, const T* __restrict__ Zs_all,
+                                                  T* __restrict__ K_all) {
     // (the three array pointers are separate __restrict__ kernel arguments: only then may the compiler read the x rows with SCALAR
     //  loads -- a pointer inside the by-value struct could alias the output and would be fetched with per-lane vector loads)
     const int MODE = FAST ? (int)MXF_WRITE : a.mode;
@@ -91,11 +89,12 @@ __global__ __launch_bounds__(NW * 64) void gram_kernel(GramArgs<T> a, const T* _
     constexpr int VEC = Vec16<T>::n;
     typedef typename Vec16<T>::type V;
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = NW == 1 ? 0 : tid >> 6;
+    const int lane = threadIdx.x & 63;
     const int s = blockIdx.z;
-    const int TRr = a.tr;                       // rows per block (<= TR)
+    const int TRr = a.tr;                       // rows per block
     const int64_t row0 = (int64_t)(blockIdx.x / a.ncb) * TRr;
-    const int64_t col0 = ((int64_t)(blockIdx.x % a.ncb) * NW + wave) * (64 * VEC) + (int64_t)lane * VEC;
+    const int64_t wcol0 = (int64_t)(blockIdx.x % a.ncb) * (64 * VEC);      // first column of the wave (wave-uniform)
+    const int64_t col0 = wcol0 + (int64_t)lane * VEC;
     if (col0 >= a.N2 || row0 >= a.N) return;
 
     const T variance = (KIND == MXF_K_LINEAR) ? (T)1 : a.var[(int64_t)s * a.svar];
@@ -122,7 +121,6 @@ __global__ __launch_bounds__(NW * 64) void gram_kernel(GramArgs<T> a, const T* _
     // WHITE kernel) is a compile-time flag: only the few waves whose tile touches the diagonal run the variant with the compares.
     // the "+ noise / jitter on the diagonal" and the WHITE kernel touch one element per row: a SCALAR test (is this row inside the
     // wave's column range?) guards the per-lane compares, so the row loop carries no vector compare for them
-    const int64_t wcol0 = ((int64_t)(blockIdx.x % a.ncb) * NW + wave) * (64 * VEC);      // first column of the wave (wave-uniform)
     const bool diag_possible = __builtin_amdgcn_readfirstlane((int)(a.square && (KIND == MXF_K_WHITE || dadd != (T)0))) != 0;
     auto do_row = [&](int r) {
         const int64_t row = row0 + r;
@@ -184,7 +182,7 @@ __global__ __launch_bounds__(NW * 64) void gram_kernel(GramArgs<T> a, const T* _
             T* po = reinterpret_cast<T*>(&out);
 #pragma unroll
             for (int v = 0; v < VEC; ++v) po[v] = kv[v];
-            if (MODE == MXF_WRITE && (FAST || a.nt)) __builtin_nontemporal_store(out, reinterpret_cast<V*>(dst));
+            if (MODE == MXF_WRITE) __builtin_nontemporal_store(out, reinterpret_cast<V*>(dst));
             else *reinterpret_cast<V*>(dst) = out;
         } else {
 #pragma unroll
@@ -400,84 +398,88 @@ __global__ __launch_bounds__(256) void gram_generic_kernel(GramArgs<T> a) {
     }
 }
 
+// one operand's padded copy: S sample copies (grid.y) of pad rows
+template <typename T, int QT, int KIND>
+void prescale(hipStream_t st, int S, const T* X, int64_t sX, const T* ls, int64_t sls, int ard, int64_t N, int Q, int64_t pad, T* out, T* norms,
+              int raw, const T* centre, int64_t sC) {
+    hipLaunchKernelGGL((prescale_kernel<T, QT, KIND>), dim3((unsigned)((pad * QT + 255) / 256), (unsigned)S), dim3(256), 0, st, X, sX, ls, sls, ard,
+                       N, Q, pad, out, norms, raw, centre, sC);
+}
+
+// buf: the scratch the plan laid out (nullptr: the path takes none)
+template <typename T>
+GramArgs<T> gram_args(const MxfGram& d, const GramPlan& p, const T* buf, bool vec_ok) {
+    GramArgs<T> a{};
+    a.square = d.X2 == nullptr;
+    a.X = (const T*)d.X; a.X2 = a.square ? a.X : (const T*)d.X2; a.sX = d.sX; a.sX2 = a.square ? d.sX : d.sX2;
+    a.ls = (const T*)d.ls; a.sls = d.sls; a.ard = d.ard; a.var = (const T*)d.var; a.svar = d.svar;
+    a.dadd = (const T*)d.diag_add; a.sdadd = d.sdiag; a.jitter = (T)d.jitter;
+    if (buf) { a.Xs = buf + p.xs; a.Zs = buf + p.zs; a.sXs = p.sxs; a.sZs = p.szs; }
+    a.K = (T*)d.K.p; a.ldk = d.K.ld; a.sK = d.K.stride;
+    a.N = d.N; a.N2 = a.square ? d.N : d.N2; a.Q = d.Q;
+    a.mode = d.mode; a.vecst = vec_ok; a.tr = p.tr; a.ncb = p.ncb;
+    return a;
+}
+
+// the coordinate kernels (Q <= 16): the pre-scaled copies into the handle's Gram scratch, then the plan's path
+template <typename T, int KIND, int QT>
+int gram_coord(mxf_ctx* h, hipStream_t st, const MxfGram& d, const GramPlan& p, bool vec_ok) {
+    using namespace mxf_gram_tiles;
+    constexpr bool RBF = KIND == MXF_K_RBF;
+    constexpr int XF = (RBF && sizeof(T) == 8) ? 1 : 0, TRC = RBF ? (sizeof(T) == 4 ? TR_RBF_F32 : TR_RBF_F64) : 0;      // gram_lean_kernel's form of this (T, KIND)
+    T* buf = nullptr;
+    if (p.bytes) {
+        buf = (T*)mxf_gram_ws(h, p.bytes);
+        if (!buf) MXF_FAIL(h, -4, "mxf_gram: cannot allocate %zu bytes for the pre-scaled coordinates", p.bytes);
+    }
+    const GramArgs<T> a = gram_args<T>(d, p, buf, vec_ok);
+    const bool xf = p.path == MXF_GRAM_LEAN_XF;
+    if (buf) {
+        const T* cen = p.centre == MXF_GRAM_CENTRE_NONE ? nullptr : (p.centre == MXF_GRAM_CENTRE_X2 ? a.X2 : a.X);
+        prescale<T, QT, KIND>(st, p.Sx, a.X, a.sX, a.ls, a.sls, a.ard, a.N, a.Q, p.padx, buf + p.xs, xf ? buf + p.xn : nullptr, 0, cen, p.scen);
+        if (!a.square)
+            prescale<T, QT, KIND>(st, p.Sz, a.X2, a.sX2, a.ls, a.sls, a.ard, a.N2, a.Q, p.padc, buf + p.zs, xf ? buf + p.zn : nullptr, 0, cen, p.scen);
+    }
+    const dim3 g(p.grid[0], p.grid[1], p.grid[2]);
+    if (p.path == MXF_GRAM_LEAN || xf) {
+        const bool hd = a.square && a.dadd != nullptr;
+        GramLean<T> l;
+        l.N = a.N; l.N2 = a.N2; l.ldk = a.ldk; l.sXs = a.sXs; l.sZs = a.sZs; l.sK = a.sK; l.svar = a.svar; l.sXn = p.sxn; l.sZn = p.szn;
+        l.tr = a.tr; l.has_diag = p.has_diag;
+        l.sdadd = hd ? a.sdadd : 0; l.dscale = hd ? (T)1 : (T)0; l.jitter = a.square ? a.jitter : (T)0;
+        const T* dptr = hd ? a.dadd : (a.var ? a.var : a.Xs);          // any readable word when there is no diagonal term
+        hipLaunchKernelGGL((gram_lean_kernel<T, QT, KIND, XF, TRC>), g, dim3(64), 0, st, a.Xs, a.Zs, a.K, a.var, dptr,
+                           xf ? (const T*)(buf + p.xn) : nullptr, xf ? (const T*)(buf + p.zn) : nullptr, l);
+    } else if (p.path == MXF_GRAM_COORD_FAST) hipLaunchKernelGGL((gram_kernel<T, QT, KIND, true>), g, dim3(64), 0, st, a, a.Xs, a.Zs, a.K);
+    else hipLaunchKernelGGL((gram_kernel<T, QT, KIND, false>), g, dim3(64), 0, st, a, a.Xs, a.Zs, a.K);
+    MXF_LAUNCH_CHECK(h);
+    return 0;
+}
+
 template <typename T, int KIND>
-int launch_kind(mxf_ctx* h, GramArgs<T> a, int S, int mode, hipStream_t st) {
+int launch_kind(mxf_ctx* h, hipStream_t st, const MxfGram& d) {
     constexpr int VEC = Vec16<T>::n;
-    if (mode < 0 || mode > 2) MXF_FAIL(h, -2, "mxf_gram: bad mode %d", mode);
-    a.mode = mode;
-    if (a.Q > 16) {
-        dim3 g((unsigned)((a.N2 + 255) / 256), (unsigned)(a.N < 65535 ? a.N : 65535), (unsigned)S);
-        hipLaunchKernelGGL((gram_generic_kernel<T, KIND>), g, dim3(256), 0, st, a);
+    if (d.mode < 0 || d.mode > 2) MXF_FAIL(h, -2, "mxf_gram: bad mode %d", d.mode);
+    const bool square = d.X2 == nullptr;
+    const bool vec_ok = (d.K.ld % VEC == 0) && (d.K.stride % VEC == 0) && (((uintptr_t)d.K.p) % 16 == 0);
+    const GramPlan p = gram_plan(KIND, sizeof(T), d.S, d.N, d.N2, d.Q, square, d.sX, d.sX2, d.sls, vec_ok, d.mode,
+                                 square && (d.diag_add != nullptr || (T)d.jitter != (T)0));
+    if (p.refusal) MXF_FAIL(h, p.rc, "mxf_gram: %s", p.refusal);
+    if (p.path == MXF_GRAM_GENERIC) {
+        hipLaunchKernelGGL((gram_generic_kernel<T, KIND>), dim3(p.grid[0], p.grid[1], p.grid[2]), dim3(mxf_gram_tiles::GENERIC_COLS), 0, st,
+                           gram_args<T>(d, p, nullptr, vec_ok));
         MXF_LAUNCH_CHECK(h);
         return 0;
     }
-    a.vecst = (a.ldk % VEC == 0) && (a.sK % VEC == 0) && (((uintptr_t)a.K) % 16 == 0);
-    // rows per block, measured on MI355X at N=65536, Q=8 (tests/probes/gram_variants.hip, tests/probes/gram_time.py): single-wave workgroups;
-    // float32 RBF 12 rows as a compile-time constant with the diagonal term hoisted (gram_lean_kernel TRC); float64 RBF in the expansion form
-    // (gram_lean_kernel XF) 16 rows (5.71 ms = 6.02 TB/s, 32: 5.95, 64: 6.36 ms); the VALU-heavier epilogues (Matern, ...) 64
-    a.tr = (KIND == MXF_K_RBF && sizeof(T) == 4) ? 12 : (KIND == MXF_K_RBF ? 16 : 64);
-    a.nt = 1;
-    const int64_t cw = 64 * VEC;                        // columns per workgroup
-    a.ncb = (unsigned)((a.N2 + cw - 1) / cw);
-    const int64_t nblk = (int64_t)a.ncb * ((a.N + a.tr - 1) / a.tr);
-    if (nblk > 2147483647LL) MXF_FAIL(h, -3, "mxf_gram: problem too large for one launch");
-    dim3 g((unsigned)nblk, 1, (unsigned)S);
-#define GO(QT)                                                                                                        \
-    do {                                                                                                              \
-        const bool fast = a.vecst && mode == MXF_WRITE && a.nt && (a.N2 % VEC == 0);                                  \
-        const bool lean_ok = fast && KIND != MXF_K_BIAS && KIND != MXF_K_WHITE && (a.N + a.tr - 1) / a.tr <= 65535; \
-        const bool xf = lean_ok && sizeof(T) == 8 && KIND == MXF_K_RBF;                                               \
-        T* xnorm = nullptr; T* znorm = nullptr; int64_t sxn = 0, szn = 0;                                             \
-        if (KIND != MXF_K_BIAS && KIND != MXF_K_WHITE) {                                                              \
-            const int64_t padr = (a.N + TR - 1) / TR * TR, padc = (a.N2 + 4 * 64 * VEC - 1) / (4 * 64 * VEC) * (4 * 64 * VEC); \
-            const int Sx = (a.sX == 0 && a.sls == 0) ? 1 : S, Sz = (a.sX2 == 0 && a.sls == 0) ? 1 : S;                \
-            /* the common centre of both operands: the first row of X, or of X2 when X is sampled and X2 shared (its pre-scaled copy is then \
-               shared by the samples and must not depend on one of them) */                                           \
-            const bool cen_x2_ = !a.square && a.sX != 0 && a.sX2 == 0 && a.X2 != nullptr;                             \
-            const T* cen_ = (KIND == MXF_K_LINEAR) ? (const T*)nullptr : (cen_x2_ ? a.X2 : a.X);                      \
-            const int64_t scen_ = cen_x2_ ? 0 : a.sX;                                                                 \
-            const int64_t padx = a.square ? (padr > padc ? padr : padc) : padr;                                       \
-            const size_t ncoord = ((size_t)Sx * padx + (a.square ? 0 : (size_t)Sz * padc)) * QT;                     \
-            const size_t need = (ncoord + (xf ? (size_t)Sx * padx + (a.square ? 0 : (size_t)Sz * padc) : 0)) * sizeof(T); \
-            T* buf = (T*)mxf_gram_ws(h, need);                                                                        \
-            if (!buf) MXF_FAIL(h, -4, "mxf_gram: cannot allocate %zu bytes for the pre-scaled coordinates", need);    \
-            xnorm = xf ? buf + ncoord : nullptr; sxn = (Sx == 1) ? 0 : padx;                                          \
-            hipLaunchKernelGGL((prescale_kernel<T, QT, KIND>), dim3((unsigned)((padx * QT + 255) / 256), Sx), dim3(256), 0, st, a.X, a.sX, \
-                               a.ls, a.sls, a.ard, a.N, a.Q, padx, buf, xnorm, 0, cen_, scen_);                       \
-            a.Xs = buf; a.sXs = (Sx == 1) ? 0 : padx * QT;                                                            \
-            if (a.square) { a.Zs = buf; a.sZs = a.sXs; znorm = xnorm; szn = sxn; }                                    \
-            else {                                                                                                    \
-                T* bz = buf + (size_t)Sx * padx * QT;                                                                 \
-                znorm = xf ? xnorm + (size_t)Sx * padx : nullptr; szn = (Sz == 1) ? 0 : padc;                         \
-                hipLaunchKernelGGL((prescale_kernel<T, QT, KIND>), dim3((unsigned)((padc * QT + 255) / 256), Sz), dim3(256), 0, st, a.X2, \
-                                   a.sX2, a.ls, a.sls, a.ard, a.N2, a.Q, padc, bz, znorm, 0, cen_, scen_);            \
-                a.Zs = bz; a.sZs = (Sz == 1) ? 0 : padc * QT;                                                         \
-            }                                                                                                         \
-        }                                                                                                             \
-        if (lean_ok) {                                                                                                \
-            GramLean<T> l;                                                                                            \
-            l.N = a.N; l.N2 = a.N2; l.ldk = a.ldk; l.sXs = a.sXs; l.sZs = a.sZs; l.sK = a.sK; l.svar = a.svar; l.tr = a.tr; \
-            const bool hd = a.square && a.dadd != nullptr;                                                            \
-            l.sdadd = hd ? a.sdadd : 0; l.dscale = hd ? (T)1 : (T)0; l.jitter = a.square ? a.jitter : (T)0;           \
-            l.has_diag = ((hd || l.jitter != (T)0) ? 1 : 0) | ((xf && a.square) ? 2 : 0); l.sXn = sxn; l.sZn = szn;   \
-            const T* dptr = hd ? a.dadd : (a.var ? a.var : a.Xs);          /* any readable word when there is no diagonal term */ \
-            dim3 gl(a.ncb, (unsigned)((a.N + a.tr - 1) / a.tr), (unsigned)S);                                         \
-            if constexpr (sizeof(T) == 8 && KIND == MXF_K_RBF)                                                        \
-                hipLaunchKernelGGL((gram_lean_kernel<T, QT, KIND, 1, 16>), gl, dim3(64), 0, st, a.Xs, a.Zs, a.K, a.var, dptr, (const T*)xnorm, (const T*)znorm, l); \
-            else if constexpr (sizeof(T) == 4 && KIND == MXF_K_RBF)                                                   \
-                hipLaunchKernelGGL((gram_lean_kernel<T, QT, KIND, 0, 12>), gl, dim3(64), 0, st, a.Xs, a.Zs, a.K, a.var, dptr, (const T*)nullptr, (const T*)nullptr, l); \
-            else hipLaunchKernelGGL((gram_lean_kernel<T, QT, KIND, 0, 0>), gl, dim3(64), 0, st, a.Xs, a.Zs, a.K, a.var, dptr, (const T*)nullptr, (const T*)nullptr, l); \
-        } else if (fast) hipLaunchKernelGGL((gram_kernel<T, QT, KIND, 1, true>), g, dim3(64), 0, st, a, a.Xs, a.Zs, a.K); \
-        else hipLaunchKernelGGL((gram_kernel<T, QT, KIND, 1, false>), g, dim3(64), 0, st, a, a.Xs, a.Zs, a.K);                         \
-    } while (0)
-    if (KIND == MXF_K_BIAS || KIND == MXF_K_WHITE) GO(2);
-    else if (a.Q <= 2) GO(2);
-    else if (a.Q <= 4) GO(4);
-    else if (a.Q <= 8) GO(8);
-    else GO(16);
-#undef GO
-    MXF_LAUNCH_CHECK(h);
-    return 0;
+    return dispatch<2, 4, 8, 16>(p.QT, [&](auto qt) { return gram_coord<T, KIND, decltype(qt)::value>(h, st, d, p, vec_ok); });
+}
+
+template <typename T>
+int gram_typed(mxf_ctx* h, hipStream_t st, const MxfGram& d) {
+    const int rc = dispatch<MXF_K_RBF, MXF_K_MATERN12, MXF_K_MATERN32, MXF_K_MATERN52, MXF_K_LINEAR, MXF_K_BIAS, MXF_K_WHITE>(
+        d.kind, [&](auto kind) { return launch_kind<T, decltype(kind)::value>(h, st, d); });
+    if (rc == NO_CASE) MXF_FAIL(h, -2, "mxf_gram: unknown kernel kind %d", d.kind);
+    return rc;
 }
 
 // ---- Gram matrix written as split planes (the f16x2 operand format of gemm_split.hip: two scaled f16 terms) ---------------------------
@@ -498,7 +500,7 @@ typedef unsigned int gp_u32x4 __attribute__((ext_vector_type(4)));
 // Measured (planes_store.hip): 1.82 / 1.69 ms for the two 8.6 GB passes of the bench step, the same as the r02 staged kernel (LDS, 256
 // threads, a thread <-> (row, k half)) -- neither the LDS staging nor the VALU count (16 -> 14 instructions per covariance here) is what bounds them; the store-only twin
 // of the same pattern takes 1.45 - 1.65 ms alone, memset 1.36 ms; PLAIN instead of non-temporal stores: 2.1 - 2.4 ms inside the step.
-// ACC (r04): the squared distance as sum_q ((x_q - z_q)^2) (c / l_q)^2 from the RAW coordinates -- difference first, scale after -- instead of
+// (r04) The squared distance as sum_q ((x_q - z_q)^2) (c / l_q)^2 from the RAW coordinates -- difference first, scale after -- instead of
 // the difference of pre-scaled coordinates: the rounding of x / l (2^-24 |x / l|) no longer enters r^2 of NEAR pairs, the ones that carry the
 // covariance.  At length-scale 0.2 on [-2, 2] (a deep GP's hidden layer) the pre-scaled form's Gram error, amplified by |T| ~ sqrt(cond) in
 // q_n = k_n . T_n, was 2/3 of the whitened tier's ELBO error (3.9e-5 -> 4e-6 relative; tests/test_gpu_f32_guard.py two-layer case).
@@ -515,24 +517,22 @@ typedef unsigned int gp_u32x4 __attribute__((ext_vector_type(4)));
 #else
 #define MXF_PLANES_OCC
 #endif
-template <int QT, int KIND, int PT, bool ACC = false>
+template <int QT, int KIND, int PT>
 __global__ __launch_bounds__(64) MXF_PLANES_OCC void gram_planes_lean_kernel(int64_t R, int64_t Kn, const float* __restrict__ Xmin_s, const float* __restrict__ Xmaj_s,
                                                               const float* __restrict__ var, unsigned short* __restrict__ P, int64_t pstride,
                                                               int kb_per_block, const float* __restrict__ wk, int Pw, float* __restrict__ U,
-                                                              int64_t ldU, const float* __restrict__ ls = nullptr, int ard = 0, int Q = 0,
-                                                              const float* __restrict__ majs = nullptr, const float* __restrict__ mins = nullptr,
-                                                              int64_t period = 1) {
-    // majs / mins (ACC form only; the streaming heteroscedastic SVGP bound, svgp_regression.py:61-67): every covariance is multiplied by
+                                                              int64_t ldU, const float* __restrict__ ls, int ard, int Q,
+                                                              const float* __restrict__ majs, const float* __restrict__ mins, int64_t period) {
+    // Xmin_s / Xmaj_s: the RAW coordinates, zero-padded to QT (prescale_kernel raw); ls, ard, Q: the length-scales the differences are scaled by.
+    // majs / mins (optional; the streaming heteroscedastic SVGP bound, svgp_regression.py:61-67): every covariance is multiplied by
     // majs[major index % period] (wave-uniform) and / or mins[minor index % period] (per lane) before it is split into planes -- and before
     // it enters the fused row U -- i.e. the planes hold K diag(s) resp. diag(s) K for per-row weights s <= 1
     const int lane = threadIdx.x;
     float s2[QT];
-    if constexpr (ACC) {
 #pragma unroll
-        for (int q = 0; q < QT; ++q) {
-            const float m = q < Q ? coord_scale<float, KIND>() / ls[ard ? q : 0] : 0.f;      // wave-uniform: scalar loads
-            s2[q] = m * m;
-        }
+    for (int q = 0; q < QT; ++q) {
+        const float m = q < Q ? coord_scale<float, KIND>() / ls[ard ? q : 0] : 0.f;      // wave-uniform: scalar loads
+        s2[q] = m * m;
     }
     const int64_t bxi = blockIdx.x;
     const int byi = blockIdx.y;
@@ -541,7 +541,7 @@ __global__ __launch_bounds__(64) MXF_PLANES_OCC void gram_planes_lean_kernel(int
 #pragma unroll
     for (int q = 0; q < QT; q += 4) *reinterpret_cast<f32x4_t*>(&z[q]) = *reinterpret_cast<const f32x4_t*>(Xmin_s + r * QT + q);   // padded
     float mscale = 1.f;
-    if constexpr (ACC) { if (mins) mscale = mins[(r < R ? r : R - 1) % period]; }
+    if (mins) mscale = mins[(r < R ? r : R - 1) % period];
     float uacc[PT > 0 ? PT : 1];
 #pragma unroll
     for (int p = 0; p < (PT > 0 ? PT : 1); ++p) uacc[p] = 0.f;
@@ -569,15 +569,13 @@ __global__ __launch_bounds__(64) MXF_PLANES_OCC void gram_planes_lean_kernel(int
                     const f32x2 xx = {xk[nl * QT + q], xk[nl * QT + q + 1]};
                     const f32x2 zz = {z[q], z[q + 1]};
                     const f32x2 d = xx - zz;
-                    if constexpr (ACC) { const f32x2 ss = {s2[q], s2[q + 1]}; acc2 = __builtin_elementwise_fma(d * d, ss, acc2); }
-                    else acc2 = __builtin_elementwise_fma(d, d, acc2);
+                    const f32x2 ss = {s2[q], s2[q + 1]};
+                    acc2 = __builtin_elementwise_fma(d * d, ss, acc2);
                 }
                 const float red = acc2.x + acc2.y;
                 float kv = (FULL || kb * 16 + nl < Kn) ? cov_from<float, KIND>(red, 16384.f) : 0.f;
-                if constexpr (ACC) {
-                    if (majs) { const int64_t km = FULL ? kb * 16 + nl : ((kb * 16 + nl < Kn) ? kb * 16 + nl : Kn - 1); kv *= majs[km % period]; }
-                    if (mins) kv *= mscale;
-                }
+                if (majs) { const int64_t km = FULL ? kb * 16 + nl : ((kb * 16 + nl < Kn) ? kb * 16 + nl : Kn - 1); kv *= majs[km % period]; }
+                if (mins) kv *= mscale;
                 if (PT > 0) {
                     const int64_t kk = FULL ? kb * 16 + nl : ((kb * 16 + nl < Kn) ? kb * 16 + nl : Kn - 1);     // (kv == 0 beyond Kn)
 #pragma unroll
@@ -624,66 +622,39 @@ __global__ __launch_bounds__(64) MXF_PLANES_OCC void gram_planes_lean_kernel(int
     }
 }
 
-template <int KIND>
-int gram_planes_kind(mxf_ctx* h, int64_t R, int64_t Kn, int Q, const float* Xmin, const float* Xmaj, const float* ls, int ard,
-                     const float* var, unsigned short* planes, int64_t pstride, float* scratch, hipStream_t st, int mode,
-                     const float* wk, int Pw, float* U, int64_t ldU, const float* majs, const float* mins, int64_t period) {
-    const int QT = Q <= 8 ? 8 : 16;
-    const int64_t padr = (R + 127) / 128 * 128, padk = ((Kn + 15) / 16 + 15) / 16 * 256;
-    float* buf = scratch;     // (padr + padk) * QT floats, caller-owned: two of these run concurrently on different streams
-    float* bmaj = buf + (size_t)padr * QT;
-    const int64_t K16 = (Kn + 15) / 16;
-    const bool fuse_u = U != nullptr;
-    if (fuse_u && (Pw > 8 || !wk)) MXF_FAIL(h, -3, "gram planes: fused w^T K needs w and P <= 8");
-    if (mode != MXF_SPLIT_F16X2) MXF_FAIL(h, -3, "gram planes: the f16x2 format only");
-    const int raw = 1;                // difference-then-scale distances (gram_planes_lean_kernel ACC)
-    int kbpb = fuse_u ? (int)K16 : (int)MXF_KNOB("MXF_PLANES_KB", 8);
-    while (!fuse_u && (K16 + kbpb - 1) / kbpb > 65535) kbpb *= 2;
-    dim3 lgrid((unsigned)((R + 63) / 64), (unsigned)((K16 + kbpb - 1) / kbpb));
-#define GO(QTV)                                                                                                                       \
-    do {                                                                                                                              \
-        hipLaunchKernelGGL((prescale_kernel<float, QTV, KIND>), dim3((unsigned)((padr * QTV + 255) / 256), 1), dim3(256), 0, st, Xmin, (int64_t)0, ls, \
-                           (int64_t)0, ard, R, Q, padr, buf, (float*)nullptr, raw);                                                   \
-        hipLaunchKernelGGL((prescale_kernel<float, QTV, KIND>), dim3((unsigned)((padk * QTV + 255) / 256), 1), dim3(256), 0, st, Xmaj, (int64_t)0, ls, \
-                           (int64_t)0, ard, Kn, Q, padk, bmaj, (float*)nullptr, raw);                                                 \
-        if (fuse_u && Pw == 1)                                                                                                        \
-            hipLaunchKernelGGL((gram_planes_lean_kernel<QTV, KIND, 1, true>), lgrid, dim3(64), 0, st, R, Kn, (const float*)buf, (const float*)bmaj, var, planes, pstride, kbpb, wk, Pw, U, ldU, ls, ard, Q, majs, mins, period); \
-        else if (fuse_u)                                                                                                              \
-            hipLaunchKernelGGL((gram_planes_lean_kernel<QTV, KIND, 8, true>), lgrid, dim3(64), 0, st, R, Kn, (const float*)buf, (const float*)bmaj, var, planes, pstride, kbpb, wk, Pw, U, ldU, ls, ard, Q, majs, mins, period); \
-        else                                                                                                                          \
-            hipLaunchKernelGGL((gram_planes_lean_kernel<QTV, KIND, 0, true>), lgrid, dim3(64), 0, st, R, Kn, (const float*)buf, (const float*)bmaj, var, planes, pstride, kbpb, wk, Pw, U, ldU, ls, ard, Q, majs, mins, period); \
-    } while (0)
-    if (QT == 8) GO(8); else GO(16);
-#undef GO
+// the padded RAW coordinates of both operands into the caller's scratch (difference-then-scale distances, above), then the pass
+template <int KIND, int QT>
+int gram_planes_launch(mxf_ctx* h, hipStream_t st, const MxfGramPlanes& d, const GramPlanesPlan& p) {
+    float* bmin = d.scratch;
+    float* bmaj = bmin + (size_t)p.padr * QT;
+    prescale<float, QT, KIND>(st, 1, d.Xmin, 0, d.ls, 0, d.ard, d.R, d.Q, p.padr, bmin, nullptr, 1, nullptr, 0);
+    prescale<float, QT, KIND>(st, 1, d.Xmaj, 0, d.ls, 0, d.ard, d.Kn, d.Q, p.padk, bmaj, nullptr, 1, nullptr, 0);
+    dispatch<0, 1, 8>(p.PT, [&](auto pt) {
+        hipLaunchKernelGGL((gram_planes_lean_kernel<QT, KIND, decltype(pt)::value>), dim3(p.grid[0], p.grid[1]), dim3(64), 0, st, d.R, d.Kn,
+                           (const float*)bmin, (const float*)bmaj, d.var, d.planes, d.pstride, p.kbpb, d.w, d.Pw, d.U, d.ldU, d.ls, d.ard, d.Q,
+                           d.majs, d.mins, d.period);
+        return 0;
+    });
     MXF_LAUNCH_CHECK(h);
     return 0;
 }
 
-template <typename T>
-int gram_typed(mxf_ctx* h, int kind, int S, int64_t N, int64_t N2, int Q,
-               const void* X, int64_t sX, const void* X2, int64_t sX2, const void* ls, int ard, int64_t sls,
-               const void* var, int64_t svar, const void* dadd, int64_t sdadd, double jitter, int mode,
-               void* K, int64_t ldk, int64_t sK, hipStream_t st) {
-    GramArgs<T> a;
-    a.X = (const T*)X; a.square = (X2 == nullptr);
-    a.X2 = a.square ? (const T*)X : (const T*)X2;
-    a.sX = sX; a.sX2 = a.square ? sX : sX2;
-    a.ls = (const T*)ls; a.sls = sls; a.var = (const T*)var; a.svar = svar;
-    a.dadd = (const T*)dadd; a.sdadd = sdadd; a.jitter = (T)jitter;
-    a.K = (T*)K; a.N = N; a.N2 = a.square ? N : N2; a.ldk = ldk; a.sK = sK; a.Q = Q; a.ard = ard;
-    switch (kind) {
-        case MXF_K_RBF: return launch_kind<T, MXF_K_RBF>(h, a, S, mode, st);
-        case MXF_K_MATERN12: return launch_kind<T, MXF_K_MATERN12>(h, a, S, mode, st);
-        case MXF_K_MATERN32: return launch_kind<T, MXF_K_MATERN32>(h, a, S, mode, st);
-        case MXF_K_MATERN52: return launch_kind<T, MXF_K_MATERN52>(h, a, S, mode, st);
-        case MXF_K_LINEAR: return launch_kind<T, MXF_K_LINEAR>(h, a, S, mode, st);
-        case MXF_K_BIAS: return launch_kind<T, MXF_K_BIAS>(h, a, S, mode, st);
-        case MXF_K_WHITE: return launch_kind<T, MXF_K_WHITE>(h, a, S, mode, st);
-    }
-    MXF_FAIL(h, -2, "mxf_gram: unknown kernel kind %d", kind);
-}
-
 }  // namespace
+
+int mxf_gram_internal(mxf_ctx* h, hipStream_t st, const MxfGram& d) {
+    if (d.S <= 0 || d.N < 0 || d.N2 < 0 || d.Q <= 0)
+        MXF_FAIL(h, -2, "mxf_gram: bad shape S=%d N=%lld N2=%lld Q=%d", d.S, (long long)d.N, (long long)d.N2, d.Q);
+    const int64_t n2 = d.X2 ? d.N2 : d.N;
+    if (d.N == 0 || n2 == 0) return 0;
+    if (!d.X || !d.K.p) MXF_FAIL(h, -2, "mxf_gram: null X or K_out");
+    if (d.kind != MXF_K_BIAS && d.kind != MXF_K_WHITE && !d.ls) MXF_FAIL(h, -2, "mxf_gram: null lengthscale/variances");
+    if (d.kind != MXF_K_LINEAR && !d.var) MXF_FAIL(h, -2, "mxf_gram: null variance");
+    if (d.K.ld < n2) MXF_FAIL(h, -2, "mxf_gram: ldk < N2");
+    if (d.S > 65535) MXF_FAIL(h, -3, "mxf_gram: S too large");
+    if (d.dtype == MXF_F32) return gram_typed<float>(h, st, d);
+    if (d.dtype == MXF_F64) return gram_typed<double>(h, st, d);
+    MXF_FAIL(h, -2, "mxf_gram: bad dtype %d", d.dtype);
+}
 
 extern "C" int mxf_gram(mxf_handle h, int kind, int dtype, int S, int64_t N, int64_t N2, int Q,
                         const void* X, int64_t strideS_X, const void* X2, int64_t strideS_X2,
@@ -692,45 +663,26 @@ extern "C" int mxf_gram(mxf_handle h, int kind, int dtype, int S, int64_t N, int
                         const void* diag_add, int64_t strideS_diag, double jitter, int mode,
                         void* K_out, int64_t ldk, int64_t strideS_K, void* stream) {
     if (!h) return -1;
-    if (S <= 0 || N < 0 || N2 < 0 || Q <= 0) MXF_FAIL(h, -2, "mxf_gram: bad shape S=%d N=%lld N2=%lld Q=%d", S, (long long)N, (long long)N2, Q);
-    const int64_t n2 = X2 ? N2 : N;
-    if (N == 0 || n2 == 0) return 0;
-    if (!X || !K_out) MXF_FAIL(h, -2, "mxf_gram: null X or K_out");
-    if (kind != MXF_K_BIAS && kind != MXF_K_WHITE && !lengthscale) MXF_FAIL(h, -2, "mxf_gram: null lengthscale/variances");
-    if (kind != MXF_K_LINEAR && !variance) MXF_FAIL(h, -2, "mxf_gram: null variance");
-    if (ldk < n2) MXF_FAIL(h, -2, "mxf_gram: ldk < N2");
-    if (S > 65535) MXF_FAIL(h, -3, "mxf_gram: S too large");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MXF_F32)
-        return gram_typed<float>(h, kind, S, N, N2, Q, X, strideS_X, X2, strideS_X2, lengthscale, ard, strideS_ls,
-                                 variance, strideS_var, diag_add, strideS_diag, jitter, mode, K_out, ldk, strideS_K, st);
-    if (dtype == MXF_F64)
-        return gram_typed<double>(h, kind, S, N, N2, Q, X, strideS_X, X2, strideS_X2, lengthscale, ard, strideS_ls,
-                                  variance, strideS_var, diag_add, strideS_diag, jitter, mode, K_out, ldk, strideS_K, st);
-    MXF_FAIL(h, -2, "mxf_gram: bad dtype %d", dtype);
+    return mxf_gram_internal(h, (hipStream_t)stream,
+                             {.kind = kind, .dtype = dtype, .S = S, .N = N, .N2 = N2, .Q = Q, .X = X, .sX = strideS_X, .X2 = X2, .sX2 = strideS_X2,
+                              .ls = lengthscale, .ard = ard, .sls = strideS_ls, .var = variance, .svar = strideS_var, .diag_add = diag_add,
+                              .sdiag = strideS_diag, .jitter = jitter, .mode = mode, .K = {K_out, ldk, strideS_K}});
 }
 
 // Gram matrix cov(xmin[r], xmaj[k]) (r < R, k < Kn) as split planes in the f16x2 format (float32 inputs, stationary kernels); see
 // gram_planes_lean_kernel.  planes: 2 * pstride elements, pstride = mxf_split_plane_elems(R, Kn).
-size_t mxf_gram_planes_scratch_bytes(int64_t R, int64_t Kn, int Q) {
-    const int QT = Q <= 8 ? 8 : 16;
-    const int64_t padr = (R + 127) / 128 * 128, padk = ((Kn + 15) / 16 + 15) / 16 * 256;
-    return (size_t)(padr + padk) * QT * sizeof(float);
-}
+size_t mxf_gram_planes_scratch_bytes(int64_t R, int64_t Kn, int Q) { return gram_planes_plan(R, Kn, Q, false, false, 0, 1).bytes; }
 
-int mxf_gram_planes_internal(mxf_ctx* h, int kind, int64_t R, int64_t Kn, int Q, const float* Xmin, const float* Xmaj, const float* ls,
-                             int ard, const float* var, unsigned short* planes, int64_t pstride, float* scratch, hipStream_t st, int mode,
-                             const float* wk, int Pw, float* U, int64_t ldU, const float* majs, const float* mins, int64_t period) {
-    if (R <= 0 || Kn <= 0) return 0;
-    if (!scratch) MXF_FAIL(h, -2, "gram planes: scratch of mxf_gram_planes_scratch_bytes() bytes required");
-    if (Q > 16) MXF_FAIL(h, -3, "gram planes: Q > 16 not supported");
-    switch (kind) {
-        case MXF_K_RBF: return gram_planes_kind<MXF_K_RBF>(h, R, Kn, Q, Xmin, Xmaj, ls, ard, var, planes, pstride, scratch, st, mode, wk, Pw, U, ldU, majs, mins, period);
-        case MXF_K_MATERN12: return gram_planes_kind<MXF_K_MATERN12>(h, R, Kn, Q, Xmin, Xmaj, ls, ard, var, planes, pstride, scratch, st, mode, wk, Pw, U, ldU, majs, mins, period);
-        case MXF_K_MATERN32: return gram_planes_kind<MXF_K_MATERN32>(h, R, Kn, Q, Xmin, Xmaj, ls, ard, var, planes, pstride, scratch, st, mode, wk, Pw, U, ldU, majs, mins, period);
-        case MXF_K_MATERN52: return gram_planes_kind<MXF_K_MATERN52>(h, R, Kn, Q, Xmin, Xmaj, ls, ard, var, planes, pstride, scratch, st, mode, wk, Pw, U, ldU, majs, mins, period);
-    }
-    MXF_FAIL(h, -2, "gram planes: stationary kernels only (kind %d)", kind);
+int mxf_gram_planes_internal(mxf_ctx* h, hipStream_t st, const MxfGramPlanes& d) {
+    if (d.R <= 0 || d.Kn <= 0) return 0;
+    if (!d.scratch) MXF_FAIL(h, -2, "gram planes: scratch of mxf_gram_planes_scratch_bytes() bytes required");
+    const GramPlanesPlan p = gram_planes_plan(d.R, d.Kn, d.Q, d.U != nullptr, d.w != nullptr, d.Pw, MXF_KNOB("MXF_PLANES_KB", 8));
+    if (p.refusal) MXF_FAIL(h, p.rc, "gram planes: %s", p.refusal);
+    const int rc = dispatch<MXF_K_RBF, MXF_K_MATERN12, MXF_K_MATERN32, MXF_K_MATERN52>(d.kind, [&](auto kind) {
+        return dispatch<8, 16>(p.QT, [&](auto qt) { return gram_planes_launch<decltype(kind)::value, decltype(qt)::value>(h, st, d, p); });
+    });
+    if (rc == NO_CASE) MXF_FAIL(h, -2, "gram planes: stationary kernels only (kind %d)", d.kind);
+    return rc;
 }
 
 // C ABI of the planes pass (include/mxf_gp.h): argument checks, the padded raw coordinates in the handle's Gram scratch (where mxf_gram keeps
@@ -752,8 +704,9 @@ extern "C" int mxf_gram_planes(mxf_handle h, int kind, int64_t R, int64_t Kn, in
     const size_t need = mxf_gram_planes_scratch_bytes(R, Kn, Q);
     float* scratch = (float*)mxf_gram_ws(h, need);
     if (!scratch) MXF_FAIL(h, -4, "mxf_gram_planes: cannot allocate %zu bytes for the padded coordinates", need);
-    return mxf_gram_planes_internal(h, kind, R, Kn, Q, (const float*)Xmin, (const float*)Xmaj, (const float*)lengthscale, ard,
-                                    (const float*)variance, (unsigned short*)planes, (int64_t)mxf_split_plane_elems(R, Kn), scratch,
-                                    (hipStream_t)stream, MXF_SPLIT_F16X2, (const float*)w, w ? Pw : 0, (float*)U, ldU, (const float*)majs,
-                                    (const float*)mins, period);
+    return mxf_gram_planes_internal(h, (hipStream_t)stream,
+                                    {.kind = kind, .R = R, .Kn = Kn, .Q = Q, .Xmin = (const float*)Xmin, .Xmaj = (const float*)Xmaj,
+                                     .ls = (const float*)lengthscale, .ard = ard, .var = (const float*)variance, .planes = (unsigned short*)planes,
+                                     .pstride = (int64_t)mxf_split_plane_elems(R, Kn), .scratch = scratch, .w = (const float*)w, .Pw = w ? Pw : 0,
+                                     .U = (float*)U, .ldU = ldU, .majs = (const float*)majs, .mins = (const float*)mins, .period = period});
 }

@@ -9,25 +9,15 @@
 
 namespace {
 
-template <typename T> __device__ __forceinline__ T g2_exp2_neg(T x);
-template <> __device__ __forceinline__ float g2_exp2_neg<float>(float x) { return __builtin_amdgcn_exp2f(-x); }
-template <> __device__ __forceinline__ double g2_exp2_neg<double>(double x) { return mxf_exp2_neg_f64(x); }
-template <typename T> __device__ __forceinline__ T g2_exp_nonpos(T x);
-template <> __device__ __forceinline__ float g2_exp_nonpos<float>(float x) { return __expf(x); }
-template <> __device__ __forceinline__ double g2_exp_nonpos<double>(double x) { return mxf_exp_nonpos_f64(x); }
-template <typename T> __device__ __forceinline__ T g2_sqrt(T x);
-template <> __device__ __forceinline__ float g2_sqrt<float>(float x) { return __builtin_sqrtf(x); }
-template <> __device__ __forceinline__ double g2_sqrt<double>(double x) { return sqrt(x); }
-
 // covariance from the scaled squared distance (RBF: scaled so that k = v 2^-red; Matern: red = r^2, clipped at 1e-14 as matern.py:84-88 does)
 template <typename T>
 __device__ __forceinline__ T g2_cov(int kind, T red, T v) {
-    if (kind == MXF_K_RBF) return v * g2_exp2_neg<T>(red);
-    const T r0 = g2_sqrt<T>(red < (T)1e-14 ? (T)1e-14 : red);
-    if (kind == MXF_K_MATERN12) return v * g2_exp_nonpos<T>(-r0);
-    if (kind == MXF_K_MATERN32) { const T r = (T)1.7320508075688772 * r0; return v * ((T)1 + r) * g2_exp_nonpos<T>(-r); }
+    if (kind == MXF_K_RBF) return v * fast_exp2_neg<T>(red);
+    const T r0 = t_sqrt<T>(red < (T)1e-14 ? (T)1e-14 : red);
+    if (kind == MXF_K_MATERN12) return v * t_exp<T>(-r0);
+    if (kind == MXF_K_MATERN32) { const T r = (T)1.7320508075688772 * r0; return v * ((T)1 + r) * t_exp<T>(-r); }
     const T r = (T)2.23606797749979 * r0;                                   // MATERN52: un-clipped r^2 in the 5/3 r^2 term (matern.py:87)
-    return v * ((T)1 + r + (T)(5.0 / 3.0) * red) * g2_exp_nonpos<T>(-r);
+    return v * ((T)1 + r + (T)(5.0 / 3.0) * red) * t_exp<T>(-r);
 }
 
 struct G2Args {

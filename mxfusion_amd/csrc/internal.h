@@ -34,6 +34,19 @@ int mxf_trtri_internal(mxf_ctx* h, int dtype, int S, int64_t n, const void* L, i
                        int64_t sI, hipStream_t st);
 int mxf_sumlogdiag_internal(mxf_ctx* h, int dtype, int S, int64_t n, const void* L, int64_t ldl, int64_t sL, void* out, hipStream_t st);
 
+// K = k(X, X2) for S samples (gram.hip), the same kind of descriptor; mxf_gram of include/mxf_gp.h documents the operands.
+struct MxfGram {
+    int kind = 0, dtype = 0;
+    int S = 1; int64_t N = 0, N2 = 0; int Q = 0;        // S samples of an (N x N2) Gram over Q coordinates
+    const void* X = nullptr; int64_t sX = 0;            // (N x Q); the s* members are per-sample strides in elements, 0 = shared by the samples
+    const void* X2 = nullptr; int64_t sX2 = 0;          // (N2 x Q); nullptr: the square Gram of X with itself (N2 is ignored)
+    const void* ls = nullptr; int ard = 0; int64_t sls = 0; const void* var = nullptr; int64_t svar = 0;
+    const void* diag_add = nullptr; int64_t sdiag = 0; double jitter = 0.0;      // square Gram only: K[i][i] += diag_add[s] + jitter
+    int mode = MXF_WRITE;
+    MxfMatW K;
+};
+int mxf_gram_internal(mxf_ctx* h, hipStream_t st, const MxfGram& d);
+
 // The Gram reverse passes take plain descriptors (aggregates, every member defaulted, as the split GEMMs' below): a call site names what it passes.
 // Plain reverse mode of a stationary Gram (gram_bwd.hip): dK -> dX, dX2, dls, dvar, all ACCUMULATED into; outputs may be nullptr.
 struct MxfGramBwd {
@@ -106,13 +119,20 @@ struct MxfBtURow { const float* w = nullptr; float* U = nullptr; double uscale =
 bool mxf_gemm_bt_ok(int64_t M, int64_t N, int64_t K);
 int mxf_gemm_bt_internal(mxf_ctx* h, hipStream_t st, int64_t M, int64_t N, int64_t K, MxfSplitScale scale, MxfPlanes A, MxfPlanes Bt, int64_t btR,
                          MxfSplitOut out, MxfBtURow u = {}, MxfSplitSched sched = {});
+// Gram matrix cov(Xmin[r], Xmaj[k]) (r < R, k < Kn) as two f16 planes (float32 inputs, stationary kernels; gram.hip), plane element (r, k) at
+// ((k / 16) * R + r) * 16 + k % 16
+struct MxfGramPlanes {
+    int kind = 0; int64_t R = 0, Kn = 0; int Q = 0;
+    const float* Xmin = nullptr; const float* Xmaj = nullptr; const float* ls = nullptr; int ard = 0; const float* var = nullptr;
+    unsigned short* planes = nullptr; int64_t pstride = 0;      // 2 * pstride elements, pstride = mxf_split_plane_elems(R, Kn)
+    float* scratch = nullptr;                                   // mxf_gram_planes_scratch_bytes() bytes, caller-owned: two of these run concurrently on different streams
+    // optional fused product U[p][r] = sum_k w[k][p] cov(Xmin[r], Xmaj[k]): w (Kn x Pw), U (Pw x ldU); see gram_planes_lean_kernel
+    const float* w = nullptr; int Pw = 0; float* U = nullptr; int64_t ldU = 0;
+    // optional per-row weights (period entries, index taken modulo period) on the major / minor index
+    const float* majs = nullptr; const float* mins = nullptr; int64_t period = 1;
+};
 size_t mxf_gram_planes_scratch_bytes(int64_t R, int64_t Kn, int Q);
-int mxf_gram_planes_internal(mxf_ctx* h, int kind, int64_t R, int64_t Kn, int Q, const float* Xmin, const float* Xmaj, const float* ls,
-                             int ard, const float* var, unsigned short* planes, int64_t pstride, float* scratch, hipStream_t st,
-                             int mode = MXF_SPLIT_F16X2, const float* wk = nullptr, int Pw = 0, float* U = nullptr, int64_t ldU = 0,
-                             const float* majs = nullptr, const float* mins = nullptr, int64_t period = 1);
-// (majs / mins: optional per-row weights (period entries, index taken modulo period) on the major / minor index -- f16x2 lean kernel only)
-// (wk (Kn x Pw), U (Pw x ldU): optional fused product U[p][r] = sum_k wk[k][p] cov(xmin[r], xmaj[k]); see gram_planes_kernel)
+int mxf_gram_planes_internal(mxf_ctx* h, hipStream_t st, const MxfGramPlanes& d);
 
 // whiten.hip: two f16 planes of an (R x K) operand -> the planes of its transpose (K x R); U != nullptr: U[k] = scale[0] * sc2 * sum_r a[r] x(r, k)
 int mxf_upart_reduce_internal(mxf_ctx* h, int64_t N, int nparts, const float* Upart, const float* scale, float sc2, float* U, hipStream_t st);

@@ -69,6 +69,13 @@ int cov_update(mxf_ctx* h, hipStream_t st, int dtype, int S, int64_t Nt, int64_t
                                      .beta = 1.0, .C = {vout, Nt, Nt * Nt}, .batch = S});
 }
 
+// vout_s (Nt x Nt) = K(Xt_s, Xt_s): the prior covariance of each sample's test inputs, hyper-parameters shared
+template <typename T>
+int test_cov(mxf_ctx* h, hipStream_t st, int kind, int dtype, int S, int64_t Nt, int Q, const T* Xt, const T* ls, int ard, const T* var, T* vout) {
+    return mxf_gram_internal(h, st, {.kind = kind, .dtype = dtype, .S = S, .N = Nt, .Q = Q, .X = Xt, .sX = Nt * Q, .ls = ls, .ard = ard, .var = var,
+                                     .K = {vout, Nt, Nt * Nt}});
+}
+
 template <typename T>
 int gp_predict_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t N, int64_t Nt, int Q, int P, const T* Xc, const T* Xt, const T* ls, int ard,
                      const T* var, const T* L, int64_t ldl, const T* LinvY, const T* noise, int noise_free, int full_cov, T* mean, T* vout,
@@ -77,7 +84,8 @@ int gp_predict_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t N, int64_t 
     T* V = (T*)mxf_ws(h, sizeof(T) * (size_t)N * C + sizeof(T) * (size_t)C);
     if (!V) MXF_FAIL(h, -4, "mxf_gp_predict: cannot allocate %zu bytes of scratch", sizeof(T) * (size_t)N * C);
     T* cd = V + (size_t)N * C;
-    int rc = mxf_gram(h, kind, dtype, 1, N, C, Q, Xc, 0, Xt, 0, ls, ard, 0, var, 0, nullptr, 0, 0.0, MXF_WRITE, V, C, 0, st);   // Kxt (N x S Nt) :160
+    int rc = mxf_gram_internal(h, st, {.kind = kind, .dtype = dtype, .N = N, .N2 = C, .Q = Q, .X = Xc, .X2 = Xt, .ls = ls, .ard = ard, .var = var,
+                                       .K = {V, C}});                                                                             // Kxt (N x S Nt) :160
     if (rc) return rc;
     rc = mxf_trsm_internal(h, dtype, 0, 1, N, C, L, ldl, 0, V, C, 0, 0, st);                                                      // V = L^-1 Kxt :161
     if (rc) return rc;
@@ -89,7 +97,7 @@ int gp_predict_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t N, int64_t 
         hipLaunchKernelGGL((var_diag_kernel<T>), dim3(gridn(C)), dim3(256), 0, st, C, var, (const T*)cd, (const T*)nullptr, noise_free ? (const T*)nullptr : noise, vout);
     } else {
         // per sample: K(Xt_s, Xt_s) - V_s^T V_s (+ noise I)  :186-190
-        rc = mxf_gram(h, kind, dtype, S, Nt, Nt, Q, Xt, Nt * Q, nullptr, 0, ls, ard, 0, var, 0, nullptr, 0, 0.0, MXF_WRITE, vout, Nt, Nt * Nt, st);
+        rc = test_cov(h, st, kind, dtype, S, Nt, Q, Xt, ls, ard, var, vout);
         if (rc) return rc;
         rc = cov_update(h, st, dtype, S, Nt, N, -1.0, V, V, vout);
         if (rc) return rc;
@@ -115,7 +123,8 @@ int svgp_predict_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t M, int64_
     hipLaunchKernelGGL((diag_embed_kernel<T>), dim3(gridn(MM)), dim3(256), 0, st, M, sdiag, Su);
     int rc = mxf_gemm_internal(h, st, {.dtype = dtype, .tb = 1, .M = M, .N = M, .K = M, .A = {W, M}, .B = {W, M}, .beta = 1.0, .C = {Su, M}});  // S = W W^T + diag :145
     if (rc) return rc;
-    rc = mxf_gram(h, kind, dtype, 1, M, M, Q, Z, 0, nullptr, 0, ls, ard, 0, var, 0, nullptr, 0, jitter, MXF_WRITE, Lm, M, 0, st);     // Kuu (+ jitter) :146-148
+    rc = mxf_gram_internal(h, st, {.kind = kind, .dtype = dtype, .N = M, .Q = Q, .X = Z, .ls = ls, .ard = ard, .var = var, .jitter = jitter,
+                                   .K = {Lm, M}});                                                                                   // Kuu (+ jitter) :146-148
     if (rc) return rc;
     rc = mxf_potrf_internal(h, dtype, 1, M, Lm, M, 0, info, st);                                                                     // L :149
     if (rc) return rc;
@@ -133,7 +142,8 @@ int svgp_predict_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t M, int64_
     rc = mxf_trsm_internal(h, dtype, 1, 1, M, P, Lm, M, 0, wv, P, 0, 0, st);                                                         // L^-T L^-1 mu :154
     if (rc) return rc;
     // test inputs
-    rc = mxf_gram(h, kind, dtype, 1, M, C, Q, Z, 0, Xt, 0, ls, ard, 0, var, 0, nullptr, 0, 0.0, MXF_WRITE, V, C, 0, st);             // Kxt :157
+    rc = mxf_gram_internal(h, st, {.kind = kind, .dtype = dtype, .N = M, .N2 = C, .Q = Q, .X = Z, .X2 = Xt, .ls = ls, .ard = ard, .var = var,
+                                   .K = {V, C}});                                                                                    // Kxt :157
     if (rc) return rc;
     rc = mxf_gemm_internal(h, st, {.dtype = dtype, .ta = 1, .M = C, .N = P, .K = M, .A = {V, C}, .B = {wv, P}, .C = {mean, P}});      // Kxt^T wv :158
     if (rc) return rc;
@@ -148,7 +158,7 @@ int svgp_predict_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t M, int64_
         if (rc) return rc;
         hipLaunchKernelGGL((var_diag_kernel<T>), dim3(gridn(C)), dim3(256), 0, st, C, var, (const T*)cd1, (const T*)cd2, noise_free ? (const T*)nullptr : noise, vout);   // :166-172
     } else {
-        rc = mxf_gram(h, kind, dtype, S, Nt, Nt, Q, Xt, Nt * Q, nullptr, 0, ls, ard, 0, var, 0, nullptr, 0, 0.0, MXF_WRITE, vout, Nt, Nt * Nt, st);
+        rc = test_cov(h, st, kind, dtype, S, Nt, Q, Xt, ls, ard, var, vout);
         if (rc) return rc;
         rc = cov_update(h, st, dtype, S, Nt, M, -1.0, V, V, vout);                                                                  // :176-178
         if (rc) return rc;

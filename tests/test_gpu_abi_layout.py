@@ -296,9 +296,9 @@ def test_potrf_f64_more_block_rows_than_cus_falls_back_to_columns():
 
 
 # =================================================================================================================== mxf_gram / gram2
-# gram.hip launch_kind: vecst = ldk % VEC == 0 and sK % VEC == 0 and K_out 16-byte aligned (VEC = 4 floats / 2 doubles).
-#   WRITE, vecst, N2 % VEC == 0 -> gram_lean_kernel (16-byte non-temporal stores; float32 RBF: TRC = 12, float64 RBF: XF form, else run-time rows)
-#   otherwise                   -> gram_kernel<.., false>: 16-byte stores for the lanes with col0 + VEC <= N2 when vecst, element-wise else;
+# gram_plan.h gram_plan: vec_ok = ldk % VEC == 0 and sK % VEC == 0 and K_out 16-byte aligned (VEC = 4 floats / 2 doubles).
+#   WRITE, vec_ok, N2 % VEC == 0 -> LEAN / LEAN_XF: gram_lean_kernel (16-byte non-temporal stores; float32 RBF: TRC = 12, float64 RBF: XF form, else run-time rows)
+#   otherwise                   -> COORD_SLOW: gram_kernel<T, QT, KIND, false>: 16-byte stores for the lanes with col0 + VEC <= N2 when vecst, element-wise else;
 #                                  ACC_ADD / ACC_MUL read the window's old contents
 #   Q > 16                      -> gram_generic_kernel (one element per thread)
 # N2 = 1028 is a multiple of both vector widths, 1031 of neither.
