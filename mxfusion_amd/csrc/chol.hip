@@ -11,10 +11,11 @@
 // (N^3/3 flops), latency bound on the 64-wide critical path.
 #include "common.h"
 #include "internal.h"
+#include "chol_plan.h"
 
 namespace {
 
-constexpr int NB = 64;     // inner block
+using namespace mxf_chol_tiles;      // NB = 64 (inner block), NBO = 512 (outer panel), TRI_MIN
 
 // 1/sqrt(d) to full precision: hardware v_rsq estimate + Newton steps (cheaper than a correctly-rounded sqrt AND a division)
 __device__ __forceinline__ float inv_sqrt(float d) { float r = rsqrtf(d); r = r * (1.5f - 0.5f * d * r * r); return r; }
@@ -26,8 +27,6 @@ __device__ __forceinline__ double inv_sqrt(double d) {
     const double e = fma(-(d * y), y, 1.0);
     return fma(y * e, fma(e, 0.375, 0.5), y);
 }
-constexpr int NBO = 512;   // outer panel
-constexpr int TRI_MIN = 1024;   // trtri merge levels from this block size on use the triangular-aware GEMM k ranges
 
 __device__ __forceinline__ float readlane_t(float v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); }
 __device__ __forceinline__ double readlane_t(double v, int l) {
@@ -928,31 +927,32 @@ int trtri_merge_p2(mxf_ctx* h, int dtype, int64_t b1, int64_t b2, T* Ip, int64_t
     return 0;
 }
 
-// Log-depth blocked inverse of a lower-triangular matrix.  Level 0: all 64x64 diagonal blocks (one launch).  Level l merges pairs of
-// bs-blocks (all complete pairs of a matrix as one batch, then a ragged last pair).  From TRI_MIN-wide blocks on the products skip the zero
-// k range -- trtri(8192) 6.9 -> 5.0 ms; the small levels keep the plain split-K products, which fill the chip better.
+// Log-depth blocked inverse of a lower-triangular matrix.  Level 0: all 64x64 diagonal blocks (one launch); then the merge levels of
+// chol_plan.h (trtri_level).  From TRI_MIN-wide blocks on the products skip the zero k range -- trtri(8192) 6.9 -> 5.0 ms; the small levels
+// keep the plain split-K products, which fill the chip better.
 template <typename T>
-int trtri_typed(mxf_ctx* h, int dtype, int S, int64_t n, const T* L, int64_t ldl, int64_t sL, T* Li, int64_t ldi, int64_t sI, hipStream_t st) {
-    if (n > 65535) MXF_FAIL(h, -3, "mxf_trtri: n too large");
+int trtri_typed(mxf_ctx* h, hipStream_t st, const MxfTrtri& d) {
+    const int64_t n = d.n, ldl = d.L.ld, sL = d.L.stride, ldi = d.Linv.ld, sI = d.Linv.stride;
+    const T* L = (const T*)d.L.p; T* Li = (T*)d.Linv.p;
+    const int dtype = d.dtype, S = d.S;
+    if (const char* why = chol_rows_refusal(n)) MXF_FAIL(h, -3, "mxf_trtri: %s", why);
     const int64_t nblk = (n + NB - 1) / NB;
     hipLaunchKernelGGL((trtri_diag_kernel<T>), dim3((unsigned)nblk, S), dim3(64), 0, st, L, ldl, sL, Li, ldi, sI, n);
-    for (int64_t bs = NB; bs < n; bs *= 2) {
-        const int64_t npairs_full = n / (2 * bs);                 // pairs whose second block is complete
-        const int64_t rem0 = npairs_full * 2 * bs;                  // start of a possible ragged last pair
-        const int64_t b2 = n - rem0 - bs;                           // rows of its second block
-        const bool tri = bs >= TRI_MIN;
+    for (int l = 0; l < trtri_levels(n); ++l) {
+        const TrtriLevel v = trtri_level(n, l);
         for (int s = 0; s < S; ++s) {
             const T* Ls = L + (int64_t)s * sL;
             T* Is = Li + (int64_t)s * sI;
-            if (npairs_full > 0) {
-                const int64_t stL = 2 * bs * (ldl + 1), stI = 2 * bs * (ldi + 1);
-                int rc = trtri_merge_p1<T>(h, dtype, bs, bs, Ls, ldl, stL, Is, ldi, stI, (int)npairs_full, tri, st);
-                if (!rc) rc = trtri_merge_p2<T>(h, dtype, bs, bs, Is, ldi, stI, (int)npairs_full, tri, st);
+            if (v.pairs > 0) {
+                const int64_t stL = 2 * v.bs * (ldl + 1), stI = 2 * v.bs * (ldi + 1);
+                int rc = trtri_merge_p1<T>(h, dtype, v.bs, v.bs, Ls, ldl, stL, Is, ldi, stI, (int)v.pairs, v.tri, st);
+                if (!rc) rc = trtri_merge_p2<T>(h, dtype, v.bs, v.bs, Is, ldi, stI, (int)v.pairs, v.tri, st);
                 if (rc) return rc;
             }
-            if (rem0 < n && b2 > 0) {
-                int rc = trtri_merge_p1<T>(h, dtype, bs, b2, Ls + rem0 * (ldl + 1), ldl, 0, Is + rem0 * (ldi + 1), ldi, 0, 1, tri, st);
-                if (!rc) rc = trtri_merge_p2<T>(h, dtype, bs, b2, Is + rem0 * (ldi + 1), ldi, 0, 1, tri, st);
+            if (v.ragged_b2 > 0) {
+                const int64_t r0 = v.ragged_at;
+                int rc = trtri_merge_p1<T>(h, dtype, v.bs, v.ragged_b2, Ls + r0 * (ldl + 1), ldl, 0, Is + r0 * (ldi + 1), ldi, 0, 1, v.tri, st);
+                if (!rc) rc = trtri_merge_p2<T>(h, dtype, v.bs, v.ragged_b2, Is + r0 * (ldi + 1), ldi, 0, 1, v.tri, st);
                 if (rc) return rc;
             }
         }
@@ -962,57 +962,21 @@ int trtri_typed(mxf_ctx* h, int dtype, int S, int64_t n, const T* L, int64_t ldl
     return 0;
 }
 
-// ---- potrf: the plan ------------------------------------------------------------------------------------------------------------------------
-// Which form a factorisation takes, decided once per call (potrf_plan).  float64 with n a multiple of 64: the tile kernel, one launch up to
-// MXF_POTRF_ONE_MAX = 512, one per outer panel of NBO columns beyond; float32 and ragged n: one panel-kernel launch per 64 columns.
-// The stages rely on:   one_launch => panel_tiles;   panel_tiles => T is double, n % NB == 0 and a workgroup per block row fits the device;
-//   eager => look => the handle's auxiliary streams and events exist (mxf_potrf_aux_init);   eager => panel_tiles and S == 1;
-//   split(c0) => panel_tiles.
-struct PotrfPlan {
-    int64_t n; int S;
-    bool panel_tiles;      // the tile kernel factors a whole outer panel in one launch
-    bool one_launch;       // ... and the whole matrix is one such panel, whatever its width
-    bool look;             // look-ahead: the trailing update is split between the caller's stream and potrf_aux (PotrfCall::trailing_update)
-    bool eager;            // L^-1 is formed next to the factorisation (PotrfCall::eager_row_block)
-    int64_t split_rows;    // an outer panel with at least this many block rows below it takes the split form (0: never)
-    int64_t rbw;           // eager: rows of a row block of the inverse
-
-    int64_t panel_end(int64_t c0) const { return !one_launch && c0 + NBO < n ? c0 + NBO : n; }
-    // does the outer panel at c0 take the split form (chain launch + rows-below launch)?
-    bool split(int64_t c0) const { return panel_tiles && split_rows > 0 && (n - panel_end(c0)) / NB >= split_rows; }
-    // eager: row block [rb0, pe) of L is final once the panel ending at pe has been factored (the rows above it in these columns are zero)
-    bool fires_at(int64_t pe) const { return pe % rbw == 0 || pe == n; }
-    int64_t next_fire(int64_t pe) const {
-        do pe = panel_end(pe); while (!fires_at(pe));
-        return pe;
-    }
-};
-
-// The tile kernel's workgroups hand tiles to each other through progress counters: every workgroup of a launch must be RESIDENT at once (one per
-// CU: 256 threads at one wave per SIMD, ~76 KB of LDS), or a waiting workgroup could hold the CU its producer needs.  The grid (block rows x
-// batch) is therefore bounded by the CU count of the device; larger problems take the launch-per-panel form.
-// Look-ahead (n >= 2048, not while the stream is being captured: the auxiliary streams are not part of the capture): at n = 8192 the 128 panel steps
-// (85 us each) otherwise serialise with 3.7 ms of trailing GEMMs.
-// Eager inverse (a buffer for it, one matrix, whole outer panels, at least 16 of them and 4 row blocks): potrf(8192) is bound by its serial path
-// (16 x (head update + chain + rows below)), the chip is ~40 % idle under it, and trtri(8192) afterwards took 3.9 ms of a 15 ms MAP step.  Row
-// blocks of MXF_POTRF_EAGER_INV = 2 outer panels (0: no eager inverse); DESIGN_HISTORY.md, "Variants measured and removed", has the other widths.
-PotrfPlan potrf_plan(mxf_ctx* h, size_t esize, int S, int64_t n, hipStream_t st, bool want_inverse) {
+// ---- potrf: the plan's inputs ---------------------------------------------------------------------------------------------------------------
+// Which form a factorisation takes is potrf_plan (chol_plan.h), decided once per call from this request: the shape, the CU count, the knobs and,
+// only where look-ahead is possible at all, the capture state and the handle's auxiliary streams, created here on first use.
+PotrfRequest potrf_request(mxf_ctx* h, size_t esize, int S, int64_t n, hipStream_t st, bool want_inverse, bool zero_upper) {
     static const int ncu = [] { int dev = 0, v = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 64; return v; }();
-    static const int one_max = MXF_KNOB("MXF_POTRF_ONE_MAX", 512);     // (n = 2048 as ONE left-looking launch: 2.6 ms vs 1.9 -- the last block rows carry 32 i^2 columns of products each)
-    static const int split_rows = MXF_KNOB("MXF_POTRF_SPLIT_ROWS", 64);
-    static const int eager_panels = MXF_KNOB("MXF_POTRF_EAGER_INV", 2);
-    PotrfPlan p;
-    p.n = n; p.S = S; p.split_rows = split_rows; p.rbw = (int64_t)eager_panels * NBO;
-    p.panel_tiles = esize == 8 && n % NB == 0 && n >= 2 * NB && S <= 64 && (int64_t)(n / NB) * S <= ncu;
-    p.one_launch = p.panel_tiles && n <= one_max;
-    p.look = false;
-    if (!p.one_launch) {
+    static const int64_t one_max = MXF_KNOB("MXF_POTRF_ONE_MAX", 512), split_rows = MXF_KNOB("MXF_POTRF_SPLIT_ROWS", 64), eager_panels = MXF_KNOB("MXF_POTRF_EAGER_INV", 2);
+    PotrfRequest r{.esize = esize, .S = S, .n = n, .ncu = ncu, .want_inverse = want_inverse, .zero_upper = zero_upper,
+                   .one_max = one_max, .split_rows = split_rows, .eager_panels = eager_panels};
+    if (potrf_may_look(r)) {
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         (void)hipStreamIsCapturing(st, &cap);
-        p.look = n >= 2048 && cap == hipStreamCaptureStatusNone && mxf_potrf_aux_init(h);
+        r.capturing = cap != hipStreamCaptureStatusNone;
+        r.aux_streams = !r.capturing && mxf_potrf_aux_init(h);
     }
-    p.eager = want_inverse && eager_panels && S == 1 && p.panel_tiles && p.look && n % NBO == 0 && n >= 16 * NBO && n >= 4 * p.rbw;
-    return p;
+    return r;
 }
 
 // ---- potrf: one call and its stages ---------------------------------------------------------------------------------------------------------
@@ -1086,11 +1050,11 @@ struct PotrfCall : PotrfPlan {
     // What is left behind the factorisation is the last block's diagonal inverse and p2.  join() brings potrf_inv back to st; potrf_inv_diag's
     // work always ends in an ev_pc that potrf_inv has waited on.
     int eager_row_block(int64_t pe) {
-        const int64_t rb0 = (pe - 1) / rbw * rbw;
+        const int64_t rb0 = row_block_start(pe);
         hipStream_t qd = h->potrf_inv_diag, qp = h->potrf_inv;
         MXF_HIP(h, hipEventRecord(h->ev_pi, st));
         MXF_HIP(h, hipStreamWaitEvent(qd, h->ev_pi, 0));
-        int rc = trtri_typed<T>(h, dtype, 1, pe - rb0, A + rb0 * (lda + 1), lda, 0, Ie + rb0 * (ldie + 1), ldie, 0, qd);
+        int rc = trtri_typed<T>(h, qd, {.dtype = dtype, .n = pe - rb0, .L = {A + rb0 * (lda + 1), lda}, .Linv = {Ie + rb0 * (ldie + 1), ldie}});
         if (rc) return rc;
         MXF_HIP(h, hipEventRecord(h->ev_pc, qd));
         MXF_HIP(h, hipStreamWaitEvent(qp, h->ev_pc, 0));       // (block 0: p1 of block 1 reads this inverse)
@@ -1148,14 +1112,16 @@ struct PotrfCall : PotrfPlan {
     }
 };
 
-// Ie != nullptr: L^-1 may be formed into Ie next to the factorisation (PotrfPlan::eager); *eager_done tells the caller whether it was (else:
-// call trtri afterwards).
+// d.Linv.p (float64 only): L^-1 may be formed into it next to the factorisation (PotrfPlan::eager); *d.inv_done tells the caller whether it was
+// (else: call trtri afterwards).
 template <typename T>
-int potrf_typed(mxf_ctx* h, int dtype, int S, int64_t n, T* A, int64_t lda, int64_t sA, int* info, hipStream_t st, bool zero_upper, bool zero_info,
-                T* Ie = nullptr, int64_t ldie = 0, bool* eager_done = nullptr) {
-    if (eager_done) *eager_done = false;
-    if (info && zero_info) MXF_HIP(h, hipMemsetAsync(info, 0, sizeof(int) * S, st));
-    PotrfCall<T> c{potrf_plan(h, sizeof(T), S, n, st, Ie != nullptr), h, dtype, A, lda, sA, info, st, Ie, ldie, {}};
+int potrf_typed(mxf_ctx* h, hipStream_t st, const MxfPotrf& d) {
+    const int64_t n = d.n;
+    T* A = (T*)d.A.p; T* Ie = sizeof(T) == 8 ? (T*)d.Linv.p : nullptr;
+    const PotrfPlan plan = potrf_plan(potrf_request(h, sizeof(T), d.S, n, st, Ie != nullptr, d.zero_upper));
+    if (plan.refusal) MXF_FAIL(h, -3, "mxf_potrf: %s", plan.refusal);
+    if (d.info && d.zero_info) MXF_HIP(h, hipMemsetAsync(d.info, 0, sizeof(int) * d.S, st));
+    PotrfCall<T> c{plan, h, d.dtype, A, d.A.ld, d.A.stride, d.info, st, Ie, d.Linv.ld, {}};
     int rc = 0;
     for (int64_t c0 = 0, pe; c0 < n && !rc; c0 = pe) {
         pe = c.panel_end(c0);
@@ -1165,32 +1131,31 @@ int potrf_typed(mxf_ctx* h, int dtype, int S, int64_t n, T* A, int64_t lda, int6
     }
     if (!rc) rc = c.join();
     if (rc) return rc;
-    if (eager_done) *eager_done = c.eager;
-    if (n > 1 && zero_upper) {      // (internal callers that only ever read the lower triangle skip this pass)
-        if (n > 65535) MXF_FAIL(h, -3, "mxf_potrf: n too large");
-        hipLaunchKernelGGL((zero_upper_kernel<T>), dim3((unsigned)((n + 255) / 256), (unsigned)n, S), dim3(256), 0, st, A, n, lda, sA);
-    }
+    if (d.inv_done) *d.inv_done = c.eager;
+    // (internal callers that only ever read the lower triangle skip this pass)
+    if (n > 1 && d.zero_upper) hipLaunchKernelGGL((zero_upper_kernel<T>), dim3((unsigned)((n + 255) / 256), (unsigned)n, d.S), dim3(256), 0, st, A, n, d.A.ld, d.A.stride);
     MXF_LAUNCH_CHECK(h);
     return 0;
 }
 
-// B <- op(L)^-1 B.  rhs_lower: B is (block) lower triangular (used by trtri): block row k only touches columns < (k+1)*NB
+// B <- op(L)^-1 B
 template <typename T>
-int trsm_typed(mxf_ctx* h, int dtype, int transpose, int S, int64_t n, int64_t nrhs, const T* L, int64_t ldl, int64_t sL,
-               T* B, int64_t ldb, int64_t sB, int rhs_lower, hipStream_t st) {
+int trsm_typed(mxf_ctx* h, hipStream_t st, const MxfTrsm& d) {
+    const int64_t n = d.n, nrhs = d.nrhs, ldl = d.L.ld, sL = d.L.stride, ldb = d.B.ld, sB = d.B.stride;
+    const T* L = (const T*)d.L.p; T* B = (T*)d.B.p;
+    const int dtype = d.dtype, S = d.S;
     const int64_t nblk = (n + NB - 1) / NB;
-    if (!transpose) {
+    if (!d.transpose) {
         for (int64_t kb = 0; kb < nblk; ++kb) {
             const int64_t k0 = kb * NB;
             const int nb = (int)((k0 + NB < n) ? NB : n - k0);
-            const int64_t ncols = rhs_lower ? ((k0 + nb < nrhs) ? k0 + nb : nrhs) : nrhs;
             if (k0 > 0) {
-                int rc = mxf_gemm_internal(h, st, {.dtype = dtype, .M = nb, .N = ncols, .K = k0, .alpha = -1.0, .A = {L + k0 * ldl, ldl, sL}, .B = {B, ldb, sB},
+                int rc = mxf_gemm_internal(h, st, {.dtype = dtype, .M = nb, .N = nrhs, .K = k0, .alpha = -1.0, .A = {L + k0 * ldl, ldl, sL}, .B = {B, ldb, sB},
                                                    .beta = 1.0, .C = {B + k0 * ldb, ldb, sB}, .batch = S});
                 if (rc) return rc;
             }
-            hipLaunchKernelGGL((solve_cols_kernel<T, false>), dim3((unsigned)((ncols + 255) / 256), S), dim3(256), 0, st, L, ldl, sL, B,
-                               ldb, sB, k0, nb, (int64_t)0, ncols);
+            hipLaunchKernelGGL((solve_cols_kernel<T, false>), dim3((unsigned)((nrhs + 255) / 256), S), dim3(256), 0, st, L, ldl, sL, B,
+                               ldb, sB, k0, nb, (int64_t)0, nrhs);
         }
     } else {
         for (int64_t kb = nblk - 1; kb >= 0; --kb) {
@@ -1212,36 +1177,33 @@ int trsm_typed(mxf_ctx* h, int dtype, int transpose, int S, int64_t n, int64_t n
 
 }  // namespace
 
-int mxf_potrf_internal(mxf_ctx* h, int dtype, int S, int64_t n, void* A, int64_t lda, int64_t sA, int* info, hipStream_t st, bool zero_upper, bool zero_info,
-                       void* Linv_eager, int64_t ldie, bool* eager_done) {
-    if (eager_done) *eager_done = false;
-    if (n <= 0 || S <= 0) return 0;
-    if (dtype == MXF_F32) return potrf_typed<float>(h, dtype, S, n, (float*)A, lda, sA, info, st, zero_upper, zero_info);
-    if (dtype == MXF_F64) return potrf_typed<double>(h, dtype, S, n, (double*)A, lda, sA, info, st, zero_upper, zero_info, (double*)Linv_eager, ldie, eager_done);
-    MXF_FAIL(h, -2, "mxf_potrf: bad dtype %d", dtype);
+int mxf_potrf_internal(mxf_ctx* h, hipStream_t st, const MxfPotrf& d) {
+    if (d.inv_done) *d.inv_done = false;
+    if (d.n <= 0 || d.S <= 0) return 0;
+    if (d.dtype == MXF_F32) return potrf_typed<float>(h, st, d);
+    if (d.dtype == MXF_F64) return potrf_typed<double>(h, st, d);
+    MXF_FAIL(h, -2, "mxf_potrf: bad dtype %d", d.dtype);
 }
 
-int mxf_trsm_internal(mxf_ctx* h, int dtype, int transpose, int S, int64_t n, int64_t nrhs, const void* L, int64_t ldl,
-                      int64_t sL, void* B, int64_t ldb, int64_t sB, int rhs_lower, hipStream_t st) {
-    if (n <= 0 || nrhs <= 0 || S <= 0) return 0;
-    if (dtype == MXF_F32) return trsm_typed<float>(h, dtype, transpose, S, n, nrhs, (const float*)L, ldl, sL, (float*)B, ldb, sB, rhs_lower, st);
-    if (dtype == MXF_F64) return trsm_typed<double>(h, dtype, transpose, S, n, nrhs, (const double*)L, ldl, sL, (double*)B, ldb, sB, rhs_lower, st);
-    MXF_FAIL(h, -2, "mxf_trsm: bad dtype %d", dtype);
+int mxf_trsm_internal(mxf_ctx* h, hipStream_t st, const MxfTrsm& d) {
+    if (d.n <= 0 || d.nrhs <= 0 || d.S <= 0) return 0;
+    if (d.dtype == MXF_F32) return trsm_typed<float>(h, st, d);
+    if (d.dtype == MXF_F64) return trsm_typed<double>(h, st, d);
+    MXF_FAIL(h, -2, "mxf_trsm: bad dtype %d", d.dtype);
 }
 
-int mxf_trtri_internal(mxf_ctx* h, int dtype, int S, int64_t n, const void* L, int64_t ldl, int64_t sL, void* Linv, int64_t ldi,
-                       int64_t sI, hipStream_t st) {
-    if (n <= 0 || S <= 0) return 0;
-    if (dtype == MXF_F32) return trtri_typed<float>(h, dtype, S, n, (const float*)L, ldl, sL, (float*)Linv, ldi, sI, st);
-    if (dtype == MXF_F64) return trtri_typed<double>(h, dtype, S, n, (const double*)L, ldl, sL, (double*)Linv, ldi, sI, st);
-    MXF_FAIL(h, -2, "mxf_trtri: bad dtype %d", dtype);
+int mxf_trtri_internal(mxf_ctx* h, hipStream_t st, const MxfTrtri& d) {
+    if (d.n <= 0 || d.S <= 0) return 0;
+    if (d.dtype == MXF_F32) return trtri_typed<float>(h, st, d);
+    if (d.dtype == MXF_F64) return trtri_typed<double>(h, st, d);
+    MXF_FAIL(h, -2, "mxf_trtri: bad dtype %d", d.dtype);
 }
 
-int mxf_sumlogdiag_internal(mxf_ctx* h, int dtype, int S, int64_t n, const void* L, int64_t ldl, int64_t sL, void* out, hipStream_t st) {
-    if (S <= 0) return 0;
-    if (dtype == MXF_F32) hipLaunchKernelGGL((sumlogdiag_kernel<float>), dim3(S), dim3(256), 0, st, (const float*)L, n, ldl, sL, (float*)out);
-    else if (dtype == MXF_F64) hipLaunchKernelGGL((sumlogdiag_kernel<double>), dim3(S), dim3(256), 0, st, (const double*)L, n, ldl, sL, (double*)out);
-    else MXF_FAIL(h, -2, "mxf_sumlogdiag: bad dtype %d", dtype);
+int mxf_sumlogdiag_internal(mxf_ctx* h, hipStream_t st, const MxfSumLogDiag& d) {
+    if (d.S <= 0) return 0;
+    if (d.dtype == MXF_F32) hipLaunchKernelGGL((sumlogdiag_kernel<float>), dim3(d.S), dim3(256), 0, st, (const float*)d.L.p, d.n, d.L.ld, d.L.stride, (float*)d.out);
+    else if (d.dtype == MXF_F64) hipLaunchKernelGGL((sumlogdiag_kernel<double>), dim3(d.S), dim3(256), 0, st, (const double*)d.L.p, d.n, d.L.ld, d.L.stride, (double*)d.out);
+    else MXF_FAIL(h, -2, "mxf_sumlogdiag: bad dtype %d", d.dtype);
     MXF_LAUNCH_CHECK(h);
     return 0;
 }
@@ -1249,26 +1211,27 @@ int mxf_sumlogdiag_internal(mxf_ctx* h, int dtype, int S, int64_t n, const void*
 extern "C" int mxf_potrf(mxf_handle h, int dtype, int S, int64_t n, void* A, int64_t lda, int64_t strideS_A, int* info, void* stream) {
     if (!h) return -1;
     if (n < 0 || S < 0 || (n > 0 && (!A || lda < n))) MXF_FAIL(h, -2, "mxf_potrf: bad arguments");
-    return mxf_potrf_internal(h, dtype, S, n, A, lda, strideS_A, info, (hipStream_t)stream);
+    return mxf_potrf_internal(h, (hipStream_t)stream, {.dtype = dtype, .S = S, .n = n, .A = {A, lda, strideS_A}, .info = info});
 }
 
 extern "C" int mxf_trsm(mxf_handle h, int dtype, int transpose, int S, int64_t n, int64_t nrhs, const void* L, int64_t ldl,
                         int64_t strideS_L, void* B, int64_t ldb, int64_t strideS_B, void* stream) {
     if (!h) return -1;
     if (n < 0 || nrhs < 0 || S < 0 || (n > 0 && nrhs > 0 && (!L || !B || ldl < n || ldb < nrhs))) MXF_FAIL(h, -2, "mxf_trsm: bad arguments");
-    return mxf_trsm_internal(h, dtype, transpose, S, n, nrhs, L, ldl, strideS_L, B, ldb, strideS_B, 0, (hipStream_t)stream);
+    return mxf_trsm_internal(h, (hipStream_t)stream, {.dtype = dtype, .transpose = transpose, .S = S, .n = n, .nrhs = nrhs, .L = {L, ldl, strideS_L},
+                                                      .B = {B, ldb, strideS_B}});
 }
 
 extern "C" int mxf_trtri(mxf_handle h, int dtype, int S, int64_t n, const void* L, int64_t ldl, int64_t strideS_L, void* Linv,
                          int64_t ldi, int64_t strideS_I, void* stream) {
     if (!h) return -1;
     if (n < 0 || S < 0 || (n > 0 && (!L || !Linv || ldl < n || ldi < n))) MXF_FAIL(h, -2, "mxf_trtri: bad arguments");
-    return mxf_trtri_internal(h, dtype, S, n, L, ldl, strideS_L, Linv, ldi, strideS_I, (hipStream_t)stream);
+    return mxf_trtri_internal(h, (hipStream_t)stream, {.dtype = dtype, .S = S, .n = n, .L = {L, ldl, strideS_L}, .Linv = {Linv, ldi, strideS_I}});
 }
 
 extern "C" int mxf_sumlogdiag(mxf_handle h, int dtype, int S, int64_t n, const void* L, int64_t ldl, int64_t strideS_L, void* out,
                               void* stream) {
     if (!h) return -1;
     if (n < 0 || S < 0 || (n > 0 && (!L || !out))) MXF_FAIL(h, -2, "mxf_sumlogdiag: bad arguments");
-    return mxf_sumlogdiag_internal(h, dtype, S, n, L, ldl, strideS_L, out, (hipStream_t)stream);
+    return mxf_sumlogdiag_internal(h, (hipStream_t)stream, {.dtype = dtype, .S = S, .n = n, .L = {L, ldl, strideS_L}, .out = out});
 }

@@ -324,6 +324,17 @@ inline int cross_gram(mxf_ctx* h, hipStream_t st, int kind, int dtype, int Q, in
                       const void* var, void* K) {
     return mxf_gram_internal(h, st, {.kind = kind, .dtype = dtype, .N = n, .N2 = n2, .Q = Q, .X = A, .X2 = B, .ls = ls, .ard = ard, .var = var, .K = {K, n2}});
 }
+// The sparse models' float64 M x M factorisations, one dense matrix each: L = chol(A) in place; L^-1; sum_i log L[i][i].
+// bare (the SVGP core): the strict upper triangle stays as it was (trtri / sumlogdiag read the lower one only) and the caller has zeroed info
+inline int potrf_f64(mxf_ctx* h, hipStream_t st, int64_t M, double* A, int* info, bool bare = false) {
+    return mxf_potrf_internal(h, st, {.dtype = MXF_F64, .n = M, .A = {A, M, M * M}, .info = info, .zero_upper = !bare, .zero_info = !bare});
+}
+inline int trtri_f64(mxf_ctx* h, hipStream_t st, int64_t M, const double* L, double* Linv) {
+    return mxf_trtri_internal(h, st, {.dtype = MXF_F64, .n = M, .L = {L, M, M * M}, .Linv = {Linv, M, M * M}});
+}
+inline int sumlogdiag_f64(mxf_ctx* h, hipStream_t st, int64_t M, const double* L, double* out) {
+    return mxf_sumlogdiag_internal(h, st, {.dtype = MXF_F64, .n = M, .L = {L, M, M * M}, .out = out});
+}
 
 // ================================================================================================ exact GP
 template <typename T>
@@ -351,11 +362,12 @@ int gp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t N, int Q, in
     const bool tri_skinny = via_inverse && S == 1 && P <= 8;
     // (r05) float64, one matrix: the factorisation forms L^-1 itself, row block by row block on a third stream next to its serial chain
     bool inv_done = false;
-    rc = mxf_potrf_internal(h, dtype, S, N, L, N, NN, info, st, true, true, (via_inverse && S == 1 && sizeof(T) == 8) ? (void*)Linv : nullptr, N,
-                            &inv_done);   // :61
+    rc = mxf_potrf_internal(h, st, {.dtype = dtype, .S = S, .n = N, .A = {L, N, NN}, .info = info,
+                                    .Linv = {(via_inverse && S == 1 && sizeof(T) == 8) ? Linv : nullptr, N}, .inv_done = &inv_done});   // :61
     if (rc) return rc;
+    auto trtri = [&] { return mxf_trtri_internal(h, st, {.dtype = dtype, .S = S, .n = N, .L = {L, N, NN}, .Linv = {Linv, N, NN}}); };
     if (via_inverse) {
-        if (!inv_done) rc = mxf_trtri_internal(h, dtype, S, N, L, N, NN, Linv, N, NN, st);
+        if (!inv_done) rc = trtri();
         if (rc) return rc;
         if (tri_skinny) hipLaunchKernelGGL((trmv_lower_kernel<T>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, N, P, (const T*)Linv, N, Y, (int64_t)P, LinvY);
         else {
@@ -364,10 +376,10 @@ int gp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t N, int Q, in
         }
     } else {
         hipLaunchKernelGGL((bcast_copy_kernel<T>), dim3(gridn(S * NP)), dim3(256), 0, st, S, NP, Y, sY, LinvY, (T)1);
-        rc = mxf_trsm_internal(h, dtype, 0, S, N, P, L, N, NN, LinvY, P, NP, 0, st);
+        rc = mxf_trsm_internal(h, st, {.dtype = dtype, .S = S, .n = N, .nrhs = P, .L = {L, N, NN}, .B = {LinvY, P, NP}});
         if (rc) return rc;
     }
-    rc = mxf_sumlogdiag_internal(h, dtype, S, N, L, N, NN, sld, st);                    // :67
+    rc = mxf_sumlogdiag_internal(h, st, {.dtype = dtype, .S = S, .n = N, .L = {L, N, NN}, .out = sld});                    // :67
     if (rc) return rc;
     hipLaunchKernelGGL((sumsq_kernel<T>), dim3(S), dim3(256), 0, st, NP, LinvY, NP, ss);
     hipLaunchKernelGGL((gp_finalize_kernel<T>), dim3((S + 63) / 64), dim3(64), 0, st, S, N, P, sld, ss, logL);   // :68-70
@@ -376,7 +388,7 @@ int gp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t N, int Q, in
 
     // reverse mode: dlogL/dK = 1/2 (alpha alpha^T - P K^-1), alpha = K^-1 Y; dlogL/dY = -alpha
     if (!via_inverse) {
-        rc = mxf_trtri_internal(h, dtype, S, N, L, N, NN, Linv, N, NN, st);
+        rc = trtri();
         if (rc) return rc;
     }
     // per sample, lower triangle: dK = -P/2 Linv^T Linv + beta dK (L^-1 lower triangular: tile (i, j <= i) needs k >= i only)
@@ -1287,10 +1299,10 @@ struct SvgpCall : SvgpPlan {
         MXF_HIP(h, hipEventRecord(h->ev_k1, st));
         MXF_HIP(h, hipStreamWaitEvent(s2_, h->ev_k1, 0));
         hipLaunchKernelGGL(norm1_sym16_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, s2_, M, (const double*)Sui, M, h->cond_dev);
-        int rc = mxf_potrf_internal(h, MXF_F64, 1, M, Lm, M, MM, info, st, false, false);                     // L :83 (trtri / sumlogdiag read the lower triangle only)
+        int rc = potrf_f64(h, st, M, Lm, info, true);                                                          // L :83 (trtri / sumlogdiag read the lower triangle only)
         if (rc) return rc;
         MXF_STAGE(h, "potrf Kuu", st);
-        rc = mxf_trtri_internal(h, MXF_F64, 1, M, Lm, M, MM, Linv, M, MM, st);
+        rc = trtri_f64(h, st, M, Lm, Linv);
         if (rc) return rc;
         MXF_STAGE(h, "trtri Kuu", st);
         return 0;
@@ -1371,13 +1383,13 @@ struct SvgpCall : SvgpPlan {
         // (a plain kernel, not hipMemcpyAsync: the runtime's copy path sat idle for ~1 ms before it started next to busy queues -- r02 timeline:
         //  the Su chain did not begin until 1.66 ms although nothing in the Kuu chain feeds it)
         copy_convert(MM, (const D*)Su, tmp, s2_);
-        int rc = mxf_potrf_internal(h, MXF_F64, 1, M, tmp, M, MM, info2, s2_, false, false);                  // Ls = chol(Su) :84
+        int rc = potrf_f64(h, s2_, M, tmp, info2, true);                                                      // Ls = chol(Su) :84
         if (rc) return rc;
         MXF_STAGE(h, "potrf Su (s2)", s2_);
-        rc = mxf_sumlogdiag_internal(h, MXF_F64, 1, M, tmp, M, MM, sc + 1, s2_);
+        rc = sumlogdiag_f64(h, s2_, M, tmp, sc + 1);
         if (rc) return rc;
         if (want_grad) {
-            rc = mxf_trtri_internal(h, MXF_F64, 1, M, tmp, M, MM, Lsinv, M, MM, s2_);
+            rc = trtri_f64(h, s2_, M, tmp, Lsinv);
             if (rc) return rc;
             rc = mm(1, 0, 1.0, Lsinv, Lsinv, 0.0, Sui, s2_);
             if (rc) return rc;
@@ -1440,7 +1452,7 @@ struct SvgpCall : SvgpPlan {
         hipLaunchKernelGGL(norm1_sym16_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, s2_, M, (const double*)Ki, M, h->cond_dev + 1);
         hipLaunchKernelGGL((dot_kernel<D>), dim3(dotgrid(MP)), dim3(256), 0, s2_, MP, (const D*)mud, (const D*)wd, 1.0, sc + 3);
         hipLaunchKernelGGL((dot_kernel<D>), dim3(dotgrid(MM)), dim3(256), 0, s2_, MM, (const D*)Ki, (const D*)Su, 1.0, sc + 2);
-        const int rc = mxf_sumlogdiag_internal(h, MXF_F64, 1, M, Lm, M, MM, sc + 0, s2_);
+        const int rc = sumlogdiag_f64(h, s2_, M, Lm, sc + 0);
         if (rc) return rc;
         MXF_HIP(h, hipEventRecord(h->ev_k3, s2_));
         return 0;
@@ -1820,15 +1832,15 @@ int sgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int64_t B, int64_t M, int 
     if (rc) return rc;
     hipLaunchKernelGGL(norm1_sym16_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, st, M, (const double*)Lm, M, h->cond_dev);
     MXF_HIP(h, hipMemcpyAsync(Cm, Lm, MM * sizeof(D), hipMemcpyDeviceToDevice, st));
-    rc = mxf_potrf_internal(h, MXF_F64, 1, M, Lm, M, MM, info, st);                                  // L :77
+    rc = potrf_f64(h, st, M, Lm, info);                                                              // L :77
     if (rc) return rc;
-    rc = mxf_trtri_internal(h, MXF_F64, 1, M, Lm, M, MM, Linv, M, MM, st);
+    rc = trtri_f64(h, st, M, Lm, Linv);
     if (rc) return rc;
     rc = mm64(1, Linv, Linv, M, Ki);
     if (rc) return rc;
     hipLaunchKernelGGL(norm1_sym16_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, st, M, (const double*)Ki, M, h->cond_dev + 1);
     hipLaunchKernelGGL(cond_publish_kernel, dim3(1), dim3(1), 0, st, h->cond_dev, h->cond_host + 2 * h->cond_slot);
-    rc = mxf_sumlogdiag_internal(h, MXF_F64, 1, M, Lm, M, MM, sc + 0, st);
+    rc = sumlogdiag_f64(h, st, M, Lm, sc + 0);
     if (rc) return rc;
     // streaming statistics: Psi2 = Kuf Kuf^T (TN on the transposed Gram), psi1 = Kuf Y, ups = |Y|^2
     rc = cross_gram(h, st, kind, dtype, Q, M, Z, B, X, ls, ard, var, Kuf);                 // Kuf :74
@@ -1844,11 +1856,11 @@ int sgp_logpdf_typed(mxf_ctx* h, int kind, int dtype, int64_t B, int64_t M, int 
     hipLaunchKernelGGL((sumsq_kernel<T>), dim3(1), dim3(256), 0, st, B * P, Y, (int64_t)0, sc + 6);
     // C = Kuu + Psi2/s2, Lc = chol(C), Ci, a = Ci psi1
     hipLaunchKernelGGL(sgp_add_psi2_kernel, dim3(gridn(MM)), dim3(256), 0, st, MM, Cm, (const D*)Psi2d, (const D*)noised);
-    rc = mxf_potrf_internal(h, MXF_F64, 1, M, Cm, M, MM, info2, st);
+    rc = potrf_f64(h, st, M, Cm, info2);
     if (rc) return rc;
-    rc = mxf_sumlogdiag_internal(h, MXF_F64, 1, M, Cm, M, MM, sc + 1, st);
+    rc = sumlogdiag_f64(h, st, M, Cm, sc + 1);
     if (rc) return rc;
-    rc = mxf_trtri_internal(h, MXF_F64, 1, M, Cm, M, MM, Lcinv, M, MM, st);
+    rc = trtri_f64(h, st, M, Cm, Lcinv);
     if (rc) return rc;
     rc = mm64(1, Lcinv, Lcinv, M, Ci);
     if (rc) return rc;

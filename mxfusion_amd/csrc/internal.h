@@ -21,18 +21,25 @@ struct MxfGemm {
 };
 int mxf_gemm_internal(mxf_ctx* h, hipStream_t st, const MxfGemm& d);
 
-// zero_upper = false: leave the strict upper triangle outside the 64 x 64 diagonal blocks as it was (callers that only read the lower part)
-// zero_info = false: the caller has zeroed `info` already (the SVGP composite clears its status words in one launch off the critical path)
-int mxf_potrf_internal(mxf_ctx* h, int dtype, int S, int64_t n, void* A, int64_t lda, int64_t sA, int* info, hipStream_t st, bool zero_upper = true,
-                       bool zero_info = true, void* Linv_eager = nullptr, int64_t ldie = 0, bool* eager_done = nullptr);
-// (Linv_eager: float64, S = 1, large n: L^-1 is formed into this (n x n, leading dimension ldie) buffer NEXT TO the factorisation, row block by row
-//  block on a third stream; *eager_done says whether it was -- if not, the caller runs mxf_trtri_internal as before)
-// rhs_lower: B is block-lower-triangular (trtri); only columns < (k+1)*64 of block row k are touched
-int mxf_trsm_internal(mxf_ctx* h, int dtype, int transpose, int S, int64_t n, int64_t nrhs, const void* L, int64_t ldl,
-                      int64_t sL, void* B, int64_t ldb, int64_t sB, int rhs_lower, hipStream_t st);
-int mxf_trtri_internal(mxf_ctx* h, int dtype, int S, int64_t n, const void* L, int64_t ldl, int64_t sL, void* Linv, int64_t ldi,
-                       int64_t sI, hipStream_t st);
-int mxf_sumlogdiag_internal(mxf_ctx* h, int dtype, int S, int64_t n, const void* L, int64_t ldl, int64_t sL, void* out, hipStream_t st);
+// The Cholesky family (chol.hip), the same kind of descriptor: S matrices of n x n; mxf_potrf / mxf_trsm / mxf_trtri / mxf_sumlogdiag of
+// include/mxf_gp.h document the operands.
+struct MxfPotrf {
+    int dtype = 0, S = 1; int64_t n = 0;
+    MxfMatW A;                  // factored in place
+    int* info = nullptr;
+    bool zero_upper = true;     // false: leave the strict upper triangle outside the 64 x 64 diagonal blocks as it was (callers that only read the lower part)
+    bool zero_info = true;      // false: the caller has zeroed `info` already (the SVGP composite clears its status words in one launch off the critical path)
+    // optional (float64, S = 1, large n): L^-1 is formed into this n x n buffer NEXT TO the factorisation, row block by row block on a third
+    // stream; *inv_done says whether it was -- if not, the caller runs mxf_trtri_internal as before
+    MxfMatW Linv; bool* inv_done = nullptr;
+};
+struct MxfTrsm { int dtype = 0, transpose = 0, S = 1; int64_t n = 0, nrhs = 0; MxfMat L; MxfMatW B; };      // B (n x nrhs) <- op(L)^-1 B
+struct MxfTrtri { int dtype = 0, S = 1; int64_t n = 0; MxfMat L; MxfMatW Linv; };
+struct MxfSumLogDiag { int dtype = 0, S = 1; int64_t n = 0; MxfMat L; void* out = nullptr; };               // out[s] = sum_i log |L_s[i][i]|
+int mxf_potrf_internal(mxf_ctx* h, hipStream_t st, const MxfPotrf& d);
+int mxf_trsm_internal(mxf_ctx* h, hipStream_t st, const MxfTrsm& d);
+int mxf_trtri_internal(mxf_ctx* h, hipStream_t st, const MxfTrtri& d);
+int mxf_sumlogdiag_internal(mxf_ctx* h, hipStream_t st, const MxfSumLogDiag& d);
 
 // K = k(X, X2) for S samples (gram.hip), the same kind of descriptor; mxf_gram of include/mxf_gp.h documents the operands.
 struct MxfGram {

@@ -76,6 +76,11 @@ int test_cov(mxf_ctx* h, hipStream_t st, int kind, int dtype, int S, int64_t Nt,
                                      .K = {vout, Nt, Nt * Nt}});
 }
 
+// B (n x nrhs, dense rows) <- op(L)^-1 B for one lower-triangular L
+inline int solve(mxf_ctx* h, hipStream_t st, int dtype, int transpose, int64_t n, int64_t nrhs, const void* L, int64_t ldl, void* B) {
+    return mxf_trsm_internal(h, st, {.dtype = dtype, .transpose = transpose, .n = n, .nrhs = nrhs, .L = {L, ldl}, .B = {B, nrhs}});
+}
+
 template <typename T>
 int gp_predict_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t N, int64_t Nt, int Q, int P, const T* Xc, const T* Xt, const T* ls, int ard,
                      const T* var, const T* L, int64_t ldl, const T* LinvY, const T* noise, int noise_free, int full_cov, T* mean, T* vout,
@@ -87,7 +92,7 @@ int gp_predict_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t N, int64_t 
     int rc = mxf_gram_internal(h, st, {.kind = kind, .dtype = dtype, .N = N, .N2 = C, .Q = Q, .X = Xc, .X2 = Xt, .ls = ls, .ard = ard, .var = var,
                                        .K = {V, C}});                                                                             // Kxt (N x S Nt) :160
     if (rc) return rc;
-    rc = mxf_trsm_internal(h, dtype, 0, 1, N, C, L, ldl, 0, V, C, 0, 0, st);                                                      // V = L^-1 Kxt :161
+    rc = solve(h, st, dtype, 0, N, C, L, ldl, V);                                                                                 // V = L^-1 Kxt :161
     if (rc) return rc;
     rc = mxf_gemm_internal(h, st, {.dtype = dtype, .ta = 1, .M = C, .N = P, .K = N, .A = {V, C}, .B = {LinvY, P}, .C = {mean, P}});  // V^T LinvY :162
     if (rc) return rc;
@@ -126,20 +131,20 @@ int svgp_predict_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t M, int64_
     rc = mxf_gram_internal(h, st, {.kind = kind, .dtype = dtype, .N = M, .Q = Q, .X = Z, .ls = ls, .ard = ard, .var = var, .jitter = jitter,
                                    .K = {Lm, M}});                                                                                   // Kuu (+ jitter) :146-148
     if (rc) return rc;
-    rc = mxf_potrf_internal(h, dtype, 1, M, Lm, M, 0, info, st);                                                                     // L :149
+    rc = mxf_potrf_internal(h, st, {.dtype = dtype, .n = M, .A = {Lm, M}, .info = info});                                            // L :149
     if (rc) return rc;
-    rc = mxf_potrf_internal(h, dtype, 1, M, Su, M, 0, info ? info + 1 : nullptr, st);                                                // Ls :150
+    rc = mxf_potrf_internal(h, st, {.dtype = dtype, .n = M, .A = {Su, M}, .info = info ? info + 1 : nullptr});                       // Ls :150
     if (rc) return rc;
     MXF_HIP(h, hipMemcpyAsync(LinvLs, Su, sizeof(T) * MM, hipMemcpyDeviceToDevice, st));
-    rc = mxf_trsm_internal(h, dtype, 0, 1, M, M, Lm, M, 0, LinvLs, M, 0, 0, st);                                                     // L^-1 Ls :151
+    rc = solve(h, st, dtype, 0, M, M, Lm, M, LinvLs);                                                                                // L^-1 Ls :151
     if (rc) return rc;
     MXF_HIP(h, hipMemcpyAsync(Linvmu, mu, sizeof(T) * M * P, hipMemcpyDeviceToDevice, st));
-    rc = mxf_trsm_internal(h, dtype, 0, 1, M, P, Lm, M, 0, Linvmu, P, 0, 0, st);                                                     // L^-1 mu :152
+    rc = solve(h, st, dtype, 0, M, P, Lm, M, Linvmu);                                                                                // L^-1 mu :152
     if (rc) return rc;
     rc = mxf_gemm_internal(h, st, {.dtype = dtype, .tb = 1, .M = M, .N = M, .K = M, .A = {LinvLs, M}, .B = {LinvLs, M}, .C = {LSL, M}});  // (L^-1 Ls)(L^-1 Ls)^T :153
     if (rc) return rc;
     MXF_HIP(h, hipMemcpyAsync(wv, Linvmu, sizeof(T) * M * P, hipMemcpyDeviceToDevice, st));
-    rc = mxf_trsm_internal(h, dtype, 1, 1, M, P, Lm, M, 0, wv, P, 0, 0, st);                                                         // L^-T L^-1 mu :154
+    rc = solve(h, st, dtype, 1, M, P, Lm, M, wv);                                                                                    // L^-T L^-1 mu :154
     if (rc) return rc;
     // test inputs
     rc = mxf_gram_internal(h, st, {.kind = kind, .dtype = dtype, .N = M, .N2 = C, .Q = Q, .X = Z, .X2 = Xt, .ls = ls, .ard = ard, .var = var,
@@ -147,7 +152,7 @@ int svgp_predict_typed(mxf_ctx* h, int kind, int dtype, int S, int64_t M, int64_
     if (rc) return rc;
     rc = mxf_gemm_internal(h, st, {.dtype = dtype, .ta = 1, .M = C, .N = P, .K = M, .A = {V, C}, .B = {wv, P}, .C = {mean, P}});      // Kxt^T wv :158
     if (rc) return rc;
-    rc = mxf_trsm_internal(h, dtype, 0, 1, M, C, Lm, M, 0, V, C, 0, 0, st);                                                          // V = L^-1 Kxt :162
+    rc = solve(h, st, dtype, 0, M, C, Lm, M, V);                                                                                     // V = L^-1 Kxt :162
     if (rc) return rc;
     rc = mxf_gemm_internal(h, st, {.dtype = dtype, .M = M, .N = C, .K = M, .A = {LSL, M}, .B = {V, C}, .C = {tmp, C}});               // :165
     if (rc) return rc;

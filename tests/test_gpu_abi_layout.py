@@ -184,7 +184,7 @@ def test_split_gemm_layouts(mode, shape, layout):
 
 
 # ================================================================================= mxf_potrf / mxf_trsm / mxf_trtri / mxf_sumlogdiag
-# Plan form per n (chol.hip potrf_plan): ragged n -> potrf_panel_kernel per 64 columns + gemm updates on sub-blocks A + r0 lda + k0
+# Plan form per n (chol_plan.h potrf_plan): ragged n -> potrf_panel_kernel per 64 columns + gemm updates on sub-blocks A + r0 lda + k0
 # (65: two panels, 200: four); float64 192 -> potrf_tiles_kernel, one launch; float64 1536 -> potrf_tiles_kernel per 512-column outer panel
 # + trailing gemm (LDS-DMA when the sub-block pointers, lda and stride allow it: not with lead1 / ld+3 / gap5); float64 1024: two outer
 # panels; float32 (192, 1024, 1536): the column form.  All chol.hip kernels index element-wise, so an offset base is safe in them; the
