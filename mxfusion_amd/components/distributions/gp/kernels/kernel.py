@@ -34,6 +34,26 @@ class _GramFn(torch.autograd.Function):
         return None, None, dX, dX2, dls, dvar
 
 
+class _PsiRBFFn(torch.autograd.Function):
+    """(Psi1, Psi2) of the RBF kernel under x_n ~ N(mu_n, diag(s_n)) in one fused forward call (mxf_psi_rbf_fwd) and one fused reverse call
+    (mxf_psi_rbf_bwd), which recomputes the N M^2 / 2 terms of Psi2 instead of keeping them."""
+
+    @staticmethod
+    def forward(ctx, ard, mu, s, Z, ls, var):
+        ops_ = [t.contiguous() for t in (mu, s, Z, ls, var)]
+        ctx.ard = ard
+        ctx.save_for_backward(*ops_)
+        ctx.set_materialize_grads(False)          # an unused statistic arrives as None and costs no pass
+        return ops.psi_rbf(*ops_, ard)
+
+    @staticmethod
+    def backward(ctx, G1, G2):
+        ops_ = ctx.saved_tensors
+        acc = [torch.zeros_like(t) if ctx.needs_input_grad[i + 1] else None for i, t in enumerate(ops_)]
+        ops.psi_rbf_bwd_(*ops_, ctx.ard, None if G1 is None else G1.contiguous(), None if G2 is None else G2.contiguous(), *acc)
+        return (None,) + tuple(acc)
+
+
 class _Gram2Fn(torch.autograd.Function):
     """k1 + k2 or k1 * k2 of two stationary kernels in ONE forward pass (mxf_gram2); the reverse mode is mxf_gram_bwd per sub-kernel --
     with dK for a sum, with dK times the other kernel's Gram (recomputed: one mxf_gram each) for a product."""
@@ -200,6 +220,14 @@ class Kernel(object):
     # description used by the fused module algorithms: (kind, ard) for a single stationary kernel, else None
     def fused_spec(self):
         return None
+
+    def psi_statistics(self, F, X_mean, X_var, Z, **kernel_params):
+        """(psi0, Psi1, Psi2): the expectations of Kdiag, K(Z, X) and K(Z, X) K(X, Z) under X ~ N(X_mean, diag(X_var)).  Closed forms exist
+        for the RBF kernel only (RBF.psi_statistics)."""
+        from mxfusion_amd.common.exceptions import ModelSpecificationError
+        raise ModelSpecificationError('psi statistics (uncertain inputs) are supported for a single RBF kernel over all input dimensions '
+                                      '(ARD or not, at most %d of them); got %s%s' % (ops._lib.PSI_MAX_Q, type(self).__name__,
+                                      ' with active_dims' if self.active_dims is not None else ''))
 
 
 class NativeKernel(Kernel):

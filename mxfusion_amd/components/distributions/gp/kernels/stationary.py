@@ -3,7 +3,8 @@ import torch
 
 from mxfusion_amd.components.variables.variable import Variable
 from mxfusion_amd.components.variables.var_trans import PositiveTransformation
-from .kernel import NativeKernel, _GramFn
+from mxfusion_amd import ops
+from .kernel import NativeKernel, _GramFn, _PsiRBFFn
 
 
 class StationaryKernel(NativeKernel):
@@ -35,6 +36,15 @@ class RBF(StationaryKernel):
 
     def __init__(self, input_dim, ARD=False, variance=1., lengthscale=1., name='rbf', active_dims=None, dtype=None, ctx=None):
         super(RBF, self).__init__(input_dim, ARD, variance, lengthscale, name, active_dims, dtype, ctx)
+
+    def psi_statistics(self, F, X_mean, X_var, Z, **kernel_params):
+        """psi0 (S,) = N variance, Psi1 (S, M, N), Psi2 (S, M, M) under X ~ N(X_mean, diag(X_var)), X_var >= 0 (mxf_psi_rbf_fwd / _bwd),
+        differentiable in X_mean, X_var, Z, lengthscale and variance; every operand carries the sample axis (extent 1: shared)."""
+        if self.active_dims is not None or X_mean.shape[-1] > ops._lib.PSI_MAX_Q:
+            return super(RBF, self).psi_statistics(F, X_mean, X_var, Z, **kernel_params)
+        p = self._strip(kernel_params)
+        Psi1, Psi2 = _PsiRBFFn.apply(bool(self.ARD), X_mean, X_var, Z, p['lengthscale'], p['variance'])
+        return X_mean.shape[-2] * p['variance'][:, 0], Psi1, Psi2
 
 
 class Matern52(StationaryKernel):

@@ -613,6 +613,45 @@ def lik_moments(kind, m, v, num_nodes=20):
     return e1, e2
 
 
+def _psi_operands(what, mu, s, Z, lengthscale, variance, ard, *buffers):
+    """(S, N, M, Q, [pointer, sample stride of mu, s, Z], [lengthscale, ard, stride], [variance, stride]) of the RBF psi statistics:
+    mu, s (S|1, N, Q), Z (S|1, M, Q), lengthscale (S|1, Q with ard else 1), variance (S|1, 1)"""
+    _same_kind(what, mu, s, Z, lengthscale, variance, *buffers, contiguous=True)
+    if mu.dim() != 3 or s.shape[1:] != mu.shape[1:] or s.dim() != 3 or Z.dim() != 3 or Z.shape[2] != mu.shape[2]:
+        raise ValueError('%s: mu and s are (S|1, N, Q) and Z is (S|1, M, Q); got %s, %s, %s' % (what, tuple(mu.shape), tuple(s.shape), tuple(Z.shape)))
+    N, M, Q = int(mu.shape[1]), int(Z.shape[1]), int(mu.shape[2])
+    if lengthscale.dim() != 2 or lengthscale.shape[1] != (Q if ard else 1) or variance.dim() != 2 or variance.shape[1] != 1:
+        raise ValueError('%s: lengthscale is (S|1, %d) and variance (S|1, 1); got %s, %s'
+                         % (what, Q if ard else 1, tuple(lengthscale.shape), tuple(variance.shape)))
+    ops_ = (mu, s, Z, lengthscale, variance)
+    S = num_samples(*ops_)
+    if any(t.shape[0] not in (1, S) for t in ops_):
+        raise ValueError('%s: the sample axes must be 1 or %d' % (what, S))
+    st = lambda t: [_p(t), 0 if t.shape[0] == 1 else t.stride(0)]
+    return S, N, M, Q, st(mu) + st(s) + st(Z), [_p(lengthscale), int(bool(ard)), st(lengthscale)[1]], st(variance)
+
+
+def psi_rbf(mu, s, Z, lengthscale, variance, ard, want_psi1=True, want_psi2=True):
+    """(Psi1 (S, M, N), Psi2 (S, M, M)) of the RBF kernel under x_n ~ N(mu_n, diag(s_n)), s >= 0; None for the one not wanted
+    (mxf_psi_rbf_fwd).  Psi2 is bitwise symmetric."""
+    S, N, M, Q, big, ls, var = _psi_operands('psi statistics', mu, s, Z, lengthscale, variance, ard)
+    Psi1 = torch.empty((S, M, N), dtype=mu.dtype, device=mu.device) if want_psi1 else None
+    Psi2 = torch.empty((S, M, M), dtype=mu.dtype, device=mu.device) if want_psi2 else None
+    _lib.call('mxf_psi_rbf_fwd', _h(mu), _dt(mu), S, N, M, Q, *big, *ls, *var, _p(Psi1), _p(Psi2), _stream())
+    return Psi1, Psi2
+
+
+def psi_rbf_bwd_(mu, s, Z, lengthscale, variance, ard, G1, G2, dmu_acc=None, ds_acc=None, dZ_acc=None, dls_acc=None, dvar_acc=None):
+    """The reverse mode of psi_rbf: the cotangents G1 (S, M, N) and G2 (S, M, M, need not be symmetric), either None, ACCUMULATED into
+    buffers shaped like the operands, a shared sample axis at extent 1 and summed over (mxf_psi_rbf_bwd)."""
+    S, N, M, Q, big, ls, var = _psi_operands('psi statistics', mu, s, Z, lengthscale, variance, ard, G1, G2, dmu_acc, ds_acc, dZ_acc, dls_acc,
+                                             dvar_acc)
+    _check_buffers('psi statistics', (G1, (S, M, N)), (G2, (S, M, M)), (dmu_acc, mu.shape), (ds_acc, s.shape), (dZ_acc, Z.shape),
+                   (dls_acc, lengthscale.shape), (dvar_acc, variance.shape))
+    _lib.call('mxf_psi_rbf_bwd', _h(mu), _dt(mu), S, N, M, Q, *big, *ls, *var, _p(G1), _p(G2), _p(dmu_acc), _p(ds_acc), _p(dZ_acc), _p(dls_acc),
+              _p(dvar_acc), _stream())
+
+
 MVN_MAX_ORDER = 32      # the order up to which the mxf_mvn_* entry points run (MVN_MAX of mvn.hip)
 
 
