@@ -283,11 +283,6 @@ __global__ void bcast_copy_kernel(int S, int64_t n, const T* __restrict__ src, i
 inline unsigned dotgrid(int64_t n) { int64_t b = (n + 255) / 256; if (b < 1) b = 1; if (b > 64) b = 64; return (unsigned)b; }
 inline unsigned gridn(int64_t n) { int64_t b = (n + 255) / 256; if (b < 1) b = 1; if (b > 4096) b = 4096; return (unsigned)b; }
 
-struct Carver {   // bump allocator over the handle's scratch; with a null base it only counts
-    char* base; size_t off = 0;
-    explicit Carver(void* p) : base((char*)p) {}
-    template <typename U> U* take(size_t n) { U* p = base ? (U*)(base + off) : nullptr; off += mxf_align(n * sizeof(U)); return p; }
-};
 // A composite's scratch layout is ONE list of take() calls (`layout`), run once to count the bytes and once to carve them, so the two
 // cannot disagree.  false (need = the bytes asked for) when the scratch cannot be allocated.
 template <typename F>
@@ -961,26 +956,12 @@ __global__ __launch_bounds__(256) void norm1_sym16_kernel(int64_t n, const doubl
     }
 }
 
-// Which path one SVGP call takes, from shapes, strides, dtype and h->svgp_form, and the sizes every stage uses.  The stages rely on:
-//   use_split  => float32, want_grad, !het, SB % 16 == 0        whiten    => use_split
-//   bt_path    => use_split, !whiten                             bt_wh     => whiten
-//   het_stream => !het, float32                                  het_split => het, float32
-//   fused       = want_grad && !het: the streaming reverse pass, its accumulate-into outputs cleared at the start of the call
-struct SvgpPlan {
-    bool use_mat, ysamp, het_stream, het, fused, use_split, whiten, bt_path, bt_wh, het_split;
-    int SS, SYc, lsn;           // samples with columns of their own, Y samples per column, length-scales
-    int64_t SB, MM, MP;
-    double a1, bw;
-    size_t pl_big, pl_h0, gp_scr;
-    const float* split_var;
-};
-
-// One SVGP call: its arguments (in the order of the C ABI), its plan, its scratch and the stages that queue its launches.  The stages run in
-// enqueue order, which is priority order across the three streams -- the host needs ~5 us per launch and a step has ~280 of them.
+// One SVGP call: its arguments, its plan (svgp_plan.h), its scratch and the stages that queue its launches.  The stages run in enqueue order,
+// which is priority order across the three streams -- the host needs ~5 us per launch and a step has ~280 of them.
 template <typename T>
-struct SvgpCall : SvgpPlan {
+struct SvgpCall : SvgpPlan, SvgpScratch<T> {
     typedef double D;
-    mxf_ctx* h; int kind, dtype, S; int64_t B, M; int Q, P;
+    mxf_ctx* h; int kind, dtype, S; int64_t B; int Q, P;
     const T* X; int64_t sX; const T* Y; int64_t sY; const T* Z; const T* noise; int64_t nrows; int ncols;
     const T* mu; const T* W; const T* sdiag; const T* ls; int ard; const T* var;
     double jitter, scaling, gscale;
@@ -988,6 +969,28 @@ struct SvgpCall : SvgpPlan {
     T* dX; T* dY; T* dZ; T* dnoise; T* dmu; T* dW; T* dSdiag; T* dls; T* dvar;
     hipStream_t st;
     SvgpMat<T> mat;
+    double a1, bw;                  // gscale * scaling, gscale * S
+    const float* split_var;
+    SvgpRequest req;
+    SvgpSchedule sched;
+
+    SvgpCall(mxf_ctx* h_, const MxfSvgp& d)
+        : SvgpScratch<T>(), h(h_), kind(d.kind), dtype(d.dtype), S(d.S), B(d.B), Q(d.Q), P(d.P), X((const T*)d.X), sX(d.sX), Y((const T*)d.Y), sY(d.sY), Z((const T*)d.Z),
+          noise((const T*)d.noise), nrows(d.nrows), ncols(d.ncols), mu((const T*)d.mu), W((const T*)d.W), sdiag((const T*)d.sdiag), ls((const T*)d.ls),
+          ard(d.ard), var((const T*)d.var), jitter(d.jitter), scaling(d.scaling), gscale(d.gscale), logL((T*)d.logL), info(d.info), want_grad(d.want_grad),
+          dX((T*)d.dX), dY((T*)d.dY), dZ((T*)d.dZ), dnoise((T*)d.dnoise), dmu((T*)d.dmu), dW((T*)d.dW), dSdiag((T*)d.dSdiag), dls((T*)d.dls),
+          dvar((T*)d.dvar), st((hipStream_t)d.stream),
+          mat{(const T*)d.Kuu, (const T*)d.Kuf, (const T*)d.Kdiag, (T*)d.dKuu, (T*)d.dKuf, (T*)d.dKdiag}, a1(d.gscale * d.scaling),
+          bw(d.gscale * (double)d.S), split_var((const float*)d.var) {
+        M = d.M;
+    }
+    // (the scratch pointers live in a base that depends on T: named here so that the stages read them as plain members)
+    typedef SvgpScratch<T> Sc;
+    using Sc::Zd, Sc::lsd, Sc::vard, Sc::noised, Sc::mud, Sc::Wd, Sc::sd, Sc::Lm, Sc::Linv, Sc::Ki, Sc::Su, Sc::Lsinv, Sc::Sui, Sc::KiSu, Sc::H0,
+          Sc::tmp, Sc::wd, Sc::sc, Sc::scal, Sc::ad, Sc::hhs, Sc::hbe2, Sc::G, Sc::T1, Sc::AKi, Sc::T2, Sc::dKuu, Sc::dSu, Sc::Gw, Sc::dmud, Sc::dZc,
+          Sc::dlsc, Sc::dvc, Sc::Aext, Sc::wT, Sc::Text, Sc::qbuf, Sc::Kuf, Sc::Kfu, Sc::Psi2, Sc::R, Sc::Eb, Sc::aT, Sc::plKfu, Sc::plH0, Sc::plKuf,
+          Sc::plLi, Sc::wpl, Sc::plVt, Sc::hsA, Sc::hsK, Sc::hsS, Sc::gscr0, Sc::gscr1, Sc::sigf, Sc::upart, Sc::hcs, Sc::hrs, Sc::hys, Sc::hnz, Sc::info2,
+          Sc::hsw, Sc::pVt;
 
     // float32 mode: the symmetric products of the core -- Ki, H0 and X = Ki G Ki -- as lower tiles + mirror (half the work of a product that
     // runs on the 88 CUs Psi2 leaves in the few-sample regime; the results become exactly symmetric), and the core's reverse mode in the X form.
@@ -1000,15 +1003,6 @@ struct SvgpCall : SvgpPlan {
 
     hipStream_t sd_ = nullptr, s2_ = nullptr;             // h->side, h->side2
     double* cond_slot = nullptr;
-    int t_blocked = 0;
-
-    // scratch (carve; what a path does not take stays null)
-    D *Zd, *lsd, *vard, *noised, *mud, *Wd, *sd, *Lm, *Linv, *Ki, *Su, *Lsinv, *Sui, *KiSu, *H0, *tmp, *wd, *sc, *scal, *ad, *hhs, *hbe2;
-    D *G, *T1, *AKi, *T2, *dKuu, *dSu, *Gw, *dmud, *dZc, *dlsc, *dvc;
-    T *Aext, *wT, *Text, *qbuf, *Kuf, *Kfu, *Psi2, *R, *Eb, *aT;
-    unsigned short *plKfu, *plH0, *plKuf, *plLi, *wpl, *plVt, *hsA, *hsK, *hsS;
-    float *gscr0, *gscr1, *sigf, *upart, *hcs, *hrs, *hys, *hnz;
-    int* info2; unsigned* hsw; int64_t pVt;
 
     // C = alpha op(A) op(B) + beta C for M x M float64 operands (lower: the lower tiles only)
     int mm(int ta, int tb, double alpha, const D* A, const D* Bm, double beta, D* C, hipStream_t s_, int lower = 0) {
@@ -1036,93 +1030,19 @@ struct SvgpCall : SvgpPlan {
     }
     void publish_cond() { hipLaunchKernelGGL(cond_publish_kernel, dim3(1), dim3(1), 0, st, h->cond_dev, cond_slot); }
 
-    // every path flag of the call, and the shape checks that go with them
+    // the path flags and sizes (svgp_plan.h), the Psi2 / Phi / V schedule with the probe build's knobs, and the scratch
     int plan() {
-        constexpr bool f32 = sizeof(T) == 4;
-        if (P > 8) MXF_FAIL(h, -3, "mxf_svgp_logpdf: P > 8 outputs not supported");
-        if ((nrows != 1 && nrows != B) || (ncols != 1 && ncols != P)) MXF_FAIL(h, -2, "mxf_svgp_logpdf: noise_var must be (1|B, 1|P)");
-        use_mat = mat.Kuu != nullptr;
-        // sampled Y over shared X (hence shared Kuf, T, U): the S samples share the B columns -- generic path, the data term is quadratic in Y
-        ysamp = S > 1 && sX == 0 && sY != 0;
-        if (ysamp && sY != B * P) MXF_FAIL(h, -2, "mxf_svgp_logpdf: Y samples must be contiguous");
-        SS = (sX == 0) ? 1 : S;
-        SB = (int64_t)SS * B;
-        // generic path (het): Kuf-side reverse mode through a materialised dKuf (not the streaming fused pass); also for Q > 16 inputs, which the
-        // register-tiled fused reverse pass does not cover (gram_bwd.hip: generic kernel).  Per-row noise (B, 1) with one output column on the
-        // float32 split path runs the STREAMING form (het_stream: het_* kernels above); every other heteroscedastic shape keeps the generic path.
-        het_stream = f32 && want_grad && nrows == B && nrows > 1 && ncols == 1 && P == 1 && !use_mat && !ysamp && Q <= 8 && (B % 16 == 0) &&
-                     (M % 16 == 0) && M >= 128 && h->svgp_form == MXF_SVGP_EXPLICIT && mxf_svgp_bwd_is_mfma(kind, dtype, SB, B, Q, P, X);
-        het = (nrows > 1 || ncols > 1 || use_mat || ysamp || Q > 16) && !het_stream;
-        if (sX != 0 && sX != B * Q) MXF_FAIL(h, -2, "mxf_svgp_logpdf: X samples must be contiguous");
-        if (S > 1 && sX == 0 && sY == 0) MXF_FAIL(h, -3, "mxf_svgp_logpdf: S > 1 with neither X nor Y sampled");
-        SYc = ysamp ? S : 1;
-        MM = M * M; MP = M * P;
-        lsn = ard ? Q : 1;
-        a1 = gscale * scaling; bw = gscale * (double)S;
-        fused = want_grad && !het;
-        // float32 streaming: the two big GEMMs run on the 16-bit matrix pipe from split planes of their operands (gemm_split.hip), in the format
-        // of two scaled f16 terms (three products)
-        use_split = fused && f32 && (SB % 16 == 0) && (M % 16 == 0) && M >= 128 && Q <= 16;
-        pl_big = mxf_split_plane_elems(M, SB); pl_h0 = mxf_split_plane_elems(M, M);     // == mxf_split_plane_elems(SB, M)
-        gp_scr = use_split ? mxf_gram_planes_scratch_bytes(SB, SB, Q) : 0;      // upper bound for either orientation
-        split_var = (const float*)var;
-        // float32 streaming form (mxf_svgp_configure): the whitened tier runs on the f16x2 split kernels' wide forms only
-        whiten = f32 && want_grad && h->svgp_form == MXF_SVGP_WHITENED;
-        if (whiten && !(use_split && (M % 128) == 0 && (SB % 256) == 0))
-            MXF_FAIL(h, -3, "mxf_svgp_logpdf: the whitened float32 form needs M %% 128 == 0, S B %% 256 == 0, Q <= 16, homoscedastic noise (see mxf_svgp_whitened_ok)");
-        // ONE set of Kuf planes: T = H0 Kuf reads the planes Psi2 reads (operand (m, k = n)) through gemm_bt.hip's transposing LDS read, and forms
-        // the row U = w^T Kuf on the way (a second planes pass wrote 8.6 GB between the two products: 1.8 ms of the 24 ms step with the matrix pipe
-        // idle).  Needs the explicit float32 form, one output column, whole 256 x 256 tiles.
-        bt_path = use_split && !whiten && !het_stream && P == 1 && M <= 2048 && mxf_gemm_bt_ok(M, SB, M);
-        // the whitened tier likewise: T = Hh V reads the planes of V that Phi = V V^T reads (the V product's planes output IS the K-major layout),
-        // and forms U = a^T V on the way -- the V product writes neither the planes of V^T (8.6 GB) nor the partial sums of U
-        bt_wh = whiten && P == 1 && M <= 2048 && mxf_gemm_bt_ok(M, SB, M);
-        // the generic (materialised-Gram / heteroscedastic) float32 path's two big products on the f16 matrix pipe as well: T = H0 Kuf through the
-        // K-major product from the planes of Kuf (split from the float32 Gram: one maxabs + one split pass, 0.17 ms at 512 x 131 072), and
-        // G' = Ksc Kuf^T from the planes of Ksc and the same Kuf planes -- f32-equivalent like the streaming path's products (three f16 products, f32
-        // accumulation) where the generic kernel ran true-f32 MFMAs at 100 TF: the deep GP's first layer 0.68 + 0.66 ms -> planes 0.35 + products 0.3.
-        het_split = het && f32 && want_grad && mxf_gemm_bt_ok(M, SB, M) && (int64_t)M * SB >= (int64_t)1 << 24;
-        return 0;
-    }
-
-    // the scratch layout, one list: scratch() runs it once to count and once to carve
-    void carve(Carver& cv) {
-        Zd = cv.take<D>(M * Q); lsd = cv.take<D>(lsn); vard = cv.take<D>(1); noised = cv.take<D>(1);     // f64 copies of the parameters
-        mud = cv.take<D>(MP); Wd = cv.take<D>(MM); sd = cv.take<D>(M);
-        Lm = cv.take<D>(MM); Linv = cv.take<D>(MM); Ki = cv.take<D>(MM); Su = cv.take<D>(MM); Lsinv = cv.take<D>(MM);
-        Sui = cv.take<D>(MM); KiSu = cv.take<D>(MM); H0 = cv.take<D>(MM); tmp = cv.take<D>(MM);
-        wd = cv.take<D>(MP); sc = cv.take<D>(16); scal = cv.take<D>(2 * (size_t)S); info2 = cv.take<int>(8);
-        Aext = cv.take<T>((size_t)(M + P) * M); wT = cv.take<T>(MP);
-        Text = cv.take<T>((size_t)(M + P) * SB); qbuf = cv.take<T>((size_t)SB);
-        if (use_split) {
-            plKfu = cv.take<unsigned short>(3 * pl_big); plH0 = cv.take<unsigned short>(3 * pl_h0); plKuf = cv.take<unsigned short>(3 * pl_big);
-            gscr0 = (float*)cv.take<char>(gp_scr); gscr1 = (float*)cv.take<char>(gp_scr);
-        } else {
-            Kuf = cv.take<T>((size_t)M * SB);        // Kuf, Kfu in the streaming dtype
-            if (want_grad) Kfu = cv.take<T>((size_t)M * SB);
-        }
-        if (whiten) { plLi = cv.take<unsigned short>(2 * pl_h0); ad = cv.take<D>(MP); aT = cv.take<T>(MP); sigf = cv.take<float>(4); upart = cv.take<float>((size_t)(M / 128) * SB); }
-        if (bt_path || bt_wh) wpl = cv.take<unsigned short>(2 * (size_t)M + 8);
-        if (het_stream) { hcs = cv.take<float>(B); hrs = cv.take<float>(B); hys = cv.take<float>((size_t)(sY == 0 ? B : SB)); hhs = cv.take<D>(4); hbe2 = cv.take<D>(S); hnz = cv.take<float>(4); }
-        if (het_split) { hsA = cv.take<unsigned short>(2 * pl_h0); hsK = cv.take<unsigned short>(2 * pl_big); hsS = cv.take<unsigned short>(2 * pl_big); hsw = cv.take<unsigned>(4); }
-        if (want_grad) {
-            Psi2 = cv.take<T>(MM); R = cv.take<T>(MP); Eb = cv.take<T>((size_t)SB * P);
-            G = cv.take<D>(MM); T1 = cv.take<D>(MM); AKi = cv.take<D>(MM); T2 = cv.take<D>(MM); dKuu = cv.take<D>(MM); dSu = cv.take<D>(MM);
-            Gw = cv.take<D>(MP); dmud = cv.take<D>(MP); dZc = cv.take<D>(M * Q); dlsc = cv.take<D>(lsn); dvc = cv.take<D>(4);
-        }
-        // sc: [0]=sumlogdiag L, [1]=sumlogdiag Ls, [2]=tr(Ki Su), [3]=mu.w, [4]=dnoise, [5]=dvar_direct, [6], [7]: whitened tier's q_n total
-    }
-
-    int scratch() {
+        req.esize = sizeof(T); req.kind = kind; req.S = S; req.B = B; req.M = M; req.Q = Q; req.P = P; req.sX = sX; req.sY = sY; req.nrows = nrows; req.ncols = ncols;
+        req.ard = ard; req.want_grad = want_grad; req.use_mat = mat.Kuu != nullptr; req.form = h->svgp_form; req.x_aligned16 = ((uintptr_t)X % 16) == 0;
+        static_cast<SvgpPlan&>(*this) = svgp_plan(req);
+        if (refusal) MXF_FAIL(h, rc, "%s", refusal);
+        sched = svgp_psi2_schedule(*this, mxf_svgp_knobs());
         size_t need;
-        if (!carve_scratch(h, [&](Carver& cv) { carve(cv); }, need)) MXF_FAIL(h, -4, "mxf_svgp_logpdf: cannot allocate %zu bytes of scratch", need);
+        if (!carve_scratch(h, [&](Carver& cv) { this->carve(cv, req, *this); }, need)) MXF_FAIL(h, -4, "mxf_svgp_logpdf: cannot allocate %zu bytes of scratch", need);
         // whitened tier: the planes of V^T (operand (n, k = m) of T = Hh V) go into the THIRD plane slots of the two big buffers (sized for the
         // three-plane bf16 format; the whitened tier runs two-plane f16x2 only) -- the V product writes them next to V's own planes while other
         // workgroups still read the Kfu planes, so they cannot share that buffer's first two slots
         if (whiten) { plVt = plKfu + 2 * pl_big; pVt = (int64_t)((plKuf + 2 * pl_big) - plVt); }
-        // (training step on the split path whose reverse pass runs on the matrix pipe: T is written in 16-column blocks, so that each 16 x 16
-        //  tile that pass reads is one contiguous KB instead of 16 pieces of 64 bytes, 4 SB bytes apart)
-        t_blocked = (use_split && mxf_svgp_bwd_reads_blocked(kind, dtype, SB, B, Q, P, Text)) ? 1 : 0;
         return 0;
     }
 
@@ -1200,10 +1120,6 @@ struct SvgpCall : SvgpPlan {
     // side stream: Kuf_all (as a Gram or as split planes; whitened: the Kfu planes), Kfu_all and Psi2.  Queued before the Kuu chain: these few
     // launches carry the bulk of the device work.
     int kuf_psi2() {
-        static const int64_t psi2_ka = MXF_KNOB("MXF_SVGP_PSI2_KA", -1);
-        static const bool psi2_ra_env = MXF_KNOB_SET("MXF_SVGP_PSI2_RA");
-        static const int psi2_ra = (int)MXF_KNOB("MXF_SVGP_PSI2_RA", 148);
-        static const int psi2_rb = MXF_KNOB("MXF_SVGP_PSI2_RB", 16);
         int rc;
         if (use_mat) {
             Kuf = const_cast<T*>(mat.Kuf);          // the caller's Gram is only ever read (a copy into the scratch: 268 MB, 0.13 ms at 512 x 131 072)
@@ -1235,36 +1151,22 @@ struct SvgpCall : SvgpPlan {
         }
         if (!use_split) MXF_HIP(h, hipEventRecord(h->ev_aux, sd_));          // Kuf ready: the T GEMM waits for it
         if (!fused || whiten) return 0;
-        // Psi2 = Kuf Kuf^T depends on neither the core nor the T GEMM nor the reverse pass: it starts at once on the side stream,
-        // lower blocks only, split-K.  float32: from the split planes of Kuf (gemm_split.hip); float64 / fallback: from the TRANSPOSED
-        // Gram Kfu (S*B x M, rows = contiguous lines) as a TN GEMM (the NT form on Kuf reads 256 K-strided streams per workgroup).
-        // Two launches: phase A covers the first KA = 128 M columns (about as long as the core chains run) with ONE workgroup per CU on
-        // ~216 CUs, so that the core chains' f64 workgroups (a whole CU's LDS / registers each) still find free CUs; phase B (the rest)
-        // fills the chip.  Same-box A/B at 4 samples per GPU: 13.65 -> 12.95 ms per step; neutral at 32 samples.
-        // (few samples per GPU: the whole product runs in the reduced-occupancy form -- the core chains are the critical path there and
-        //  Psi2 is short; same-box at 4 samples: 5.46 -> 5.20 ms per step; at 32 samples a longer first phase costs 0.1-0.4 ms)
-        const int64_t ka_dflt = (use_split ? 192 : 128) * M;
-        // one set of planes (bt_path): nothing but the core chains runs next to Psi2, so the whole product leaves them 32 CUs and there is no
-        // reduced first phase -- the chains finish under Psi2 and T starts when Psi2 ends (same box, 32 samples: 23.5 -> 22.85 ms per step with
-        // a second planes pass beside it before; 24 CUs: 23.8; 40: 22.9)
-        const int64_t ka_req = psi2_ka >= 0 ? psi2_ka : (use_split && SB <= 2 * ka_dflt ? SB : (bt_path ? 0 : ka_dflt));
-        const int rb_phase_b = (bt_path && !MXF_KNOB_SET("MXF_SVGP_PSI2_RB")) ? 32 : psi2_rb;
-        const int64_t KA = (ka_req > 0 && ka_req < SB) ? ka_req / 32 * 32 : (ka_req > 0 ? SB : 0);
+        // Psi2 = Kuf Kuf^T in the two launches of the schedule (svgp_plan.h), lower blocks only, split-K.  float32: from the split planes of Kuf
+        // (gemm_split.hip); float64 / fallback: from the TRANSPOSED Gram Kfu (S*B x M, rows = contiguous lines) as a TN GEMM (the NT form on Kuf
+        // reads 256 K-strided streams per workgroup).
+        const int64_t KA = sched.KA;
         MXF_T0(h, MXF_T_PSI2, sd_);
         if (use_split) {
             const MxfSplitScale kuf2 = {.alpha = (double)split_ga * split_ga, .ad0 = split_var, .pow0 = 2};      // both operands are Kuf planes: k / variance 2^14
             if (KA > 0) {
-                // 4 workgroups of the two-term kernel fit a CU: (256 - 202) * 4 = 216 workgroups = one per CU on 216 CUs.  One-planes path:
-                // (256 - 214) * 4 = 168 workgroups -- the chains are alone on what Psi2 leaves, and 88 CUs serve the few-sample step better than 40
-                // (same box, 4 samples: 4.30 -> 4.21 ms; 210: 4.25-4.32, 218: 4.22-4.26, 224: 4.27; configs[3] at 4 samples 2.41 -> 2.37)
                 rc = mxf_gemm_split_internal(h, sd_, split_mode, M, M, KA, kuf2, {plKuf, (int64_t)pl_big}, {plKuf, (int64_t)pl_big},
-                                             {.C = (float*)Psi2, .ldc = M, .lower_only = 1}, {.reserve_cus = psi2_ra_env ? psi2_ra : (bt_path ? 214 : 202)});
+                                             {.C = (float*)Psi2, .ldc = M, .lower_only = 1}, {.reserve_cus = sched.reserve_a});
                 if (rc) return rc;
             }
             if (KA < SB) {
                 const unsigned short* pk = plKuf + (KA / 16) * M * 16;
                 rc = mxf_gemm_split_internal(h, sd_, split_mode, M, M, SB - KA, kuf2, {pk, (int64_t)pl_big}, {pk, (int64_t)pl_big},
-                                             {.C = (float*)Psi2, .ldc = M, .beta = KA > 0 ? 1.0 : 0.0, .lower_only = 1}, {.reserve_cus = rb_phase_b});
+                                             {.C = (float*)Psi2, .ldc = M, .beta = KA > 0 ? 1.0 : 0.0, .lower_only = 1}, {.reserve_cus = sched.reserve_b});
                 if (rc) return rc;
             }
         } else {
@@ -1272,12 +1174,12 @@ struct SvgpCall : SvgpPlan {
             if (rc) return rc;
             if (KA > 0) {
                 rc = mxf_gemm_internal(h, sd_, {.dtype = dtype, .ta = 1, .M = M, .N = M, .K = KA, .A = {Kfu, M}, .B = {Kfu, M}, .C = {Psi2, M}, .lower_only = 1,
-                                                .reserve_cus = psi2_ra});
+                                                .reserve_cus = sched.reserve_a});
                 if (rc) return rc;
             }
             if (KA < SB) {
                 rc = mxf_gemm_internal(h, sd_, {.dtype = dtype, .ta = 1, .M = M, .N = M, .K = SB - KA, .A = {Kfu + KA * M, M}, .B = {Kfu + KA * M, M},
-                                                .beta = KA > 0 ? 1.0 : 0.0, .C = {Psi2, M}, .lower_only = 1, .reserve_cus = psi2_rb});
+                                                .beta = KA > 0 ? 1.0 : 0.0, .C = {Psi2, M}, .lower_only = 1, .reserve_cus = sched.reserve_b});
                 if (rc) return rc;
             }
         }
@@ -1310,7 +1212,6 @@ struct SvgpCall : SvgpPlan {
 
     // whitened tier: the planes of L^-1 and a = L^-1 mu on the caller's stream; V = L^-1 Kuf, U = a^T V and Phi = V V^T on the side stream
     int whiten_v_phi() {
-        static const int psi2_rb = MXF_KNOB("MXF_SVGP_PSI2_RB", 16);
         if (!whiten) return 0;
         unsigned* limax = (unsigned*)(info2 + 4);           // bit pattern of max |L^-1| (word cleared by svgp_init_kernel)
         // L^-1 as f16x2 planes (the A operand of V = L^-1 Kuf); Aext is free until Hh is formed
@@ -1330,14 +1231,12 @@ struct SvgpCall : SvgpPlan {
         // partial sums of U = a^T V (a separate transposition + U pass over the planes took 3.3 ms of the 35 ms step -- 17 GB of traffic).
         MXF_HIP(h, hipStreamWaitEvent(sd_, h->ev_aux2, 0));
         MXF_T0(h, MXF_T_VGEMM, sd_);
-        // (few samples per GPU: the Kuu chain on the caller's stream is the critical path -- both side-stream products leave it 40 CUs)
-        const bool few = SB <= 2 * 192 * M;
         const bool vt = !bt_wh, u1 = vt && P == 1;      // (bt_wh: planes of V only -- T and U come from them, gemm_bt.hip)
         MxfSplitOut v = {.planes = plKuf, .pstride = (int64_t)pl_big, .a_lower = 1};
         if (vt) { v.planes_t = plVt; v.pstride_t = pVt; }
         if (u1) { v.avec = (const float*)aT; v.Upart = upart; }
         rc = mxf_gemm_split_internal(h, sd_, split_mode, M, SB, M, {.alpha = 1.0, .ad0 = sigf, .pow0 = 1}, {plLi, (int64_t)pl_h0, (const unsigned*)limax},
-                                     {plKfu, (int64_t)pl_big}, v, {.reserve_cus = few ? 40 : 0});
+                                     {plKfu, (int64_t)pl_big}, v, {.reserve_cus = sched.reserve_v});
         if (rc) return rc;
         MXF_T1(h, MXF_T_VGEMM, sd_);
         MXF_STAGE(h, "V = Linv Kuf (sd)", sd_);
@@ -1357,7 +1256,7 @@ struct SvgpCall : SvgpPlan {
         MXF_T0(h, MXF_T_PSI2, sd_);
         rc = mxf_gemm_split_internal(h, sd_, split_mode, M, M, SB, {.alpha = (double)split_ga * split_ga, .ad0 = split_var, .pow0 = 1},
                                      {plKuf, (int64_t)pl_big}, {plKuf, (int64_t)pl_big}, {.C = (float*)Psi2, .ldc = M, .lower_only = 1},
-                                     {.reserve_cus = few ? 202 : psi2_rb});
+                                     {.reserve_cus = sched.reserve_phi});
         if (rc) return rc;
         symmetrize(Psi2, sd_);
         MXF_T1(h, MXF_T_PSI2, sd_);
@@ -1728,7 +1627,6 @@ struct SvgpCall : SvgpPlan {
 template <typename T>
 int svgp_logpdf_typed(SvgpCall<T>& c) {
     if (int rc = c.plan()) return rc;
-    if (int rc = c.scratch()) return rc;
     if (int rc = c.prologue()) return rc;               // st
     if (int rc = c.kuu_fork()) return rc;               // st
     if (int rc = c.su_side2()) return rc;               // side2
@@ -1945,25 +1843,19 @@ extern "C" int mxf_gp_logpdf(mxf_handle h, int kind, int dtype, int S, int64_t N
     });
 }
 
-static int svgp_dispatch(mxf_handle h, const char* fn, int kind, int dtype, int S, int64_t B, int64_t M, int Q, int P,
-                         const void* X, int64_t strideS_X, const void* Y, int64_t strideS_Y, const void* Z, const void* noise_var,
-                         int64_t noise_rows, int noise_cols, const void* qU_mean, const void* qU_cov_W, const void* qU_cov_diag,
-                         const void* lengthscale, int ard, const void* variance, double jitter, double scaling, double gscale,
-                         void* logL, int* info, int want_grad, void* dX, void* dY, void* dZ, void* dnoise, void* dmu, void* dW,
-                         void* dSdiag, void* dls, void* dvar, void* stream) {
-    if (!h) return -1;
-    if (S <= 0 || B <= 0 || M <= 0 || Q <= 0 || P <= 0) MXF_FAIL(h, -2, "%s: bad shape", fn);
-    if (!X || !Y || !Z || !noise_var || !qU_mean || !qU_cov_W || !qU_cov_diag || !lengthscale || !variance || !logL)
-        MXF_FAIL(h, -2, "%s: null argument", fn);
-    if (kind > MXF_K_MATERN52) MXF_FAIL(h, -2, "%s: stationary kernels only", fn);
-    return by_dtype(h, fn, dtype, [&](auto t) {
-        typedef decltype(t) T;
-        SvgpCall<T> c{{}, h, kind, dtype, S, B, M, Q, P, (const T*)X, strideS_X, (const T*)Y, strideS_Y, (const T*)Z, (const T*)noise_var,
-                      noise_rows, noise_cols, (const T*)qU_mean, (const T*)qU_cov_W, (const T*)qU_cov_diag, (const T*)lengthscale, ard,
-                      (const T*)variance, jitter, scaling, gscale, (T*)logL, info, want_grad, (T*)dX, (T*)dY, (T*)dZ, (T*)dnoise, (T*)dmu,
-                      (T*)dW, (T*)dSdiag, (T*)dls, (T*)dvar, (hipStream_t)stream};
+// the typed call behind every SVGP entry point; svgp_checked: behind those that take coordinates
+static int svgp_run(mxf_handle h, const char* fn, const MxfSvgp& d) {
+    return by_dtype(h, fn, d.dtype, [&](auto t) {
+        SvgpCall<decltype(t)> c(h, d);
         return svgp_logpdf_typed(c);
     });
+}
+static int svgp_checked(mxf_handle h, const char* fn, const MxfSvgp& d) {
+    if (!h) return -1;
+    if (d.S <= 0 || d.B <= 0 || d.M <= 0 || d.Q <= 0 || d.P <= 0) MXF_FAIL(h, -2, "%s: bad shape", fn);
+    if (!d.X || !d.Y || !d.Z || !d.noise || !d.mu || !d.W || !d.sdiag || !d.ls || !d.var || !d.logL) MXF_FAIL(h, -2, "%s: null argument", fn);
+    if (d.kind > MXF_K_MATERN52) MXF_FAIL(h, -2, "%s: stationary kernels only", fn);
+    return svgp_run(h, fn, d);
 }
 
 extern "C" int mxf_svgp_logpdf(mxf_handle h, int kind, int dtype, int S, int64_t B, int64_t M, int Q, int P,
@@ -1974,9 +1866,11 @@ extern "C" int mxf_svgp_logpdf(mxf_handle h, int kind, int dtype, int S, int64_t
                                void* logL, int* info, int want_grad,
                                void* dX, void* dY, void* dZ, void* dnoise, void* dmu, void* dW, void* dSdiag,
                                void* dls, void* dvar, void* stream) {
-    return svgp_dispatch(h, "mxf_svgp_logpdf", kind, dtype, S, B, M, Q, P, X, strideS_X, Y, strideS_Y, Z, noise_var, 1, 1, qU_mean, qU_cov_W,
-                         qU_cov_diag, lengthscale, ard, variance, jitter, scaling, gscale, logL, info, want_grad, dX, dY, dZ, dnoise, dmu, dW,
-                         dSdiag, dls, dvar, stream);
+    return svgp_checked(h, "mxf_svgp_logpdf",
+                        {.kind = kind, .dtype = dtype, .S = S, .B = B, .M = M, .Q = Q, .P = P, .X = X, .sX = strideS_X, .Y = Y, .sY = strideS_Y, .Z = Z,
+                         .noise = noise_var, .mu = qU_mean, .W = qU_cov_W, .sdiag = qU_cov_diag, .ls = lengthscale, .ard = ard, .var = variance,
+                         .jitter = jitter, .scaling = scaling, .gscale = gscale, .logL = logL, .info = info, .want_grad = want_grad, .dX = dX, .dY = dY,
+                         .dZ = dZ, .dnoise = dnoise, .dmu = dmu, .dW = dW, .dSdiag = dSdiag, .dls = dls, .dvar = dvar, .stream = stream});
 }
 
 // Sampled hyper-parameters / inducing inputs / q(u) (runtime_variable.py:96-118: every operand may carry its own sample axis; the
@@ -1996,17 +1890,21 @@ extern "C" int mxf_svgp_logpdf_sampled(mxf_handle h, int kind, int dtype, int S,
     if (S <= 0) MXF_FAIL(h, -2, "mxf_svgp_logpdf_sampled: bad shape");
     if (dtype != MXF_F32 && dtype != MXF_F64) MXF_FAIL(h, -2, "mxf_svgp_logpdf_sampled: bad dtype %d", dtype);
     const int64_t e = (int64_t)mxf_esize(dtype), lsn = ard ? Q : 1;
-    auto at = [&](const void* p, int64_t off) -> const void* { return p ? (const void*)((const char*)p + off * e) : nullptr; };
-    auto atw = [&](void* p, int64_t off) -> void* { return p ? (void*)((char*)p + off * e) : nullptr; };
-    for (int s = 0; s < S; ++s) {
-        const int rc = svgp_dispatch(h, "mxf_svgp_logpdf_sampled", kind, dtype, 1, B, M, Q, P, at(X, s * strideS_X), 0, at(Y, s * strideS_Y), 0,
-                                     at(Z, s * strideS_Z), at(noise_var, s * strideS_noise), 1, 1, at(qU_mean, s * strideS_mu),
-                                     at(qU_cov_W, s * strideS_W), at(qU_cov_diag, s * strideS_sd), at(lengthscale, s * strideS_ls), ard,
-                                     at(variance, s * strideS_var), jitter, scaling, gscale, atw(logL, s), info ? info + s : nullptr, want_grad,
-                                     atw(dX, (int64_t)s * B * Q), atw(dY, (int64_t)s * B * P), atw(dZ, (int64_t)s * M * Q), atw(dnoise, s),
-                                     atw(dmu, (int64_t)s * M * P), atw(dW, (int64_t)s * M * M), atw(dSdiag, (int64_t)s * M), atw(dls, (int64_t)s * lsn),
-                                     atw(dvar, s), stream);
-        if (rc) return rc;
+    // one sample per call (S = 1, sample strides 0): the whole call's descriptor, then per sample a copy with its operands moved to slice s
+    const MxfSvgp all = {.kind = kind, .dtype = dtype, .B = B, .M = M, .Q = Q, .P = P, .X = X, .Y = Y, .Z = Z, .noise = noise_var, .mu = qU_mean, .W = qU_cov_W,
+                         .sdiag = qU_cov_diag, .ls = lengthscale, .ard = ard, .var = variance, .jitter = jitter, .scaling = scaling, .gscale = gscale,
+                         .logL = logL, .info = info, .want_grad = want_grad, .dX = dX, .dY = dY, .dZ = dZ, .dnoise = dnoise, .dmu = dmu, .dW = dW,
+                         .dSdiag = dSdiag, .dls = dls, .dvar = dvar, .stream = stream};
+    auto in = [&](const void*& p, int64_t off) { if (p) p = (const char*)p + off * e; };
+    auto out = [&](void*& p, int64_t off) { if (p) p = (char*)p + off * e; };
+    for (int64_t s = 0; s < S; ++s) {
+        MxfSvgp d = all;
+        in(d.X, s * strideS_X); in(d.Y, s * strideS_Y); in(d.Z, s * strideS_Z); in(d.noise, s * strideS_noise); in(d.mu, s * strideS_mu);
+        in(d.W, s * strideS_W); in(d.sdiag, s * strideS_sd); in(d.ls, s * strideS_ls); in(d.var, s * strideS_var);
+        out(d.logL, s); if (info) d.info = info + s;
+        out(d.dX, s * B * Q); out(d.dY, s * B * P); out(d.dZ, s * M * Q); out(d.dnoise, s); out(d.dmu, s * M * P); out(d.dW, s * M * M);
+        out(d.dSdiag, s * M); out(d.dls, s * lsn); out(d.dvar, s);
+        if (const int rc = svgp_checked(h, "mxf_svgp_logpdf_sampled", d)) return rc;
     }
     return 0;
 }
@@ -2019,9 +1917,11 @@ extern "C" int mxf_svgp_logpdf_het(mxf_handle h, int kind, int dtype, int S, int
                                    void* logL, int* info, int want_grad,
                                    void* dX, void* dY, void* dZ, void* dnoise, void* dmu, void* dW, void* dSdiag,
                                    void* dls, void* dvar, void* stream) {
-    return svgp_dispatch(h, "mxf_svgp_logpdf_het", kind, dtype, S, B, M, Q, P, X, strideS_X, Y, strideS_Y, Z, noise_var, noise_rows, noise_cols,
-                         qU_mean, qU_cov_W, qU_cov_diag, lengthscale, ard, variance, jitter, scaling, gscale, logL, info, want_grad, dX, dY, dZ,
-                         dnoise, dmu, dW, dSdiag, dls, dvar, stream);
+    return svgp_checked(h, "mxf_svgp_logpdf_het",
+                        {.kind = kind, .dtype = dtype, .S = S, .B = B, .M = M, .Q = Q, .P = P, .X = X, .sX = strideS_X, .Y = Y, .sY = strideS_Y, .Z = Z,
+                         .noise = noise_var, .nrows = noise_rows, .ncols = noise_cols, .mu = qU_mean, .W = qU_cov_W, .sdiag = qU_cov_diag, .ls = lengthscale, .ard = ard, .var = variance,
+                         .jitter = jitter, .scaling = scaling, .gscale = gscale, .logL = logL, .info = info, .want_grad = want_grad, .dX = dX, .dY = dY,
+                         .dZ = dZ, .dnoise = dnoise, .dmu = dmu, .dW = dW, .dSdiag = dSdiag, .dls = dls, .dvar = dvar, .stream = stream});
 }
 
 extern "C" int mxf_svgp_logpdf_mat(mxf_handle h, int dtype, int S, int64_t B, int64_t M, int P, const void* Kuu, const void* Kuf, const void* Kdiag,
@@ -2032,16 +1932,12 @@ extern "C" int mxf_svgp_logpdf_mat(mxf_handle h, int dtype, int S, int64_t B, in
     if (!h) return -1;
     if (S <= 0 || B <= 0 || M <= 0 || P <= 0) MXF_FAIL(h, -2, "mxf_svgp_logpdf_mat: bad shape");
     if (S > 1 && strideS_Y != B * P) MXF_FAIL(h, -2, "mxf_svgp_logpdf_mat: S > 1 needs contiguous Y samples (S, B, P)");
-    const int64_t sYv = S > 1 ? strideS_Y : 0;
     if (!Kuu || !Kuf || !Kdiag || !Y || !noise_var || !qU_mean || !qU_cov_W || !qU_cov_diag || !logL) MXF_FAIL(h, -2, "mxf_svgp_logpdf_mat: null argument");
-    return by_dtype(h, "mxf_svgp_logpdf_mat", dtype, [&](auto t) {
-        typedef decltype(t) T;
-        SvgpCall<T> c{{}, h, MXF_K_RBF, dtype, S, B, M, 1, P, (const T*)Kuf /* unused X */, 0, (const T*)Y, sYv, nullptr, (const T*)noise_var,
-                      noise_rows, noise_cols, (const T*)qU_mean, (const T*)qU_cov_W, (const T*)qU_cov_diag, nullptr, 0, nullptr, jitter, scaling,
-                      gscale, (T*)logL, info, want_grad, nullptr, (T*)dY, nullptr, (T*)dnoise, (T*)dmu, (T*)dW, (T*)dSdiag, nullptr, nullptr,
-                      (hipStream_t)stream, {(const T*)Kuu, (const T*)Kuf, (const T*)Kdiag, (T*)dKuu, (T*)dKuf, (T*)dKdiag}};
-        return svgp_logpdf_typed(c);
-    });
+    return svgp_run(h, "mxf_svgp_logpdf_mat",
+                    {.dtype = dtype, .S = S, .B = B, .M = M, .P = P, .Y = Y, .sY = S > 1 ? strideS_Y : 0, .noise = noise_var, .nrows = noise_rows,
+                     .ncols = noise_cols, .mu = qU_mean, .W = qU_cov_W, .sdiag = qU_cov_diag, .jitter = jitter, .scaling = scaling, .gscale = gscale,
+                     .logL = logL, .info = info, .want_grad = want_grad, .dY = dY, .dnoise = dnoise, .dmu = dmu, .dW = dW, .dSdiag = dSdiag,
+                     .stream = stream, .Kuu = Kuu, .Kuf = Kuf, .Kdiag = Kdiag, .dKuu = dKuu, .dKuf = dKuf, .dKdiag = dKdiag});
 }
 
 extern "C" int mxf_sgp_logpdf(mxf_handle h, int kind, int dtype, int64_t B, int64_t M, int Q, int P, const void* X, const void* Y,

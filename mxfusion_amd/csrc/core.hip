@@ -93,8 +93,7 @@ extern "C" int mxf_svgp_timing_read(mxf_handle h, double* ms_out) {
 }
 
 extern "C" int mxf_svgp_whitened_ok(int dtype, int S, int64_t B, int64_t M, int Q, int P, int64_t strideS_X) {
-    const int64_t SB = (strideS_X == 0 ? 1 : (int64_t)S) * B;
-    return (dtype == MXF_F32 && S > 0 && B > 0 && (M % 128) == 0 && M >= 128 && (SB % 256) == 0 && Q <= 16 && P <= 8 && !(S > 1 && strideS_X == 0)) ? 1 : 0;
+    return ((dtype == MXF_F32 || dtype == MXF_F64) && svgp_whitened_ok(mxf_esize(dtype), S, B, M, Q, P, strideS_X)) ? 1 : 0;
 }
 
 extern "C" int mxf_svgp_last_cond(mxf_handle h, double* cond1_out) {

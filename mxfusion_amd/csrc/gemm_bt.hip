@@ -341,7 +341,7 @@ __global__ __launch_bounds__(256) void bt_wsplit_kernel(int64_t K, int64_t Kp, c
 
 }  // namespace
 
-bool mxf_gemm_bt_ok(int64_t M, int64_t N, int64_t K) { return M > 0 && N > 0 && K >= 48 && (M % 256) == 0 && (N % 256) == 0 && (K % 16) == 0; }
+bool mxf_gemm_bt_ok(int64_t M, int64_t N, int64_t K) { return gemm_bt_shape_ok(M, N, K); }
 
 // C (M x N) = alpha * ad0[0] / scale(maxbits) * A (M x K) * Bt (K x N) from f16x2 planes: A planes as in gemm_split.hip ((m, k): ((k / 16) * M
 // + m) * 16 + k % 16), Bt = the planes of the (btR >= K rows, k' = N) operand ((n / 16) * btR + k) * 16 + n % 16.  out.blocked: C in 16-column

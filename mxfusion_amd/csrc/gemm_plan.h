@@ -22,6 +22,11 @@ constexpr int DBK = 16;                                 // LDS-DMA kernel: k til
 constexpr int SBM_ = 64, SBK_ = 16;                     // small-tile float64 kernel: block tile (square) and k tile
 }  // namespace mxf_gemm_tiles
 
+// The split GEMMs (gemm_split.hip, gemm_bt.hip): elements of ONE plane of an (R x K) operand, and the shapes the K-major product takes
+// (whole 256 x 256 output tiles, k in steps of 16 and at least three of them)
+inline size_t split_plane_elems(int64_t R, int64_t K) { return (size_t)((K + 15) / 16) * (size_t)R * 16; }
+inline bool gemm_bt_shape_ok(int64_t M, int64_t N, int64_t K) { return M > 0 && N > 0 && K >= 48 && (M % 256) == 0 && (N % 256) == 0 && (K % 16) == 0; }
+
 enum { MXF_GEMM_SMALL_F64 = 0, MXF_GEMM_DMA_F64 = 1, MXF_GEMM_GENERIC = 2 };
 struct GemmPlan {
     const char* refusal = nullptr; int rc = 0;     // why the launcher cannot take this shape, and its error code (nothing below is valid then)

@@ -775,7 +775,7 @@ __global__ void split_scale_kernel(float* C, int64_t M, int64_t N, int64_t ldc, 
 
 }  // namespace
 
-size_t mxf_split_plane_elems(int64_t R, int64_t K) { return (size_t)((K + 15) / 16) * (size_t)R * 16; }
+size_t mxf_split_plane_elems(int64_t R, int64_t K) { return split_plane_elems(R, K); }
 
 int mxf_maxabs_internal(mxf_ctx* h, int64_t R, int64_t K, const float* x, int64_t ld, unsigned* out, hipStream_t st, bool zero) {
     if (zero) MXF_HIP(h, hipMemsetAsync(out, 0, sizeof(unsigned), st));

@@ -671,7 +671,7 @@ extern "C" int mxf_gram(mxf_handle h, int kind, int dtype, int S, int64_t N, int
 
 // Gram matrix cov(xmin[r], xmaj[k]) (r < R, k < Kn) as split planes in the f16x2 format (float32 inputs, stationary kernels); see
 // gram_planes_lean_kernel.  planes: 2 * pstride elements, pstride = mxf_split_plane_elems(R, Kn).
-size_t mxf_gram_planes_scratch_bytes(int64_t R, int64_t Kn, int Q) { return gram_planes_plan(R, Kn, Q, false, false, 0, 1).bytes; }
+size_t mxf_gram_planes_scratch_bytes(int64_t R, int64_t Kn, int Q) { return gram_planes_scratch_bytes(R, Kn, Q); }
 
 int mxf_gram_planes_internal(mxf_ctx* h, hipStream_t st, const MxfGramPlanes& d) {
     if (d.R <= 0 || d.Kn <= 0) return 0;

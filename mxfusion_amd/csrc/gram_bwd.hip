@@ -20,7 +20,7 @@
 namespace {
 
 constexpr int TRB = MXF_BWD_TRB;
-constexpr int PMAX_ALL = 8;
+constexpr int PMAX_ALL = MXF_BWD_PMAX_ALL;
 
 template <typename T>
 struct GramBwdArgs {
@@ -437,7 +437,7 @@ int mxf_gram_bwd_internal(mxf_ctx* h, hipStream_t st, const MxfGramBwd& d) {
 // may T be handed over in 16-column blocks?  The matrix-pipe pass (RBF) requires it; the difference-form pass (Matern kinds, P > 1, Q > 8) reads
 // either layout for Q <= 16 -- so that those calls keep the wide blocked-output T product (11.3 instead of 13.4 ms at the bench shape)
 bool mxf_svgp_bwd_reads_blocked(int kind, int dtype, int64_t SB, int64_t B, int Q, int P, const void* Text) {
-    return mxf_svgp_bwd_is_mfma(kind, dtype, SB, B, Q, P, Text) || (dtype == MXF_F32 && Q <= 16 && P <= PMAX_ALL && SB % 16 == 0);
+    return mxf_svgp_bwd_is_mfma(kind, dtype, SB, B, Q, P, Text) || svgp_bwd_diff_reads_blocked(dtype == MXF_F32, SB, Q, P);
 }
 
 int mxf_svgp_bwd_fused_internal(mxf_ctx* h, hipStream_t st, const MxfSvgpBwd& d) {

@@ -35,6 +35,15 @@ inline GramBwdPlan gram_bwd_plan(int64_t N, int64_t N2, int S, int QT, int PT, s
     return p;
 }
 
+// ---- which pass the SVGP-fused reverse mode takes: the shape halves of mxf_svgp_bwd_is_mfma / mxf_svgp_bwd_reads_blocked (the other half is
+// the 16-byte alignment of T, which the SVGP composite's scratch always has) -----------------------------------------------------------------
+constexpr int MXF_BWD_PMAX_ALL = 8;      // output columns of the difference-form fused pass's widest kernel
+inline bool svgp_bwd_mfma_shape(bool rbf, bool f32, int64_t SB, int64_t B, int Q, int P) {
+    return rbf && f32 && P == 1 && Q <= 8 && SB % 4 == 0 && SB >= 16 && B % 16 == 0;
+}
+// the difference-form pass reads T in 16-column blocks as well as row-major for these shapes (the matrix-pipe pass reads blocks only)
+inline bool svgp_bwd_diff_reads_blocked(bool f32, int64_t SB, int Q, int P) { return f32 && Q <= 16 && P <= MXF_BWD_PMAX_ALL && SB % 16 == 0; }
+
 // ---- matrix-pipe pass (svgp_bwd_mfma_kernel): a block owns ct groups of 64 columns and a band of MXF_MF_RB rows ------------------------
 #ifndef MXF_MF_MT
 #define MXF_MF_MT 8

@@ -114,3 +114,5 @@ static inline GramPlanesPlan gram_planes_plan(int64_t R, int64_t Kn, int Q, bool
     p.PT = fused ? (Pw == 1 ? 1 : 8) : 0;
     return p;
 }
+// the caller-owned scratch of one planes pass: the same function of (R, Kn, Q) whatever else is asked
+static inline size_t gram_planes_scratch_bytes(int64_t R, int64_t Kn, int Q) { return gram_planes_plan(R, Kn, Q, false, false, 0, 1).bytes; }

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include "gemm_plan.h"      // MXF_TRI_*
+#include "svgp_plan.h"
 
 void mxf_comm_release(mxf_ctx* h);      // comm.hip: destroys the handle's RCCL communicator, if any
 
@@ -145,3 +146,25 @@ int mxf_gram_planes_internal(mxf_ctx* h, hipStream_t st, const MxfGramPlanes& d)
 int mxf_upart_reduce_internal(mxf_ctx* h, int64_t N, int nparts, const float* Upart, const float* scale, float sc2, float* U, hipStream_t st);
 int mxf_planes_transpose_internal(mxf_ctx* h, int64_t R, int64_t K, const unsigned short* in, int64_t pin, unsigned short* out, int64_t pout,
                                   const float* a, const float* scale, float sc2, float* U, hipStream_t st);
+
+// One SVGP call (composite.hip), the same kind of descriptor: each entry point names what it passes; mxf_svgp_logpdf, _het and _mat of
+// include/mxf_gp.h document the operands.
+struct MxfSvgp {
+    int kind = MXF_K_RBF, dtype = 0, S = 1; int64_t B = 0, M = 0; int Q = 1, P = 0;
+    const void* X = nullptr; int64_t sX = 0; const void* Y = nullptr; int64_t sY = 0; const void* Z = nullptr;
+    const void* noise = nullptr; int64_t nrows = 1; int ncols = 1;
+    const void* mu = nullptr; const void* W = nullptr; const void* sdiag = nullptr; const void* ls = nullptr; int ard = 0; const void* var = nullptr;
+    double jitter = 0.0, scaling = 1.0, gscale = 1.0;
+    void* logL = nullptr; int* info = nullptr; int want_grad = 0;
+    void* dX = nullptr; void* dY = nullptr; void* dZ = nullptr; void* dnoise = nullptr; void* dmu = nullptr; void* dW = nullptr; void* dSdiag = nullptr;
+    void* dls = nullptr; void* dvar = nullptr;
+    void* stream = nullptr;
+    // optional: the caller's own Grams in place of X, Z and the covariance parameters, and their gradients
+    const void* Kuu = nullptr; const void* Kuf = nullptr; const void* Kdiag = nullptr; void* dKuu = nullptr; void* dKuf = nullptr; void* dKdiag = nullptr;
+};
+// the probe build's Psi2 knobs, read once
+inline const SvgpKnobs& mxf_svgp_knobs() {
+    static const SvgpKnobs k = {MXF_KNOB("MXF_SVGP_PSI2_KA", -1), (int)MXF_KNOB("MXF_SVGP_PSI2_RA", 148), MXF_KNOB_SET("MXF_SVGP_PSI2_RA"),
+                                (int)MXF_KNOB("MXF_SVGP_PSI2_RB", 16), MXF_KNOB_SET("MXF_SVGP_PSI2_RB")};
+    return k;
+}

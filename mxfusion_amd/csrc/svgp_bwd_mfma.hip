@@ -561,7 +561,7 @@ __global__ __launch_bounds__(256) void bwd_prescale_kernel(const float* __restri
 // usual initialisation -- its dX / dZ came out 10-20 % off for Matern12 and 1e-3 off for Matern32 / 52 at Q = 3 ... 8, against 1e-6 ... 5e-5 from the
 // difference-form pass (tests/probes/bwd_form_accuracy.py).
 bool mxf_svgp_bwd_is_mfma(int kind, int dtype, int64_t SB, int64_t B, int Q, int P, const void* Text) {
-    return kind == MXF_K_RBF && dtype == MXF_F32 && P == 1 && Q <= 8 && SB % 4 == 0 && SB >= 16 && B % 16 == 0 && ((uintptr_t)Text % 16) == 0;
+    return svgp_bwd_mfma_shape(kind == MXF_K_RBF, dtype == MXF_F32, SB, B, Q, P) && ((uintptr_t)Text % 16) == 0;
 }
 
 int mxf_svgp_bwd_mfma_internal(mxf_ctx* h, hipStream_t st, const MxfSvgpBwd& d) {
