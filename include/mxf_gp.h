@@ -472,7 +472,11 @@ int mxf_lik_moments(mxf_handle h, int kind, int dtype, int S, int64_t n, int P, 
  * symmetric.
  * mxf_psi_rbf_bwd: the cotangents G1 (S, M, N) and G2 (S, M, M), either may be null; G2 need not be symmetric (G2 + G2^T is what counts).
  * The gradients are ACCUMULATED into dense buffers shaped like their operands with a shared sample axis at extent 1 (then summed over the
- * samples): dmu, ds (S|1, N, Q), dZ (S|1, M, Q), dls (S|1, Q or 1), dvar (S|1, 1); any may be null.                                      */
+ * samples): dmu, ds (S|1, N, Q), dZ (S|1, M, Q), dls (S|1, Q or 1), dvar (S|1, 1); any may be null.
+ * mxf_psi_rbf_quad: the per-row contraction R[s,n,j] = sum_{m,m'} A[s,j,m,m'] psi2n[s,n,m,m'] of the terms Psi2 sums over n, for J >= 1
+ * weight matrices A (S|1, J, M, M) that need not be symmetric (A_j + A_j^T is what counts; strideS_A is 0 or J M M).  R (S, N, J) is
+ * WRITTEN.  A thread owns a row; the sum over (m, m') is formed in double for either dtype.  J < 1 or a null A or R is status -2.  It is
+ * the second moment of a sparse-GP prediction at a Gaussian test input (BayesianGPLVMUncertainInputPrediction).  No reverse mode.      */
 #define MXF_PSI_MAX_Q 16
 int mxf_psi_rbf_fwd(mxf_handle h, int dtype, int S, int64_t N, int64_t M, int Q, const void* mu, int64_t strideS_mu,
                     const void* s, int64_t strideS_s, const void* Z, int64_t strideS_Z, const void* lengthscale, int ard, int64_t strideS_ls,
@@ -481,6 +485,9 @@ int mxf_psi_rbf_bwd(mxf_handle h, int dtype, int S, int64_t N, int64_t M, int Q,
                     const void* s, int64_t strideS_s, const void* Z, int64_t strideS_Z, const void* lengthscale, int ard, int64_t strideS_ls,
                     const void* variance, int64_t strideS_var, const void* G1, const void* G2, void* dmu_acc, void* ds_acc, void* dZ_acc,
                     void* dls_acc, void* dvar_acc, void* stream);
+int mxf_psi_rbf_quad(mxf_handle h, int dtype, int S, int64_t N, int64_t M, int Q, const void* mu, int64_t strideS_mu,
+                     const void* s, int64_t strideS_s, const void* Z, int64_t strideS_Z, const void* lengthscale, int ard, int64_t strideS_ls,
+                     const void* variance, int64_t strideS_var, int J, const void* A, int64_t strideS_A, void* R, void* stream);
 
 /* Multivariate normal of order n <= 32 over x (S, B, n), mean (S|1, B|1, n) and A (S|1, B|1, n, n): A is the covariance (form 0) or the
  * precision (form 1).  A larger n is status -3 from every entry point, and no buffer is touched (such matrices take mxf_potrf /

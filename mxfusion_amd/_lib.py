@@ -61,6 +61,7 @@ SIGNATURES = {
     'mxf_lik_moments': [_i, _i, _i, _i64, _i, _vp, _i64, _vp, _i64, _i, _pd, _pd, _vp, _vp, _vp],
     'mxf_psi_rbf_fwd': [_i, _i, _i64, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i, _i64, _vp, _i64, _vp, _vp, _vp],
     'mxf_psi_rbf_bwd': [_i, _i, _i64, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    'mxf_psi_rbf_quad': [_i, _i, _i64, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i, _i64, _vp, _i64, _i, _vp, _i64, _vp, _vp],
     'mxf_mvn_factor': [_i, _i, _i, _i64, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
     'mxf_mvn_logpdf': [_i, _i, _i, _i64, _i, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _i, _i64, _d, _vp, _vp],
     'mxf_mvn_logpdf_bwd': [_i, _i, _i, _i64, _i, _vp, _i64, _vp, _i64, _i64, _vp, _i, _i64, _vp, _d, _vp, _vp, _vp, _vp],

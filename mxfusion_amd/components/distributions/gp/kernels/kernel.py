@@ -229,6 +229,11 @@ class Kernel(object):
                                       '(ARD or not, at most %d of them); got %s%s' % (ops._lib.PSI_MAX_Q, type(self).__name__,
                                       ' with active_dims' if self.active_dims is not None else ''))
 
+    def psi2_quadratic(self, F, X_mean, X_var, Z, A, **kernel_params):
+        """R (S, N, J), R[n, j] = sum_{m,m'} A[j, m, m'] E[k(z_m, x_n) k(x_n, z_m')] under X ~ N(X_mean, diag(X_var)): the terms of Psi2
+        contracted per row with the J matrices A (S|1, J, M, M).  Supported where psi_statistics is (RBF.psi2_quadratic)."""
+        return Kernel.psi_statistics(self, F, X_mean, X_var, Z, **kernel_params)         # raises, naming what is supported
+
 
 class NativeKernel(Kernel):
     @property

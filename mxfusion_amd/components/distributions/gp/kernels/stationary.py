@@ -46,6 +46,17 @@ class RBF(StationaryKernel):
         Psi1, Psi2 = _PsiRBFFn.apply(bool(self.ARD), X_mean, X_var, Z, p['lengthscale'], p['variance'])
         return X_mean.shape[-2] * p['variance'][:, 0], Psi1, Psi2
 
+    def psi2_quadratic(self, F, X_mean, X_var, Z, A, **kernel_params):
+        """R (S, N, J), R[s, n, j] = sum_{m,m'} A[s, j, m, m'] psi2n[s, n, m, m'] (mxf_psi_rbf_quad); A (S|1, J, M, M) need not be symmetric.
+        It has no reverse mode: under autograd, an operand that requires a gradient is an error."""
+        if self.active_dims is not None or X_mean.shape[-1] > ops._lib.PSI_MAX_Q:
+            return super(RBF, self).psi2_quadratic(F, X_mean, X_var, Z, A, **kernel_params)
+        p = self._strip(kernel_params)
+        ops_ = (X_mean, X_var, Z, p['lengthscale'], p['variance'], A)
+        if torch.is_grad_enabled() and any(t.requires_grad for t in ops_):
+            raise NotImplementedError('RBF.psi2_quadratic has no reverse mode: call it under torch.no_grad() or on detached operands')
+        return ops.psi_rbf_quad(*[t.contiguous() for t in ops_[:5]], bool(self.ARD), A.contiguous())
+
 
 class Matern52(StationaryKernel):
     _kind = 'matern52'

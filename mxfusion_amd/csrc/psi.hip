@@ -10,7 +10,8 @@
 //     exponent that depends on (m, m') only, and var^2, multiply the finished sum once.
 //   row-owned (psi2_bwd_rows_kernel, psi1_*_kernel: dmu, ds and the row part of dl): a thread owns one row n, its constants live in
 //     registers, and the pairs (z / 2 padded to QP, and the weight matrix W[m,m'] = (G2 + G2^T) var^2 exp(-D), halved on the diagonal, of
-//     psi2_weight_kernel) arrive as scalar loads.  psi2n is recomputed in both passes and never stored.
+//     psi2_weight_kernel) arrive as scalar loads.  psi2n is recomputed in both passes and never stored.  psi2_quad_rows_kernel is the
+//     forward-only sibling: R[n,j] = sum_{m,m'} A_j[m,m'] psi2n[n,m,m'] with PSI_JB weights per pair in one scalar load, no M_q / U_q sums.
 // Rows (pair-owned) and m (row-owned) are split over grid.y until about 2048 workgroups exist, so a small M or a small N still fills the
 // device.  Every sum that crosses workgroups is a double, for either dtype: a thread sums at most PSI_ROWS rows (or one m's m' <= m) in T,
 // adds that to a double register, and ends with one atomic into a double accumulator -- zeroed handle scratch (Psi2, float32 gradients:
@@ -29,6 +30,7 @@ constexpr int PSI_RB = 128;         // row-owned Psi2 reverse pass: rows (thread
 constexpr int PSI_R1 = 256;         // row-owned Psi1 kernels: rows (threads) per workgroup
 constexpr int PSI_MCH = 32;         // row-owned Psi1 kernels: the m of one chunk
 constexpr int PSI_TARGET = 2048;    // workgroups the splits aim for
+constexpr int PSI_JB = 4;           // row-owned contraction: weight matrices per pass (a pair's PSI_JB weights are one scalar load)
 
 template <typename T>
 struct PsiOps {
@@ -303,6 +305,83 @@ __global__ __launch_bounds__(PSI_RB) void psi2_bwd_rows_kernel(PsiOps<T> o, cons
     sums.store(2, o, live, s, n, 1.0, a, sv, l2, dmuacc, own_mu, dsacc, own_s, dl2acc);
 }
 
+// Wq[s][m][m'][j] = var^2 exp(-D[m,m']) (A_{j0+j}[m,m'] + A_{j0+j}[m',m]) for m' < m, var^2 A_{j0+j}[m,m] on the diagonal; 0 above it and for
+// j0 + j >= J.  A (S or 1, J, M, M), need not be symmetric.
+template <typename T, int QP>
+__global__ __launch_bounds__(256) void psi2_quad_weight_kernel(PsiOps<T> o, const T* __restrict__ zh, const T* __restrict__ A, int64_t ss_A, int J, int j0,
+                                                               T* __restrict__ Wq) {
+    const int64_t MM = o.M * o.M, total = (int64_t)o.S * MM;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t s = i / MM, r = i - s * MM, m = r / o.M, m2 = r - m * o.M;
+        T w[PSI_JB];
+#pragma unroll
+        for (int j = 0; j < PSI_JB; ++j) w[j] = 0;
+        if (m2 <= m) {
+            T l2[QP], D = 0;
+            psi_l2<T, QP>(o, s, l2);
+            const T *pz = zh + (s * o.M + m) * QP, *pz2 = zh + (s * o.M + m2) * QP;
+#pragma unroll
+            for (int q = 0; q < QP; ++q) D += psi2_dist_q<T>((T)2 * pz[q], (T)2 * pz2[q], l2[q]);
+            const T var = o.var[s * o.ss_var], f = var * var * t_exp<T>(-D);
+#pragma unroll
+            for (int j = 0; j < PSI_JB; ++j) {
+                if (j0 + j < J) {
+                    const T* g = A + s * ss_A + (int64_t)(j0 + j) * MM;
+                    w[j] = f * (m == m2 ? g[r] : g[r] + g[m2 * o.M + m]);
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < PSI_JB; ++j) Wq[i * PSI_JB + j] = w[j];
+    }
+}
+
+// R[s][n][j0 + j] = sum_{m, m' <= m} Wq[s][m][m'][j] term(n, m, m'), j < PSI_JB: the term once per pair, into PSI_JB accumulators.  With
+// grid.y = 1 a thread writes its row's results (out); otherwise it adds them to the zeroed doubles acc (S, N, J), narrowed by
+// psi_narrow_kernel after the last pass.
+template <typename T, int QP>
+__global__ __launch_bounds__(PSI_RB) void psi2_quad_rows_kernel(PsiOps<T> o, const T* __restrict__ zh, const T* __restrict__ Wq, int J, int j0,
+                                                                double* __restrict__ acc, T* __restrict__ out) {
+    const int64_t s = blockIdx.z, n = (int64_t)blockIdx.x * PSI_RB + threadIdx.x;
+    const bool live = n < o.N;
+    T l2[QP], mu[QP], sv[QP], a[QP], c;
+    psi_l2<T, QP>(o, s, l2);
+    psi_own_row<T, QP>(o, 2, s, live ? n : o.N - 1, l2, mu, sv, a, c);
+    double R[PSI_JB];
+#pragma unroll
+    for (int j = 0; j < PSI_JB; ++j) R[j] = 0;
+    for (int64_t m = blockIdx.y; m < o.M; m += gridDim.y) {      // interleaved: the triangle's rows are of unequal length
+        const T *pz = zh + (s * o.M + m) * QP, *w = Wq + (s * o.M + m) * o.M * PSI_JB;
+        T r_[PSI_JB], em[QP];       // mu - zbar = (mu - z_m / 2) - z_m' / 2: the first difference once per m
+#pragma unroll
+        for (int j = 0; j < PSI_JB; ++j) r_[j] = 0;
+#pragma unroll
+        for (int q = 0; q < QP; ++q) em[q] = mu[q] - pz[q];
+        for (int64_t m2 = 0; m2 <= m; ++m2) {
+            T ae[QP];
+            const T t = psi2_term<T, QP>(em, a, c, zh + (s * o.M + m2) * QP, ae);
+#pragma unroll
+            for (int j = 0; j < PSI_JB; ++j) r_[j] += w[m2 * PSI_JB + j] * t;
+        }
+#pragma unroll
+        for (int j = 0; j < PSI_JB; ++j) R[j] += (double)r_[j];
+    }
+    if (!live) return;
+    const int64_t at = (s * o.N + n) * J + j0;
+#pragma unroll
+    for (int j = 0; j < PSI_JB; ++j) {
+        if (j0 + j < J) {
+            if (acc) atomic_add(acc + at + j, R[j]);
+            else out[at + j] = (T)R[j];
+        }
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void psi_narrow_kernel(int64_t total, const double* __restrict__ acc, T* __restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) out[i] = (T)acc[i];
+}
+
 // Psi1's reverse mode, row-owned, one chunk of PSI_MCH values of m per workgroup: cotangent G1 (S, M, N).  dZ[m] = var sum_n g term a d needs a sum over the rows: one wavefront sum and one
 // atomic per (m, q) and wavefront -- N M Q / 64 of them, nothing next to the N M^2 terms of Psi2.
 template <typename T, int QP>
@@ -369,6 +448,7 @@ struct PsiArgs {
     const void *mu, *s, *Z, *ls, *var; int64_t ss_mu, ss_s, ss_Z, ss_ls, ss_var;
     void *Psi1, *Psi2;                            // forward
     const void *G1, *G2; void *dmu, *ds, *dZ, *dls, *dvar;      // reverse
+    int J; const void* A; int64_t ss_A; void* R;  // contraction
 };
 
 // the scratch of one call: pieces of one allocation, every one aligned to 256 bytes
@@ -457,7 +537,36 @@ int psi_bwd(mxf_handle h, const PsiArgs& a, hipStream_t st) {
     return 0;
 }
 
-int run(mxf_handle h, const char* name, bool fwd, const PsiArgs& a, void* stream) {
+// R (S, N, J) = sum_{m,m'} A_j[m,m'] psi2n[n,m,m'], PSI_JB values of j per pass over the terms; the weights of one pass are reused by the next
+// (stream order).  m is split over grid.y as in the reverse pass.
+template <typename T, int QP>
+int psi_quad(mxf_handle h, const PsiArgs& a, hipStream_t st) {
+    const PsiOps<T> o = {a.S, a.N, a.M, a.Q, a.ard, (const T*)a.mu, a.ss_mu, (const T*)a.s, a.ss_s, (const T*)a.Z, a.ss_Z, (const T*)a.ls, a.ss_ls, (const T*)a.var, a.ss_var};
+    const int64_t SM = (int64_t)a.S * a.M, bx = cdiv(a.N, PSI_RB), total = (int64_t)a.S * a.N * a.J;
+    const int mch = (int)clampi(cdiv(PSI_TARGET, bx * a.S), 1, clampi(a.M, 1, 65535));
+    PsiScratch sc;
+    const size_t at_z = sc.take((size_t)SM * QP * sizeof(T)), at_zh = sc.take((size_t)SM * QP * sizeof(T));
+    const size_t at_wq = sc.take((size_t)SM * a.M * PSI_JB * sizeof(T));
+    const size_t at_acc = sc.take(mch > 1 ? (size_t)total * sizeof(double) : 0);
+    char* ws = (char*)mxf_ws(h, sc.bytes);
+    if (!ws) MXF_FAIL(h, -4, "mxf_psi_rbf_quad: out of memory for %zu bytes of scratch", sc.bytes);
+    T *zf = (T*)(ws + at_z), *zh = (T*)(ws + at_zh), *Wq = (T*)(ws + at_wq);
+    double* acc = mch > 1 ? (double*)(ws + at_acc) : nullptr;
+    if (acc) MXF_HIP(h, hipMemsetAsync(acc, 0, (size_t)total * sizeof(double), st));
+    hipLaunchKernelGGL((psi_prep_kernel<T, QP>), dim3(grid_for((int64_t)a.S * (a.N + a.M))), dim3(256), 0, st, o, (T*)nullptr, zf, zh);
+    for (int j0 = 0; j0 < a.J; j0 += PSI_JB) {
+        hipLaunchKernelGGL((psi2_quad_weight_kernel<T, QP>), dim3(grid_for(SM * a.M)), dim3(256), 0, st, o, zh, (const T*)a.A, a.ss_A, a.J, j0, Wq);
+        hipLaunchKernelGGL((psi2_quad_rows_kernel<T, QP>), dim3((unsigned)bx, (unsigned)mch, (unsigned)a.S), dim3(PSI_RB), 0, st, o, zh, Wq, a.J, j0, acc,
+                           (T*)a.R);
+    }
+    if (acc) hipLaunchKernelGGL((psi_narrow_kernel<T>), dim3(grid_for(total)), dim3(256), 0, st, total, acc, (T*)a.R);
+    MXF_LAUNCH_CHECK(h);
+    return 0;
+}
+
+enum PsiCall { PSI_FWD, PSI_BWD, PSI_QUAD };
+
+int run(mxf_handle h, const char* name, PsiCall call, const PsiArgs& a, void* stream) {
     if (!h) return -1;
     if (a.dtype != MXF_F32 && a.dtype != MXF_F64) MXF_FAIL(h, -2, "%s: bad dtype %d", name, a.dtype);
     if (a.S < 1 || a.S > 65535 || a.N < 1 || a.M < 1 || a.Q < 1) MXF_FAIL(h, -2, "%s: 1 <= S <= 65535 samples, N, M, Q >= 1", name);
@@ -468,14 +577,17 @@ int run(mxf_handle h, const char* name, bool fwd, const PsiArgs& a, void* stream
     if ((a.ss_mu != 0 && a.ss_mu != a.N * a.Q) || (a.ss_s != 0 && a.ss_s != a.N * a.Q) || (a.ss_Z != 0 && a.ss_Z != a.M * a.Q) ||
         (a.ss_ls != 0 && a.ss_ls != nl) || (a.ss_var != 0 && a.ss_var != 1))
         MXF_FAIL(h, -2, "%s: a sample stride must be 0 or the elements of one sample (mu, s: N Q; Z: M Q; lengthscale: Q or 1; variance: 1)", name);
+    if (call == PSI_QUAD) {
+        if (a.J < 1 || !a.A || !a.R) MXF_FAIL(h, -2, "%s: J >= 1 weight matrices, A and R not null", name);
+        if (a.ss_A != 0 && a.ss_A != (int64_t)a.J * a.M * a.M) MXF_FAIL(h, -2, "%s: the sample stride of A must be 0 or J M M", name);
+    }
     const hipStream_t st = (hipStream_t)stream;
     const int qp = a.Q <= 4 ? 4 : (a.Q <= 8 ? 8 : 16);
-#define MXF_PSI_GO(T)                                                                        \
-    (qp == 4 ? (fwd ? psi_fwd<T, 4>(h, a, st) : psi_bwd<T, 4>(h, a, st))                     \
-             : qp == 8 ? (fwd ? psi_fwd<T, 8>(h, a, st) : psi_bwd<T, 8>(h, a, st))           \
-                       : (fwd ? psi_fwd<T, 16>(h, a, st) : psi_bwd<T, 16>(h, a, st)))
+#define MXF_PSI_QP(T, QP) (call == PSI_FWD ? psi_fwd<T, QP>(h, a, st) : call == PSI_BWD ? psi_bwd<T, QP>(h, a, st) : psi_quad<T, QP>(h, a, st))
+#define MXF_PSI_GO(T) (qp == 4 ? MXF_PSI_QP(T, 4) : qp == 8 ? MXF_PSI_QP(T, 8) : MXF_PSI_QP(T, 16))
     return a.dtype == MXF_F32 ? MXF_PSI_GO(float) : MXF_PSI_GO(double);
 #undef MXF_PSI_GO
+#undef MXF_PSI_QP
 }
 
 }  // namespace
@@ -486,7 +598,7 @@ extern "C" int mxf_psi_rbf_fwd(mxf_handle h, int dtype, int S, int64_t N, int64_
     PsiArgs a = {dtype, S, N, M, Q, ard, mu, s, Z, lengthscale, variance, strideS_mu, strideS_s, strideS_Z, strideS_ls, strideS_var};
     a.Psi1 = Psi1;
     a.Psi2 = Psi2;
-    return run(h, "mxf_psi_rbf_fwd", true, a, stream);
+    return run(h, "mxf_psi_rbf_fwd", PSI_FWD, a, stream);
 }
 
 extern "C" int mxf_psi_rbf_bwd(mxf_handle h, int dtype, int S, int64_t N, int64_t M, int Q, const void* mu, int64_t strideS_mu, const void* s,
@@ -496,5 +608,13 @@ extern "C" int mxf_psi_rbf_bwd(mxf_handle h, int dtype, int S, int64_t N, int64_
     PsiArgs a = {dtype, S, N, M, Q, ard, mu, s, Z, lengthscale, variance, strideS_mu, strideS_s, strideS_Z, strideS_ls, strideS_var};
     a.G1 = G1; a.G2 = G2;
     a.dmu = dmu_acc; a.ds = ds_acc; a.dZ = dZ_acc; a.dls = dls_acc; a.dvar = dvar_acc;
-    return run(h, "mxf_psi_rbf_bwd", false, a, stream);
+    return run(h, "mxf_psi_rbf_bwd", PSI_BWD, a, stream);
+}
+
+extern "C" int mxf_psi_rbf_quad(mxf_handle h, int dtype, int S, int64_t N, int64_t M, int Q, const void* mu, int64_t strideS_mu, const void* s,
+                                int64_t strideS_s, const void* Z, int64_t strideS_Z, const void* lengthscale, int ard, int64_t strideS_ls,
+                                const void* variance, int64_t strideS_var, int J, const void* A, int64_t strideS_A, void* R, void* stream) {
+    PsiArgs a = {dtype, S, N, M, Q, ard, mu, s, Z, lengthscale, variance, strideS_mu, strideS_s, strideS_Z, strideS_ls, strideS_var};
+    a.J = J; a.A = A; a.ss_A = strideS_A; a.R = R;
+    return run(h, "mxf_psi_rbf_quad", PSI_QUAD, a, stream);
 }

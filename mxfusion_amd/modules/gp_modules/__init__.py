@@ -3,4 +3,4 @@ from .svgp_regression import SVGPRegression  # noqa: F401
 from .sparsegp_regression import SparseGPRegression  # noqa: F401
 from .likelihoods import BernoulliLogit, BernoulliProbit, PoissonExp  # noqa: F401
 from .svgp_likelihood import SVGPLikelihood  # noqa: F401
-from .bayesian_gplvm import BayesianGPLVM  # noqa: F401
+from .bayesian_gplvm import BayesianGPLVM, BayesianGPLVMUncertainInputPrediction  # noqa: F401

@@ -11,6 +11,7 @@ replaced by their expectations under q(X), the psi statistics (closed form for t
 
 one deterministic evaluation with exact gradients.  The posterior over the inducing outputs has the form of the sparse GP's, so
 prediction at deterministic test inputs is SparseGPRegressionMeanVariancePrediction unchanged: the module graph exposes X_mean as graph.X.
+Prediction at uncertain test inputs is BayesianGPLVMUncertainInputPrediction (gp.gplvm_predict_uncertain, attached by the user).
 
   BayesianGPLVMLogPdf.compute -> mxf_psi_rbf_fwd / mxf_psi_rbf_bwd for the statistics in the model's dtype, kern.K + the differentiable
                                  mxf_potrf / mxf_trsm / mxf_gemm bridges (gp/_linalg.py) for the M x M chain, in float64
@@ -26,6 +27,7 @@ from ...common.exceptions import InferenceError, ModelSpecificationError
 from ...components.variables.variable import Variable
 from ...components.variables.var_trans import PositiveTransformation
 from ...components.distributions.gp import _linalg as lin
+from ...inference.inference_alg import SamplingAlgorithm
 from ...inference.variational import VariationalInference
 from ..module import Module, ModuleGraph
 from .sparsegp_regression import SparseGPRegressionMeanVariancePrediction
@@ -86,6 +88,56 @@ class BayesianGPLVMLogPdf(VariationalInference):
             self.set_parameter(variables, self.graphs[1].L, nf(L[0].detach()))
             self.set_parameter(variables, self.graphs[1].LA, nf(LA[0].detach()))
         return logL.float() if narrow else logL
+
+
+class BayesianGPLVMUncertainInputPrediction(SamplingAlgorithm):
+    """The exact first two moments of the prediction at uncertain test inputs x*_n ~ N(X_mean[n], diag(X_var[n])), X_var >= 0 (the one step
+    of moment-matched multi-step prediction).  With the persisted L, LA, wv and C = L^-T (I - LA^-T LA^-1) L^-1:
+
+      mean[n, p] = sum_m Psi1*[m, n] wv[m, p]                        (+ the mean function)
+      var[n, p]  = variance + sum_{m,m'} A_p[m,m'] psi2n*[n,m,m'] - (sum_m Psi1*[m, n] wv[m, p])^2,    A_p = wv_p wv_p^T - C
+
+    (+ noise_var unless noise_free).  The variance differs per output column, because the spread of the mean under q(x*) does: both moments
+    are (S, N*, P).  Only per-point variances; no reverse mode in the test inputs.
+
+      compute -> mxf_psi_rbf_fwd (Psi1*) and mxf_psi_rbf_quad (the contraction, N* x P numbers from N* M^2 / 2 terms that are never stored) in
+                 the model's dtype; C, A and the final cancellation in float64 through the mxf_trsm / mxf_gemm bridges
+    """
+
+    def __init__(self, model, posterior, observed, target_variables=None, noise_free=True):
+        super(BayesianGPLVMUncertainInputPrediction, self).__init__(model=model, observed=observed, extra_graphs=[posterior],
+                                                                    target_variables=target_variables)
+        self.noise_free = noise_free
+
+    def compute(self, F, variables):
+        g, post = self.model, self.graphs[1]
+        mu, s, Z, noise_var = (variables[v] for v in (g.X, g.X_var, g.inducing_inputs, g.noise_var))
+        L, LA, wv = (variables[v].double() for v in (post.L, post.LA, post.wv))
+        kern = g.kernel
+        kern_params = kern.fetch_parameters(variables)
+        ops._require_gpu(mu)
+        with torch.no_grad():
+            p = kern._strip(kern_params)
+            stat = [t.contiguous() for t in (mu, s, Z, p['lengthscale'], p['variance'])]
+            Psi1, _ = ops.psi_rbf(*stat, bool(kern.ARD), want_psi2=False)                     # (S, M, N*), in the model's dtype
+            M = Z.shape[-2]
+            eye = torch.eye(M, dtype=torch.float64, device=mu.device).unsqueeze(0)
+            Linv = lin.trsm(L, eye.expand(L.shape[0], M, M))
+            LAinvLinv = lin.trsm(LA, Linv)
+            C = lin.gemm(Linv, Linv, transA=True) - lin.gemm(LAinvLinv, LAinvLinv, transA=True)
+            wvt = wv.transpose(-1, -2)                                                         # (S|1, P, M)
+            A = wvt.unsqueeze(-1) * wvt.unsqueeze(-2) - C.unsqueeze(1)                         # (S|1, P, M, M)
+            R = kern.psi2_quadratic(F, mu, s, Z, A.to(mu.dtype), **kern_params).double()       # (S, N*, P)
+            m0 = lin.gemm(Psi1.double(), wv, transA=True)                                      # (S, N*, P)
+            var = p['variance'].double().unsqueeze(-1) + R - m0 * m0
+            if not self.noise_free:
+                var = var + noise_var.double().unsqueeze(-1)
+            mean = m0 + variables[g.mean].double() if g.F.factor.has_mean else m0
+            mean, var = mean.to(mu.dtype), var.to(mu.dtype)
+        outcomes = {g.Y.uuid: (mean, var)}
+        if self.target_variables:
+            return tuple(outcomes[v] for v in self.target_variables)
+        return outcomes
 
 
 class BayesianGPLVM(Module):
@@ -156,6 +208,9 @@ class BayesianGPLVM(Module):
         self.attach_prediction_algorithms(targets=self.output_names, conditionals=self.input_names,
                                           algorithm=SparseGPRegressionMeanVariancePrediction(self._module_graph, self._extra_graphs[0], observed),
                                           alg_name='gplvm_predict')
+        # not registered: the default prediction stays gplvm_predict.  A user re-attaches it under that name to predict at uncertain inputs.
+        object.__setattr__(self, 'gplvm_predict_uncertain',
+                           BayesianGPLVMUncertainInputPrediction(self._module_graph, self._extra_graphs[0], observed))
 
     def prepare_executor(self, rv_scaling=None, global_weight=None):
         if rv_scaling is not None and any(v.uuid in rv_scaling for _, v in self.outputs):

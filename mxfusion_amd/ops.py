@@ -652,6 +652,20 @@ def psi_rbf_bwd_(mu, s, Z, lengthscale, variance, ard, G1, G2, dmu_acc=None, ds_
               _p(dvar_acc), _stream())
 
 
+def psi_rbf_quad(mu, s, Z, lengthscale, variance, ard, A):
+    """R (S, N, J), R[s, n, j] = sum_{m,m'} A[s, j, m, m'] psi2n[s, n, m, m']: the terms Psi2 sums over n, contracted per row with J weight
+    matrices A (S|1, J, M, M) that need not be symmetric (mxf_psi_rbf_quad).  No reverse mode."""
+    S, N, M, Q, big, ls, var = _psi_operands('psi statistics', mu, s, Z, lengthscale, variance, ard, A)
+    if A.dim() != 4 or A.shape[1] < 1 or tuple(A.shape[2:]) != (M, M):
+        raise ValueError('psi statistics: A is (S|1, J, %d, %d) with J >= 1; got %s' % (M, M, tuple(A.shape)))
+    if S > 1 and A.shape[0] not in (1, S):
+        raise ValueError('psi statistics: the sample axes must be 1 or %d' % S)
+    S, J = max(S, int(A.shape[0])), int(A.shape[1])
+    R = torch.empty((S, N, J), dtype=mu.dtype, device=mu.device)
+    _lib.call('mxf_psi_rbf_quad', _h(mu), _dt(mu), S, N, M, Q, *big, *ls, *var, J, _p(A), 0 if A.shape[0] == 1 else A.stride(0), _p(R), _stream())
+    return R
+
+
 MVN_MAX_ORDER = 32      # the order up to which the mxf_mvn_* entry points run (MVN_MAX of mvn.hip)
 
 
