@@ -456,6 +456,36 @@ int mxf_lik_expect_elem(mxf_handle h, int kind, int dtype, int S, int64_t n, int
 int mxf_lik_moments(mxf_handle h, int kind, int dtype, int S, int64_t n, int P, const void* m, int64_t strideS_m,
                     const void* v, int64_t strideS_v, int nq, const double* nodes, const double* weights, void* e1, void* e2, void* stream);
 
+/* Robust-max, the multi-class likelihood of the sparse variational GP (Hernandez-Lobato et al. 2011): C latent functions per row, a label
+ * y in {0 .. C-1}, p(y | f) = 1 - eps where f_y is the largest of the row and eps / (C - 1) otherwise.  No reference counterpart.  Under
+ * independent marginals f_c ~ N(m[c], v), one v per row,
+ *   p = P(f_y is the largest) ~ sum_k w_k / sqrt(pi) prod_{c != y} Phi((m[y] - m[c]) / sqrt(v_eff) + sqrt(2) x_k),   v_eff = max(v, 1e-12)
+ *   E[log p(y | f)] = L0 + p (L1 - L0),   L1 = log(1 - eps),   L0 = log(eps / (C - 1))
+ * with nodes and weights as in mxf_lik_expect (host arrays, nq <= MXF_LIK_MAX_NODES, carried in the kernel arguments: nothing is allocated
+ * or copied and the calls capture into a hipGraph).  y (S|1, n, 1) of the call's dtype, m (S|1, n, C) and v (S|1, n) are dense; strideS_*
+ * is the sample stride in elements (n, n C, n), or 0 for an operand shared by the S samples.  A v below the floor 1e-12, a negative one
+ * included, counts as the floor.  The label is read as an integer -- truncated toward zero and clamped to [0, C - 1] -- so no label value
+ * can index outside the row: -1 reads as 0, C as C - 1, 2.5 as 2.  2 <= C <= MXF_ROBUSTMAX_MAX_C: any other C is status -3 and no
+ * buffer is touched.  Every intermediate is finite in float32 for |m[y] - m[c]| <= 1e3 (mxfusion_amd/csrc/likelihood.h has the argument).
+ *
+ * mxf_robustmax_expect: out[s] += scale * sum_i E[log p(y_i | f_i)], out (S) ACCUMULATED INTO and required; in the same pass the reverse
+ * mode, accumulated with w = scale, or scale * cot[s] given the per-sample weights cot (S, device, dtype of the call): the exact derivatives
+ * of the quadrature sum (not Price's theorem: the integrand couples the C values of a row).  With P_k the product at node k and
+ * lambda = phi / Phi:
+ *   dm[s,i,c] += -w (L1 - L0) / sqrt(v_eff) sum_k w_k P_k lambda(z_kc)   (c != y),      dm[s,i,y] += minus the sum of those over c != y
+ *   dv[s,i]   += -w (L1 - L0) / (2 v_eff^(3/2)) sum_k w_k P_k sum_{c != y} lambda(z_kc) (m[y] - m[c])      (nothing where v < 1e-12)
+ * A node whose P_k underflows to 0 contributes exactly 0.  dm (S, n, C) and dv (S, n) always carry the sample axis: the caller of a
+ * shared m or v sums them over s.  dm and dv may each be null.  eps is in (0, 1): anything else is status -2.
+ * mxf_robustmax_probs: probs[s,i,c] = P(f_c is the largest), (S, n, C), WRITTEN.  Forward only.  The values are NOT renormalised: their sum
+ * over c differs from 1 by the error of the rule (at nq = 20 with v = 25 in the data 7e-5 for C = 10 and 1.6e-3 for C = 32; 2e-9 for
+ * C = 2 and v <= 4).                                                                                                                    */
+#define MXF_ROBUSTMAX_MAX_C 32
+int mxf_robustmax_expect(mxf_handle h, int dtype, int S, int64_t n, int C, const void* y, int64_t strideS_y, const void* m,
+                         int64_t strideS_m, const void* v, int64_t strideS_v, int nq, const double* nodes, const double* weights,
+                         double eps, const void* cot, double scale, void* out_acc, void* dm_acc, void* dv_acc, void* stream);
+int mxf_robustmax_probs(mxf_handle h, int dtype, int S, int64_t n, int C, const void* m, int64_t strideS_m, const void* v,
+                        int64_t strideS_v, int nq, const double* nodes, const double* weights, void* probs, void* stream);
+
 /* RBF psi statistics: the expected kernel under a Gaussian input x_n ~ N(mu_n, diag(s_n)), the closed form that replaces Kuf and
  * Kuf Kuf^T in the collapsed sparse-GP bound when the inputs are uncertain (Titsias & Lawrence 2010, "Bayesian Gaussian Process Latent
  * Variable Model").  No reference counterpart: the reference averages its bound over draws of x.  With l2_q = lengthscale_q^2:

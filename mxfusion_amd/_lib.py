@@ -14,6 +14,7 @@ D_GAMMA, D_GAMMA_MV, D_BETA, D_LAPLACE, D_UNIFORM, D_BERNOULLI, D_NORMAL_PREC = 
 TR_SOFTPLUS, TR_LOGISTIC = range(2)
 LIK_BERNOULLI_LOGIT, LIK_BERNOULLI_PROBIT, LIK_POISSON_EXP = range(3)
 LIK_MAX_NODES = 64         # MXF_LIK_MAX_NODES: quadrature nodes per call
+ROBUSTMAX_MAX_C = 32       # MXF_ROBUSTMAX_MAX_C: classes of a robust-max row
 PSI_MAX_Q = 16             # MXF_PSI_MAX_Q: input dimensions of the psi statistics
 TR_MAX_SEG = 32            # MXF_TR_MAX_SEG: segments per launch; a longer list takes further launches inside the call
 ACT_IDENTITY, ACT_TANH, ACT_RELU, ACT_SIGMOID = range(4)
@@ -59,6 +60,8 @@ SIGNATURES = {
     'mxf_lik_expect': [_i, _i, _i, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i, _pd, _pd, _vp, _d, _vp, _vp, _vp, _vp],
     'mxf_lik_expect_elem': [_i, _i, _i, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i, _pd, _pd, _d, _vp, _vp],
     'mxf_lik_moments': [_i, _i, _i, _i64, _i, _vp, _i64, _vp, _i64, _i, _pd, _pd, _vp, _vp, _vp],
+    'mxf_robustmax_expect': [_i, _i, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i, _pd, _pd, _d, _vp, _d, _vp, _vp, _vp, _vp],
+    'mxf_robustmax_probs': [_i, _i, _i64, _i, _vp, _i64, _vp, _i64, _i, _pd, _pd, _vp, _vp],
     'mxf_psi_rbf_fwd': [_i, _i, _i64, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i, _i64, _vp, _i64, _vp, _vp, _vp],
     'mxf_psi_rbf_bwd': [_i, _i, _i64, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     'mxf_psi_rbf_quad': [_i, _i, _i64, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i, _i64, _vp, _i64, _i, _vp, _i64, _vp, _vp],

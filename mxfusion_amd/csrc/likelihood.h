@@ -77,6 +77,74 @@ MXF_HD inline void mxf_log_ndtr(T z, T& l, T& d1, T& d2) {
 template <typename T>
 MXF_HD inline T mxf_ndtr(T z) { return (T)0.5 * erfc(-z * (T)0.70710678118654752440); }
 
+// Robust-max, the multi-class likelihood of robustmax.hip: one row of C latent values f_c ~ N(m_c, v) and a label y,
+//   p = P(f_y is the largest) ~ sum_k w_k P_k,   P_k = prod_{c != y} Phi(z_kc),   z_kc = d_c + x_k,   d_c = (m_y - m_c) / sqrt(v_eff)
+// with v_eff = max(v, MXF_ROBUSTMAX_V_FLOOR), x_k the nodes times sqrt 2 and w_k the weights over sqrt pi.  The derivatives are those of the
+// sum itself: with lambda = phi / Phi and G_c = sum_k w_k P_k lambda(z_kc),
+//   dp/dm_c = -G_c / sqrt(v_eff) (c != y),   dp/dm_y = sum_{c != y} G_c / sqrt(v_eff),   dp/dv = -sum_c G_c d_c / (2 v_eff)   (0 below the floor).
+// P_k = exp(sum_c log Phi(z_kc)) from mxf_log_ndtr, never a product of Phi; a node whose P_k underflows to 0 adds nothing to any sum, so
+// 0 * lambda is never formed.  With |m_y - m_c| <= 1e3 every intermediate is finite in float32: at the floor |z| <= 1e9, lambda <= 1e9 + 1 and
+// log Phi >= -5e17 per class, -1.6e19 over 31 classes; P_k > 0 needs sum log Phi > -104, so |z| < 15 wherever a term is added, and
+// G_c d_c / v_eff <= 15 * 1e9 * 1e12.  CP is C padded to a compile-time size so that the row lives in registers; a padded class enters no product.
+#define MXF_ROBUSTMAX_V_FLOOR 1e-12
+
+// one node: P_k of the row d at the node x; lam[c] = lambda(z_kc) of the classes in the product, 0 for y and for the padding
+template <typename T, int CP>
+MXF_HD inline T mxf_robustmax_node(int C, int y, const T* d, T x, T* lam) {
+    T sl = 0;
+#pragma unroll
+    for (int c = 0; c < CP; ++c) {
+        lam[c] = 0;
+        if (c < C && c != y) {
+            T l, d1, d2;
+            mxf_log_ndtr<T>(d[c] + x, l, d1, d2);
+            sl += l;
+            lam[c] = d1;
+        }
+    }
+    return exp(sl);
+}
+
+// one row: returns p; with GRAD, dpm[c] = dp/dm_c (CP entries, 0 in the padding) and dpv = dp/dv.  q holds x[], w[] and nq (scaled as above).
+template <typename T, int CP, bool GRAD, typename Q>
+MXF_HD inline T mxf_robustmax_row(int C, int y, const T* m, T v, const Q& q, T* dpm, T& dpv) {
+    const bool floored = !(v >= (T)MXF_ROBUSTMAX_V_FLOOR);
+    const T ve = floored ? (T)MXF_ROBUSTMAX_V_FLOOR : v, rs = (T)1 / sqrt(ve);
+    T my = 0, d[CP], G[CP];
+#pragma unroll
+    for (int c = 0; c < CP; ++c) my = c == y ? m[c] : my;
+#pragma unroll
+    for (int c = 0; c < CP; ++c) {
+        d[c] = c < C ? (my - m[c]) * rs : (T)0;
+        G[c] = 0;
+    }
+    T p = 0;
+    for (int k = 0; k < q.nq; ++k) {
+        T lam[CP];
+        const T P = mxf_robustmax_node<T, CP>(C, y, d, q.x[k], lam);
+        if (P > (T)0) {
+            const T wP = q.w[k] * P;
+            p += wP;
+            if (GRAD) {
+#pragma unroll
+                for (int c = 0; c < CP; ++c) G[c] += wP * lam[c];
+            }
+        }
+    }
+    if (GRAD) {
+        T sy = 0, sv = 0;
+#pragma unroll
+        for (int c = 0; c < CP; ++c) {       // (G is 0 at y and in the padding)
+            sy += G[c];
+            sv += G[c] * d[c];
+        }
+#pragma unroll
+        for (int c = 0; c < CP; ++c) dpm[c] = rs * (c == y ? sy : -G[c]);
+        dpv = floored ? (T)0 : (T)-0.5 * sv / ve;
+    }
+    return p;
+}
+
 // One observation y: set() holds what does not depend on f, eval() gives g = log p(y | f), g' and g''.
 template <typename T, int KIND>
 struct MxfLik {

@@ -1,6 +1,6 @@
 from .gp_regression import GPRegression  # noqa: F401
 from .svgp_regression import SVGPRegression  # noqa: F401
 from .sparsegp_regression import SparseGPRegression  # noqa: F401
-from .likelihoods import BernoulliLogit, BernoulliProbit, PoissonExp  # noqa: F401
+from .likelihoods import BernoulliLogit, BernoulliProbit, PoissonExp, RobustMax  # noqa: F401
 from .svgp_likelihood import SVGPLikelihood  # noqa: F401
 from .bayesian_gplvm import BayesianGPLVM, BayesianGPLVMUncertainInputPrediction  # noqa: F401

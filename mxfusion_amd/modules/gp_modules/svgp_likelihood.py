@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from ... import ops
+from ...common.exceptions import ModelSpecificationError
 from ...components.variables.variable import Variable
 from ...components.variables.var_trans import PositiveTransformation
 from ...components.distributions.gp import _linalg as lin
@@ -130,13 +131,14 @@ class SVGPLikelihoodPrediction(SamplingAlgorithm):
 
 
 class SVGPLikelihood(Module):
-    """y[n, p] ~ likelihood(f_p(x_n)), f_p ~ GP(mean, kernel) through M inducing points with q(u_p) = N(qU_mean[:, p], W W^T + diag(d))."""
+    """y[n, p] ~ likelihood(f_p(x_n)), f_p ~ GP(mean, kernel) through M inducing points with q(u_p) = N(qU_mean[:, p], W W^T + diag(d)).  A
+    likelihood with `num_latent` set (RobustMax) has that many latent functions over one label column: y[n, 0] ~ likelihood(f_1..C(x_n))."""
 
     row_additive = True      # the bound is a sum over data rows plus -KL(q(u) || p(u)): row shards add up
 
     def __init__(self, X, kernel, likelihood, inducing_inputs=None, num_inducing=10, mean=None, rand_gen=None, dtype=None, ctx=None):
         if not isinstance(likelihood, Likelihood):
-            raise TypeError('SVGPLikelihood: likelihood must be a BernoulliLogit, BernoulliProbit or PoissonExp, got %r' % (likelihood,))
+            raise TypeError('SVGPLikelihood: likelihood must be a BernoulliLogit, BernoulliProbit, PoissonExp or RobustMax, got %r' % (likelihood,))
         if not isinstance(X, Variable):
             X = Variable(value=X)
         if inducing_inputs is None:
@@ -172,7 +174,10 @@ class SVGPLikelihood(Module):
         post = ModuleGraph(name='svgp_posterior')
         post.qU_cov_diag = Variable(shape=(M,), transformation=PositiveTransformation())
         post.qU_cov_W = Variable(shape=(M, M))
-        post.qU_mean = Variable(shape=(M, Y.shape[-1]))
+        if self.likelihood.num_latent is not None and Y.shape[-1] != 1:
+            raise ModelSpecificationError('SVGPLikelihood: %s takes its labels in one column, so the last axis of the output shape must be 1; '
+                                          'got %s' % (type(self.likelihood).__name__, tuple(Y.shape)))
+        post.qU_mean = Variable(shape=(M, self.likelihood.num_latent or Y.shape[-1]))
         return graph, [post]
 
     def _attach_default_inference_algorithms(self):

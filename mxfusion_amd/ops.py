@@ -613,6 +613,47 @@ def lik_moments(kind, m, v, num_nodes=20):
     return e1, e2
 
 
+def _robustmax_operands(what, y, m, v, *buffers):
+    """(S, n, C, [(pointer, sample stride) of y, m, v]) of the robust-max likelihood: m (S|1, n, C), v (S|1, n), y (S|1, n, 1) or None"""
+    _same_kind(what, m, v, y, *buffers, contiguous=True)
+    if m.dim() != 3 or v.dim() != 2 or v.shape[1] != m.shape[1] or (y is not None and (y.dim() != 3 or tuple(y.shape[1:]) != (m.shape[1], 1))):
+        raise ValueError('%s: y is (S|1, n, 1), m is (S|1, n, C) and v is (S|1, n); got %s, %s, %s'
+                         % (what, None if y is None else tuple(y.shape), tuple(m.shape), tuple(v.shape)))
+    S = num_samples(y, m, v)
+    if any(t is not None and t.shape[0] not in (1, S) for t in (y, m, v)):
+        raise ValueError('%s: the sample axes must be 1 or %d' % (what, S))
+    n, C = int(m.shape[1]), int(m.shape[2])
+    if not 2 <= C <= _lib.ROBUSTMAX_MAX_C:
+        raise ValueError('%s: 2 <= C <= %d classes, got %d' % (what, _lib.ROBUSTMAX_MAX_C, C))
+    return S, n, C, [a for t in (y, m, v) if t is not None for a in (_p(t), 0 if t.shape[0] == 1 else t.stride(0))]
+
+
+def robustmax_expect_(y, m, v, eps, scale, out_acc, dm_acc=None, dv_acc=None, cot=None, num_nodes=20):
+    """out_acc[s] += scale * sum_i E[log p(y[s,i] | f)] of the robust-max likelihood -- 1 - eps where the label's latent value is the largest of
+    the row's C, eps / (C - 1) otherwise -- under f_c ~ N(m[s,i,c], v[s,i]), by Gauss-Hermite quadrature over the label's value, and the
+    reverse mode in the same pass: dm_acc (S, n, C) and dv_acc (S, n) += w times the exact derivatives of the quadrature sum, w = scale, or
+    scale * cot[s] given per-sample weights cot (S,).  y (S|1, n, 1) holds integer-valued labels (read clamped to [0, C - 1]), m (S|1, n, C),
+    v (S|1, n); the gradient buffers always carry the sample axis (mxf_robustmax_expect)."""
+    S, n, C, strided = _robustmax_operands('robust-max expectation', y, m, v, out_acc, dm_acc, dv_acc, cot)
+    if not 0.0 < float(eps) < 1.0:
+        raise ValueError('robust-max expectation: eps must lie in (0, 1), got %r' % (eps,))
+    if out_acc is None:
+        raise ValueError('robust-max expectation: out_acc is required')
+    _check_buffers('robust-max expectation', (out_acc, (S,)), (cot, (S,)), (dm_acc, (S, n, C)), (dv_acc, (S, n)))
+    _lib.call('mxf_robustmax_expect', _h(m), _dt(m), S, n, C, *strided, *lik_nodes(num_nodes), float(eps), _p(cot), float(scale), _p(out_acc),
+              _p(dm_acc), _p(dv_acc), _stream())
+    return out_acc
+
+
+def robustmax_probs(m, v, num_nodes=20):
+    """probs[s,i,c] = P(f_c is the largest of the row) under f_c ~ N(m[s,i,c], v[s,i]), (S, n, C); not renormalised: the sum over c differs
+    from 1 by the error of the quadrature rule (mxf_robustmax_probs)."""
+    S, n, C, strided = _robustmax_operands('robust-max probabilities', None, m, v)
+    probs = torch.empty((S, n, C), dtype=m.dtype, device=m.device)
+    _lib.call('mxf_robustmax_probs', _h(m), _dt(m), S, n, C, *strided, *lik_nodes(num_nodes), _p(probs), _stream())
+    return probs
+
+
 def _psi_operands(what, mu, s, Z, lengthscale, variance, ard, *buffers):
     """(S, N, M, Q, [pointer, sample stride of mu, s, Z], [lengthscale, ard, stride], [variance, stride]) of the RBF psi statistics:
     mu, s (S|1, N, Q), Z (S|1, M, Q), lengthscale (S|1, Q with ard else 1), variance (S|1, 1)"""
