@@ -519,6 +519,29 @@ int mxf_psi_rbf_quad(mxf_handle h, int dtype, int S, int64_t N, int64_t M, int Q
                      const void* s, int64_t strideS_s, const void* Z, int64_t strideS_Z, const void* lengthscale, int ard, int64_t strideS_ls,
                      const void* variance, int64_t strideS_var, int J, const void* A, int64_t strideS_A, void* R, void* stream);
 
+/* Random Fourier feature expansion of stationary GP prior draws, the prior part of a pathwise posterior sample (Wilson et al. 2020,
+ * "Efficiently sampling functions from Gaussian process posteriors").  No reference counterpart.
+ *   out[s,n,j] = sum_d cos(X[s,n,:] . Omega[s,d,:] + phase[s,d]) W[s,d,j]
+ * X (S|1, N, Q), the frequencies Omega (S|1, D, Q) with the lengthscales already divided in, phase (S|1, D) and the weights W (S|1, D, J) with
+ * the amplitude already multiplied in are dense; strideS_* is the sample stride in elements, or 0 for an operand shared by the S samples.
+ * 1 <= Q <= MXF_RFF_MAX_Q: a larger Q is status -3, and no buffer is touched; a null pointer or a bad shape or stride is status -2.  The
+ * N x D cosines are never stored: a thread owns a row and evaluates each cosine once for all J columns; the sum over d is formed in double
+ * for either dtype (mxfusion_amd/csrc/rff.hip has the decomposition).  float32 uses the hardware cosine and sine on an argument reduced to
+ * one revolution.  Scratch comes from the handle.
+ *
+ * mxf_rff_eval: out (S, N, J) is WRITTEN.
+ * mxf_rff_eval_bwd: the cotangent G (S, N, J) of out; the gradient in the inputs,
+ *   dX[s,n,q] += -sum_d sin(X[s,n,:] . Omega[s,d,:] + phase[s,d]) Omega[s,d,q] sum_j G[s,n,j] W[s,d,j],
+ * is ACCUMULATED into dX_acc, dense and shaped like X, a shared sample axis at extent 1 and summed over.  There is no reverse mode for
+ * Omega, phase or W.                                                                                                                    */
+#define MXF_RFF_MAX_Q 16
+int mxf_rff_eval(mxf_handle h, int dtype, int S, int64_t N, int64_t D, int Q, int J, const void* X, int64_t strideS_X,
+                 const void* Omega, int64_t strideS_Om, const void* phase, int64_t strideS_ph, const void* W, int64_t strideS_W, void* out,
+                 void* stream);
+int mxf_rff_eval_bwd(mxf_handle h, int dtype, int S, int64_t N, int64_t D, int Q, int J, const void* X, int64_t strideS_X,
+                     const void* Omega, int64_t strideS_Om, const void* phase, int64_t strideS_ph, const void* W, int64_t strideS_W,
+                     const void* G, void* dX_acc, void* stream);
+
 /* Multivariate normal of order n <= 32 over x (S, B, n), mean (S|1, B|1, n) and A (S|1, B|1, n, n): A is the covariance (form 0) or the
  * precision (form 1).  A larger n is status -3 from every entry point, and no buffer is touched (such matrices take mxf_potrf /
  * mxf_trsm).  Replaces MultivariateNormal.log_pdf_impl (components/distributions/normal.py:157-178: linalg.potrf, linalg.trsm,

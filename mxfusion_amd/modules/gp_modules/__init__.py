@@ -4,3 +4,5 @@ from .sparsegp_regression import SparseGPRegression  # noqa: F401
 from .likelihoods import BernoulliLogit, BernoulliProbit, PoissonExp, RobustMax  # noqa: F401
 from .svgp_likelihood import SVGPLikelihood  # noqa: F401
 from .bayesian_gplvm import BayesianGPLVM, BayesianGPLVMUncertainInputPrediction  # noqa: F401
+from .pathwise import (GPRegressionPathwiseSampling, SVGPRegressionPathwiseSampling, SparseGPRegressionPathwiseSampling,  # noqa: F401
+                       PathwiseSamples)

@@ -707,6 +707,63 @@ def psi_rbf_quad(mu, s, Z, lengthscale, variance, ard, A):
     return R
 
 
+def _rff_operands(what, X, Omega, phase, W, *buffers):
+    """(S, N, D, Q, J, [pointer, sample stride of X, Omega, phase, W]) of the random Fourier features: X (S|1, N, Q), Omega (S|1, D, Q),
+    phase (S|1, D), W (S|1, D, J)"""
+    _same_kind(what, X, Omega, phase, W, *buffers, contiguous=True)
+    if X.dim() != 3 or Omega.dim() != 3 or phase.dim() != 2 or W.dim() != 3 or Omega.shape[2] != X.shape[2] or phase.shape[1] != Omega.shape[1] \
+            or W.shape[1] != Omega.shape[1]:
+        raise ValueError('%s: X is (S|1, N, Q), Omega (S|1, D, Q), phase (S|1, D) and W (S|1, D, J); got %s, %s, %s, %s'
+                         % (what, tuple(X.shape), tuple(Omega.shape), tuple(phase.shape), tuple(W.shape)))
+    N, D, Q, J = int(X.shape[1]), int(Omega.shape[1]), int(X.shape[2]), int(W.shape[2])
+    if min(N, D, Q, J) < 1:
+        raise ValueError('%s: N, D, Q and J must be at least 1; got %d, %d, %d, %d' % (what, N, D, Q, J))
+    ops_ = (X, Omega, phase, W)
+    S = num_samples(*ops_)
+    if any(t.shape[0] not in (1, S) for t in ops_):
+        raise ValueError('%s: the sample axes must be 1 or %d' % (what, S))
+    args = []
+    for t in ops_:
+        args += [_p(t), 0 if t.shape[0] == 1 else t.stride(0)]
+    return S, N, D, Q, J, args
+
+
+def rff_eval(X, Omega, phase, W):
+    """out (S, N, J), out[s, n, j] = sum_d cos(X[s, n] . Omega[s, d] + phase[s, d]) W[s, d, j]: D random Fourier features of a stationary
+    prior draw, each cosine evaluated once for the J columns and none of them stored (mxf_rff_eval)."""
+    S, N, D, Q, J, args = _rff_operands('random features', X, Omega, phase, W)
+    out = torch.empty((S, N, J), dtype=X.dtype, device=X.device)
+    _lib.call('mxf_rff_eval', _h(X), _dt(X), S, N, D, Q, J, *args, _p(out), _stream())
+    return out
+
+
+def rff_eval_bwd_(X, Omega, phase, W, G, dX_acc):
+    """The reverse mode of rff_eval in X: the cotangent G (S, N, J), the gradient ACCUMULATED into dX_acc, shaped like X, a shared sample axis
+    at extent 1 and summed over (mxf_rff_eval_bwd).  Omega, phase and W have no reverse mode."""
+    S, N, D, Q, J, args = _rff_operands('random features', X, Omega, phase, W, G, dX_acc)
+    _check_buffers('random features', (G, (S, N, J)), (dX_acc, X.shape))
+    _lib.call('mxf_rff_eval_bwd', _h(X), _dt(X), S, N, D, Q, J, *args, _p(G), _p(dX_acc), _stream())
+
+
+class RFFEval(torch.autograd.Function):
+    """rff_eval with its reverse mode in X; the basis and the weights are constants of a drawn sample path."""
+
+    @staticmethod
+    def forward(ctx, X, Omega, phase, W):
+        ops_ = [t.contiguous() for t in (X, Omega, phase, W)]
+        ctx.save_for_backward(*ops_)
+        return rff_eval(*ops_)
+
+    @staticmethod
+    def backward(ctx, G):
+        X = ctx.saved_tensors[0]
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        dX = torch.zeros_like(X)
+        rff_eval_bwd_(*ctx.saved_tensors, G.contiguous(), dX)
+        return dX, None, None, None
+
+
 MVN_MAX_ORDER = 32      # the order up to which the mxf_mvn_* entry points run (MVN_MAX of mvn.hip)
 
 
