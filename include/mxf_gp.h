@@ -542,6 +542,33 @@ int mxf_rff_eval_bwd(mxf_handle h, int dtype, int S, int64_t N, int64_t D, int Q
                      const void* Omega, int64_t strideS_Om, const void* phase, int64_t strideS_ph, const void* W, int64_t strideS_W,
                      const void* G, void* dX_acc, void* stream);
 
+/* Matrix-free product of a stationary covariance matrix with a block of J vectors, the primitive of conjugate-gradient exact GP regression
+ * (Wang et al. 2019, "Exact Gaussian processes on a million data points").  No reference counterpart.
+ *   out[s,n,j] = sum_n2 k(X[s,n,:], X2[s,n2,:]) V[s,n2,j]   (+ diag_add[s] V[s,n,j] when X2 is NULL: the square product with X2 = X, N2 = N)
+ * kind is MXF_K_RBF or MXF_K_MATERN12 / 32 / 52, and the covariance of a pair is the function of the operands that mxf_gram evaluates (the
+ * difference form on operands centred on the first row of X2, the same clipping of r in the Matern kinds).  X (S|1, N, Q), X2 (S|1, N2, Q),
+ * lengthscale (S|1, Q with ard else 1), variance and diag_add (S|1, 1; diag_add may be NULL, and is ignored with an X2) and V (S|1, N2, J) are
+ * dense; strideS_* is the sample stride in elements, or 0 for an operand shared by the S samples.  1 <= Q <= MXF_KMV_MAX_Q: a larger Q is
+ * status -3, and no buffer is touched; S <= 65535, N, N2 <= 2^31, J <= 2^16; a null pointer, a bad shape or a bad stride is status -2.
+ * Nothing of size N x N2 is stored: a thread owns a row and evaluates each covariance once for J (up to 16 at a time) columns; the sum over
+ * n2 is formed in double for either dtype (mxfusion_amd/csrc/kmv.hip has the decomposition).  Scratch, (N2 (Q + J) elements and, for few
+ * rows and many columns, S N J doubles), comes from the handle.
+ *
+ * mxf_kmv: out (S, N, J) is WRITTEN.
+ * mxf_kmv_bwd: the gradient of the weighted bilinear form  sum_s sum_j w[j] A[s,:,j]^T K(X[s], X2[s]) V[s,:,j]  in lengthscale and variance,
+ *   ACCUMULATED into dls_acc and dvar_acc, shaped like lengthscale and variance, a shared sample axis at extent 1 and summed over; either may
+ *   be NULL.  A (S|1, N, J); w: J doubles on the HOST, read before the call returns.  The cotangent of a pair, sum_j w[j] A[n,j] V[n2,j], is
+ *   formed in registers.  There is no reverse mode in X or X2, and none is needed for V: the gradient of the product in V is mxf_kmv with X
+ *   and X2 exchanged.                                                                                                                       */
+#define MXF_KMV_MAX_Q 16
+int mxf_kmv(mxf_handle h, int kind, int dtype, int S, int64_t N, int64_t N2, int Q, int J, const void* X, int64_t strideS_X, const void* X2,
+            int64_t strideS_X2, const void* lengthscale, int64_t strideS_ls, int ard, const void* variance, int64_t strideS_var,
+            const void* diag_add, int64_t strideS_da, const void* V, int64_t strideS_V, void* out, void* stream);
+int mxf_kmv_bwd(mxf_handle h, int kind, int dtype, int S, int64_t N, int64_t N2, int Q, int J, const void* X, int64_t strideS_X, const void* X2,
+                int64_t strideS_X2, const void* lengthscale, int64_t strideS_ls, int ard, const void* variance, int64_t strideS_var,
+                const void* A, int64_t strideS_A, const void* V, int64_t strideS_V, const double* w, void* dls_acc, void* dvar_acc,
+                void* stream);
+
 /* Multivariate normal of order n <= 32 over x (S, B, n), mean (S|1, B|1, n) and A (S|1, B|1, n, n): A is the covariance (form 0) or the
  * precision (form 1).  A larger n is status -3 from every entry point, and no buffer is touched (such matrices take mxf_potrf /
  * mxf_trsm).  Replaces MultivariateNormal.log_pdf_impl (components/distributions/normal.py:157-178: linalg.potrf, linalg.trsm,

@@ -234,6 +234,14 @@ class Kernel(object):
         contracted per row with the J matrices A (S|1, J, M, M).  Supported where psi_statistics is (RBF.psi2_quadratic)."""
         return Kernel.psi_statistics(self, F, X_mean, X_var, Z, **kernel_params)         # raises, naming what is supported
 
+    def matvec(self, F, X, V, X2=None, diag_add=None, **kernel_params):
+        """K(X, X2) V (+ diag_add V for the square product) without the covariance matrix.  Supported for a single stationary kernel over
+        all input dimensions (StationaryKernel.matvec)."""
+        from mxfusion_amd.common.exceptions import ModelSpecificationError
+        raise ModelSpecificationError('the matrix-free kernel product is supported for a single stationary kernel (RBF, Matern12, Matern32, '
+                                      'Matern52; ARD or not) over all input dimensions, at most %d of them; got %s%s'
+                                      % (ops._lib.KMV_MAX_Q, type(self).__name__, ' with active_dims' if self.active_dims is not None else ''))
+
 
 class NativeKernel(Kernel):
     @property

@@ -30,6 +30,17 @@ class StationaryKernel(NativeKernel):
     def fused_spec(self):
         return (self._kind, bool(self.ARD)) if self.active_dims is None else None
 
+    def matvec(self, F, X, V, X2=None, diag_add=None, **kernel_params):
+        """K(X, X2) V (S, N, J), plus diag_add V for the square product (X2 None), without the N x N2 matrix (mxf_kmv): X (S|1, N, Q),
+        X2 (S|1, N2, Q), V (S|1, N2, J), diag_add (S|1, 1).  Differentiable in V, lengthscale and variance (mxf_kmv_bwd); there is no reverse
+        mode in X, X2 or diag_add: under autograd, one of them that requires a gradient is an error."""
+        if self.fused_spec() is None or X.shape[-1] > ops._lib.KMV_MAX_Q:
+            return super(StationaryKernel, self).matvec(F, X, V, X2, diag_add, **kernel_params)
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (X, X2, diag_add)):
+            raise NotImplementedError('%s.matvec has no reverse mode in X, X2 or diag_add: detach them' % type(self).__name__)
+        p = self._strip(kernel_params)
+        return ops.KernelMatvec.apply(self._kind, bool(self.ARD), X, X2, p['lengthscale'], p['variance'], V, diag_add)
+
 
 class RBF(StationaryKernel):
     _kind = 'rbf'

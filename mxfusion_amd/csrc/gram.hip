@@ -15,6 +15,7 @@
 #include "common.h"
 #include "internal.h"
 #include "gram_plan.h"
+#include "kmv.h"          // coord_scale, cov_from: shared with the matrix-free product (kmv.hip)
 #include <limits.h>
 #include <stdlib.h>
 #include <type_traits>
@@ -41,26 +42,6 @@ struct GramArgs {
     unsigned ncb;          // column blocks (grid.x = ncb * row blocks, column block fastest)
     T jitter;
 };
-
-// coordinate pre-scale so that the RBF epilogue is a bare exp2:  exp(-r2/2) = 2^-(c^2 r2), c^2 = log2(e)/2
-template <typename T, int KIND> __device__ __forceinline__ T coord_scale() {
-    return KIND == MXF_K_RBF ? (T)0.84932180028801904272 /* sqrt(0.5*log2(e)) */ : (T)1;
-}
-
-// value of the covariance from the reduced quantity (scaled r2, or the dot product for LINEAR)
-template <typename T, int KIND> __device__ __forceinline__ T cov_from(T red, T variance) {
-    if (KIND == MXF_K_RBF) return variance * fast_exp2_neg<T>(red);
-    if (KIND == MXF_K_MATERN12) { T r = t_sqrt<T>(red < (T)1e-14 ? (T)1e-14 : red); return variance * t_exp<T>(-r); }
-    if (KIND == MXF_K_MATERN32) {
-        T r = (T)1.7320508075688772 * t_sqrt<T>(red < (T)1e-14 ? (T)1e-14 : red);
-        return variance * ((T)1 + r) * t_exp<T>(-r);
-    }
-    if (KIND == MXF_K_MATERN52) {   // matern.py:85-87: clipped r in the linear/exp terms, UN-clipped r2 in 5/3 r2
-        T r = (T)2.23606797749979 * t_sqrt<T>(red < (T)1e-14 ? (T)1e-14 : red);
-        return variance * ((T)1 + r + (T)(5.0 / 3.0) * red) * t_exp<T>(-r);
-    }
-    return red;   // LINEAR: the dot product itself
-}
 
 // 2^(t / 64) for float64 from a 64-entry table of 2^(j / 64) (LDS) and a degree-5 polynomial on |g| <= 1/2 (g in 64ths): 11 VALU
 // operations + one ds_read_b64 instead of the 18 of the degree-13 form (truncation (ln2/128)^6 / 6! = 3.5e-17; result within ~1 ulp).

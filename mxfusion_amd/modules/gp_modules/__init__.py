@@ -6,3 +6,5 @@ from .svgp_likelihood import SVGPLikelihood  # noqa: F401
 from .bayesian_gplvm import BayesianGPLVM, BayesianGPLVMUncertainInputPrediction  # noqa: F401
 from .pathwise import (GPRegressionPathwiseSampling, SVGPRegressionPathwiseSampling, SparseGPRegressionPathwiseSampling,  # noqa: F401
                        PathwiseSamples)
+from .iterative_gp_regression import (IterativeGPRegression, IterativeGPRegressionLogPdf,  # noqa: F401
+                                       IterativeGPRegressionMeanVariancePrediction)

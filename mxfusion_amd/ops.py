@@ -764,7 +764,92 @@ class RFFEval(torch.autograd.Function):
         return dX, None, None, None
 
 
-MVN_MAX_ORDER = 32      # the order up to which the mxf_mvn_* entry points run (MVN_MAX of mvn.hip)
+def _kmv_operands(what, kind, X, X2, lengthscale, variance, ard, V, *buffers):
+    """(S, N, N2, Q, J, [kind, dtype, S, N, N2, Q, J, X, X2, lengthscale, ard, variance with their sample strides]) of the matrix-free kernel
+    product: X (S|1, N, Q), X2 (S|1, N2, Q) or None (square), lengthscale (S|1, Q with ard else 1), variance (S|1, 1), V (S|1, N2, J)"""
+    _same_kind(what, X, X2, lengthscale, variance, V, *buffers, contiguous=True)
+    kind = KIND[kind] if isinstance(kind, str) else kind
+    if kind not in (_lib.K_RBF, _lib.K_MATERN12, _lib.K_MATERN32, _lib.K_MATERN52):
+        raise ValueError('%s: stationary kernels only (rbf, matern12, matern32, matern52)' % what)
+    if X.dim() != 3 or (X2 is not None and (X2.dim() != 3 or X2.shape[2] != X.shape[2])) or V.dim() != 3:
+        raise ValueError('%s: X is (S|1, N, Q), X2 (S|1, N2, Q) or None and V (S|1, N2, J); got %s, %s, %s'
+                         % (what, tuple(X.shape), None if X2 is None else tuple(X2.shape), tuple(V.shape)))
+    N, Q, J = int(X.shape[1]), int(X.shape[2]), int(V.shape[2])
+    N2 = N if X2 is None else int(X2.shape[1])
+    if min(N, N2, Q, J) < 1 or V.shape[1] != N2:
+        raise ValueError('%s: N, N2, Q and J must be at least 1 and V must have N2 = %d rows; got V %s' % (what, N2, tuple(V.shape)))
+    if lengthscale.dim() != 2 or lengthscale.shape[1] != (Q if ard else 1) or variance.dim() != 2 or variance.shape[1] != 1:
+        raise ValueError('%s: lengthscale is (S|1, %d) and variance (S|1, 1); got %s, %s'
+                         % (what, Q if ard else 1, tuple(lengthscale.shape), tuple(variance.shape)))
+    ops_ = [t for t in (X, X2, lengthscale, variance, V) if t is not None]
+    S = num_samples(*ops_)
+    if any(t.shape[0] not in (1, S) for t in ops_):
+        raise ValueError('%s: the sample axes must be 1 or %d' % (what, S))
+    st = lambda t: [_p(t), 0 if t is None or t.shape[0] == 1 else t.stride(0)]
+    return S, N, N2, Q, J, [kind, _dt(X), S, N, N2, Q, J] + st(X) + st(X2) + st(lengthscale) + [int(bool(ard))] + st(variance)
+
+
+def kernel_matvec(kind, X, X2, lengthscale, variance, ard, V, diag_add=None):
+    """out (S, N, J) = K(X, X2) V (+ diag_add V for the square product, X2 None) without the N x N2 matrix: each covariance evaluated once for
+    the J columns and none of them stored (mxf_kmv).  The covariance of a pair is the one gram() writes.  diag_add (S|1, 1)."""
+    S, N, N2, Q, J, args = _kmv_operands('kernel product', kind, X, X2, lengthscale, variance, ard, V, diag_add)
+    if diag_add is not None:
+        if X2 is not None:
+            raise ValueError('kernel product: diag_add goes with the square product (X2 None)')
+        if diag_add.dim() != 2 or diag_add.shape[1] != 1 or diag_add.shape[0] not in (1, S):
+            raise ValueError('kernel product: diag_add is (S|1, 1); got %s' % (tuple(diag_add.shape),))
+    out = torch.empty((S, N, J), dtype=X.dtype, device=X.device)
+    _lib.call('mxf_kmv', _h(X), *args, _p(diag_add), 0 if diag_add is None or diag_add.shape[0] == 1 else diag_add.stride(0),
+              _p(V), 0 if V.shape[0] == 1 else V.stride(0), _p(out), _stream())
+    return out
+
+
+def kernel_matvec_bwd_(kind, X, X2, lengthscale, variance, ard, A, V, w=None, dls_acc=None, dvar_acc=None):
+    """The gradient of sum_s sum_j w[j] A[s, :, j]^T K(X[s], X2[s]) V[s, :, j] in lengthscale and variance, ACCUMULATED into buffers shaped like
+    them, a shared sample axis at extent 1 and summed over (mxf_kmv_bwd).  A (S|1, N, J), V (S|1, N2, J), w: J numbers (None: ones).  The
+    N x N2 cotangent sum_j w[j] A[:, j] V[:, j]^T is never stored.  There is no reverse mode in X or X2."""
+    S, N, N2, Q, J, args = _kmv_operands('kernel product', kind, X, X2, lengthscale, variance, ard, V, A, dls_acc, dvar_acc)
+    if A.dim() != 3 or tuple(A.shape[1:]) != (N, J) or A.shape[0] not in (1, S):
+        raise ValueError('kernel product: A is (S|1, %d, %d); got %s' % (N, J, tuple(A.shape)))
+    _check_buffers('kernel product', (dls_acc, lengthscale.shape), (dvar_acc, variance.shape))
+    w = [1.0] * J if w is None else [float(x) for x in w]
+    if len(w) != J:
+        raise ValueError('kernel product: %d weights for J = %d columns' % (len(w), J))
+    _lib.call('mxf_kmv_bwd', _h(X), *args, _p(A), 0 if A.shape[0] == 1 else A.stride(0), _p(V), 0 if V.shape[0] == 1 else V.stride(0),
+              (_lib._c.c_double * J)(*w), _p(dls_acc), _p(dvar_acc), _stream())
+
+
+class KernelMatvec(torch.autograd.Function):
+    """kernel_matvec, differentiable in V (the product with X and X2 exchanged), lengthscale and variance (kernel_matvec_bwd_); X, X2 and
+    diag_add have no reverse mode."""
+
+    @staticmethod
+    def forward(ctx, kind, ard, X, X2, ls, var, V, diag_add):
+        ops_ = [None if t is None else t.contiguous() for t in (X, X2, ls, var, V, diag_add)]
+        ctx.kind, ctx.ard = kind, ard
+        ctx.save_for_backward(*ops_)
+        X, X2, ls, var, V, diag_add = ops_
+        return kernel_matvec(kind, X, X2, ls, var, ard, V, diag_add)
+
+    @staticmethod
+    def backward(ctx, G):
+        X, X2, ls, var, V, diag_add = ctx.saved_tensors
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3] or ctx.needs_input_grad[7]:
+            raise NotImplementedError('the matrix-free kernel product has no reverse mode in X, X2 or diag_add: detach them')
+        G = G.contiguous()
+        dls = torch.zeros_like(ls) if ctx.needs_input_grad[4] else None
+        dvar = torch.zeros_like(var) if ctx.needs_input_grad[5] else None
+        if dls is not None or dvar is not None:
+            kernel_matvec_bwd_(ctx.kind, X, X2, ls, var, ctx.ard, G, V, None, dls, dvar)
+        dV = None
+        if ctx.needs_input_grad[6]:         # K(X, X2)^T G = K(X2, X) G (+ diag_add G)
+            dV = kernel_matvec(ctx.kind, X if X2 is None else X2, None if X2 is None else X, ls, var, ctx.ard, G, diag_add)
+            if V.shape[0] == 1 and dV.shape[0] > 1:
+                dV = dV.sum(0, keepdim=True)
+        return None, None, None, None, dls, dvar, dV, None
+
+
+MVN_MAX_ORDER = 32     # the order up to which the mxf_mvn_* entry points run (MVN_MAX of mvn.hip)
 
 
 def _mvn_rows(x, mean):
