@@ -6,6 +6,8 @@
 #include <string.h>
 #include <string>
 #include <stdlib.h>
+#include <limits.h>
+#include <type_traits>
 #include "../../include/mxf_gp.h"
 
 // Tuning knobs: numbers of the shipped path (grid sizes, periods, block sizes), instruments, and shapes a test forces.  The shipped library
@@ -215,6 +217,17 @@ static inline bool mxf_potrf_aux_init(mxf_ctx* h) { return mxf_async_init(mxf_po
 
 static inline size_t mxf_esize(int dtype) { return dtype == MXF_F64 ? 8 : 4; }
 static inline size_t mxf_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+
+// f(std::integral_constant<int, V>) for the V among VS that equals v; NO_CASE: none does
+constexpr int NO_CASE = INT_MIN;
+template <int... VS, typename F>
+int dispatch(int v, F&& f) {
+    int rc = NO_CASE;
+    (void)((v == VS && ((rc = f(std::integral_constant<int, VS>{})), true)) || ...);
+    return rc;
+}
+// the element type of a dtype tag: dispatch<MXF_F32, MXF_F64>(dtype, [&](auto dt) { using T = mxf_elem_t<decltype(dt)::value>; ... })
+template <int DTYPE> using mxf_elem_t = std::conditional_t<DTYPE == MXF_F64, double, float>;
 
 // ---- device helpers -------------------------------------------------------------------------
 template <typename T> struct Vec16;   // 16-byte vector of T

@@ -16,20 +16,9 @@
 #include "internal.h"
 #include "gram_plan.h"
 #include "kmv.h"          // coord_scale, cov_from: shared with the matrix-free product (kmv.hip)
-#include <limits.h>
 #include <stdlib.h>
-#include <type_traits>
 
 namespace {
-
-// f(std::integral_constant<int, V>) for the V among VS that equals v; NO_CASE: none does
-constexpr int NO_CASE = INT_MIN;
-template <int... VS, typename F>
-int dispatch(int v, F&& f) {
-    int rc = NO_CASE;
-    (void)((v == VS && ((rc = f(std::integral_constant<int, VS>{})), true)) || ...);
-    return rc;
-}
 
 template <typename T>
 struct GramArgs {

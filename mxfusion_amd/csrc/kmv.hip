@@ -16,16 +16,11 @@
 // V, KMV_WG columns per prep launch) and sums g f and g f' ((x_q - z_q) c / l_q)^2 per thread, per wavefront in double, and over the
 // wavefronts in zeroed double scratch; one thread adds the totals to the caller's buffers (the pattern of psi_close_kernel).
 #include "common.h"
+#include "fused_plan.h"      // KMV_*: the tile sizes; kmv_plan
 #include "kmv.h"
+#include "shared_grad.h"   // mxf_narrow_kernel
 
 namespace {
-
-constexpr int KMV_RB = 128;         // rows (threads) per workgroup
-constexpr int KMV_CH = 64;          // values of n2 summed in T between two additions to the double register
-constexpr int KMV_JB = 16;          // columns of V per pair and pass (one scalar load)
-constexpr int KMV_JB_SMALL = 4;     // the same for J <= KMV_JB_SMALL
-constexpr int KMV_TARGET = 1024;    // workgroups the split of n2 aims for
-constexpr int KMV_WG = 64;          // weights of the bilinear form per prep launch (a kernel argument)
 
 template <typename T>
 struct KmvOps {
@@ -92,7 +87,7 @@ __device__ __forceinline__ void kmv_range(int64_t N2, int64_t ch, int64_t& c0, i
 }
 
 // out[s][n][j] = variance sum_n2 f(n, n2) V[n2][j] (+ diag_add V[n][j]).  With grid.y = 1 a thread writes its row's results (out); otherwise
-// it adds them to the zeroed doubles acc (S, N, J), narrowed by kmv_narrow_kernel; the diagonal term is workgroup row 0's.
+// it adds them to the zeroed doubles acc (S, N, J), narrowed by mxf_narrow_kernel; the diagonal term is workgroup row 0's.
 template <typename T, int QP, int JB, int KIND>
 __global__ __launch_bounds__(KMV_RB) void kmv_fwd_kernel(KmvOps<T> o, const T* __restrict__ zs_all, int64_t ss_zs, const T* __restrict__ vb_all,
                                                          int64_t ss_vb, int npass, int64_t ch, double* __restrict__ acc, T* __restrict__ out) {
@@ -143,11 +138,6 @@ __global__ __launch_bounds__(KMV_RB) void kmv_fwd_kernel(KmvOps<T> o, const T* _
             }
         }
     }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void kmv_narrow_kernel(int64_t total, const double* __restrict__ acc, T* __restrict__ out) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) out[i] = (T)acc[i];
 }
 
 // The sums of the reverse mode: dlacc[s][q] += sum_{n,n2} g f' d_q^2 and dvacc[s] += sum_{n,n2} g f, with d_q the scaled difference and
@@ -234,68 +224,40 @@ __global__ void kmv_close_kernel(KmvOps<T> o, const double* __restrict__ dlacc, 
     }
 }
 
-static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-static inline int64_t clampi(int64_t x, int64_t lo, int64_t hi) { return x < lo ? lo : (x > hi ? hi : x); }
-
 struct KmvArgs {
-    int kind, dtype, S; int64_t N, N2; int Q, J;
-    const void *X, *X2, *ls, *var, *da, *V; int64_t ss_X, ss_X2, ss_ls, ss_var, ss_da, ss_V; int ard;
-    void* out;                                                              // forward
-    const void* A; int64_t ss_A; const double* w; void *dls, *dvar;         // reverse
+    int kind = MXF_K_RBF, dtype = MXF_F32, S = 0; int64_t N = 0, N2 = 0; int Q = 0, J = 0;
+    const void *X = nullptr, *X2 = nullptr, *ls = nullptr, *var = nullptr, *da = nullptr, *V = nullptr;
+    int64_t ss_X = 0, ss_X2 = 0, ss_ls = 0, ss_var = 0, ss_da = 0, ss_V = 0; int ard = 0;
+    void* out = nullptr;                                                                                      // forward
+    const void* A = nullptr; int64_t ss_A = 0; const double* w = nullptr; void *dls = nullptr, *dvar = nullptr;      // reverse
 };
 
-struct KmvScratch {
-    size_t bytes = 0;
-    size_t take(size_t b) { const size_t at = bytes; bytes += mxf_align(b); return at; }
-};
-
-// the values of n2 per workgroup row (a multiple of KMV_CH) and the number of such rows: 1 unless the row blocks alone leave the device empty
-static inline void kmv_split(int S, int64_t N, int64_t N2, int64_t* ch, int* rows) {
-    const int64_t want = clampi(cdiv(KMV_TARGET, cdiv(N, KMV_RB) * S), 1, clampi(cdiv(N2, KMV_CH), 1, 65535));
-    *ch = cdiv(cdiv(N2, want), KMV_CH) * KMV_CH;
-    *rows = (int)cdiv(N2, *ch);
-}
-
+// ask the plan (fused_plan.h: kmv_plan), carve, launch
 template <typename T, int QP, int JB, int KIND>
-int kmv_run(mxf_handle h, const char* name, const KmvArgs& a, bool bwd, hipStream_t st) {
-    const bool square = a.X2 == nullptr;
-    const int64_t N2 = square ? a.N : a.N2, ss_Z = square ? a.ss_X : a.ss_X2;
-    const KmvOps<T> o = {a.S, a.N, N2, a.Q, a.J, a.ard, (int)square, (const T*)a.X, a.ss_X, (const T*)(square ? a.X : a.X2), ss_Z,
+int kmv_launch(mxf_handle h, const char* name, const KmvArgs& a, const KmvPlan& p, bool bwd, hipStream_t st) {
+    const KmvOps<T> o = {a.S, a.N, p.N2, a.Q, a.J, a.ard, (int)p.square, (const T*)a.X, a.ss_X, (const T*)(p.square ? a.X : a.X2), p.ss_Z,
                          (const T*)a.ls, a.ss_ls, (const T*)a.var, a.ss_var, (const T*)a.da, a.ss_da, (const T*)a.V, a.ss_V};
-    const int npass = (int)cdiv(a.J, JB);
-    const int64_t S_z = (ss_Z || a.ss_ls) ? a.S : 1, S_V = a.ss_V ? a.S : 1;
-    int64_t ch;
-    int rows;
-    kmv_split(a.S, a.N, N2, &ch, &rows);
-    const int64_t n_out = (int64_t)a.S * a.N * a.J;
-    // zeroed doubles: the forward results under a split of n2; the sums of the reverse mode, (S, QP) and (S)
-    const size_t n_zero = bwd ? (size_t)a.S * (QP + 1) : (rows > 1 ? (size_t)n_out : 0);
-    KmvScratch sc;
-    const size_t at_zs = sc.take((size_t)(S_z * N2) * QP * sizeof(T)), at_vb = sc.take((size_t)(S_V * npass * N2) * JB * sizeof(T));
-    const size_t at_zero = sc.take(n_zero * sizeof(double));
-    char* ws = (char*)mxf_ws(h, sc.bytes);
-    if (!ws) MXF_FAIL(h, -4, "%s: out of memory for %zu bytes of scratch", name, sc.bytes);
-    double* zero = n_zero ? (double*)(ws + at_zero) : nullptr;
-    if (zero) MXF_HIP(h, hipMemsetAsync(zero, 0, n_zero * sizeof(double), st));
-    T *zs = (T*)(ws + at_zs), *vb = (T*)(ws + at_vb);
-    hipLaunchKernelGGL((kmv_prep_z_kernel<T, QP, KIND>), dim3(grid_for(S_z * N2)), dim3(256), 0, st, o, S_z, zs);
-    const int gp = KMV_WG / JB;         // passes per prep launch of the reverse mode: KMV_WG weights
-    for (int pass0 = 0; pass0 < npass; pass0 += bwd ? gp : npass) {
+    char* ws = (char*)mxf_ws(h, p.bytes);
+    if (!ws) MXF_FAIL(h, -4, "%s: out of memory for %zu bytes of scratch", name, p.bytes);
+    double* zero = p.n_zero ? (double*)(ws + p.at_zero) : nullptr;
+    if (zero) MXF_HIP(h, hipMemsetAsync(zero, 0, p.n_zero * sizeof(double), st));
+    T *zs = (T*)(ws + p.at_zs), *vb = (T*)(ws + p.at_vb);
+    hipLaunchKernelGGL((kmv_prep_z_kernel<T, QP, KIND>), dim3(grid_for(p.n_prep_z)), dim3(256), 0, st, o, p.S_z, zs);
+    for (int pass0 = 0; pass0 < p.npass; pass0 += p.gp) {
+        const KmvPrepV pv = kmv_prep_v(p, pass0);
         KmvWeights wt;
         wt.use = bwd;
-        const int np = bwd ? (int)clampi(npass - pass0, 1, gp) : npass;
         for (int k = 0; k < KMV_WG; ++k) wt.w[k] = (bwd && (int64_t)pass0 * JB + k < a.J) ? a.w[(int64_t)pass0 * JB + k] : 0.0;
-        hipLaunchKernelGGL((kmv_prep_v_kernel<T, JB>), dim3(grid_for(S_V * np * N2)), dim3(256), 0, st, o, S_V, npass, pass0, np, wt, vb);
+        hipLaunchKernelGGL((kmv_prep_v_kernel<T, JB>), dim3(grid_for(pv.items)), dim3(256), 0, st, o, p.S_V, p.npass, pass0, pv.np, wt, vb);
     }
-    const int64_t ss_zs = S_z > 1 ? N2 * QP : 0, ss_vb = S_V > 1 ? (int64_t)npass * N2 * JB : 0;
-    const dim3 grid((unsigned)cdiv(a.N, KMV_RB), (unsigned)rows, (unsigned)a.S);
+    const dim3 grid(p.grid[0], p.grid[1], p.grid[2]);
     if (!bwd) {
-        hipLaunchKernelGGL((kmv_fwd_kernel<T, QP, JB, KIND>), grid, dim3(KMV_RB), 0, st, o, (const T*)zs, ss_zs, (const T*)vb, ss_vb, npass, ch, zero,
-                           (T*)a.out);
-        if (zero) hipLaunchKernelGGL((kmv_narrow_kernel<T>), dim3(grid_for(n_out)), dim3(256), 0, st, n_out, (const double*)zero, (T*)a.out);
+        hipLaunchKernelGGL((kmv_fwd_kernel<T, QP, JB, KIND>), grid, dim3(KMV_RB), 0, st, o, (const T*)zs, p.ss_zs, (const T*)vb, p.ss_vb, p.npass, p.ch,
+                           zero, (T*)a.out);
+        if (zero) hipLaunchKernelGGL((mxf_narrow_kernel<T>), dim3(grid_for(p.n_out)), dim3(256), 0, st, p.n_out, (const double*)zero, (T*)a.out);
     } else {
-        double *dlacc = zero, *dvacc = zero + (size_t)a.S * QP;
-        hipLaunchKernelGGL((kmv_bwd_kernel<T, QP, JB, KIND>), grid, dim3(KMV_RB), 0, st, o, (const T*)zs, ss_zs, (const T*)vb, ss_vb, npass, ch,
+        double *dlacc = zero, *dvacc = (double*)(ws + p.at_dv);
+        hipLaunchKernelGGL((kmv_bwd_kernel<T, QP, JB, KIND>), grid, dim3(KMV_RB), 0, st, o, (const T*)zs, p.ss_zs, (const T*)vb, p.ss_vb, p.npass, p.ch,
                            (const T*)a.A, a.ss_A, a.dls ? dlacc : nullptr, a.dvar ? dvacc : nullptr);
         hipLaunchKernelGGL((kmv_close_kernel<T, QP>), dim3(1), dim3(64), 0, st, o, (const double*)dlacc, (const double*)dvacc, (T*)a.dls,
                            (int)(a.ss_ls != 0), (T*)a.dvar, (int)(a.ss_var != 0));
@@ -304,45 +266,27 @@ int kmv_run(mxf_handle h, const char* name, const KmvArgs& a, bool bwd, hipStrea
     return 0;
 }
 
-template <typename T, int QP, int JB>
-int kmv_kind(mxf_handle h, const char* name, const KmvArgs& a, bool bwd, hipStream_t st) {
-    switch (a.kind) {
-        case MXF_K_RBF: return kmv_run<T, QP, JB, MXF_K_RBF>(h, name, a, bwd, st);
-        case MXF_K_MATERN12: return kmv_run<T, QP, JB, MXF_K_MATERN12>(h, name, a, bwd, st);
-        case MXF_K_MATERN32: return kmv_run<T, QP, JB, MXF_K_MATERN32>(h, name, a, bwd, st);
-        default: return kmv_run<T, QP, JB, MXF_K_MATERN52>(h, name, a, bwd, st);
-    }
-}
-
 int run(mxf_handle h, const char* name, const KmvArgs& a, bool bwd, void* stream) {
     if (!h) return -1;
     if (a.dtype != MXF_F32 && a.dtype != MXF_F64) MXF_FAIL(h, -2, "%s: bad dtype %d", name, a.dtype);
     if (a.kind != MXF_K_RBF && a.kind != MXF_K_MATERN12 && a.kind != MXF_K_MATERN32 && a.kind != MXF_K_MATERN52)
         MXF_FAIL(h, -2, "%s: stationary kernels only (kind %d)", name, a.kind);
-    const bool square = a.X2 == nullptr;
-    const int64_t N2 = square ? a.N : a.N2;
-    if (a.S < 1 || a.S > 65535 || a.N < 1 || N2 < 1 || a.Q < 1 || a.J < 1) MXF_FAIL(h, -2, "%s: 1 <= S <= 65535 samples, N, N2, Q, J >= 1", name);
-    if (a.Q > MXF_KMV_MAX_Q) MXF_FAIL(h, -3, "%s: Q = %d above the limit of %d input dimensions", name, a.Q, MXF_KMV_MAX_Q);
-    if (a.N > ((int64_t)1 << 31) || N2 > ((int64_t)1 << 31) || a.J > (1 << 16)) MXF_FAIL(h, -2, "%s: N, N2 <= 2^31, J <= 2^16", name);
-    if (!a.X || !a.ls || !a.var || !a.V) MXF_FAIL(h, -2, "%s: null X, lengthscale, variance or V", name);
-    if (bwd) {
-        if (!a.A || !a.w) MXF_FAIL(h, -2, "%s: null A or w", name);
-        if (!a.dls && !a.dvar) MXF_FAIL(h, -2, "%s: null dls_acc and dvar_acc", name);
-    } else if (!a.out) MXF_FAIL(h, -2, "%s: null out", name);
-    const int64_t nl = a.ard ? a.Q : 1;
-    if ((a.ss_X != 0 && a.ss_X != a.N * a.Q) || (!square && a.ss_X2 != 0 && a.ss_X2 != N2 * a.Q) || (a.ss_ls != 0 && a.ss_ls != nl) ||
-        (a.ss_var != 0 && a.ss_var != 1) || (a.da && a.ss_da != 0 && a.ss_da != 1) || (a.ss_V != 0 && a.ss_V != N2 * a.J) ||
-        (bwd && a.ss_A != 0 && a.ss_A != a.N * a.J))
-        MXF_FAIL(h, -2, "%s: a sample stride must be 0 or the elements of one sample (X: N Q; X2: N2 Q; lengthscale: Q or 1; variance, diag_add: 1; "
-                 "V: N2 J; A: N J)", name);
-    const hipStream_t st = (hipStream_t)stream;
-    const int qp = a.Q <= 4 ? 4 : (a.Q <= 8 ? 8 : 16);
-    const bool small = a.J <= KMV_JB_SMALL;
-#define MXF_KMV_JB(T, QP) (small ? kmv_kind<T, QP, KMV_JB_SMALL>(h, name, a, bwd, st) : kmv_kind<T, QP, KMV_JB>(h, name, a, bwd, st))
-#define MXF_KMV_GO(T) (qp == 4 ? MXF_KMV_JB(T, 4) : qp == 8 ? MXF_KMV_JB(T, 8) : MXF_KMV_JB(T, 16))
-    return a.dtype == MXF_F32 ? MXF_KMV_GO(float) : MXF_KMV_GO(double);
-#undef MXF_KMV_GO
-#undef MXF_KMV_JB
+    const KmvPlan p = kmv_plan({.esize = mxf_esize(a.dtype), .bwd = bwd, .S = a.S, .N = a.N, .N2 = a.N2, .Q = a.Q, .J = a.J, .ard = a.ard,
+                                .ss_X = a.ss_X, .ss_X2 = a.ss_X2, .ss_ls = a.ss_ls, .ss_var = a.ss_var, .ss_da = a.ss_da, .ss_V = a.ss_V, .ss_A = a.ss_A,
+                                .has_X = a.X != nullptr, .has_X2 = a.X2 != nullptr, .has_ls = a.ls != nullptr, .has_var = a.var != nullptr,
+                                .has_da = a.da != nullptr, .has_V = a.V != nullptr, .has_out = a.out != nullptr, .has_A = a.A != nullptr,
+                                .has_w = a.w != nullptr, .has_dls = a.dls != nullptr, .has_dvar = a.dvar != nullptr});
+    if (p.rc) MXF_FAIL(h, p.rc, "%s: %s", name, p.refusal);
+    return dispatch<MXF_F32, MXF_F64>(a.dtype, [&](auto dt) {
+        return dispatch<4, 8, 16>(p.qp, [&](auto qp) {
+            return dispatch<KMV_JB_SMALL, KMV_JB>(p.jb, [&](auto jb) {
+                return dispatch<MXF_K_RBF, MXF_K_MATERN12, MXF_K_MATERN32, MXF_K_MATERN52>(a.kind, [&](auto kind) {
+                    return kmv_launch<mxf_elem_t<decltype(dt)::value>, decltype(qp)::value, decltype(jb)::value, decltype(kind)::value>(
+                        h, name, a, p, bwd, (hipStream_t)stream);
+                });
+            });
+        });
+    });
 }
 
 }  // namespace
@@ -350,9 +294,9 @@ int run(mxf_handle h, const char* name, const KmvArgs& a, bool bwd, void* stream
 extern "C" int mxf_kmv(mxf_handle h, int kind, int dtype, int S, int64_t N, int64_t N2, int Q, int J, const void* X, int64_t strideS_X, const void* X2,
                        int64_t strideS_X2, const void* lengthscale, int64_t strideS_ls, int ard, const void* variance, int64_t strideS_var,
                        const void* diag_add, int64_t strideS_da, const void* V, int64_t strideS_V, void* out, void* stream) {
-    KmvArgs a = {kind, dtype, S, N, N2, Q, J, X, X2, lengthscale, variance, X2 ? nullptr : diag_add, V, strideS_X, strideS_X2, strideS_ls, strideS_var,
-                 strideS_da, strideS_V, ard};
-    a.out = out;
+    const KmvArgs a = {.kind = kind, .dtype = dtype, .S = S, .N = N, .N2 = N2, .Q = Q, .J = J, .X = X, .X2 = X2, .ls = lengthscale, .var = variance,
+                       .da = X2 ? nullptr : diag_add, .V = V, .ss_X = strideS_X, .ss_X2 = strideS_X2, .ss_ls = strideS_ls, .ss_var = strideS_var,
+                       .ss_da = strideS_da, .ss_V = strideS_V, .ard = ard, .out = out};
     return run(h, "mxf_kmv", a, false, stream);
 }
 
@@ -360,12 +304,8 @@ extern "C" int mxf_kmv_bwd(mxf_handle h, int kind, int dtype, int S, int64_t N, 
                            const void* X2, int64_t strideS_X2, const void* lengthscale, int64_t strideS_ls, int ard, const void* variance,
                            int64_t strideS_var, const void* A, int64_t strideS_A, const void* V, int64_t strideS_V, const double* w, void* dls_acc,
                            void* dvar_acc, void* stream) {
-    KmvArgs a = {kind, dtype, S, N, N2, Q, J, X, X2, lengthscale, variance, nullptr, V, strideS_X, strideS_X2, strideS_ls, strideS_var, 0, strideS_V, ard};
-    a.out = nullptr;
-    a.A = A;
-    a.ss_A = strideS_A;
-    a.w = w;
-    a.dls = dls_acc;
-    a.dvar = dvar_acc;
+    const KmvArgs a = {.kind = kind, .dtype = dtype, .S = S, .N = N, .N2 = N2, .Q = Q, .J = J, .X = X, .X2 = X2, .ls = lengthscale, .var = variance,
+                       .V = V, .ss_X = strideS_X, .ss_X2 = strideS_X2, .ss_ls = strideS_ls, .ss_var = strideS_var, .ss_V = strideS_V, .ard = ard,
+                       .A = A, .ss_A = strideS_A, .w = w, .dls = dls_acc, .dvar = dvar_acc};
     return run(h, "mxf_kmv_bwd", a, true, stream);
 }

@@ -27,6 +27,26 @@
 #define MXF_LIK_KIND_PROBIT 1
 #define MXF_LIK_KIND_POISSON 2
 
+#ifndef MXF_LIK_MAX_NODES
+#define MXF_LIK_MAX_NODES 64       // as include/mxf_gp.h
+#endif
+
+// A Gauss-Hermite rule as the quadrature kernels take it, in their arguments: x_k = sqrt(2) node_k and w_k = weight_k / sqrt(pi), rounded to T
+// once, zeros from nq up to MXF_LIK_MAX_NODES
+template <typename T>
+struct MxfQuadNodes { T x[MXF_LIK_MAX_NODES], w[MXF_LIK_MAX_NODES]; int nq; };
+
+template <typename T>
+inline MxfQuadNodes<T> mxf_quad_nodes(int nq, const double* nodes, const double* weights) {
+    MxfQuadNodes<T> q;
+    q.nq = nq;
+    for (int k = 0; k < MXF_LIK_MAX_NODES; ++k) {
+        q.x[k] = k < nq ? (T)(1.41421356237309504880 * nodes[k]) : (T)0;
+        q.w[k] = k < nq ? (T)(0.56418958354775628695 * weights[k]) : (T)0;
+    }
+    return q;
+}
+
 // log sigmoid(z) and its first two derivatives in z
 template <typename T>
 MXF_HD inline void mxf_log_sigmoid(T z, T& l, T& d1, T& d2) {

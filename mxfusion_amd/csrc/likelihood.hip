@@ -9,29 +9,27 @@
 // T once): the index k is uniform over the wavefront, so they are scalar loads from the argument segment and nothing is re-read from a
 // table in global memory; the library allocates and copies nothing.  A thread owns one row of m (its P columns share v and the
 // sqrt), a workgroup takes (sample, chunk) pairs off a one-dimensional grid and closes each with one block sum and ONE atomic into out[s]
-// (the plan of univariate_ps_kernel); the gradients and the un-reduced outputs have one writer per element and need no atomics.
+// (per_sample_plan of fused_plan.h, as univariate_ps_kernel); the gradients and the un-reduced outputs have one writer per element and need no atomics.
 #include "common.h"
+#include "fused_plan.h"      // per_sample_plan
 #include "likelihood.h"
 
 namespace {
 
-template <typename T>
-struct LikNodes { T x[MXF_LIK_MAX_NODES], w[MXF_LIK_MAX_NODES]; int nq; };
-
 struct LikArgs {
-    int S; int64_t n; int P;
-    const void* y; int64_t ss_y;
-    const void* m; int64_t ss_m;
-    const void* v; int64_t ss_v;
-    const void* cot; double scale;
-    void *out, *dm, *dv;       // LIK_REDUCED: out (S), dm (S, n, P), dv (S, n); LIK_ELEM: out (S, n, P); LIK_MOMENTS: out = E[mu], dm = E[mu^2], both (S, n, P)
+    int S = 0; int64_t n = 0; int P = 0;
+    const void* y = nullptr; int64_t ss_y = 0;
+    const void* m = nullptr; int64_t ss_m = 0;
+    const void* v = nullptr; int64_t ss_v = 0;
+    const void* cot = nullptr; double scale = 1.0;
+    void *out = nullptr, *dm = nullptr, *dv = nullptr;       // LIK_REDUCED: out (S), dm (S, n, P), dv (S, n); LIK_ELEM: out (S, n, P); LIK_MOMENTS: out = E[mu], dm = E[mu^2], both (S, n, P)
 };
 enum { LIK_REDUCED = 0, LIK_ELEM = 1, LIK_MOMENTS = 2 };
 
 template <typename T, int KIND, int MODE>
 __global__ __launch_bounds__(256) void lik_kernel(int S, int64_t n, int P, int chunks, const T* __restrict__ y, int64_t ss_y,
                                                   const T* __restrict__ m, int64_t ss_m, const T* __restrict__ v, int64_t ss_v,
-                                                  const LikNodes<T> q, const T* __restrict__ cot, T scale, T* __restrict__ out,
+                                                  const MxfQuadNodes<T> q, const T* __restrict__ cot, T scale, T* __restrict__ out,
                                                   T* __restrict__ dm, T* __restrict__ dv) {
     __shared__ T red[16];
     const int64_t pairs = (int64_t)S * chunks, nP = n * P;
@@ -85,44 +83,12 @@ __global__ __launch_bounds__(256) void lik_kernel(int S, int64_t n, int P, int c
     }
 }
 
-// Grid: up to 512 chunks of rows per sample, fewer where S of them would pass 8192 workgroups, at most 65 536 workgroups that loop over
-// the rest of the pairs (uni_ps_plan of unidist.h: the cap on same-address atomics holds per sample).
-struct LikPlan { int chunks; unsigned grid; };
-static inline LikPlan lik_plan(int S, int64_t n) {
-    int64_t c = (n + 255) / 256;
-    if (c > 512) c = 512;
-    const int64_t fit = 8192 / (int64_t)S;
-    if (c > fit) c = fit;
-    if (c < 1) c = 1;
-    int64_t g = (int64_t)S * c;
-    if (g > 65536) g = 65536;
-    return {(int)c, (unsigned)g};
-}
-
-template <typename T, int KIND>
-void launch_kind(const LikArgs& a, const LikNodes<T>& q, int mode, hipStream_t st) {
-    const LikPlan p = lik_plan(a.S, a.n);
-    const dim3 grid(p.grid), block(256);
-#define MXF_LIK_LAUNCH(MODE)                                                                                                              \
-    hipLaunchKernelGGL((lik_kernel<T, KIND, MODE>), grid, block, 0, st, a.S, a.n, a.P, p.chunks, (const T*)a.y, a.ss_y, (const T*)a.m,   \
-                       a.ss_m, (const T*)a.v, a.ss_v, q, (const T*)a.cot, (T)a.scale, (T*)a.out, (T*)a.dm, (T*)a.dv)
-    if (mode == LIK_ELEM) MXF_LIK_LAUNCH(LIK_ELEM);
-    else if (mode == LIK_MOMENTS) MXF_LIK_LAUNCH(LIK_MOMENTS);
-    else MXF_LIK_LAUNCH(LIK_REDUCED);
-#undef MXF_LIK_LAUNCH
-}
-
-template <typename T>
-void launch(int kind, const LikArgs& a, int nq, const double* nodes, const double* weights, int mode, hipStream_t st) {
-    LikNodes<T> q;
-    q.nq = nq;
-    for (int k = 0; k < MXF_LIK_MAX_NODES; ++k) {
-        q.x[k] = k < nq ? (T)(1.41421356237309504880 * nodes[k]) : (T)0;
-        q.w[k] = k < nq ? (T)(0.56418958354775628695 * weights[k]) : (T)0;
-    }
-    if (kind == MXF_LIK_BERNOULLI_LOGIT) launch_kind<T, MXF_LIK_BERNOULLI_LOGIT>(a, q, mode, st);
-    else if (kind == MXF_LIK_BERNOULLI_PROBIT) launch_kind<T, MXF_LIK_BERNOULLI_PROBIT>(a, q, mode, st);
-    else launch_kind<T, MXF_LIK_POISSON_EXP>(a, q, mode, st);
+template <typename T, int KIND, int MODE>
+int lik_launch(const LikArgs& a, const MxfQuadNodes<T>& q, hipStream_t st) {
+    const PerSamplePlan p = per_sample_plan(a.S, a.n);
+    hipLaunchKernelGGL((lik_kernel<T, KIND, MODE>), dim3(p.grid), dim3(256), 0, st, a.S, a.n, a.P, p.chunks, (const T*)a.y, a.ss_y, (const T*)a.m,
+                       a.ss_m, (const T*)a.v, a.ss_v, q, (const T*)a.cot, (T)a.scale, (T*)a.out, (T*)a.dm, (T*)a.dv);
+    return 0;
 }
 
 // argument checks shared by the entry points, then the launch
@@ -137,8 +103,14 @@ int run(mxf_handle h, const char* name, int kind, int dtype, const LikArgs& a, i
     if (!a.m || !a.v || (mode != LIK_MOMENTS && !a.y)) MXF_FAIL(h, -2, "%s: null y, m or v", name);
     if ((a.ss_y != 0 && a.ss_y != a.n * a.P) || (a.ss_m != 0 && a.ss_m != a.n * a.P) || (a.ss_v != 0 && a.ss_v != a.n))
         MXF_FAIL(h, -2, "%s: a sample stride must be 0 or the elements of one sample (y, m: n P; v: n)", name);
-    if (dtype == MXF_F32) launch<float>(kind, a, nq, nodes, weights, mode, (hipStream_t)stream);
-    else launch<double>(kind, a, nq, nodes, weights, mode, (hipStream_t)stream);
+    dispatch<MXF_F32, MXF_F64>(dtype, [&](auto dt) {
+        using T = mxf_elem_t<decltype(dt)::value>;
+        const MxfQuadNodes<T> q = mxf_quad_nodes<T>(nq, nodes, weights);
+        return dispatch<MXF_LIK_BERNOULLI_LOGIT, MXF_LIK_BERNOULLI_PROBIT, MXF_LIK_POISSON_EXP>(kind, [&](auto k) {
+            return dispatch<LIK_REDUCED, LIK_ELEM, LIK_MOMENTS>(
+                mode, [&](auto md) { return lik_launch<T, decltype(k)::value, decltype(md)::value>(a, q, (hipStream_t)stream); });
+        });
+    });
     MXF_LAUNCH_CHECK(h);
     return 0;
 }
@@ -151,7 +123,8 @@ static_assert(MXF_LIK_BERNOULLI_LOGIT == MXF_LIK_KIND_LOGIT && MXF_LIK_BERNOULLI
 extern "C" int mxf_lik_expect(mxf_handle h, int kind, int dtype, int S, int64_t n, int P, const void* y, int64_t strideS_y, const void* m,
                               int64_t strideS_m, const void* v, int64_t strideS_v, int nq, const double* nodes, const double* weights,
                               const void* cot, double scale, void* out_acc, void* dm_acc, void* dv_acc, void* stream) {
-    const LikArgs a = {S, n, P, y, strideS_y, m, strideS_m, v, strideS_v, cot, scale, out_acc, dm_acc, dv_acc};
+    const LikArgs a = {.S = S, .n = n, .P = P, .y = y, .ss_y = strideS_y, .m = m, .ss_m = strideS_m, .v = v, .ss_v = strideS_v, .cot = cot, .scale = scale,
+                       .out = out_acc, .dm = dm_acc, .dv = dv_acc};
     return run(h, "mxf_lik_expect", kind, dtype, a, nq, nodes, weights, LIK_REDUCED, stream);
 }
 
@@ -159,13 +132,13 @@ extern "C" int mxf_lik_expect_elem(mxf_handle h, int kind, int dtype, int S, int
                                    const void* m, int64_t strideS_m, const void* v, int64_t strideS_v, int nq, const double* nodes,
                                    const double* weights, double scale, void* out, void* stream) {
     if (h && n > 0 && S > 0 && P > 0 && !out) MXF_FAIL(h, -2, "mxf_lik_expect_elem: null out");
-    const LikArgs a = {S, n, P, y, strideS_y, m, strideS_m, v, strideS_v, nullptr, scale, out, nullptr, nullptr};
+    const LikArgs a = {.S = S, .n = n, .P = P, .y = y, .ss_y = strideS_y, .m = m, .ss_m = strideS_m, .v = v, .ss_v = strideS_v, .scale = scale, .out = out};
     return run(h, "mxf_lik_expect_elem", kind, dtype, a, nq, nodes, weights, LIK_ELEM, stream);
 }
 
 extern "C" int mxf_lik_moments(mxf_handle h, int kind, int dtype, int S, int64_t n, int P, const void* m, int64_t strideS_m, const void* v,
                                int64_t strideS_v, int nq, const double* nodes, const double* weights, void* e1, void* e2, void* stream) {
     if (h && n > 0 && S > 0 && P > 0 && (!e1 || !e2)) MXF_FAIL(h, -2, "mxf_lik_moments: null output");
-    const LikArgs a = {S, n, P, nullptr, 0, m, strideS_m, v, strideS_v, nullptr, 1.0, e1, e2, nullptr};
+    const LikArgs a = {.S = S, .n = n, .P = P, .m = m, .ss_m = strideS_m, .v = v, .ss_v = strideS_v, .scale = 1.0, .out = e1, .dm = e2};
     return run(h, "mxf_lik_moments", kind, dtype, a, nq, nodes, weights, LIK_MOMENTS, stream);
 }

@@ -18,19 +18,12 @@
 // folded into the caller's buffer with one rounding) or the caller's float64 buffer itself.  With one chunk an element has one writer.
 // Psi2 is written from its lower triangle to both halves by one kernel: bitwise symmetric.
 #include "common.h"
+#include "fused_plan.h"      // PSI_*: the tile sizes; psi_fwd_plan, psi_bwd_plan, psi_quad_plan
 #include "shared_grad.h"
 #define MXF_PSI_EXP(T, x) t_exp<T>(x)
 #include "psi.h"
 
 namespace {
-
-constexpr int PSI_TILE = 16;        // pair-owned: a workgroup of 256 threads owns PSI_TILE x PSI_TILE pairs
-constexpr int PSI_ROWS = 64;        // pair-owned: rows summed in T between two additions to the double register
-constexpr int PSI_RB = 128;         // row-owned Psi2 reverse pass: rows (threads) per workgroup
-constexpr int PSI_R1 = 256;         // row-owned Psi1 kernels: rows (threads) per workgroup
-constexpr int PSI_MCH = 32;         // row-owned Psi1 kernels: the m of one chunk
-constexpr int PSI_TARGET = 2048;    // workgroups the splits aim for
-constexpr int PSI_JB = 4;           // row-owned contraction: weight matrices per pass (a pair's PSI_JB weights are one scalar load)
 
 template <typename T>
 struct PsiOps {
@@ -338,7 +331,7 @@ __global__ __launch_bounds__(256) void psi2_quad_weight_kernel(PsiOps<T> o, cons
 
 // R[s][n][j0 + j] = sum_{m, m' <= m} Wq[s][m][m'][j] term(n, m, m'), j < PSI_JB: the term once per pair, into PSI_JB accumulators.  With
 // grid.y = 1 a thread writes its row's results (out); otherwise it adds them to the zeroed doubles acc (S, N, J), narrowed by
-// psi_narrow_kernel after the last pass.
+// mxf_narrow_kernel after the last pass.
 template <typename T, int QP>
 __global__ __launch_bounds__(PSI_RB) void psi2_quad_rows_kernel(PsiOps<T> o, const T* __restrict__ zh, const T* __restrict__ Wq, int J, int j0,
                                                                 double* __restrict__ acc, T* __restrict__ out) {
@@ -375,11 +368,6 @@ __global__ __launch_bounds__(PSI_RB) void psi2_quad_rows_kernel(PsiOps<T> o, con
             else out[at + j] = (T)R[j];
         }
     }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void psi_narrow_kernel(int64_t total, const double* __restrict__ acc, T* __restrict__ out) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) out[i] = (T)acc[i];
 }
 
 // Psi1's reverse mode, row-owned, one chunk of PSI_MCH values of m per workgroup: cotangent G1 (S, M, N).  dZ[m] = var sum_n g term a d needs a sum over the rows: one wavefront sum and one
@@ -440,99 +428,69 @@ __global__ void psi_close_kernel(PsiOps<T> o, const double* __restrict__ dl2acc,
     }
 }
 
-static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-static inline int64_t clampi(int64_t x, int64_t lo, int64_t hi) { return x < lo ? lo : (x > hi ? hi : x); }
-
 struct PsiArgs {
-    int dtype, S; int64_t N, M; int Q, ard;
-    const void *mu, *s, *Z, *ls, *var; int64_t ss_mu, ss_s, ss_Z, ss_ls, ss_var;
-    void *Psi1, *Psi2;                            // forward
-    const void *G1, *G2; void *dmu, *ds, *dZ, *dls, *dvar;      // reverse
-    int J; const void* A; int64_t ss_A; void* R;  // contraction
+    int dtype = MXF_F32, S = 0; int64_t N = 0, M = 0; int Q = 0, ard = 0;
+    const void *mu = nullptr, *s = nullptr, *Z = nullptr, *ls = nullptr, *var = nullptr; int64_t ss_mu = 0, ss_s = 0, ss_Z = 0, ss_ls = 0, ss_var = 0;
+    void *Psi1 = nullptr, *Psi2 = nullptr;                                                                          // forward
+    const void *G1 = nullptr, *G2 = nullptr; void *dmu = nullptr, *ds = nullptr, *dZ = nullptr, *dls = nullptr, *dvar = nullptr;      // reverse
+    int J = 0; const void* A = nullptr; int64_t ss_A = 0; void* R = nullptr;                                        // contraction
 };
 
-// the scratch of one call: pieces of one allocation, every one aligned to 256 bytes
-struct PsiScratch {
-    size_t bytes = 0;
-    size_t take(size_t b) { const size_t at = bytes; bytes += mxf_align(b); return at; }
-};
+template <typename T>
+PsiOps<T> psi_ops(const PsiArgs& a) {
+    return {a.S, a.N, a.M, a.Q, a.ard, (const T*)a.mu, a.ss_mu, (const T*)a.s, a.ss_s, (const T*)a.Z, a.ss_Z, (const T*)a.ls, a.ss_ls, (const T*)a.var, a.ss_var};
+}
+inline dim3 psi_dim3(const unsigned* g) { return dim3(g[0], g[1], g[2]); }
 
+// The three launchers: the plan (fused_plan.h) has every size, grid and scratch offset; carve, launch
 template <typename T, int QP>
-int psi_fwd(mxf_handle h, const PsiArgs& a, hipStream_t st) {
-    const PsiOps<T> o = {a.S, a.N, a.M, a.Q, a.ard, (const T*)a.mu, a.ss_mu, (const T*)a.s, a.ss_s, (const T*)a.Z, a.ss_Z, (const T*)a.ls, a.ss_ls, (const T*)a.var, a.ss_var};
-    const int64_t SM = (int64_t)a.S * a.M;
-    PsiScratch sc;
-    const size_t at_z = sc.take((size_t)SM * QP * sizeof(T)), at_zh = sc.take((size_t)SM * QP * sizeof(T));
-    const size_t at_rows = a.Psi2 ? sc.take((size_t)a.S * a.N * psi_rs<QP>() * sizeof(T)) : 0;
-    const size_t at_acc = a.Psi2 ? sc.take((size_t)SM * a.M * sizeof(double)) : 0;
-    char* ws = (char*)mxf_ws(h, sc.bytes);
-    if (!ws) MXF_FAIL(h, -4, "mxf_psi_rbf_fwd: out of memory for %zu bytes of scratch", sc.bytes);
-    T *zf = (T*)(ws + at_z), *zh = (T*)(ws + at_zh), *rows = a.Psi2 ? (T*)(ws + at_rows) : nullptr;
-    hipLaunchKernelGGL((psi_prep_kernel<T, QP>), dim3(grid_for((int64_t)a.S * (a.N + a.M))), dim3(256), 0, st, o, rows, zf, zh);
-    if (a.Psi1)
-        hipLaunchKernelGGL((psi1_fwd_kernel<T, QP>), dim3((unsigned)cdiv(a.N, PSI_R1), (unsigned)cdiv(a.M, PSI_MCH), (unsigned)a.S), dim3(PSI_R1), 0, st, o, zf,
-                           (T*)a.Psi1);
+int psi_fwd(mxf_handle h, const char* name, const PsiArgs& a, const PsiPlan& p, hipStream_t st) {
+    const PsiOps<T> o = psi_ops<T>(a);
+    char* ws = (char*)mxf_ws(h, p.bytes);
+    if (!ws) MXF_FAIL(h, -4, "%s: out of memory for %zu bytes of scratch", name, p.bytes);
+    T *zf = (T*)(ws + p.at_z), *zh = (T*)(ws + p.at_zh), *rows = a.Psi2 ? (T*)(ws + p.at_rows) : nullptr;
+    hipLaunchKernelGGL((psi_prep_kernel<T, QP>), dim3(grid_for(p.n_prep)), dim3(256), 0, st, o, rows, zf, zh);
+    if (a.Psi1) hipLaunchKernelGGL((psi1_fwd_kernel<T, QP>), psi_dim3(p.grid1), dim3(PSI_R1), 0, st, o, zf, (T*)a.Psi1);
     if (a.Psi2) {
-        double* acc2 = (double*)(ws + at_acc);
-        MXF_HIP(h, hipMemsetAsync(acc2, 0, (size_t)SM * a.M * sizeof(double), st));
-        const int64_t nt = cdiv(a.M, PSI_TILE), pairs = nt * (nt + 1) / 2;
-        const int rch = (int)clampi(cdiv(PSI_TARGET, pairs * a.S), 1, clampi(cdiv(a.N, PSI_ROWS), 1, 65535));
-        hipLaunchKernelGGL((psi2_pairs_kernel<T, QP, false>), dim3((unsigned)pairs, (unsigned)rch, (unsigned)a.S), dim3(256), 0, st, o, rows, zh, rch, acc2,
-                           (const T*)nullptr, (double*)nullptr, 0, (double*)nullptr, (double*)nullptr);
-        hipLaunchKernelGGL((psi2_mirror_kernel<T>), dim3(grid_for(SM * a.M)), dim3(256), 0, st, SM * a.M, a.M, acc2, (T*)a.Psi2);
+        double* acc2 = (double*)(ws + p.at_acc);
+        MXF_HIP(h, hipMemsetAsync(acc2, 0, p.zero_bytes, st));
+        hipLaunchKernelGGL((psi2_pairs_kernel<T, QP, false>), psi_dim3(p.grid_pairs), dim3(256), 0, st, o, rows, zh, p.rch, acc2, (const T*)nullptr,
+                           (double*)nullptr, 0, (double*)nullptr, (double*)nullptr);
+        hipLaunchKernelGGL((psi2_mirror_kernel<T>), dim3(grid_for(p.n_mm)), dim3(256), 0, st, p.n_mm, a.M, acc2, (T*)a.Psi2);
     }
     MXF_LAUNCH_CHECK(h);
     return 0;
 }
 
 template <typename T, int QP>
-int psi_bwd(mxf_handle h, const PsiArgs& a, hipStream_t st) {
-    const PsiOps<T> o = {a.S, a.N, a.M, a.Q, a.ard, (const T*)a.mu, a.ss_mu, (const T*)a.s, a.ss_s, (const T*)a.Z, a.ss_Z, (const T*)a.ls, a.ss_ls, (const T*)a.var, a.ss_var};
-    const int64_t SM = (int64_t)a.S * a.M;
-    const int own_mu = a.ss_mu != 0, own_s = a.ss_s != 0, own_Z = a.ss_Z != 0, own_l = a.ss_ls != 0, own_v = a.ss_var != 0;
-    const int64_t n_mu = (own_mu ? a.S : 1) * a.N * a.Q, n_s = (own_s ? a.S : 1) * a.N * a.Q, n_Z = (own_Z ? a.S : 1) * a.M * a.Q;
-    const bool pairs_pass = a.G2 && (a.dZ || a.dls || a.dvar), rows_pass = a.G2 && (a.dmu || a.ds || a.dls), wide = sizeof(T) == 4;
-    PsiScratch sc;
-    const size_t at_z = sc.take((size_t)SM * QP * sizeof(T)), at_zh = sc.take((size_t)SM * QP * sizeof(T));
-    const size_t at_rows = pairs_pass ? sc.take((size_t)a.S * a.N * psi_rs<QP>() * sizeof(T)) : 0;
-    const size_t at_wt = rows_pass ? sc.take((size_t)SM * a.M * sizeof(T)) : 0;
-    // zeroed doubles, back to back: dl2 (S, QP), dvar (S), and for float32 the three large gradients (the segments of one mxf_fold_kernel)
-    const size_t at_zero = sc.bytes;
-    const size_t at_l2 = sc.take((size_t)a.S * QP * sizeof(double)), at_dv = sc.take((size_t)a.S * sizeof(double));
-    const size_t at_big = sc.take(wide ? (size_t)(n_mu + n_s + n_Z) * sizeof(double) : 0);
-    char* ws = (char*)mxf_ws(h, sc.bytes);
-    if (!ws) MXF_FAIL(h, -4, "mxf_psi_rbf_bwd: out of memory for %zu bytes of scratch", sc.bytes);
-    MXF_HIP(h, hipMemsetAsync(ws + at_zero, 0, sc.bytes - at_zero, st));
-    T *zf = (T*)(ws + at_z), *zh = (T*)(ws + at_zh), *rows = pairs_pass ? (T*)(ws + at_rows) : nullptr;
-    double *dl2acc = (double*)(ws + at_l2), *dvacc = (double*)(ws + at_dv), *big = (double*)(ws + at_big);
-    double* dmuacc = !a.dmu ? nullptr : (wide ? big : (double*)a.dmu);
-    double* dsacc = !a.ds ? nullptr : (wide ? big + n_mu : (double*)a.ds);
-    double* dZacc = !a.dZ ? nullptr : (wide ? big + n_mu + n_s : (double*)a.dZ);
-    hipLaunchKernelGGL((psi_prep_kernel<T, QP>), dim3(grid_for((int64_t)a.S * (a.N + a.M))), dim3(256), 0, st, o, rows, zf, zh);
-    if (a.G1) {
-        hipLaunchKernelGGL((psi1_bwd_kernel<T, QP>), dim3((unsigned)cdiv(a.N, PSI_R1), (unsigned)cdiv(a.M, PSI_MCH), (unsigned)a.S), dim3(PSI_R1), 0, st, o, zf, (const T*)a.G1, dmuacc, own_mu,
-                           dsacc, own_s, dZacc, own_Z, a.dls ? dl2acc : nullptr, a.dvar ? dvacc : nullptr);
+int psi_bwd(mxf_handle h, const char* name, const PsiArgs& a, const PsiPlan& p, hipStream_t st) {
+    const PsiOps<T> o = psi_ops<T>(a);
+    char* ws = (char*)mxf_ws(h, p.bytes);
+    if (!ws) MXF_FAIL(h, -4, "%s: out of memory for %zu bytes of scratch", name, p.bytes);
+    MXF_HIP(h, hipMemsetAsync(ws + p.at_zero, 0, p.zero_bytes, st));
+    T *zf = (T*)(ws + p.at_z), *zh = (T*)(ws + p.at_zh), *rows = p.pairs_pass ? (T*)(ws + p.at_rows) : nullptr;
+    double *dl2acc = (double*)(ws + p.at_l2), *dvacc = (double*)(ws + p.at_dv), *big = (double*)(ws + p.at_big);
+    double* dmuacc = !a.dmu ? nullptr : (p.wide ? big : (double*)a.dmu);
+    double* dsacc = !a.ds ? nullptr : (p.wide ? big + p.end[0] : (double*)a.ds);
+    double* dZacc = !a.dZ ? nullptr : (p.wide ? big + p.end[1] : (double*)a.dZ);
+    hipLaunchKernelGGL((psi_prep_kernel<T, QP>), dim3(grid_for(p.n_prep)), dim3(256), 0, st, o, rows, zf, zh);
+    if (a.G1)
+        hipLaunchKernelGGL((psi1_bwd_kernel<T, QP>), psi_dim3(p.grid1), dim3(PSI_R1), 0, st, o, zf, (const T*)a.G1, dmuacc, p.own_mu, dsacc, p.own_s, dZacc,
+                           p.own_Z, a.dls ? dl2acc : nullptr, a.dvar ? dvacc : nullptr);
+    if (p.pairs_pass)
+        hipLaunchKernelGGL((psi2_pairs_kernel<T, QP, true>), psi_dim3(p.grid_pairs), dim3(256), 0, st, o, rows, zh, p.rch, (double*)nullptr, (const T*)a.G2,
+                           dZacc, p.own_Z, a.dls ? dl2acc : nullptr, a.dvar ? dvacc : nullptr);
+    if (p.rows_pass) {
+        T* Wt = (T*)(ws + p.at_wt);
+        hipLaunchKernelGGL((psi2_weight_kernel<T, QP>), dim3(grid_for(p.n_mm)), dim3(256), 0, st, o, zh, (const T*)a.G2, Wt);
+        hipLaunchKernelGGL((psi2_bwd_rows_kernel<T, QP>), psi_dim3(p.grid_rows), dim3(PSI_RB), 0, st, o, zh, Wt, dmuacc, p.own_mu, dsacc, p.own_s,
+                           a.dls ? dl2acc : nullptr);
     }
-    if (pairs_pass) {
-        const int64_t nt = cdiv(a.M, PSI_TILE), pairs = nt * (nt + 1) / 2;
-        const int rch = (int)clampi(cdiv(PSI_TARGET, pairs * a.S), 1, clampi(cdiv(a.N, PSI_ROWS), 1, 65535));
-        hipLaunchKernelGGL((psi2_pairs_kernel<T, QP, true>), dim3((unsigned)pairs, (unsigned)rch, (unsigned)a.S), dim3(256), 0, st, o, rows, zh, rch,
-                           (double*)nullptr, (const T*)a.G2, dZacc, own_Z, a.dls ? dl2acc : nullptr, a.dvar ? dvacc : nullptr);
-    }
-    if (rows_pass) {
-        T* Wt = (T*)(ws + at_wt);
-        hipLaunchKernelGGL((psi2_weight_kernel<T, QP>), dim3(grid_for(SM * a.M)), dim3(256), 0, st, o, zh, (const T*)a.G2, Wt);
-        const int64_t bx = cdiv(a.N, PSI_RB);
-        const int mch = (int)clampi(cdiv(PSI_TARGET, bx * a.S), 1, clampi(a.M, 1, 65535));
-        hipLaunchKernelGGL((psi2_bwd_rows_kernel<T, QP>), dim3((unsigned)bx, (unsigned)mch, (unsigned)a.S), dim3(PSI_RB), 0, st, o, zh, Wt, dmuacc, own_mu, dsacc,
-                           own_s, a.dls ? dl2acc : nullptr);
-    }
-    if (wide && (a.dmu || a.ds || a.dZ)) {
-        const FoldTable f = {big, {(float*)a.dmu, (float*)a.ds, (float*)a.dZ}, {n_mu, n_mu + n_s, n_mu + n_s + n_Z}};
+    if (p.fold) {
+        const FoldTable f = {big, {(float*)a.dmu, (float*)a.ds, (float*)a.dZ}, {p.end[0], p.end[1], p.end[2]}};
         hipLaunchKernelGGL(mxf_fold_kernel, dim3(grid_for(f.end[SHARED_SEGS - 1])), dim3(256), 0, st, f);
     }
-    if (a.dls || a.dvar)
-        hipLaunchKernelGGL((psi_close_kernel<T, QP>), dim3(1), dim3(64), 0, st, o, dl2acc, dvacc, (T*)a.dls, own_l, (T*)a.dvar, own_v);
+    if (p.close) hipLaunchKernelGGL((psi_close_kernel<T, QP>), dim3(1), dim3(64), 0, st, o, dl2acc, dvacc, (T*)a.dls, p.own_l, (T*)a.dvar, p.own_v);
     MXF_LAUNCH_CHECK(h);
     return 0;
 }
@@ -540,26 +498,19 @@ int psi_bwd(mxf_handle h, const PsiArgs& a, hipStream_t st) {
 // R (S, N, J) = sum_{m,m'} A_j[m,m'] psi2n[n,m,m'], PSI_JB values of j per pass over the terms; the weights of one pass are reused by the next
 // (stream order).  m is split over grid.y as in the reverse pass.
 template <typename T, int QP>
-int psi_quad(mxf_handle h, const PsiArgs& a, hipStream_t st) {
-    const PsiOps<T> o = {a.S, a.N, a.M, a.Q, a.ard, (const T*)a.mu, a.ss_mu, (const T*)a.s, a.ss_s, (const T*)a.Z, a.ss_Z, (const T*)a.ls, a.ss_ls, (const T*)a.var, a.ss_var};
-    const int64_t SM = (int64_t)a.S * a.M, bx = cdiv(a.N, PSI_RB), total = (int64_t)a.S * a.N * a.J;
-    const int mch = (int)clampi(cdiv(PSI_TARGET, bx * a.S), 1, clampi(a.M, 1, 65535));
-    PsiScratch sc;
-    const size_t at_z = sc.take((size_t)SM * QP * sizeof(T)), at_zh = sc.take((size_t)SM * QP * sizeof(T));
-    const size_t at_wq = sc.take((size_t)SM * a.M * PSI_JB * sizeof(T));
-    const size_t at_acc = sc.take(mch > 1 ? (size_t)total * sizeof(double) : 0);
-    char* ws = (char*)mxf_ws(h, sc.bytes);
-    if (!ws) MXF_FAIL(h, -4, "mxf_psi_rbf_quad: out of memory for %zu bytes of scratch", sc.bytes);
-    T *zf = (T*)(ws + at_z), *zh = (T*)(ws + at_zh), *Wq = (T*)(ws + at_wq);
-    double* acc = mch > 1 ? (double*)(ws + at_acc) : nullptr;
-    if (acc) MXF_HIP(h, hipMemsetAsync(acc, 0, (size_t)total * sizeof(double), st));
-    hipLaunchKernelGGL((psi_prep_kernel<T, QP>), dim3(grid_for((int64_t)a.S * (a.N + a.M))), dim3(256), 0, st, o, (T*)nullptr, zf, zh);
-    for (int j0 = 0; j0 < a.J; j0 += PSI_JB) {
-        hipLaunchKernelGGL((psi2_quad_weight_kernel<T, QP>), dim3(grid_for(SM * a.M)), dim3(256), 0, st, o, zh, (const T*)a.A, a.ss_A, a.J, j0, Wq);
-        hipLaunchKernelGGL((psi2_quad_rows_kernel<T, QP>), dim3((unsigned)bx, (unsigned)mch, (unsigned)a.S), dim3(PSI_RB), 0, st, o, zh, Wq, a.J, j0, acc,
-                           (T*)a.R);
+int psi_quad(mxf_handle h, const char* name, const PsiArgs& a, const PsiPlan& p, hipStream_t st) {
+    const PsiOps<T> o = psi_ops<T>(a);
+    char* ws = (char*)mxf_ws(h, p.bytes);
+    if (!ws) MXF_FAIL(h, -4, "%s: out of memory for %zu bytes of scratch", name, p.bytes);
+    T *zf = (T*)(ws + p.at_z), *zh = (T*)(ws + p.at_zh), *Wq = (T*)(ws + p.at_wt);
+    double* acc = p.split ? (double*)(ws + p.at_acc) : nullptr;
+    if (acc) MXF_HIP(h, hipMemsetAsync(acc, 0, p.zero_bytes, st));
+    hipLaunchKernelGGL((psi_prep_kernel<T, QP>), dim3(grid_for(p.n_prep)), dim3(256), 0, st, o, (T*)nullptr, zf, zh);
+    for (int pass = 0; pass < p.npass; ++pass) {
+        hipLaunchKernelGGL((psi2_quad_weight_kernel<T, QP>), dim3(grid_for(p.n_mm)), dim3(256), 0, st, o, zh, (const T*)a.A, a.ss_A, a.J, pass * PSI_JB, Wq);
+        hipLaunchKernelGGL((psi2_quad_rows_kernel<T, QP>), psi_dim3(p.grid_rows), dim3(PSI_RB), 0, st, o, zh, Wq, a.J, pass * PSI_JB, acc, (T*)a.R);
     }
-    if (acc) hipLaunchKernelGGL((psi_narrow_kernel<T>), dim3(grid_for(total)), dim3(256), 0, st, total, acc, (T*)a.R);
+    if (acc) hipLaunchKernelGGL((mxf_narrow_kernel<T>), dim3(grid_for(p.n_out)), dim3(256), 0, st, p.n_out, acc, (T*)a.R);
     MXF_LAUNCH_CHECK(h);
     return 0;
 }
@@ -569,25 +520,22 @@ enum PsiCall { PSI_FWD, PSI_BWD, PSI_QUAD };
 int run(mxf_handle h, const char* name, PsiCall call, const PsiArgs& a, void* stream) {
     if (!h) return -1;
     if (a.dtype != MXF_F32 && a.dtype != MXF_F64) MXF_FAIL(h, -2, "%s: bad dtype %d", name, a.dtype);
-    if (a.S < 1 || a.S > 65535 || a.N < 1 || a.M < 1 || a.Q < 1) MXF_FAIL(h, -2, "%s: 1 <= S <= 65535 samples, N, M, Q >= 1", name);
-    if (a.Q > MXF_PSI_MAX_Q) MXF_FAIL(h, -3, "%s: Q = %d above the limit of %d input dimensions", name, a.Q, MXF_PSI_MAX_Q);
-    if (a.M > ((int64_t)1 << 20) || a.N > ((int64_t)1 << 31)) MXF_FAIL(h, -2, "%s: M <= 2^20, N <= 2^31", name);
-    if (!a.mu || !a.s || !a.Z || !a.ls || !a.var) MXF_FAIL(h, -2, "%s: null mu, s, Z, lengthscale or variance", name);
-    const int64_t nl = a.ard ? a.Q : 1;
-    if ((a.ss_mu != 0 && a.ss_mu != a.N * a.Q) || (a.ss_s != 0 && a.ss_s != a.N * a.Q) || (a.ss_Z != 0 && a.ss_Z != a.M * a.Q) ||
-        (a.ss_ls != 0 && a.ss_ls != nl) || (a.ss_var != 0 && a.ss_var != 1))
-        MXF_FAIL(h, -2, "%s: a sample stride must be 0 or the elements of one sample (mu, s: N Q; Z: M Q; lengthscale: Q or 1; variance: 1)", name);
-    if (call == PSI_QUAD) {
-        if (a.J < 1 || !a.A || !a.R) MXF_FAIL(h, -2, "%s: J >= 1 weight matrices, A and R not null", name);
-        if (a.ss_A != 0 && a.ss_A != (int64_t)a.J * a.M * a.M) MXF_FAIL(h, -2, "%s: the sample stride of A must be 0 or J M M", name);
-    }
+    const PsiRequest r = {.esize = mxf_esize(a.dtype), .S = a.S, .N = a.N, .M = a.M, .Q = a.Q, .ard = a.ard,
+                          .ss_mu = a.ss_mu, .ss_s = a.ss_s, .ss_Z = a.ss_Z, .ss_ls = a.ss_ls, .ss_var = a.ss_var,
+                          .has_mu = a.mu != nullptr, .has_s = a.s != nullptr, .has_Z = a.Z != nullptr, .has_ls = a.ls != nullptr, .has_var = a.var != nullptr,
+                          .has_Psi1 = a.Psi1 != nullptr, .has_Psi2 = a.Psi2 != nullptr, .has_G1 = a.G1 != nullptr, .has_G2 = a.G2 != nullptr,
+                          .has_dmu = a.dmu != nullptr, .has_ds = a.ds != nullptr, .has_dZ = a.dZ != nullptr, .has_dls = a.dls != nullptr,
+                          .has_dvar = a.dvar != nullptr, .J = a.J, .ss_A = a.ss_A, .has_A = a.A != nullptr, .has_R = a.R != nullptr};
+    const PsiPlan p = call == PSI_FWD ? psi_fwd_plan(r) : call == PSI_BWD ? psi_bwd_plan(r) : psi_quad_plan(r);
+    if (p.rc) MXF_FAIL(h, p.rc, "%s: %s", name, p.refusal);
     const hipStream_t st = (hipStream_t)stream;
-    const int qp = a.Q <= 4 ? 4 : (a.Q <= 8 ? 8 : 16);
-#define MXF_PSI_QP(T, QP) (call == PSI_FWD ? psi_fwd<T, QP>(h, a, st) : call == PSI_BWD ? psi_bwd<T, QP>(h, a, st) : psi_quad<T, QP>(h, a, st))
-#define MXF_PSI_GO(T) (qp == 4 ? MXF_PSI_QP(T, 4) : qp == 8 ? MXF_PSI_QP(T, 8) : MXF_PSI_QP(T, 16))
-    return a.dtype == MXF_F32 ? MXF_PSI_GO(float) : MXF_PSI_GO(double);
-#undef MXF_PSI_GO
-#undef MXF_PSI_QP
+    return dispatch<MXF_F32, MXF_F64>(a.dtype, [&](auto dt) {
+        using T = mxf_elem_t<decltype(dt)::value>;
+        return dispatch<4, 8, 16>(p.qp, [&](auto qp) {
+            constexpr int QP = decltype(qp)::value;
+            return call == PSI_FWD ? psi_fwd<T, QP>(h, name, a, p, st) : call == PSI_BWD ? psi_bwd<T, QP>(h, name, a, p, st) : psi_quad<T, QP>(h, name, a, p, st);
+        });
+    });
 }
 
 }  // namespace
@@ -595,9 +543,8 @@ int run(mxf_handle h, const char* name, PsiCall call, const PsiArgs& a, void* st
 extern "C" int mxf_psi_rbf_fwd(mxf_handle h, int dtype, int S, int64_t N, int64_t M, int Q, const void* mu, int64_t strideS_mu, const void* s,
                                int64_t strideS_s, const void* Z, int64_t strideS_Z, const void* lengthscale, int ard, int64_t strideS_ls,
                                const void* variance, int64_t strideS_var, void* Psi1, void* Psi2, void* stream) {
-    PsiArgs a = {dtype, S, N, M, Q, ard, mu, s, Z, lengthscale, variance, strideS_mu, strideS_s, strideS_Z, strideS_ls, strideS_var};
-    a.Psi1 = Psi1;
-    a.Psi2 = Psi2;
+    const PsiArgs a = {.dtype = dtype, .S = S, .N = N, .M = M, .Q = Q, .ard = ard, .mu = mu, .s = s, .Z = Z, .ls = lengthscale, .var = variance,
+                       .ss_mu = strideS_mu, .ss_s = strideS_s, .ss_Z = strideS_Z, .ss_ls = strideS_ls, .ss_var = strideS_var, .Psi1 = Psi1, .Psi2 = Psi2};
     return run(h, "mxf_psi_rbf_fwd", PSI_FWD, a, stream);
 }
 
@@ -605,16 +552,17 @@ extern "C" int mxf_psi_rbf_bwd(mxf_handle h, int dtype, int S, int64_t N, int64_
                                int64_t strideS_s, const void* Z, int64_t strideS_Z, const void* lengthscale, int ard, int64_t strideS_ls,
                                const void* variance, int64_t strideS_var, const void* G1, const void* G2, void* dmu_acc, void* ds_acc, void* dZ_acc,
                                void* dls_acc, void* dvar_acc, void* stream) {
-    PsiArgs a = {dtype, S, N, M, Q, ard, mu, s, Z, lengthscale, variance, strideS_mu, strideS_s, strideS_Z, strideS_ls, strideS_var};
-    a.G1 = G1; a.G2 = G2;
-    a.dmu = dmu_acc; a.ds = ds_acc; a.dZ = dZ_acc; a.dls = dls_acc; a.dvar = dvar_acc;
+    const PsiArgs a = {.dtype = dtype, .S = S, .N = N, .M = M, .Q = Q, .ard = ard, .mu = mu, .s = s, .Z = Z, .ls = lengthscale, .var = variance,
+                       .ss_mu = strideS_mu, .ss_s = strideS_s, .ss_Z = strideS_Z, .ss_ls = strideS_ls, .ss_var = strideS_var, .G1 = G1, .G2 = G2,
+                       .dmu = dmu_acc, .ds = ds_acc, .dZ = dZ_acc, .dls = dls_acc, .dvar = dvar_acc};
     return run(h, "mxf_psi_rbf_bwd", PSI_BWD, a, stream);
 }
 
 extern "C" int mxf_psi_rbf_quad(mxf_handle h, int dtype, int S, int64_t N, int64_t M, int Q, const void* mu, int64_t strideS_mu, const void* s,
                                 int64_t strideS_s, const void* Z, int64_t strideS_Z, const void* lengthscale, int ard, int64_t strideS_ls,
                                 const void* variance, int64_t strideS_var, int J, const void* A, int64_t strideS_A, void* R, void* stream) {
-    PsiArgs a = {dtype, S, N, M, Q, ard, mu, s, Z, lengthscale, variance, strideS_mu, strideS_s, strideS_Z, strideS_ls, strideS_var};
-    a.J = J; a.A = A; a.ss_A = strideS_A; a.R = R;
+    const PsiArgs a = {.dtype = dtype, .S = S, .N = N, .M = M, .Q = Q, .ard = ard, .mu = mu, .s = s, .Z = Z, .ls = lengthscale, .var = variance,
+                       .ss_mu = strideS_mu, .ss_s = strideS_s, .ss_Z = strideS_Z, .ss_ls = strideS_ls, .ss_var = strideS_var,
+                       .J = J, .A = A, .ss_A = strideS_A, .R = R};
     return run(h, "mxf_psi_rbf_quad", PSI_QUAD, a, stream);
 }

@@ -15,6 +15,7 @@
 // by 2 pi (in double, one rounding), the argument is reduced with fract, and the gradient is multiplied by 2 pi once per row.  float64 calls the
 // library's cos and sin on radians.
 #include "common.h"
+#include "fused_plan.h"      // RFF_*: the tile sizes; rff_plan
 #include "shared_grad.h"
 
 namespace {
@@ -35,12 +36,6 @@ template <> struct RffTrig<double> {
 #include "rff.h"
 
 namespace {
-
-constexpr int RFF_RB = 128;         // rows (threads) per workgroup
-constexpr int RFF_DCH = 64;         // values of d summed in T between two additions to the double register
-constexpr int RFF_JB = 16;          // weights per feature and pass (one scalar load)
-constexpr int RFF_JB_SMALL = 4;     // the same for J <= RFF_JB_SMALL
-constexpr int RFF_TARGET = 1024;    // workgroups the split of d aims for
 
 template <typename T>
 struct RffOps {
@@ -97,7 +92,7 @@ __device__ __forceinline__ void rff_d_range(int64_t D, int64_t ch, int64_t& d0, 
 }
 
 // out[s][n][j] = sum_d cos(.) W[d][j].  With grid.y = 1 a thread writes its row's results (out); otherwise it adds them to the zeroed
-// doubles acc (S, N, J), narrowed by rff_narrow_kernel.
+// doubles acc (S, N, J), narrowed by mxf_narrow_kernel.
 template <typename T, int QP, int JB>
 __global__ __launch_bounds__(RFF_RB) void rff_fwd_kernel(RffOps<T> o, RffPrep<T> p, int64_t ch, double* __restrict__ acc, T* __restrict__ out) {
     const int64_t s = blockIdx.z, n = (int64_t)blockIdx.x * RFF_RB + threadIdx.x;
@@ -137,11 +132,6 @@ __global__ __launch_bounds__(RFF_RB) void rff_fwd_kernel(RffOps<T> o, RffPrep<T>
             }
         }
     }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void rff_narrow_kernel(int64_t total, const double* __restrict__ acc, T* __restrict__ out) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) out[i] = (T)acc[i];
 }
 
 // dX[s][n][q] += -sum_d sin(.) omega[d][q] sum_j G[s][n][j] W[d][j]: the thread owns dX[n,:], sums every pass and every d of its range in
@@ -194,61 +184,34 @@ __global__ __launch_bounds__(RFF_RB) void rff_bwd_kernel(RffOps<T> o, RffPrep<T>
     }
 }
 
-static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-static inline int64_t clampi(int64_t x, int64_t lo, int64_t hi) { return x < lo ? lo : (x > hi ? hi : x); }
-
 struct RffArgs {
-    int dtype, S; int64_t N, D; int Q, J;
-    const void *X, *Omega, *phase, *W; int64_t ss_X, ss_Om, ss_ph, ss_W;
-    void* out;                      // forward
-    const void* G; void* dX;        // reverse
+    int dtype = MXF_F32, S = 0; int64_t N = 0, D = 0; int Q = 0, J = 0;
+    const void *X = nullptr, *Omega = nullptr, *phase = nullptr, *W = nullptr; int64_t ss_X = 0, ss_Om = 0, ss_ph = 0, ss_W = 0;
+    void* out = nullptr;                                // forward
+    const void* G = nullptr; void* dX = nullptr;        // reverse
 };
 
-struct RffScratch {
-    size_t bytes = 0;
-    size_t take(size_t b) { const size_t at = bytes; bytes += mxf_align(b); return at; }
-};
-
-// the values of d per workgroup row (a multiple of RFF_DCH) and the number of such rows: 1 unless the row blocks alone leave the device empty
-static inline void rff_split(int S, int64_t N, int64_t D, int64_t* ch, int* dch) {
-    const int64_t want = clampi(cdiv(RFF_TARGET, cdiv(N, RFF_RB) * S), 1, clampi(cdiv(D, RFF_DCH), 1, 65535));
-    *ch = cdiv(cdiv(D, want), RFF_DCH) * RFF_DCH;
-    *dch = (int)cdiv(D, *ch);
-}
-
+// ask the plan (fused_plan.h: rff_plan), carve, launch
 template <typename T, int QP, int JB>
-int rff_run(mxf_handle h, const char* name, const RffArgs& a, bool bwd, hipStream_t st) {
+int rff_launch(mxf_handle h, const char* name, const RffArgs& a, const RffPlan& p, bool bwd, hipStream_t st) {
     const RffOps<T> o = {a.S, a.N, a.D, a.Q, a.J, (const T*)a.X, a.ss_X, (const T*)a.Omega, a.ss_Om, (const T*)a.phase, a.ss_ph, (const T*)a.W, a.ss_W};
-    const int npass = (int)cdiv(a.J, JB), own_X = a.ss_X != 0;
-    const int64_t S_om = a.ss_Om ? a.S : 1, S_ph = a.ss_ph ? a.S : 1, S_W = a.ss_W ? a.S : 1;
-    int64_t ch;
-    int dch;
-    rff_split(a.S, a.N, a.D, &ch, &dch);
-    // what is summed across threads goes through doubles: the forward results under a split of d; the gradient under a split or a shared X
-    const int64_t n_out = (int64_t)a.S * a.N * a.J, n_dx = (own_X ? a.S : 1) * a.N * a.Q;
-    const bool summed = bwd ? (dch > 1 || (!own_X && a.S > 1)) : dch > 1;
-    const bool scratch_sum = summed && !(bwd && sizeof(T) == 8);         // a float64 gradient is summed in the caller's buffer itself
-    RffScratch sc;
-    const size_t at_om = sc.take((size_t)(S_om * a.D) * QP * sizeof(T)), at_ph = sc.take((size_t)(S_ph * a.D) * sizeof(T));
-    const size_t at_wb = sc.take((size_t)(S_W * npass * a.D) * JB * sizeof(T));
-    const size_t n_acc = scratch_sum ? (size_t)(bwd ? n_dx : n_out) : 0, at_acc = sc.take(n_acc * sizeof(double));
-    char* ws = (char*)mxf_ws(h, sc.bytes);
-    if (!ws) MXF_FAIL(h, -4, "%s: out of memory for %zu bytes of scratch", name, sc.bytes);
-    double* acc = scratch_sum ? (double*)(ws + at_acc) : nullptr;
-    if (acc) MXF_HIP(h, hipMemsetAsync(acc, 0, n_acc * sizeof(double), st));
-    T *om = (T*)(ws + at_om), *ph = (T*)(ws + at_ph), *wb = (T*)(ws + at_wb);
-    hipLaunchKernelGGL((rff_prep_kernel<T, QP, JB>), dim3(grid_for((S_om + S_ph + S_W * npass) * a.D)), dim3(256), 0, st, o, npass, om, ph, wb);
-    const RffPrep<T> p = {om, a.ss_Om ? a.D * QP : 0, ph, a.ss_ph ? a.D : 0, wb, a.ss_W ? (int64_t)npass * a.D * JB : 0, npass};
-    const dim3 grid((unsigned)cdiv(a.N, RFF_RB), (unsigned)dch, (unsigned)a.S);
+    char* ws = (char*)mxf_ws(h, p.bytes);
+    if (!ws) MXF_FAIL(h, -4, "%s: out of memory for %zu bytes of scratch", name, p.bytes);
+    double* acc = p.scratch_sum ? (double*)(ws + p.at_acc) : nullptr;
+    if (acc) MXF_HIP(h, hipMemsetAsync(acc, 0, p.zero_bytes, st));
+    T *om = (T*)(ws + p.at_om), *ph = (T*)(ws + p.at_ph), *wb = (T*)(ws + p.at_wb);
+    hipLaunchKernelGGL((rff_prep_kernel<T, QP, JB>), dim3(grid_for(p.n_prep)), dim3(256), 0, st, o, p.npass, om, ph, wb);
+    const RffPrep<T> prep = {om, p.ss_om, ph, p.ss_ph, wb, p.ss_wb, p.npass};
+    const dim3 grid(p.grid[0], p.grid[1], p.grid[2]);
     if (!bwd) {
-        hipLaunchKernelGGL((rff_fwd_kernel<T, QP, JB>), grid, dim3(RFF_RB), 0, st, o, p, ch, acc, (T*)a.out);
-        if (acc) hipLaunchKernelGGL((rff_narrow_kernel<T>), dim3(grid_for(n_out)), dim3(256), 0, st, n_out, acc, (T*)a.out);
+        hipLaunchKernelGGL((rff_fwd_kernel<T, QP, JB>), grid, dim3(RFF_RB), 0, st, o, prep, p.ch, acc, (T*)a.out);
+        if (acc) hipLaunchKernelGGL((mxf_narrow_kernel<T>), dim3(grid_for(p.n_out)), dim3(256), 0, st, p.n_out, acc, (T*)a.out);
     } else {
-        double* dacc = !summed ? nullptr : (acc ? acc : (double*)a.dX);
-        hipLaunchKernelGGL((rff_bwd_kernel<T, QP, JB>), grid, dim3(RFF_RB), 0, st, o, p, ch, (const T*)a.G, dacc, own_X, (T*)a.dX);
+        double* dacc = !p.summed ? nullptr : (acc ? acc : (double*)a.dX);
+        hipLaunchKernelGGL((rff_bwd_kernel<T, QP, JB>), grid, dim3(RFF_RB), 0, st, o, prep, p.ch, (const T*)a.G, dacc, p.own_X, (T*)a.dX);
         if (acc) {
-            const FoldTable f = {acc, {(float*)a.dX, nullptr, nullptr}, {n_dx, n_dx, n_dx}};
-            hipLaunchKernelGGL(mxf_fold_kernel, dim3(grid_for(n_dx)), dim3(256), 0, st, f);
+            const FoldTable f = {acc, {(float*)a.dX, nullptr, nullptr}, {p.n_dx, p.n_dx, p.n_dx}};
+            hipLaunchKernelGGL(mxf_fold_kernel, dim3(grid_for(p.n_dx)), dim3(256), 0, st, f);
         }
     }
     MXF_LAUNCH_CHECK(h);
@@ -258,38 +221,33 @@ int rff_run(mxf_handle h, const char* name, const RffArgs& a, bool bwd, hipStrea
 int run(mxf_handle h, const char* name, const RffArgs& a, bool bwd, void* stream) {
     if (!h) return -1;
     if (a.dtype != MXF_F32 && a.dtype != MXF_F64) MXF_FAIL(h, -2, "%s: bad dtype %d", name, a.dtype);
-    if (a.S < 1 || a.S > 65535 || a.N < 1 || a.D < 1 || a.Q < 1 || a.J < 1) MXF_FAIL(h, -2, "%s: 1 <= S <= 65535 samples, N, D, Q, J >= 1", name);
-    if (a.Q > MXF_RFF_MAX_Q) MXF_FAIL(h, -3, "%s: Q = %d above the limit of %d input dimensions", name, a.Q, MXF_RFF_MAX_Q);
-    if (a.N > ((int64_t)1 << 31) || a.D > ((int64_t)1 << 24) || a.J > (1 << 16)) MXF_FAIL(h, -2, "%s: N <= 2^31, D <= 2^24, J <= 2^16", name);
-    if (!a.X || !a.Omega || !a.phase || !a.W) MXF_FAIL(h, -2, "%s: null X, Omega, phase or W", name);
-    if (bwd ? (!a.G || !a.dX) : !a.out) MXF_FAIL(h, -2, "%s: null %s", name, bwd ? "G or dX_acc" : "out");
-    if ((a.ss_X != 0 && a.ss_X != a.N * a.Q) || (a.ss_Om != 0 && a.ss_Om != a.D * a.Q) || (a.ss_ph != 0 && a.ss_ph != a.D) ||
-        (a.ss_W != 0 && a.ss_W != a.D * a.J))
-        MXF_FAIL(h, -2, "%s: a sample stride must be 0 or the elements of one sample (X: N Q; Omega: D Q; phase: D; W: D J)", name);
-    const hipStream_t st = (hipStream_t)stream;
-    const int qp = a.Q <= 4 ? 4 : (a.Q <= 8 ? 8 : 16);
-    const bool small = a.J <= RFF_JB_SMALL;
-#define MXF_RFF_JB(T, QP) (small ? rff_run<T, QP, RFF_JB_SMALL>(h, name, a, bwd, st) : rff_run<T, QP, RFF_JB>(h, name, a, bwd, st))
-#define MXF_RFF_GO(T) (qp == 4 ? MXF_RFF_JB(T, 4) : qp == 8 ? MXF_RFF_JB(T, 8) : MXF_RFF_JB(T, 16))
-    return a.dtype == MXF_F32 ? MXF_RFF_GO(float) : MXF_RFF_GO(double);
-#undef MXF_RFF_GO
-#undef MXF_RFF_JB
+    const RffPlan p = rff_plan({.esize = mxf_esize(a.dtype), .bwd = bwd, .S = a.S, .N = a.N, .D = a.D, .Q = a.Q, .J = a.J,
+                                .ss_X = a.ss_X, .ss_Om = a.ss_Om, .ss_ph = a.ss_ph, .ss_W = a.ss_W,
+                                .has_X = a.X != nullptr, .has_Om = a.Omega != nullptr, .has_ph = a.phase != nullptr, .has_W = a.W != nullptr,
+                                .has_out = a.out != nullptr, .has_G = a.G != nullptr, .has_dX = a.dX != nullptr});
+    if (p.rc) MXF_FAIL(h, p.rc, "%s: %s", name, p.refusal);
+    return dispatch<MXF_F32, MXF_F64>(a.dtype, [&](auto dt) {
+        return dispatch<4, 8, 16>(p.qp, [&](auto qp) {
+            return dispatch<RFF_JB_SMALL, RFF_JB>(p.jb, [&](auto jb) {
+                return rff_launch<mxf_elem_t<decltype(dt)::value>, decltype(qp)::value, decltype(jb)::value>(h, name, a, p, bwd, (hipStream_t)stream);
+            });
+        });
+    });
 }
 
 }  // namespace
 
 extern "C" int mxf_rff_eval(mxf_handle h, int dtype, int S, int64_t N, int64_t D, int Q, int J, const void* X, int64_t strideS_X, const void* Omega,
                             int64_t strideS_Om, const void* phase, int64_t strideS_ph, const void* W, int64_t strideS_W, void* out, void* stream) {
-    RffArgs a = {dtype, S, N, D, Q, J, X, Omega, phase, W, strideS_X, strideS_Om, strideS_ph, strideS_W};
-    a.out = out;
+    const RffArgs a = {.dtype = dtype, .S = S, .N = N, .D = D, .Q = Q, .J = J, .X = X, .Omega = Omega, .phase = phase, .W = W,
+                       .ss_X = strideS_X, .ss_Om = strideS_Om, .ss_ph = strideS_ph, .ss_W = strideS_W, .out = out};
     return run(h, "mxf_rff_eval", a, false, stream);
 }
 
 extern "C" int mxf_rff_eval_bwd(mxf_handle h, int dtype, int S, int64_t N, int64_t D, int Q, int J, const void* X, int64_t strideS_X, const void* Omega,
                                 int64_t strideS_Om, const void* phase, int64_t strideS_ph, const void* W, int64_t strideS_W, const void* G, void* dX_acc,
                                 void* stream) {
-    RffArgs a = {dtype, S, N, D, Q, J, X, Omega, phase, W, strideS_X, strideS_Om, strideS_ph, strideS_W};
-    a.G = G;
-    a.dX = dX_acc;
+    const RffArgs a = {.dtype = dtype, .S = S, .N = N, .D = D, .Q = Q, .J = J, .X = X, .Omega = Omega, .phase = phase, .W = W,
+                       .ss_X = strideS_X, .ss_Om = strideS_Om, .ss_ph = strideS_ph, .ss_W = strideS_W, .G = G, .dX = dX_acc};
     return run(h, "mxf_rff_eval_bwd", a, true, stream);
 }

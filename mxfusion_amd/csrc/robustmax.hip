@@ -14,20 +14,18 @@
 // integer clamped to [0, C - 1]: no label value can index outside the row.
 // Nothing is allocated and no table is read from global memory, so the entry points capture into a hipGraph.
 #include "common.h"
+#include "fused_plan.h"      // per_sample_plan
 #include "likelihood.h"
 
 namespace {
 
-template <typename T>
-struct RmNodes { T x[MXF_LIK_MAX_NODES], w[MXF_LIK_MAX_NODES]; int nq; };
-
 struct RmArgs {
-    int S; int64_t n; int C;
-    const void* y; int64_t ss_y;
-    const void* m; int64_t ss_m;
-    const void* v; int64_t ss_v;
-    const void* cot; double scale, l0, dl;      // L0 and L1 - L0
-    void *out, *dm, *dv;       // RM_EXPECT: out (S), dm (S, n, C), dv (S, n); RM_PROBS: out = probs (S, n, C)
+    int S = 0; int64_t n = 0; int C = 0;
+    const void* y = nullptr; int64_t ss_y = 0;
+    const void* m = nullptr; int64_t ss_m = 0;
+    const void* v = nullptr; int64_t ss_v = 0;
+    const void* cot = nullptr; double scale = 1.0, l0 = 0.0, dl = 1.0;      // L0 and L1 - L0
+    void *out = nullptr, *dm = nullptr, *dv = nullptr;       // RM_EXPECT: out (S), dm (S, n, C), dv (S, n); RM_PROBS: out = probs (S, n, C)
 };
 enum { RM_EXPECT = 0, RM_PROBS = 1 };
 
@@ -38,7 +36,7 @@ __device__ __forceinline__ int rm_label(T y, int C) { return y > (T)0 ? (y < (T)
 template <typename T, int CP, int MODE>
 __global__ __launch_bounds__(256) void robustmax_kernel(int S, int64_t n, int C, int chunks, const T* __restrict__ y, int64_t ss_y,
                                                         const T* __restrict__ m, int64_t ss_m, const T* __restrict__ v, int64_t ss_v,
-                                                        const RmNodes<T> q, const T* __restrict__ cot, T scale, T l0, T dl,
+                                                        const MxfQuadNodes<T> q, const T* __restrict__ cot, T scale, T l0, T dl,
                                                         T* __restrict__ out, T* __restrict__ dm, T* __restrict__ dv) {
     __shared__ T red[16];
     const int64_t pairs = (int64_t)S * chunks, nC = n * C;
@@ -77,44 +75,13 @@ __global__ __launch_bounds__(256) void robustmax_kernel(int S, int64_t n, int C,
     }
 }
 
-// Grid: lik_plan of likelihood.hip restated -- up to 512 chunks of 256 rows per sample, fewer where S of them would pass 8192 workgroups, at
-// most 65 536 workgroups that loop over the rest of the pairs; out[s] receives `chunks` atomics whatever S is.
-struct RmPlan { int chunks; unsigned grid; };
-static inline RmPlan rm_plan(int S, int64_t n) {
-    int64_t c = (n + 255) / 256;
-    if (c > 512) c = 512;
-    const int64_t fit = 8192 / (int64_t)S;
-    if (c > fit) c = fit;
-    if (c < 1) c = 1;
-    int64_t g = (int64_t)S * c;
-    if (g > 65536) g = 65536;
-    return {(int)c, (unsigned)g};
-}
-
-template <typename T, int CP>
-void launch_cp(const RmArgs& a, const RmNodes<T>& q, int mode, hipStream_t st) {
-    const RmPlan p = rm_plan(a.S, a.n);
-    const dim3 grid(p.grid), block(256);
-#define MXF_RM_LAUNCH(MODE)                                                                                                               \
-    hipLaunchKernelGGL((robustmax_kernel<T, CP, MODE>), grid, block, 0, st, a.S, a.n, a.C, p.chunks, (const T*)a.y, a.ss_y, (const T*)a.m, \
-                       a.ss_m, (const T*)a.v, a.ss_v, q, (const T*)a.cot, (T)a.scale, (T)a.l0, (T)a.dl, (T*)a.out, (T*)a.dm, (T*)a.dv)
-    if (mode == RM_PROBS) MXF_RM_LAUNCH(RM_PROBS);
-    else MXF_RM_LAUNCH(RM_EXPECT);
-#undef MXF_RM_LAUNCH
-}
-
-template <typename T>
-void launch(const RmArgs& a, int nq, const double* nodes, const double* weights, int mode, hipStream_t st) {
-    RmNodes<T> q;
-    q.nq = nq;
-    for (int k = 0; k < MXF_LIK_MAX_NODES; ++k) {
-        q.x[k] = k < nq ? (T)(1.41421356237309504880 * nodes[k]) : (T)0;
-        q.w[k] = k < nq ? (T)(0.56418958354775628695 * weights[k]) : (T)0;
-    }
-    if (a.C <= 4) launch_cp<T, 4>(a, q, mode, st);
-    else if (a.C <= 8) launch_cp<T, 8>(a, q, mode, st);
-    else if (a.C <= 16) launch_cp<T, 16>(a, q, mode, st);
-    else launch_cp<T, 32>(a, q, mode, st);
+// Grid: per_sample_plan of fused_plan.h; out[s] receives `chunks` atomics whatever S is.
+template <typename T, int CP, int MODE>
+int rm_launch(const RmArgs& a, const MxfQuadNodes<T>& q, hipStream_t st) {
+    const PerSamplePlan p = per_sample_plan(a.S, a.n);
+    hipLaunchKernelGGL((robustmax_kernel<T, CP, MODE>), dim3(p.grid), dim3(256), 0, st, a.S, a.n, a.C, p.chunks, (const T*)a.y, a.ss_y, (const T*)a.m,
+                       a.ss_m, (const T*)a.v, a.ss_v, q, (const T*)a.cot, (T)a.scale, (T)a.l0, (T)a.dl, (T*)a.out, (T*)a.dm, (T*)a.dv);
+    return 0;
 }
 
 // argument checks shared by the entry points (those of run() in likelihood.hip), then the launch
@@ -128,8 +95,14 @@ int run(mxf_handle h, const char* name, int dtype, const RmArgs& a, int nq, cons
     if (!a.m || !a.v || (mode == RM_EXPECT && !a.y)) MXF_FAIL(h, -2, "%s: null y, m or v", name);
     if ((a.ss_y != 0 && a.ss_y != a.n) || (a.ss_m != 0 && a.ss_m != a.n * a.C) || (a.ss_v != 0 && a.ss_v != a.n))
         MXF_FAIL(h, -2, "%s: a sample stride must be 0 or the elements of one sample (y, v: n; m: n C)", name);
-    if (dtype == MXF_F32) launch<float>(a, nq, nodes, weights, mode, (hipStream_t)stream);
-    else launch<double>(a, nq, nodes, weights, mode, (hipStream_t)stream);
+    dispatch<MXF_F32, MXF_F64>(dtype, [&](auto dt) {
+        using T = mxf_elem_t<decltype(dt)::value>;
+        const MxfQuadNodes<T> q = mxf_quad_nodes<T>(nq, nodes, weights);
+        return dispatch<4, 8, 16, 32>(a.C <= 4 ? 4 : (a.C <= 8 ? 8 : (a.C <= 16 ? 16 : 32)), [&](auto cp) {       // the row padded to registers
+            return dispatch<RM_EXPECT, RM_PROBS>(
+                mode, [&](auto md) { return rm_launch<T, decltype(cp)::value, decltype(md)::value>(a, q, (hipStream_t)stream); });
+        });
+    });
     MXF_LAUNCH_CHECK(h);
     return 0;
 }
@@ -142,13 +115,14 @@ extern "C" int mxf_robustmax_expect(mxf_handle h, int dtype, int S, int64_t n, i
     if (h && n > 0 && S > 0 && !(eps > 0.0 && eps < 1.0)) MXF_FAIL(h, -2, "mxf_robustmax_expect: eps = %g outside (0, 1)", eps);
     if (h && n > 0 && S > 0 && !out_acc) MXF_FAIL(h, -2, "mxf_robustmax_expect: null out");
     const double l0 = C >= 2 ? log(eps / (double)(C - 1)) : 0.0, l1 = log1p(-eps);
-    const RmArgs a = {S, n, C, y, strideS_y, m, strideS_m, v, strideS_v, cot, scale, l0, l1 - l0, out_acc, dm_acc, dv_acc};
+    const RmArgs a = {.S = S, .n = n, .C = C, .y = y, .ss_y = strideS_y, .m = m, .ss_m = strideS_m, .v = v, .ss_v = strideS_v, .cot = cot, .scale = scale,
+                      .l0 = l0, .dl = l1 - l0, .out = out_acc, .dm = dm_acc, .dv = dv_acc};
     return run(h, "mxf_robustmax_expect", dtype, a, nq, nodes, weights, RM_EXPECT, stream);
 }
 
 extern "C" int mxf_robustmax_probs(mxf_handle h, int dtype, int S, int64_t n, int C, const void* m, int64_t strideS_m, const void* v,
                                    int64_t strideS_v, int nq, const double* nodes, const double* weights, void* probs, void* stream) {
     if (h && n > 0 && S > 0 && !probs) MXF_FAIL(h, -2, "mxf_robustmax_probs: null probs");
-    const RmArgs a = {S, n, C, nullptr, 0, m, strideS_m, v, strideS_v, nullptr, 1.0, 0.0, 1.0, probs, nullptr, nullptr};
+    const RmArgs a = {.S = S, .n = n, .C = C, .m = m, .ss_m = strideS_m, .v = v, .ss_v = strideS_v, .scale = 1.0, .l0 = 0.0, .dl = 1.0, .out = probs};
     return run(h, "mxf_robustmax_probs", dtype, a, nq, nodes, weights, RM_PROBS, stream);
 }

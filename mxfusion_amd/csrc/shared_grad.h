@@ -59,6 +59,12 @@ static __global__ __launch_bounds__(256) void mxf_fold_kernel(FoldTable t) {
     }
 }
 
+// out[i] = acc[i], rounded once: the sums that a split reduction axis left in zeroed doubles (rff.hip, kmv.hip, psi.hip)
+template <typename T>
+static __global__ __launch_bounds__(256) void mxf_narrow_kernel(int64_t total, const double* __restrict__ acc, T* __restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) out[i] = (T)acc[i];
+}
+
 // The accumulators of up to three segments, in out->acc: the buffers themselves for double; for float32 consecutive pieces of one zeroed
 // scratch allocation of the handle (-4 if it cannot be had).  name: the entry point, for the message.
 template <typename T>

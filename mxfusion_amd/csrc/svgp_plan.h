@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "fused_plan.h"     // Carver
 #include "gemm_plan.h"
 #include "gram_bwd_plan.h"
 #include "gram_plan.h"      // ... and include/mxf_gp.h: MXF_K_*, MXF_SVGP_*
@@ -141,11 +142,6 @@ static inline SvgpSchedule svgp_psi2_schedule(const SvgpPlan& p, const SvgpKnobs
 }
 
 // ---- scratch -----------------------------------------------------------------------------------------------------------------------------
-struct Carver {   // bump allocator over a scratch buffer in 256-byte granules; with a null base it only counts
-    char* base; size_t off = 0;
-    explicit Carver(void* p) : base((char*)p) {}
-    template <typename U> U* take(size_t n) { U* p = base ? (U*)(base + off) : nullptr; off += (n * sizeof(U) + 255) / 256 * 256; return p; }
-};
 // The SVGP call's scratch (what a path does not take stays null) and its layout, one list: run once to count and once to carve
 template <typename T>
 struct SvgpScratch {

@@ -4,6 +4,7 @@
 // at link time.
 #pragma once
 #include "common.h"
+#include "fused_plan.h"      // per_sample_plan
 #include "special.h"
 
 namespace {
@@ -162,7 +163,7 @@ __global__ __launch_bounds__(256) void univariate_elem_kernel(int S, int64_t n, 
 
 // out[s] += scale * sum_i log p(x[s,i] | a, b).  A workgroup takes (sample, chunk) pairs p = s * chunks + c off a one-dimensional grid --
 // S never rides on a 65 535-limited axis, and pairs beyond the grid are looped over -- and walks its chunk's elements i = c * 256 + t,
-// + chunks * 256, ...; one block_sum and ONE atomic per pair, so out[s] receives `chunks` atomics whatever S is (uni_ps_plan).
+// + chunks * 256, ...; one block_sum and ONE atomic per pair, so out[s] receives `chunks` atomics whatever S is (per_sample_plan of fused_plan.h).
 template <typename T, int KIND>
 __global__ __launch_bounds__(256) void univariate_ps_kernel(int S, int64_t n, int chunks, const T* __restrict__ x, const T* __restrict__ a,
                                                             int64_t n_a, int64_t ss_a, const T* __restrict__ b, int64_t n_b, int64_t ss_b,
@@ -188,21 +189,6 @@ __global__ __launch_bounds__(256) void univariate_ps_kernel(int S, int64_t n, in
     }
 }
 
-// Grid of univariate_ps_kernel.  The cap on same-address atomics (grid_for_reduce: ~15 ns apiece at the L2) holds PER SAMPLE here, S
-// addresses take them in parallel: up to 512 chunks per sample, fewer where S of them would pass 8192 workgroups (32 per CU), and a grid
-// of at most 65 536 workgroups that loops over the rest of the pairs.
-struct UniPsPlan { int chunks; unsigned grid; };
-static inline UniPsPlan uni_ps_plan(int S, int64_t n) {
-    int64_t c = (n + 255) / 256;
-    if (c > 512) c = 512;
-    const int64_t fit = 8192 / (int64_t)S;
-    if (c > fit) c = fit;
-    if (c < 1) c = 1;
-    int64_t g = (int64_t)S * c;
-    if (g > 65536) g = 65536;
-    return {(int)c, (unsigned)g};
-}
-
 struct UniArgs {
     int S; int64_t n;
     const void *x, *a; int64_t n_a, ss_a;
@@ -220,7 +206,7 @@ void uni_launch_kind(const UniArgs& u, int mode, hipStream_t st) {
         hipLaunchKernelGGL((univariate_elem_kernel<T, KIND>), dim3(grid_for(u.n)), block, 0, st, u.S, u.n, (const T*)u.x, (const T*)u.a, u.n_a,
                            u.ss_a, (const T*)u.b, u.n_b, u.ss_b, (T)u.scale, (T*)u.out);
     else if (mode == UNI_PER_SAMPLE) {
-        const UniPsPlan p = uni_ps_plan(u.S, u.n);
+        const PerSamplePlan p = per_sample_plan(u.S, u.n);      // (fused_plan.h)
         hipLaunchKernelGGL((univariate_ps_kernel<T, KIND>), dim3(p.grid), block, 0, st, u.S, u.n, p.chunks, (const T*)u.x, (const T*)u.a, u.n_a,
                            u.ss_a, (const T*)u.b, u.n_b, u.ss_b, (T)u.scale, (T*)u.out);
     } else                                                          // (the cap of grid_for_reduce is for the closing atomics)

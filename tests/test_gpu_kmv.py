@@ -136,18 +136,6 @@ def test_forward_and_reverse(case, dtype):
     _close(only, g['dvar'] + 1.0, sc['dvar'] + 1.0, dtype, 'reverse, variance alone')
 
 
-def test_launch_shapes_of_the_cases():
-    """the split formula of kmv_split in csrc/kmv.hip at the cases above: which split n2, into how many rows"""
-    cdiv = lambda a, b: -(-a // b)
-
-    def split(N, N2, S):
-        want = max(1, min(cdiv(1024, cdiv(N, 128) * S), max(1, min(cdiv(N2, 64), 65535))))
-        ch = cdiv(cdiv(N2, want), 64) * 64
-        return ch, cdiv(N2, ch)
-    assert split(100, 5000, 1) == (64, 79) and split(140000, 3, 1) == (64, 1) and split(129, 63, 1) == (64, 1) and split(129, 65, 1) == (64, 2)
-    assert split(300, 200, 1) == (64, 4) and split(300, 300, 2) == (64, 5) and split(1, 1, 1) == (64, 1)
-
-
 def test_status_codes_leave_the_buffers_alone():
     """Q = 17 is -3; a null pointer, a bad stride, a non-stationary kind and J = 0 are -2; nothing is written"""
     from mxfusion_amd import _lib, ops

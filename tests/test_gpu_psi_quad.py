@@ -99,15 +99,6 @@ def test_contraction(case, dtype):
     _close(got, ref, mag, dtype, 'R')
 
 
-def test_launch_shapes_of_the_large_cases():
-    """the launch formula of psi_quad in csrc/psi.hip at the two large cases: workgroups over m, strides over m and the tail"""
-    cdiv = lambda a, b: -(-a // b)
-    mch = lambda N, M, S: max(1, min(cdiv(2048, cdiv(N, 128) * S), M))
-    assert mch(43700, 13, 1) == 6 and 13 // 6 == 2 and 13 % 6 == 1
-    assert mch(262100, 2, 1) == 1
-    assert all(mch(n, m, s) > 1 for n, m, q, a, j, s, own in CASES[:-2] if m > 1)
-
-
 @pytest.mark.parametrize('dtype', [torch.float64, torch.float32], ids=['f64', 'f32'])
 def test_only_the_symmetric_part_of_the_weights_counts(dtype):
     """A and (A + A^T) / 2 have the same A + A^T bit for bit (halving is exact): the same R to the bar"""

@@ -91,18 +91,6 @@ def test_forward_and_reverse(case, dtype):
     _close(dX, dref + 1.0, dmag + 1.0, dtype, 'reverse')
 
 
-def test_launch_shapes_of_the_cases():
-    """the split formula of rff_split in csrc/rff.hip at the cases above: which split d, into how many rows, with what tail"""
-    cdiv = lambda a, b: -(-a // b)
-
-    def split(N, D, S):
-        want = max(1, min(cdiv(1024, cdiv(N, 128) * S), max(1, min(cdiv(D, 64), 65535))))
-        ch = cdiv(cdiv(D, want), 64) * 64
-        return ch, cdiv(D, ch)
-    assert split(70000, 3, 1) == (64, 1) and split(70000, 130, 1) == (128, 2) and split(131073, 65, 1) == (128, 1)
-    assert split(129, 130, 1) == (64, 3) and split(129, 70, 2) == (64, 2) and split(129, 5, 2) == (64, 1) and split(1, 65, 1) == (64, 2)
-
-
 def test_autograd_function_against_central_differences():
     """float64, N = 3, D = 5, Q = 2: the gradient of ops.RFFEval in X against central differences of its own forward pass (torch.autograd.gradcheck,
     step 1e-6: truncation 1e-12 |Omega|^3, rounding 1e-16 / 1e-6); no gradient for the basis and the weights"""
