@@ -569,6 +569,27 @@ int mxf_kmv_bwd(mxf_handle h, int kind, int dtype, int S, int64_t N, int64_t N2,
                 const void* A, int64_t strideS_A, const void* V, int64_t strideS_V, const double* w, void* dls_acc, void* dvar_acc,
                 void* stream);
 
+/* Nearest-centre assignment and one Lloyd iteration of k-means, the primitive of initialising inducing inputs from data
+ * (mxfusion_amd/util/inducing.py).  No reference counterpart: the reference draws its inducing inputs from a standard normal.
+ *   idx[n] = argmin_m sum_q (X[n,q] - C[m,q])^2,   d2[n] = that minimum
+ * There is no sample axis.  X (N, Q) and the centres C (M, Q) are dense row-major in dtype (float32 or float64).  The distance is the
+ * difference form, summed in the working dtype -- not |x|^2 - 2 x.c + |c|^2, which cancels for nearby points.  m is scanned in ascending
+ * order with a strict <: among exact ties the SMALLEST index wins (a contract).  Inputs are finite: the caller's precondition, not checked.
+ * 1 <= Q <= MXF_NEAREST_MAX_Q: a larger Q is status -3, and no buffer is touched; a null required pointer, N, M or Q < 1, N > 2^31,
+ * M > 2^31 - 1 or C_new == C is status -2.  Nothing of size N x M is stored: a thread owns a row and scans the centres, which arrive as
+ * scalar loads (mxfusion_amd/csrc/nearest.hip has the decomposition).  Scratch, M Q elements and for a step M (Q + 1) doubles (Q padded to
+ * 4, 8 or 16), comes from the handle.
+ *
+ * mxf_nearest: idx (N) int32 is WRITTEN, and d2 (N) in dtype where it is not NULL.
+ * mxf_kmeans_step: one Lloyd iteration in one call.  C_new (M, Q) is WRITTEN: row m is the mean of the rows of X assigned to m (summed in
+ *   double, rounded once), or C[m] bitwise where no row is, with counts[m] = 0.  counts (M) int64 and inertia[0] = sum_n d2[n] (a double
+ *   on the device) are WRITTEN; idx (N) is written where it is not NULL.  C_new must not alias C.  The sums are atomic: C_new and inertia
+ *   can differ in their last bits from call to call, idx and counts cannot.                                                                */
+#define MXF_NEAREST_MAX_Q 16
+int mxf_nearest(mxf_handle h, int dtype, int64_t N, int64_t M, int Q, const void* X, const void* C, int32_t* idx, void* d2, void* stream);
+int mxf_kmeans_step(mxf_handle h, int dtype, int64_t N, int64_t M, int Q, const void* X, const void* C, void* C_new, int32_t* idx,
+                    int64_t* counts, double* inertia, void* stream);
+
 /* Multivariate normal of order n <= 32 over x (S, B, n), mean (S|1, B|1, n) and A (S|1, B|1, n, n): A is the covariance (form 0) or the
  * precision (form 1).  A larger n is status -3 from every entry point, and no buffer is touched (such matrices take mxf_potrf /
  * mxf_trsm).  Replaces MultivariateNormal.log_pdf_impl (components/distributions/normal.py:157-178: linalg.potrf, linalg.trsm,

@@ -18,7 +18,8 @@ ROBUSTMAX_MAX_C = 32       # MXF_ROBUSTMAX_MAX_C: classes of a robust-max row
 PSI_MAX_Q = 16             # MXF_PSI_MAX_Q: input dimensions of the psi statistics
 RFF_MAX_Q = 16             # MXF_RFF_MAX_Q: input dimensions of the random Fourier features
 KMV_MAX_Q = 16             # MXF_KMV_MAX_Q: input dimensions of the matrix-free kernel product
-TR_MAX_SEG = 32            # MXF_TR_MAX_SEG: segments per launch; a longer list takes further launches inside the call
+NEAREST_MAX_Q = 16         # MXF_NEAREST_MAX_Q: input dimensions of the nearest-centre assignment
+TR_MAX_SEG = 32           # MXF_TR_MAX_SEG: segments per launch; a longer list takes further launches inside the call
 ACT_IDENTITY, ACT_TANH, ACT_RELU, ACT_SIGMOID = range(4)
 DENSE_MAX_WIDTH = 128
 EW_ADD, EW_SUBTRACT, EW_MULTIPLY, EW_DIVIDE, EW_POWER, EW_SQUARE, EW_EXP, EW_LOG = range(8)
@@ -71,6 +72,8 @@ SIGNATURES = {
     'mxf_rff_eval_bwd': [_i, _i, _i64, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
     'mxf_kmv': [_i, _i, _i, _i64, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
     'mxf_kmv_bwd': [_i, _i, _i, _i64, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _pd, _vp, _vp, _vp],
+    'mxf_nearest': [_i, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp],
+    'mxf_kmeans_step': [_i, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     'mxf_mvn_factor': [_i, _i, _i, _i64, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
     'mxf_mvn_logpdf': [_i, _i, _i, _i64, _i, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _i, _i64, _d, _vp, _vp],
     'mxf_mvn_logpdf_bwd': [_i, _i, _i, _i64, _i, _vp, _i64, _vp, _i64, _i64, _vp, _i, _i64, _vp, _d, _vp, _vp, _vp, _vp],

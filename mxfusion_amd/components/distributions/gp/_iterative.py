@@ -36,27 +36,35 @@ class Preconditioner(object):
         return z + self.L @ eps[self.N:] if self.rank else z
 
 
-def pivoted_cholesky(row, diag, rank):
+def pivoted_cholesky(row, diag, rank, return_pivots=False):
     """L (N, r), r <= rank, of the greedy pivoted Cholesky of a positive semi-definite matrix: `row(i)` is its row at the 0-d index tensor i,
     (N,), and `diag` its diagonal (N,).  Stops early at a pivot below 1e-12 of the largest diagonal entry; rank 0 gives None.  The pivot
-    stays on the device: the one host read per column is the stopping test."""
+    stays on the device: the one host read per column is the stopping test.  With return_pivots, (L, pivots): the r pivot rows in the order
+    they were taken, an int64 tensor on the device (the rows that greedily maximise the conditional variance)."""
     N = int(diag.shape[0])
     rank = min(int(rank), N)
     if rank <= 0:
-        return None
+        return (None, torch.zeros(0, dtype=torch.int64, device=diag.device)) if return_pivots else None
     d = diag.clone()
     floor = 1e-12 * float(d.max())
     L = torch.zeros((N, rank), dtype=diag.dtype, device=diag.device)
-    m = 0
+    pivots = []
+    done = rank
     for m in range(rank):
         piv = torch.argmax(d)
         dp = d[piv]
         if float(dp) <= floor:
-            return L[:, :m].contiguous() if m else None
+            done = m
+            break
         col = (row(piv) - L[:, :m] @ L[piv, :m]) / torch.sqrt(dp)
         L[:, m] = col
         d = (d - col * col).clamp_min(0.0)
         d[piv] = 0.0
+        pivots.append(piv)
+    if done < rank:
+        L = L[:, :done].contiguous() if done else None
+    if return_pivots:
+        return L, (torch.stack(pivots) if pivots else torch.zeros(0, dtype=torch.int64, device=diag.device))
     return L
 
 

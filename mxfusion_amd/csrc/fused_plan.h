@@ -1,6 +1,7 @@
-// Grids, chunk sizes, accumulation paths, scratch layouts and refusals of the row-owned launchers (rff.hip, kmv.hip, psi.hip) and the grid of
-// the per-sample reductions (unidist.h, likelihood.hip, robustmax.hip), as pure functions of the request: plain C++, no HIP, checked on the
-// host by tests/host/fused_plan_check.cpp.  The tile sizes are the kernels' own: the .hip files read them from here.
+// Grids, chunk sizes, accumulation paths, scratch layouts and refusals of the row-owned launchers (rff.hip, kmv.hip, psi.hip, nearest.hip) and
+// the grid of the per-sample reductions (unidist.h, likelihood.hip, robustmax.hip), as pure functions of the request: plain C++, no HIP,
+// checked on the host by tests/host/fused_plan_check.cpp and tests/host/nearest_plan_check.cpp.  The tile sizes are the kernels' own: the
+// .hip files read them from here.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -325,6 +326,51 @@ static inline PsiPlan psi_quad_plan(const PsiRequest& r) {
     p.at_wt = mxf_piece(cv, (size_t)p.n_mm * PSI_JB * r.esize);
     p.zero_bytes = p.split ? (size_t)p.n_out * sizeof(double) : 0;
     p.at_zero = p.at_acc = mxf_piece(cv, p.zero_bytes);
+    p.bytes = cv.off;
+    return p;
+}
+
+// ---- nearest.hip -------------------------------------------------------------------------------------------------------------------------
+constexpr int NEAREST_RB = 128;     // rows (threads) per workgroup
+
+struct NearestRequest {
+    size_t esize = 4; bool step = false;      // step: mxf_kmeans_step, else mxf_nearest
+    int64_t N = 0, M = 0; int Q = 0;
+    bool has_X = false, has_C = false, has_idx = false;                                      // idx is required by mxf_nearest only
+    bool has_Cnew = false, has_counts = false, has_inertia = false, alias = false;          // step; alias: C_new == C
+};
+// Scratch: the centres padded to QP (cp), then for a step the zeroed accumulators back to back: M QP double sums, M 64-bit counts and
+// the inertia, [at_zero, at_zero + zero_bytes).  An absent piece has offset 0.
+struct NearestPlan : FusedRefusal {
+    int qp = 0;
+    unsigned grid = 1;                  // of nearest_kernel: blocks of NEAREST_RB rows; M is not split
+    int64_t n_prep = 0, n_close = 0;    // items of nearest_prep_kernel (M) and of kmeans_close_kernel (M, step only)
+    size_t at_cp = 0, at_sums = 0, at_counts = 0, at_inertia = 0, at_zero = 0, zero_bytes = 0, bytes = 0;
+};
+
+static inline NearestPlan nearest_plan(const NearestRequest& r) {
+    NearestPlan p;
+    if (r.N < 1 || r.M < 1 || r.Q < 1) { p.refuse(-2, "N, M, Q >= 1"); return p; }
+    if (r.Q > MXF_NEAREST_MAX_Q) { p.refuse_q(r.Q, MXF_NEAREST_MAX_Q); return p; }
+    if (r.N > ((int64_t)1 << 31) || r.M > ((int64_t)1 << 31) - 1) { p.refuse(-2, "N <= 2^31, M <= 2^31 - 1"); return p; }
+    if (!r.has_X || !r.has_C) { p.refuse(-2, "null X or C"); return p; }
+    if (r.step) {
+        if (!r.has_Cnew || !r.has_counts || !r.has_inertia) { p.refuse(-2, "null C_new, counts or inertia"); return p; }
+        if (r.alias) { p.refuse(-2, "C_new must not alias C"); return p; }
+    } else if (!r.has_idx) { p.refuse(-2, "null idx"); return p; }
+    p.qp = mxf_qp(r.Q);
+    p.grid = (unsigned)mxf_cdiv(r.N, NEAREST_RB);
+    p.n_prep = r.M;
+    Carver cv(nullptr);
+    p.at_cp = mxf_piece(cv, (size_t)r.M * p.qp * r.esize);
+    if (r.step) {
+        p.n_close = r.M;
+        p.at_zero = cv.off;
+        p.at_sums = mxf_piece(cv, (size_t)r.M * p.qp * sizeof(double));
+        p.at_counts = mxf_piece(cv, (size_t)r.M * sizeof(int64_t));
+        p.at_inertia = mxf_piece(cv, sizeof(double));
+        p.zero_bytes = cv.off - p.at_zero;
+    }
     p.bytes = cv.off;
     return p;
 }

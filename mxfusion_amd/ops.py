@@ -849,7 +849,41 @@ class KernelMatvec(torch.autograd.Function):
         return None, None, None, None, dls, dvar, dV, None
 
 
-MVN_MAX_ORDER = 32     # the order up to which the mxf_mvn_* entry points run (MVN_MAX of mvn.hip)
+def _nearest_operands(what, X, C):
+    """(N, M, Q) of the nearest-centre assignment: X (N, Q) and the centres C (M, Q), no sample axis"""
+    _same_kind(what, X, C, contiguous=True)
+    if X.dim() != 2 or C.dim() != 2 or C.shape[1] != X.shape[1]:
+        raise ValueError('%s: X is (N, Q) and C (M, Q); got %s, %s' % (what, tuple(X.shape), tuple(C.shape)))
+    N, M, Q = int(X.shape[0]), int(C.shape[0]), int(X.shape[1])
+    if min(N, M, Q) < 1:
+        raise ValueError('%s: N, M and Q must be at least 1; got %d, %d, %d' % (what, N, M, Q))
+    return N, M, Q
+
+
+def nearest(X, C, want_d2=True):
+    """(idx, d2): idx (N,) int32, idx[n] = argmin_m |X[n] - C[m]|^2 with the smallest index among exact ties, and d2 (N,) that minimum
+    (None without want_d2); the N x M distances are never stored (mxf_nearest).  X (N, Q), C (M, Q).  No reverse mode."""
+    N, M, Q = _nearest_operands('nearest centre', X, C)
+    idx = torch.empty((N,), dtype=torch.int32, device=X.device)
+    d2 = torch.empty((N,), dtype=X.dtype, device=X.device) if want_d2 else None
+    _lib.call('mxf_nearest', _h(X), _dt(X), N, M, Q, _p(X), _p(C), _p(idx), _p(d2), _stream())
+    return idx, d2
+
+
+def kmeans_step(X, C):
+    """(C_new, idx, counts, inertia) of one Lloyd iteration in one call (mxf_kmeans_step): C_new (M, Q) the means of the rows assigned to each
+    centre (C[m] itself where none is), idx (N,) int32 the assignment, counts (M,) int64 and inertia, a 0-d float64 device tensor, the sum
+    of the squared distances to the assigned centres.  X (N, Q), C (M, Q).  No reverse mode."""
+    N, M, Q = _nearest_operands('k-means step', X, C)
+    C_new = torch.empty_like(C)
+    idx = torch.empty((N,), dtype=torch.int32, device=X.device)
+    counts = torch.empty((M,), dtype=torch.int64, device=X.device)
+    inertia = torch.empty((), dtype=torch.float64, device=X.device)
+    _lib.call('mxf_kmeans_step', _h(X), _dt(X), N, M, Q, _p(X), _p(C), _p(C_new), _p(idx), _p(counts), _p(inertia), _stream())
+    return C_new, idx, counts, inertia
+
+
+MVN_MAX_ORDER = 32    # the order up to which the mxf_mvn_* entry points run (MVN_MAX of mvn.hip)
 
 
 def _mvn_rows(x, mean):
