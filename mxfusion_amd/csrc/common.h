@@ -9,6 +9,7 @@
 #include <limits.h>
 #include <type_traits>
 #include "../../include/mxf_gp.h"
+#include "pointwise_plan.h"      // grid_for, grid_for_reduce
 
 // Tuning knobs: numbers of the shipped path (grid sizes, periods, block sizes), instruments, and shapes a test forces.  The shipped library
 // is built WITHOUT -DMXF_PROBES: every knob is its compile-time default and the library reads no MXF_* environment variable except
@@ -228,6 +229,20 @@ int dispatch(int v, F&& f) {
 }
 // the element type of a dtype tag: dispatch<MXF_F32, MXF_F64>(dtype, [&](auto dt) { using T = mxf_elem_t<decltype(dt)::value>; ... })
 template <int DTYPE> using mxf_elem_t = std::conditional_t<DTYPE == MXF_F64, double, float>;
+// The pointwise and per-row launchers (elementwise.hip .. transform.hip): launch(T()) with the element type of `dtype`, each launch written
+// once in T.  An unknown dtype is the family's refusal; a launcher that returns non-zero has refused itself; otherwise the launch is checked.
+static inline int mxf_bad_dtype(mxf_handle h, const char* name, int dtype) { MXF_FAIL(h, -2, "%s: bad dtype %d", name, dtype); }
+template <typename F>
+int mxf_typed(mxf_handle h, const char* name, int dtype, F&& launch) {
+    const int rc = dispatch<MXF_F32, MXF_F64>(dtype, [&](auto dt) {
+        using T = mxf_elem_t<decltype(dt)::value>;
+        if constexpr (std::is_void_v<decltype(launch(T()))>) { launch(T()); return 0; } else return launch(T());
+    });
+    if (rc == NO_CASE) return mxf_bad_dtype(h, name, dtype);
+    if (rc) return rc;
+    MXF_LAUNCH_CHECK(h);
+    return 0;
+}
 
 // ---- device helpers -------------------------------------------------------------------------
 template <typename T> struct Vec16;   // 16-byte vector of T
@@ -345,23 +360,6 @@ __device__ __forceinline__ void atomic_add(double* p, double v) { unsafeAtomicAd
 // the same into LDS (workgroup scope)
 __device__ __forceinline__ void lds_add(float* p, float v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void lds_add(double* p, double v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-
-// kernels that end in ONE same-address atomic per workgroup (the scalar sums of normal_logpdf_kernel and univariate_logpdf_kernel): 2048 of them serialise at the L2
-// (~15 ns apiece: 33 us for the 2 M-element log-pdf of a 4-sample step, of which the data take 6) -- two workgroups per CU
-static inline unsigned grid_for_reduce(int64_t n) {
-    int64_t b = (n + 255) / 256;
-    if (b < 1) b = 1;
-    if (b > 512) b = 512;
-    return (unsigned)b;
-}
-
-// grid-stride elementwise kernels without such an atomic
-static inline unsigned grid_for(int64_t n) {
-    int64_t b = (n + 255) / 256;
-    if (b < 1) b = 1;
-    if (b > 2048) b = 2048;
-    return (unsigned)b;
-}
 
 // C-ABI entry points implemented across translation units share these internal (typed) launchers
 

@@ -18,7 +18,6 @@
 
 namespace {
 
-constexpr int DENSE_MAX = 128;      // widths
 constexpr int FWD_OC = 32;          // forward: output columns per chunk of W
 constexpr int BWD_OC = 16;          // reverse: rows of W per chunk
 
@@ -189,85 +188,49 @@ struct DenseCall {
     const void* X; int64_t ldx, ss_x;
     const void* W; int64_t ss_w;
     const void* b; int64_t ss_b;
+    const void* Y;                  // the output of the forward pass, an operand of the reverse pass
+    const void* dY; void *dX, *dW, *db;
 };
 
-// the checks that do not depend on the operands; S <= 0 or N <= 0 is the caller's to return 0 on after them
-int check_head(mxf_handle h, const DenseCall& c) {
-    if (c.dtype != MXF_F32 && c.dtype != MXF_F64) MXF_FAIL(h, -2, "%s: bad dtype %d", c.name, c.dtype);
-    if (c.I < 1 || c.O < 1 || c.I > DENSE_MAX || c.O > DENSE_MAX)
-        MXF_FAIL(h, -3, "%s: widths I = %d, O = %d; 1 .. %d are supported", c.name, c.I, c.O, DENSE_MAX);
-    if (c.act < 0 || c.act > 3) MXF_FAIL(h, -2, "%s: activation %d (0 identity, 1 tanh, 2 relu, 3 sigmoid)", c.name, c.act);
-    return 0;
-}
-
-int check_operands(mxf_handle h, const DenseCall& c, int64_t* tiles, int tile_rows) {
-    if (!c.X || !c.W) MXF_FAIL(h, -2, "%s: null operand", c.name);
-    if (c.ldx < c.I) MXF_FAIL(h, -2, "%s: ldx = %lld < I = %d", c.name, (long long)c.ldx, c.I);
-    if (c.ss_x != 0 && c.ss_x < (c.N - 1) * c.ldx + c.I)
-        MXF_FAIL(h, -2, "%s: the sample stride of X is 0 or at least (N - 1) ldx + I = %lld, got %lld", c.name,
-                 (long long)((c.N - 1) * c.ldx + c.I), (long long)c.ss_x);
-    if (c.ss_w != 0 && c.ss_w != (int64_t)c.O * c.I)
-        MXF_FAIL(h, -2, "%s: the sample stride of W is 0 or O I = %d (dense), got %lld", c.name, c.O * c.I, (long long)c.ss_w);
-    if (c.ss_b != 0 && c.ss_b != c.O) MXF_FAIL(h, -2, "%s: the sample stride of b is 0 or O = %d, got %lld", c.name, c.O, (long long)c.ss_b);
-    *tiles = (c.N + tile_rows - 1) / tile_rows;
-    if (*tiles * c.S > 0x7fffffffLL) MXF_FAIL(h, -2, "%s: %lld row tiles x %d samples exceed the grid", c.name, (long long)*tiles, c.S);
-    return 0;
-}
-
 template <typename T>
-DenseArgs<T> args_of(const DenseCall& c, int64_t tiles) {
-    return {c.S, c.N, c.I, c.O, c.act, (const T*)c.X, c.ldx, c.ss_x, (const T*)c.W, c.ss_w, (const T*)c.b, c.ss_b, tiles};
-}
-
-template <typename T>
-int launch_fwd(mxf_handle h, const DenseCall& c, void* Y, hipStream_t st) {
-    int64_t tiles;
-    if (int rc = check_operands(h, c, &tiles, DenseTile<T>::rows)) return rc;
-    hipLaunchKernelGGL(dense_fwd_kernel<T>, dim3((unsigned)(tiles * c.S)), dim3(256), 0, st, args_of<T>(c, tiles), (T*)Y);
-    return 0;
-}
-
-template <typename T>
-int launch_bwd(mxf_handle h, const DenseCall& c, const void* Y, const void* dY, void* dX, void* dW, void* db, hipStream_t st) {
-    int64_t tiles;
-    if (int rc = check_operands(h, c, &tiles, DenseTile<T>::rows)) return rc;
-    const bool by_rows = dX && c.ss_x == 0 && c.S > 1;
+int launch(mxf_handle h, const DenseCall& c, const DensePlan& p, bool bwd, hipStream_t st) {
+    static_assert(DenseTile<float>::rows == 32 && DenseTile<double>::rows == 16, "dense_tile_rows (pointwise_plan.h) holds the tile heights");
+    const DenseArgs<T> a = {.S = c.S, .N = c.N, .I = c.I, .O = c.O, .act = c.act, .X = (const T*)c.X, .ldx = c.ldx, .ss_x = c.ss_x, .W = (const T*)c.W,
+                            .ss_w = c.ss_w, .b = (const T*)c.b, .ss_b = c.ss_b, .tiles = p.tiles};
+    if (!bwd) {
+        hipLaunchKernelGGL(dense_fwd_kernel<T>, dim3(p.grid), dim3(256), 0, st, a, (T*)c.Y);
+        return 0;
+    }
     SharedSums sums;          // dW and db are sums over the row tiles: in double whenever they are wanted, shared over s or not
-    if (int rc = shared_sums_open<T>(h, c.name, {{dW, shared_numel(c.ss_w, true, c.S, 1, (int64_t)c.O * c.I)}, {db, shared_numel(c.ss_b, true, c.S, 1, c.O)}},
-                                     st, &sums))
-        return rc;
-    hipLaunchKernelGGL(dense_bwd_kernel<T>, dim3((unsigned)(by_rows ? tiles : tiles * c.S)), dim3(256), 0, st, args_of<T>(c, tiles),
-                       (const T*)Y, (const T*)dY, (T*)dX, sums.acc[0], sums.acc[1], by_rows ? 1 : 0);
+    if (int rc = shared_sums_open<T>(h, c.name, {{c.dW, p.n_dw}, {c.db, p.n_db}}, st, &sums)) return rc;
+    hipLaunchKernelGGL(dense_bwd_kernel<T>, dim3(p.grid), dim3(256), 0, st, a, (const T*)c.Y, (const T*)c.dY, (T*)c.dX, sums.acc[0], sums.acc[1], p.by_rows ? 1 : 0);
     shared_sums_close(sums, st);
     return 0;
+}
+
+int run(mxf_handle h, const DenseCall& c, bool bwd, void* stream) {
+    if (!h) return -1;
+    const DensePlan p = dense_plan({.dtype = c.dtype, .bwd = bwd, .S = c.S, .N = c.N, .I = c.I, .O = c.O, .act = c.act, .ldx = c.ldx, .ss_x = c.ss_x,
+                                    .ss_w = c.ss_w, .ss_b = c.ss_b, .has_X = c.X != nullptr, .has_W = c.W != nullptr, .has_Y = c.Y != nullptr,
+                                    .has_dY = c.dY != nullptr, .has_dX = c.dX != nullptr, .has_dW = c.dW != nullptr, .has_db = c.db != nullptr});
+    if (p.rc) MXF_FAIL(h, p.rc, "%s: %s", c.name, p.refusal);
+    if (p.empty) return 0;
+    return mxf_typed(h, c.name, c.dtype, [&](auto t) { return launch<decltype(t)>(h, c, p, bwd, (hipStream_t)stream); });
 }
 
 }  // namespace
 
 extern "C" int mxf_dense_fwd(mxf_handle h, int dtype, int S, int64_t N, int I, int O, int act, const void* X, int64_t ldx, int64_t strideS_x,
                              const void* W, int64_t strideS_w, const void* b, int64_t strideS_b, void* Y, void* stream) {
-    if (!h) return -1;
-    const DenseCall c = {"mxf_dense_fwd", dtype, S, N, I, O, act, X, ldx, strideS_x, W, strideS_w, b, b ? strideS_b : 0};
-    if (int rc = check_head(h, c)) return rc;
-    if (S <= 0 || N <= 0) return 0;
-    if (!Y) MXF_FAIL(h, -2, "%s: null Y", c.name);
-    if (int rc = dtype == MXF_F32 ? launch_fwd<float>(h, c, Y, (hipStream_t)stream) : launch_fwd<double>(h, c, Y, (hipStream_t)stream)) return rc;
-    MXF_LAUNCH_CHECK(h);
-    return 0;
+    const DenseCall c = {.name = "mxf_dense_fwd", .dtype = dtype, .S = S, .N = N, .I = I, .O = O, .act = act, .X = X, .ldx = ldx, .ss_x = strideS_x,
+                         .W = W, .ss_w = strideS_w, .b = b, .ss_b = b ? strideS_b : 0, .Y = Y};
+    return run(h, c, false, stream);
 }
 
 extern "C" int mxf_dense_bwd(mxf_handle h, int dtype, int S, int64_t N, int I, int O, int act, const void* X, int64_t ldx, int64_t strideS_x,
                              const void* W, int64_t strideS_w, int64_t strideS_b, const void* Y, const void* dY, void* dX_acc, void* dW_acc,
                              void* db_acc, void* stream) {
-    if (!h) return -1;
-    const DenseCall c = {"mxf_dense_bwd", dtype, S, N, I, O, act, X, ldx, strideS_x, W, strideS_w, nullptr, strideS_b};
-    if (int rc = check_head(h, c)) return rc;
-    if (S <= 0 || N <= 0) return 0;
-    if (!Y || !dY) MXF_FAIL(h, -2, "%s: null Y or dY", c.name);
-    if (!dX_acc && !dW_acc && !db_acc) return 0;
-    if (int rc = dtype == MXF_F32 ? launch_bwd<float>(h, c, Y, dY, dX_acc, dW_acc, db_acc, (hipStream_t)stream)
-                                  : launch_bwd<double>(h, c, Y, dY, dX_acc, dW_acc, db_acc, (hipStream_t)stream))
-        return rc;
-    MXF_LAUNCH_CHECK(h);
-    return 0;
+    const DenseCall c = {.name = "mxf_dense_bwd", .dtype = dtype, .S = S, .N = N, .I = I, .O = O, .act = act, .X = X, .ldx = ldx, .ss_x = strideS_x,
+                         .W = W, .ss_w = strideS_w, .ss_b = strideS_b, .Y = Y, .dY = dY, .dX = dX_acc, .dW = dW_acc, .db = db_acc};
+    return run(h, c, true, stream);
 }

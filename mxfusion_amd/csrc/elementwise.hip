@@ -181,51 +181,42 @@ __global__ void diag_of_kernel(int64_t total, int64_t n, const T* __restrict__ g
 
 }  // namespace
 
-#define DISPATCH(h, dtype, name, CALLF, CALLD)             \
-    do {                                                   \
-        if (dtype == MXF_F32) { CALLF; }                   \
-        else if (dtype == MXF_F64) { CALLD; }              \
-        else MXF_FAIL(h, -2, name ": bad dtype %d", dtype); \
-        MXF_LAUNCH_CHECK(h);                               \
-        return 0;                                          \
-    } while (0)
-
 extern "C" int mxf_softplus_fwd(mxf_handle h, int dtype, int64_t n, const void* x, void* y, void* stream) {
     if (!h) return -1;
     if (n <= 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    DISPATCH(h, dtype, "mxf_softplus_fwd",
-             hipLaunchKernelGGL((softplus_fwd_kernel<float>), dim3(grid_for(n)), dim3(256), 0, st, n, (const float*)x, (float*)y),
-             hipLaunchKernelGGL((softplus_fwd_kernel<double>), dim3(grid_for(n)), dim3(256), 0, st, n, (const double*)x, (double*)y));
+    return mxf_typed(h, "mxf_softplus_fwd", dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((softplus_fwd_kernel<T>), dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, n, (const T*)x, (T*)y);
+    });
 }
 
 extern "C" int mxf_softplus_bwd(mxf_handle h, int dtype, int64_t n, const void* x, const void* dy, void* dx_acc, void* stream) {
     if (!h) return -1;
     if (n <= 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    DISPATCH(h, dtype, "mxf_softplus_bwd",
-             hipLaunchKernelGGL((softplus_bwd_kernel<float>), dim3(grid_for(n)), dim3(256), 0, st, n, (const float*)x, (const float*)dy, (float*)dx_acc),
-             hipLaunchKernelGGL((softplus_bwd_kernel<double>), dim3(grid_for(n)), dim3(256), 0, st, n, (const double*)x, (const double*)dy, (double*)dx_acc));
+    return mxf_typed(h, "mxf_softplus_bwd", dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((softplus_bwd_kernel<T>), dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, n, (const T*)x, (const T*)dy, (T*)dx_acc);
+    });
 }
 
 extern "C" int mxf_normal_reparam(mxf_handle h, int dtype, int S, int64_t n, const void* mean, const void* var, const void* eps,
                                   void* x, void* stream) {
     if (!h) return -1;
     if (n <= 0 || S <= 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    DISPATCH(h, dtype, "mxf_normal_reparam",
-             hipLaunchKernelGGL((reparam_kernel<float>), dim3(grid_for(n)), dim3(256), 0, st, S, n, (const float*)mean, (const float*)var, (const float*)eps, (float*)x),
-             hipLaunchKernelGGL((reparam_kernel<double>), dim3(grid_for(n)), dim3(256), 0, st, S, n, (const double*)mean, (const double*)var, (const double*)eps, (double*)x));
+    return mxf_typed(h, "mxf_normal_reparam", dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((reparam_kernel<T>), dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, S, n, (const T*)mean, (const T*)var, (const T*)eps, (T*)x);
+    });
 }
 
 extern "C" int mxf_normal_reparam_bwd(mxf_handle h, int dtype, int S, int64_t n, const void* var, const void* eps, const void* dx,
                                       void* dmean_acc, void* dvar_acc, void* stream) {
     if (!h) return -1;
     if (n <= 0 || S <= 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    DISPATCH(h, dtype, "mxf_normal_reparam_bwd",
-             hipLaunchKernelGGL((reparam_bwd_kernel<float>), dim3(grid_for(n)), dim3(256), 0, st, S, n, (const float*)var, (const float*)eps, (const float*)dx, (float*)dmean_acc, (float*)dvar_acc),
-             hipLaunchKernelGGL((reparam_bwd_kernel<double>), dim3(grid_for(n)), dim3(256), 0, st, S, n, (const double*)var, (const double*)eps, (const double*)dx, (double*)dmean_acc, (double*)dvar_acc));
+    return mxf_typed(h, "mxf_normal_reparam_bwd", dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((reparam_bwd_kernel<T>), dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, S, n, (const T*)var, (const T*)eps, (const T*)dx, (T*)dmean_acc, (T*)dvar_acc);
+    });
 }
 
 extern "C" int mxf_normal_reparam_prec(mxf_handle h, int dtype, int S, int64_t n, const void* mean, const void* precision, const void* eps,
@@ -233,10 +224,10 @@ extern "C" int mxf_normal_reparam_prec(mxf_handle h, int dtype, int S, int64_t n
     if (!h) return -1;
     if (n <= 0 || S <= 0) return 0;
     if (!mean || !precision || !eps || !x) MXF_FAIL(h, -2, "mxf_normal_reparam_prec: null argument");
-    hipStream_t st = (hipStream_t)stream;
-    DISPATCH(h, dtype, "mxf_normal_reparam_prec",
-             hipLaunchKernelGGL((reparam_prec_kernel<float>), dim3(grid_for(n)), dim3(256), 0, st, S, n, (const float*)mean, (const float*)precision, (const float*)eps, (float*)x),
-             hipLaunchKernelGGL((reparam_prec_kernel<double>), dim3(grid_for(n)), dim3(256), 0, st, S, n, (const double*)mean, (const double*)precision, (const double*)eps, (double*)x));
+    return mxf_typed(h, "mxf_normal_reparam_prec", dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((reparam_prec_kernel<T>), dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, S, n, (const T*)mean, (const T*)precision, (const T*)eps, (T*)x);
+    });
 }
 
 extern "C" int mxf_normal_reparam_prec_bwd(mxf_handle h, int dtype, int S, int64_t n, const void* precision, const void* eps, const void* dx,
@@ -244,10 +235,11 @@ extern "C" int mxf_normal_reparam_prec_bwd(mxf_handle h, int dtype, int S, int64
     if (!h) return -1;
     if (n <= 0 || S <= 0) return 0;
     if (!precision || !eps || !dx) MXF_FAIL(h, -2, "mxf_normal_reparam_prec_bwd: null argument");
-    hipStream_t st = (hipStream_t)stream;
-    DISPATCH(h, dtype, "mxf_normal_reparam_prec_bwd",
-             hipLaunchKernelGGL((reparam_prec_bwd_kernel<float>), dim3(grid_for(n)), dim3(256), 0, st, S, n, (const float*)precision, (const float*)eps, (const float*)dx, (float*)dmean_acc, (float*)dprecision_acc),
-             hipLaunchKernelGGL((reparam_prec_bwd_kernel<double>), dim3(grid_for(n)), dim3(256), 0, st, S, n, (const double*)precision, (const double*)eps, (const double*)dx, (double*)dmean_acc, (double*)dprecision_acc));
+    return mxf_typed(h, "mxf_normal_reparam_prec_bwd", dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((reparam_prec_bwd_kernel<T>), dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, S, n, (const T*)precision, (const T*)eps,
+                           (const T*)dx, (T*)dmean_acc, (T*)dprecision_acc);
+    });
 }
 
 extern "C" int mxf_normal_logpdf(mxf_handle h, int dtype, int S, int64_t n, const void* x, const void* mean, int64_t n_mean,
@@ -256,26 +248,25 @@ extern "C" int mxf_normal_logpdf(mxf_handle h, int dtype, int S, int64_t n, cons
     if (!h) return -1;
     if (n <= 0 || S <= 0) return 0;
     if ((n_mean != 1 && n_mean != n) || (n_var != 1 && n_var != n)) MXF_FAIL(h, -2, "mxf_normal_logpdf: mean/var must have 1 or n elements");
-    hipStream_t st = (hipStream_t)stream;
-    DISPATCH(h, dtype, "mxf_normal_logpdf",
-             hipLaunchKernelGGL((normal_logpdf_kernel<float>), dim3(grid_for_reduce(n)), dim3(256), 0, st, S, n, (const float*)x, (const float*)mean, n_mean, (const float*)var, n_var, (float)scale, (float*)out_acc, (float*)dx_acc, (float*)dmean_acc, (float*)dvar_acc),
-             hipLaunchKernelGGL((normal_logpdf_kernel<double>), dim3(grid_for_reduce(n)), dim3(256), 0, st, S, n, (const double*)x, (const double*)mean, n_mean, (const double*)var, n_var, scale, (double*)out_acc, (double*)dx_acc, (double*)dmean_acc, (double*)dvar_acc));
+    return mxf_typed(h, "mxf_normal_logpdf", dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((normal_logpdf_kernel<T>), dim3(grid_for_reduce(n)), dim3(256), 0, (hipStream_t)stream, S, n, (const T*)x, (const T*)mean,
+                           n_mean, (const T*)var, n_var, (T)scale, (T*)out_acc, (T*)dx_acc, (T*)dmean_acc, (T*)dvar_acc);
+    });
 }
 
 // the per-sample sums and their reverse mode: univariate_ps_kernel / univariate_logpdf_kernel (unidist.h) with the Normal's evaluation struct
 static int normal_ps_run(mxf_handle h, const char* name, int dtype, const UniArgs& u, int mode, void* stream) {
     if (const int rc = uni_check(h, name, dtype, u)) return rc < 0 ? rc : 0;
-    if (dtype == MXF_F32) uni_launch_kind<float, MXF_D_NORMAL_>(u, mode, (hipStream_t)stream);
-    else uni_launch_kind<double, MXF_D_NORMAL_>(u, mode, (hipStream_t)stream);
-    MXF_LAUNCH_CHECK(h);
-    return 0;
+    return mxf_typed(h, name, dtype, [&](auto t) { uni_launch_kind<decltype(t), MXF_D_NORMAL_>(u, mode, (hipStream_t)stream); });
 }
 
 extern "C" int mxf_normal_logpdf_ps(mxf_handle h, int dtype, int S, int64_t n, const void* x, const void* mean, int64_t n_mean,
                                     int64_t strideS_mean, const void* var, int64_t n_var, int64_t strideS_var, double scale, void* out_acc,
                                     void* stream) {
     if (h && n > 0 && S > 0 && !out_acc) MXF_FAIL(h, -2, "mxf_normal_logpdf_ps: null out");
-    const UniArgs u = {S, n, x, mean, n_mean, strideS_mean, var, n_var, strideS_var, scale, nullptr, 0, 0, out_acc, nullptr, nullptr, nullptr};
+    const UniArgs u = {.S = S, .n = n, .x = x, .a = mean, .n_a = n_mean, .ss_a = strideS_mean, .b = var, .n_b = n_var, .ss_b = strideS_var,
+                       .scale = scale, .out = out_acc};
     return normal_ps_run(h, "mxf_normal_logpdf_ps", dtype, u, UNI_PER_SAMPLE, stream);
 }
 
@@ -283,7 +274,8 @@ extern "C" int mxf_normal_logpdf_ps_bwd(mxf_handle h, int dtype, int S, int64_t 
                                         int64_t strideS_mean, const void* var, int64_t n_var, int64_t strideS_var, const void* w, double scale,
                                         void* dx_acc, void* dmean_acc, void* dvar_acc, void* stream) {
     if (h && n > 0 && S > 0 && !w) MXF_FAIL(h, -2, "mxf_normal_logpdf_ps_bwd: null weights");
-    const UniArgs u = {S, n, x, mean, n_mean, strideS_mean, var, n_var, strideS_var, scale, w, 1, 0, nullptr, dx_acc, dmean_acc, dvar_acc};
+    const UniArgs u = {.S = S, .n = n, .x = x, .a = mean, .n_a = n_mean, .ss_a = strideS_mean, .b = var, .n_b = n_var, .ss_b = strideS_var,
+                       .scale = scale, .cot = w, .cs_s = 1, .cs_i = 0, .dx = dx_acc, .da = dmean_acc, .db = dvar_acc};
     return normal_ps_run(h, "mxf_normal_logpdf_ps_bwd", dtype, u, UNI_REDUCED, stream);
 }
 
@@ -292,11 +284,12 @@ extern "C" int mxf_adam_step(mxf_handle h, int dtype, int64_t n, void* w, const 
     if (!h) return -1;
     if (n <= 0) return 0;
     if (t < 1) MXF_FAIL(h, -2, "mxf_adam_step: t must be >= 1");
-    hipStream_t st = (hipStream_t)stream;
     const double lr_t = lr * sqrt(1.0 - pow(beta2, (double)t)) / (1.0 - pow(beta1, (double)t));
-    DISPATCH(h, dtype, "mxf_adam_step",
-             hipLaunchKernelGGL((adam_kernel<float>), dim3(grid_for(n)), dim3(256), 0, st, n, (float*)w, (const float*)g, (float*)m, (float*)v, (float)lr_t, (float)beta1, (float)beta2, (float)epsilon, (float)rescale_grad),
-             hipLaunchKernelGGL((adam_kernel<double>), dim3(grid_for(n)), dim3(256), 0, st, n, (double*)w, (const double*)g, (double*)m, (double*)v, lr_t, beta1, beta2, epsilon, rescale_grad));
+    return mxf_typed(h, "mxf_adam_step", dtype, [&](auto e) {
+        using T = decltype(e);
+        hipLaunchKernelGGL((adam_kernel<T>), dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, n, (T*)w, (const T*)g, (T*)m, (T*)v, (T)lr_t, (T)beta1,
+                           (T)beta2, (T)epsilon, (T)rescale_grad);
+    });
 }
 
 // out[0] = sum_i g[i] if all g[i] agree to 1e-6 relative, NaN otherwise (n small: the upstream gradient of the per-sample log-pdfs)
@@ -316,10 +309,10 @@ __global__ __launch_bounds__(64) void uniform_sum_kernel(int64_t n, const T* __r
 extern "C" int mxf_uniform_sum(mxf_handle h, int dtype, int64_t n, const void* g, void* out, void* stream) {
     if (!h) return -1;
     if (n <= 0 || !g || !out) MXF_FAIL(h, -2, "mxf_uniform_sum: bad argument");
-    hipStream_t st = (hipStream_t)stream;
-    DISPATCH(h, dtype, "mxf_uniform_sum",
-             hipLaunchKernelGGL((uniform_sum_kernel<float>), dim3(1), dim3(64), 0, st, n, (const float*)g, (float*)out),
-             hipLaunchKernelGGL((uniform_sum_kernel<double>), dim3(1), dim3(64), 0, st, n, (const double*)g, (double*)out));
+    return mxf_typed(h, "mxf_uniform_sum", dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((uniform_sum_kernel<T>), dim3(1), dim3(64), 0, (hipStream_t)stream, n, (const T*)g, (T*)out);
+    });
 }
 
 // MXNet SGD (optimizer 'sgd' of gluon.Trainer): g = rescale * grad + wd * w; momentum == 0: w -= lr g; else mom = momentum mom - lr g, w += mom
@@ -336,10 +329,10 @@ extern "C" int mxf_sgd_step(mxf_handle h, int dtype, int64_t n, void* w, const v
                             double rescale_grad, void* stream) {
     if (!h) return -1;
     if (n <= 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    DISPATCH(h, dtype, "mxf_sgd_step",
-             hipLaunchKernelGGL((sgd_kernel<float>), dim3(grid_for(n)), dim3(256), 0, st, n, (float*)w, (const float*)g, (float*)mom, (float)lr, (float)momentum, (float)wd, (float)rescale_grad),
-             hipLaunchKernelGGL((sgd_kernel<double>), dim3(grid_for(n)), dim3(256), 0, st, n, (double*)w, (const double*)g, (double*)mom, lr, momentum, wd, rescale_grad));
+    return mxf_typed(h, "mxf_sgd_step", dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((sgd_kernel<T>), dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, n, (T*)w, (const T*)g, (T*)mom, (T)lr, (T)momentum, (T)wd, (T)rescale_grad);
+    });
 }
 
 // The other optimisers gluon.Trainer is commonly driven with by name (batch_loop.py:46-49 hands `optimizer` to the Trainer): MXNet's
@@ -385,54 +378,45 @@ extern "C" int mxf_opt_step(mxf_handle h, int kind, int dtype, int64_t n, void* 
     if (!h) return -1;
     if (n <= 0) return 0;
     if (!w || !g || !s1 || (kind == MXF_OPT_ADADELTA && !s2)) MXF_FAIL(h, -2, "mxf_opt_step: null argument");
-    hipStream_t st = (hipStream_t)stream;
-#define OPT_GO(K)                                                                                                                              \
-    DISPATCH(h, dtype, "mxf_opt_step",                                                                                                          \
-             hipLaunchKernelGGL((opt_kernel<float, K>), dim3(grid_for(n)), dim3(256), 0, st, n, (float*)w, (const float*)g, (float*)s1, (float*)s2, (float)lr, (float)p1, (float)epsilon, (float)wd, (float)rescale_grad), \
-             hipLaunchKernelGGL((opt_kernel<double, K>), dim3(grid_for(n)), dim3(256), 0, st, n, (double*)w, (const double*)g, (double*)s1, (double*)s2, lr, p1, epsilon, wd, rescale_grad))
-    switch (kind) {
-        case MXF_OPT_RMSPROP: OPT_GO(MXF_OPT_RMSPROP);
-        case MXF_OPT_ADAGRAD: OPT_GO(MXF_OPT_ADAGRAD);
-        case MXF_OPT_ADADELTA: OPT_GO(MXF_OPT_ADADELTA);
-        case MXF_OPT_NAG: OPT_GO(MXF_OPT_NAG);
-    }
-#undef OPT_GO
-    MXF_FAIL(h, -2, "mxf_opt_step: unknown optimiser kind %d", kind);
+    const int rc = dispatch<MXF_OPT_RMSPROP, MXF_OPT_ADAGRAD, MXF_OPT_ADADELTA, MXF_OPT_NAG>(kind, [&](auto k) {
+        return mxf_typed(h, "mxf_opt_step", dtype, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((opt_kernel<T, decltype(k)::value>), dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, n, (T*)w, (const T*)g, (T*)s1,
+                               (T*)s2, (T)lr, (T)p1, (T)epsilon, (T)wd, (T)rescale_grad);
+        });
+    });
+    if (rc == NO_CASE) MXF_FAIL(h, -2, "mxf_opt_step: unknown optimiser kind %d", kind);
+    return rc;
 }
 
 extern "C" int mxf_coldot(mxf_handle h, int dtype, int S, int64_t M, int64_t N, const void* A, int64_t lda, int64_t strideS_A,
                           const void* B, int64_t ldb, int64_t strideS_B, void* out, void* stream) {
     if (!h) return -1;
     if (S <= 0 || N <= 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    dim3 g((unsigned)((N + 255) / 256), (unsigned)S);
-    if ((int64_t)S * N < 16384 && M >= 64) {
-        dim3 gs((unsigned)((N + 15) / 16), (unsigned)S);
-        DISPATCH(h, dtype, "mxf_coldot",
-                 hipLaunchKernelGGL((coldot_small_kernel<float>), gs, dim3(256), 0, st, M, N, (const float*)A, lda, strideS_A, (const float*)B, ldb, strideS_B, (float*)out),
-                 hipLaunchKernelGGL((coldot_small_kernel<double>), gs, dim3(256), 0, st, M, N, (const double*)A, lda, strideS_A, (const double*)B, ldb, strideS_B, (double*)out));
-    }
-    DISPATCH(h, dtype, "mxf_coldot",
-             hipLaunchKernelGGL((coldot_kernel<float>), g, dim3(256), 0, st, M, N, (const float*)A, lda, strideS_A, (const float*)B, ldb, strideS_B, (float*)out),
-             hipLaunchKernelGGL((coldot_kernel<double>), g, dim3(256), 0, st, M, N, (const double*)A, lda, strideS_A, (const double*)B, ldb, strideS_B, (double*)out));
+    const ColdotPlan p = coldot_plan(S, M, N);      // (pointwise_plan.h)
+    return mxf_typed(h, "mxf_coldot", dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((p.small ? coldot_small_kernel<T> : coldot_kernel<T>), dim3(p.grid[0], p.grid[1]), dim3(256), 0, (hipStream_t)stream, M, N,
+                           (const T*)A, lda, strideS_A, (const T*)B, ldb, strideS_B, (T*)out);
+    });
 }
 
 extern "C" int mxf_make_diagonal(mxf_handle h, int dtype, int64_t batch, int64_t n, const void* a, void* out, void* stream) {
     if (!h) return -1;
     if (batch <= 0 || n <= 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
     const int64_t total = batch * n * n;
-    DISPATCH(h, dtype, "mxf_make_diagonal",
-             hipLaunchKernelGGL((make_diagonal_kernel<float>), dim3(grid_for(total)), dim3(256), 0, st, total, n, (const float*)a, (float*)out),
-             hipLaunchKernelGGL((make_diagonal_kernel<double>), dim3(grid_for(total)), dim3(256), 0, st, total, n, (const double*)a, (double*)out));
+    return mxf_typed(h, "mxf_make_diagonal", dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((make_diagonal_kernel<T>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, total, n, (const T*)a, (T*)out);
+    });
 }
 
 extern "C" int mxf_diag_of(mxf_handle h, int dtype, int64_t batch, int64_t n, const void* g, void* out, void* stream) {
     if (!h) return -1;
     if (batch <= 0 || n <= 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
     const int64_t total = batch * n;
-    DISPATCH(h, dtype, "mxf_diag_of",
-             hipLaunchKernelGGL((diag_of_kernel<float>), dim3(grid_for(total)), dim3(256), 0, st, total, n, (const float*)g, (float*)out),
-             hipLaunchKernelGGL((diag_of_kernel<double>), dim3(grid_for(total)), dim3(256), 0, st, total, n, (const double*)g, (double*)out));
+    return mxf_typed(h, "mxf_diag_of", dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((diag_of_kernel<T>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, total, n, (const T*)g, (T*)out);
+    });
 }

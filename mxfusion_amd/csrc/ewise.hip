@@ -21,16 +21,9 @@
 
 namespace {
 
-constexpr int EW_RANK = MXF_EW_MAX_RANK;
 constexpr int EW_TAB = 1024;                          // LDS sums per operand (doubles)
-constexpr int64_t EW_LIMIT = (int64_t)1 << 35;        // elements of the output, and the span of an operand
 
-struct EwArgs {
-    int rank, op;
-    int64_t extent[EW_RANK];
-    int64_t sx[EW_RANK], sy[EW_RANK];      // operand strides in elements, 0: shared
-    int64_t gx[EW_RANK], gy[EW_RANK];      // strides of the dense gradients (shared axes at extent 1), 0: shared
-};
+struct EwArgs : EwAxes {};                            // (pointwise_plan.h: rank, op, extents, operand and gradient strides)
 
 template <typename T>
 __device__ __forceinline__ T ew_apply(int op, T x, T y) {
@@ -266,97 +259,37 @@ __global__ __launch_bounds__(256) void ewise_bwd_kernel(EwArgs a, const T* __res
             if (ty[i] != 0.0) atomic_add(py.acc + i, ty[i]);
 }
 
-// What both entry points check and derive.  Returns 1 where there is nothing to do (an empty extent).
-struct EwPlan {
-    EwArgs a;
-    int64_t items, chunks, total;
-    bool shared_x, shared_y;
-    int64_t numel_gx, numel_gy;
-};
+// the 32- or 64-bit item counter of the plan's wide_index
+template <int WIDE> using ew_index_t = std::conditional_t<WIDE != 0, uint64_t, uint32_t>;
 
-int ew_plan(mxf_handle h, const char* name, int op, int dtype, int rank, const int64_t* extent, const void* x, const int64_t* stride_x,
-            const void* y, const int64_t* stride_y, EwPlan* p) {
-    if (dtype != MXF_F32 && dtype != MXF_F64) MXF_FAIL(h, -2, "%s: bad dtype %d", name, dtype);
-    if (op < 0 || op > 7) MXF_FAIL(h, -2, "%s: op %d (0 add .. 7 log)", name, op);
-    if (rank < 1) MXF_FAIL(h, -2, "%s: rank %d", name, rank);
-    if (rank > EW_RANK) MXF_FAIL(h, -3, "%s: rank %d after merging; up to %d axes are supported", name, rank, EW_RANK);
-    const bool binary = op <= 4;
-    if (!extent || !stride_x || !x || (binary && (!y || !stride_y))) MXF_FAIL(h, -2, "%s: null operand, extent or stride array", name);
-    *p = EwPlan();
-    p->a.rank = rank;
-    p->a.op = op;
-    int64_t total = 1, span_x = 0, span_y = 0;
-    for (int d = 0; d < rank; ++d) {
-        const int64_t e = extent[d], sx = e > 1 ? stride_x[d] : 0, sy = binary && e > 1 ? stride_y[d] : 0;
-        if (e < 0 || sx < 0 || sy < 0) MXF_FAIL(h, -2, "%s: axis %d has extent %lld, strides %lld, %lld", name, d, (long long)e, (long long)sx, (long long)sy);
-        if (e > EW_LIMIT || sx > EW_LIMIT || sy > EW_LIMIT) MXF_FAIL(h, -3, "%s: axis %d is beyond 2^35 elements", name, d);
-        p->a.extent[d] = e;
-        p->a.sx[d] = sx;
-        p->a.sy[d] = sy;
-        if (e > 1 && sx == 0) p->shared_x = true;
-        if (e > 1 && sy == 0 && binary) p->shared_y = true;
-        if (e == 0) total = 0;
-        else if (total > EW_LIMIT / e) MXF_FAIL(h, -3, "%s: more than 2^35 elements", name);
-        else total *= e;
-        span_x += e ? (e - 1) * sx : 0;
-        span_y += e ? (e - 1) * sy : 0;
-        if (span_x > EW_LIMIT || span_y > EW_LIMIT) MXF_FAIL(h, -3, "%s: an operand spans more than 2^35 elements", name);
-    }
-    p->total = total;
-    if (total == 0) return 1;
-    // the dense gradients: row-major over the extents with the operand's shared axes at 1
-    p->numel_gx = p->numel_gy = 1;
-    for (int d = rank - 1; d >= 0; --d) {
-        const bool own_x = p->a.extent[d] > 1 && p->a.sx[d] != 0, own_y = binary && p->a.extent[d] > 1 && p->a.sy[d] != 0;
-        p->a.gx[d] = own_x ? p->numel_gx : 0;
-        p->a.gy[d] = own_y ? p->numel_gy : 0;
-        if (own_x) p->numel_gx *= p->a.extent[d];
-        if (own_y) p->numel_gy *= p->a.extent[d];
-    }
-    return 0;
+// y, dx, dy: null where the plan has no use for them (a unary op; a gradient that is not wanted)
+template <typename T>
+int ew_launch_fwd(const EwisePlan& p, const void* x, const void* y, void* z, hipStream_t st) {
+    const EwArgs a = {p.a};
+    return dispatch<0, 1>(p.wide_index, [&](auto wide) {
+        using IDX = ew_index_t<decltype(wide)::value>;
+        hipLaunchKernelGGL((ewise_fwd_kernel<T, IDX>), dim3(p.grid), dim3(256), 0, st, a, (const T*)x, (const T*)y, (T*)z, (IDX)p.items, (IDX)p.chunks);
+        return 0;
+    });
 }
 
 template <typename T>
-void ew_items(EwPlan* p) {
-    constexpr int V = Vec16<T>::n;
-    const int64_t inner = p->a.extent[p->a.rank - 1];
-    p->chunks = (inner + V - 1) / V;
-    p->items = p->total / inner * p->chunks;
-}
-
-template <typename T>
-int ew_launch_fwd(const EwPlan& p, const void* x, const void* y, void* z, hipStream_t st) {
-    if (p.items < ((int64_t)1 << 31))
-        hipLaunchKernelGGL((ewise_fwd_kernel<T, uint32_t>), dim3(grid_for(p.items)), dim3(256), 0, st, p.a, (const T*)x, (const T*)y, (T*)z,
-                           (uint32_t)p.items, (uint32_t)p.chunks);
-    else
-        hipLaunchKernelGGL((ewise_fwd_kernel<T, uint64_t>), dim3(grid_for(p.items)), dim3(256), 0, st, p.a, (const T*)x, (const T*)y, (T*)z,
-                           (uint64_t)p.items, (uint64_t)p.chunks);
-    return 0;
-}
-
-template <typename T>
-int ew_launch_bwd(mxf_handle h, const EwPlan& p, const void* x, const void* y, const void* dz, void* dx, void* dy, hipStream_t st) {
+int ew_launch_bwd(mxf_handle h, const EwisePlan& p, const void* x, const void* y, const void* dz, void* dx, void* dy, hipStream_t st) {
     SharedSums sums;
-    if (int rc = shared_sums_open<T>(h, "mxf_ewise_bwd", {{p.shared_x ? dx : nullptr, p.numel_gx}, {p.shared_y ? dy : nullptr, p.numel_gy}}, st, &sums))
-        return rc;
-    const int last = p.a.rank - 1;
-    const EwGrad px = {p.shared_x ? nullptr : dx, sums.acc[0], p.numel_gx, p.a.extent[last] > 1 && p.a.sx[last] == 0};
-    const EwGrad py = {p.shared_y ? nullptr : dy, sums.acc[1], p.numel_gy, p.a.extent[last] > 1 && p.a.sy[last] == 0};
-    const unsigned grid = sums.acc[0] || sums.acc[1] ? grid_for_reduce(p.items) : grid_for(p.items);
-    if (p.items < ((int64_t)1 << 31))
-        hipLaunchKernelGGL((ewise_bwd_kernel<T, uint32_t>), dim3(grid), dim3(256), 0, st, p.a, (const T*)x, (const T*)y, (const T*)dz, px, py,
-                           (uint32_t)p.items, (uint32_t)p.chunks);
-    else
-        hipLaunchKernelGGL((ewise_bwd_kernel<T, uint64_t>), dim3(grid), dim3(256), 0, st, p.a, (const T*)x, (const T*)y, (const T*)dz, px, py,
-                           (uint64_t)p.items, (uint64_t)p.chunks);
+    if (int rc = shared_sums_open<T>(h, "mxf_ewise_bwd", {{p.sum_x ? dx : nullptr, p.numel_gx}, {p.sum_y ? dy : nullptr, p.numel_gy}}, st, &sums)) return rc;
+    const EwArgs a = {p.a};
+    const EwGrad px = {.dense = p.shared_x ? nullptr : dx, .acc = sums.acc[0], .numel = p.numel_gx, .inner_shared = p.inner_shared_x};
+    const EwGrad py = {.dense = p.shared_y ? nullptr : dy, .acc = sums.acc[1], .numel = p.numel_gy, .inner_shared = p.inner_shared_y};
+    dispatch<0, 1>(p.wide_index, [&](auto wide) {
+        using IDX = ew_index_t<decltype(wide)::value>;
+        hipLaunchKernelGGL((ewise_bwd_kernel<T, IDX>), dim3(p.grid), dim3(256), 0, st, a, (const T*)x, (const T*)y, (const T*)dz, px, py, (IDX)p.items, (IDX)p.chunks);
+        return 0;
+    });
     shared_sums_close(sums, st);
     return 0;
 }
 
 // ---- reductions behind the sample axis: x dense (outer, R, inner) -> y dense (outer, inner) -----------------------------------------------
-
-constexpr int64_t RED_WAVE_MAX = 512;      // inner == 1: a wave per row up to this R, a workgroup per row beyond
 
 __device__ __forceinline__ double wave_prod(double v) {
 #pragma unroll
@@ -471,44 +404,28 @@ __global__ __launch_bounds__(256) void reduce_prod_bwd_rows_kernel(int64_t rows,
     }
 }
 
-int red_check(mxf_handle h, const char* name, int kind, int dtype, int64_t outer, int64_t R, int64_t inner) {
-    if (dtype != MXF_F32 && dtype != MXF_F64) MXF_FAIL(h, -2, "%s: bad dtype %d", name, dtype);
-    if (kind < 0 || kind > 2) MXF_FAIL(h, -2, "%s: kind %d (0 sum, 1 mean, 2 prod)", name, kind);
-    if (outer < 0 || R < 1 || inner < 0) MXF_FAIL(h, -2, "%s: extents (%lld, %lld, %lld)", name, (long long)outer, (long long)R, (long long)inner);
-    if (outer && inner && (outer > EW_LIMIT / inner || outer * inner > EW_LIMIT / R)) MXF_FAIL(h, -3, "%s: more than 2^35 elements", name);
-    return 0;
+struct RedArgs { int kind; int64_t outer, R, inner; const void *x, *y; void* out; };      // y: dy of the reverse pass; out: y, or dx_acc
+
+template <typename T>
+void red_launch_fwd(const RedArgs& a, const ReducePlan& p, hipStream_t st) {
+    if (p.rows)
+        hipLaunchKernelGGL(reduce_rows_kernel<T>, dim3(p.grid), dim3(256), 0, st, a.kind, a.outer, a.R, (const T*)a.x, (T*)a.out, p.by_wave ? 1 : 0);
+    else
+        hipLaunchKernelGGL(reduce_cols_kernel<T>, dim3(p.grid), dim3(256), 0, st, a.kind, a.outer, a.R, a.inner, (const T*)a.x, (T*)a.out);
 }
 
 template <typename T>
-void red_launch_fwd(int kind, int64_t outer, int64_t R, int64_t inner, const void* x, void* y, hipStream_t st) {
-    if (inner == 1) {
-        const bool by_wave = R <= RED_WAVE_MAX;
-        const int64_t blocks = by_wave ? (outer + 3) / 4 : outer;
-        hipLaunchKernelGGL(reduce_rows_kernel<T>, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, kind, outer, R, (const T*)x, (T*)y,
-                           by_wave ? 1 : 0);
-    } else {
-        hipLaunchKernelGGL(reduce_cols_kernel<T>, dim3(grid_for(outer * inner)), dim3(256), 0, st, kind, outer, R, inner, (const T*)x, (T*)y);
-    }
-}
-
-template <typename T>
-int red_launch_bwd(mxf_handle h, int kind, int64_t outer, int64_t R, int64_t inner, const void* x, const void* dy, void* dx, hipStream_t st) {
-    if (kind != 2) {
-        hipLaunchKernelGGL(reduce_spread_kernel<T>, dim3(grid_for(outer * R * inner)), dim3(256), 0, st, outer, R, inner, kind == 1 ? 1.0 / (double)R : 1.0,
-                           (const T*)dy, (T*)dx);
+int red_launch_bwd(mxf_handle h, const RedArgs& a, const ReducePlan& p, hipStream_t st) {
+    if (p.spread) {
+        hipLaunchKernelGGL(reduce_spread_kernel<T>, dim3(p.grid), dim3(256), 0, st, a.outer, a.R, a.inner, a.kind == 1 ? 1.0 / (double)a.R : 1.0, (const T*)a.y, (T*)a.out);
         return 0;
     }
-    double* suffix = (double*)mxf_ws(h, (size_t)(outer * R * inner) * sizeof(double));
-    if (!suffix) MXF_FAIL(h, -4, "mxf_reduce_bwd: out of memory for %lld scratch doubles", (long long)(outer * R * inner));
-    if (inner == 1) {
-        const bool by_wave = R <= RED_WAVE_MAX;
-        const int64_t blocks = by_wave ? (outer + 3) / 4 : outer;
-        hipLaunchKernelGGL(reduce_prod_bwd_rows_kernel<T>, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, outer, R, (const T*)x,
-                           (const T*)dy, suffix, (T*)dx, by_wave ? 1 : 0);
-    } else {
-        hipLaunchKernelGGL(reduce_prod_bwd_kernel<T>, dim3(grid_for(outer * inner)), dim3(256), 0, st, outer, R, inner, (const T*)x, (const T*)dy, suffix,
-                           (T*)dx);
-    }
+    double* suffix = (double*)mxf_ws(h, (size_t)p.scratch * sizeof(double));
+    if (!suffix) MXF_FAIL(h, -4, "mxf_reduce_bwd: out of memory for %lld scratch doubles", (long long)p.scratch);
+    if (p.rows)
+        hipLaunchKernelGGL(reduce_prod_bwd_rows_kernel<T>, dim3(p.grid), dim3(256), 0, st, a.outer, a.R, (const T*)a.x, (const T*)a.y, suffix, (T*)a.out, p.by_wave ? 1 : 0);
+    else
+        hipLaunchKernelGGL(reduce_prod_bwd_kernel<T>, dim3(p.grid), dim3(256), 0, st, a.outer, a.R, a.inner, (const T*)a.x, (const T*)a.y, suffix, (T*)a.out);
     return 0;
 }
 
@@ -517,67 +434,42 @@ int red_launch_bwd(mxf_handle h, int kind, int64_t outer, int64_t R, int64_t inn
 extern "C" int mxf_ewise_fwd(mxf_handle h, int op, int dtype, int rank, const int64_t* extent, const void* x, const int64_t* stride_x,
                              const void* y, const int64_t* stride_y, void* z, void* stream) {
     if (!h) return -1;
-    EwPlan p;
-    const int rc = ew_plan(h, "mxf_ewise_fwd", op, dtype, rank, extent, x, stride_x, y, stride_y, &p);
-    if (rc) return rc < 0 ? rc : 0;
-    if (!z) MXF_FAIL(h, -2, "mxf_ewise_fwd: null z");
-    if (op > 4) y = nullptr;
-    if (dtype == MXF_F32) {
-        ew_items<float>(&p);
-        ew_launch_fwd<float>(p, x, y, z, (hipStream_t)stream);
-    } else {
-        ew_items<double>(&p);
-        ew_launch_fwd<double>(p, x, y, z, (hipStream_t)stream);
-    }
-    MXF_LAUNCH_CHECK(h);
-    return 0;
+    const EwisePlan p = ewise_plan({.dtype = dtype, .op = op, .rank = rank, .extent = extent, .stride_x = stride_x, .stride_y = stride_y,
+                                    .has_x = x != nullptr, .has_y = y != nullptr, .has_z = z != nullptr});
+    if (p.rc) MXF_FAIL(h, p.rc, "mxf_ewise_fwd: %s", p.refusal);
+    if (p.empty) return 0;
+    return mxf_typed(h, "mxf_ewise_fwd", dtype, [&](auto t) { return ew_launch_fwd<decltype(t)>(p, x, p.binary ? y : nullptr, z, (hipStream_t)stream); });
 }
 
 extern "C" int mxf_ewise_bwd(mxf_handle h, int op, int dtype, int rank, const int64_t* extent, const void* x, const int64_t* stride_x,
                              const void* y, const int64_t* stride_y, const void* dz, void* dx_acc, void* dy_acc, void* stream) {
     if (!h) return -1;
-    EwPlan p;
-    const int rc = ew_plan(h, "mxf_ewise_bwd", op, dtype, rank, extent, x, stride_x, y, stride_y, &p);
-    if (rc) return rc < 0 ? rc : 0;
-    if (!dz) MXF_FAIL(h, -2, "mxf_ewise_bwd: null dz");
-    if (op > 4) {
-        y = nullptr;
-        dy_acc = nullptr;
-    }
-    if (!dx_acc && !dy_acc) return 0;
-    int rl;
-    if (dtype == MXF_F32) {
-        ew_items<float>(&p);
-        rl = ew_launch_bwd<float>(h, p, x, y, dz, dx_acc, dy_acc, (hipStream_t)stream);
-    } else {
-        ew_items<double>(&p);
-        rl = ew_launch_bwd<double>(h, p, x, y, dz, dx_acc, dy_acc, (hipStream_t)stream);
-    }
-    if (rl) return rl;
-    MXF_LAUNCH_CHECK(h);
-    return 0;
+    const EwisePlan p = ewise_plan({.dtype = dtype, .op = op, .rank = rank, .bwd = true, .extent = extent, .stride_x = stride_x, .stride_y = stride_y,
+                                    .has_x = x != nullptr, .has_y = y != nullptr, .has_z = dz != nullptr, .has_dx = dx_acc != nullptr,
+                                    .has_dy = dy_acc != nullptr});
+    if (p.rc) MXF_FAIL(h, p.rc, "mxf_ewise_bwd: %s", p.refusal);
+    if (p.empty) return 0;
+    return mxf_typed(h, "mxf_ewise_bwd", dtype, [&](auto t) {
+        return ew_launch_bwd<decltype(t)>(h, p, x, p.binary ? y : nullptr, dz, dx_acc, p.binary ? dy_acc : nullptr, (hipStream_t)stream);
+    });
 }
 
 extern "C" int mxf_reduce_fwd(mxf_handle h, int kind, int dtype, int64_t outer, int64_t R, int64_t inner, const void* x, void* y, void* stream) {
     if (!h) return -1;
-    if (int rc = red_check(h, "mxf_reduce_fwd", kind, dtype, outer, R, inner)) return rc;
-    if (outer == 0 || inner == 0) return 0;
-    if (!x || !y) MXF_FAIL(h, -2, "mxf_reduce_fwd: null x or y");
-    if (dtype == MXF_F32) red_launch_fwd<float>(kind, outer, R, inner, x, y, (hipStream_t)stream);
-    else red_launch_fwd<double>(kind, outer, R, inner, x, y, (hipStream_t)stream);
-    MXF_LAUNCH_CHECK(h);
-    return 0;
+    const ReducePlan p = reduce_plan({.dtype = dtype, .kind = kind, .outer = outer, .R = R, .inner = inner, .has_x = x != nullptr, .has_y = y != nullptr});
+    if (p.rc) MXF_FAIL(h, p.rc, "mxf_reduce_fwd: %s", p.refusal);
+    if (p.empty) return 0;
+    const RedArgs a = {.kind = kind, .outer = outer, .R = R, .inner = inner, .x = x, .out = y};
+    return mxf_typed(h, "mxf_reduce_fwd", dtype, [&](auto t) { red_launch_fwd<decltype(t)>(a, p, (hipStream_t)stream); });
 }
 
 extern "C" int mxf_reduce_bwd(mxf_handle h, int kind, int dtype, int64_t outer, int64_t R, int64_t inner, const void* x, const void* dy,
                               void* dx_acc, void* stream) {
     if (!h) return -1;
-    if (int rc = red_check(h, "mxf_reduce_bwd", kind, dtype, outer, R, inner)) return rc;
-    if (outer == 0 || inner == 0 || !dx_acc) return 0;
-    if (!dy || (kind == 2 && !x)) MXF_FAIL(h, -2, "mxf_reduce_bwd: null x or dy");
-    if (int rc = dtype == MXF_F32 ? red_launch_bwd<float>(h, kind, outer, R, inner, x, dy, dx_acc, (hipStream_t)stream)
-                                  : red_launch_bwd<double>(h, kind, outer, R, inner, x, dy, dx_acc, (hipStream_t)stream))
-        return rc;
-    MXF_LAUNCH_CHECK(h);
-    return 0;
+    const ReducePlan p = reduce_plan({.dtype = dtype, .kind = kind, .bwd = true, .outer = outer, .R = R, .inner = inner, .has_x = x != nullptr,
+                                      .has_y = dy != nullptr, .has_dx = dx_acc != nullptr});
+    if (p.rc) MXF_FAIL(h, p.rc, "mxf_reduce_bwd: %s", p.refusal);
+    if (p.empty) return 0;
+    const RedArgs a = {.kind = kind, .outer = outer, .R = R, .inner = inner, .x = x, .y = dy, .out = dx_acc};
+    return mxf_typed(h, "mxf_reduce_bwd", dtype, [&](auto t) { return red_launch_bwd<decltype(t)>(h, a, p, (hipStream_t)stream); });
 }

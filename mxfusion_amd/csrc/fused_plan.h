@@ -3,6 +3,7 @@
 // checked on the host by tests/host/fused_plan_check.cpp and tests/host/nearest_plan_check.cpp.  The tile sizes are the kernels' own: the
 // .hip files read them from here.
 #pragma once
+#include <stdarg.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -47,6 +48,9 @@ static inline size_t mxf_piece(Carver& cv, size_t bytes) { const size_t at = cv.
 struct FusedRefusal {
     int rc = 0; char refusal[192] = "";
     void refuse(int code, const char* why) { rc = code; snprintf(refusal, sizeof(refusal), "%s", why); }
+    __attribute__((format(printf, 3, 4))) void refusef(int code, const char* fmt, ...) {      // the texts that carry numbers
+        va_list ap; va_start(ap, fmt); rc = code; vsnprintf(refusal, sizeof(refusal), fmt, ap); va_end(ap);
+    }
     void refuse_q(int Q, int limit) { rc = -3; snprintf(refusal, sizeof(refusal), "Q = %d above the limit of %d input dimensions", Q, limit); }
 };
 static inline bool stride_ok(int64_t ss, int64_t one_sample) { return ss == 0 || ss == one_sample; }

@@ -197,7 +197,7 @@ __global__ __launch_bounds__(256) void mvn_inverse_bwd_kernel(int form, int S, i
 }
 
 int check_common(mxf_handle h, const char* name, int dtype, int form, int n) {
-    if (dtype != MXF_F32 && dtype != MXF_F64) MXF_FAIL(h, -2, "%s: bad dtype %d", name, dtype);
+    if (dtype != MXF_F32 && dtype != MXF_F64) return mxf_bad_dtype(h, name, dtype);
     if (form != 0 && form != 1) MXF_FAIL(h, -2, "%s: form is 0 (covariance) or 1 (precision), got %d", name, form);
     if (n < 1 || n > MVN_MAX) MXF_FAIL(h, -3, "%s: order n = %d is outside 1..%d (larger matrices take mxf_potrf / mxf_trsm)", name, n, MVN_MAX);
     return 0;
@@ -222,15 +222,14 @@ int check_rows(mxf_handle h, const char* name, const MvnCall& c) {
 
 template <typename T>
 MvnRows<T> rows_of(const MvnCall& c) {
-    return {c.form, c.S, c.B, c.n, (const T*)c.x, c.ss_x, (const T*)c.mean, c.ss_m, c.sb_m, (const T*)c.F, (const T*)c.logdet, c.S_A, c.B_A,
-            (T)c.scale};
+    return {.form = c.form, .S = c.S, .B = c.B, .n = c.n, .x = (const T*)c.x, .ss_x = c.ss_x, .mean = (const T*)c.mean, .ss_m = c.ss_m, .sb_m = c.sb_m,
+            .F = (const T*)c.F, .logdet = (const T*)c.logdet, .S_A = c.S_A, .B_A = c.B_A, .scale = (T)c.scale};
 }
 
 template <typename T>
 void launch_logpdf(const MvnCall& c, void* out, hipStream_t st) {
     const int64_t rows = (int64_t)c.S * c.B;
-    hipLaunchKernelGGL((mvn_logpdf_kernel<T>), dim3(grid_for(rows * 32)), dim3(256), 0, st, rows_of<T>(c),
-                       (T)(0.5 * c.n * 1.8378770664093454836 /* log 2 pi */), (T*)out);
+    hipLaunchKernelGGL((mvn_logpdf_kernel<T>), dim3(grid_for(rows * 32)), dim3(256), 0, st, rows_of<T>(c), (T)(0.5 * c.n * 1.8378770664093454836 /* log 2 pi */), (T*)out);
 }
 
 // dx, dmean and dA where their operand is shared over an axis are summed in double (shared_grad.h); mvn_inverse_bwd_kernel adds dA's float32
@@ -265,45 +264,36 @@ extern "C" int mxf_mvn_factor(mxf_handle h, int dtype, int form, int S_A, int64_
     if (!A || !F || !logdet || !info) MXF_FAIL(h, -2, "mxf_mvn_factor: null operand");
     if (lda < n || strideS_A < 0 || strideB_A < 0) MXF_FAIL(h, -2, "mxf_mvn_factor: lda %lld < n = %d, or a negative stride", (long long)lda, n);
     const int64_t M = (int64_t)S_A * B_A;
-    const dim3 grid(grid_for(M * 64)), block(256);
-    if (dtype == MXF_F32)
-        hipLaunchKernelGGL((mvn_factor_kernel<float>), grid, block, 0, (hipStream_t)stream, form, M, B_A, n, (const float*)A, lda, strideS_A,
-                           strideB_A, (float*)F, (float*)logdet, info);
-    else
-        hipLaunchKernelGGL((mvn_factor_kernel<double>), grid, block, 0, (hipStream_t)stream, form, M, B_A, n, (const double*)A, lda,
-                           strideS_A, strideB_A, (double*)F, (double*)logdet, info);
-    MXF_LAUNCH_CHECK(h);
-    return 0;
+    return mxf_typed(h, "mxf_mvn_factor", dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((mvn_factor_kernel<T>), dim3(grid_for(M * 64)), dim3(256), 0, (hipStream_t)stream, form, M, B_A, n, (const T*)A, lda, strideS_A,
+                           strideB_A, (T*)F, (T*)logdet, info);
+    });
 }
 
 extern "C" int mxf_mvn_logpdf(mxf_handle h, int dtype, int form, int S, int64_t B, int n, const void* x, int64_t strideS_x, const void* mean,
                               int64_t strideS_mean, int64_t strideB_mean, const void* F, const void* logdet, int S_A, int64_t B_A,
                               double scale, void* out, void* stream) {
     if (!h) return -1;
-    const MvnCall c = {dtype, form, S, B, n, x, strideS_x, mean, strideS_mean, strideB_mean, F, logdet, S_A, B_A, scale};
+    const MvnCall c = {.dtype = dtype, .form = form, .S = S, .B = B, .n = n, .x = x, .ss_x = strideS_x, .mean = mean, .ss_m = strideS_mean,
+                       .sb_m = strideB_mean, .F = F, .logdet = logdet, .S_A = S_A, .B_A = B_A, .scale = scale};
     if (int rc = check_common(h, "mxf_mvn_logpdf", dtype, form, n)) return rc;
     if (S <= 0 || B <= 0) return 0;
     if (int rc = check_rows(h, "mxf_mvn_logpdf", c)) return rc;
     if (!out || !logdet) MXF_FAIL(h, -2, "mxf_mvn_logpdf: null out or logdet");
-    if (dtype == MXF_F32) launch_logpdf<float>(c, out, (hipStream_t)stream);
-    else launch_logpdf<double>(c, out, (hipStream_t)stream);
-    MXF_LAUNCH_CHECK(h);
-    return 0;
+    return mxf_typed(h, "mxf_mvn_logpdf", dtype, [&](auto t) { launch_logpdf<decltype(t)>(c, out, (hipStream_t)stream); });
 }
 
 extern "C" int mxf_mvn_logpdf_bwd(mxf_handle h, int dtype, int form, int S, int64_t B, int n, const void* x, int64_t strideS_x,
                                   const void* mean, int64_t strideS_mean, int64_t strideB_mean, const void* F, int S_A, int64_t B_A,
                                   const void* cot, double scale, void* dx_acc, void* dmean_acc, void* dA_acc, void* stream) {
     if (!h) return -1;
-    const MvnCall c = {dtype, form, S, B, n, x, strideS_x, mean, strideS_mean, strideB_mean, F, nullptr, S_A, B_A, scale};
+    const MvnCall c = {.dtype = dtype, .form = form, .S = S, .B = B, .n = n, .x = x, .ss_x = strideS_x, .mean = mean, .ss_m = strideS_mean,
+                       .sb_m = strideB_mean, .F = F, .S_A = S_A, .B_A = B_A, .scale = scale};
     if (int rc = check_common(h, "mxf_mvn_logpdf_bwd", dtype, form, n)) return rc;
     if (S <= 0 || B <= 0) return 0;
     if (int rc = check_rows(h, "mxf_mvn_logpdf_bwd", c)) return rc;
     if (!cot) MXF_FAIL(h, -2, "mxf_mvn_logpdf_bwd: null cotangent");
     if (!dx_acc && !dmean_acc && !dA_acc) return 0;
-    if (int rc = dtype == MXF_F32 ? launch_bwd<float>(h, c, cot, dx_acc, dmean_acc, dA_acc, (hipStream_t)stream)
-                                  : launch_bwd<double>(h, c, cot, dx_acc, dmean_acc, dA_acc, (hipStream_t)stream))
-        return rc;
-    MXF_LAUNCH_CHECK(h);
-    return 0;
+    return mxf_typed(h, "mxf_mvn_logpdf_bwd", dtype, [&](auto t) { return launch_bwd<decltype(t)>(h, c, cot, dx_acc, dmean_acc, dA_acc, (hipStream_t)stream); });
 }

@@ -249,89 +249,39 @@ struct SimplexCall {
     int one_hot, normalize;
     double scale;
     bool labels;        // x holds one element per row (the Categorical without one-hot encoding)
+    bool bwd, dirichlet;
 };
 
-// S <= 0 or B <= 0 is the caller's to return 0 on, after the checks that do not depend on the operands
-int check_head(mxf_handle h, const SimplexCall& c) {
-    if (c.dtype != MXF_F32 && c.dtype != MXF_F64) MXF_FAIL(h, -2, "%s: bad dtype %d", c.name, c.dtype);
-    if (c.K < 1) MXF_FAIL(h, -2, "%s: K = %d classes, at least 1 is needed", c.name, c.K);
-    return 0;
-}
-
-int check_rows(mxf_handle h, const SimplexCall& c) {
-    if (!c.x || !c.p) MXF_FAIL(h, -2, "%s: null operand", c.name);
-    const int64_t dense_x = c.B * (c.labels ? 1 : c.K);
-    if (c.ss_x != 0 && c.ss_x != dense_x)
-        MXF_FAIL(h, -2, "%s: the sample stride of x is 0 or %lld (dense), got %lld", c.name, (long long)dense_x, (long long)c.ss_x);
-    if (c.sb_p != 0 && c.sb_p != c.K)
-        MXF_FAIL(h, -2, "%s: the batch stride of the parameter is 0 or K = %d, got %lld", c.name, c.K, (long long)c.sb_p);
-    const int64_t dense_p = (c.sb_p ? c.B : 1) * c.K;
-    if (c.ss_p != 0 && c.ss_p != dense_p)
-        MXF_FAIL(h, -2, "%s: the sample stride of the parameter is 0 or %lld (dense), got %lld", c.name, (long long)dense_p, (long long)c.ss_p);
-    return 0;
-}
-
+// out (forward), or cot and the gradient buffers of the parameter and of x (reverse: either may be null).  The parameter's gradient is
+// summed in double (shared_grad.h) where it is shared over the batch axis.
 template <typename T>
-SimplexArgs<T> args_of(const SimplexCall& c, bool by_batch) {
-    return {c.S, c.B, c.K, (const T*)c.x, c.ss_x, (const T*)c.p, c.ss_p, c.sb_p, c.one_hot, c.normalize, (T)c.scale, by_batch ? 1 : 0};
-}
-
-#define SIMPLEX_LAUNCH(kernel, T, K, items, st, ...)                                                                              \
-    do {                                                                                                                          \
-        if ((K) <= 4) hipLaunchKernelGGL((kernel<T, 4>), dim3(grid_for((items) * 4)), dim3(256), 0, st, __VA_ARGS__);             \
-        else if ((K) <= 16) hipLaunchKernelGGL((kernel<T, 16>), dim3(grid_for((items) * 16)), dim3(256), 0, st, __VA_ARGS__);     \
-        else hipLaunchKernelGGL((kernel<T, 64>), dim3(grid_for((items) * 64)), dim3(256), 0, st, __VA_ARGS__);                    \
-    } while (0)
-
-template <typename T>
-void launch_fwd(const SimplexCall& c, bool dirichlet, void* out, hipStream_t st) {
-    const int64_t rows = (int64_t)c.S * c.B;
-    const SimplexArgs<T> a = args_of<T>(c, false);
-    if (dirichlet) SIMPLEX_LAUNCH(dirichlet_logpdf_kernel, T, c.K, rows, st, a, (T*)out);
-    else SIMPLEX_LAUNCH(categorical_logpdf_kernel, T, c.K, rows, st, a, (T*)out);
-}
-
-// dp, dx: the gradient buffers of the parameter and of x (either may be null).  The parameter's gradient is summed in double
-// (shared_grad.h) where it is shared over the batch axis.
-template <typename T>
-int launch_bwd(mxf_handle h, const SimplexCall& c, bool dirichlet, const void* cot, void* dp, void* dx, hipStream_t st) {
-    const bool p_atomic = dp && shared_over(true, c.sb_p, c.S, c.B);
-    const bool by_batch = (dp && !p_atomic && c.ss_p == 0 && c.S > 1) || (dx && c.ss_x == 0 && c.S > 1);
-    const int64_t items = by_batch ? c.B : (int64_t)c.S * c.B;
+int launch(mxf_handle h, const SimplexCall& c, const SimplexPlan& p, void* out, const void* cot, void* dp, void* dx, hipStream_t st) {
     SharedSums sums;
-    if (int rc = shared_sums_open<T>(h, c.name, {{dp, p_atomic ? shared_numel(c.ss_p, false, c.S, c.B, c.K) : 0}}, st, &sums)) return rc;
-    const SimplexArgs<T> a = args_of<T>(c, by_batch);
-    if (dirichlet) SIMPLEX_LAUNCH(dirichlet_logpdf_bwd_kernel, T, c.K, items, st, a, (const T*)cot, (T*)dx, (T*)dp, sums.acc[0]);
-    else SIMPLEX_LAUNCH(categorical_logpdf_bwd_kernel, T, c.K, items, st, a, (const T*)cot, (T*)dp, (T*)dx, sums.acc[0]);
+    if (int rc = shared_sums_open<T>(h, c.name, {{dp, p.n_sum}}, st, &sums)) return rc;
+    const SimplexArgs<T> a = {.S = c.S, .B = c.B, .K = c.K, .x = (const T*)c.x, .ss_x = c.ss_x, .p = (const T*)c.p, .ss_p = c.ss_p, .sb_p = c.sb_p,
+                              .one_hot = c.one_hot, .normalize = c.normalize, .scale = (T)c.scale, .by_batch = p.by_batch ? 1 : 0};
+    dispatch<4, 16, 64>(p.bucket, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        const dim3 grid(p.grid), block(256);
+        if (!c.bwd && c.dirichlet) hipLaunchKernelGGL((dirichlet_logpdf_kernel<T, W>), grid, block, 0, st, a, (T*)out);
+        else if (!c.bwd) hipLaunchKernelGGL((categorical_logpdf_kernel<T, W>), grid, block, 0, st, a, (T*)out);
+        else if (c.dirichlet) hipLaunchKernelGGL((dirichlet_logpdf_bwd_kernel<T, W>), grid, block, 0, st, a, (const T*)cot, (T*)dx, (T*)dp, sums.acc[0]);
+        else hipLaunchKernelGGL((categorical_logpdf_bwd_kernel<T, W>), grid, block, 0, st, a, (const T*)cot, (T*)dp, (T*)dx, sums.acc[0]);
+        return 0;
+    });
     shared_sums_close(sums, st);
     return 0;
 }
 
-int run_fwd(mxf_handle h, const SimplexCall& c, bool dirichlet, void* out, void* stream) {
+int run(mxf_handle h, const SimplexCall& c, void* out, const void* cot, void* dp, void* dx, void* stream) {
     if (!h) return -1;
-    if (int rc = check_head(h, c)) return rc;
-    if (c.S <= 0 || c.B <= 0) return 0;
-    if (int rc = check_rows(h, c)) return rc;
-    if (!out) MXF_FAIL(h, -2, "%s: null out", c.name);
-    if (c.dtype == MXF_F32) launch_fwd<float>(c, dirichlet, out, (hipStream_t)stream);
-    else launch_fwd<double>(c, dirichlet, out, (hipStream_t)stream);
-    MXF_LAUNCH_CHECK(h);
-    return 0;
-}
-
-int run_bwd(mxf_handle h, const SimplexCall& c, bool dirichlet, const void* cot, void* dp, void* dx, void* stream) {
-    if (!h) return -1;
-    if (int rc = check_head(h, c)) return rc;
-    if (!dirichlet && !c.one_hot && dx) MXF_FAIL(h, -2, "%s: dx_acc must be null without one-hot encoding (a label has no gradient)", c.name);
-    if (c.S <= 0 || c.B <= 0) return 0;
-    if (int rc = check_rows(h, c)) return rc;
-    if (!cot) MXF_FAIL(h, -2, "%s: null cotangent", c.name);
-    if (!dp && !dx) return 0;
-    if (int rc = c.dtype == MXF_F32 ? launch_bwd<float>(h, c, dirichlet, cot, dp, dx, (hipStream_t)stream)
-                                    : launch_bwd<double>(h, c, dirichlet, cot, dp, dx, (hipStream_t)stream))
-        return rc;
-    MXF_LAUNCH_CHECK(h);
-    return 0;
+    const SimplexPlan p = simplex_plan({.dtype = c.dtype, .bwd = c.bwd, .dirichlet = c.dirichlet, .S = c.S, .B = c.B, .K = c.K, .ss_x = c.ss_x,
+                                        .ss_p = c.ss_p, .sb_p = c.sb_p, .one_hot = c.one_hot != 0, .labels = c.labels, .has_x = c.x != nullptr,
+                                        .has_p = c.p != nullptr, .has_out = out != nullptr, .has_cot = cot != nullptr, .has_dp = dp != nullptr,
+                                        .has_dx = dx != nullptr});
+    if (p.rc) MXF_FAIL(h, p.rc, "%s: %s", c.name, p.refusal);
+    if (p.empty) return 0;
+    return mxf_typed(h, c.name, c.dtype, [&](auto t) { return launch<decltype(t)>(h, c, p, out, cot, dp, dx, (hipStream_t)stream); });
 }
 
 }  // namespace
@@ -339,29 +289,33 @@ int run_bwd(mxf_handle h, const SimplexCall& c, bool dirichlet, const void* cot,
 extern "C" int mxf_categorical_logpdf(mxf_handle h, int dtype, int S, int64_t B, int K, const void* logp, int64_t strideS_lp,
                                       int64_t strideB_lp, const void* x, int64_t strideS_x, int one_hot, int normalize, double scale,
                                       void* out, void* stream) {
-    const SimplexCall c = {"mxf_categorical_logpdf", dtype, S, B, K, x, strideS_x, logp, strideS_lp, strideB_lp, one_hot != 0, normalize != 0,
-                           scale, one_hot == 0};
-    return run_fwd(h, c, false, out, stream);
+    const SimplexCall c = {.name = "mxf_categorical_logpdf", .dtype = dtype, .S = S, .B = B, .K = K, .x = x, .ss_x = strideS_x, .p = logp,
+                           .ss_p = strideS_lp, .sb_p = strideB_lp, .one_hot = one_hot != 0, .normalize = normalize != 0, .scale = scale,
+                           .labels = one_hot == 0};
+    return run(h, c, out, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int mxf_categorical_logpdf_bwd(mxf_handle h, int dtype, int S, int64_t B, int K, const void* logp, int64_t strideS_lp,
                                           int64_t strideB_lp, const void* x, int64_t strideS_x, int one_hot, int normalize, const void* cot,
                                           double scale, void* dlogp_acc, void* dx_acc, void* stream) {
-    const SimplexCall c = {"mxf_categorical_logpdf_bwd", dtype, S, B, K, x, strideS_x, logp, strideS_lp, strideB_lp, one_hot != 0,
-                           normalize != 0, scale, one_hot == 0};
-    return run_bwd(h, c, false, cot, dlogp_acc, dx_acc, stream);
+    const SimplexCall c = {.name = "mxf_categorical_logpdf_bwd", .dtype = dtype, .S = S, .B = B, .K = K, .x = x, .ss_x = strideS_x, .p = logp,
+                           .ss_p = strideS_lp, .sb_p = strideB_lp, .one_hot = one_hot != 0, .normalize = normalize != 0, .scale = scale,
+                           .labels = one_hot == 0, .bwd = true};
+    return run(h, c, nullptr, cot, dlogp_acc, dx_acc, stream);
 }
 
 extern "C" int mxf_dirichlet_logpdf(mxf_handle h, int dtype, int S, int64_t B, int K, const void* x, int64_t strideS_x, const void* alpha,
                                     int64_t strideS_a, int64_t strideB_a, int normalize, double scale, void* out, void* stream) {
-    const SimplexCall c = {"mxf_dirichlet_logpdf", dtype, S, B, K, x, strideS_x, alpha, strideS_a, strideB_a, 1, normalize != 0, scale, false};
-    return run_fwd(h, c, true, out, stream);
+    const SimplexCall c = {.name = "mxf_dirichlet_logpdf", .dtype = dtype, .S = S, .B = B, .K = K, .x = x, .ss_x = strideS_x, .p = alpha,
+                           .ss_p = strideS_a, .sb_p = strideB_a, .one_hot = 1, .normalize = normalize != 0, .scale = scale, .dirichlet = true};
+    return run(h, c, out, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int mxf_dirichlet_logpdf_bwd(mxf_handle h, int dtype, int S, int64_t B, int K, const void* x, int64_t strideS_x, const void* alpha,
                                         int64_t strideS_a, int64_t strideB_a, int normalize, const void* cot, double scale, void* dx_acc,
                                         void* dalpha_acc, void* stream) {
-    const SimplexCall c = {"mxf_dirichlet_logpdf_bwd", dtype, S, B, K, x, strideS_x, alpha, strideS_a, strideB_a, 1, normalize != 0, scale,
-                           false};
-    return run_bwd(h, c, true, cot, dalpha_acc, dx_acc, stream);
+    const SimplexCall c = {.name = "mxf_dirichlet_logpdf_bwd", .dtype = dtype, .S = S, .B = B, .K = K, .x = x, .ss_x = strideS_x, .p = alpha,
+                           .ss_p = strideS_a, .sb_p = strideB_a, .one_hot = 1, .normalize = normalize != 0, .scale = scale, .bwd = true,
+                           .dirichlet = true};
+    return run(h, c, nullptr, cot, dalpha_acc, dx_acc, stream);
 }

@@ -87,7 +87,7 @@ int run(mxf_handle h, const char* name, int dtype, int nseg, const int* kinds, c
         const void* x, const void* dy, void* out, bool bwd, hipStream_t st) {
     if (!h) return -1;
     if (nseg <= 0) return 0;
-    if (dtype != MXF_F32 && dtype != MXF_F64) MXF_FAIL(h, -2, "%s: bad dtype %d", name, dtype);
+    if (dtype != MXF_F32 && dtype != MXF_F64) return mxf_bad_dtype(h, name, dtype);
     if (!kinds || !sizes || !p0 || !p1) MXF_FAIL(h, -2, "%s: null segment table", name);
     int64_t total = 0;
     for (int k = 0; k < nseg; ++k) {              // every segment is checked before anything is launched
@@ -120,14 +120,12 @@ int run(mxf_handle h, const char* name, int dtype, int nseg, const int* kinds, c
         }
         if (m == 0) continue;
         const dim3 grid(grid_for(longest), (unsigned)m), block(256);
-        if (dtype == MXF_F32) {
-            if (bwd) hipLaunchKernelGGL((transform_bwd_kernel<float>), grid, block, 0, st, t, (const float*)x, (const float*)dy, (float*)out);
-            else hipLaunchKernelGGL((transform_fwd_kernel<float>), grid, block, 0, st, t, (const float*)x, (float*)out);
-        } else {
-            if (bwd) hipLaunchKernelGGL((transform_bwd_kernel<double>), grid, block, 0, st, t, (const double*)x, (const double*)dy, (double*)out);
-            else hipLaunchKernelGGL((transform_fwd_kernel<double>), grid, block, 0, st, t, (const double*)x, (double*)out);
-        }
-        MXF_LAUNCH_CHECK(h);
+        const int rc = mxf_typed(h, name, dtype, [&](auto e) {
+            using T = decltype(e);
+            if (bwd) hipLaunchKernelGGL((transform_bwd_kernel<T>), grid, block, 0, st, t, (const T*)x, (const T*)dy, (T*)out);
+            else hipLaunchKernelGGL((transform_fwd_kernel<T>), grid, block, 0, st, t, (const T*)x, (T*)out);
+        });
+        if (rc) return rc;
     }
     return 0;
 }

@@ -219,7 +219,7 @@ void uni_launch_kind(const UniArgs& u, int mode, hipStream_t st) {
 static inline int uni_check(mxf_handle h, const char* name, int dtype, const UniArgs& u) {
     if (!h) return -1;
     if (u.n <= 0 || u.S <= 0) return 1;
-    if (dtype != MXF_F32 && dtype != MXF_F64) MXF_FAIL(h, -2, "%s: bad dtype %d", name, dtype);
+    if (dtype != MXF_F32 && dtype != MXF_F64) return mxf_bad_dtype(h, name, dtype);
     if (!u.x || !u.a || !u.b) MXF_FAIL(h, -2, "%s: null x or parameter", name);
     if ((u.n_a != 1 && u.n_a != u.n) || (u.n_b != 1 && u.n_b != u.n)) MXF_FAIL(h, -2, "%s: the parameters must have 1 or n elements", name);
     if ((u.ss_a != 0 && (u.ss_a != u.n || u.n_a != u.n)) || (u.ss_b != 0 && (u.ss_b != u.n || u.n_b != u.n)))

@@ -13,29 +13,18 @@
 
 namespace {
 
-template <typename T>
-void launch(int kind, const UniArgs& u, int mode, hipStream_t st) {
-    switch (kind) {
-        case MXF_D_GAMMA: uni_launch_kind<T, MXF_D_GAMMA>(u, mode, st); break;
-        case MXF_D_GAMMA_MV: uni_launch_kind<T, MXF_D_GAMMA_MV>(u, mode, st); break;
-        case MXF_D_BETA: uni_launch_kind<T, MXF_D_BETA>(u, mode, st); break;
-        case MXF_D_LAPLACE: uni_launch_kind<T, MXF_D_LAPLACE>(u, mode, st); break;
-        case MXF_D_BERNOULLI: uni_launch_kind<T, MXF_D_BERNOULLI>(u, mode, st); break;
-        case MXF_D_NORMAL_PREC: uni_launch_kind<T, MXF_D_NORMAL_PREC>(u, mode, st); break;
-        default: uni_launch_kind<T, MXF_D_UNIFORM>(u, mode, st); break;
-    }
-}
-
 // argument checks shared by the entry points, then the launch
 int run(mxf_handle h, const char* name, int kind, int dtype, const UniArgs& u, int mode, void* stream) {
     if (!h) return -1;
     if (u.n <= 0 || u.S <= 0) return 0;
     if (kind < MXF_D_GAMMA || kind > MXF_D_NORMAL_PREC) MXF_FAIL(h, -2, "%s: unknown distribution kind %d", name, kind);
     if (const int rc = uni_check(h, name, dtype, u)) return rc < 0 ? rc : 0;
-    if (dtype == MXF_F32) launch<float>(kind, u, mode, (hipStream_t)stream);
-    else launch<double>(kind, u, mode, (hipStream_t)stream);
-    MXF_LAUNCH_CHECK(h);
-    return 0;
+    return mxf_typed(h, name, dtype, [&](auto t) {
+        return dispatch<MXF_D_GAMMA, MXF_D_GAMMA_MV, MXF_D_BETA, MXF_D_LAPLACE, MXF_D_UNIFORM, MXF_D_BERNOULLI, MXF_D_NORMAL_PREC>(kind, [&](auto k) {
+            uni_launch_kind<decltype(t), decltype(k)::value>(u, mode, (hipStream_t)stream);
+            return 0;
+        });
+    });
 }
 
 }  // namespace
@@ -43,7 +32,7 @@ int run(mxf_handle h, const char* name, int kind, int dtype, const UniArgs& u, i
 extern "C" int mxf_univariate_logpdf(mxf_handle h, int kind, int dtype, int S, int64_t n, const void* x, const void* a, int64_t n_a,
                                      const void* b, int64_t n_b, double scale, void* out_acc, void* dx_acc, void* da_acc, void* db_acc,
                                      void* stream) {
-    const UniArgs u = {S, n, x, a, n_a, 0, b, n_b, 0, scale, nullptr, 0, 0, out_acc, dx_acc, da_acc, db_acc};
+    const UniArgs u = {.S = S, .n = n, .x = x, .a = a, .n_a = n_a, .b = b, .n_b = n_b, .scale = scale, .out = out_acc, .dx = dx_acc, .da = da_acc, .db = db_acc};
     return run(h, "mxf_univariate_logpdf", kind, dtype, u, UNI_REDUCED, stream);
 }
 
@@ -51,7 +40,7 @@ extern "C" int mxf_univariate_logpdf_elem(mxf_handle h, int kind, int dtype, int
                                           int64_t strideS_a, const void* b, int64_t n_b, int64_t strideS_b, double scale, void* out,
                                           void* stream) {
     if (h && n > 0 && S > 0 && !out) MXF_FAIL(h, -2, "mxf_univariate_logpdf_elem: null out");
-    const UniArgs u = {S, n, x, a, n_a, strideS_a, b, n_b, strideS_b, scale, nullptr, 0, 0, out, nullptr, nullptr, nullptr};
+    const UniArgs u = {.S = S, .n = n, .x = x, .a = a, .n_a = n_a, .ss_a = strideS_a, .b = b, .n_b = n_b, .ss_b = strideS_b, .scale = scale, .out = out};
     return run(h, "mxf_univariate_logpdf_elem", kind, dtype, u, UNI_ELEM, stream);
 }
 
@@ -59,7 +48,8 @@ extern "C" int mxf_univariate_logpdf_bwd(mxf_handle h, int kind, int dtype, int 
                                          int64_t strideS_a, const void* b, int64_t n_b, int64_t strideS_b, const void* cot, double scale,
                                          void* dx_acc, void* da_acc, void* db_acc, void* stream) {
     if (h && n > 0 && S > 0 && !cot) MXF_FAIL(h, -2, "mxf_univariate_logpdf_bwd: null cotangent");
-    const UniArgs u = {S, n, x, a, n_a, strideS_a, b, n_b, strideS_b, scale, cot, n, 1, nullptr, dx_acc, da_acc, db_acc};
+    const UniArgs u = {.S = S, .n = n, .x = x, .a = a, .n_a = n_a, .ss_a = strideS_a, .b = b, .n_b = n_b, .ss_b = strideS_b, .scale = scale, .cot = cot, .cs_s = n,
+                       .cs_i = 1, .dx = dx_acc, .da = da_acc, .db = db_acc};
     return run(h, "mxf_univariate_logpdf_bwd", kind, dtype, u, UNI_REDUCED, stream);
 }
 
@@ -67,7 +57,7 @@ extern "C" int mxf_univariate_logpdf_ps(mxf_handle h, int kind, int dtype, int S
                                         int64_t strideS_a, const void* b, int64_t n_b, int64_t strideS_b, double scale, void* out_acc,
                                         void* stream) {
     if (h && n > 0 && S > 0 && !out_acc) MXF_FAIL(h, -2, "mxf_univariate_logpdf_ps: null out");
-    const UniArgs u = {S, n, x, a, n_a, strideS_a, b, n_b, strideS_b, scale, nullptr, 0, 0, out_acc, nullptr, nullptr, nullptr};
+    const UniArgs u = {.S = S, .n = n, .x = x, .a = a, .n_a = n_a, .ss_a = strideS_a, .b = b, .n_b = n_b, .ss_b = strideS_b, .scale = scale, .out = out_acc};
     return run(h, "mxf_univariate_logpdf_ps", kind, dtype, u, UNI_PER_SAMPLE, stream);
 }
 
@@ -75,6 +65,7 @@ extern "C" int mxf_univariate_logpdf_ps_bwd(mxf_handle h, int kind, int dtype, i
                                             int64_t strideS_a, const void* b, int64_t n_b, int64_t strideS_b, const void* w, double scale,
                                             void* dx_acc, void* da_acc, void* db_acc, void* stream) {
     if (h && n > 0 && S > 0 && !w) MXF_FAIL(h, -2, "mxf_univariate_logpdf_ps_bwd: null weights");
-    const UniArgs u = {S, n, x, a, n_a, strideS_a, b, n_b, strideS_b, scale, w, 1, 0, nullptr, dx_acc, da_acc, db_acc};
+    const UniArgs u = {.S = S, .n = n, .x = x, .a = a, .n_a = n_a, .ss_a = strideS_a, .b = b, .n_b = n_b, .ss_b = strideS_b, .scale = scale, .cot = w, .cs_s = 1,
+                       .cs_i = 0, .dx = dx_acc, .da = da_acc, .db = db_acc};
     return run(h, "mxf_univariate_logpdf_ps_bwd", kind, dtype, u, UNI_REDUCED, stream);
 }

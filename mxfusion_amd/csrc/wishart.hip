@@ -158,7 +158,7 @@ struct WishCall {
 };
 
 int check_common(mxf_handle h, const char* name, int dtype, int n) {
-    if (dtype != MXF_F32 && dtype != MXF_F64) MXF_FAIL(h, -2, "%s: bad dtype %d", name, dtype);
+    if (dtype != MXF_F32 && dtype != MXF_F64) return mxf_bad_dtype(h, name, dtype);
     if (n < 1 || n > MVN_MAX) MXF_FAIL(h, -3, "%s: order n = %d is outside 1..%d (larger matrices take mxf_potrf / mxf_trsm)", name, n, MVN_MAX);
     return 0;
 }
@@ -174,7 +174,8 @@ int check_rows(mxf_handle h, const char* name, const WishCall& c) {
 
 template <typename T>
 WishRows<T> rows_of(const WishCall& c) {
-    return {c.S, c.B, c.n, (const T*)c.X, c.ldx, c.ss_X, (const T*)c.dof, c.ss_d, c.sb_d, (const T*)c.V, c.ldv, c.ss_V, c.sb_V, c.S_V, c.B_V, c.scale};
+    return {.S = c.S, .B = c.B, .n = c.n, .X = (const T*)c.X, .ldx = c.ldx, .ss_X = c.ss_X, .dof = (const T*)c.dof, .ss_d = c.ss_d, .sb_d = c.sb_d,
+            .V = (const T*)c.V, .ldv = c.ldv, .ss_V = c.ss_V, .sb_V = c.sb_V, .S_V = c.S_V, .B_V = c.B_V, .scale = c.scale};
 }
 
 // a workgroup (one wavefront) per row, grid-stride above 4096 rows
@@ -207,17 +208,16 @@ extern "C" int mxf_wishart_logpdf(mxf_handle h, int dtype, int S, int64_t B, int
                                   const void* dof, int64_t strideS_dof, int64_t strideB_dof, const void* V, int64_t ldv, int64_t strideS_V,
                                   int64_t strideB_V, int S_V, int64_t B_V, double scale, void* out, int* info, void* stream) {
     if (!h) return -1;
-    const WishCall c = {dtype, S, B, n, X, ldx, strideS_X, dof, strideS_dof, strideB_dof, V, ldv, strideS_V, strideB_V, S_V, B_V, scale};
+    const WishCall c = {.dtype = dtype, .S = S, .B = B, .n = n, .X = X, .ldx = ldx, .ss_X = strideS_X, .dof = dof, .ss_d = strideS_dof, .sb_d = strideB_dof,
+                        .V = V, .ldv = ldv, .ss_V = strideS_V, .sb_V = strideB_V, .S_V = S_V, .B_V = B_V, .scale = scale};
     if (int rc = check_common(h, "mxf_wishart_logpdf", dtype, n)) return rc;
     if (S <= 0 || B <= 0) return 0;
     if (int rc = check_rows(h, "mxf_wishart_logpdf", c)) return rc;
     if (!out || !info) MXF_FAIL(h, -2, "mxf_wishart_logpdf: null out or info");
-    if (dtype == MXF_F32)
-        hipLaunchKernelGGL((wishart_logpdf_kernel<float>), dim3(grid_of(c)), dim3(64), 0, (hipStream_t)stream, rows_of<float>(c), (float*)out, info);
-    else
-        hipLaunchKernelGGL((wishart_logpdf_kernel<double>), dim3(grid_of(c)), dim3(64), 0, (hipStream_t)stream, rows_of<double>(c), (double*)out, info);
-    MXF_LAUNCH_CHECK(h);
-    return 0;
+    return mxf_typed(h, "mxf_wishart_logpdf", dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((wishart_logpdf_kernel<T>), dim3(grid_of(c)), dim3(64), 0, (hipStream_t)stream, rows_of<T>(c), (T*)out, info);
+    });
 }
 
 extern "C" int mxf_wishart_logpdf_bwd(mxf_handle h, int dtype, int S, int64_t B, int n, const void* X, int64_t ldx, int64_t strideS_X,
@@ -225,15 +225,12 @@ extern "C" int mxf_wishart_logpdf_bwd(mxf_handle h, int dtype, int S, int64_t B,
                                       int64_t strideS_V, int64_t strideB_V, int S_V, int64_t B_V, const void* cot, double scale, void* dX_acc,
                                       void* ddof_acc, void* dV_acc, void* stream) {
     if (!h) return -1;
-    const WishCall c = {dtype, S, B, n, X, ldx, strideS_X, dof, strideS_dof, strideB_dof, V, ldv, strideS_V, strideB_V, S_V, B_V, scale};
+    const WishCall c = {.dtype = dtype, .S = S, .B = B, .n = n, .X = X, .ldx = ldx, .ss_X = strideS_X, .dof = dof, .ss_d = strideS_dof, .sb_d = strideB_dof,
+                        .V = V, .ldv = ldv, .ss_V = strideS_V, .sb_V = strideB_V, .S_V = S_V, .B_V = B_V, .scale = scale};
     if (int rc = check_common(h, "mxf_wishart_logpdf_bwd", dtype, n)) return rc;
     if (S <= 0 || B <= 0) return 0;
     if (int rc = check_rows(h, "mxf_wishart_logpdf_bwd", c)) return rc;
     if (!cot) MXF_FAIL(h, -2, "mxf_wishart_logpdf_bwd: null cotangent");
     if (!dX_acc && !ddof_acc && !dV_acc) return 0;
-    if (int rc = dtype == MXF_F32 ? launch_bwd<float>(h, c, cot, dX_acc, ddof_acc, dV_acc, (hipStream_t)stream)
-                                  : launch_bwd<double>(h, c, cot, dX_acc, ddof_acc, dV_acc, (hipStream_t)stream))
-        return rc;
-    MXF_LAUNCH_CHECK(h);
-    return 0;
+    return mxf_typed(h, "mxf_wishart_logpdf_bwd", dtype, [&](auto t) { return launch_bwd<decltype(t)>(h, c, cot, dX_acc, ddof_acc, dV_acc, (hipStream_t)stream); });
 }
