@@ -590,6 +590,53 @@ int mxf_nearest(mxf_handle h, int dtype, int64_t N, int64_t M, int Q, const void
 int mxf_kmeans_step(mxf_handle h, int dtype, int64_t N, int64_t M, int Q, const void* X, const void* C, void* C_new, int32_t* idx,
                     int64_t* counts, double* inertia, void* stream);
 
+/* The k nearest rows of C (Nc, Q) for every row of X (N, Q), the neighbour search of nearest-neighbour (Vecchia) GP regression.  No reference
+ * counterpart.  With causal != 0 the candidates of row n are the rows j < n of X itself: the caller passes C == X and Nc == N, anything else
+ * is status -2.  Otherwise they are all rows j < Nc.  There is no sample axis; X and C are dense row-major in dtype.  The distance is
+ * mxf_nearest's difference form, summed in the working dtype.  idx (N, k) int32 and, where it is not NULL, d2 (N, k) in dtype are WRITTEN:
+ * a row's slots are sorted ascending by (d2, j), lexicographic and strict, so the result is deterministic and among exact ties the smaller
+ * index comes first; slots beyond the number of candidates hold idx = -1 and d2 = +inf.  Inputs are finite: the caller's precondition.
+ * 1 <= Q <= MXF_KNN_MAX_Q and 1 <= k <= MXF_KNN_MAX_K: above either is status -3, and no buffer is touched; a null required pointer, N, Nc, Q
+ * or k < 1, N > 2^31 or Nc > 2^31 - 1 is status -2.  Nothing of size N x Nc is stored: a thread owns a row, keeps its running list in
+ * registers and scans the candidates, which arrive as scalar loads (mxfusion_amd/csrc/knn.hip).  Scratch, Nc Q elements (Q padded to 4, 8
+ * or 16), comes from the handle.  A lengthscale is the caller's job: pass X / lengthscale.                                                */
+#define MXF_KNN_MAX_Q 16
+#define MXF_KNN_MAX_K 32
+int mxf_knn(mxf_handle h, int dtype, int64_t N, int64_t Nc, int Q, int k, int causal, const void* X, const void* C, int32_t* idx, void* d2,
+            void* stream);
+
+/* Nearest-neighbour (Vecchia) Gaussian process regression (Vecchia 1988; Datta et al. 2016): every row is conditioned on at most k <= 32
+ * other rows, so the log-likelihood is a sum of N independent problems of order k.  No reference counterpart.  With c the neighbours of a
+ * row (nbr (rows, k) int32: entries are -1, an empty slot anywhere in the row, or a row of X), A = K(X_c, X_c) + noise I,
+ * kappa = K(X_c, x), a = k(x, x) + noise:
+ *   b = A^-1 kappa,  alpha = A^-1 Y_c,  s = a - kappa^T b,  r = y - kappa^T alpha,  l = -P/2 log 2 pi - P/2 log s - |r|^2 / (2 s)
+ * kind is MXF_K_RBF or MXF_K_MATERN12 / 32 / 52 and the covariance of a pair is the function of its scaled distance that mxf_gram evaluates,
+ * the clip of r in the Matern kinds included (so k(x, x) of the log-pdf is the diagonal mxf_gram writes; the predictor's k(x*, x*) is the
+ * variance, as mxf_kdiag).  X (N, Q), Y (N, P), lengthscale (Q with ard else 1), variance (1) and noise (1) are dense in dtype on the
+ * device; there is no sample axis.  Q <= MXF_KNN_MAX_Q, k <= MXF_KNN_MAX_K, P <= MXF_VECCHIA_MAX_P: above is status -3, and no buffer is
+ * touched; a null required pointer or an extent < 1 is status -2.  The caller's preconditions, not checked: the entries of nbr are -1 or in
+ * [0, N) and, for the log-pdf of row i, < i (an entry outside [0, N) is read as -1).  The k x k matrices live in LDS in double for either
+ * dtype; nothing of size N x k^2 is stored or saved between the passes.  A pivot that is not positive makes that row's term, and with it the
+ * value and the gradients, NaN; nothing traps.  The value and the parameter gradients are summed per workgroup in double and meet in double
+ * scratch with atomics, and dY is scattered with atomics: their last bits can differ from call to call.
+ *
+ * mxf_vecchia_cond: the predictor.  For every row of Xt (Nt, Q) with its neighbours nbr (Nt, k) among the rows of X, mean_out (Nt, P) =
+ *   kappa^T alpha and var_out (Nt) = k(x*, x*) - kappa^T b, the latent values, are WRITTEN.
+ * mxf_vecchia_logpdf: terms_out (N) in dtype, the l_i, where it is not NULL, and value_out[0], their sum (a double on the device), are WRITTEN.
+ * mxf_vecchia_logpdf_bwd: the gradient of g[0] * sum_i l_i (g: one element of dtype on the device) in lengthscale (dls: Q with ard else
+ *   1), variance (dvar), noise (dnoise) and Y (dY (N, P)), WRITTEN, not accumulated; each may be NULL.  The factor is recomputed.  There is no
+ *   reverse mode in X.                                                                                                                    */
+#define MXF_VECCHIA_MAX_P 32
+int mxf_vecchia_cond(mxf_handle h, int kind, int dtype, int64_t Nt, int64_t N, int Q, int P, int k, int ard, const void* Xt, const void* X,
+                     const void* Y, const int32_t* nbr, const void* lengthscale, const void* variance, const void* noise, void* mean_out,
+                     void* var_out, void* stream);
+int mxf_vecchia_logpdf(mxf_handle h, int kind, int dtype, int64_t N, int Q, int P, int k, int ard, const void* X, const void* Y,
+                       const int32_t* nbr, const void* lengthscale, const void* variance, const void* noise, void* terms_out, double* value_out,
+                       void* stream);
+int mxf_vecchia_logpdf_bwd(mxf_handle h, int kind, int dtype, int64_t N, int Q, int P, int k, int ard, const void* X, const void* Y,
+                           const int32_t* nbr, const void* lengthscale, const void* variance, const void* noise, const void* g, void* dls,
+                           void* dvar, void* dnoise, void* dY, void* stream);
+
 /* Multivariate normal of order n <= 32 over x (S, B, n), mean (S|1, B|1, n) and A (S|1, B|1, n, n): A is the covariance (form 0) or the
  * precision (form 1).  A larger n is status -3 from every entry point, and no buffer is touched (such matrices take mxf_potrf /
  * mxf_trsm).  Replaces MultivariateNormal.log_pdf_impl (components/distributions/normal.py:157-178: linalg.potrf, linalg.trsm,

@@ -19,6 +19,9 @@ PSI_MAX_Q = 16             # MXF_PSI_MAX_Q: input dimensions of the psi statisti
 RFF_MAX_Q = 16             # MXF_RFF_MAX_Q: input dimensions of the random Fourier features
 KMV_MAX_Q = 16             # MXF_KMV_MAX_Q: input dimensions of the matrix-free kernel product
 NEAREST_MAX_Q = 16         # MXF_NEAREST_MAX_Q: input dimensions of the nearest-centre assignment
+KNN_MAX_Q = 16             # MXF_KNN_MAX_Q: input dimensions of the k-nearest-neighbour search and of the Vecchia kernels
+KNN_MAX_K = 32             # MXF_KNN_MAX_K: neighbours per row
+VECCHIA_MAX_P = 32         # MXF_VECCHIA_MAX_P: output columns of the Vecchia kernels
 TR_MAX_SEG = 32           # MXF_TR_MAX_SEG: segments per launch; a longer list takes further launches inside the call
 ACT_IDENTITY, ACT_TANH, ACT_RELU, ACT_SIGMOID = range(4)
 DENSE_MAX_WIDTH = 128
@@ -74,6 +77,10 @@ SIGNATURES = {
     'mxf_kmv_bwd': [_i, _i, _i, _i64, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _pd, _vp, _vp, _vp],
     'mxf_nearest': [_i, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp],
     'mxf_kmeans_step': [_i, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    'mxf_knn': [_i, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    'mxf_vecchia_cond': [_i, _i, _i64, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    'mxf_vecchia_logpdf': [_i, _i, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    'mxf_vecchia_logpdf_bwd': [_i, _i, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     'mxf_mvn_factor': [_i, _i, _i, _i64, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
     'mxf_mvn_logpdf': [_i, _i, _i, _i64, _i, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _i, _i64, _d, _vp, _vp],
     'mxf_mvn_logpdf_bwd': [_i, _i, _i, _i64, _i, _vp, _i64, _vp, _i64, _i64, _vp, _i, _i64, _vp, _d, _vp, _vp, _vp, _vp],

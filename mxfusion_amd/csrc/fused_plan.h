@@ -1,6 +1,7 @@
-// Grids, chunk sizes, accumulation paths, scratch layouts and refusals of the row-owned launchers (rff.hip, kmv.hip, psi.hip, nearest.hip) and
+// Grids, chunk sizes, accumulation paths, scratch layouts and refusals of the row-owned launchers (rff.hip, kmv.hip, psi.hip, nearest.hip,
+// knn.hip), of the per-row small-matrix launcher vecchia.hip and
 // the grid of the per-sample reductions (unidist.h, likelihood.hip, robustmax.hip), as pure functions of the request: plain C++, no HIP,
-// checked on the host by tests/host/fused_plan_check.cpp and tests/host/nearest_plan_check.cpp.  The tile sizes are the kernels' own: the
+// checked on the host by tests/host/fused_plan_check.cpp, nearest_plan_check.cpp and vecchia_plan_check.cpp.  The tile sizes are the kernels' own: the
 // .hip files read them from here.
 #pragma once
 #include <stdarg.h>
@@ -8,7 +9,7 @@
 #include <stdint.h>
 #include <stdio.h>
 
-#include "../../include/mxf_gp.h"      // MXF_PSI_MAX_Q, MXF_RFF_MAX_Q, MXF_KMV_MAX_Q
+#include "../../include/mxf_gp.h"      // MXF_PSI_MAX_Q, MXF_RFF_MAX_Q, MXF_KMV_MAX_Q, MXF_KNN_MAX_*, MXF_VECCHIA_MAX_P
 
 constexpr int RFF_RB = 128;         // rows (threads) per workgroup
 constexpr int RFF_DCH = 64;         // values of d summed in T between two additions to the double register
@@ -376,5 +377,92 @@ static inline NearestPlan nearest_plan(const NearestRequest& r) {
         p.zero_bytes = cv.off - p.at_zero;
     }
     p.bytes = cv.off;
+    return p;
+}
+
+// ---- knn.hip -----------------------------------------------------------------------------------------------------------------------------
+constexpr int KNN_RB = 128;         // rows (threads) per workgroup
+
+// slots of the register list the kernel is compiled for
+static inline int mxf_kp(int k) { return k <= 8 ? 8 : (k <= 16 ? 16 : 32); }
+
+struct KnnRequest {
+    size_t esize = 4;
+    int64_t N = 0, Nc = 0; int Q = 0, k = 0; bool causal = false;
+    bool has_X = false, has_C = false, has_idx = false, same = false;      // same: C == X
+};
+// Scratch: the candidates padded to QP (cp)
+struct KnnPlan : FusedRefusal {
+    int qp = 0, kp = 0;                 // the kernel's <QP, KP>
+    unsigned grid = 1;                  // of knn_kernel: blocks of KNN_RB rows; the candidates are not split
+    int64_t n_prep = 0;                 // items of knn_prep_kernel (Nc)
+    size_t at_cp = 0, bytes = 0;
+};
+
+static inline KnnPlan knn_plan(const KnnRequest& r) {
+    KnnPlan p;
+    if (r.N < 1 || r.Nc < 1 || r.Q < 1 || r.k < 1) { p.refuse(-2, "N, Nc, Q, k >= 1"); return p; }
+    if (r.Q > MXF_KNN_MAX_Q) { p.refuse_q(r.Q, MXF_KNN_MAX_Q); return p; }
+    if (r.k > MXF_KNN_MAX_K) { p.refusef(-3, "k = %d above the limit of %d neighbours", r.k, MXF_KNN_MAX_K); return p; }
+    if (r.N > ((int64_t)1 << 31) || r.Nc > ((int64_t)1 << 31) - 1) { p.refuse(-2, "N <= 2^31, Nc <= 2^31 - 1"); return p; }
+    if (!r.has_X || !r.has_C || !r.has_idx) { p.refuse(-2, "null X, C or idx"); return p; }
+    if (r.causal && (!r.same || r.Nc != r.N)) { p.refuse(-2, "a causal search takes C == X and Nc == N"); return p; }
+    p.qp = mxf_qp(r.Q);
+    p.kp = mxf_kp(r.k);
+    p.grid = (unsigned)mxf_cdiv(r.N, KNN_RB);
+    p.n_prep = r.Nc;
+    Carver cv(nullptr);
+    p.at_cp = mxf_piece(cv, (size_t)r.Nc * p.qp * r.esize);
+    p.bytes = cv.off;
+    return p;
+}
+
+// ---- vecchia.hip -------------------------------------------------------------------------------------------------------------------------
+constexpr int VECCHIA_ROWS = 2;         // rows of the data set (groups of 32 lanes, a tile each) per workgroup
+constexpr int VECCHIA_MAX_GRID = 4096;  // workgroups; each takes further rows in a loop and closes with one atomic per sum
+
+enum { VECCHIA_COND = 0, VECCHIA_LOGPDF = 1, VECCHIA_BWD = 2 };
+struct VecchiaRequest {
+    size_t esize = 4; int call = VECCHIA_LOGPDF;
+    int64_t Nt = 0, N = 0; int Q = 0, P = 0, k = 0;      // Nt: the predictor's rows (ignored by the other two)
+    bool has_Xt = false, has_X = false, has_Y = false, has_nbr = false, has_ls = false, has_var = false, has_noise = false;
+    bool has_mean = false, has_vout = false;             // cond
+    bool has_value = false;                              // logpdf
+    bool has_g = false, has_dY = false;                  // bwd
+};
+// Scratch: zeroed doubles, n_acc of them: the value (logpdf), or the QP sums of the lengthscale, the variance's and the noise's (bwd)
+struct VecchiaPlan : FusedRefusal {
+    int qp = 0;
+    int64_t rows = 0;                   // Nt or N
+    unsigned grid = 1;                  // workgroups of VECCHIA_ROWS rows, at most VECCHIA_MAX_GRID
+    int n_acc = 0;
+    size_t at_acc = 0, zero_bytes = 0, bytes = 0;
+    size_t dy_bytes = 0;                // of dY, zeroed before the scatter (0: no dY)
+};
+
+static inline VecchiaPlan vecchia_plan(const VecchiaRequest& r) {
+    VecchiaPlan p;
+    const bool cond = r.call == VECCHIA_COND;
+    if (r.N < 1 || r.Q < 1 || r.P < 1 || r.k < 1 || (cond && r.Nt < 1)) { p.refuse(-2, "N, Nt, Q, P, k >= 1"); return p; }
+    if (r.Q > MXF_KNN_MAX_Q) { p.refuse_q(r.Q, MXF_KNN_MAX_Q); return p; }
+    if (r.k > MXF_KNN_MAX_K) { p.refusef(-3, "k = %d above the limit of %d neighbours", r.k, MXF_KNN_MAX_K); return p; }
+    if (r.P > MXF_VECCHIA_MAX_P) { p.refusef(-3, "P = %d above the limit of %d output columns", r.P, MXF_VECCHIA_MAX_P); return p; }
+    if (r.N > ((int64_t)1 << 31) - 1 || (cond && r.Nt > ((int64_t)1 << 31) - 1)) { p.refuse(-2, "N, Nt <= 2^31 - 1"); return p; }
+    if (!r.has_X || !r.has_Y || !r.has_nbr || !r.has_ls || !r.has_var || !r.has_noise) {
+        p.refuse(-2, "null X, Y, nbr, lengthscale, variance or noise");
+        return p;
+    }
+    if (cond && (!r.has_Xt || !r.has_mean || !r.has_vout)) { p.refuse(-2, "null Xt, mean_out or var_out"); return p; }
+    if (r.call == VECCHIA_LOGPDF && !r.has_value) { p.refuse(-2, "null value_out"); return p; }
+    if (r.call == VECCHIA_BWD && !r.has_g) { p.refuse(-2, "null g"); return p; }
+    p.qp = mxf_qp(r.Q);
+    p.rows = cond ? r.Nt : r.N;
+    p.grid = (unsigned)mxf_clampi(mxf_cdiv(p.rows, VECCHIA_ROWS), 1, VECCHIA_MAX_GRID);
+    p.n_acc = cond ? 0 : (r.call == VECCHIA_LOGPDF ? 1 : p.qp + 2);
+    Carver cv(nullptr);
+    p.zero_bytes = (size_t)p.n_acc * sizeof(double);
+    p.at_acc = mxf_piece(cv, p.zero_bytes);
+    p.bytes = cv.off;
+    p.dy_bytes = (r.call == VECCHIA_BWD && r.has_dY) ? (size_t)r.N * r.P * r.esize : 0;
     return p;
 }

@@ -8,3 +8,5 @@ from .pathwise import (GPRegressionPathwiseSampling, SVGPRegressionPathwiseSampl
                        PathwiseSamples)
 from .iterative_gp_regression import (IterativeGPRegression, IterativeGPRegressionLogPdf,  # noqa: F401
                                        IterativeGPRegressionMeanVariancePrediction)
+from .vecchia_gp_regression import (VecchiaGPRegression, VecchiaGPRegressionLogPdf,  # noqa: F401
+                                     VecchiaGPRegressionMeanVariancePrediction)

@@ -883,6 +883,101 @@ def kmeans_step(X, C):
     return C_new, idx, counts, inertia
 
 
+def knn(X, C=None, k=1, causal=False, want_d2=True):
+    """(idx, d2): idx (N, k) int32, the k nearest rows of C (Nc, Q) for every row of X (N, Q), sorted ascending by (distance, index), and d2
+    (N, k) their squared distances (None without want_d2); slots beyond the number of candidates hold -1 and +inf.  causal: the candidates of
+    row n are the rows j < n of X itself (C None or X).  The N x Nc distances are never stored (mxf_knn).  No reverse mode."""
+    if causal and C is not None and C is not X:
+        raise ValueError('k nearest neighbours: a causal search runs within X (C None)')
+    C = X if C is None else C
+    N, Nc, Q = _nearest_operands('k nearest neighbours', X, C)
+    k = int(k)
+    if k < 1:
+        raise ValueError('k nearest neighbours: k must be at least 1; got %d' % k)
+    idx = torch.empty((N, k), dtype=torch.int32, device=X.device)
+    d2 = torch.empty((N, k), dtype=X.dtype, device=X.device) if want_d2 else None
+    _lib.call('mxf_knn', _h(X), _dt(X), N, Nc, Q, k, int(bool(causal)), _p(X), _p(C), _p(idx), _p(d2), _stream())
+    return idx, d2
+
+
+def _vecchia_operands(what, kind, X, Y, nbr, lengthscale, variance, noise, ard, rows, *others):
+    """(N, Q, P, k, [kind, dtype], [X, Y, nbr, lengthscale, variance, noise pointers]) of the Vecchia kernels: X (N, Q), Y (N, P), nbr (rows, k)
+    int32, lengthscale (Q with ard else 1), variance (1), noise (1); no sample axis"""
+    _same_kind(what, X, Y, lengthscale, variance, noise, *others, contiguous=True)
+    kind = KIND[kind] if isinstance(kind, str) else kind
+    if kind not in (_lib.K_RBF, _lib.K_MATERN12, _lib.K_MATERN32, _lib.K_MATERN52):
+        raise ValueError('%s: stationary kernels only (rbf, matern12, matern32, matern52)' % what)
+    if X.dim() != 2 or Y.dim() != 2 or Y.shape[0] != X.shape[0] or nbr.dim() != 2:
+        raise ValueError('%s: X is (N, Q), Y (N, P) and nbr (rows, k); got %s, %s, %s' % (what, tuple(X.shape), tuple(Y.shape), tuple(nbr.shape)))
+    N, Q, P, k = int(X.shape[0]), int(X.shape[1]), int(Y.shape[1]), int(nbr.shape[1])
+    if min(N, Q, P, k) < 1 or nbr.shape[0] != rows:
+        raise ValueError('%s: N, Q, P and k must be at least 1 and nbr must have %d rows; got nbr %s' % (what, rows, tuple(nbr.shape)))
+    if nbr.dtype != torch.int32 or nbr.device != X.device or not nbr.is_contiguous():
+        raise TypeError('%s: nbr is a contiguous int32 tensor on the device of X' % what)
+    if lengthscale.numel() != (Q if ard else 1) or variance.numel() != 1 or noise.numel() != 1:
+        raise ValueError('%s: lengthscale has %d elements, variance and noise one; got %s, %s, %s'
+                         % (what, Q if ard else 1, tuple(lengthscale.shape), tuple(variance.shape), tuple(noise.shape)))
+    return N, Q, P, k, [kind, _dt(X)], [_p(X), _p(Y), _p(nbr), _p(lengthscale), _p(variance), _p(noise)]
+
+
+def vecchia_cond(kind, Xt, X, Y, nbr, lengthscale, variance, noise, ard):
+    """(mean (Nt, P), var (Nt,)) of the latent function at the rows of Xt (Nt, Q), each conditioned on its neighbours nbr (Nt, k) int32 among
+    the rows of X (N, Q) with Y (N, P): kappa^T (K_cc + noise I)^-1 Y_c and variance - kappa^T (K_cc + noise I)^-1 kappa (mxf_vecchia_cond).
+    -1 in nbr is an empty slot."""
+    if Xt.dim() != 2 or Xt.shape[1] != X.shape[-1] or Xt.shape[0] < 1:
+        raise ValueError('Vecchia predictor: Xt is (Nt, Q) with Nt >= 1; got %s' % (tuple(Xt.shape),))
+    Nt = int(Xt.shape[0])
+    N, Q, P, k, head, ptrs = _vecchia_operands('Vecchia predictor', kind, X, Y, nbr, lengthscale, variance, noise, ard, Nt, Xt)
+    mean = torch.empty((Nt, P), dtype=X.dtype, device=X.device)
+    var = torch.empty((Nt,), dtype=X.dtype, device=X.device)
+    _lib.call('mxf_vecchia_cond', _h(X), *head, Nt, N, Q, P, k, int(bool(ard)), _p(Xt), *ptrs, _p(mean), _p(var), _stream())
+    return mean, var
+
+
+def vecchia_logpdf(kind, X, Y, nbr, lengthscale, variance, noise, ard, want_terms=True):
+    """(value, terms): the Vecchia log-likelihood sum_i log N(y_i | y_c(i)) of Y (N, P) at X (N, Q) with the neighbour sets nbr (N, k) int32
+    (entries of row i are -1 or < i), a 0-d float64 device tensor, and its N terms (None without want_terms) (mxf_vecchia_logpdf)."""
+    N, Q, P, k, head, ptrs = _vecchia_operands('Vecchia log-pdf', kind, X, Y, nbr, lengthscale, variance, noise, ard, X.shape[0])
+    terms = torch.empty((N,), dtype=X.dtype, device=X.device) if want_terms else None
+    value = torch.empty((), dtype=torch.float64, device=X.device)
+    _lib.call('mxf_vecchia_logpdf', _h(X), *head, N, Q, P, k, int(bool(ard)), *ptrs, _p(terms), _p(value), _stream())
+    return value, terms
+
+
+def vecchia_logpdf_bwd(kind, X, Y, nbr, lengthscale, variance, noise, ard, g, want=(True, True, True, True)):
+    """(dls, dvar, dnoise, dY) of g * vecchia_logpdf's value, g one element of X's dtype on the device; want: which of the four are formed,
+    the others are None (mxf_vecchia_logpdf_bwd).  There is no reverse mode in X."""
+    N, Q, P, k, head, ptrs = _vecchia_operands('Vecchia log-pdf', kind, X, Y, nbr, lengthscale, variance, noise, ard, X.shape[0], g)
+    if g.numel() != 1:
+        raise ValueError('Vecchia log-pdf: g has one element; got %s' % (tuple(g.shape),))
+    outs = [torch.empty_like(t) if w else None for t, w in zip((lengthscale, variance, noise, Y), want)]
+    _lib.call('mxf_vecchia_logpdf_bwd', _h(X), *head, N, Q, P, k, int(bool(ard)), *ptrs, _p(g), *[_p(t) for t in outs], _stream())
+    return tuple(outs)
+
+
+class VecchiaLogPdf(torch.autograd.Function):
+    """vecchia_logpdf's value in X's dtype, shape (1,), differentiable in Y, noise, lengthscale and variance (vecchia_logpdf_bwd, which
+    recomputes the factors); the neighbour sets are constants, and X has no reverse mode."""
+
+    @staticmethod
+    def forward(ctx, kind, ard, X, Y, nbr, noise, ls, var):
+        X, Y, noise, ls, var = [t.detach().contiguous() for t in (X, Y, noise, ls, var)]
+        ctx.kind, ctx.ard = kind, ard
+        ctx.save_for_backward(X, Y, nbr, noise, ls, var)
+        value, _ = vecchia_logpdf(kind, X, Y, nbr, ls, var, noise, ard, want_terms=False)
+        return value.to(X.dtype).reshape(1)
+
+    @staticmethod
+    def backward(ctx, g):
+        X, Y, nbr, noise, ls, var = ctx.saved_tensors
+        if ctx.needs_input_grad[2]:
+            raise NotImplementedError('the Vecchia log-pdf has no reverse mode in X: detach it')
+        need = ctx.needs_input_grad
+        dls, dvar, dnoise, dY = vecchia_logpdf_bwd(ctx.kind, X, Y, nbr, ls, var, noise, ctx.ard, g.reshape(1).contiguous(),
+                                                   want=(need[6], need[7], need[5], need[3]))
+        return None, None, None, dY, None, dnoise, dls, dvar
+
+
 MVN_MAX_ORDER = 32    # the order up to which the mxf_mvn_* entry points run (MVN_MAX of mvn.hip)
 
 
