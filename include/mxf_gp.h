@@ -172,6 +172,38 @@ int mxf_gram_bwd(mxf_handle h, int kind, int dtype, int S, int64_t N, int64_t N2
                  const void* dK, int64_t lddk, int64_t strideS_dK,
                  void* dX, void* dX2, void* dls, void* dvar, void* stream);
 
+/* Gram build of the covariances that are NOT a function of one scaled distance: they work on the per-dimension differences
+ * tau_d = x_d - x2_d, formed from the raw coordinates first (coincident rows give tau = 0 and an exact diagonal).  The reference has none
+ * of them; the conventions are GPflow's / scikit-learn's (RQ) and Wilson & Adams 2013 (SpectralMixture).  Each kind takes three parameter
+ * operands, each with its own sample stride (0: shared by the samples):
+ *   kind             p0               p1                        p2                      K(tau)
+ *   MXF_KD_PERIODIC  variance (S|1,1) lengthscale (S|1, Q|1)    period (S|1, Q|1)       p0 exp(-1/2 sum_d sin^2(pi tau_d / p2_d) / p1_d^2)
+ *   MXF_KD_RQ        variance (S|1,1) lengthscale (S|1, Q|1)    alpha (S|1, 1)          p0 (1 + r2 / (2 p2))^-p2,  r2 = sum_d tau_d^2 / p1_d^2
+ *   MXF_KD_SM        weights (S|1,A)  means (S|1, A, Q)         scales (S|1, A, Q)      sum_a p0_a exp(-2 pi^2 sum_d tau_d^2 p2_ad^2) prod_d cos(2 pi tau_d p1_ad)
+ * (Q|1: Q values with ard, one without; ard and A are ignored where the table has no use for them.  Means are in cycles per unit of input.)
+ * X, X2 (NULL: the square Gram), diag_add, jitter, K_out / ldk / strideS_K as mxf_gram; K_out is overwritten.  Limits: Q <= MXF_GD_MAX_Q for
+ * PERIODIC and RQ, Q <= MXF_GD_SM_MAX_Q and A <= MXF_GD_SM_MAX_A for SM.  Status: -2 for an unknown kind or dtype, an extent < 1, a null
+ * X / p0 / p1 / p2 / K_out, a negative stride or ldk < N2; -3 above a limit (checked before the pointers); no buffer is touched then.        */
+enum { MXF_KD_PERIODIC = 0, MXF_KD_RQ = 1, MXF_KD_SM = 2 };
+#define MXF_GD_MAX_Q 16
+#define MXF_GD_SM_MAX_Q 8
+#define MXF_GD_SM_MAX_A 8
+int mxf_gram_diff(mxf_handle h, int kind, int dtype, int S, int64_t N, int64_t N2, int Q, int A,
+                  const void* X, int64_t strideS_X, const void* X2, int64_t strideS_X2,
+                  const void* p0, int64_t strideS_p0, const void* p1, int64_t strideS_p1, const void* p2, int64_t strideS_p2, int ard,
+                  const void* diag_add, int64_t strideS_diag, double jitter,
+                  void* K_out, int64_t ldk, int64_t strideS_K, void* stream);
+
+/* Its reverse mode: given dK (S, N, N2; row stride lddk) it recomputes K pair by pair and ACCUMULATES INTO dX (S|1, N, Q), dX2 (S|1, N2, Q)
+ * [ignored when X2 == NULL: both roles flow into dX] and dp0, dp1, dp2, each laid out as its operand with its operand's sample stride -- a
+ * shared operand's gradient is summed over the samples, a non-ard operand's over the dimensions (as mxf_gram_bwd).  The caller zeroes the
+ * outputs; any of them may be NULL and its work is skipped.  dK need not be symmetric.  Status codes as mxf_gram_diff.                      */
+int mxf_gram_diff_bwd(mxf_handle h, int kind, int dtype, int S, int64_t N, int64_t N2, int Q, int A,
+                      const void* X, int64_t strideS_X, const void* X2, int64_t strideS_X2,
+                      const void* p0, int64_t strideS_p0, const void* p1, int64_t strideS_p1, const void* p2, int64_t strideS_p2, int ard,
+                      const void* dK, int64_t lddk, int64_t strideS_dK,
+                      void* dX, void* dX2, void* dp0, void* dp1, void* dp2, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Dense building blocks (MXNet linalg.* call sites).  All batched over S with strides.  */
 

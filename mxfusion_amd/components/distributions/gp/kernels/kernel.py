@@ -34,6 +34,25 @@ class _GramFn(torch.autograd.Function):
         return None, None, dX, dX2, dls, dvar
 
 
+class _GramDiffFn(torch.autograd.Function):
+    """The same for the difference-form families (mxf_gram_diff / mxf_gram_diff_bwd): kind 'periodic', 'rq' or 'sm' and its three
+    parameter operands."""
+
+    @staticmethod
+    def forward(ctx, kind, ard, X, X2, p0, p1, p2):
+        ctx.kind, ctx.ard = kind, ard
+        ctx.save_for_backward(X, X2, p0, p1, p2)
+        return ops.gram_diff(kind, X, X2, p0, p1, p2, ard)
+
+    @staticmethod
+    def backward(ctx, dK):
+        X, X2, p0, p1, p2 = ctx.saved_tensors
+        need = [n for n, i in (('X', 2), ('p0', 4), ('p1', 5), ('p2', 6)) if ctx.needs_input_grad[i]]
+        if X2 is not None and ctx.needs_input_grad[3]:
+            need.append('X2')
+        return (None, None) + ops.gram_diff_bwd(ctx.kind, X, X2, p0, p1, p2, ctx.ard, dK.contiguous(), need=need)
+
+
 class _PsiRBFFn(torch.autograd.Function):
     """(Psi1, Psi2) of the RBF kernel under x_n ~ N(mu_n, diag(s_n)) in one fused forward call (mxf_psi_rbf_fwd) and one fused reverse call
     (mxf_psi_rbf_bwd), which recomputes the N M^2 / 2 terms of Psi2 instead of keeping them."""

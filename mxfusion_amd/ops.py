@@ -311,6 +311,63 @@ def gram_bwd(kind, X, X2, lengthscale, variance, ard, dK, need=('X', 'X2', 'ls',
     return dX, dX2, dls, dvar
 
 
+KIND_DIFF = {'periodic': _lib.KD_PERIODIC, 'rq': _lib.KD_RQ, 'sm': _lib.KD_SM}
+
+
+def _diff_operands(what, kind, ard, X, X2, p0, p1, p2, *others):
+    """(kind code, contiguous operands, A) of the difference-form families: X (S|1, N, Q), X2 (S|1, N2, Q) or None, and per kind
+    periodic: variance (S|1, 1), lengthscale (S|1, Q|1), period (S|1, Q|1);  rq: variance, lengthscale, alpha (S|1, 1);
+    sm: weights (S|1, A), means (S|1, A, Q), scales (S|1, A, Q)."""
+    _same_kind(what, X, X2, p0, p1, p2, *others)
+    kd = KIND_DIFF[kind] if isinstance(kind, str) else kind
+    if kd == _lib.KD_SM and not (p1.dim() == 3 and p1.shape[-2:] == (p0.shape[-1], X.shape[-1]) and p2.shape[-2:] == p1.shape[-2:]):
+        raise ValueError('%s: a spectral mixture takes weights (S|1, A), means and scales (S|1, A, Q); got %s, %s, %s'
+                         % (what, tuple(p0.shape), tuple(p1.shape), tuple(p2.shape)))
+    if kd != _lib.KD_SM:
+        n = X.shape[-1] if ard else 1
+        want = (1, n, n if kd == _lib.KD_PERIODIC else 1)
+        if tuple(t.shape[-1] for t in (p0, p1, p2)) != want:
+            raise ValueError('%s: %s takes parameter operands of extents %s (ard = %s, Q = %d); got %s, %s, %s'
+                             % (what, kind, want, bool(ard), X.shape[-1], tuple(p0.shape), tuple(p1.shape), tuple(p2.shape)))
+    return kd, [_c(t) for t in (X, X2, p0, p1, p2)], (p0.shape[-1] if kd == _lib.KD_SM else 1)
+
+
+def gram_diff(kind, X, X2, p0, p1, p2, ard, diag_add=None, jitter=0.0, out=None):
+    """K(X, X2) (S, N, N2) of a covariance that works on the per-dimension differences (mxf_gram_diff): kind 'periodic', 'rq' or 'sm' with
+    the three parameter operands _diff_operands lists; diag_add (S|1, 1) and jitter go on the diagonal of a square Gram (X2 None)."""
+    kd, (X, X2, p0, p1, p2), A = _diff_operands('gram_diff', kind, ard, X, X2, p0, p1, p2, diag_add, out)
+    diag_add = _c(diag_add)
+    S = num_samples(X, X2, p0, p1, p2, diag_add)
+    N, Q = X.shape[-2], X.shape[-1]
+    N2 = N if X2 is None else X2.shape[-2]
+    if out is None:
+        out = torch.empty((S, N, N2), dtype=X.dtype, device=X.device)
+    if N == 0 or N2 == 0:
+        return out
+    _lib.call('mxf_gram_diff', _h(X), kd, _dt(X), S, N, N2, Q, A, _p(X), _ss(X), _p(X2), _ss(X2), _p(p0), _ss(p0), _p(p1), _ss(p1),
+              _p(p2), _ss(p2), int(bool(ard)), _p(diag_add), _ss(diag_add), float(jitter),
+              _p(out), out.stride(-2), out.stride(0) if out.dim() == 3 else 0, _stream())
+    return out
+
+
+def gram_diff_bwd(kind, X, X2, p0, p1, p2, ard, dK, need=('X', 'X2', 'p0', 'p1', 'p2')):
+    """Reverse mode of gram_diff(); returns (dX, dX2, dp0, dp1, dp2) shaped like their primals (summed over S for broadcast operands),
+    None for what `need` leaves out."""
+    kd, (X, X2, p0, p1, p2), A = _diff_operands('gram_diff_bwd', kind, ard, X, X2, p0, p1, p2, dK)
+    dK = _c(dK)
+    S = dK.shape[0]
+    N, Q = X.shape[-2], X.shape[-1]
+    N2 = N if X2 is None else X2.shape[-2]
+    dX = torch.zeros_like(X) if 'X' in need else None
+    dX2 = torch.zeros_like(X2) if (X2 is not None and 'X2' in need) else None
+    dp0, dp1, dp2 = [torch.zeros_like(t) if n in need else None for n, t in (('p0', p0), ('p1', p1), ('p2', p2))]
+    if N == 0 or N2 == 0:
+        return dX, dX2, dp0, dp1, dp2
+    _lib.call('mxf_gram_diff_bwd', _h(X), kd, _dt(X), S, N, N2, Q, A, _p(X), _ss(X), _p(X2), _ss(X2), _p(p0), _ss(p0), _p(p1), _ss(p1),
+              _p(p2), _ss(p2), int(bool(ard)), _p(dK), dK.stride(-2), dK.stride(0), _p(dX), _p(dX2), _p(dp0), _p(dp1), _p(dp2), _stream())
+    return dX, dX2, dp0, dp1, dp2
+
+
 def potrf_(A, info=None):
     """in-place batched lower Cholesky of A (S,n,n); returns (A, info) with info an int32 device tensor."""
     S, n = A.shape[0], A.shape[-1]
