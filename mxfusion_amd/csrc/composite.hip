@@ -1666,8 +1666,11 @@ __global__ void sgp_grads_kernel(int64_t M, int P, const double* __restrict__ Ci
         const double GC = -0.5 * P * Ci[idx] - 0.5 * is2 * is2 * aa;
         G2[idx] = (T)(gscale * 2.0 * (GC * is2 + 0.5 * P * is2 * Ki[idx]));
         GKuu[idx] = gscale * (GC + 0.5 * P * Ki[idx] - 0.5 * P * is2 * KPK[idx]);
-        if (idx < M * P) Gpsi1[idx] = (T)(gscale * a[idx] * is2 * is2);
     }
+    // Gpsi1 is M x P: a loop of its own, not a branch of the M x M one -- with P > M that left its entries from M M on unwritten (stale
+    // scratch in dKuf and dY, i.e. in every gradient but dnoise, under a correct logL)
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < M * P; idx += (int64_t)gridDim.x * blockDim.x)
+        Gpsi1[idx] = (T)(gscale * a[idx] * is2 * is2);
 }
 // sc: [0] sumlogdiag L  [1] sumlogdiag Lc  [2] <psi1,a>  [3] <Ki,Psi2>  [4] <Ci,Psi2>  [5] a^T Psi2 a  [6] ups
 template <typename T>

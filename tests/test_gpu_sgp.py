@@ -168,3 +168,156 @@ def test_sparse_gp_float32_guard_widens_above_the_limit():
         assert (g.tier == G.EXPLICIT) == explicit and g.cond_max > 0, (ell, g.tier, g.cond_max)
         assert out[0].dtype == torch.float32 and t['Z'].grad.dtype == torch.float32 and bool(torch.isfinite(t['Z'].grad).all())
         assert abs(float(out[0][0]) - ref) <= 1e-5 * abs(ref), (ell, float(out[0][0]), ref)
+
+
+# ---- the shape sweep of mxf_sgp_logpdf (tests/_sgp_cases.py: shapes, inputs, the float64 oracle once per case) ---------------------------
+import _sgp_cases as C  # noqa: E402
+
+SWEEP = [(s, k, a, d) for s in C.SHAPES for k in C.KINDS for a in (True, False) for d in (torch.float64, torch.float32)]
+OUT_KEYS = ('logL',) + C.POST_KEYS + C.GRAD_KEYS
+
+
+def _sgp_call(kind, ard, a, dtype, **kw):
+    from mxfusion_amd import ops
+    r = ops.sgp_logpdf(kind, *[_t(a[n], dtype) for n in ('X', 'Y', 'Z', 'noise', 'ls', 'var')], ard, jitter=kw.pop('jitter', C.JITTER), **kw)
+    return {k: v.cpu().numpy() for k, v in r.items()}
+
+
+@pytest.mark.parametrize('shape,kind,ard,dtype', SWEEP, ids=['%s-%s-%s-%s' % ('x'.join(map(str, s)), k, 'ard' if a else 'iso', str(d)[-7:])
+                                                            for s, k, a, d in SWEEP])
+def test_sgp_composite_shape_sweep(shape, kind, ard, dtype):
+    """logL, wv, L, LA and the six gradients against the float64 oracle at the smallest shapes that cross each seam of the call, with the
+    tolerances of test_sgp_composite_vs_oracle (tests/_sgp_cases.py: failed_keys); info is zero.  Every failing key is reported at once.
+    Before the Gpsi1 loop of sgp_grads_kernel ran over M P, every P > M case failed here on dX, dY, dZ, dls, dvar and nothing else."""
+    a, ref, cond = C.build(shape, kind, ard)
+    r = _sgp_call(kind, ard, a, dtype, want_grad=True)
+    assert int(np.abs(r['info']).sum()) == 0
+    assert r['wv'].shape == ref['wv'].shape and r['dX'].shape == a['X'].shape and r['dY'].shape == a['Y'].shape and r['dls'].shape == a['ls'].shape
+    bad = C.failed_keys(r, ref, shape, dtype == torch.float64)
+    err = {k: float(np.abs(np.asarray(r[k], dtype=np.float64).reshape(np.shape(ref[k])) - ref[k]).max()) for k in bad}
+    assert not bad, (bad, err, 'cond_1(Kuu) = %.3g' % cond)
+
+
+def test_sgp_composite_gscale_scales_the_gradients_only():
+    shape, kind, g = (5, 3, 2, 7), 'matern52', -0.37
+    a, ref, _ = C.build(shape, kind, False)
+    r1 = _sgp_call(kind, False, a, torch.float64, want_grad=True)
+    rg = _sgp_call(kind, False, a, torch.float64, want_grad=True, gscale=g)
+    for k in ('logL', 'info') + C.POST_KEYS:
+        assert np.array_equal(r1[k], rg[k]), k
+    for k in C.GRAD_KEYS:
+        assert np.allclose(rg[k], g * r1[k], rtol=1e-13, atol=0.), (k, float(np.abs(rg[k] / (g * r1[k]) - 1).max()))
+    assert C.failed_keys(r1, ref, shape, True) == []
+
+
+@pytest.mark.parametrize('dtype', [torch.float64, torch.float32])
+def test_sgp_composite_value_only_call_is_the_same_value(dtype):
+    for shape in ((5, 3, 2, 7), (3, 17, 1, 20)):
+        a, ref, _ = C.build(shape, 'matern32', True)
+        r0 = _sgp_call('matern32', True, a, dtype, want_grad=False)
+        r1 = _sgp_call('matern32', True, a, dtype, want_grad=True)
+        assert sorted(r0) == sorted(('logL', 'info') + C.POST_KEYS)
+        for k in r0:
+            assert np.array_equal(r0[k], r1[k]), (shape, k)
+        assert C.failed_keys(dict(ref, **r0), ref, shape, dtype == torch.float64) == [] and int(np.abs(r0['info']).sum()) == 0
+
+
+@pytest.mark.parametrize('dtype', [torch.float64, torch.float32])
+def test_sgp_composite_small_call_after_a_large_one_reads_no_stale_scratch(dtype):
+    """(70, 65, 2, 3) first, then (5, 3, 2, 7) twice: the scratch of the small P > M call lies inside what the large call wrote.  The two
+    small results are bit-identical and both meet the sweep's tolerances."""
+    big, small = (70, 65, 2, 3), (5, 3, 2, 7)
+    ab, refb, _ = C.build(big, 'rbf', True)
+    a, ref, _ = C.build(small, 'rbf', True)
+    rb = _sgp_call('rbf', True, ab, dtype, want_grad=True)
+    r1 = _sgp_call('rbf', True, a, dtype, want_grad=True)
+    r2 = _sgp_call('rbf', True, a, dtype, want_grad=True)
+    assert C.failed_keys(rb, refb, big, dtype == torch.float64) == []
+    for k in OUT_KEYS + ('info',):
+        assert np.array_equal(r1[k], r2[k]), k
+    assert C.failed_keys(r1, ref, small, dtype == torch.float64) == [] and C.failed_keys(r2, ref, small, dtype == torch.float64) == []
+
+
+@pytest.mark.parametrize('shape', [(3, 17, 1, 20), (40, 33, 3, 40)], ids=['M17', 'M33'])
+def test_sgp_composite_publishes_the_condition_number(shape):
+    """ops.svgp_last_cond() after a float64 call is |K|_1 |K^-1|_1 of the oracle's Kuu + jitter I (numpy float64) at M = 16 + 1 and 32 + 1:
+    the only reader of norm1_sym16_kernel at an M that is no multiple of its 16 rows per workgroup."""
+    from mxfusion_amd import ops
+    for kind in ('rbf', 'matern52'):
+        a, _, cond = C.build(shape, kind, True)
+        r = _sgp_call(kind, True, a, torch.float64, want_grad=False)
+        got = ops.svgp_last_cond()
+        assert int(np.abs(r['info']).sum()) == 0
+        assert abs(got - cond) <= 1e-8 * cond, (kind, got, cond)
+
+
+def test_sgp_composite_reports_a_singular_kuu():
+    """Two identical inducing rows, jitter 0, variance 1, float64, M = 3.  The Gram kernel forms distances from differences, so K01 = K00 =
+    K11 = 1 exactly; potrf_panel_kernel's first column is l = (1, 1, .) (inv_sqrt(1) = 1 after its correction step), the second pivot
+    fma(-1, 1, 1) = 0 fails `d > 0`, is recorded in info (= 2) and replaced by 1 so that the factor stays finite: no fault, no NaN needed."""
+    a, _, _ = C.build((5, 3, 2, 7), 'rbf', True)
+    a = {k: np.array(v) for k, v in a.items()}
+    a['Z'][1] = a['Z'][0]
+    a['var'] = np.array([1.0])
+    r = _sgp_call('rbf', True, a, torch.float64, want_grad=True, jitter=0.0)
+    assert int(r['info'][0]) != 0 or not np.isfinite(r['logL'][0]), (r['info'], r['logL'])
+
+
+def test_sgp_module_more_outputs_than_inducing_points():
+    """SparseGPRegression on the fused call with P = 7 > M = 3 and a scalar lengthscale (Matern52, ARD off), N = 5, float64, MAP: the loss,
+    the flat gradient slices of Z, noise_var, lengthscale and variance (the oracle through softplus) and the four prediction settings."""
+    from mxfusion_amd import Model, Variable
+    from mxfusion_amd.components.variables import PositiveTransformation
+    from mxfusion_amd.components.distributions.gp.kernels import Matern52
+    from mxfusion_amd.modules.gp_modules import SparseGPRegression
+    from mxfusion_amd.inference import GradBasedInference, MAP, BatchInferenceLoop, TransferInference, ModulePredictionAlgorithm
+    N, M, Q, D = 5, 3, 2, 7
+    a, _, _ = C.build((N, M, Q, D), 'matern52', False)
+    X, Y, Z, ls, var, noise = (np.array(a[n]) for n in ('X', 'Y', 'Z', 'ls', 'var', 'noise'))
+    Xt = np.random.RandomState(11).uniform(-2, 2, (4, Q))
+    t64 = lambda v: _t(v, torch.float64)
+    kern = Matern52(Q, ARD=False, variance=t64(var), lengthscale=t64(ls), dtype='float64')
+    assert kern.fused_spec() == ('matern52', False)
+    m = Model()
+    m.N = Variable()
+    m.X = Variable(shape=(m.N, Q))
+    m.Z = Variable(shape=(M, Q), initial_value=t64(Z))
+    m.noise_var = Variable(shape=(1,), transformation=PositiveTransformation(), initial_value=t64(noise))
+    m.Y = SparseGPRegression.define_variable(X=m.X, kernel=kern, noise_var=m.noise_var, inducing_inputs=m.Z, shape=(m.N, D), dtype='float64')
+    m.Y.factor.sgp_log_pdf.jitter = C.JITTER
+    grads, losses = [], []
+
+    class Rec(BatchInferenceLoop):
+        def step(self, ex, data, params):
+            loss = super(Rec, self).step(ex, data, params)
+            losses.append(float(loss.detach()))
+            return loss
+
+        def _exchange(self, param_dict, loss):
+            grads.append(param_dict.flat.grad.clone())
+            return loss
+    infr = GradBasedInference(MAP(model=m, observed=[m.X, m.Y]), grad_loop=Rec(), dtype='float64')
+    infr.run(X=t64(X), Y=t64(Y), max_iter=1, learning_rate=1e-9)
+    ok, sp = O.Matern52(Q, ARD=False), O.softplus
+    raw = {n: O.inv_softplus(O.T(v)).clone().requires_grad_(True) for n, v in dict(ls=ls, var=var, noise=noise).items()}
+    Zr = O.T(Z).clone().requires_grad_(True)
+    kp = lambda: {'matern52_lengthscale': sp(raw['ls'])[None], 'matern52_variance': sp(raw['var'])[None]}
+    logL, post = O.sgp_log_pdf(ok, O.T(X)[None], O.T(Y)[None], Zr[None], sp(raw['noise'])[None], kp(), jitter=C.JITTER, return_posterior=True)
+    (-logL.sum()).backward()
+    assert abs(losses[0] - float(-logL.sum())) <= 1e-9 * abs(float(logL.sum()))
+    P = infr.params
+    for v, ref in ((m.noise_var, raw['noise'].grad), (kern.lengthscale, raw['ls'].grad), (kern.variance, raw['var'].grad), (m.Z, Zr.grad)):
+        o, n, _ = P._slices[v.uuid]
+        assert np.allclose(grads[0][o:o + n].cpu().numpy(), ref.numpy().ravel(), rtol=1e-7, atol=1e-9), v.name
+    gp = m.Y.factor
+    for nf in (True, False):
+        for dg in (True, False):
+            infr2 = TransferInference(ModulePredictionAlgorithm(m, observed=[m.X], target_variables=[m.Y]), infr_params=infr.params, dtype='float64')
+            gp.sgp_predict.noise_free = nf
+            gp.sgp_predict.diagonal_variance = dg
+            mu, v = infr2.run(X=t64(Xt))[0]
+            with torch.no_grad():
+                rmu, rvar = O.sgp_predict(ok, O.T(Xt)[None], O.T(Z)[None], O.T(noise)[None], post[1][None], post[2][None], post[0][None],
+                                          {k: t.detach() for k, t in kp().items()}, noise_free=nf, diagonal_variance=dg)
+            assert tuple(mu.shape) == tuple(rmu.shape) == (1, 4, D) and tuple(v.shape) == tuple(rvar.shape) == ((1, 4) if dg else (1, 4, 4))
+            assert np.allclose(mu.cpu().numpy(), rmu.numpy(), atol=1e-7) and np.allclose(v.cpu().numpy(), rvar.numpy(), atol=1e-7), (nf, dg)
