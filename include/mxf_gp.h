@@ -204,6 +204,38 @@ int mxf_gram_diff_bwd(mxf_handle h, int kind, int dtype, int S, int64_t N, int64
                       const void* dK, int64_t lddk, int64_t strideS_dK,
                       void* dX, void* dX2, void* dp0, void* dp1, void* dp2, void* stream);
 
+/* Gram build of the intrinsic coregionalisation model (multi-output GPs) in ONE pass and ONE write:
+ *   K[s, i, j] = k_kind(x_i, x2_j) * B[s|0, idx[i], idx2[j]]
+ * kind is MXF_K_RBF or MXF_K_MATERN12 / 32 / 52 with X, X2 (NULL: the square Gram), lengthscale, ard, variance, diag_add, jitter, K_out / ldk
+ * / strideS_K as mxf_gram (K_out is overwritten; the distance is formed from the coordinate differences first, scaled after, as mxf_gram2).
+ *   idx (N), idx2 (N2) : int32 output index of each row of X / X2, shared by the samples; idx2 is ignored on the square Gram (idx serves both
+ *                        sides).  An index outside [0, T) is clamped into the range before it addresses B: a wrong value, never a read
+ *                        outside B.  Validating the indices is the caller's business.
+ *   B : (S|1, T, T) in the call's dtype, packed rows; strideS_B is 0 (shared) or T * T.  B need not be symmetric.
+ * A sample stride of lengthscale is 0 or its row (Q with ard, else 1), of variance 0 or 1.  Limits: Q <= 16, T <= MXF_ICM_MAX_T.  Status: -2
+ * for a non-stationary kind, a bad dtype, an extent < 1, a null operand, a negative stride, ldk < N2 or a parameter stride that is neither;
+ * -3 above a limit (checked before the pointers); no buffer is touched then.                                                               */
+#define MXF_ICM_MAX_T 32
+int mxf_gram_icm(mxf_handle h, int kind, int dtype, int S, int64_t N, int64_t N2, int Q, int T,
+                 const void* X, int64_t strideS_X, const void* X2, int64_t strideS_X2, const int32_t* idx, const int32_t* idx2,
+                 const void* lengthscale, int ard, int64_t strideS_ls, const void* variance, int64_t strideS_var,
+                 const void* B, int64_t strideS_B, const void* diag_add, int64_t strideS_diag, double jitter,
+                 void* K_out, int64_t ldk, int64_t strideS_K, void* stream);
+
+/* Its reverse mode: given dK (S, N, N2; row stride lddk; not necessarily symmetric) it recomputes k pair by pair and ACCUMULATES INTO
+ *   dX, dX2, dls, dvar : what mxf_gram_bwd gives for the cotangent dK[i, j] * B[idx[i], idx2[j]] (dX2 is ignored when X2 == NULL: both roles
+ *                        flow into dX);
+ *   dB[s|0, a, b] += sum over the pairs with idx[i] = a and idx2[j] = b of dK[s, i, j] * k(x_i, x2_j)   (laid out as B; on the square Gram
+ *                        (a, b) and (b, a) receive their own pairs: nothing is symmetrised).
+ * A gradient whose operand is shared by the samples is the sum over them.  dB, dls and dvar are summed in double for either dtype and
+ * rounded once (float32: through scratch of the handle).  The caller zeroes the outputs; any of them may be NULL and its work is skipped.
+ * Status codes as mxf_gram_icm; -4 when the scratch cannot be had.                                                                        */
+int mxf_gram_icm_bwd(mxf_handle h, int kind, int dtype, int S, int64_t N, int64_t N2, int Q, int T,
+                     const void* X, int64_t strideS_X, const void* X2, int64_t strideS_X2, const int32_t* idx, const int32_t* idx2,
+                     const void* lengthscale, int ard, int64_t strideS_ls, const void* variance, int64_t strideS_var,
+                     const void* B, int64_t strideS_B, const void* dK, int64_t lddk, int64_t strideS_dK,
+                     void* dX, void* dX2, void* dls, void* dvar, void* dB, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Dense building blocks (MXNet linalg.* call sites).  All batched over S with strides.  */
 

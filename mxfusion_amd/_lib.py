@@ -12,6 +12,7 @@ K_RBF, K_MATERN12, K_MATERN32, K_MATERN52, K_LINEAR, K_BIAS, K_WHITE = range(7)
 WRITE, ACC_ADD, ACC_MUL = 0, 1, 2
 KD_PERIODIC, KD_RQ, KD_SM = range(3)      # MXF_KD_*: the difference-form covariances (mxf_gram_diff)
 GD_MAX_Q, GD_SM_MAX_Q, GD_SM_MAX_A = 16, 8, 8   # MXF_GD_MAX_Q, MXF_GD_SM_MAX_Q, MXF_GD_SM_MAX_A
+ICM_MAX_T = 32             # MXF_ICM_MAX_T: outputs of the fused coregionalisation Gram pass (mxf_gram_icm)
 D_GAMMA, D_GAMMA_MV, D_BETA, D_LAPLACE, D_UNIFORM, D_BERNOULLI, D_NORMAL_PREC = range(7)
 TR_SOFTPLUS, TR_LOGISTIC = range(2)
 LIK_BERNOULLI_LOGIT, LIK_BERNOULLI_PROBIT, LIK_POISSON_EXP = range(3)
@@ -49,6 +50,10 @@ SIGNATURES = {
                       _vp, _i64, _i64, _vp],
     'mxf_gram_diff_bwd': [_i, _i, _i, _i64, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i, _vp, _i64, _i64,
                           _vp, _vp, _vp, _vp, _vp, _vp],
+    'mxf_gram_icm': [_i, _i, _i, _i64, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _d,
+                     _vp, _i64, _i64, _vp],
+    'mxf_gram_icm_bwd': [_i, _i, _i, _i64, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64,
+                         _vp, _vp, _vp, _vp, _vp, _vp],
     'mxf_gemm': [_i, _i, _i, _i64, _i64, _i64, _d, _vp, _i64, _i64, _vp, _i64, _i64, _d, _vp, _i64, _i64, _i, _vp],
     'mxf_potrf': [_i, _i, _i64, _vp, _i64, _i64, _vp, _vp],
     'mxf_trsm': [_i, _i, _i, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp],

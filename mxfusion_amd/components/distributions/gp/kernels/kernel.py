@@ -109,6 +109,33 @@ class _Gram2Fn(torch.autograd.Function):
         return (None, out[0], out[1]) + tuple(grads)
 
 
+# Whether a `stationary * Coregionalize` product takes the fused HIP pass (mxf_gram_icm / mxf_gram_icm_bwd), per dtype.  Off: MultiplyKernel
+# does not take the branch and the product runs as it did before the branch existed -- one Gram per sub-kernel (mxf_gram and the torch
+# gather), their product, and torch autograd through them.  The defaults follow the measurement in DESIGN.md section 18
+# (tests/probes/gram_icm_time.py): fused where both passes are faster than that path by more than its run-to-run spread.
+FUSED_ICM = {torch.float32: True, torch.float64: True}
+
+
+class _GramICMFn(torch.autograd.Function):
+    """K = k(X, X2) * B[idx][:, idx2] for a stationary k in one fused pass (mxf_gram_icm) and its reverse mode in one (mxf_gram_icm_bwd):
+    dB comes back as a (S|1, T, T) gradient and W, kappa get theirs from B = W W^T + diag(kappa) in torch autograd."""
+
+    @staticmethod
+    def forward(ctx, kind, ard, X, X2, idx, idx2, ls, var, B):
+        ctx.kind, ctx.ard = kind, ard
+        ctx.save_for_backward(X, X2, idx, idx2, ls, var, B)
+        return ops.gram_icm(kind, X, X2, idx, idx2, ls, var, ard, B)
+
+    @staticmethod
+    def backward(ctx, dK):
+        X, X2, idx, idx2, ls, var, B = ctx.saved_tensors
+        need = [n for n, k in (('X', 2), ('ls', 6), ('var', 7), ('B', 8)) if ctx.needs_input_grad[k]]
+        if X2 is not None and ctx.needs_input_grad[3]:
+            need.append('X2')
+        dX, dX2, dls, dvar, dB = ops.gram_icm_bwd(ctx.kind, X, X2, idx, idx2, ls, var, ctx.ard, B, dK, need=need)
+        return None, None, dX, dX2, None, None, dls, dvar, dB
+
+
 def rename_duplicate_names(names):
     """util/util.py:65-100: [(index, new name)] for every repeated name -- the repeat gets the first free `<prefix><count>` (a trailing
     integer of the name counts as its counter): ['a', 'b', 'a', 'a'] -> [(2, 'a0'), (3, 'a1')]."""
@@ -341,12 +368,41 @@ class MultiplyKernel(CombinationKernel):
     def _compute_K(self, F, X, X2=None, **params):
         """multiply_kernel.py:44-67."""
         K = self._fused_pair(X, X2, params, ops.ACC_MUL)
+        if K is None:
+            K = self._fused_icm(X, X2, params)
         if K is not None:
             return K
         K = self.sub_kernels[0].K(F, X, X2, **params)
         for k in self.sub_kernels[1:]:
             K = K * k.K(F, X, X2, **params)
         return K
+
+    def _fused_icm(self, X, X2, params):
+        """A stationary sub-kernel times a Coregionalize sub-kernel on disjoint columns (the intrinsic coregionalisation model), in either
+        order: ONE Gram pass that multiplies by B[idx[i], idx2[j]] in its epilogue (mxf_gram_icm) instead of a Gram, a gathered B and their
+        product.  None when the product does not qualify (it then takes the generic path above)."""
+        from .coregionalize import Coregionalize
+        ks = self.sub_kernels
+        if len(ks) != 2 or not X.is_cuda:
+            return None
+        kc, kst = (ks[0], ks[1]) if isinstance(ks[0], Coregionalize) else (ks[1], ks[0])
+        if not isinstance(kc, Coregionalize) or getattr(kst, '_kind', None) is None or not hasattr(kst, 'ARD'):
+            return None
+        if not FUSED_ICM.get(X.dtype) or kc.num_outputs > ops._lib.ICM_MAX_T:
+            return None
+        if kc.active_dims is None or set(kc.active_dims) & set(range(X.shape[-1]) if kst.active_dims is None else kst.active_dims):
+            return None
+        Xs, X2s = kst._slice(X), kst._slice(X2)
+        N2 = Xs.shape[-2] if X2s is None else X2s.shape[-2]
+        if Xs.shape[-1] > 16 or Xs.shape[-2] > 64 * 65535 or Xs.shape[-2] == 0 or N2 == 0:      # (65 535 bands of 64 rows in one launch)
+            return None
+        pc, ps = kc._strip(params), kst._strip(params)
+        if ops.num_samples(Xs, X2s, ps['lengthscale'], ps['variance'], pc['kappa'], pc.get('W')) > 65535:      # (the grid's sample axis)
+            return None
+        B = kc.coregionalization_matrix(pc['kappa'], pc.get('W'))
+        idx = kc.output_index(kc._slice(X))
+        idx2 = None if X2 is None else kc.output_index(kc._slice(X2))
+        return _GramICMFn.apply(kst._kind, bool(kst.ARD), Xs, X2s, idx, idx2, ps['lengthscale'], ps['variance'], B.contiguous())
 
     def _compute_Kdiag(self, F, X, **params):
         K = self.sub_kernels[0].Kdiag(F, X, **params)

@@ -368,6 +368,75 @@ def gram_diff_bwd(kind, X, X2, p0, p1, p2, ard, dK, need=('X', 'X2', 'p0', 'p1',
     return dX, dX2, dp0, dp1, dp2
 
 
+def _icm_operands(what, kind, ard, X, X2, idx, idx2, ls, var, B, *others):
+    """(kind code, operands, T) of the fused coregionalisation pass: X (S|1, N, Q), X2 (S|1, N2, Q) or None, idx (N,) and idx2 (N2,) int32
+    (idx2 None on the square Gram), lengthscale (S|1, Q|1), variance (S|1, 1), B (S|1, T, T).  The limits (Q <= 16, T <= ICM_MAX_T) are
+    the entry point's to refuse."""
+    _same_kind(what, X, X2, ls, var, B, *others)
+    kd = KIND[kind] if isinstance(kind, str) else kind
+    N2 = X.shape[-2] if X2 is None else X2.shape[-2]
+    if B.dim() != 3 or B.shape[-1] != B.shape[-2]:
+        raise ValueError('%s: B must be (S|1, T, T); got %s' % (what, tuple(B.shape)))
+    want = (X.shape[-1] if ard else 1, 1)
+    if (ls.shape[-1], var.shape[-1]) != want:
+        raise ValueError('%s: lengthscale and variance of extents %s (ard = %s, Q = %d); got %s, %s'
+                         % (what, want, bool(ard), X.shape[-1], tuple(ls.shape), tuple(var.shape)))
+    for name, t, n in (('idx', idx, X.shape[-2]), ('idx2', idx2, N2)):
+        if t is None and (name == 'idx' or X2 is not None):
+            raise ValueError('%s: %s is missing' % (what, name))
+        if t is not None and (t.dtype != torch.int32 or t.device != X.device or tuple(t.shape) != (n,)):
+            raise TypeError('%s: %s must be an int32 tensor of shape (%d,) on %s; got %s %s on %s' % (what, name, n, X.device, t.dtype, tuple(t.shape), t.device))
+    return kd, [_c(t) for t in (X, X2, idx, None if X2 is None else idx2, ls, var, B)], B.shape[-1]
+
+
+def _rows_fit(t):
+    """a matrix operand the kernels read with a row stride: unit column stride, rows that do not overlap"""
+    return t.dim() == 3 and t.stride(-1) == 1 and t.stride(-2) >= t.shape[-1]
+
+
+def gram_icm(kind, X, X2, idx, idx2, ls, var, ard, B, diag_add=None, jitter=0.0, out=None):
+    """K[s, i, j] = k(x_i, x2_j) B[s|0, idx[i], idx2[j]] (S, N, N2) in one pass (mxf_gram_icm): a stationary `kind` times a
+    coregionalisation matrix, operands as _icm_operands lists them; diag_add (S|1, 1) and jitter go on the diagonal of a square Gram (X2
+    None).  `out` may be a view with a row stride above N2."""
+    kd, (X, X2, idx, idx2, ls, var, B), T = _icm_operands('gram_icm', kind, ard, X, X2, idx, idx2, ls, var, B, diag_add, out)
+    diag_add = _c(diag_add)
+    S = num_samples(X, X2, ls, var, B, diag_add)
+    N, Q = X.shape[-2], X.shape[-1]
+    N2 = N if X2 is None else X2.shape[-2]
+    if out is None:
+        out = torch.empty((S, N, N2), dtype=X.dtype, device=X.device)
+    elif tuple(out.shape) != (S, N, N2) or not _rows_fit(out):
+        raise ValueError('gram_icm: out must be (%d, %d, %d) with a unit column stride; got %s, strides %s' % (S, N, N2, tuple(out.shape), out.stride()))
+    if N == 0 or N2 == 0:
+        return out
+    _lib.call('mxf_gram_icm', _h(X), kd, _dt(X), S, N, N2, Q, T, _p(X), _ss(X), _p(X2), _ss(X2), _p(idx), _p(idx2),
+              _p(ls), int(bool(ard)), _ss(ls), _p(var), _ss(var), _p(B), _ss(B), _p(diag_add), _ss(diag_add), float(jitter),
+              _p(out), out.stride(-2), out.stride(0), _stream())
+    return out
+
+
+def gram_icm_bwd(kind, X, X2, idx, idx2, ls, var, ard, B, dK, need=('X', 'X2', 'ls', 'var', 'B')):
+    """Reverse mode of gram_icm(); returns (dX, dX2, dls, dvar, dB) shaped like their primals (summed over S for broadcast operands), None
+    for what `need` leaves out.  dK (S, N, N2) may have a row stride above N2."""
+    kd, (X, X2, idx, idx2, ls, var, B), T = _icm_operands('gram_icm_bwd', kind, ard, X, X2, idx, idx2, ls, var, B, dK)
+    if not _rows_fit(dK):
+        dK = dK.contiguous()
+    S = dK.shape[0]
+    N, Q = X.shape[-2], X.shape[-1]
+    N2 = N if X2 is None else X2.shape[-2]
+    if tuple(dK.shape) != (S, N, N2) or S < num_samples(X, X2, ls, var, B):
+        raise ValueError('gram_icm_bwd: dK must be (S, %d, %d) with S the operands\' sample count; got %s' % (N, N2, tuple(dK.shape)))
+    dX = torch.zeros_like(X) if 'X' in need else None
+    dX2 = torch.zeros_like(X2) if (X2 is not None and 'X2' in need) else None
+    dls, dvar, dB = [torch.zeros_like(t) if n in need else None for n, t in (('ls', ls), ('var', var), ('B', B))]
+    if N == 0 or N2 == 0:
+        return dX, dX2, dls, dvar, dB
+    _lib.call('mxf_gram_icm_bwd', _h(X), kd, _dt(X), S, N, N2, Q, T, _p(X), _ss(X), _p(X2), _ss(X2), _p(idx), _p(idx2),
+              _p(ls), int(bool(ard)), _ss(ls), _p(var), _ss(var), _p(B), _ss(B), _p(dK), dK.stride(-2), dK.stride(0),
+              _p(dX), _p(dX2), _p(dls), _p(dvar), _p(dB), _stream())
+    return dX, dX2, dls, dvar, dB
+
+
 def potrf_(A, info=None):
     """in-place batched lower Cholesky of A (S,n,n); returns (A, info) with info an int32 device tensor."""
     S, n = A.shape[0], A.shape[-1]
