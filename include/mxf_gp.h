@@ -172,6 +172,35 @@ int mxf_gram_bwd(mxf_handle h, int kind, int dtype, int S, int64_t N, int64_t N2
                  const void* dK, int64_t lddk, int64_t strideS_dK,
                  void* dX, void* dX2, void* dls, void* dvar, void* stream);
 
+/* The stationary Gram build and its reverse mode for WIDE inputs, MXF_GW_MIN_Q <= Q <= MXF_GW_MAX_Q (regression tables, feature layers,
+ * pixels): tiled passes that move the coordinates through LDS a chunk at a time where every other Gram kernel keeps a point's Q <= 16
+ * coordinates in registers.  kind is MXF_K_RBF or MXF_K_MATERN12 / 32 / 52; the arguments mirror mxf_gram and mxf_gram_bwd one for one:
+ * the sample axis with one stride per operand (0: shared), X2 == NULL for the square Gram, diag_add / jitter on its diagonal, K_out / ldk /
+ * strideS_K; mode must be MXF_WRITE.  The distance is formed from the coordinate differences first and scaled after, so coincident rows
+ * give r^2 = 0 exactly.  The reverse mode ACCUMULATES INTO dX, dX2 (ignored when X2 == NULL: both roles flow into dX), dls, dvar, any of
+ * which may be NULL; a shared operand's gradient is summed over the samples, a non-ard length-scale's over the dimensions.
+ * Status: -3, before any buffer is touched, for Q < MXF_GW_MIN_Q, Q > MXF_GW_MAX_Q, a kind that is not stationary or a grid that does not
+ * fit (more than 65535 x 64 rows, or 65535 samples); -2 for a bad dtype or mode, an extent < 1, a null X / lengthscale / variance / K_out /
+ * dK, a negative stride or ldk < N2.
+ * mxf_gram_wide_configure: the handle's switch for `dtype`.  Where it is on, every stationary mxf_gram (mode MXF_WRITE) and mxf_gram_bwd
+ * with Q >= MXF_GW_MIN_Q, and every composite and predictor that builds its Grams through them, runs on these passes; where it is off
+ * they run on the one-pair-per-thread kernels.  DESIGN.md 19 has the measurements behind the defaults.                                  */
+#define MXF_GW_MIN_Q 17
+#define MXF_GW_MAX_Q 16384
+int mxf_gram_wide_configure(mxf_handle h, int dtype, int on);
+int mxf_gram_wide(mxf_handle h, int kind, int dtype, int S, int64_t N, int64_t N2, int Q,
+                  const void* X, int64_t strideS_X, const void* X2, int64_t strideS_X2,
+                  const void* lengthscale, int ard, int64_t strideS_ls,
+                  const void* variance, int64_t strideS_var,
+                  const void* diag_add, int64_t strideS_diag, double jitter, int mode,
+                  void* K_out, int64_t ldk, int64_t strideS_K, void* stream);
+int mxf_gram_wide_bwd(mxf_handle h, int kind, int dtype, int S, int64_t N, int64_t N2, int Q,
+                      const void* X, int64_t strideS_X, const void* X2, int64_t strideS_X2,
+                      const void* lengthscale, int ard, int64_t strideS_ls,
+                      const void* variance, int64_t strideS_var,
+                      const void* dK, int64_t lddk, int64_t strideS_dK,
+                      void* dX, void* dX2, void* dls, void* dvar, void* stream);
+
 /* Gram build of the covariances that are NOT a function of one scaled distance: they work on the per-dimension differences
  * tau_d = x_d - x2_d, formed from the raw coordinates first (coincident rows give tau = 0 and an exact diagonal).  The reference has none
  * of them; the conventions are GPflow's / scikit-learn's (RQ) and Wilson & Adams 2013 (SpectralMixture).  Each kind takes three parameter

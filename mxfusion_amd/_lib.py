@@ -13,6 +13,7 @@ WRITE, ACC_ADD, ACC_MUL = 0, 1, 2
 KD_PERIODIC, KD_RQ, KD_SM = range(3)      # MXF_KD_*: the difference-form covariances (mxf_gram_diff)
 GD_MAX_Q, GD_SM_MAX_Q, GD_SM_MAX_A = 16, 8, 8   # MXF_GD_MAX_Q, MXF_GD_SM_MAX_Q, MXF_GD_SM_MAX_A
 ICM_MAX_T = 32             # MXF_ICM_MAX_T: outputs of the fused coregionalisation Gram pass (mxf_gram_icm)
+GW_MIN_Q, GW_MAX_Q = 17, 16384   # MXF_GW_MIN_Q, MXF_GW_MAX_Q: input dimensions of the wide Gram passes (mxf_gram_wide)
 D_GAMMA, D_GAMMA_MV, D_BETA, D_LAPLACE, D_UNIFORM, D_BERNOULLI, D_NORMAL_PREC = range(7)
 TR_SOFTPLUS, TR_LOGISTIC = range(2)
 LIK_BERNOULLI_LOGIT, LIK_BERNOULLI_PROBIT, LIK_POISSON_EXP = range(3)
@@ -46,6 +47,11 @@ SIGNATURES = {
                   _vp, _i64, _i64, _vp],
     'mxf_gram_bwd': [_i, _i, _i, _i64, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i, _i64, _vp, _i64, _vp, _i64, _i64,
                      _vp, _vp, _vp, _vp, _vp],
+    'mxf_gram_wide_configure': [_i, _i],
+    'mxf_gram_wide': [_i, _i, _i, _i64, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i, _i64, _vp, _i64, _vp, _i64, _d, _i,
+                      _vp, _i64, _i64, _vp],
+    'mxf_gram_wide_bwd': [_i, _i, _i, _i64, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i, _i64, _vp, _i64, _vp, _i64, _i64,
+                          _vp, _vp, _vp, _vp, _vp],
     'mxf_gram_diff': [_i, _i, _i, _i64, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i, _vp, _i64, _d,
                       _vp, _i64, _i64, _vp],
     'mxf_gram_diff_bwd': [_i, _i, _i, _i64, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i, _vp, _i64, _i64,
@@ -210,7 +216,21 @@ def handle(device_index):
                            'fallback.' % (device_index, rc))
         h = out
         _handles[key] = h
+        for dtype, on in gram_wide.items():
+            call('mxf_gram_wide_configure', h, dtype, int(on))
     return h
+
+
+# dtype code -> whether stationary Gram calls with Q >= GW_MIN_Q run on the tiled wide passes (mxf_gram_wide_configure): what every new handle
+# is given; ops.WIDE_GRAM is the public face
+gram_wide = {F32: True, F64: True}
+
+
+def gram_wide_configure(dtype, on):
+    """The switch of `dtype` (F32 / F64) for every handle there is and every handle to come."""
+    gram_wide[int(dtype)] = bool(on)
+    for h in list(_handles.values()):
+        call('mxf_gram_wide_configure', h, int(dtype), int(bool(on)))
 
 
 def workspace_generation(device_index):

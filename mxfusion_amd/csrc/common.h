@@ -100,6 +100,7 @@ struct mxf_ctx {
     double* cond_host = nullptr; // pinned, device-visible host words, MXF_COND_SLOTS x [running MAX, last] of the condition numbers the training calls published into their slot (mxf_svgp_cond_nowait / mxf_svgp_cond_slot)
     int svgp_form = 0;         // float32 streaming form of the next SVGP training calls (mxf_svgp_configure): 0 explicit inverse, 1 whitened
     int cond_slot = 0;         // the slot the next SVGP training calls publish their condition number into
+    bool gram_wide[2] = {true, true};      // [float32, float64]: stationary Gram calls with Q > 16 run on gram_wide.hip (mxf_gram_wide_configure)
     void* comm = nullptr;      // RCCL communicator of mxf_comm_init (comm.hip); nullptr on single-GPU handles
     int comm_nranks = 0, comm_rank = -1;
     mxf_ring flags;            // arrival counters for in-kernel workgroup hand-offs (potrf panel); each use leaves 0 behind

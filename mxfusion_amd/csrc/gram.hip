@@ -621,6 +621,11 @@ int mxf_gram_internal(mxf_ctx* h, hipStream_t st, const MxfGram& d) {
     if (d.kind != MXF_K_LINEAR && !d.var) MXF_FAIL(h, -2, "mxf_gram: null variance");
     if (d.K.ld < n2) MXF_FAIL(h, -2, "mxf_gram: ldk < N2");
     if (d.S > 65535) MXF_FAIL(h, -3, "mxf_gram: S too large");
+    if (d.Q > 16) {      // wide inputs: the tiled pass of gram_wide.hip where the handle's switch is on
+        bool taken = false;
+        const int rc = mxf_gram_wide_route(h, st, d, &taken);
+        if (taken) return rc;
+    }
     if (d.dtype == MXF_F32) return gram_typed<float>(h, st, d);
     if (d.dtype == MXF_F64) return gram_typed<double>(h, st, d);
     MXF_FAIL(h, -2, "mxf_gram: bad dtype %d", d.dtype);

@@ -429,6 +429,11 @@ int fused_typed(mxf_ctx* h, hipStream_t st, const MxfSvgpBwd& d) {
 
 int mxf_gram_bwd_internal(mxf_ctx* h, hipStream_t st, const MxfGramBwd& d) {
     if (d.S <= 0 || d.N <= 0 || (d.X2 && d.N2 <= 0)) return 0;
+    if (d.Q > 16) {      // wide inputs: the tiled pass of gram_wide.hip where the handle's switch is on
+        bool taken = false;
+        const int rc = mxf_gram_wide_bwd_route(h, st, d, &taken);
+        if (taken) return rc;
+    }
     if (d.dtype == MXF_F32) return bwd_typed<float>(h, st, d);
     if (d.dtype == MXF_F64) return bwd_typed<double>(h, st, d);
     MXF_FAIL(h, -2, "mxf_gram_bwd: bad dtype %d", d.dtype);

@@ -68,6 +68,10 @@ struct MxfGramBwd {
     bool dk_symmetric = false;      // square case only: the caller vouches that dK is symmetric -- the row-side sums are skipped and the column side counts twice
 };
 int mxf_gram_bwd_internal(mxf_ctx* h, hipStream_t st, const MxfGramBwd& d);
+// gram_wide.hip: the tiled passes for Q > 16.  *taken: the handle's switch is on and the call is theirs (it has been launched, the status
+// is the return value); otherwise nothing has happened and the caller runs what it always ran.
+int mxf_gram_wide_route(mxf_ctx* h, hipStream_t st, const MxfGram& d, bool* taken);
+int mxf_gram_wide_bwd_route(mxf_ctx* h, hipStream_t st, const MxfGramBwd& d, bool* taken);
 
 // SVGP-fused reverse pass over Text = [H0; w^T] Kuf_all (rows 0..M-1: T, rows M..M+P-1: U), which never materialises dKuf.  dXall is WRITTEN
 // (not accumulated); dZ, dls, dvar, R, scal are accumulated into (the caller zeroes them); dY is written or (dY_shared) accumulated.

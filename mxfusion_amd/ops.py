@@ -311,6 +311,56 @@ def gram_bwd(kind, X, X2, lengthscale, variance, ard, dK, need=('X', 'X2', 'ls',
     return dX, dX2, dls, dvar
 
 
+class _WideGramSwitch(dict):
+    """dtype -> bool; setting an entry pushes it to the library handles (mxf_gram_wide_configure)"""
+
+    def __setitem__(self, dtype, on):
+        _lib.gram_wide_configure(F64 if dtype == torch.float64 else F32, on)
+        dict.__setitem__(self, dtype, bool(on))
+
+
+# Whether gram / gram_bwd and everything built on them (Kernel.K, the GP, SVGP and sparse-GP composites, the predictors) run stationary
+# kernels with more than 16 input dimensions on the tiled wide passes (gram_wide) or on the one-pair-per-thread kernels.  The defaults are
+# the measured ones (DESIGN.md 19).
+WIDE_GRAM = _WideGramSwitch({torch.float32: _lib.gram_wide[F32], torch.float64: _lib.gram_wide[F64]})
+
+
+def gram_wide(kind, X, X2, lengthscale, variance, ard, diag_add=None, jitter=0.0, out=None):
+    """gram() for the stationary kinds at GW_MIN_Q <= Q <= GW_MAX_Q input dimensions on the tiled pass (mxf_gram_wide), whatever WIDE_GRAM
+    says.  Shapes as gram(); the output is overwritten."""
+    X, X2, lengthscale, variance, diag_add = _c(X), _c(X2), _c(lengthscale), _c(variance), _c(diag_add)
+    _same_kind('gram_wide', X, X2, lengthscale, variance, diag_add, out)
+    S = num_samples(X, X2, lengthscale, variance, diag_add)
+    N, Q = X.shape[-2], X.shape[-1]
+    N2 = N if X2 is None else X2.shape[-2]
+    if out is None:
+        out = torch.empty((S, N, N2), dtype=X.dtype, device=X.device)
+    _lib.call('mxf_gram_wide', _h(X), KIND[kind] if isinstance(kind, str) else kind, _dt(X), S, N, N2, Q,
+              _p(X), _ss(X), _p(X2), _ss(X2), _p(lengthscale), int(bool(ard)), _ss(lengthscale),
+              _p(variance), _ss(variance), _p(diag_add), _ss(diag_add), float(jitter), WRITE,
+              _p(out), out.stride(-2), out.stride(0) if out.dim() == 3 else 0, _stream())
+    return out
+
+
+def gram_wide_bwd(kind, X, X2, lengthscale, variance, ard, dK, need=('X', 'X2', 'ls', 'var'), into=None):
+    """Reverse mode of gram_wide() (mxf_gram_wide_bwd); returns (dX, dX2, dls, dvar) as gram_bwd() does.  into: optional (dX, dX2, dls, dvar)
+    buffers shaped like the primals, which the named gradients are ACCUMULATED into instead of fresh zeros (None: a fresh one)."""
+    X, X2, lengthscale, variance, dK = _c(X), _c(X2), _c(lengthscale), _c(variance), _c(dK)
+    _same_kind('gram_wide_bwd', X, X2, lengthscale, variance, dK)
+    S = dK.shape[0]
+    N, Q = X.shape[-2], X.shape[-1]
+    N2 = N if X2 is None else X2.shape[-2]
+    into = into or (None,) * 4
+    prim = (('X', X), ('X2', X2), ('ls', lengthscale), ('var', variance))
+    _same_kind('gram_wide_bwd', X, *into, contiguous=True)
+    _check_buffers('gram_wide_bwd', *[(b, p.shape) for b, (_, p) in zip(into, prim) if p is not None])
+    dX, dX2, dls, dvar = [None if p is None or n not in need else (torch.zeros_like(p) if b is None else b) for b, (n, p) in zip(into, prim)]
+    _lib.call('mxf_gram_wide_bwd', _h(X), KIND[kind] if isinstance(kind, str) else kind, _dt(X), S, N, N2, Q,
+              _p(X), _ss(X), _p(X2), _ss(X2), _p(lengthscale), int(bool(ard)), _ss(lengthscale), _p(variance), _ss(variance),
+              _p(dK), dK.stride(-2), dK.stride(0), _p(dX), _p(dX2), _p(dls), _p(dvar), _stream())
+    return dX, dX2, dls, dvar
+
+
 KIND_DIFF = {'periodic': _lib.KD_PERIODIC, 'rq': _lib.KD_RQ, 'sm': _lib.KD_SM}
 
 
