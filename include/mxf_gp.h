@@ -662,6 +662,24 @@ int mxf_kmv_bwd(mxf_handle h, int kind, int dtype, int S, int64_t N, int64_t N2,
                 const void* A, int64_t strideS_A, const void* V, int64_t strideS_V, const double* w, void* dls_acc, void* dvar_acc,
                 void* stream);
 
+/* The same product and the same reverse mode for WIDE inputs, MXF_KMV_WIDE_MIN_Q <= Q <= MXF_KMV_WIDE_MAX_Q: the argument lists and the
+ * meaning of mxf_kmv and mxf_kmv_bwd, one for one.  Where those keep a row's coordinates in registers, here a workgroup owns a band of 64
+ * rows and walks tiles of 64 columns whose coordinates pass through LDS a chunk at a time (the tiling of mxf_gram_wide: the difference is
+ * taken first and scaled after, on the raw operands, so coincident rows give r^2 = 0 exactly); a tile's covariances live in registers and
+ * are multiplied into the columns of V at once (mxfusion_amd/csrc/kmv_wide.hip has the decomposition).  Nothing of size N x N2 is stored.
+ * Status: -3, and no buffer is touched, for Q outside the range; -2 for everything mxf_kmv answers -2 to, with its texts.
+ * Scratch from the handle: Q + J elements (times S where the lengthscale has a sample axis), and S N J doubles for the forward product of
+ * few row bands and many columns, S (Q + 1) doubles for the reverse mode.                                                                  */
+#define MXF_KMV_WIDE_MIN_Q 17
+#define MXF_KMV_WIDE_MAX_Q 16384
+int mxf_kmv_wide(mxf_handle h, int kind, int dtype, int S, int64_t N, int64_t N2, int Q, int J, const void* X, int64_t strideS_X, const void* X2,
+                 int64_t strideS_X2, const void* lengthscale, int64_t strideS_ls, int ard, const void* variance, int64_t strideS_var,
+                 const void* diag_add, int64_t strideS_da, const void* V, int64_t strideS_V, void* out, void* stream);
+int mxf_kmv_wide_bwd(mxf_handle h, int kind, int dtype, int S, int64_t N, int64_t N2, int Q, int J, const void* X, int64_t strideS_X,
+                     const void* X2, int64_t strideS_X2, const void* lengthscale, int64_t strideS_ls, int ard, const void* variance,
+                     int64_t strideS_var, const void* A, int64_t strideS_A, const void* V, int64_t strideS_V, const double* w, void* dls_acc,
+                     void* dvar_acc, void* stream);
+
 /* Nearest-centre assignment and one Lloyd iteration of k-means, the primitive of initialising inducing inputs from data
  * (mxfusion_amd/util/inducing.py).  No reference counterpart: the reference draws its inducing inputs from a standard normal.
  *   idx[n] = argmin_m sum_q (X[n,q] - C[m,q])^2,   d2[n] = that minimum

@@ -21,7 +21,8 @@ LIK_MAX_NODES = 64         # MXF_LIK_MAX_NODES: quadrature nodes per call
 ROBUSTMAX_MAX_C = 32       # MXF_ROBUSTMAX_MAX_C: classes of a robust-max row
 PSI_MAX_Q = 16             # MXF_PSI_MAX_Q: input dimensions of the psi statistics
 RFF_MAX_Q = 16             # MXF_RFF_MAX_Q: input dimensions of the random Fourier features
-KMV_MAX_Q = 16             # MXF_KMV_MAX_Q: input dimensions of the matrix-free kernel product
+KMV_MAX_Q = 16             # MXF_KMV_MAX_Q: input dimensions of the matrix-free kernel product (mxf_kmv)
+KMV_WIDE_MIN_Q, KMV_WIDE_MAX_Q = 17, 16384   # MXF_KMV_WIDE_MIN_Q, MXF_KMV_WIDE_MAX_Q: the same of its tiled form (mxf_kmv_wide)
 NEAREST_MAX_Q = 16         # MXF_NEAREST_MAX_Q: input dimensions of the nearest-centre assignment
 KNN_MAX_Q = 16             # MXF_KNN_MAX_Q: input dimensions of the k-nearest-neighbour search and of the Vecchia kernels
 KNN_MAX_K = 32             # MXF_KNN_MAX_K: neighbours per row
@@ -92,6 +93,8 @@ SIGNATURES = {
     'mxf_rff_eval_bwd': [_i, _i, _i64, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
     'mxf_kmv': [_i, _i, _i, _i64, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
     'mxf_kmv_bwd': [_i, _i, _i, _i64, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _pd, _vp, _vp, _vp],
+    'mxf_kmv_wide': [_i, _i, _i, _i64, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
+    'mxf_kmv_wide_bwd': [_i, _i, _i, _i64, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _pd, _vp, _vp, _vp],
     'mxf_nearest': [_i, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp],
     'mxf_kmeans_step': [_i, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     'mxf_knn': [_i, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],

@@ -286,7 +286,7 @@ class Kernel(object):
         from mxfusion_amd.common.exceptions import ModelSpecificationError
         raise ModelSpecificationError('the matrix-free kernel product is supported for a single stationary kernel (RBF, Matern12, Matern32, '
                                       'Matern52; ARD or not) over all input dimensions, at most %d of them; got %s%s'
-                                      % (ops._lib.KMV_MAX_Q, type(self).__name__, ' with active_dims' if self.active_dims is not None else ''))
+                                      % (ops._lib.KMV_WIDE_MAX_Q, type(self).__name__, ' with active_dims' if self.active_dims is not None else ''))
 
 
 class NativeKernel(Kernel):

@@ -3,6 +3,7 @@ processes on a million data points").  No reference counterpart; the model-side 
 sign and scaling of log_pdf, usable under MAP / GradBasedInference).
 
   IterativeGPRegressionLogPdf.compute                 -> one batched CG solve of (K + noise I) [Y | Z] on mxf_kmv, one mxf_kmv_bwd
+                                                         (mxf_kmv_wide, mxf_kmv_wide_bwd above 16 input dimensions)
   IterativeGPRegressionMeanVariancePrediction.compute -> mxf_kmv for the mean, CG on chunks of test columns for the variance
 
 What is estimated.  With Khat = K + noise I, alpha = Khat^-1 Y, T probes z_i ~ N(0, P), P the pivoted-Cholesky preconditioner, U = Khat^-1 Z
@@ -122,7 +123,7 @@ class IterativeGPRegressionLogPdf(VariationalInference):
         ls, var = kern_params[kern.name + '_lengthscale'], kern_params[kern.name + '_variance']
         if self.model.F.factor.has_mean:
             Y = Y - variables[self.model.mean]
-        if X.shape[-1] > ops._lib.KMV_MAX_Q:
+        if X.shape[-1] > ops._lib.KMV_WIDE_MAX_Q:
             kern.matvec(F, X, Y)            # raises, naming the limit
         S = max(t.shape[0] for t in (X, Y, noise_var, ls, var))
         logL, alpha0 = [], None
@@ -184,7 +185,7 @@ class IterativeGPRegressionMeanVariancePrediction(SamplingAlgorithm):
 
 class IterativeGPRegression(Module):
     """GPRegression's model, evaluated matrix-free: a single stationary kernel (RBF, Matern12 / 32 / 52, ARD or not) over all input
-    dimensions, at most 16 of them; anything else is a ModelSpecificationError."""
+    dimensions, at most 16384 of them; anything else is a ModelSpecificationError."""
 
     def __init__(self, X, kernel, noise_var, mean=None, num_probes=10, precond_rank=15, cg_tol=1e-8, max_cg_iter=1000, rand_gen=None, dtype=None,
                  ctx=None):

@@ -965,9 +965,14 @@ def _kmv_operands(what, kind, X, X2, lengthscale, variance, ard, V, *buffers):
     return S, N, N2, Q, J, [kind, _dt(X), S, N, N2, Q, J] + st(X) + st(X2) + st(lengthscale) + [int(bool(ard))] + st(variance)
 
 
+def _kmv_entry(Q, bwd=False):
+    """the entry point of the kernel product at Q input dimensions: a row's coordinates in registers up to KMV_MAX_Q, tiled through LDS above"""
+    return ('mxf_kmv' if Q <= _lib.KMV_MAX_Q else 'mxf_kmv_wide') + ('_bwd' if bwd else '')
+
+
 def kernel_matvec(kind, X, X2, lengthscale, variance, ard, V, diag_add=None):
     """out (S, N, J) = K(X, X2) V (+ diag_add V for the square product, X2 None) without the N x N2 matrix: each covariance evaluated once for
-    the J columns and none of them stored (mxf_kmv).  The covariance of a pair is the one gram() writes.  diag_add (S|1, 1)."""
+    the J columns and none of them stored (mxf_kmv; mxf_kmv_wide above 16 input dimensions).  The covariance of a pair is the one gram() writes.  diag_add (S|1, 1)."""
     S, N, N2, Q, J, args = _kmv_operands('kernel product', kind, X, X2, lengthscale, variance, ard, V, diag_add)
     if diag_add is not None:
         if X2 is not None:
@@ -975,14 +980,14 @@ def kernel_matvec(kind, X, X2, lengthscale, variance, ard, V, diag_add=None):
         if diag_add.dim() != 2 or diag_add.shape[1] != 1 or diag_add.shape[0] not in (1, S):
             raise ValueError('kernel product: diag_add is (S|1, 1); got %s' % (tuple(diag_add.shape),))
     out = torch.empty((S, N, J), dtype=X.dtype, device=X.device)
-    _lib.call('mxf_kmv', _h(X), *args, _p(diag_add), 0 if diag_add is None or diag_add.shape[0] == 1 else diag_add.stride(0),
+    _lib.call(_kmv_entry(Q), _h(X), *args, _p(diag_add), 0 if diag_add is None or diag_add.shape[0] == 1 else diag_add.stride(0),
               _p(V), 0 if V.shape[0] == 1 else V.stride(0), _p(out), _stream())
     return out
 
 
 def kernel_matvec_bwd_(kind, X, X2, lengthscale, variance, ard, A, V, w=None, dls_acc=None, dvar_acc=None):
     """The gradient of sum_s sum_j w[j] A[s, :, j]^T K(X[s], X2[s]) V[s, :, j] in lengthscale and variance, ACCUMULATED into buffers shaped like
-    them, a shared sample axis at extent 1 and summed over (mxf_kmv_bwd).  A (S|1, N, J), V (S|1, N2, J), w: J numbers (None: ones).  The
+    them, a shared sample axis at extent 1 and summed over (mxf_kmv_bwd; mxf_kmv_wide_bwd above 16 input dimensions).  A (S|1, N, J), V (S|1, N2, J), w: J numbers (None: ones).  The
     N x N2 cotangent sum_j w[j] A[:, j] V[:, j]^T is never stored.  There is no reverse mode in X or X2."""
     S, N, N2, Q, J, args = _kmv_operands('kernel product', kind, X, X2, lengthscale, variance, ard, V, A, dls_acc, dvar_acc)
     if A.dim() != 3 or tuple(A.shape[1:]) != (N, J) or A.shape[0] not in (1, S):
@@ -991,7 +996,7 @@ def kernel_matvec_bwd_(kind, X, X2, lengthscale, variance, ard, A, V, w=None, dl
     w = [1.0] * J if w is None else [float(x) for x in w]
     if len(w) != J:
         raise ValueError('kernel product: %d weights for J = %d columns' % (len(w), J))
-    _lib.call('mxf_kmv_bwd', _h(X), *args, _p(A), 0 if A.shape[0] == 1 else A.stride(0), _p(V), 0 if V.shape[0] == 1 else V.stride(0),
+    _lib.call(_kmv_entry(Q, bwd=True), _h(X), *args, _p(A), 0 if A.shape[0] == 1 else A.stride(0), _p(V), 0 if V.shape[0] == 1 else V.stride(0),
               (_lib._c.c_double * J)(*w), _p(dls_acc), _p(dvar_acc), _stream())
 
 
