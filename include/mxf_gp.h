@@ -651,8 +651,14 @@ int mxf_rff_eval_bwd(mxf_handle h, int dtype, int S, int64_t N, int64_t D, int Q
  * mxf_kmv_bwd: the gradient of the weighted bilinear form  sum_s sum_j w[j] A[s,:,j]^T K(X[s], X2[s]) V[s,:,j]  in lengthscale and variance,
  *   ACCUMULATED into dls_acc and dvar_acc, shaped like lengthscale and variance, a shared sample axis at extent 1 and summed over; either may
  *   be NULL.  A (S|1, N, J); w: J doubles on the HOST, read before the call returns.  The cotangent of a pair, sum_j w[j] A[n,j] V[n2,j], is
- *   formed in registers.  There is no reverse mode in X or X2, and none is needed for V: the gradient of the product in V is mxf_kmv with X
- *   and X2 exchanged.                                                                                                                       */
+ *   formed in registers.  None is needed for V: the gradient of the product in V is mxf_kmv with X and X2 exchanged.
+ * mxf_kmv_bwd_x: the gradient of the same bilinear form in X and X2, ACCUMULATED into dX_acc and dX2_acc, shaped like X and X2, a shared
+ *   sample axis at extent 1 and summed over (in ascending order of s: the result is deterministic unless n2 is split over workgroups);
+ *   the dX / dX2 of mxf_gram_bwd for the cotangent sum_j w[j] A[:,j] V[:,j]^T, which is never stored.  Operands, limits and status codes
+ *   are mxf_kmv_bwd's.  Either output may be NULL, not both (-2).  With X2 NULL, X plays both roles, both contributions go into dX_acc,
+ *   and a non-null dX2_acc is -2.  A clipped pair of a Matern kind has no slope, as in mxf_gram_bwd: coincident rows contribute 0.
+ *   Nothing is written on an error.  Scratch from the handle: (N + N2) (Q + J) elements, and S N Q doubles where a result is summed over
+ *   workgroups or samples (mxfusion_amd/csrc/kmv_bwd_x.hip has the decomposition).                                                         */
 #define MXF_KMV_MAX_Q 16
 int mxf_kmv(mxf_handle h, int kind, int dtype, int S, int64_t N, int64_t N2, int Q, int J, const void* X, int64_t strideS_X, const void* X2,
             int64_t strideS_X2, const void* lengthscale, int64_t strideS_ls, int ard, const void* variance, int64_t strideS_var,
@@ -661,6 +667,10 @@ int mxf_kmv_bwd(mxf_handle h, int kind, int dtype, int S, int64_t N, int64_t N2,
                 int64_t strideS_X2, const void* lengthscale, int64_t strideS_ls, int ard, const void* variance, int64_t strideS_var,
                 const void* A, int64_t strideS_A, const void* V, int64_t strideS_V, const double* w, void* dls_acc, void* dvar_acc,
                 void* stream);
+int mxf_kmv_bwd_x(mxf_handle h, int kind, int dtype, int S, int64_t N, int64_t N2, int Q, int J, const void* X, int64_t strideS_X,
+                  const void* X2, int64_t strideS_X2, const void* lengthscale, int64_t strideS_ls, int ard, const void* variance,
+                  int64_t strideS_var, const void* A, int64_t strideS_A, const void* V, int64_t strideS_V, const double* w, void* dX_acc,
+                  void* dX2_acc, void* stream);
 
 /* The same product and the same reverse mode for WIDE inputs, MXF_KMV_WIDE_MIN_Q <= Q <= MXF_KMV_WIDE_MAX_Q: the argument lists and the
  * meaning of mxf_kmv and mxf_kmv_bwd, one for one.  Where those keep a row's coordinates in registers, here a workgroup owns a band of 64

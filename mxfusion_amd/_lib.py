@@ -93,6 +93,7 @@ SIGNATURES = {
     'mxf_rff_eval_bwd': [_i, _i, _i64, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
     'mxf_kmv': [_i, _i, _i, _i64, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
     'mxf_kmv_bwd': [_i, _i, _i, _i64, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _pd, _vp, _vp, _vp],
+    'mxf_kmv_bwd_x': [_i, _i, _i, _i64, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _pd, _vp, _vp, _vp],
     'mxf_kmv_wide': [_i, _i, _i, _i64, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
     'mxf_kmv_wide_bwd': [_i, _i, _i, _i64, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _pd, _vp, _vp, _vp],
     'mxf_nearest': [_i, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp],

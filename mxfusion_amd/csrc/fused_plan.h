@@ -140,6 +140,7 @@ struct KmvRequest {
     size_t esize = 4; bool bwd = false;
     int S = 0; int64_t N = 0, N2 = 0; int Q = 0, J = 0, ard = 0;      // N2 is ignored on a square product (no X2)
     int64_t ss_X = 0, ss_X2 = 0, ss_ls = 0, ss_var = 0, ss_da = 0, ss_V = 0, ss_A = 0;
+    int64_t ss_C = 0;       // of a centre that is not the second operand's first row (kmv_bwd_x_plan.h: the X2 side)
     bool has_X = false, has_X2 = false, has_ls = false, has_var = false, has_da = false, has_V = false, has_out = false, has_A = false, has_w = false,
          has_dls = false, has_dvar = false;
 };
@@ -185,7 +186,7 @@ static inline KmvPlan kmv_plan(const KmvRequest& r) {
     p.qp = mxf_qp(r.Q);
     p.jb = r.J <= KMV_JB_SMALL ? KMV_JB_SMALL : KMV_JB;
     p.npass = (int)mxf_cdiv(r.J, p.jb);
-    p.S_z = (p.ss_Z || r.ss_ls) ? r.S : 1; p.S_V = r.ss_V ? r.S : 1;
+    p.S_z = (p.ss_Z || r.ss_ls || r.ss_C) ? r.S : 1; p.S_V = r.ss_V ? r.S : 1;
     const ReduceSplit sp = reduce_split(r.S, r.N, N2, KMV_RB, KMV_CH, KMV_TARGET);
     p.ch = sp.ch; p.rows = sp.rows;
     p.grid[0] = (unsigned)mxf_cdiv(r.N, KMV_RB); p.grid[1] = (unsigned)p.rows; p.grid[2] = (unsigned)r.S;

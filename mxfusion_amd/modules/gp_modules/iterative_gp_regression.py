@@ -3,7 +3,8 @@ processes on a million data points").  No reference counterpart; the model-side 
 sign and scaling of log_pdf, usable under MAP / GradBasedInference).
 
   IterativeGPRegressionLogPdf.compute                 -> one batched CG solve of (K + noise I) [Y | Z] on mxf_kmv, one mxf_kmv_bwd
-                                                         (mxf_kmv_wide, mxf_kmv_wide_bwd above 16 input dimensions)
+                                                         (mxf_kmv_wide, mxf_kmv_wide_bwd above 16 input dimensions) and, where X
+                                                         requires a gradient, one mxf_kmv_bwd_x
   IterativeGPRegressionMeanVariancePrediction.compute -> mxf_kmv for the mean, CG on chunks of test columns for the variance
 
 What is estimated.  With Khat = K + noise I, alpha = Khat^-1 Y, T probes z_i ~ N(0, P), P the pivoted-Cholesky preconditioner, U = Khat^-1 Z
@@ -12,7 +13,8 @@ and W = P^-1 Z:
             log|Khat| (slq_logdet): consistent in the probes and the CG iterations, not unbiased at a finite number of iterations.
   gradient  1/2 sum_p alpha_p^T dKhat alpha_p - P / (2 T) sum_i u_i^T dKhat w_i: an UNBIASED estimate of the gradient of the exact log-pdf
             (E[u_i^T dKhat w_i] = tr(Khat^-1 dKhat)), up to the CG tolerance.  It is not the derivative of the value's estimate.
-The probes and the preconditioner are constants of an evaluation: nothing is differentiated through them.
+The probes and the preconditioner are constants of an evaluation: nothing is differentiated through them.  The gradient in the inputs X
+(a feature net's output, a latent input; mxf_kmv_bwd_x, at most 16 input dimensions) is the same estimate with dKhat taken in X.
 
 The draw contract.  Per evaluation and per sample of the parameters, ONE call rand_gen.sample_normal(shape=(N + r, num_probes)), r the rank
 the pivoted Cholesky reached (<= precond_rank; r = 0: P = noise I): Z = sqrt(noise) eps[:N] + L_r eps[N:].  A rand_gen that replays recorded
@@ -76,8 +78,6 @@ class _IterativeLogPdfFn(torch.autograd.Function):
     def backward(ctx, g, _):
         X, ls, var, alpha, U, W = ctx.saved_tensors
         cfg = ctx.cfg
-        if ctx.needs_input_grad[1]:
-            raise NotImplementedError('IterativeGPRegression has no reverse mode in X')
         P, T = alpha.shape[1], U.shape[1]
         w = [0.5] * P + [-0.5 * P / T] * T
         g = g.reshape(())
@@ -85,15 +85,20 @@ class _IterativeLogPdfFn(torch.autograd.Function):
         dnoise = None
         if ctx.needs_input_grad[3]:
             dnoise = (g * (0.5 * (alpha * alpha).sum() - 0.5 * P / T * (U * W).sum())).reshape(1, 1)
+        dX = torch.zeros_like(X) if ctx.needs_input_grad[1] else None
         dls = torch.zeros_like(ls) if ctx.needs_input_grad[4] else None
         dvar = torch.zeros_like(var) if ctx.needs_input_grad[5] else None
-        if dls is not None or dvar is not None:
+        if dX is not None or dls is not None or dvar is not None:
             A = torch.cat([alpha, U], dim=1).unsqueeze(0).contiguous()
             V = torch.cat([alpha, W], dim=1).unsqueeze(0).contiguous()
+        if dls is not None or dvar is not None:
             ops.kernel_matvec_bwd_(cfg.kind, X, None, ls, var, cfg.ard, A, V, w, dls, dvar)
             dls = None if dls is None else dls * g
             dvar = None if dvar is None else dvar * g
-        return None, None, dY, dnoise, dls, dvar
+        if dX is not None:          # the same bilinear form in X (at most 16 input dimensions: kernel_matvec_bwd_x_ names the limit)
+            ops.kernel_matvec_bwd_x_(cfg.kind, X, None, ls, var, cfg.ard, A, V, w, dX)
+            dX = dX * g
+        return None, dX, dY, dnoise, dls, dvar
 
 
 def _sample(t, s):

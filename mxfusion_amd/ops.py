@@ -988,21 +988,38 @@ def kernel_matvec(kind, X, X2, lengthscale, variance, ard, V, diag_add=None):
 def kernel_matvec_bwd_(kind, X, X2, lengthscale, variance, ard, A, V, w=None, dls_acc=None, dvar_acc=None):
     """The gradient of sum_s sum_j w[j] A[s, :, j]^T K(X[s], X2[s]) V[s, :, j] in lengthscale and variance, ACCUMULATED into buffers shaped like
     them, a shared sample axis at extent 1 and summed over (mxf_kmv_bwd; mxf_kmv_wide_bwd above 16 input dimensions).  A (S|1, N, J), V (S|1, N2, J), w: J numbers (None: ones).  The
-    N x N2 cotangent sum_j w[j] A[:, j] V[:, j]^T is never stored.  There is no reverse mode in X or X2."""
-    S, N, N2, Q, J, args = _kmv_operands('kernel product', kind, X, X2, lengthscale, variance, ard, V, A, dls_acc, dvar_acc)
+    N x N2 cotangent sum_j w[j] A[:, j] V[:, j]^T is never stored.  The gradient in X and X2 is kernel_matvec_bwd_x_."""
+    _kmv_bilinear(_kmv_entry(X.shape[-1], bwd=True), kind, X, X2, lengthscale, variance, ard, A, V, w, (dls_acc, lengthscale), (dvar_acc, variance))
+
+
+def _kmv_bilinear(entry, kind, X, X2, lengthscale, variance, ard, A, V, w, *outs):
+    """one reverse pass of the weighted bilinear form: outs are (buffer or None, the operand it is shaped like)"""
+    S, N, N2, Q, J, args = _kmv_operands('kernel product', kind, X, X2, lengthscale, variance, ard, V, A, *[b for b, _ in outs])
     if A.dim() != 3 or tuple(A.shape[1:]) != (N, J) or A.shape[0] not in (1, S):
         raise ValueError('kernel product: A is (S|1, %d, %d); got %s' % (N, J, tuple(A.shape)))
-    _check_buffers('kernel product', (dls_acc, lengthscale.shape), (dvar_acc, variance.shape))
+    _check_buffers('kernel product', *[(b, None if like is None else like.shape) for b, like in outs])
     w = [1.0] * J if w is None else [float(x) for x in w]
     if len(w) != J:
         raise ValueError('kernel product: %d weights for J = %d columns' % (len(w), J))
-    _lib.call(_kmv_entry(Q, bwd=True), _h(X), *args, _p(A), 0 if A.shape[0] == 1 else A.stride(0), _p(V), 0 if V.shape[0] == 1 else V.stride(0),
-              (_lib._c.c_double * J)(*w), _p(dls_acc), _p(dvar_acc), _stream())
+    _lib.call(entry, _h(X), *args, _p(A), 0 if A.shape[0] == 1 else A.stride(0), _p(V), 0 if V.shape[0] == 1 else V.stride(0),
+              (_lib._c.c_double * J)(*w), *[_p(b) for b, _ in outs], _stream())
+
+
+def kernel_matvec_bwd_x_(kind, X, X2, lengthscale, variance, ard, A, V, w=None, dX_acc=None, dX2_acc=None):
+    """The gradient of the same bilinear form in X and X2, ACCUMULATED into buffers shaped like them (mxf_kmv_bwd_x): the dX / dX2 of gram_bwd
+    for the cotangent sum_j w[j] A[:, j] V[:, j]^T, which is never stored.  Square (X2 None): both contributions go into dX_acc and dX2_acc
+    must be None.  Up to KMV_MAX_Q input dimensions."""
+    if X.shape[-1] > _lib.KMV_MAX_Q:
+        raise NotImplementedError('the matrix-free kernel product has a reverse mode in X and X2 for at most %d input dimensions; got %d'
+                                  % (_lib.KMV_MAX_Q, X.shape[-1]))
+    if X2 is None and dX2_acc is not None:
+        raise ValueError('kernel product: dX2_acc goes with an X2; the square product accumulates both contributions into dX_acc')
+    _kmv_bilinear('mxf_kmv_bwd_x', kind, X, X2, lengthscale, variance, ard, A, V, w, (dX_acc, X), (dX2_acc, X2))
 
 
 class KernelMatvec(torch.autograd.Function):
-    """kernel_matvec, differentiable in V (the product with X and X2 exchanged), lengthscale and variance (kernel_matvec_bwd_); X, X2 and
-    diag_add have no reverse mode."""
+    """kernel_matvec, differentiable in V (the product with X and X2 exchanged), lengthscale and variance (kernel_matvec_bwd_), and in X and
+    X2 up to KMV_MAX_Q input dimensions (kernel_matvec_bwd_x_); diag_add has no reverse mode."""
 
     @staticmethod
     def forward(ctx, kind, ard, X, X2, ls, var, V, diag_add):
@@ -1015,9 +1032,13 @@ class KernelMatvec(torch.autograd.Function):
     @staticmethod
     def backward(ctx, G):
         X, X2, ls, var, V, diag_add = ctx.saved_tensors
-        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3] or ctx.needs_input_grad[7]:
-            raise NotImplementedError('the matrix-free kernel product has no reverse mode in X, X2 or diag_add: detach them')
+        if ctx.needs_input_grad[7]:
+            raise NotImplementedError('the matrix-free kernel product has no reverse mode in diag_add: detach it')
         G = G.contiguous()
+        dX = torch.zeros_like(X) if ctx.needs_input_grad[2] else None
+        dX2 = torch.zeros_like(X2) if X2 is not None and ctx.needs_input_grad[3] else None
+        if dX is not None or dX2 is not None:
+            kernel_matvec_bwd_x_(ctx.kind, X, X2, ls, var, ctx.ard, G, V, None, dX, dX2)
         dls = torch.zeros_like(ls) if ctx.needs_input_grad[4] else None
         dvar = torch.zeros_like(var) if ctx.needs_input_grad[5] else None
         if dls is not None or dvar is not None:
@@ -1027,7 +1048,7 @@ class KernelMatvec(torch.autograd.Function):
             dV = kernel_matvec(ctx.kind, X if X2 is None else X2, None if X2 is None else X, ls, var, ctx.ard, G, diag_add)
             if V.shape[0] == 1 and dV.shape[0] > 1:
                 dV = dV.sum(0, keepdim=True)
-        return None, None, None, None, dls, dvar, dV, None
+        return None, None, dX, dX2, dls, dvar, dV, None
 
 
 def _nearest_operands(what, X, C):
